@@ -1,7 +1,7 @@
-"""Regenerates tests/golden/psx_vectors.json from the REFERENCE's own index
-generator (utils/src/datagen.cpp compiled unmodified into oracle/_ref by
-`make -C oracle ref`).  Runs only in the build container (needs
-/root/reference); the JSON it writes is data and travels with the repo.
+"""Regenerates tests/golden/psx_vectors.json and tests/golden/reference_generator_samples.npz
+from the REFERENCE's own index generator (utils/src/datagen.cpp compiled unmodified into
+oracle/_ref by `make -C oracle ref`).  Runs only where the reference source tree is (REF_ROOT
+of oracle/Makefile); the files it writes are data and travel with the repo.
 
     python tests/golden/make_golden.py
 """
@@ -28,6 +28,16 @@ CASES = [
     (99999, 16, 2.0, True, True, 3, "int32"),
 ]
 
+# test_oracle_golden.py::test_generator_against_reference_build: 50 samples of every case,
+# with and without shuffle / permute
+REF_BUILD_CASES = [(999, 8, 1.15, "int32"), (4095, 26, 0.0, "int64"), (99999, 64, 1.05, "int32"),
+                   (12345, 7, 2.5, "int64")]
+REF_BUILD_SAMPLES = 50
+
+
+def ref_build_key(n, hot, alpha, dt, shuffle, permute):
+    return "n%d_hot%d_alpha%g_%s_shuffle%d_permute%d" % (n, hot, alpha, dt, shuffle, permute)
+
 
 def main():
     O.build(ref=True)
@@ -49,6 +59,16 @@ def main():
         json.dump(dict(_comment="Outputs of the reference's PowerLawFeatureGenerator "
                                 "(utils/src/datagen.cpp), produced by make_golden.py.",
                        cases=out), f, indent=1)
+    print("wrote", path)
+    rec = {}
+    for n, hot, alpha, dt in REF_BUILD_CASES:
+        for shuf in (False, True):
+            for perm in (False, True):
+                rec[ref_build_key(n, hot, alpha, dt, shuf, perm)] = O.psx_samples(
+                    n, hot, alpha, REF_BUILD_SAMPLES, index=np.dtype(dt).type, shuffle=shuf, permute=perm,
+                    use_reference=True)
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "reference_generator_samples.npz")
+    np.savez_compressed(path, **rec)
     print("wrote", path)
 
 

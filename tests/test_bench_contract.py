@@ -138,3 +138,31 @@ def test_gpus_n_starts_its_own_ranks_and_fails_cleanly_without_a_gpu():
     assert "needs a GPU" in r.stderr                      # the ranks' own message reaches the caller
     assert r.stdout.strip() == ""                         # no JSON line from a failed job
     assert set(glob.glob("/dev/shm/cuembed_bench_idx_*")) == before
+
+
+def test_dump_outputs_is_float32_capped_and_the_same_sample_every_run(tmp_path):
+    """--dump-outputs: the whole output when it fits, else a fixed seeded sample of rows (the same rows in every run, so
+    that two builds can be compared output for output), float32 and at most bench.DUMP_BYTES per job."""
+    import numpy as np
+    import torch
+    import bench
+    small = torch.arange(1024 * 32, dtype=torch.float16).reshape(1024, 32)
+    bench.dump_outputs(np, small, str(tmp_path / "a"), 0, 1)
+    got = np.load(tmp_path / "a" / "forward_out.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.float().numpy())
+    big = torch.randn(65536, 256).to(torch.float16)
+    for d in ("b", "c"):
+        bench.dump_outputs(np, big, str(tmp_path / d), 0, 1)
+    b, c = np.load(tmp_path / "b" / "forward_out.npy"), np.load(tmp_path / "c" / "forward_out.npy")
+    assert b.dtype == np.float32 and b.nbytes <= bench.DUMP_BYTES and b.shape == (32768, 256) and np.array_equal(b, c)
+    rows = {bytes(r) for r in big.float().numpy()}
+    assert all(bytes(r) in rows for r in b[:64])              # sampled rows, unchanged
+    bench.dump_outputs(np, big, str(tmp_path / "d"), 1, 2)     # two ranks share the budget
+    assert np.load(tmp_path / "d" / "forward_out_rank1.npy").shape == (16384, 256)
+
+
+def test_steps_must_be_positive():
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=60)
+    assert r.returncode != 0 and "--steps" in r.stderr and r.stdout == ""

@@ -1,4 +1,4 @@
-"""`python3 bench.py --gpus 2 --steps 20 --warmup 5`, typed exactly like that with no launcher around it:
+"""`python3 bench.py --gpus 2 --steps 20 --warmup 5 [--full]`, typed exactly like that with no launcher around it:
 bench.py starts its own two rank processes (before touching the GPU), they share the box's GPU(s), rank 0's
 JSON line comes back through the parent.  This is the command a scaling run issues with N = 2, 4, 8."""
 import json
@@ -26,7 +26,7 @@ def _run(extra):
 
 def test_gpus_2_as_typed():
     import torch
-    line = _run(["--gpus", "2", "--steps", "20", "--warmup", "5"])
+    line = _run(["--gpus", "2", "--steps", "20", "--warmup", "5", "--full"])
     assert line["n_gpus"] == 2 and line["steps"] == 20 and line["warmup"] == 5
     assert line["scaling"] == "weak" and line["config"]["global_batch"] == 2 * 65536
     assert line["config"]["ranks_share_gpus"] == (torch.cuda.device_count() < 2)
@@ -50,7 +50,7 @@ def test_gpus_2_as_typed():
 
 
 def test_gpus_1_line_has_the_contract_fields():
-    line = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-c3"])
+    line = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-c3", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "value_reference_protocol",
               "pct_of_hbm_peak", "preroll_ms", "steady_state", "timing"):
@@ -117,3 +117,20 @@ def test_gpus_2_under_torch_distributed_run():
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 2 * 65536 and line["value"] > 0
     assert set(glob.glob("/dev/shm/cuembed_bench_idx_*")) == before          # the node's stream file is gone
+
+
+def test_gpus_1_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) measures the headline and nothing else; --dump-outputs writes the last timed step's
+    forward output as float32, a fixed sample of 32,768 of the 65,536 rows at C2 (256 fp16 values each)."""
+    import numpy as np
+    line = _run(["--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path)])
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["full"] is False
+    assert line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "GB/s" and line["higher_is_better"] is True
+    assert line["metric"].startswith("achieved HBM GB/s (% of peak), EmbeddingForward w=256 hot=64")
+    for k in ("steady_state", "extras", "cpu_baseline", "value_reference_protocol"):
+        assert k not in line, k
+    assert "single_launch_event_ms" not in line["roofline"] and line["roofline"]["frac"] > 0
+    assert sorted(os.listdir(tmp_path)) == ["forward_out.npy"]
+    out = np.load(tmp_path / "forward_out.npy")
+    assert out.dtype == np.float32 and out.shape == (32768, 256) and np.isfinite(out).all()
+    assert np.abs(out).max() > 0

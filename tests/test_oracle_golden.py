@@ -188,17 +188,26 @@ def test_generator_golden_vectors(oracle, golden_dir, digests):
     assert oracle.psx_samples(9999999, 64, 0.0, 1)[0][:8].tolist() == g["psx_9999999_64_0_first8"]
 
 
-def test_generator_against_reference_build(oracle):
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    for n, hot, alpha, dt in [(999, 8, 1.15, np.int32), (4095, 26, 0.0, np.int64),
-                              (99999, 64, 1.05, np.int32), (12345, 7, 2.5, np.int64)]:
+def test_generator_against_reference_build(oracle, golden_dir):
+    """The oracle's generator against the reference build's own samples, recorded by tests/golden/make_golden.py in
+    reference_generator_samples.npz; where oracle/_ref is built, the live reference build is held to the recording."""
+    rec = np.load(os.path.join(golden_dir, "reference_generator_samples.npz"))
+    live = oracle.ref_lib() is not None
+    seen = 0
+    for n, hot, alpha, dt in [(999, 8, 1.15, "int32"), (4095, 26, 0.0, "int64"),
+                              (99999, 64, 1.05, "int32"), (12345, 7, 2.5, "int64")]:
         for shuf in (False, True):
             for perm in (False, True):
-                a = oracle.psx_samples(n, hot, alpha, 50, index=dt, shuffle=shuf, permute=perm)
-                b = oracle.psx_samples(n, hot, alpha, 50, index=dt, shuffle=shuf, permute=perm,
-                                       use_reference=True)
-                assert (a == b).all()
+                want = rec["n%d_hot%d_alpha%g_%s_shuffle%d_permute%d" % (n, hot, alpha, dt, shuf, perm)]
+                assert want.dtype == np.dtype(dt) and want.shape == (50, hot)
+                a = oracle.psx_samples(n, hot, alpha, 50, index=np.dtype(dt).type, shuffle=shuf, permute=perm)
+                assert (a == want).all()
+                if live:
+                    b = oracle.psx_samples(n, hot, alpha, 50, index=np.dtype(dt).type, shuffle=shuf, permute=perm,
+                                           use_reference=True)
+                    assert (b == want).all()
+                seen += 1
+    assert seen == len(rec.files) == 16
 
 
 def test_generator_properties(oracle):

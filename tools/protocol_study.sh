@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 mkdir -p "$O"; : > "$O/protocol_study.jsonl"
 cd "$R"
-run() { python bench.py --no-cpu-baseline --no-c3 "$@" 2>> "$O/protocol_study.err" | tail -n 1 >> "$O/protocol_study.jsonl"; }
+run() { python bench.py --full --no-cpu-baseline --no-c3 "$@" 2>> "$O/protocol_study.err" | tail -n 1 >> "$O/protocol_study.jsonl"; }
 for i in 1 2 3 4 5; do
   run --steps 20 --warmup 5
   run --steps 200 --warmup 20

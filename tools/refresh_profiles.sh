@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/refresh
 rm -rf "$O"; mkdir -p "$O"
 cd "$R"
-timeout 900 python bench.py --steps 20 --warmup 5 > "$O/bench_c2_line.json" 2> "$O/bench.err"     # the driver's protocol
+timeout 900 python bench.py --steps 20 --warmup 5 --full > "$O/bench_c2_line.json" 2> "$O/bench.err"     # the headline protocol, every leg
 C2="--num_categories 10000000 --embed_width 256 --batch_size 65536 --alpha 1.15 --hotness 64 --half_embedding_type=true"
 C3="--num_categories 10000000 --embed_width 128 --batch_size 65536 --alpha 1.15 --hotness 128 --csr_input=true --weighted_sum=true"
 {
@@ -57,7 +57,7 @@ timeout 600 python tools/reference_sums_timing.py >> "$O/reference_sums_run_prob
 timeout 600 python tools/exchange_device_time.py 2>> "$O/torch_probe.err" | grep '^{' > "$O/exchange_device_time.json"   # (RCCL prints its banner on stdout)
 # profiler passes last (they clock lower); the program goes directly after `--`
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_bench" -- python3 "$R/bench.py" --steps 100 --warmup 10 --no-extras --no-c5 --no-cpu-baseline > "$O/prof_bench.log" 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_bench" -- python3 "$R/bench.py" --steps 100 --warmup 10 --full --no-extras --no-c5 --no-cpu-baseline > "$O/prof_bench.log" 2>&1
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_pipeline" -- "$R/benchmarks/manual_benchmark" $C2 --iterations 10 --clear_caches=false > "$O/prof_pipeline.log" 2>&1
 cd "$R"
 timeout 900 python tools/rocprof_summary.py "$O/prof_bench" > "$O/bench_c2_kernel_trace_stats.txt" 2>/dev/null
@@ -91,7 +91,7 @@ timeout 900 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d "$O/
 cd "$R"
 # C3 (fp32 weighted CSR forward): bench.py itself is the profiled program -- every GatherReduceKernel dispatch is a C3 launch
 cd /tmp
-PC="python3 $R/bench.py --workload c3 --steps 10 --warmup 0 --no-extras --no-c5 --no-cpu-baseline"
+PC="python3 $R/bench.py --workload c3 --steps 10 --warmup 0 --full --no-extras --no-c5 --no-cpu-baseline"
 timeout 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/pmc_c3_fetch" -- $PC > "$O/pmc_c3.log" 2>&1
 timeout 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$O/pmc_c3_write" -- $PC >> "$O/pmc_c3.log" 2>&1
 timeout 900 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d "$O/pmc_c3_tcc" -- $PC >> "$O/pmc_c3.log" 2>&1
@@ -117,8 +117,8 @@ timeout 1200 bash tools/pmc_sq_pass.sh > /dev/null 2>&1 && cp "$R/gpurun_out/pmc
 # the bench line again, now with roofline.traffic from the traffic file measured above
 cp "$O/traffic_c2.json" "$R/profiles/traffic_c2.json"
 cp "$O/traffic_c3.json" "$R/profiles/traffic_c3.json"
-timeout 900 python bench.py --steps 20 --warmup 5 > "$O/bench_c2_line.json" 2>> "$O/bench.err"
-timeout 900 python bench.py --steps 200 --warmup 20 > "$O/bench_c2_line_200_steps.json" 2>> "$O/bench.err"
-timeout 900 python bench.py --gpus 2 --steps 20 --warmup 5 > "$O/bench_c2_two_ranks_sharing_one_gpu.json" 2>> "$O/bench.err"
-timeout 1500 python bench.py --gpus 8 --steps 20 --warmup 5 > "$O/bench_c2_eight_ranks_sharing_one_gpu.json" 2>> "$O/bench.err"
+timeout 900 python bench.py --steps 20 --warmup 5 --full > "$O/bench_c2_line.json" 2>> "$O/bench.err"
+timeout 900 python bench.py --steps 200 --warmup 20 --full > "$O/bench_c2_line_200_steps.json" 2>> "$O/bench.err"
+timeout 900 python bench.py --gpus 2 --steps 20 --warmup 5 --full > "$O/bench_c2_two_ranks_sharing_one_gpu.json" 2>> "$O/bench.err"
+timeout 1500 python bench.py --gpus 8 --steps 20 --warmup 5 --full > "$O/bench_c2_eight_ranks_sharing_one_gpu.json" 2>> "$O/bench.err"
 ls -la "$O"

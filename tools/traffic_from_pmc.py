@@ -99,7 +99,7 @@ def main():
     res["kernel_sources_sha16"] = bench.kernel_sources_sha16()   # bench.py reports a mismatch as traffic_stale
     K = res["kernels"]
     if a.c3_fetch and a.c3_write:
-        # passes over `bench.py --workload c3 --no-extras --no-cpu-baseline`: every GatherReduceKernel dispatch
+        # passes over `bench.py --workload c3 --full --no-extras --no-cpu-baseline`: every GatherReduceKernel dispatch
         # is a C3 forward launch (two CSR batches cycled); the first launches run on cold caches: drop two
         cf = pick(read_counters(a.c3_fetch), "GatherReduceKernel", "FETCH_SIZE")
         cw = pick(read_counters(a.c3_write), "GatherReduceKernel", "WRITE_SIZE")
