@@ -20,6 +20,6 @@ from .ops import (CONCAT, MEAN, SUM, ComputeCompressedGradIndices, EmbeddingBack
                   extract_row_ids_from_fixed, forward_launch_shape, backward_launch_shape, device_shape, get_forward_reduction_order,
                   set_forward_reduction_order, set_forward_row_load_policy, get_forward_row_load_policy, set_forward_wide_load, transpose,
                   transpose_fixed_hotness,
-                  transpose_workspace_bytes)
+                  transpose_workspace_bytes, sparse_row_update, sparse_row_update_launch_shape, UPDATE_RULES)
 
 __version__ = "0.1.0"

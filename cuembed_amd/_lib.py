@@ -118,6 +118,11 @@ def _declare(L):
     L.cuembed_backward_launch_shape.argtypes = [_I, _I, _I, ctypes.c_int64, _I, _I, _I, ctypes.POINTER(_I)]
     L.cuembed_recommended_sample_blocks_on.restype = _I
     L.cuembed_recommended_sample_blocks_on.argtypes = [_I, _I, _I, ctypes.c_int64, _I, _I, ctypes.c_int64]
+    L.cuembed_sparse_row_update.restype = None
+    L.cuembed_sparse_row_update.argtypes = [_VP, _I, _I, _VP, _I, _VP, _I, _VP, _L, _I, _L, _VP, _I, _VP, ctypes.c_float,
+                                            _VP, ctypes.c_float, _VP]
+    L.cuembed_sparse_row_update_launch_shape.restype = None
+    L.cuembed_sparse_row_update_launch_shape.argtypes = [_I, _I, _L, _I, ctypes.POINTER(_I)]
     L.cuembed_peek_last_error.restype = _I
     L.cuembed_peek_last_error.argtypes = []
     L.cuembed_version.restype = ctypes.c_char_p

@@ -2,7 +2,7 @@
 
     python -m cuembed_amd.build [--force]
 
-The three translation units are compiled in parallel and linked into
+The translation units (UNITS) are compiled in parallel and linked into
 cuembed_amd/lib/libcuembed_amd.so (in-tree, so the file travels with the repo
 snapshot to the GPU box).  hipcc cross-compiles without a GPU present.
 """
@@ -20,7 +20,8 @@ LIB_DIR = os.path.join(PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libcuembed_amd.so")
 HARNESS_PATH = os.path.join(LIB_DIR, "libcuembed_harness.so")
 OBJ_DIR = os.path.join(PKG, "build")
-UNITS = ["c_api_forward.hip", "c_api_backward.hip", "c_api_transforms.hip", "c_api_exchange.hip"]
+UNITS = ["c_api_forward.hip", "c_api_backward.hip", "c_api_transforms.hip", "c_api_exchange.hip",
+         "c_api_optimizer.hip"]
 ARCH = "gfx950"
 
 HIPCC_FLAGS = [
@@ -185,6 +186,29 @@ def build_header_api_test(force=False):
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed for the header-only API test:\n" + r.stdout)
+    with open(stamp, "w") as f:
+        f.write(digest)
+    return exe
+
+
+def build_sparse_update_test(force=False):
+    """Compiles tests/cpp/sparse_update_kat.hip: cuembed::SparseRowUpdate through the header-only API against a host
+    recomputation on exactly representable data.  Needs a GPU to RUN (tests/test_gpu_cpp_sparse_update.py)."""
+    src = os.path.join(ROOT, "tests", "cpp", "sparse_update_kat.hip")
+    exe = os.path.join(ROOT, "tests", "cpp", "sparse_update_kat")
+    stamp = exe + ".stamp"
+    deps = [src]
+    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
+        deps += [os.path.join(dirpath, f) for f in files]
+    digest = _digest_files(deps)
+    if not force and os.path.exists(exe) and os.path.exists(stamp):
+        with open(stamp) as f:
+            if f.read().strip() == digest:
+                return exe
+    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-I" + CSRC, src, "-o", exe]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("hipcc failed for tests/cpp/sparse_update_kat.hip:\n" + r.stdout)
     with open(stamp, "w") as f:
         f.write(digest)
     return exe

@@ -1,0 +1,70 @@
+// C ABI: the sparse optimizer step = explicit instantiations of cuembed::SparseRowUpdate (an extension: the
+// reference ends at the gradient).
+#include "c_api_common.hpp"
+#include "cuembed/include/sparse_update.hpp"
+
+using cuembed_c_api::Stream;
+
+namespace {
+template <typename ElemT, typename IndexT>
+void Update(void* table, float* state, int embed_width, const void* ids, const void* rows,
+            const cuembed::SparseUpdateOptions& options, cuembed_stream_t stream) {
+  cuembed::SparseRowUpdate<ElemT, IndexT>(static_cast<ElemT*>(table), state, embed_width,
+                                          static_cast<const IndexT*>(ids), static_cast<const ElemT*>(rows), options,
+                                          Stream(stream));
+}
+}  // namespace
+
+extern "C" {
+
+void cuembed_sparse_row_update(void* table, int elem_type, int embed_width, float* state, int rule, const void* ids,
+                               int index_type, const void* rows, int64_t piece_rows, int pieces, int64_t num_rows,
+                               const void* counts, int counts_are_int64, const void* last_id, float lr,
+                               const float* lr_device, float eps, cuembed_stream_t stream) {
+  cuembed::SparseUpdateOptions o;
+  switch (rule) {
+    case CUEMBED_UPDATE_SGD: o.rule = cuembed::UpdateRule::kSgd; break;
+    case CUEMBED_UPDATE_ADAGRAD: o.rule = cuembed::UpdateRule::kAdagrad; break;
+    case CUEMBED_UPDATE_ROWWISE_ADAGRAD: o.rule = cuembed::UpdateRule::kRowwiseAdagrad; break;
+    default:
+      std::cerr << "Check failed: unknown update rule at " << __FILE__ << ":" << __LINE__ << std::endl;
+      std::abort();
+  }
+  o.lr = lr;
+  o.lr_device = lr_device;
+  o.eps = eps;
+  o.piece_rows = piece_rows;
+  o.pieces = pieces;
+  o.num_rows = num_rows;
+  o.counts = counts;
+  o.counts_are_int64 = counts_are_int64 != 0;
+  o.last_id = last_id;
+#define UPD(E, I) Update<E, I>(table, state, embed_width, ids, rows, o, stream)
+  switch ((elem_type << 1) | index_type) {
+    case 0: UPD(float, int32_t); break;
+    case 1: UPD(float, int64_t); break;
+    case 2: UPD(__half, int32_t); break;
+    case 3: UPD(__half, int64_t); break;
+    case 4: UPD(__hip_bfloat16, int32_t); break;
+    case 5: UPD(__hip_bfloat16, int64_t); break;
+    default: CUEMBED_C_API_BAD_TYPE();
+  }
+#undef UPD
+}
+
+void cuembed_sparse_row_update_launch_shape(int elem_type, int embed_width, int64_t total_entries, int compute_units,
+                                            int* out) {
+  cuembed::detail::DeviceShape dev =
+      compute_units > 0 ? cuembed::detail::Mi355xShape() : cuembed::detail::CurrentDeviceShape();
+  if (compute_units > 0) dev.compute_units = compute_units;
+  const int row_bytes = embed_width * (elem_type == CUEMBED_F32 ? 4 : 2);
+  const int lane_bytes = row_bytes % 16 == 0 ? 16 : (row_bytes % 8 == 0 ? 8 : 4);   // (aligned buffers)
+  const cuembed::detail::UpdateShape s = cuembed::detail::PlanUpdate(row_bytes / lane_bytes, total_entries, dev);
+  out[0] = lane_bytes;
+  out[1] = s.lanes_per_row;
+  out[2] = s.group;
+  out[3] = s.chunks;
+  out[4] = static_cast<int>(s.grid);
+}
+
+}  // extern "C"

@@ -1,0 +1,176 @@
+// MI355X (gfx950 / CDNA4) sparse optimizer step -- host API (an extension: the reference ends at the gradient).
+//
+//   cuembed::SparseRowUpdate<ElemT, IndexT>(table, state, embed_width, ids, rows, options, stream)
+//
+// consumes the compressed gradient that EmbeddingBackward (or the sparse-gradient exchange) produced -- `ids` naming
+// table rows, `rows` their gradient rows -- and updates the named rows of `table` in place.  The number of valid
+// entries may live on the device, so a step that ends in this call needs no host read-back.
+#ifndef CUEMBED_INCLUDE_SPARSE_UPDATE_HPP_
+#define CUEMBED_INCLUDE_SPARSE_UPDATE_HPP_
+
+#include <hip/hip_bf16.h>
+#include <hip/hip_fp16.h>
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <type_traits>
+
+#include "cuembed/include/cuembed_assert.hpp"
+#include "cuembed/include/device_shape.hpp"
+#include "cuembed/include/sparse_update_kernels.hpp"
+
+namespace cuembed {
+
+//! Rule, hyper-parameters and the source of the entry count of one SparseRowUpdate call.
+struct SparseUpdateOptions {
+  UpdateRule rule = UpdateRule::kSgd;
+  float lr = 0.f;                    //!< learning rate, unless ...
+  const float* lr_device = nullptr;  //!< ... one fp32 word on the device holds it (a captured graph follows a schedule)
+  float eps = 1e-8f;                 //!< Adagrad rules: added to sqrt(state)
+  //! The entries are `pieces` blocks of `piece_rows` entries; entry j of piece p is valid iff j < count(p).
+  int64_t piece_rows = 0;            //!< capacity of one piece (rows of `ids` / `rows` per piece)
+  int pieces = 1;
+  //! Exactly one source of the counts:
+  int64_t num_rows = -1;             //!< >= 0: host-known count (one piece)
+  const void* counts = nullptr;      //!< counts[pieces] on the device, int32 or ...
+  bool counts_are_int64 = false;     //!< ... int64
+  const void* last_id = nullptr;     //!< one IndexT word on the device, count = *last_id + 1 (one piece): the
+                                     //!< convention of EmbeddingBackward with num_grad_embedding_rows < 0
+};
+
+namespace detail {
+
+//! Bytes per lane: the widest of 16 / 8 / 4 that the row size, the three data pointers and (Adagrad) the state allow.
+template <typename ElemT>
+inline int UpdateLaneBytes(const int embed_width, const void* table, const void* rows, const float* state,
+                           const bool state_per_element) {
+  const size_t row_bytes = static_cast<size_t>(embed_width) * sizeof(ElemT);
+  CUEMBED_ASSERT(embed_width > 0);
+  CUEMBED_ASSERT(row_bytes % 4 == 0);
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(rows) | row_bytes;
+  CUEMBED_ASSERT(reinterpret_cast<uintptr_t>(table) % 4 == 0 && reinterpret_cast<uintptr_t>(rows) % 4 == 0);
+  int bytes = bits % 16 == 0 ? 16 : (bits % 8 == 0 ? 8 : 4);
+  if (state_per_element) {
+    // a lane's N = bytes / sizeof(ElemT) state elements move as fp32 packs of min(N, 4)
+    const auto state_align = [](int b) { const int n = b / static_cast<int>(sizeof(ElemT)); return 4 * (n < 4 ? n : 4); };
+    while (bytes > 4 && reinterpret_cast<uintptr_t>(state) % state_align(bytes) != 0) bytes /= 2;
+    CUEMBED_ASSERT(reinterpret_cast<uintptr_t>(state) % state_align(bytes) == 0);
+  }
+  return bytes;
+}
+
+//! Launch shape of one update: lanes per entry, slices per lane, grid (pure host arithmetic).
+struct UpdateShape {
+  int lanes_per_row;  //!< width / N
+  int group;          //!< lanes per entry: a power of two <= 64
+  int chunks;         //!< 1, kUpdateMaxChunks or 0 (run-time loop)
+  unsigned grid;
+};
+
+inline UpdateShape PlanUpdate(const int lanes_per_row, const int64_t total_entries, const DeviceShape& dev) {
+  UpdateShape s;
+  s.lanes_per_row = lanes_per_row;
+  s.group = 1;
+  while (s.group < lanes_per_row && s.group < 64) s.group *= 2;
+  s.chunks = lanes_per_row <= s.group ? 1 : (lanes_per_row <= kUpdateMaxChunks * s.group ? kUpdateMaxChunks : 0);
+  const int groups_per_block = kUpdateBlockThreads / s.group;
+  const int64_t needed = (total_entries + groups_per_block - 1) / groups_per_block;
+  // as many workgroups as the device holds at once (8 per CU at 256 threads); the rest is the grid stride
+  const int64_t resident = static_cast<int64_t>(dev.compute_units) * (dev.lanes_per_cu / kUpdateBlockThreads);
+  s.grid = static_cast<unsigned>(needed < resident ? (needed < 1 ? 1 : needed) : resident);
+  return s;
+}
+
+template <typename ElemT, typename IndexT, int N, UpdateRule kRule>
+inline void LaunchSparseRowUpdate(ElemT* table, float* state, const int width, const IndexT* ids, const ElemT* rows,
+                                  const SparseUpdateOptions& o, const UpdateCounts& counts, const hipStream_t stream) {
+  const UpdateShape s = PlanUpdate(width / N, o.piece_rows * o.pieces, CurrentDeviceShape());
+#define CUEMBED_LAUNCH_UPDATE(CHUNKS)                                                                          \
+  SparseRowUpdateKernel<ElemT, IndexT, N, kRule, CHUNKS><<<dim3(s.grid), dim3(kUpdateBlockThreads), 0, stream>>>( \
+      ids, rows, table, state, width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr, o.lr_device, o.eps)
+  if (s.chunks == 1) CUEMBED_LAUNCH_UPDATE(1);
+  else if (s.chunks == kUpdateMaxChunks) CUEMBED_LAUNCH_UPDATE(kUpdateMaxChunks);
+  else CUEMBED_LAUNCH_UPDATE(0);
+#undef CUEMBED_LAUNCH_UPDATE
+}
+
+template <typename ElemT, typename IndexT, int N>
+inline void LaunchSparseRowUpdateRule(ElemT* table, float* state, const int width, const IndexT* ids, const ElemT* rows,
+                                      const SparseUpdateOptions& o, const UpdateCounts& counts, const hipStream_t stream) {
+  switch (o.rule) {
+    case UpdateRule::kSgd:
+      return LaunchSparseRowUpdate<ElemT, IndexT, N, UpdateRule::kSgd>(table, state, width, ids, rows, o, counts, stream);
+    case UpdateRule::kAdagrad:
+      return LaunchSparseRowUpdate<ElemT, IndexT, N, UpdateRule::kAdagrad>(table, state, width, ids, rows, o, counts, stream);
+    case UpdateRule::kRowwiseAdagrad:
+      return LaunchSparseRowUpdate<ElemT, IndexT, N, UpdateRule::kRowwiseAdagrad>(table, state, width, ids, rows, o, counts,
+                                                                                 stream);
+  }
+  CUEMBED_ASSERT(false && "unknown update rule");
+}
+
+}  // namespace detail
+
+/**
+ * @brief Sparse optimizer step: for every valid entry k, table[ids[k], :] and the state of row ids[k] are updated in
+ * place from rows[k, :] by options.rule.  Rows that no valid entry names are neither read nor written.
+ *
+ * All arithmetic is fp32 whatever ElemT is, with exactly one rounding to ElemT at the store.
+ *
+ * The valid entries must name DISTINCT rows, i.e. the gradient must be coalesced: the output of EmbeddingBackward on a
+ * fully sorted transpose or on ComputeCompressedGradIndicesBlocked's ids, or a piece of the sparse-gradient exchange.
+ * The UNCOALESCED gradient of a sample-blocked transpose (one entry per (block, row)) is not accepted: Adagrad is not
+ * linear and two entries on one row would race.  Entries at or past the count are ignored whatever they hold, which
+ * is what makes padded buffers safe; a count above piece_rows (the backward then wrote nothing and raised its
+ * overflow word) or below zero leaves the table unchanged.
+ *
+ * @param table  [num_categories, embed_width], updated in place
+ * @param state  nullptr (kSgd), fp32 [num_categories, embed_width] (kAdagrad) or fp32 [num_categories]
+ *               (kRowwiseAdagrad), updated in place
+ * @param ids    [pieces * piece_rows] table rows (values in [0, num_categories) wherever valid)
+ * @param rows   [pieces * piece_rows, embed_width] gradient rows, of the table's type
+ *
+ * Misuse (no or more than one count source, a missing state, a row size that is not a multiple of 4 bytes) aborts
+ * with the failed condition, like EmbeddingBackward.
+ */
+template <typename ElemT, typename IndexT>
+void SparseRowUpdate(ElemT* table,
+                     float* state,
+                     const int embed_width,
+                     const IndexT* ids,
+                     const ElemT* rows,
+                     const SparseUpdateOptions& options,
+                     const hipStream_t stream = 0) {
+  static_assert(std::is_same<ElemT, float>::value || std::is_same<ElemT, __half>::value ||
+                    std::is_same<ElemT, __hip_bfloat16>::value,
+                "SparseRowUpdate: tables must be float, __half or __hip_bfloat16");
+  static_assert(std::is_same<IndexT, int32_t>::value || std::is_same<IndexT, int64_t>::value,
+                "SparseRowUpdate: ids must be int32_t or int64_t");
+  using DevT = detail::DeviceElemT<ElemT>;
+  const int sources = (options.num_rows >= 0) + (options.counts != nullptr) + (options.last_id != nullptr);
+  CUEMBED_ASSERT(sources == 1);
+  CUEMBED_ASSERT(options.pieces >= 1 && options.piece_rows >= 0);
+  CUEMBED_ASSERT(options.pieces == 1 || options.counts != nullptr);   // several pieces: counts[pieces] on the device
+  if (options.num_rows >= 0) CUEMBED_ASSERT(options.num_rows <= options.piece_rows);
+  CUEMBED_ASSERT((options.rule == UpdateRule::kSgd) == (state == nullptr));
+  if (options.piece_rows == 0 || options.num_rows == 0) return;
+  CUEMBED_ASSERT(table != nullptr && ids != nullptr && rows != nullptr);
+  const int bytes = detail::UpdateLaneBytes<DevT>(embed_width, table, rows, state, options.rule == UpdateRule::kAdagrad);
+  detail::UpdateCounts counts;
+  counts.host_count = options.num_rows >= 0 ? options.num_rows : -1;
+  counts.count_words = options.counts;
+  counts.count_words_are_64 = options.counts_are_int64 ? 1 : 0;
+  counts.last_id = options.last_id;
+  DevT* t = reinterpret_cast<DevT*>(table);
+  const DevT* g = reinterpret_cast<const DevT*>(rows);
+  constexpr int kMaxN = 16 / static_cast<int>(sizeof(DevT));
+  if (bytes == 16) detail::LaunchSparseRowUpdateRule<DevT, IndexT, kMaxN>(t, state, embed_width, ids, g, options, counts, stream);
+  else if (bytes == 8)
+    detail::LaunchSparseRowUpdateRule<DevT, IndexT, kMaxN / 2>(t, state, embed_width, ids, g, options, counts, stream);
+  else
+    detail::LaunchSparseRowUpdateRule<DevT, IndexT, kMaxN / 4>(t, state, embed_width, ids, g, options, counts, stream);
+}
+
+}  // namespace cuembed
+
+#endif  // CUEMBED_INCLUDE_SPARSE_UPDATE_HPP_

@@ -656,6 +656,78 @@ class CuEmbEmbeddingNode : public torch::autograd::Function<CuEmbEmbeddingNode> 
 // collectives was ~60 launches and more host time than the whole forward + backward step; here it is two ops that
 // enqueue 2 and ~13 launches without returning to Python.  Nothing is read back.
 
+// Extension (cuembed::SparseRowUpdate): the sparse optimizer step on a compressed gradient, in place.  rule "sgd" /
+// "adagrad" (state fp32 [rows, width]) / "rowwise_adagrad" (state fp32 [rows]).  Valid entries, at most one of:
+// count >= 0 (host-known); counts (device words, int32 / int64: with piece_rows > 0 one per piece of piece_rows
+// entries, else one word for all entries); last_id (one word of ids' dtype, count = last_id + 1); none: every entry.
+// lr_device: one fp32 device word read by the kernel instead of lr.  One launch, nothing read back.
+void cuembed_sparse_row_update_op(at::Tensor table, const c10::optional<at::Tensor>& state_arg, const at::Tensor& ids,
+                                  const at::Tensor& rows, const std::string& rule, const double lr, const double eps,
+                                  const c10::optional<at::Tensor>& lr_device, const int64_t count,
+                                  const c10::optional<at::Tensor>& counts, const c10::optional<at::Tensor>& last_id,
+                                  const int64_t piece_rows_arg) {
+  CheckGpu(table, "table");
+  CheckGpu(ids, "ids");
+  CheckGpu(rows, "rows");
+  const int elem = ElemCode(table, "table");
+  const int idx = IndexCode(ids, "ids");
+  const int code = rule == "sgd" ? CUEMBED_UPDATE_SGD
+                   : rule == "adagrad" ? CUEMBED_UPDATE_ADAGRAD
+                   : rule == "rowwise_adagrad" ? CUEMBED_UPDATE_ROWWISE_ADAGRAD : -1;
+  TORCH_CHECK(code >= 0, "cuembed_pyt: rule must be 'sgd', 'adagrad' or 'rowwise_adagrad'");
+  TORCH_CHECK(rows.scalar_type() == table.scalar_type(), "cuembed_pyt: rows must have the table's dtype");
+  TORCH_CHECK(table.dim() == 2 && rows.dim() == 2 && rows.size(1) == table.size(1) && ids.dim() == 1 &&
+                  rows.size(0) == ids.numel() && table.is_contiguous() && rows.is_contiguous() && ids.is_contiguous(),
+              "cuembed_pyt: table [rows, width], rows [entries, width] and ids [entries] must be contiguous and agree");
+  TORCH_CHECK((table.size(1) * table.element_size()) % 4 == 0, "cuembed_pyt: the row size must be a multiple of 4 bytes");
+  at::Tensor state = state_arg.has_value() ? *state_arg : at::Tensor();
+  if (code == CUEMBED_UPDATE_SGD) {
+    TORCH_CHECK(!state.defined(), "cuembed_pyt: rule 'sgd' takes no state");
+  } else {
+    TORCH_CHECK(state.defined() && state.is_cuda() && state.scalar_type() == at::kFloat && state.is_contiguous() &&
+                    (code == CUEMBED_UPDATE_ADAGRAD ? state.sizes() == table.sizes()
+                                                    : (state.dim() == 1 && state.size(0) == table.size(0))),
+                "cuembed_pyt: the state must be a contiguous float32 GPU tensor, [rows, width] for 'adagrad', [rows] for "
+                "'rowwise_adagrad'");
+  }
+  const bool has_counts = counts.has_value() && counts->defined();
+  const bool has_last = last_id.has_value() && last_id->defined();
+  TORCH_CHECK((count >= 0) + has_counts + has_last <= 1, "cuembed_pyt: give at most one of count, counts and last_id");
+  int64_t num_rows = -1, piece_rows = ids.numel();
+  int pieces = 1, words64 = 0;
+  if (has_counts) {
+    CheckGpu(*counts, "counts");
+    words64 = IndexCode(*counts, "counts") == CUEMBED_I64;
+    TORCH_CHECK(counts->is_contiguous() && counts->numel() >= 1, "cuembed_pyt: counts must be contiguous words");
+    if (piece_rows_arg > 0) {
+      pieces = static_cast<int>(counts->numel());
+      piece_rows = piece_rows_arg;
+    }
+    TORCH_CHECK(pieces == counts->numel() && pieces * piece_rows == ids.numel(),
+                "cuembed_pyt: ids must hold counts.numel() * piece_rows entries");
+  } else if (has_last) {
+    CheckGpu(*last_id, "last_id");
+    TORCH_CHECK(last_id->scalar_type() == ids.scalar_type() && last_id->numel() == 1,
+                "cuembed_pyt: last_id must be one word of ids' dtype");
+  } else {
+    num_rows = count >= 0 ? count : ids.numel();
+    TORCH_CHECK(num_rows <= ids.numel(), "cuembed_pyt: count exceeds the entries");
+  }
+  const bool has_lr = lr_device.has_value() && lr_device->defined();
+  if (has_lr) {
+    CheckGpu(*lr_device, "lr_device");
+    TORCH_CHECK(lr_device->scalar_type() == at::kFloat && lr_device->numel() == 1, "cuembed_pyt: lr_device must be one float32 word");
+  }
+  if (ids.numel() == 0) return;
+  const at::DeviceGuard guard(table.device());
+  ::cuembed_sparse_row_update(table.data_ptr(), elem, static_cast<int>(table.size(1)),
+                              state.defined() ? static_cast<float*>(state.data_ptr()) : nullptr, code, Ptr(ids), idx,
+                              Ptr(rows), piece_rows, pieces, num_rows, has_counts ? counts->data_ptr() : nullptr, words64,
+                              has_last ? last_id->data_ptr() : nullptr, static_cast<float>(lr),
+                              has_lr ? static_cast<const float*>(lr_device->data_ptr()) : nullptr,
+                              static_cast<float>(eps), CurrentStream(table));
+}
+
 // Extension (cuembed::PackRowsByOwner): the rank's compressed gradient into the fixed slots of the all-to-all.
 void cuembed_exchange_pack_op(const at::Tensor& ids, const at::Tensor& rows, const c10::optional<at::Tensor>& count,
                               const at::Tensor& cuts, const int64_t slot_capacity, const int64_t input_capacity,
@@ -821,6 +893,9 @@ TORCH_LIBRARY(cuembed_pyt, m) {
   m.def(
       "cuembed_exchange_merge(Tensor ids, Tensor rows, int num_categories, int pad_lo, int pad_len, Tensor(a!) out_ids, "
       "Tensor(b!) out_rows, Tensor(c!)? tail, Tensor(d!) flag, Tensor(e!)? count) -> ()");
+  m.def(
+      "cuembed_sparse_row_update_(Tensor(a!) table, Tensor(b!)? state, Tensor ids, Tensor rows, str rule, float lr, "
+      "float eps, Tensor? lr_device, int count, Tensor? counts, Tensor? last_id, int piece_rows) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(cuembed_pyt, Autograd, m) {
@@ -853,4 +928,5 @@ TORCH_LIBRARY_IMPL(cuembed_pyt, CUDA, m) {  // HIP tensors use the CUDA dispatch
   m.impl("cuembed_decide_row_loads", cuembed_decide_row_loads_op);
   m.impl("cuembed_exchange_pack", cuembed_exchange_pack_op);
   m.impl("cuembed_exchange_merge", cuembed_exchange_merge_op);
+  m.impl("cuembed_sparse_row_update_", cuembed_sparse_row_update_op);
 }

@@ -69,6 +69,10 @@ def _define_python_ops():
                 " str mode, int row_loads, Tensor? sample_order, Tensor? row_loads_device) -> Tensor")
     _lib.define("cuembed_bag_order_by_length(Tensor offsets, int max_length) -> Tensor")
     _lib.define("cuembed_decide_row_loads(Tensor indices, int table_bytes, Tensor(a!) decision) -> ()")
+    _lib.define("cuembed_sparse_row_update_(Tensor(a!) table, Tensor(b!)? state, Tensor ids, Tensor rows, str rule,"
+                " float lr, float eps, Tensor? lr_device, int count, Tensor? counts, Tensor? last_id, int piece_rows)"
+                " -> ()")
+    _lib.impl("cuembed_sparse_row_update_", _sparse_row_update_impl, "CUDA")
     _lib.impl("cuembed_decide_row_loads", _decide_row_loads_impl, "CUDA")
     _lib.impl("cuembed_embedding_forward_hinted", _forward_hinted_impl, "CUDA")
     _lib.impl("cuembed_bag_order_by_length", _bag_order_impl, "CUDA")
@@ -101,6 +105,8 @@ def _define_python_ops():
 #   cuembed_embedding_forward_fixed           fixed-hotness forward with every combine mode of the C++ API (the
 #                                             reference binding only exposes CSR + sum, cuembed_embedding.cu:29-32)
 #   cuembed_embedding_weight_grad             gradient w.r.t. the per-lookup weights
+#   cuembed_sparse_row_update_                the sparse optimizer step on a compressed gradient, in place (SGD, Adagrad,
+#                                             row-wise Adagrad; the entry count may stay on the device)
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
 _INTS = (torch.int64, torch.int32)
@@ -228,6 +234,21 @@ def _weight_grad_impl(params, indices, offsets, y_grad):
                                       offsets=offsets.contiguous(), batch_size=offsets.numel() - 1, num_hots=0)
 
 
+def _sparse_row_update_impl(table, state, ids, rows, rule, lr, eps, lr_device, count, counts, last_id, piece_rows):
+    _require((count >= 0) + (counts is not None) + (last_id is not None) <= 1,
+             "give at most one of count, counts and last_id")
+    if counts is not None and piece_rows > 0:
+        kw = dict(counts=counts, piece_rows=piece_rows)
+    elif counts is not None:
+        kw = dict(count=counts)                 # one word for all entries
+    elif last_id is not None:
+        kw = dict(last_id=last_id)
+    else:
+        kw = dict(count=count if count >= 0 else None)
+    _ops.sparse_row_update(table, ids, rows, rule=rule, lr=lr if lr_device is None else lr_device, state=state, eps=eps,
+                           **kw)
+
+
 def _compress_impl(transpose_indices):
     _require(transpose_indices.is_cuda and transpose_indices.dtype in _INTS, "indices must be int tensors on the GPU")
     return _ops.compute_compressed_grad_indices(transpose_indices.contiguous())
@@ -261,6 +282,20 @@ cuembed_transpose_sample_ids = torch.ops.cuembed_pyt.cuembed_transpose_sample_id
 cuembed_transpose_fixed_hotness = torch.ops.cuembed_pyt.cuembed_transpose_fixed_hotness
 cuembed_embedding_forward = torch.ops.cuembed_pyt.cuembed_embedding_forward
 cuembed_embedding_backward = torch.ops.cuembed_pyt.cuembed_embedding_backward
+
+
+def cuembed_sparse_row_update_(table, ids, rows, rule, lr, state=None, eps=1e-8, count=None, last_id=None, counts=None,
+                               piece_rows=None):
+    """cuembed_amd.ops.sparse_row_update as the torch op cuembed_pyt::cuembed_sparse_row_update_ (in place on `table` and
+    `state`; traces under torch.compile).  Same arguments."""
+    lr_device = lr if isinstance(lr, torch.Tensor) else None
+    word = count if isinstance(count, torch.Tensor) else None
+    if word is not None and counts is not None:
+        raise ValueError("give at most one of count=, last_id= and counts=")
+    torch.ops.cuembed_pyt.cuembed_sparse_row_update_(
+        table, state, ids, rows, rule, 0.0 if lr_device is not None else float(lr), float(eps), lr_device,
+        -1 if (count is None or word is not None) else int(count), counts if word is None else word, last_id,
+        0 if piece_rows is None else int(piece_rows))
 
 
 def cuembed_forward(params, idx, offsets, weights, hints=None):
@@ -566,6 +601,11 @@ def _(params, idx, offsets, weights=None, mode="sum"):
 
 @torch.library.register_fake("cuembed_pyt::cuembed_decide_row_loads")
 def _(indices, table_bytes, decision):
+    return None
+
+
+@torch.library.register_fake("cuembed_pyt::cuembed_sparse_row_update_")
+def _(table, state, ids, rows, rule, lr, eps, lr_device=None, count=-1, counts=None, last_id=None, piece_rows=0):
     return None
 
 

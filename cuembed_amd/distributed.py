@@ -378,6 +378,13 @@ class SparseGradResult:
         tail = self._ids.view(self._world, self._piece + 2)
         return (tail[:, : self._piece].reshape(-1), self._rows, tail[:, self._piece])
 
+    def apply_to(self, updater):
+        """wait(), then the sparse optimizer step of `updater` (cuembed_amd.optim.SparseUpdater) on the pieces: entry j
+        of piece r counts iff j < counts[r], so the zero rows behind the counts are never touched (they name rows of
+        the owner's range again and would race with the real entries).  Nothing is read back."""
+        ids, rows, counts = self.wait()
+        updater.apply(ids, rows, counts=counts.contiguous(), piece_rows=self._piece)
+
     def flags(self):
         """(after wait()) every rank's overflow word of this step, a device tensor [world]."""
         return self._ids.view(self._world, self._piece + 2)[:, self._piece + 1]
@@ -404,8 +411,8 @@ class SparseGradExchange:
             ... forward / Transpose / EmbeddingBackward into (rows, ids, count) ...
             pending = ex.start(rows, ids, count)          # all-to-all + merge enqueued, all-gather in flight
             ... next batch's forward ...
-            ids_all, rows_all, counts = pending.wait()    # stream-side wait
-            table.index_add_(0, ids_all, rows_all, alpha=-lr)
+            pending.apply_to(updater)                     # stream-side wait + the sparse optimizer step on the pieces
+                                                          # (updater = cuembed_amd.optim.SparseUpdater(table, "sgd", lr))
     """
 
     def __init__(self, num_categories, width, dtype, device, pair_capacity, piece_capacity, local_capacity=0,

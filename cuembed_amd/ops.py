@@ -700,6 +700,124 @@ ExtractRowIdsFromCSR = extract_row_ids_from_csr
 ExtractRowIdsForConcat = extract_row_ids_for_concat
 
 
+# ---- sparse optimizer step (extension: the reference ends at the gradient) -----------------------------------------
+UPDATE_RULES = {"sgd": 0, "adagrad": 1, "rowwise_adagrad": 2}
+
+
+def sparse_row_update_launch_shape(elem_dtype, embed_width, total_entries, compute_units=256):
+    """Launch shape sparse_row_update would use on aligned buffers (pure host arithmetic when compute_units > 0;
+    0 = ask the current device)."""
+    out = (ctypes.c_int * 5)()
+    _lib.lib().cuembed_sparse_row_update_launch_shape(_ELEM[elem_dtype], int(embed_width), int(total_entries),
+                                                      int(compute_units), out)
+    return dict(lane_bytes=out[0], lanes_per_row=out[1], lanes_per_entry=out[2], slices_per_lane=out[3], grid=out[4])
+
+
+def sparse_row_update(table, ids, rows, *, rule, lr, state=None, eps=1e-8, count=None, last_id=None, counts=None,
+                      piece_rows=None):
+    """Sparse optimizer step (cuembed::SparseRowUpdate): for every valid entry k, table[ids[k], :] and the state of
+    that row are updated IN PLACE from the gradient row rows[k, :]; rows that no valid entry names are neither read
+    nor written.  fp32 arithmetic whatever the table's dtype, one rounding to it at the store.  Returns None.
+
+        rule="sgd"              w <- w - lr * g                                            state=None
+        rule="adagrad"          s <- s + g^2;  w <- w - lr * g / (sqrt(s) + eps)           state fp32 [rows, width]
+                                (torch.optim.Adagrad with lr_decay = 0, weight_decay = 0)
+        rule="rowwise_adagrad"  s_r <- s_r + mean_j(g_j^2);  w_j <- w_j - lr * g_j / (sqrt(s_r) + eps)   state fp32 [rows]
+
+    (ids, rows) is a compressed gradient as embedding_backward returns it -- (inverse_mapping, grad_embedding) -- or a
+    piece list of the sparse-gradient exchange.  Which entries are valid (at most one of):
+        count=int               the first `count` entries (host-known); default: all of them;
+        count=tensor            the same, read on the device: one int32 / int64 word (the num_unique of
+                                compute_compressed_grad_indices_blocked, the exchange's count);
+        last_id=tensor          one word of ids' dtype, count = last_id + 1: transpose_remapped_indices[-1:] -- the
+                                convention of embedding_backward(num_grad_embedding_rows=None);
+        counts=tensor, piece_rows=n   `counts.numel()` pieces of n entries each, entry j of piece p valid iff
+                                j < counts[p] (what SparseGradResult.wait() returns).
+    Entries at or past the count are ignored whatever they hold (the zero tail of a padded gradient names rows of the
+    batch again); a count above the capacity (the backward then wrote nothing and raised capacity_overflowed()) or below
+    zero changes nothing.  No form needs a host read-back, so the call can be captured into a HIP graph.
+
+    The valid entries must name DISTINCT rows: a coalesced gradient (a fully sorted transpose, or
+    compute_compressed_grad_indices_blocked + embedding_backward(sample_blocks=...)).  The sample-blocked UNCOALESCED
+    gradient (one entry per (block, row)) is not accepted -- use one of the coalesced kinds.
+
+    lr: a float, or a one-element fp32 device tensor read by the kernel (a captured graph then follows a schedule)."""
+    for name, t in (("table", table), ("ids", ids), ("rows", rows)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+    if rule not in UPDATE_RULES:
+        raise ValueError("rule must be one of %r, got %r" % (sorted(UPDATE_RULES), rule))
+    et = _elem_code("table", table)
+    it = _index_code("ids", ids)
+    if rows.dtype != table.dtype:
+        raise TypeError("rows must have the table's dtype (%s), got %s" % (table.dtype, rows.dtype))
+    if table.dim() != 2 or rows.dim() != 2 or rows.shape[1] != table.shape[1]:
+        raise ValueError("table must be [num_categories, width] and rows [entries, width]")
+    width = table.shape[1]
+    if (width * table.element_size()) % 4 != 0:
+        raise ValueError("the row size must be a multiple of 4 bytes")
+    n = ids.numel()
+    if ids.dim() != 1 or rows.shape[0] != n:
+        raise ValueError("ids must hold one entry per row of rows")
+    if rule == "sgd":
+        if state is not None:
+            raise ValueError("rule='sgd' takes no state")
+    else:
+        want = (table.shape[0], width) if rule == "adagrad" else (table.shape[0],)
+        if not isinstance(state, torch.Tensor):
+            raise TypeError("rule=%r needs a float32 state tensor of shape %r" % (rule, want))
+        if state.dtype != torch.float32:
+            raise TypeError("state must be float32, got %s" % state.dtype)
+        if tuple(state.shape) != want:
+            raise ValueError("rule=%r needs a state of shape %r, got %r" % (rule, want, tuple(state.shape)))
+    if (count is not None) + (last_id is not None) + (counts is not None) > 1:
+        raise ValueError("give at most one of count=, last_id= and counts=")
+    if piece_rows is not None and counts is None:
+        raise ValueError("piece_rows goes with counts=")
+    num_rows, count_words, pieces, words64 = -1, None, 1, False
+    if counts is not None:
+        if not isinstance(counts, torch.Tensor) or counts.dtype not in _INDEX or counts.dim() != 1 or counts.numel() < 1:
+            raise TypeError("counts must be a 1-D int32 or int64 tensor, one word per piece")
+        pieces = counts.numel()
+        if piece_rows is None:
+            piece_rows = n // pieces
+        if piece_rows < 0 or pieces * piece_rows != n:
+            raise ValueError("ids must hold counts.numel() * piece_rows entries")
+        count_words, words64 = counts, counts.dtype == torch.int64
+    elif isinstance(count, torch.Tensor):
+        if count.dtype not in _INDEX or count.numel() != 1:
+            raise TypeError("count must be an int or a one-element int32 / int64 tensor")
+        count_words, words64, piece_rows = count, count.dtype == torch.int64, n
+    elif last_id is not None:
+        if not isinstance(last_id, torch.Tensor) or last_id.dtype != ids.dtype or last_id.numel() != 1:
+            raise TypeError("last_id must be a one-element tensor of ids' dtype")
+        piece_rows = n
+    else:
+        num_rows = n if count is None else int(count)
+        if num_rows < 0 or num_rows > n:
+            raise ValueError("count must be in [0, ids.numel()]")
+        piece_rows = n
+    lr_word = None
+    if isinstance(lr, torch.Tensor):
+        if lr.dtype != torch.float32 or lr.numel() != 1:
+            raise TypeError("a device-side lr must be a one-element float32 tensor")
+        lr_word, lr = lr, 0.0
+    _check_dev("table", table)
+    dev = table.device
+    for name, t in (("ids", ids), ("rows", rows), ("state", state), ("count", count_words), ("last_id", last_id),
+                    ("lr", lr_word)):
+        if t is not None:
+            _check_dev(name, t, dev)
+    if n == 0:
+        return None
+    with torch.cuda.device(dev):
+        _lib.lib().cuembed_sparse_row_update(_ptr(table), et, width, _ptr(state), UPDATE_RULES[rule], _ptr(ids), it,
+                                             _ptr(rows), int(piece_rows), int(pieces), int(num_rows), _ptr(count_words),
+                                             int(words64), _ptr(last_id), float(lr), _ptr(lr_word), float(eps),
+                                             _stream(table))
+    return None
+
+
 # ---- multi-GPU: the device-side halves of the sparse gradient exchange (cuembed_amd/distributed.py) -----------------
 def exchange_pack_rows(ids, rows, count, cuts, slot_capacity, input_capacity, num_categories, send_ids, send_rows,
                        range_starts, flag):

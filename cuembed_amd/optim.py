@@ -1,0 +1,205 @@
+"""Sparse optimizers on the compressed gradient (an extension: the reference ends at the gradient).
+
+Two ways in, both ending in the same HIP kernel (cuembed_amd.ops.sparse_row_update):
+
+    SparseUpdater(table, rule, lr)              owns the optimizer state and applies (ids, rows) gradients to the
+        .apply(ids, rows, count=... | last_id=... | counts=..., piece_rows=...)      table in place;
+        .backward_and_apply(out_grad, idx, offsets, weights)   the whole backward of a sum-pooled lookup + the
+                                                update, with the row count left on the device: no host read-back, so
+                                                forward + backward_and_apply can be captured into a HIP graph;
+      SparseGradResult.apply_to(updater)        feeds it the pieces of SparseGradExchange (cuembed_amd.distributed).
+
+    SparseSGD / SparseAdagrad / RowwiseAdagrad  torch.optim.Optimizer subclasses for parameters whose .grad is the
+                                                COALESCED sparse COO tensor of
+                                                cuemb_embedding(..., sparse_grad=True | "reference" | "blocked").
+                                                An uncoalesced or dense gradient is an error, never coalesced silently.
+                                                (autograd drops the tensor's is_coalesced flag on the way into .grad;
+                                                step() then checks that the row ids ascend strictly, which reads one
+                                                byte back -- those gradient kinds read the row count back anyway.)
+
+Rules (fp32 arithmetic whatever the table's dtype, one rounding to it at the store):
+    "sgd"              w <- w - lr * g
+    "adagrad"          s <- s + g^2;  w <- w - lr * g / (sqrt(s) + eps)      (torch.optim.Adagrad, lr_decay = 0,
+                                                                              weight_decay = 0); fp32 state [rows, W]
+    "rowwise_adagrad"  s_r <- s_r + mean_j(g_j^2);  w_j <- w_j - lr * g_j / (sqrt(s_r) + eps);  fp32 state [rows]
+No momentum, weight decay, lr_decay or stochastic rounding.
+"""
+import torch
+
+from . import ops as _ops
+
+_ACCEPTED = ("the coalesced sparse COO gradient of cuemb_embedding(..., sparse_grad=True | 'reference' | 'blocked'); "
+             "for a step without a host read-back (HIP graph capture) use SparseUpdater.backward_and_apply")
+
+
+def _new_state(table, rule, initial_accumulator_value):
+    if rule == "sgd":
+        return None
+    shape = tuple(table.shape) if rule == "adagrad" else (table.shape[0],)
+    return torch.full(shape, float(initial_accumulator_value), dtype=torch.float32, device=table.device)
+
+
+class SparseUpdater:
+    """Applies compressed gradients to `table` ([num_categories, width]; fp32, fp16 or bf16) in place and owns the
+    optimizer state (`.state`: None, fp32 [num_categories, width] or fp32 [num_categories]).
+
+    lr is a float or a one-element fp32 device tensor that the kernel reads (fill it to follow a schedule inside a
+    captured graph); assign `.lr` to change it."""
+
+    def __init__(self, table, rule, lr, eps=1e-8, initial_accumulator_value=0.0):
+        if not isinstance(table, torch.Tensor) or table.dim() != 2:
+            raise TypeError("table must be a [num_categories, width] tensor")
+        if rule not in _ops.UPDATE_RULES:
+            raise ValueError("rule must be one of %r, got %r" % (sorted(_ops.UPDATE_RULES), rule))
+        if table.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError("table must be float32, float16 or bfloat16, got %s" % table.dtype)
+        if not table.is_contiguous():
+            raise ValueError("table must be contiguous")
+        self.table = table.detach()     # (a Parameter is updated through its data)
+        self.rule = rule
+        self.lr = lr
+        self.eps = float(eps)
+        self.state = _new_state(table, rule, initial_accumulator_value)
+        self._buffers = {}
+
+    def apply(self, ids, rows, count=None, last_id=None, counts=None, piece_rows=None):
+        """table[ids[k]] (and its state) <- rule, for the valid entries of a COALESCED gradient (ids, rows): see
+        cuembed_amd.ops.sparse_row_update for the count sources.  Nothing is read back."""
+        _ops.sparse_row_update(self.table, ids, rows, rule=self.rule, lr=self.lr, state=self.state, eps=self.eps,
+                               count=count, last_id=last_id, counts=counts, piece_rows=piece_rows)
+
+    def _step_buffers(self, nnz, dtype, index_dtype, weighted):
+        """Gradient rows / ids of min(nnz, num_categories) entries and the sort's workspace, kept between calls."""
+        key = (nnz, dtype, index_dtype, weighted)
+        b = self._buffers.get(key)
+        if b is None:
+            capacity = min(nnz, self.table.shape[0])
+            dev = self.table.device
+            work = _ops.transpose_workspace_bytes(nnz, index_dtype, dtype if weighted else None)
+            b = self._buffers[key] = dict(
+                rows=torch.empty((capacity, self.table.shape[1]), dtype=dtype, device=dev),
+                ids=torch.empty((capacity,), dtype=index_dtype, device=dev),
+                work=torch.empty((max(work, 1),), dtype=torch.uint8, device=dev))
+        return b
+
+    def backward_and_apply(self, out_grad, idx, offsets=None, weights=None):
+        """The backward of out = sum-pooled lookup(table, idx, offsets[, weights]) and the update, in one go:
+        row ids -> transpose (+ compressed ids) -> embedding_backward with the row count left on the device, into
+        buffers of min(lookups, num_categories) rows that this object keeps -> the update, which reads the count
+        itself.  idx [nnz] with offsets [batch + 1] (CSR, closing entry included), or idx [batch, hotness] with
+        offsets=None.  out_grad [batch, width] of the table's dtype.  No host read-back and, after the first call at a
+        size, no new device memory besides the index arrays torch's caching allocator recycles."""
+        if out_grad.dtype != self.table.dtype:
+            raise TypeError("out_grad must have the table's dtype (%s), got %s" % (self.table.dtype, out_grad.dtype))
+        if out_grad.dim() != 2 or out_grad.shape[1] != self.table.shape[1]:
+            raise ValueError("out_grad must be [batch, width]")
+        if offsets is None and idx.dim() != 2:
+            raise ValueError("without offsets, idx must be [batch, hotness]")
+        nnz = idx.numel()
+        if nnz == 0:
+            return
+        ncat = self.table.shape[0]
+        b = self._step_buffers(nnz, out_grad.dtype, idx.dtype, weights is not None)
+        out_grad = out_grad.contiguous()
+        if offsets is None:
+            t_idx, t_sid, t_w, remap = _ops.transpose_fixed_hotness(idx.contiguous(), idx.shape[0], idx.shape[1], weights,
+                                                                   workspace=b["work"], num_categories=ncat,
+                                                                   remapped=True)
+        else:
+            sid = _ops.extract_row_ids_from_csr(offsets, nnz=nnz, dtype=idx.dtype, batch_size=offsets.numel() - 1)
+            t_idx, t_sid, t_w, remap = _ops.transpose(sid, idx.contiguous(), weights, workspace=b["work"],
+                                                      num_categories=ncat, remapped=True)
+        _ops.embedding_backward(out_grad, None, t_idx, t_sid, remap, t_w, grad_embedding=b["rows"],
+                                inverse_mapping=b["ids"])
+        self.apply(b["ids"], b["rows"], last_id=remap[nnz - 1:])
+
+
+def _is_coalesced(g):
+    """Whether the sparse gradient holds one entry per row.  Autograd drops the is_coalesced flag when it stores a
+    sparse gradient in .grad, so a tensor without the flag is looked at: strictly ascending row ids are what
+    cuemb_embedding's coalesced kinds deliver (one byte read back; the flag is then set so that it is paid once per
+    gradient).  Nothing is ever coalesced here."""
+    if g.is_coalesced():
+        return True
+    ids = g._indices()
+    if ids.shape[0] != 1:
+        return False
+    if ids.shape[1] > 1 and not bool((ids[0, 1:] > ids[0, :-1]).all()):
+        return False
+    g._coalesced_(True)
+    return True
+
+
+class _SparseOptimizer(torch.optim.Optimizer):
+    """Common part of the torch.optim front ends: one SparseUpdater-style state tensor per parameter, kept in
+    self.state[p]["sum"] so that state_dict() / load_state_dict() carry it."""
+    _rule = None
+
+    def __init__(self, params, lr, eps=1e-8, initial_accumulator_value=0.0):
+        if not isinstance(lr, torch.Tensor) and lr < 0.0:
+            raise ValueError("invalid learning rate: %r" % (lr,))
+        if eps < 0.0 or initial_accumulator_value < 0.0:
+            raise ValueError("eps and initial_accumulator_value must not be negative")
+        super().__init__(params, dict(lr=lr, eps=eps, initial_accumulator_value=initial_accumulator_value))
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.dim() != 2:
+                    raise ValueError("every parameter must be a [num_categories, width] table")
+                if self._rule != "sgd":
+                    self.state[p]["sum"] = _new_state(p, self._rule, group["initial_accumulator_value"])
+
+    def load_state_dict(self, state_dict):
+        """As torch's, except that the accumulators stay fp32 (torch casts optimizer state to the parameter's dtype,
+        which would round the state of a 16-bit table)."""
+        super().load_state_dict(state_dict)
+        saved = state_dict["state"]
+        ids = [i for g in state_dict["param_groups"] for i in g["params"]]
+        params = [p for g in self.param_groups for p in g["params"]]
+        for i, p in zip(ids, params):
+            if i in saved and "sum" in saved[i]:
+                self.state[p]["sum"] = saved[i]["sum"].detach().to(device=p.device, dtype=torch.float32).clone()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                if not g.is_sparse:
+                    raise ValueError("%s needs a sparse gradient, got a dense one; accepted: %s"
+                                     % (type(self).__name__, _ACCEPTED))
+                if not _is_coalesced(g):
+                    raise ValueError("%s needs a COALESCED sparse gradient (one entry per table row), got an uncoalesced "
+                                     "one (sparse_grad='uncoalesced' / 'padded' / 'fastest'); accepted: %s"
+                                     % (type(self).__name__, _ACCEPTED))
+                if g.sparse_dim() != 1 or g.dense_dim() != 1:
+                    raise ValueError("the gradient must have one sparse (row) and one dense (column) dimension")
+                state = self.state[p].get("sum") if self._rule != "sgd" else None
+                _ops.sparse_row_update(p.data, g._indices()[0].contiguous(), g._values().contiguous(), rule=self._rule,
+                                       lr=group["lr"], state=state, eps=group["eps"])
+        return loss
+
+
+class SparseSGD(_SparseOptimizer):
+    """w <- w - lr * g on the rows of a coalesced sparse gradient (torch.optim.SGD without momentum / weight decay)."""
+    _rule = "sgd"
+
+    def __init__(self, params, lr):
+        super().__init__(params, lr)
+
+
+class SparseAdagrad(_SparseOptimizer):
+    """torch.optim.Adagrad (lr_decay = 0, weight_decay = 0) on the rows of a coalesced sparse gradient; the
+    accumulator is fp32 whatever the table's dtype."""
+    _rule = "adagrad"
+
+
+class RowwiseAdagrad(_SparseOptimizer):
+    """Adagrad with ONE accumulator per table row (the mean of the row's squared gradient): 4 bytes of state per row
+    instead of 4 * width."""
+    _rule = "rowwise_adagrad"

@@ -483,6 +483,31 @@ void cuembed_backward_launch_shape(int elem_type, int index_type, int embed_widt
 /* cuembed_recommended_sample_blocks for a described device (compute_units <= 0: the current one). */
 int cuembed_recommended_sample_blocks_on(int elem_type, int embed_width, int batch_size, int64_t nnz,
                                          int compute_units, int xcds, int64_t l2_bytes_per_xcd);
+/* ---- sparse optimizer step (extension: the reference ends at the gradient) ---------------
+ * cuembed_sparse_row_update (cuembed::SparseRowUpdate, sparse_update.hpp): for every valid entry k,
+ * table[ids[k], :] (elem_type, [num_categories, embed_width]) and the state of row ids[k] are updated in place from
+ * rows[k, :] (elem_type).  fp32 arithmetic, one rounding to the table's type at the store.
+ *   CUEMBED_UPDATE_SGD              w <- w - lr * g                                            state = NULL
+ *   CUEMBED_UPDATE_ADAGRAD          s <- s + g^2;  w <- w - lr * g / (sqrt(s) + eps)           state fp32 [num_categories, embed_width]
+ *   CUEMBED_UPDATE_ROWWISE_ADAGRAD  s_r <- s_r + mean_j(g_j^2);  w_j <- w_j - lr * g_j / (sqrt(s_r) + eps)   state fp32 [num_categories]
+ * The entries are `pieces` blocks of piece_rows entries (ids[pieces * piece_rows], rows[pieces * piece_rows,
+ * embed_width]); entry j of piece p is valid iff j < count(p), from exactly one of: num_rows >= 0 (host-known, one
+ * piece; else pass -1); counts[pieces] on the device (int32, or int64 with counts_are_int64 != 0); last_id, one
+ * index_type word on the device with count = *last_id + 1 (one piece; transpose_remapped_indices + nnz - 1 of
+ * cuembed_embedding_backward with num_grad_embedding_rows < 0).  Entries at or past the count are ignored whatever
+ * they hold; a count above piece_rows or below zero changes nothing.  The valid entries must name DISTINCT rows (a
+ * coalesced gradient; the uncoalesced gradient of a sample-blocked transpose is not accepted).  lr_device != NULL:
+ * the learning rate is read from that fp32 device word instead of lr.  One launch, no read-back. */
+enum { CUEMBED_UPDATE_SGD = 0, CUEMBED_UPDATE_ADAGRAD = 1, CUEMBED_UPDATE_ROWWISE_ADAGRAD = 2 };
+void cuembed_sparse_row_update(void* table, int elem_type, int embed_width, float* state, int rule, const void* ids,
+                               int index_type, const void* rows, int64_t piece_rows, int pieces, int64_t num_rows,
+                               const void* counts, int counts_are_int64, const void* last_id, float lr,
+                               const float* lr_device, float eps, cuembed_stream_t stream);
+/* Launch shape of cuembed_sparse_row_update for aligned buffers (no launch): out[0] = bytes per lane, out[1] = lanes
+ * per row, out[2] = lanes per entry (a power of two <= 64), out[3] = row slices a lane holds at once (0 = run-time
+ * loop), out[4] = grid size.  compute_units <= 0: the current device. */
+void cuembed_sparse_row_update_launch_shape(int elem_type, int embed_width, int64_t total_entries, int compute_units,
+                                            int* out);
 /* hipPeekAtLastError() as an int (0 = hipSuccess); launches themselves never
  * report errors, exactly like the reference. */
 int cuembed_peek_last_error(void);
