@@ -21,5 +21,7 @@ from .ops import (CONCAT, MEAN, SUM, ComputeCompressedGradIndices, EmbeddingBack
                   set_forward_reduction_order, set_forward_row_load_policy, get_forward_row_load_policy, set_forward_wide_load, transpose,
                   transpose_fixed_hotness,
                   transpose_workspace_bytes, sparse_row_update, sparse_row_update_launch_shape, UPDATE_RULES)
+from .quantized import (QuantizedEmbeddingBag, dequantize_rows, embedding_forward_quantized,  # noqa: F401
+                        quantize_rows, quantized_forward_launch_shape, quantized_row_bytes)
 
 __version__ = "0.1.0"

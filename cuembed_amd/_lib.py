@@ -123,6 +123,17 @@ def _declare(L):
                                             _VP, ctypes.c_float, _VP]
     L.cuembed_sparse_row_update_launch_shape.restype = None
     L.cuembed_sparse_row_update_launch_shape.argtypes = [_I, _I, _L, _I, ctypes.POINTER(_I)]
+    L.cuembed_quantized_row_bytes.restype = _L
+    L.cuembed_quantized_row_bytes.argtypes = [_I]
+    L.cuembed_quantize_rows.restype = None
+    L.cuembed_quantize_rows.argtypes = [_VP, _I, _I, _L, _VP, _VP]
+    L.cuembed_dequantize_rows.restype = None
+    L.cuembed_dequantize_rows.argtypes = [_VP, _I, _VP, _I, _L, _VP, _I, _VP]
+    L.cuembed_embedding_forward_quantized.restype = None
+    L.cuembed_embedding_forward_quantized.argtypes = [_VP, _I, _VP, _I, _VP, _I, _VP, _I, _I, _I, _VP, _I, _I, _VP, _VP,
+                                                      _VP]
+    L.cuembed_quantized_forward_launch_shape.restype = None
+    L.cuembed_quantized_forward_launch_shape.argtypes = [_I, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]
     L.cuembed_peek_last_error.restype = _I
     L.cuembed_peek_last_error.argtypes = []
     L.cuembed_version.restype = ctypes.c_char_p

@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <string>
 #include <tuple>
+#include <vector>
 
 #include "cuembed_amd.h"
 
@@ -850,6 +851,115 @@ at::Tensor cuemb_embedding_autograd_op(const at::Tensor& params, const at::Tenso
                                    row_loads_device.defined() ? c10::optional<at::Tensor>(row_loads_device) : c10::nullopt);
 }
 
+// ---- 8-bit row-wise quantized tables (extension; inference only).  The format is torch's own fused layout
+// (quantized::embedding_bag_byte_prepack): uint8 [rows, W + 8], codes, fp32 scale, fp32 bias. -------------------------
+
+int OutCode(const at::ScalarType t, const char* what) {
+  TORCH_CHECK(t == at::kFloat || t == at::kHalf, "cuembed_pyt: ", what, " must be float32 or float16");
+  return t == at::kFloat ? CUEMBED_F32 : CUEMBED_F16;
+}
+
+int64_t QuantizedWidth(const at::Tensor& qtable) {
+  CheckGpu(qtable, "qtable");
+  TORCH_CHECK(qtable.scalar_type() == at::kByte && qtable.dim() == 2 && qtable.is_contiguous(),
+              "cuembed_pyt: qtable must be a contiguous 2-D uint8 tensor [rows, width + 8]");
+  const int64_t width = qtable.size(1) - 8;
+  TORCH_CHECK(width > 0 && width % 4 == 0, "cuembed_pyt: row size must be a multiple of 4 bytes");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qtable.data_ptr()) % 4 == 0, "cuembed_pyt: qtable must be 4-byte aligned");
+  return width;
+}
+
+at::Tensor quantize_rows_op(const at::Tensor& table) {
+  CheckGpu(table, "table");
+  const int elem = ElemCode(table, "table");
+  TORCH_CHECK(table.dim() == 2 && table.size(1) > 0 && table.size(1) % 4 == 0,
+              "cuembed_pyt: table must be [rows, width] with a width that is a multiple of 4");
+  const at::DeviceGuard guard(table.device());
+  const at::Tensor t = table.contiguous();
+  at::Tensor out = at::empty({t.size(0), t.size(1) + 8}, t.options().dtype(at::kByte));
+  if (t.size(0) > 0)
+    ::cuembed_quantize_rows(Ptr(t), elem, static_cast<int>(t.size(1)), t.size(0), MutPtr(out), CurrentStream(t));
+  return out;
+}
+
+at::Tensor dequantize_rows_op(const at::Tensor& qtable, const c10::optional<at::Tensor>& ids, const at::ScalarType dtype) {
+  const int64_t width = QuantizedWidth(qtable);
+  const int out_code = OutCode(dtype, "dtype");
+  const at::DeviceGuard guard(qtable.device());
+  at::Tensor i;
+  int idx = CUEMBED_I32;
+  std::vector<int64_t> shape{qtable.size(0), width};
+  if (ids.has_value() && ids->defined()) {
+    CheckGpu(*ids, "ids");
+    idx = IndexCode(*ids, "ids");
+    i = ids->contiguous();
+    shape = i.sizes().vec();
+    shape.push_back(width);
+  }
+  at::Tensor out = at::empty(shape, qtable.options().dtype(dtype));
+  const int64_t n = i.defined() ? i.numel() : qtable.size(0);
+  if (n > 0)
+    ::cuembed_dequantize_rows(Ptr(qtable), static_cast<int>(width), Ptr(i), idx, n, MutPtr(out), out_code,
+                              CurrentStream(qtable));
+  return out;
+}
+
+// offsets given: CSR (batch + 1 entries); absent: fixed hotness, indices is [batch, hotness].
+at::Tensor cuemb_embedding_quantized_op(const at::Tensor& qtable, const at::Tensor& indices,
+                                        const c10::optional<at::Tensor>& offsets, const c10::optional<at::Tensor>& weights,
+                                        const std::string& mode, const at::ScalarType out_dtype, const int64_t row_loads,
+                                        const c10::optional<at::Tensor>& sample_order,
+                                        const c10::optional<at::Tensor>& row_loads_device) {
+  const int64_t width = QuantizedWidth(qtable);
+  const int out_code = OutCode(out_dtype, "out_dtype");
+  CheckGpu(indices, "indices");
+  const int idx = IndexCode(indices, "indices");
+  const bool csr = offsets.has_value() && offsets->defined();
+  const int m = Mode(mode, !csr);
+  TORCH_CHECK(row_loads >= -1 && row_loads <= 1, "cuembed_pyt: row_loads must be -1, 0 or 1");
+  const at::DeviceGuard guard(qtable.device());
+  const at::Tensor i = indices.contiguous();
+  at::Tensor o, w, order, decision;
+  int off = CUEMBED_I32;
+  int64_t batch = 0, hot = 0;
+  if (csr) {
+    CheckGpu(*offsets, "offsets");
+    off = IndexCode(*offsets, "offsets");
+    o = offsets->contiguous();
+    batch = o.numel() - 1;
+    TORCH_CHECK(batch >= 0, "cuembed_pyt: offsets must hold batch_size + 1 entries");
+  } else {
+    TORCH_CHECK(i.dim() == 2 && i.size(1) > 0, "cuembed_pyt: without offsets, indices must be [batch, hotness]");
+    batch = i.size(0);
+    hot = i.size(1);
+  }
+  if (weights.has_value() && weights->defined()) {
+    CheckGpu(*weights, "weights");
+    TORCH_CHECK(m != CUEMBED_CONCAT, "cuembed_pyt: concat does not take weights");
+    TORCH_CHECK(weights->scalar_type() == out_dtype, "cuembed_pyt: weights must have the output's dtype");
+    TORCH_CHECK(weights->numel() >= i.numel(), "cuembed_pyt: weights must have one entry per index");
+    w = weights->contiguous();
+  }
+  if (sample_order.has_value() && sample_order->defined()) {
+    order = *sample_order;
+    TORCH_CHECK(csr && order.is_cuda() && order.scalar_type() == at::kInt && order.numel() == batch && order.is_contiguous(),
+                "cuembed_pyt: sample_order (CSR only) must be a contiguous int32 permutation of the samples on the GPU");
+  }
+  if (row_loads_device.has_value() && row_loads_device->defined()) {
+    decision = *row_loads_device;
+    TORCH_CHECK(decision.is_cuda() && decision.scalar_type() == at::kInt && decision.numel() >= 4 && decision.is_contiguous(),
+                "cuembed_pyt: row_loads_device must be the contiguous 4-word int32 tensor of cuembed_decide_row_loads");
+  }
+  at::Tensor out = m == CUEMBED_CONCAT ? at::empty({batch, hot, width}, qtable.options().dtype(out_dtype))
+                                       : at::empty({batch, width}, qtable.options().dtype(out_dtype));
+  if (batch > 0)
+    ::cuembed_embedding_forward_quantized(Ptr(qtable), static_cast<int>(width), Ptr(i), idx, Ptr(o), off, Ptr(w),
+                                          static_cast<int>(batch), static_cast<int>(hot), m, MutPtr(out), out_code,
+                                          static_cast<int>(row_loads), static_cast<const int32_t*>(Ptr(order)),
+                                          static_cast<const uint32_t*>(Ptr(decision)), CurrentStream(qtable));
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(cuembed_pyt, m) {
@@ -896,6 +1006,12 @@ TORCH_LIBRARY(cuembed_pyt, m) {
   m.def(
       "cuembed_sparse_row_update_(Tensor(a!) table, Tensor(b!)? state, Tensor ids, Tensor rows, str rule, float lr, "
       "float eps, Tensor? lr_device, int count, Tensor? counts, Tensor? last_id, int piece_rows) -> ()");
+  // 8-bit row-wise quantized tables (torch's fused layout), inference only
+  m.def("quantize_rows(Tensor table) -> Tensor");
+  m.def("dequantize_rows(Tensor qtable, Tensor? ids, ScalarType dtype) -> Tensor");
+  m.def(
+      "cuemb_embedding_quantized(Tensor qtable, Tensor indices, Tensor? offsets, Tensor? weights, str mode, ScalarType "
+      "out_dtype, int row_loads, Tensor? sample_order, Tensor? row_loads_device) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(cuembed_pyt, Autograd, m) {
@@ -929,4 +1045,7 @@ TORCH_LIBRARY_IMPL(cuembed_pyt, CUDA, m) {  // HIP tensors use the CUDA dispatch
   m.impl("cuembed_exchange_pack", cuembed_exchange_pack_op);
   m.impl("cuembed_exchange_merge", cuembed_exchange_merge_op);
   m.impl("cuembed_sparse_row_update_", cuembed_sparse_row_update_op);
+  m.impl("quantize_rows", quantize_rows_op);
+  m.impl("dequantize_rows", dequantize_rows_op);
+  m.impl("cuemb_embedding_quantized", cuemb_embedding_quantized_op);
 }

@@ -72,6 +72,13 @@ def _define_python_ops():
     _lib.define("cuembed_sparse_row_update_(Tensor(a!) table, Tensor(b!)? state, Tensor ids, Tensor rows, str rule,"
                 " float lr, float eps, Tensor? lr_device, int count, Tensor? counts, Tensor? last_id, int piece_rows)"
                 " -> ()")
+    _lib.define("quantize_rows(Tensor table) -> Tensor")
+    _lib.define("dequantize_rows(Tensor qtable, Tensor? ids, ScalarType dtype) -> Tensor")
+    _lib.define("cuemb_embedding_quantized(Tensor qtable, Tensor indices, Tensor? offsets, Tensor? weights, str mode,"
+                " ScalarType out_dtype, int row_loads, Tensor? sample_order, Tensor? row_loads_device) -> Tensor")
+    _lib.impl("quantize_rows", _quantize_rows_impl, "CUDA")
+    _lib.impl("dequantize_rows", _dequantize_rows_impl, "CUDA")
+    _lib.impl("cuemb_embedding_quantized", _embedding_quantized_impl, "CUDA")
     _lib.impl("cuembed_sparse_row_update_", _sparse_row_update_impl, "CUDA")
     _lib.impl("cuembed_decide_row_loads", _decide_row_loads_impl, "CUDA")
     _lib.impl("cuembed_embedding_forward_hinted", _forward_hinted_impl, "CUDA")
@@ -107,6 +114,8 @@ def _define_python_ops():
 #   cuembed_embedding_weight_grad             gradient w.r.t. the per-lookup weights
 #   cuembed_sparse_row_update_                the sparse optimizer step on a compressed gradient, in place (SGD, Adagrad,
 #                                             row-wise Adagrad; the entry count may stay on the device)
+#   quantize_rows, dequantize_rows,           8-bit row-wise quantized tables in torch's own fused layout (inference
+#   cuemb_embedding_quantized                 only): the quantizer, its inverse, and the lookup on a fused table
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
 _INTS = (torch.int64, torch.int32)
@@ -249,6 +258,27 @@ def _sparse_row_update_impl(table, state, ids, rows, rule, lr, eps, lr_device, c
                            **kw)
 
 
+def _quantize_rows_impl(table):
+    from . import quantized as _q
+    return _q.quantize_rows(table.contiguous())
+
+
+def _dequantize_rows_impl(qtable, ids, dtype):
+    from . import quantized as _q
+    return _q.dequantize_rows(qtable, None if ids is None else ids.contiguous(), dtype)
+
+
+def _embedding_quantized_impl(qtable, indices, offsets, weights, mode, out_dtype, row_loads, sample_order, row_loads_device):
+    from . import quantized as _q
+    if offsets is None:
+        _require(indices.dim() == 2 and indices.shape[1] > 0, "without offsets, indices must be [batch, hotness]")
+    return _q.embedding_forward_quantized(
+        qtable, indices.contiguous(), None if offsets is None else offsets.contiguous(),
+        None if weights is None else weights.contiguous(), num_hots=0 if offsets is not None else indices.shape[1],
+        mode=mode, out_dtype=out_dtype, row_loads={-1: None, 0: "default", 1: "streaming"}[int(row_loads)],
+        sample_order=sample_order, row_loads_device=row_loads_device)
+
+
 def _compress_impl(transpose_indices):
     _require(transpose_indices.is_cuda and transpose_indices.dtype in _INTS, "indices must be int tensors on the GPU")
     return _ops.compute_compressed_grad_indices(transpose_indices.contiguous())
@@ -296,6 +326,29 @@ def cuembed_sparse_row_update_(table, ids, rows, rule, lr, state=None, eps=1e-8,
         table, state, ids, rows, rule, 0.0 if lr_device is not None else float(lr), float(eps), lr_device,
         -1 if (count is None or word is not None) else int(count), counts if word is None else word, last_id,
         0 if piece_rows is None else int(piece_rows))
+
+
+def quantize_rows(table):
+    """cuembed_amd.quantize_rows as the torch op cuembed_pyt::quantize_rows (traces under torch.compile)."""
+    return torch.ops.cuembed_pyt.quantize_rows(table)
+
+
+def dequantize_rows(qtable, ids=None, dtype=torch.float32):
+    """cuembed_amd.dequantize_rows as the torch op cuembed_pyt::dequantize_rows."""
+    return torch.ops.cuembed_pyt.dequantize_rows(qtable, ids, dtype)
+
+
+def cuemb_embedding_quantized(qtable, idx, offsets=None, weights=None, mode="sum", out_dtype=torch.float16, hints="auto"):
+    """The lookup on a fused 8-bit row-wise table (torch's quantized::embedding_bag_byte_prepack layout) as the torch op
+    cuembed_pyt::cuemb_embedding_quantized: CSR with `offsets` (batch + 1 entries), fixed hotness with idx [batch,
+    hotness] and no offsets (then mode may be "concat").  Inference only: nothing here is differentiable.
+    hints="auto" applies cuembed_amd.policy's scheduling hints like cuemb_embedding; results never depend on them."""
+    order = decision = None
+    if hints == "auto" and not torch.compiler.is_compiling():
+        order = _policy.sample_order(offsets, idx.numel())
+        decision = _policy.row_loads_device(qtable, idx)
+    return torch.ops.cuembed_pyt.cuemb_embedding_quantized(qtable, idx, offsets, weights, mode, out_dtype, -1, order,
+                                                           decision)
 
 
 def cuembed_forward(params, idx, offsets, weights, hints=None):
@@ -607,6 +660,30 @@ def _(indices, table_bytes, decision):
 @torch.library.register_fake("cuembed_pyt::cuembed_sparse_row_update_")
 def _(table, state, ids, rows, rule, lr, eps, lr_device=None, count=-1, counts=None, last_id=None, piece_rows=0):
     return None
+
+
+@torch.library.register_fake("cuembed_pyt::quantize_rows")
+def _(table):
+    return torch.empty((table.shape[0], table.shape[1] + 8), device=table.device, dtype=torch.uint8)
+
+
+@torch.library.register_fake("cuembed_pyt::dequantize_rows")
+def _(qtable, ids=None, dtype=torch.float32):
+    lead = (qtable.shape[0],) if ids is None else tuple(ids.shape)
+    return torch.empty(lead + (qtable.shape[1] - 8,), device=qtable.device, dtype=dtype)
+
+
+@torch.library.register_fake("cuembed_pyt::cuemb_embedding_quantized")
+def _(qtable, indices, offsets=None, weights=None, mode="sum", out_dtype=torch.float16, row_loads=-1, sample_order=None,
+      row_loads_device=None):
+    width = qtable.shape[1] - 8
+    if offsets is not None:
+        shape = (offsets.shape[0] - 1, width)
+    elif mode == "concat":
+        shape = (indices.shape[0], indices.shape[1], width)
+    else:
+        shape = (indices.shape[0], width)
+    return torch.empty(shape, device=qtable.device, dtype=out_dtype)
 
 
 @torch.library.register_fake("cuembed_pyt::cuembed_embedding_forward_hinted")

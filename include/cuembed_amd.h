@@ -508,6 +508,36 @@ void cuembed_sparse_row_update(void* table, int elem_type, int embed_width, floa
  * loop), out[4] = grid size.  compute_units <= 0: the current device. */
 void cuembed_sparse_row_update_launch_shape(int elem_type, int embed_width, int64_t total_entries, int compute_units,
                                             int* out);
+/* ---- 8-bit row-wise quantized tables (extension; inference only) ---------------------------
+ * The format is PyTorch's fused 8-bit row-wise layout (quantized::embedding_bag_byte_prepack): a row of embed_width
+ * values is embed_width + 8 bytes -- embed_width uint8 codes, the row's fp32 scale, its fp32 bias, little endian --
+ * and a value is code * scale + bias.  embed_width must be a multiple of 4; tables are contiguous
+ * [num_categories, embed_width + 8] bytes, at least 4-byte aligned (8-byte aligned tables of embed_width % 8 == 0 take
+ * the 8-byte lanes); outputs are 16-byte aligned. */
+int64_t cuembed_quantized_row_bytes(int embed_width);
+/* cuembed::QuantizeRows: in [rows, embed_width] of elem_type (fp32 / fp16 / bf16, 16-byte aligned) -> out, fused rows.
+ * scale = (max - min) / 255, bias = min, code = rint((x - min) * (255 / (max - min + 1e-8))), every step one fp32
+ * operation: the bytes torch's CPU prepack writes. */
+void cuembed_quantize_rows(const void* in, int elem_type, int embed_width, int64_t rows, void* out,
+                           cuembed_stream_t stream);
+/* cuembed::DequantizeRows: out[i, :] (out_type: CUEMBED_F32 or CUEMBED_F16) = the values of row ids[i] (ids == NULL:
+ * row i): float(code) * scale + bias in two rounded fp32 operations, then one rounding to out_type. */
+void cuembed_dequantize_rows(const void* qtable, int embed_width, const void* ids, int index_type, int64_t n, void* out,
+                             int out_type, cuembed_stream_t stream);
+/* cuembed::EmbeddingForwardQuantized: cuembed_embedding_forward on a fused table.  ret and weights are of out_type
+ * (CUEMBED_F32 or CUEMBED_F16); fp32 accumulation in lookup order; row_load_policy (-1 = the process-wide default, 0
+ * default, 1 streaming), sample_order (CSR only) and row_loads_device are the scheduling hints of
+ * cuembed_embedding_forward_device_hints and change no bit. */
+void cuembed_embedding_forward_quantized(const void* qtable, int embed_width, const void* indices, int index_type,
+                                         const void* offsets, int offset_type, const void* weights, int batch_size,
+                                         int num_hots, int mode, void* ret, int out_type, int row_load_policy,
+                                         const int32_t* sample_order, const uint32_t* row_loads_device,
+                                         cuembed_stream_t stream);
+/* Launch shape of the quantized sum / mean forward for aligned buffers (no launch): out[0] = codes per lane, out[1] =
+ * lanes per row, out[2] = samples per workgroup, out[3] = grid size, out[4] = dynamic LDS bytes, out[5] = 1 when the
+ * indices are staged in LDS.  compute_units > 0 describes the device (with xcds); <= 0: the current device. */
+void cuembed_quantized_forward_launch_shape(int index_type, int out_type, int embed_width, int batch_size, int num_hots,
+                                            int is_csr, int is_weighted, int compute_units, int xcds, int* out);
 /* hipPeekAtLastError() as an int (0 = hipSuccess); launches themselves never
  * report errors, exactly like the reference. */
 int cuembed_peek_last_error(void);
