@@ -15,6 +15,13 @@ every figure is the median over the rounds (200 calls each by default) with the 
 next to it.  A side is called faster only when its slowest round beats the other side's fastest.
 
     python benchmarks/optimizer_step_benchmark.py --out profiles/sparse_update_timing.json [--commit ID]
+
+--stochastic-rounding times something else: what stochastic rounding of the store costs.  The update alone on the same
+gradient (C4 and batch 1,024; fp16 and bf16 tables; every rule), round-to-nearest and stochastic rounding taking turns
+in one process, 50 calls a round by default; per pair the ratio of the medians and whether the two are separable beyond
+the spread (the slowest round of one below the fastest of the other).
+
+    python benchmarks/optimizer_step_benchmark.py --stochastic-rounding --out profiles/stochastic_rounding_timing.json
 """
 import argparse
 import json
@@ -75,6 +82,42 @@ def commit_id(given):
                               stderr=subprocess.DEVNULL, text=True, check=True).stdout.strip()
     except Exception:  # noqa: BLE001 - a source tree without its history
         return "unknown"
+
+
+def run_rounding_shape(torch, a, name, dtype, batch):
+    """The update alone with round-to-nearest and with stochastic rounding, alternating, per rule."""
+    import cuembed_amd as ce
+    from cuembed_amd import harness, optim
+    ncat, W, H = a.rows, a.width, a.hotness
+    dev = torch.device("cuda")
+    table = torch.empty((ncat, W), dtype=dtype, device=dev).uniform_(-1, 1)
+    idx = torch.from_numpy(harness.generate_indices(ncat, batch, H, alpha=a.alpha)).to(dev).view(batch, H)
+    gy = (torch.rand((batch, W), device=dev) * 2 - 1).mul_(2.0 ** -6).to(dtype)
+    t_idx, t_sid, _, remap = ce.transpose_fixed_hotness(idx, batch, H, num_categories=ncat, remapped=True)
+    n = int(remap[-1].item()) + 1
+    rows, ids = ce.embedding_backward(gy, n, t_idx, t_sid, remap)
+    last_id = remap[-1:].clone()
+    del t_idx, t_sid, remap, idx, gy
+    result = dict(shape=name, dtype=str(dtype).replace("torch.", ""), rows=ncat, width=W, batch=batch, hotness=H,
+                  alpha=a.alpha, gradient_rows=n, gradient_bytes=n * W * table.element_size(), update={})
+    for rule in ("sgd", "adagrad", "rowwise_adagrad"):
+        nearest = optim.SparseUpdater(table, rule, 1e-3)
+        stochastic = optim.SparseUpdater(table, rule, 1e-3, stochastic_rounding=True, seed=0x5EED)
+        sides = {"nearest": lambda up=nearest: up.apply(ids, rows, last_id=last_id),
+                 "stochastic": lambda up=stochastic: up.apply(ids, rows, last_id=last_id)}
+        got = alternate(torch, sides, a.calls, a.rounds, a.warmup)
+        moved = update_bytes(n, W, table.element_size(), ids.element_size(), rule)
+        for side in got.values():
+            side["tb_per_s"] = moved / (side["ms"] * 1e-3) / 1e12
+            side["share_of_float4_copy"] = side["tb_per_s"] / FLOAT4_COPY_TBS
+        result["update"][rule] = dict(got, algorithmic_bytes=moved, ratio=got["stochastic"]["ms"] / got["nearest"]["ms"],
+                                      separable_beyond_the_spread=faster(got["nearest"], got["stochastic"])
+                                      or faster(got["stochastic"], got["nearest"]))
+        del nearest, stochastic, sides
+        torch.cuda.empty_cache()
+    del table
+    torch.cuda.empty_cache()
+    return result
 
 
 def run_shape(torch, a, name, dtype, batch):
@@ -169,12 +212,16 @@ def main():
     p.add_argument("--alpha", type=float, default=1.15)
     p.add_argument("--batches", type=int, nargs="+", default=[65536, 1024])
     p.add_argument("--graph_batch", type=int, default=4096, help="replay the library's step from a HIP graph up to this batch")
-    p.add_argument("--calls", type=int, default=200, help="timed calls per round")
+    p.add_argument("--calls", type=int, default=None, help="timed calls per round (default 200; 50 with --stochastic-rounding)")
+    p.add_argument("--stochastic-rounding", action="store_true",
+                   help="time the update with round-to-nearest against stochastic rounding instead (fp16 and bf16 tables)")
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--out", default=None, help="write the JSON here as well")
     p.add_argument("--commit", default=None, help="commit the tree was built from (default: git rev-parse)")
     a = p.parse_args()
+    if a.calls is None:
+        a.calls = 50 if a.stochastic_rounding else 200
     import torch
     if not torch.cuda.is_available():
         sys.exit("optimizer_step_benchmark: needs a GPU (there is nothing to time without one)")
@@ -182,7 +229,19 @@ def main():
     report = dict(tool="benchmarks/optimizer_step_benchmark.py", commit=commit_id(a.commit),
                   device=torch.cuda.get_device_name(0), torch=torch.__version__, calls_per_round=a.calls, rounds=a.rounds,
                   float4_copy_tb_per_s=FLOAT4_COPY_TBS, shapes=[])
-    for batch in a.batches:
+    for batch in a.batches if a.stochastic_rounding else ():
+        for dtype in (torch.float16, torch.bfloat16):
+            name = "C4" if (batch, a.rows, a.width, a.hotness) == (65536, 10_000_000, 256, 64) else "B=%d" % batch
+            r = run_rounding_shape(torch, a, name, dtype, batch)
+            report["shapes"].append(r)
+            for rule, e in r["update"].items():
+                print("%s %s update %-16s nearest %.4f ms (spread %.4f, %.0f %% of the float4 copy), stochastic %.4f ms "
+                      "(spread %.4f, %.0f %%): ratio %.3f, separable beyond the spread: %s" % (
+                          name, r["dtype"], rule, e["nearest"]["ms"], e["nearest"]["spread"],
+                          100 * e["nearest"]["share_of_float4_copy"], e["stochastic"]["ms"], e["stochastic"]["spread"],
+                          100 * e["stochastic"]["share_of_float4_copy"], e["ratio"], e["separable_beyond_the_spread"]),
+                      flush=True)
+    for batch in () if a.stochastic_rounding else a.batches:
         for dtype in ((torch.float16, torch.float32) if batch == max(a.batches) else (torch.float16,)):
             name = "C4" if (batch, a.rows, a.width, a.hotness) == (65536, 10_000_000, 256, 64) else "B=%d" % batch
             r = run_shape(torch, a, name, dtype, batch)
@@ -203,6 +262,12 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             f.write(text + "\n")
+    if a.stochastic_rounding:
+        print(json.dumps(dict(summary=[dict(shape=s["shape"], dtype=s["dtype"],
+                                            nearest_ms={k: v["nearest"]["ms"] for k, v in s["update"].items()},
+                                            stochastic_ms={k: v["stochastic"]["ms"] for k, v in s["update"].items()})
+                                       for s in report["shapes"]])))
+        return
     print(json.dumps(dict(summary=[dict(shape=s["shape"], dtype=s["dtype"],
                                         update_ms={k: v["library"]["ms"] for k, v in s["update"].items()},
                                         torch_ms={k: v["torch"]["ms"] for k, v in s["update"].items() if "torch" in v})

@@ -121,6 +121,16 @@ def _declare(L):
     L.cuembed_sparse_row_update.restype = None
     L.cuembed_sparse_row_update.argtypes = [_VP, _I, _I, _VP, _I, _VP, _I, _VP, _L, _I, _L, _VP, _I, _VP, ctypes.c_float,
                                             _VP, ctypes.c_float, _VP]
+    _U = ctypes.c_uint64
+    L.cuembed_sparse_row_update_stochastic.restype = None
+    L.cuembed_sparse_row_update_stochastic.argtypes = [_VP, _I, _I, _VP, _I, _VP, _I, _VP, _L, _I, _L, _VP, _I, _VP,
+                                                       ctypes.c_float, _VP, ctypes.c_float, _U, _U, _VP, _VP]
+    L.cuembed_stochastic_rounding_words.restype = None
+    L.cuembed_stochastic_rounding_words.argtypes = [_U, _U, _L, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+    L.cuembed_stochastic_round.restype = ctypes.c_uint16
+    L.cuembed_stochastic_round.argtypes = [_I, ctypes.c_float, ctypes.c_uint32]
+    L.cuembed_stochastic_round_array.restype = None
+    L.cuembed_stochastic_round_array.argtypes = [_I, _VP, _VP, _L, _VP]
     L.cuembed_sparse_row_update_launch_shape.restype = None
     L.cuembed_sparse_row_update_launch_shape.argtypes = [_I, _I, _L, _I, ctypes.POINTER(_I)]
     L.cuembed_quantized_row_bytes.restype = _L

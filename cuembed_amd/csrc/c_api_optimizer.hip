@@ -1,19 +1,6 @@
 // C ABI: the sparse optimizer step = explicit instantiations of cuembed::SparseRowUpdate (an extension: the
 // reference ends at the gradient).
-#include "c_api_common.hpp"
-#include "cuembed/include/sparse_update.hpp"
-
-using cuembed_c_api::Stream;
-
-namespace {
-template <typename ElemT, typename IndexT>
-void Update(void* table, float* state, int embed_width, const void* ids, const void* rows,
-            const cuembed::SparseUpdateOptions& options, cuembed_stream_t stream) {
-  cuembed::SparseRowUpdate<ElemT, IndexT>(static_cast<ElemT*>(table), state, embed_width,
-                                          static_cast<const IndexT*>(ids), static_cast<const ElemT*>(rows), options,
-                                          Stream(stream));
-}
-}  // namespace
+#include "c_api_optimizer_common.hpp"
 
 extern "C" {
 
@@ -21,25 +8,11 @@ void cuembed_sparse_row_update(void* table, int elem_type, int embed_width, floa
                                int index_type, const void* rows, int64_t piece_rows, int pieces, int64_t num_rows,
                                const void* counts, int counts_are_int64, const void* last_id, float lr,
                                const float* lr_device, float eps, cuembed_stream_t stream) {
-  cuembed::SparseUpdateOptions o;
-  switch (rule) {
-    case CUEMBED_UPDATE_SGD: o.rule = cuembed::UpdateRule::kSgd; break;
-    case CUEMBED_UPDATE_ADAGRAD: o.rule = cuembed::UpdateRule::kAdagrad; break;
-    case CUEMBED_UPDATE_ROWWISE_ADAGRAD: o.rule = cuembed::UpdateRule::kRowwiseAdagrad; break;
-    default:
-      std::cerr << "Check failed: unknown update rule at " << __FILE__ << ":" << __LINE__ << std::endl;
-      std::abort();
-  }
-  o.lr = lr;
-  o.lr_device = lr_device;
-  o.eps = eps;
-  o.piece_rows = piece_rows;
-  o.pieces = pieces;
-  o.num_rows = num_rows;
-  o.counts = counts;
-  o.counts_are_int64 = counts_are_int64 != 0;
-  o.last_id = last_id;
-#define UPD(E, I) Update<E, I>(table, state, embed_width, ids, rows, o, stream)
+  // (round to nearest only: the stochastic kernels are c_api_optimizer_stochastic.hip's)
+  const cuembed::SparseUpdateOptions o = cuembed_c_api::UpdateOptions(rule, piece_rows, pieces, num_rows, counts,
+                                                                      counts_are_int64, last_id, lr, lr_device, eps);
+#define UPD(E, I) \
+  cuembed_c_api::Update<E, I, cuembed::UpdateRoundings::kNearestOnly>(table, state, embed_width, ids, rows, o, stream)
   switch ((elem_type << 1) | index_type) {
     case 0: UPD(float, int32_t); break;
     case 1: UPD(float, int64_t); break;

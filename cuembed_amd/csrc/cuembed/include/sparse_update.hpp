@@ -36,7 +36,19 @@ struct SparseUpdateOptions {
   bool counts_are_int64 = false;     //!< ... int64
   const void* last_id = nullptr;     //!< one IndexT word on the device, count = *last_id + 1 (one piece): the
                                      //!< convention of EmbeddingBackward with num_grad_embedding_rows < 0
+  //! Stochastic rounding of the one rounding to the table's type (__half / __hip_bfloat16 tables only; see
+  //! stochastic_rounding.hpp).  The bits depend on (rounding_seed, step, table row, column) and on nothing else: give
+  //! every call of a run the same seed and its own step.
+  bool stochastic_rounding = false;
+  uint64_t rounding_seed = 0;
+  uint64_t rounding_step = 0;                    //!< the step, unless ...
+  const int64_t* rounding_step_device = nullptr; //!< ... one int64 word on the device holds it (advance it on the
+                                                 //!< device and a replayed graph draws fresh bits)
 };
+
+//! Which roundings a SparseRowUpdate instantiation carries kernels for.  The header API carries both; the C ABI splits
+//! them over two translation units so that they compile side by side.
+enum class UpdateRoundings { kBoth, kNearestOnly, kStochasticOnly };
 
 namespace detail {
 
@@ -81,32 +93,54 @@ inline UpdateShape PlanUpdate(const int lanes_per_row, const int64_t total_entri
   return s;
 }
 
-template <typename ElemT, typename IndexT, int N, UpdateRule kRule>
+template <typename ElemT, typename IndexT, int N, UpdateRule kRule, bool kStochastic>
 inline void LaunchSparseRowUpdate(ElemT* table, float* state, const int width, const IndexT* ids, const ElemT* rows,
                                   const SparseUpdateOptions& o, const UpdateCounts& counts, const hipStream_t stream) {
   const UpdateShape s = PlanUpdate(width / N, o.piece_rows * o.pieces, CurrentDeviceShape());
-#define CUEMBED_LAUNCH_UPDATE(CHUNKS)                                                                          \
-  SparseRowUpdateKernel<ElemT, IndexT, N, kRule, CHUNKS><<<dim3(s.grid), dim3(kUpdateBlockThreads), 0, stream>>>( \
-      ids, rows, table, state, width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr, o.lr_device, o.eps)
+  UpdateRounding<kStochastic> rounding;
+  if constexpr (kStochastic) {
+    rounding.seed = o.rounding_seed;
+    rounding.step = o.rounding_step;
+    rounding.step_word = o.rounding_step_device;
+  }
+#define CUEMBED_LAUNCH_UPDATE(CHUNKS)                                                                             \
+  SparseRowUpdateKernel<ElemT, IndexT, N, kRule, CHUNKS, kStochastic>                                             \
+      <<<dim3(s.grid), dim3(kUpdateBlockThreads), 0, stream>>>(ids, rows, table, state, width, s.lanes_per_row,   \
+                                                               s.group, o.piece_rows, o.pieces, counts, o.lr,     \
+                                                               o.lr_device, o.eps, rounding)
   if (s.chunks == 1) CUEMBED_LAUNCH_UPDATE(1);
   else if (s.chunks == kUpdateMaxChunks) CUEMBED_LAUNCH_UPDATE(kUpdateMaxChunks);
   else CUEMBED_LAUNCH_UPDATE(0);
 #undef CUEMBED_LAUNCH_UPDATE
 }
 
-template <typename ElemT, typename IndexT, int N>
+template <typename ElemT, typename IndexT, int N, bool kStochastic>
 inline void LaunchSparseRowUpdateRule(ElemT* table, float* state, const int width, const IndexT* ids, const ElemT* rows,
                                       const SparseUpdateOptions& o, const UpdateCounts& counts, const hipStream_t stream) {
   switch (o.rule) {
     case UpdateRule::kSgd:
-      return LaunchSparseRowUpdate<ElemT, IndexT, N, UpdateRule::kSgd>(table, state, width, ids, rows, o, counts, stream);
+      return LaunchSparseRowUpdate<ElemT, IndexT, N, UpdateRule::kSgd, kStochastic>(table, state, width, ids, rows, o, counts, stream);
     case UpdateRule::kAdagrad:
-      return LaunchSparseRowUpdate<ElemT, IndexT, N, UpdateRule::kAdagrad>(table, state, width, ids, rows, o, counts, stream);
+      return LaunchSparseRowUpdate<ElemT, IndexT, N, UpdateRule::kAdagrad, kStochastic>(table, state, width, ids, rows, o, counts,
+                                                                                       stream);
     case UpdateRule::kRowwiseAdagrad:
-      return LaunchSparseRowUpdate<ElemT, IndexT, N, UpdateRule::kRowwiseAdagrad>(table, state, width, ids, rows, o, counts,
-                                                                                 stream);
+      return LaunchSparseRowUpdate<ElemT, IndexT, N, UpdateRule::kRowwiseAdagrad, kStochastic>(table, state, width, ids, rows, o,
+                                                                                              counts, stream);
   }
   CUEMBED_ASSERT(false && "unknown update rule");
+}
+
+//! The lane width's instantiation: N = 16 / 8 / 4 bytes of ElemT.
+template <typename ElemT, typename IndexT, bool kStochastic>
+inline void LaunchSparseRowUpdateBytes(const int bytes, ElemT* table, float* state, const int width, const IndexT* ids,
+                                       const ElemT* rows, const SparseUpdateOptions& o, const UpdateCounts& counts,
+                                       const hipStream_t stream) {
+  constexpr int kMaxN = 16 / static_cast<int>(sizeof(ElemT));
+  if (bytes == 16) LaunchSparseRowUpdateRule<ElemT, IndexT, kMaxN, kStochastic>(table, state, width, ids, rows, o, counts, stream);
+  else if (bytes == 8)
+    LaunchSparseRowUpdateRule<ElemT, IndexT, kMaxN / 2, kStochastic>(table, state, width, ids, rows, o, counts, stream);
+  else
+    LaunchSparseRowUpdateRule<ElemT, IndexT, kMaxN / 4, kStochastic>(table, state, width, ids, rows, o, counts, stream);
 }
 
 }  // namespace detail
@@ -115,7 +149,10 @@ inline void LaunchSparseRowUpdateRule(ElemT* table, float* state, const int widt
  * @brief Sparse optimizer step: for every valid entry k, table[ids[k], :] and the state of row ids[k] are updated in
  * place from rows[k, :] by options.rule.  Rows that no valid entry names are neither read nor written.
  *
- * All arithmetic is fp32 whatever ElemT is, with exactly one rounding to ElemT at the store.
+ * All arithmetic is fp32 whatever ElemT is, with exactly one rounding to ElemT at the store: to nearest, or, with
+ * options.stochastic_rounding on a __half / __hip_bfloat16 table, up or down with the probability of the value's
+ * position between its two neighbours (stochastic_rounding.hpp).  The fp32 arithmetic and the fp32 state are the same
+ * either way.
  *
  * The valid entries must name DISTINCT rows, i.e. the gradient must be coalesced: the output of EmbeddingBackward on a
  * fully sorted transpose or on ComputeCompressedGradIndicesBlocked's ids, or a piece of the sparse-gradient exchange.
@@ -130,10 +167,11 @@ inline void LaunchSparseRowUpdateRule(ElemT* table, float* state, const int widt
  * @param ids    [pieces * piece_rows] table rows (values in [0, num_categories) wherever valid)
  * @param rows   [pieces * piece_rows, embed_width] gradient rows, of the table's type
  *
- * Misuse (no or more than one count source, a missing state, a row size that is not a multiple of 4 bytes) aborts
- * with the failed condition, like EmbeddingBackward.
+ * Misuse (no or more than one count source, a missing state, a row size that is not a multiple of 4 bytes, stochastic
+ * rounding on a float table or in an instantiation without those kernels) aborts with the failed condition, like
+ * EmbeddingBackward.
  */
-template <typename ElemT, typename IndexT>
+template <typename ElemT, typename IndexT, UpdateRoundings kRoundings = UpdateRoundings::kBoth>
 void SparseRowUpdate(ElemT* table,
                      float* state,
                      const int embed_width,
@@ -153,6 +191,9 @@ void SparseRowUpdate(ElemT* table,
   CUEMBED_ASSERT(options.pieces == 1 || options.counts != nullptr);   // several pieces: counts[pieces] on the device
   if (options.num_rows >= 0) CUEMBED_ASSERT(options.num_rows <= options.piece_rows);
   CUEMBED_ASSERT((options.rule == UpdateRule::kSgd) == (state == nullptr));
+  constexpr bool kCanRoundStochastically = !std::is_same<ElemT, float>::value && kRoundings != UpdateRoundings::kNearestOnly;
+  CUEMBED_ASSERT(!options.stochastic_rounding || kCanRoundStochastically);
+  CUEMBED_ASSERT(options.stochastic_rounding || kRoundings != UpdateRoundings::kStochasticOnly);
   if (options.piece_rows == 0 || options.num_rows == 0) return;
   CUEMBED_ASSERT(table != nullptr && ids != nullptr && rows != nullptr);
   const int bytes = detail::UpdateLaneBytes<DevT>(embed_width, table, rows, state, options.rule == UpdateRule::kAdagrad);
@@ -163,12 +204,12 @@ void SparseRowUpdate(ElemT* table,
   counts.last_id = options.last_id;
   DevT* t = reinterpret_cast<DevT*>(table);
   const DevT* g = reinterpret_cast<const DevT*>(rows);
-  constexpr int kMaxN = 16 / static_cast<int>(sizeof(DevT));
-  if (bytes == 16) detail::LaunchSparseRowUpdateRule<DevT, IndexT, kMaxN>(t, state, embed_width, ids, g, options, counts, stream);
-  else if (bytes == 8)
-    detail::LaunchSparseRowUpdateRule<DevT, IndexT, kMaxN / 2>(t, state, embed_width, ids, g, options, counts, stream);
-  else
-    detail::LaunchSparseRowUpdateRule<DevT, IndexT, kMaxN / 4>(t, state, embed_width, ids, g, options, counts, stream);
+  if constexpr (kCanRoundStochastically) {
+    if (options.stochastic_rounding)
+      return detail::LaunchSparseRowUpdateBytes<DevT, IndexT, true>(bytes, t, state, embed_width, ids, g, options, counts, stream);
+  }
+  if constexpr (kRoundings != UpdateRoundings::kStochasticOnly)
+    detail::LaunchSparseRowUpdateBytes<DevT, IndexT, false>(bytes, t, state, embed_width, ids, g, options, counts, stream);
 }
 
 }  // namespace cuembed

@@ -12,7 +12,9 @@
 //     arithmetic and the stores.  Gradient rows are read once, with non-temporal loads (nothing reads them again);
 //     table rows are read and written with plain accesses (the next forward looks the hot ones up again).
 //   * All arithmetic is fp32 with one unfused IEEE operation per step (Arith) and exactly one rounding to the
-//     table's type at the store.
+//     table's type at the store: to nearest, or (kStochastic, 16-bit tables) stochastically with the counter-based bits
+//     of stochastic_rounding.hpp -- one Philox call per 16-byte slice, issued after the slice's loads; the bits depend
+//     on (seed, step, table row, column) only, so every lane width, body and grid stores the same table.
 //   * Row-wise Adagrad reduces the row's sum of squares inside the lane group with a butterfly of cross-lane reads
 //     (`__shfl_xor`): no LDS, no atomics.  Every lane ends with the same bits, so no broadcast is needed.
 //   * The number of valid entries is read on the device (UpdateCounts): the grid is fixed from the capacity, every
@@ -24,6 +26,7 @@
 #define CUEMBED_INCLUDE_SPARSE_UPDATE_KERNELS_HPP_
 
 #include "cuembed/include/gather_reduce_kernels.hpp"
+#include "cuembed/include/stochastic_rounding.hpp"
 
 namespace cuembed {
 
@@ -96,21 +99,64 @@ __device__ __forceinline__ float GroupSum(float v, const int group) {
   return v;
 }
 
-//! w <- w - step * g, one slice (SGD: step = lr; row-wise Adagrad: step = lr / (sqrt(s_r) + eps)).
+//! What stochastic rounding needs besides the fp32 value; an empty kernel argument when it is off.
+template <bool kStochastic>
+struct UpdateRounding {};
+template <>
+struct UpdateRounding<true> {
+  uint64_t seed;
+  uint64_t step;             //!< the step, unless ...
+  const int64_t* step_word;  //!< ... one int64 word on the device holds it (a replayed graph draws fresh bits)
+};
+
+//! The one rounding to the table's type, for the N elements of a slice: to nearest ...
+template <typename ElemT, int N, bool kStochastic>
+struct SliceRounding {
+  __device__ __forceinline__ ElemT operator()(const float x, const int) const { return static_cast<ElemT>(x); }
+};
+//! ... or stochastic, with the N fields of the slice's Philox call that belong to its columns (a slice of N = 8, 4 or
+//! 2 elements never straddles a column group of 8).  Only the N / 2 words that hold them are kept, picked with selects:
+//! nothing here is indexed at run time, so everything stays in registers.
 template <typename ElemT, int N>
-__device__ __forceinline__ Pack<ElemT, N> ScaledStep(const Pack<ElemT, N>& w, const Pack<ElemT, N>& g, const float step) {
+struct SliceRounding<ElemT, N, true> {
+  static_assert(N == 8 || N == 4 || N == 2, "a 16-bit slice is 16, 8 or 4 bytes");
+  uint32_t words[N / 2];
+  __device__ __forceinline__ SliceRounding() {}
+  __device__ __forceinline__ SliceRounding(const uint64_t seed, const uint64_t step, const int64_t row, const int col) {
+    const PhiloxWords p = RoundingWords(seed, step, static_cast<uint64_t>(row), static_cast<uint32_t>(col) >> 3);
+    if constexpr (N == 8) {
+      words[0] = p.w[0], words[1] = p.w[1], words[2] = p.w[2], words[3] = p.w[3];
+    } else if constexpr (N == 4) {
+      const bool upper = (col & 4) != 0;
+      words[0] = upper ? p.w[2] : p.w[0];
+      words[1] = upper ? p.w[3] : p.w[1];
+    } else {
+      const uint32_t lo = (col & 2) != 0 ? p.w[1] : p.w[0];
+      const uint32_t hi = (col & 2) != 0 ? p.w[3] : p.w[2];
+      words[0] = (col & 4) != 0 ? hi : lo;
+    }
+  }
+  __device__ __forceinline__ ElemT operator()(const float x, const int e) const {
+    return StochasticRound<ElemT>(x, (words[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu);
+  }
+};
+
+//! w <- w - step * g, one slice (SGD: step = lr; row-wise Adagrad: step = lr / (sqrt(s_r) + eps)).
+template <typename ElemT, int N, typename RoundT = SliceRounding<ElemT, N, false>>
+__device__ __forceinline__ Pack<ElemT, N> ScaledStep(const Pack<ElemT, N>& w, const Pack<ElemT, N>& g, const float step,
+                                                     const RoundT& round = RoundT()) {
   using A = Arith<float>;
   Pack<ElemT, N> out;
 #pragma unroll
   for (int e = 0; e < N; ++e)
-    out.v[e] = static_cast<ElemT>(A::add(A::widen(w.v[e]), -A::mul(step, A::widen(g.v[e]))));
+    out.v[e] = round(A::add(A::widen(w.v[e]), -A::mul(step, A::widen(g.v[e]))), e);
   return out;
 }
 
 //! Adagrad on one slice: s <- s + g^2 (in place), returns w - lr * g / (sqrt(s) + eps).
-template <typename ElemT, int N>
+template <typename ElemT, int N, typename RoundT = SliceRounding<ElemT, N, false>>
 __device__ __forceinline__ Pack<ElemT, N> AdagradStep(const Pack<ElemT, N>& w, const Pack<ElemT, N>& g, StatePack<N>& s,
-                                                      const float lr, const float eps) {
+                                                      const float lr, const float eps, const RoundT& round = RoundT()) {
   using A = Arith<float>;
   Pack<ElemT, N> out;
 #pragma unroll
@@ -119,7 +165,7 @@ __device__ __forceinline__ Pack<ElemT, N> AdagradStep(const Pack<ElemT, N>& w, c
     const float acc = A::add(s.at(e), A::mul(x, x));
     s.at(e) = acc;
     const float d = A::mul(lr, x) / A::add(sqrtf(acc), eps);
-    out.v[e] = static_cast<ElemT>(A::add(A::widen(w.v[e]), -d));
+    out.v[e] = round(A::add(A::widen(w.v[e]), -d), e);
   }
   return out;
 }
@@ -141,19 +187,28 @@ __device__ __forceinline__ float RowwiseStep(float* state_of_row, const float be
  * Launch: 1-D grid of kUpdateBlockThreads-thread workgroups, `group` (a power of two <= 64) lanes per entry,
  * lanes_per_row = width / N slices per row; kChunks >= 1 needs lanes_per_row <= kChunks * group.
  * Entries: `pieces` blocks of `piece_rows` entries, entry j of piece p valid iff j < count(p).
+ * kStochastic (16-bit ElemT only): the stores round stochastically with the bits of (rounding.seed, step).
  */
-template <typename ElemT, typename IndexT, int N, UpdateRule kRule, int kChunks>
+template <typename ElemT, typename IndexT, int N, UpdateRule kRule, int kChunks, bool kStochastic = false>
 __global__ void __launch_bounds__(kUpdateBlockThreads)
     SparseRowUpdateKernel(const IndexT* __restrict__ ids, const ElemT* __restrict__ rows, ElemT* __restrict__ table,
                           float* __restrict__ state, const int width, const int lanes_per_row, const int group,
                           const int64_t piece_rows, const int pieces, const UpdateCounts counts, const float lr_value,
-                          const float* __restrict__ lr_word, const float eps) {
+                          const float* __restrict__ lr_word, const float eps,
+                          const UpdateRounding<kStochastic> rounding = UpdateRounding<kStochastic>()) {
+  static_assert(!kStochastic || sizeof(ElemT) == 2, "stochastic rounding is for the 16-bit table types");
+  using RoundT = SliceRounding<ElemT, N, kStochastic>;
   constexpr bool kRowwise = kRule == UpdateRule::kRowwiseAdagrad;
   constexpr bool kAdagrad = kRule == UpdateRule::kAdagrad;
   // entries in flight per group: two when a lane holds one slice per entry
   constexpr int kEntries = kChunks == 1 ? 2 : 1;
   constexpr int kSlices = kChunks == 0 ? 1 : kChunks;
   const float lr = lr_word != nullptr ? *lr_word : lr_value;
+  uint64_t seed = 0, round_step = 0;
+  if constexpr (kStochastic) {
+    seed = rounding.seed;
+    round_step = rounding.step_word != nullptr ? static_cast<uint64_t>(*rounding.step_word) : rounding.step;
+  }
   const int lane = static_cast<int>(threadIdx.x) & (group - 1);
   const int groups_per_block = kUpdateBlockThreads / group;
   const int64_t first = static_cast<int64_t>(blockIdx.x) * groups_per_block + static_cast<int>(threadIdx.x) / group;
@@ -187,10 +242,14 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
           if constexpr (kAdagrad) {
             float* s_at = state + RowElems(r[0], width) + c * N;
             StatePack<N> s = StatePack<N>::Load(s_at);
-            StorePack<ElemT, N>(w_row + c * N, AdagradStep(w, g, s, lr, eps));
+            RoundT round;
+            if constexpr (kStochastic) round = RoundT(seed, round_step, r[0], c * N);
+            StorePack<ElemT, N>(w_row + c * N, AdagradStep(w, g, s, lr, eps, round));
             s.Store(s_at);
           } else {
-            StorePack<ElemT, N>(w_row + c * N, ScaledStep(w, g, step));
+            RoundT round;
+            if constexpr (kStochastic) round = RoundT(seed, round_step, r[0], c * N);
+            StorePack<ElemT, N>(w_row + c * N, ScaledStep(w, g, step, round));
           }
         }
       } else {
@@ -198,6 +257,7 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
         StatePack<N> s[kAdagrad ? kEntries : 1][kAdagrad ? kSlices : 1];
         bool has[kEntries][kSlices];
         float row_state[kEntries];
+        RoundT round[kEntries][kSlices];
 #pragma unroll
         for (int u = 0; u < kEntries; ++u) {
           if constexpr (kRowwise) row_state[u] = live[u] ? state[r[u]] : 0.f;
@@ -211,6 +271,14 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
               if constexpr (kAdagrad) s[u][c] = StatePack<N>::Load(state + RowElems(r[u], width) + col);
             }
           }
+        }
+        if constexpr (kStochastic) {
+          // the random bits need nothing that was loaded: they are computed while the loads are in flight
+#pragma unroll
+          for (int u = 0; u < kEntries; ++u)
+#pragma unroll
+            for (int c = 0; c < kSlices; ++c)
+              if (has[u][c]) round[u][c] = RoundT(seed, round_step, r[u], (lane + c * group) * N);
         }
 #pragma unroll
         for (int u = 0; u < kEntries; ++u) {
@@ -230,10 +298,10 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
             const int col = (lane + c * group) * N;
             ElemT* w_at = const_cast<ElemT*>(RowPtr(table, r[u], width)) + col;
             if constexpr (kAdagrad) {
-              StorePack<ElemT, N>(w_at, AdagradStep(w[u][c], g[u][c], s[u][c], lr, eps));
+              StorePack<ElemT, N>(w_at, AdagradStep(w[u][c], g[u][c], s[u][c], lr, eps, round[u][c]));
               s[u][c].Store(state + RowElems(r[u], width) + col);
             } else {
-              StorePack<ElemT, N>(w_at, ScaledStep(w[u][c], g[u][c], step));
+              StorePack<ElemT, N>(w_at, ScaledStep(w[u][c], g[u][c], step, round[u][c]));
             }
           }
         }

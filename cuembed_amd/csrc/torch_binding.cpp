@@ -661,12 +661,15 @@ class CuEmbEmbeddingNode : public torch::autograd::Function<CuEmbEmbeddingNode> 
 // "adagrad" (state fp32 [rows, width]) / "rowwise_adagrad" (state fp32 [rows]).  Valid entries, at most one of:
 // count >= 0 (host-known); counts (device words, int32 / int64: with piece_rows > 0 one per piece of piece_rows
 // entries, else one word for all entries); last_id (one word of ids' dtype, count = last_id + 1); none: every entry.
-// lr_device: one fp32 device word read by the kernel instead of lr.  One launch, nothing read back.
+// lr_device: one fp32 device word read by the kernel instead of lr.  stochastic_rounding (fp16 / bf16 tables): the
+// rounding to the table's type is stochastic with the bits of (seed, step) -- the signed words carry the unsigned 64-bit
+// values -- or of (seed, *step_device), one int64 device word.  One launch, nothing read back.
 void cuembed_sparse_row_update_op(at::Tensor table, const c10::optional<at::Tensor>& state_arg, const at::Tensor& ids,
                                   const at::Tensor& rows, const std::string& rule, const double lr, const double eps,
                                   const c10::optional<at::Tensor>& lr_device, const int64_t count,
                                   const c10::optional<at::Tensor>& counts, const c10::optional<at::Tensor>& last_id,
-                                  const int64_t piece_rows_arg) {
+                                  const int64_t piece_rows_arg, const bool stochastic_rounding, const int64_t seed,
+                                  const int64_t step, const c10::optional<at::Tensor>& step_device) {
   CheckGpu(table, "table");
   CheckGpu(ids, "ids");
   CheckGpu(rows, "rows");
@@ -719,8 +722,30 @@ void cuembed_sparse_row_update_op(at::Tensor table, const c10::optional<at::Tens
     CheckGpu(*lr_device, "lr_device");
     TORCH_CHECK(lr_device->scalar_type() == at::kFloat && lr_device->numel() == 1, "cuembed_pyt: lr_device must be one float32 word");
   }
+  const bool has_step = step_device.has_value() && step_device->defined();
+  if (stochastic_rounding) {
+    TORCH_CHECK(table.scalar_type() != at::kFloat,
+                "cuembed_pyt: stochastic_rounding is for float16 / bfloat16 tables: a float32 table is not rounded");
+    if (has_step) {
+      CheckGpu(*step_device, "step_device");
+      TORCH_CHECK(step_device->scalar_type() == at::kLong && step_device->numel() == 1 &&
+                      step_device->device() == table.device(),
+                  "cuembed_pyt: step_device must be one int64 word on the table's device");
+    }
+  }
   if (ids.numel() == 0) return;
   const at::DeviceGuard guard(table.device());
+  if (stochastic_rounding) {
+    ::cuembed_sparse_row_update_stochastic(
+        table.data_ptr(), elem, static_cast<int>(table.size(1)),
+        state.defined() ? static_cast<float*>(state.data_ptr()) : nullptr, code, Ptr(ids), idx, Ptr(rows), piece_rows,
+        pieces, num_rows, has_counts ? counts->data_ptr() : nullptr, words64,
+        has_last ? last_id->data_ptr() : nullptr, static_cast<float>(lr),
+        has_lr ? static_cast<const float*>(lr_device->data_ptr()) : nullptr, static_cast<float>(eps),
+        static_cast<uint64_t>(seed), static_cast<uint64_t>(step),
+        has_step ? static_cast<const int64_t*>(step_device->data_ptr()) : nullptr, CurrentStream(table));
+    return;
+  }
   ::cuembed_sparse_row_update(table.data_ptr(), elem, static_cast<int>(table.size(1)),
                               state.defined() ? static_cast<float*>(state.data_ptr()) : nullptr, code, Ptr(ids), idx,
                               Ptr(rows), piece_rows, pieces, num_rows, has_counts ? counts->data_ptr() : nullptr, words64,
@@ -1005,7 +1030,8 @@ TORCH_LIBRARY(cuembed_pyt, m) {
       "Tensor(b!) out_rows, Tensor(c!)? tail, Tensor(d!) flag, Tensor(e!)? count) -> ()");
   m.def(
       "cuembed_sparse_row_update_(Tensor(a!) table, Tensor(b!)? state, Tensor ids, Tensor rows, str rule, float lr, "
-      "float eps, Tensor? lr_device, int count, Tensor? counts, Tensor? last_id, int piece_rows) -> ()");
+      "float eps, Tensor? lr_device, int count, Tensor? counts, Tensor? last_id, int piece_rows, bool "
+      "stochastic_rounding=False, int seed=0, int step=0, Tensor? step_device=None) -> ()");
   // 8-bit row-wise quantized tables (torch's fused layout), inference only
   m.def("quantize_rows(Tensor table) -> Tensor");
   m.def("dequantize_rows(Tensor qtable, Tensor? ids, ScalarType dtype) -> Tensor");

@@ -70,8 +70,8 @@ def _define_python_ops():
     _lib.define("cuembed_bag_order_by_length(Tensor offsets, int max_length) -> Tensor")
     _lib.define("cuembed_decide_row_loads(Tensor indices, int table_bytes, Tensor(a!) decision) -> ()")
     _lib.define("cuembed_sparse_row_update_(Tensor(a!) table, Tensor(b!)? state, Tensor ids, Tensor rows, str rule,"
-                " float lr, float eps, Tensor? lr_device, int count, Tensor? counts, Tensor? last_id, int piece_rows)"
-                " -> ()")
+                " float lr, float eps, Tensor? lr_device, int count, Tensor? counts, Tensor? last_id, int piece_rows,"
+                " bool stochastic_rounding=False, int seed=0, int step=0, Tensor? step_device=None) -> ()")
     _lib.define("quantize_rows(Tensor table) -> Tensor")
     _lib.define("dequantize_rows(Tensor qtable, Tensor? ids, ScalarType dtype) -> Tensor")
     _lib.define("cuemb_embedding_quantized(Tensor qtable, Tensor indices, Tensor? offsets, Tensor? weights, str mode,"
@@ -243,7 +243,8 @@ def _weight_grad_impl(params, indices, offsets, y_grad):
                                       offsets=offsets.contiguous(), batch_size=offsets.numel() - 1, num_hots=0)
 
 
-def _sparse_row_update_impl(table, state, ids, rows, rule, lr, eps, lr_device, count, counts, last_id, piece_rows):
+def _sparse_row_update_impl(table, state, ids, rows, rule, lr, eps, lr_device, count, counts, last_id, piece_rows,
+                            stochastic_rounding=False, seed=0, step=0, step_device=None):
     _require((count >= 0) + (counts is not None) + (last_id is not None) <= 1,
              "give at most one of count, counts and last_id")
     if counts is not None and piece_rows > 0:
@@ -254,6 +255,9 @@ def _sparse_row_update_impl(table, state, ids, rows, rule, lr, eps, lr_device, c
         kw = dict(last_id=last_id)
     else:
         kw = dict(count=count if count >= 0 else None)
+    if stochastic_rounding:     # (the schema's ints are signed 64-bit words: the same bits as the unsigned seed / step)
+        kw.update(stochastic_rounding=True, seed=seed % 2 ** 64,
+                  step=step % 2 ** 64 if step_device is None else step_device)
     _ops.sparse_row_update(table, ids, rows, rule=rule, lr=lr if lr_device is None else lr_device, state=state, eps=eps,
                            **kw)
 
@@ -314,18 +318,30 @@ cuembed_embedding_forward = torch.ops.cuembed_pyt.cuembed_embedding_forward
 cuembed_embedding_backward = torch.ops.cuembed_pyt.cuembed_embedding_backward
 
 
+def _signed_word(name, v):
+    """An int in [0, 2**64) as the signed 64-bit word of the same bits (what a torch op's `int` carries)."""
+    if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 64:
+        raise ValueError("%s must be an int in [0, 2**64), got %r" % (name, v))
+    return v - 2 ** 64 if v >= 2 ** 63 else v
+
+
 def cuembed_sparse_row_update_(table, ids, rows, rule, lr, state=None, eps=1e-8, count=None, last_id=None, counts=None,
-                               piece_rows=None):
+                               piece_rows=None, stochastic_rounding=False, seed=0, step=0):
     """cuembed_amd.ops.sparse_row_update as the torch op cuembed_pyt::cuembed_sparse_row_update_ (in place on `table` and
     `state`; traces under torch.compile).  Same arguments."""
     lr_device = lr if isinstance(lr, torch.Tensor) else None
     word = count if isinstance(count, torch.Tensor) else None
     if word is not None and counts is not None:
         raise ValueError("give at most one of count=, last_id= and counts=")
+    args = (table, state, ids, rows, rule, 0.0 if lr_device is not None else float(lr), float(eps), lr_device,
+            -1 if (count is None or word is not None) else int(count), counts if word is None else word, last_id,
+            0 if piece_rows is None else int(piece_rows))
+    if not stochastic_rounding:
+        torch.ops.cuembed_pyt.cuembed_sparse_row_update_(*args)
+        return
+    step_device = step if isinstance(step, torch.Tensor) else None
     torch.ops.cuembed_pyt.cuembed_sparse_row_update_(
-        table, state, ids, rows, rule, 0.0 if lr_device is not None else float(lr), float(eps), lr_device,
-        -1 if (count is None or word is not None) else int(count), counts if word is None else word, last_id,
-        0 if piece_rows is None else int(piece_rows))
+        *args, True, _signed_word("seed", seed), 0 if step_device is not None else _signed_word("step", step), step_device)
 
 
 def quantize_rows(table):
@@ -658,7 +674,8 @@ def _(indices, table_bytes, decision):
 
 
 @torch.library.register_fake("cuembed_pyt::cuembed_sparse_row_update_")
-def _(table, state, ids, rows, rule, lr, eps, lr_device=None, count=-1, counts=None, last_id=None, piece_rows=0):
+def _(table, state, ids, rows, rule, lr, eps, lr_device=None, count=-1, counts=None, last_id=None, piece_rows=0,
+      stochastic_rounding=False, seed=0, step=0, step_device=None):
     return None
 
 

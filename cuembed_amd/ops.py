@@ -713,8 +713,37 @@ def sparse_row_update_launch_shape(elem_dtype, embed_width, total_entries, compu
     return dict(lane_bytes=out[0], lanes_per_row=out[1], lanes_per_entry=out[2], slices_per_lane=out[3], grid=out[4])
 
 
+def stochastic_rounding_words(seed, step, row, column_group):
+    """The four Philox4x32-10 output words that serve columns [8 * column_group, 8 * column_group + 8) of table row
+    `row` at (seed, step) under sparse_row_update(stochastic_rounding=True): column c takes half (c % 8) % 2 (low half
+    first) of word (c % 8) / 2.  Host arithmetic only."""
+    out = (ctypes.c_uint32 * 4)()
+    _lib.lib().cuembed_stochastic_rounding_words(int(seed), int(step), int(row), int(column_group), out)
+    return tuple(out)
+
+
+def stochastic_round(elem_dtype, x, r16):
+    """The 16-bit pattern the fp32 value x is rounded to with the random field r16, for torch.float16 / torch.bfloat16
+    tables (the rule of sparse_row_update(stochastic_rounding=True)).  Host arithmetic only."""
+    if elem_dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError("stochastic rounding is for float16 / bfloat16 tables, got %s" % (elem_dtype,))
+    return int(_lib.lib().cuembed_stochastic_round(_ELEM[elem_dtype], float(x), int(r16)))
+
+
+def stochastic_round_array(elem_dtype, x, r16):
+    """stochastic_round for CPU tensors: x float32 [n], r16 int32 [n] (fields in [0, 65536)) -> the patterns as int32 [n]."""
+    if elem_dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError("stochastic rounding is for float16 / bfloat16 tables, got %s" % (elem_dtype,))
+    if x.dtype != torch.float32 or r16.dtype != torch.int32 or x.is_cuda or r16.is_cuda or x.shape != r16.shape:
+        raise TypeError("x must be a float32 and r16 an int32 CPU tensor of the same shape")
+    x, r16 = x.contiguous(), r16.contiguous()
+    out = torch.empty(x.shape, dtype=torch.int16)
+    _lib.lib().cuembed_stochastic_round_array(_ELEM[elem_dtype], x.data_ptr(), r16.data_ptr(), x.numel(), out.data_ptr())
+    return out.to(torch.int32) & 0xFFFF
+
+
 def sparse_row_update(table, ids, rows, *, rule, lr, state=None, eps=1e-8, count=None, last_id=None, counts=None,
-                      piece_rows=None):
+                      piece_rows=None, stochastic_rounding=False, seed=0, step=0):
     """Sparse optimizer step (cuembed::SparseRowUpdate): for every valid entry k, table[ids[k], :] and the state of
     that row are updated IN PLACE from the gradient row rows[k, :]; rows that no valid entry names are neither read
     nor written.  fp32 arithmetic whatever the table's dtype, one rounding to it at the store.  Returns None.
@@ -741,7 +770,15 @@ def sparse_row_update(table, ids, rows, *, rule, lr, state=None, eps=1e-8, count
     compute_compressed_grad_indices_blocked + embedding_backward(sample_blocks=...)).  The sample-blocked UNCOALESCED
     gradient (one entry per (block, row)) is not accepted -- use one of the coalesced kinds.
 
-    lr: a float, or a one-element fp32 device tensor read by the kernel (a captured graph then follows a schedule)."""
+    lr: a float, or a one-element fp32 device tensor read by the kernel (a captured graph then follows a schedule).
+
+    stochastic_rounding=True (float16 / bfloat16 tables): the one rounding to the table's dtype goes up or down with the
+    probability of the fp32 value's position between its two neighbours, so that updates below half a unit in the last
+    place survive on average instead of being rounded away at every step.  The random bits are a pure function of
+    (seed, step, table row, column) -- Philox4x32-10, see stochastic_rounding_words / stochastic_round -- whatever the
+    alignment, the launch shape or the count source: keep `seed` (an int in [0, 2**64)) for a run and give every call
+    its own `step`, an int in [0, 2**64) or a one-element int64 device tensor that the kernel reads (advance it on the
+    device and a replayed graph draws fresh bits).  The fp32 arithmetic and the state are the same as without."""
     for name, t in (("table", table), ("ids", ids), ("rows", rows)):
         if not isinstance(t, torch.Tensor):
             raise TypeError("%s must be a torch.Tensor" % name)
@@ -797,6 +834,20 @@ def sparse_row_update(table, ids, rows, *, rule, lr, state=None, eps=1e-8, count
         if num_rows < 0 or num_rows > n:
             raise ValueError("count must be in [0, ids.numel()]")
         piece_rows = n
+    step_word = None
+    if stochastic_rounding:
+        if table.dtype == torch.float32:
+            raise TypeError("stochastic_rounding is for float16 / bfloat16 tables: a float32 table is not rounded")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must be an int in [0, 2**64), got %r" % (seed,))
+        if isinstance(step, torch.Tensor):
+            if step.dtype != torch.int64 or step.numel() != 1:
+                raise TypeError("a device-side step must be a one-element int64 tensor")
+            step_word, step = step, 0
+        elif isinstance(step, bool) or not isinstance(step, int) or not 0 <= step < 2 ** 64:
+            raise ValueError("step must be an int in [0, 2**64) or a one-element int64 device tensor, got %r" % (step,))
+        if step_word is not None and step_word.device != table.device:
+            raise ValueError("step must be on the table's device (%s), got %s" % (table.device, step_word.device))
     lr_word = None
     if isinstance(lr, torch.Tensor):
         if lr.dtype != torch.float32 or lr.numel() != 1:
@@ -805,12 +856,18 @@ def sparse_row_update(table, ids, rows, *, rule, lr, state=None, eps=1e-8, count
     _check_dev("table", table)
     dev = table.device
     for name, t in (("ids", ids), ("rows", rows), ("state", state), ("count", count_words), ("last_id", last_id),
-                    ("lr", lr_word)):
+                    ("lr", lr_word), ("step", step_word)):
         if t is not None:
             _check_dev(name, t, dev)
     if n == 0:
         return None
     with torch.cuda.device(dev):
+        if stochastic_rounding:
+            _lib.lib().cuembed_sparse_row_update_stochastic(
+                _ptr(table), et, width, _ptr(state), UPDATE_RULES[rule], _ptr(ids), it, _ptr(rows), int(piece_rows),
+                int(pieces), int(num_rows), _ptr(count_words), int(words64), _ptr(last_id), float(lr), _ptr(lr_word),
+                float(eps), seed, step, _ptr(step_word), _stream(table))
+            return None
         _lib.lib().cuembed_sparse_row_update(_ptr(table), et, width, _ptr(state), UPDATE_RULES[rule], _ptr(ids), it,
                                              _ptr(rows), int(piece_rows), int(pieces), int(num_rows), _ptr(count_words),
                                              int(words64), _ptr(last_id), float(lr), _ptr(lr_word), float(eps),

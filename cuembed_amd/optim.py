@@ -22,7 +22,14 @@ Rules (fp32 arithmetic whatever the table's dtype, one rounding to it at the sto
     "adagrad"          s <- s + g^2;  w <- w - lr * g / (sqrt(s) + eps)      (torch.optim.Adagrad, lr_decay = 0,
                                                                               weight_decay = 0); fp32 state [rows, W]
     "rowwise_adagrad"  s_r <- s_r + mean_j(g_j^2);  w_j <- w_j - lr * g_j / (sqrt(s_r) + eps);  fp32 state [rows]
-No momentum, weight decay, lr_decay or stochastic rounding.
+No momentum, weight decay or lr_decay.
+
+Stochastic rounding (stochastic_rounding=True, seed=...; float16 / bfloat16 tables): the rounding to the table's dtype
+goes up or down with the probability of the fp32 value's position between its neighbours, so that updates below half a
+unit in the last place are kept on average instead of being rounded away at every step.  The bits are a pure function
+of (seed, step, table row, column); the step count lives on the device (SparseUpdater.rounding_step, advanced in place
+after every apply, so a captured graph draws fresh bits at every replay) or in the optimizer's state
+(state[p]["rounding_step"], carried by state_dict()).
 """
 import torch
 
@@ -44,9 +51,13 @@ class SparseUpdater:
     optimizer state (`.state`: None, fp32 [num_categories, width] or fp32 [num_categories]).
 
     lr is a float or a one-element fp32 device tensor that the kernel reads (fill it to follow a schedule inside a
-    captured graph); assign `.lr` to change it."""
+    captured graph); assign `.lr` to change it.
 
-    def __init__(self, table, rule, lr, eps=1e-8, initial_accumulator_value=0.0):
+    stochastic_rounding=True (16-bit tables): every apply rounds stochastically with the bits of (seed, rounding_step),
+    where `.rounding_step` is an int64 device word that starts at 0 and is advanced on the device after every apply --
+    nothing is read back, so backward_and_apply stays capturable."""
+
+    def __init__(self, table, rule, lr, eps=1e-8, initial_accumulator_value=0.0, stochastic_rounding=False, seed=0):
         if not isinstance(table, torch.Tensor) or table.dim() != 2:
             raise TypeError("table must be a [num_categories, width] tensor")
         if rule not in _ops.UPDATE_RULES:
@@ -61,12 +72,24 @@ class SparseUpdater:
         self.eps = float(eps)
         self.state = _new_state(table, rule, initial_accumulator_value)
         self._buffers = {}
+        self.stochastic_rounding = bool(stochastic_rounding)
+        self.seed = seed
+        self.rounding_step = None
+        if self.stochastic_rounding:
+            _check_rounding(table, seed)
+            self.rounding_step = torch.zeros((1,), dtype=torch.int64, device=table.device)
 
     def apply(self, ids, rows, count=None, last_id=None, counts=None, piece_rows=None):
         """table[ids[k]] (and its state) <- rule, for the valid entries of a COALESCED gradient (ids, rows): see
         cuembed_amd.ops.sparse_row_update for the count sources.  Nothing is read back."""
+        if not self.stochastic_rounding:
+            _ops.sparse_row_update(self.table, ids, rows, rule=self.rule, lr=self.lr, state=self.state, eps=self.eps,
+                                   count=count, last_id=last_id, counts=counts, piece_rows=piece_rows)
+            return
         _ops.sparse_row_update(self.table, ids, rows, rule=self.rule, lr=self.lr, state=self.state, eps=self.eps,
-                               count=count, last_id=last_id, counts=counts, piece_rows=piece_rows)
+                               count=count, last_id=last_id, counts=counts, piece_rows=piece_rows,
+                               stochastic_rounding=True, seed=self.seed, step=self.rounding_step)
+        self.rounding_step.add_(1)      # on the device, after the kernel in stream order: one apply = one step
 
     def _step_buffers(self, nnz, dtype, index_dtype, weighted):
         """Gradient rows / ids of min(nnz, num_categories) entries and the sort's workspace, kept between calls."""
@@ -114,6 +137,13 @@ class SparseUpdater:
         self.apply(b["ids"], b["rows"], last_id=remap[nnz - 1:])
 
 
+def _check_rounding(table, seed):
+    if table.dtype == torch.float32:
+        raise TypeError("stochastic_rounding is for float16 / bfloat16 tables: a float32 table is not rounded")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be an int in [0, 2**64), got %r" % (seed,))
+
+
 def _is_coalesced(g):
     """Whether the sparse gradient holds one entry per row.  Autograd drops the is_coalesced flag when it stores a
     sparse gradient in .grad, so a tensor without the flag is looked at: strictly ascending row ids are what
@@ -132,19 +162,25 @@ def _is_coalesced(g):
 
 class _SparseOptimizer(torch.optim.Optimizer):
     """Common part of the torch.optim front ends: one SparseUpdater-style state tensor per parameter, kept in
-    self.state[p]["sum"] so that state_dict() / load_state_dict() carry it."""
+    self.state[p]["sum"] so that state_dict() / load_state_dict() carry it.  With stochastic_rounding=True the number of
+    steps taken on a parameter is self.state[p]["rounding_step"] (a Python int: step() reads the gradient's size back
+    anyway), so a resumed optimizer continues the same bit stream."""
     _rule = None
 
-    def __init__(self, params, lr, eps=1e-8, initial_accumulator_value=0.0):
+    def __init__(self, params, lr, eps=1e-8, initial_accumulator_value=0.0, stochastic_rounding=False, seed=0):
         if not isinstance(lr, torch.Tensor) and lr < 0.0:
             raise ValueError("invalid learning rate: %r" % (lr,))
         if eps < 0.0 or initial_accumulator_value < 0.0:
             raise ValueError("eps and initial_accumulator_value must not be negative")
-        super().__init__(params, dict(lr=lr, eps=eps, initial_accumulator_value=initial_accumulator_value))
+        super().__init__(params, dict(lr=lr, eps=eps, initial_accumulator_value=initial_accumulator_value,
+                                      stochastic_rounding=bool(stochastic_rounding), seed=seed))
         for group in self.param_groups:
             for p in group["params"]:
                 if p.dim() != 2:
                     raise ValueError("every parameter must be a [num_categories, width] table")
+                if group["stochastic_rounding"]:
+                    _check_rounding(p, group["seed"])
+                    self.state[p]["rounding_step"] = 0
                 if self._rule != "sgd":
                     self.state[p]["sum"] = _new_state(p, self._rule, group["initial_accumulator_value"])
 
@@ -158,6 +194,8 @@ class _SparseOptimizer(torch.optim.Optimizer):
         for i, p in zip(ids, params):
             if i in saved and "sum" in saved[i]:
                 self.state[p]["sum"] = saved[i]["sum"].detach().to(device=p.device, dtype=torch.float32).clone()
+            if i in saved and "rounding_step" in saved[i]:
+                self.state[p]["rounding_step"] = int(saved[i]["rounding_step"])
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -180,8 +218,15 @@ class _SparseOptimizer(torch.optim.Optimizer):
                 if g.sparse_dim() != 1 or g.dense_dim() != 1:
                     raise ValueError("the gradient must have one sparse (row) and one dense (column) dimension")
                 state = self.state[p].get("sum") if self._rule != "sgd" else None
+                if not group.get("stochastic_rounding", False):
+                    _ops.sparse_row_update(p.data, g._indices()[0].contiguous(), g._values().contiguous(),
+                                           rule=self._rule, lr=group["lr"], state=state, eps=group["eps"])
+                    continue
+                step = int(self.state[p].get("rounding_step", 0))
                 _ops.sparse_row_update(p.data, g._indices()[0].contiguous(), g._values().contiguous(), rule=self._rule,
-                                       lr=group["lr"], state=state, eps=group["eps"])
+                                       lr=group["lr"], state=state, eps=group["eps"], stochastic_rounding=True,
+                                       seed=group["seed"], step=step)
+                self.state[p]["rounding_step"] = step + 1
         return loss
 
 
@@ -189,8 +234,8 @@ class SparseSGD(_SparseOptimizer):
     """w <- w - lr * g on the rows of a coalesced sparse gradient (torch.optim.SGD without momentum / weight decay)."""
     _rule = "sgd"
 
-    def __init__(self, params, lr):
-        super().__init__(params, lr)
+    def __init__(self, params, lr, stochastic_rounding=False, seed=0):
+        super().__init__(params, lr, stochastic_rounding=stochastic_rounding, seed=seed)
 
 
 class SparseAdagrad(_SparseOptimizer):

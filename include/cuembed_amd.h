@@ -508,6 +508,33 @@ void cuembed_sparse_row_update(void* table, int elem_type, int embed_width, floa
  * loop), out[4] = grid size.  compute_units <= 0: the current device. */
 void cuembed_sparse_row_update_launch_shape(int elem_type, int embed_width, int64_t total_entries, int compute_units,
                                             int* out);
+/* cuembed_sparse_row_update with STOCHASTIC ROUNDING of the one rounding to the table's type (elem_type CUEMBED_F16 or
+ * CUEMBED_BF16; the fp32 arithmetic and the fp32 state are those of cuembed_sparse_row_update).  An update smaller than
+ * half a unit in the last place of a 16-bit table is otherwise rounded away at every step.  The fp32 value x is rounded
+ * away from zero with the probability of its position between its two neighbours, decided by a 16-bit random field r:
+ *   fp16: q = the spacing of fp16 at |x| (2^(e-10) for |x| >= 2^-14, else 2^-24), m = |x| / q, i = floor(m),
+ *         t = floor((m - i) * 2^13); away from zero iff t + (r & 0x1FFF) >= 2^13; the result is +-(i + up) * q;
+ *   bf16: r is added to the low 16 bits of x's pattern, which are then dropped.
+ * A representable x is unchanged for every r, a result past the largest finite value is +-inf, inf and NaN convert as
+ * usual, the sign of zero is kept.  The fields come from Philox4x32-10: one call serves columns [8 * G, 8 * G + 8) of
+ * table row R, with counter (R low 32, R high 32, G, step low 32) and key (seed low 32, seed high 32 ^ step high 32);
+ * column c takes half (c % 8) % 2 (low half first) of output word (c % 8) / 2.  The bits therefore depend on (seed, step,
+ * table row, column) only -- not on alignment, the launch shape, the entry's position or the count source: give every
+ * call of a run the same seed and its own step.  step_device != NULL: the step is read from that int64 device word
+ * instead of `step` (advance it on the device and a replayed graph draws fresh bits).  One launch, no read-back. */
+void cuembed_sparse_row_update_stochastic(void* table, int elem_type, int embed_width, float* state, int rule,
+                                          const void* ids, int index_type, const void* rows, int64_t piece_rows,
+                                          int pieces, int64_t num_rows, const void* counts, int counts_are_int64,
+                                          const void* last_id, float lr, const float* lr_device, float eps,
+                                          uint64_t seed, uint64_t step, const int64_t* step_device,
+                                          cuembed_stream_t stream);
+/* The specification above as host code (no launch, no device): out[0..3] = the four Philox output words of the call
+ * for (seed, step, row, column_group) ... */
+void cuembed_stochastic_rounding_words(uint64_t seed, uint64_t step, int64_t row, uint32_t column_group, uint32_t* out);
+/* ... and the 16-bit pattern that x is rounded to with the field r16 (elem_type CUEMBED_F16 or CUEMBED_BF16). */
+uint16_t cuembed_stochastic_round(int elem_type, float x, uint32_t r16);
+/* The same for n values on the host: out[i] = cuembed_stochastic_round(elem_type, x[i], r16[i]). */
+void cuembed_stochastic_round_array(int elem_type, const float* x, const uint32_t* r16, int64_t n, uint16_t* out);
 /* ---- 8-bit row-wise quantized tables (extension; inference only) ---------------------------
  * The format is PyTorch's fused 8-bit row-wise layout (quantized::embedding_bag_byte_prepack): a row of embed_width
  * values is embed_width + 8 bytes -- embed_width uint8 codes, the row's fp32 scale, its fp32 bias, little endian --
