@@ -21,7 +21,8 @@ from .ops import (CONCAT, MEAN, SUM, ComputeCompressedGradIndices, EmbeddingBack
                   set_forward_reduction_order, set_forward_row_load_policy, get_forward_row_load_policy, set_forward_wide_load, transpose,
                   transpose_fixed_hotness,
                   transpose_workspace_bytes, sparse_row_update, sparse_row_update_launch_shape, UPDATE_RULES,
-                  stochastic_rounding_words, stochastic_round, stochastic_round_array)
+                  stochastic_rounding_words, stochastic_round, stochastic_round_array, sparse_row_adam,
+                  adam_bias_factor, new_adam_clock, adam_clock_advance, ADAM_RULES)
 from .quantized import (QuantizedEmbeddingBag, dequantize_rows, embedding_forward_quantized,  # noqa: F401
                         quantize_rows, quantized_forward_launch_shape, quantized_row_bytes)
 

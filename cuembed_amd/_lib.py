@@ -133,6 +133,14 @@ def _declare(L):
     L.cuembed_stochastic_round_array.argtypes = [_I, _VP, _VP, _L, _VP]
     L.cuembed_sparse_row_update_launch_shape.restype = None
     L.cuembed_sparse_row_update_launch_shape.argtypes = [_I, _I, _L, _I, ctypes.POINTER(_I)]
+    _F = ctypes.c_float
+    _adam = [_VP, _I, _I, _VP, _VP, _I, _VP, _I, _VP, _L, _I, _L, _VP, _I, _VP, _F, _VP, _F, _VP, _F, _F, _F, _F, _F, _F]
+    L.cuembed_sparse_row_adam.restype = None
+    L.cuembed_sparse_row_adam.argtypes = _adam + [_VP]
+    L.cuembed_sparse_row_adam_stochastic.restype = None
+    L.cuembed_sparse_row_adam_stochastic.argtypes = _adam + [_U, _U, _VP, _VP]
+    L.cuembed_adam_clock_advance.restype = None
+    L.cuembed_adam_clock_advance.argtypes = [_VP, _VP, ctypes.c_double, ctypes.c_double, _VP]
     L.cuembed_quantized_row_bytes.restype = _L
     L.cuembed_quantized_row_bytes.argtypes = [_I]
     L.cuembed_quantize_rows.restype = None

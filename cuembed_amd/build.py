@@ -21,7 +21,8 @@ LIB_PATH = os.path.join(LIB_DIR, "libcuembed_amd.so")
 HARNESS_PATH = os.path.join(LIB_DIR, "libcuembed_harness.so")
 OBJ_DIR = os.path.join(PKG, "build")
 UNITS = ["c_api_forward.hip", "c_api_backward.hip", "c_api_transforms.hip", "c_api_exchange.hip",
-         "c_api_optimizer.hip", "c_api_optimizer_stochastic.hip", "c_api_quantized.hip"]
+         "c_api_optimizer.hip", "c_api_optimizer_stochastic.hip", "c_api_optimizer_adam.hip",
+         "c_api_optimizer_adam_stochastic.hip", "c_api_quantized.hip"]
 ARCH = "gfx950"
 
 HIPCC_FLAGS = [
@@ -233,6 +234,30 @@ def build_stochastic_rounding_test(force=False):
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed for tests/cpp/stochastic_rounding_kat.hip:\n" + r.stdout)
+    with open(stamp, "w") as f:
+        f.write(digest)
+    return exe
+
+
+def build_sparse_adam_test(force=False):
+    """Compiles tests/cpp/sparse_adam_kat.hip: cuembed::SparseRowAdam and cuembed::AdamClockAdvance through the
+    header-only API against expected values written in the source (exactly representable data).  Needs a GPU to RUN
+    (tests/test_gpu_cpp_sparse_adam.py)."""
+    src = os.path.join(ROOT, "tests", "cpp", "sparse_adam_kat.hip")
+    exe = os.path.join(ROOT, "tests", "cpp", "sparse_adam_kat")
+    stamp = exe + ".stamp"
+    deps = [src]
+    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
+        deps += [os.path.join(dirpath, f) for f in files]
+    digest = _digest_files(deps)
+    if not force and os.path.exists(exe) and os.path.exists(stamp):
+        with open(stamp) as f:
+            if f.read().strip() == digest:
+                return exe
+    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-I" + CSRC, src, "-o", exe]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("hipcc failed for tests/cpp/sparse_adam_kat.hip:\n" + r.stdout)
     with open(stamp, "w") as f:
         f.write(digest)
     return exe

@@ -52,10 +52,11 @@ enum class UpdateRoundings { kBoth, kNearestOnly, kStochasticOnly };
 
 namespace detail {
 
-//! Bytes per lane: the widest of 16 / 8 / 4 that the row size, the three data pointers and (Adagrad) the state allow.
+//! Bytes per lane: the widest of 16 / 8 / 4 that the row size, the three data pointers and the per-element state
+//! (Adagrad's accumulator; Adam's first moment and, as `state2`, its second) allow.
 template <typename ElemT>
 inline int UpdateLaneBytes(const int embed_width, const void* table, const void* rows, const float* state,
-                           const bool state_per_element) {
+                           const bool state_per_element, const float* state2 = nullptr) {
   const size_t row_bytes = static_cast<size_t>(embed_width) * sizeof(ElemT);
   CUEMBED_ASSERT(embed_width > 0);
   CUEMBED_ASSERT(row_bytes % 4 == 0);
@@ -65,8 +66,9 @@ inline int UpdateLaneBytes(const int embed_width, const void* table, const void*
   if (state_per_element) {
     // a lane's N = bytes / sizeof(ElemT) state elements move as fp32 packs of min(N, 4)
     const auto state_align = [](int b) { const int n = b / static_cast<int>(sizeof(ElemT)); return 4 * (n < 4 ? n : 4); };
-    while (bytes > 4 && reinterpret_cast<uintptr_t>(state) % state_align(bytes) != 0) bytes /= 2;
-    CUEMBED_ASSERT(reinterpret_cast<uintptr_t>(state) % state_align(bytes) == 0);
+    const uintptr_t state_bits = reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(state2);
+    while (bytes > 4 && state_bits % state_align(bytes) != 0) bytes /= 2;
+    CUEMBED_ASSERT(state_bits % state_align(bytes) == 0);
   }
   return bytes;
 }

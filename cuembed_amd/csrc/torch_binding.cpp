@@ -754,6 +754,113 @@ void cuembed_sparse_row_update_op(at::Tensor table, const c10::optional<at::Tens
                               static_cast<float>(eps), CurrentStream(table));
 }
 
+// Extension (cuembed::SparseRowAdam): the sparse Adam step on a compressed gradient, in place on the table and both
+// moments (exp_avg fp32 [rows, width]; exp_avg_sq the same, or fp32 [rows] with rowwise).  bias_factor is
+// sqrt(1 - beta2^t) / (1 - beta1^t) of the step (1: no correction); lr_device / bias_factor_device: one fp32 device word
+// read by the kernel instead.  The count sources and stochastic rounding are cuembed_sparse_row_update_'s.  1 - beta is
+// formed in double and rounded once.  One launch, nothing read back.
+void cuembed_sparse_row_adam_op(at::Tensor table, at::Tensor exp_avg, at::Tensor exp_avg_sq, const at::Tensor& ids,
+                                const at::Tensor& rows, const bool rowwise, const double lr, const double bias_factor,
+                                const double beta1, const double beta2, const double eps, const double weight_decay,
+                                const c10::optional<at::Tensor>& lr_device,
+                                const c10::optional<at::Tensor>& bias_factor_device, const int64_t count,
+                                const c10::optional<at::Tensor>& counts, const c10::optional<at::Tensor>& last_id,
+                                const int64_t piece_rows_arg, const bool stochastic_rounding, const int64_t seed,
+                                const int64_t step, const c10::optional<at::Tensor>& step_device) {
+  CheckGpu(table, "table");
+  CheckGpu(ids, "ids");
+  CheckGpu(rows, "rows");
+  const int elem = ElemCode(table, "table");
+  const int idx = IndexCode(ids, "ids");
+  TORCH_CHECK(rows.scalar_type() == table.scalar_type(), "cuembed_pyt: rows must have the table's dtype");
+  TORCH_CHECK(table.dim() == 2 && rows.dim() == 2 && rows.size(1) == table.size(1) && ids.dim() == 1 &&
+                  rows.size(0) == ids.numel() && table.is_contiguous() && rows.is_contiguous() && ids.is_contiguous(),
+              "cuembed_pyt: table [rows, width], rows [entries, width] and ids [entries] must be contiguous and agree");
+  TORCH_CHECK((table.size(1) * table.element_size()) % 4 == 0, "cuembed_pyt: the row size must be a multiple of 4 bytes");
+  TORCH_CHECK(exp_avg.defined() && exp_avg.is_cuda() && exp_avg.scalar_type() == at::kFloat && exp_avg.is_contiguous() &&
+                  exp_avg.sizes() == table.sizes(),
+              "cuembed_pyt: exp_avg must be a contiguous float32 GPU tensor of the table's shape");
+  TORCH_CHECK(exp_avg_sq.defined() && exp_avg_sq.is_cuda() && exp_avg_sq.scalar_type() == at::kFloat &&
+                  exp_avg_sq.is_contiguous() &&
+                  (rowwise ? (exp_avg_sq.dim() == 1 && exp_avg_sq.size(0) == table.size(0))
+                           : exp_avg_sq.sizes() == table.sizes()),
+              "cuembed_pyt: exp_avg_sq must be a contiguous float32 GPU tensor, [rows, width] or, rowwise, [rows]");
+  TORCH_CHECK(exp_avg.device() == table.device() && exp_avg_sq.device() == table.device(),
+              "cuembed_pyt: exp_avg and exp_avg_sq must be on the table's device");
+  // a lane moves at least 4 bytes of the table, so 4 / sizeof(element) moment words at a time
+  const uintptr_t state_align = 4 * (4 / static_cast<uintptr_t>(table.element_size()));
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(exp_avg.data_ptr()) % state_align == 0, "cuembed_pyt: exp_avg must be ",
+              state_align, "-byte aligned for a ", table.scalar_type(), " table");
+  TORCH_CHECK(rowwise || reinterpret_cast<uintptr_t>(exp_avg_sq.data_ptr()) % state_align == 0,
+              "cuembed_pyt: exp_avg_sq must be ", state_align, "-byte aligned for a ", table.scalar_type(), " table");
+  TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "cuembed_pyt: betas must lie in [0, 1)");
+  TORCH_CHECK(eps >= 0.0 && weight_decay >= 0.0, "cuembed_pyt: eps and weight_decay must not be negative");
+  const bool has_counts = counts.has_value() && counts->defined();
+  const bool has_last = last_id.has_value() && last_id->defined();
+  TORCH_CHECK((count >= 0) + has_counts + has_last <= 1, "cuembed_pyt: give at most one of count, counts and last_id");
+  int64_t num_rows = -1, piece_rows = ids.numel();
+  int pieces = 1, words64 = 0;
+  if (has_counts) {
+    CheckGpu(*counts, "counts");
+    words64 = IndexCode(*counts, "counts") == CUEMBED_I64;
+    TORCH_CHECK(counts->is_contiguous() && counts->numel() >= 1, "cuembed_pyt: counts must be contiguous words");
+    if (piece_rows_arg > 0) {
+      pieces = static_cast<int>(counts->numel());
+      piece_rows = piece_rows_arg;
+    }
+    TORCH_CHECK(pieces == counts->numel() && pieces * piece_rows == ids.numel(),
+                "cuembed_pyt: ids must hold counts.numel() * piece_rows entries");
+  } else if (has_last) {
+    CheckGpu(*last_id, "last_id");
+    TORCH_CHECK(last_id->scalar_type() == ids.scalar_type() && last_id->numel() == 1,
+                "cuembed_pyt: last_id must be one word of ids' dtype");
+  } else {
+    num_rows = count >= 0 ? count : ids.numel();
+    TORCH_CHECK(num_rows <= ids.numel(), "cuembed_pyt: count exceeds the entries");
+  }
+  const auto word = [&](const c10::optional<at::Tensor>& t, const char* name) -> const float* {
+    if (!t.has_value() || !t->defined()) return nullptr;
+    CheckGpu(*t, name);
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() == 1, "cuembed_pyt: ", name, " must be one float32 word");
+    return static_cast<const float*>(t->data_ptr());
+  };
+  const float* lr_word = word(lr_device, "lr_device");
+  const float* bias_word = word(bias_factor_device, "bias_factor_device");
+  const bool has_step = step_device.has_value() && step_device->defined();
+  if (stochastic_rounding) {
+    TORCH_CHECK(table.scalar_type() != at::kFloat,
+                "cuembed_pyt: stochastic_rounding is for float16 / bfloat16 tables: a float32 table is not rounded");
+    if (has_step) {
+      CheckGpu(*step_device, "step_device");
+      TORCH_CHECK(step_device->scalar_type() == at::kLong && step_device->numel() == 1 &&
+                      step_device->device() == table.device(),
+                  "cuembed_pyt: step_device must be one int64 word on the table's device");
+    }
+  }
+  if (ids.numel() == 0) return;
+  const at::DeviceGuard guard(table.device());
+  const int rule = rowwise ? CUEMBED_ROWWISE_ADAM : CUEMBED_ADAM;
+  float* m = static_cast<float*>(exp_avg.data_ptr());
+  float* v = static_cast<float*>(exp_avg_sq.data_ptr());
+  const float b1 = static_cast<float>(beta1), omb1 = static_cast<float>(1.0 - beta1);
+  const float b2 = static_cast<float>(beta2), omb2 = static_cast<float>(1.0 - beta2);
+  if (stochastic_rounding) {
+    ::cuembed_sparse_row_adam_stochastic(
+        table.data_ptr(), elem, static_cast<int>(table.size(1)), m, v, rule, Ptr(ids), idx, Ptr(rows), piece_rows, pieces,
+        num_rows, has_counts ? counts->data_ptr() : nullptr, words64, has_last ? last_id->data_ptr() : nullptr,
+        static_cast<float>(lr), lr_word, static_cast<float>(bias_factor), bias_word, b1, omb1, b2, omb2,
+        static_cast<float>(eps), static_cast<float>(weight_decay), static_cast<uint64_t>(seed),
+        static_cast<uint64_t>(step), has_step ? static_cast<const int64_t*>(step_device->data_ptr()) : nullptr,
+        CurrentStream(table));
+    return;
+  }
+  ::cuembed_sparse_row_adam(table.data_ptr(), elem, static_cast<int>(table.size(1)), m, v, rule, Ptr(ids), idx, Ptr(rows),
+                            piece_rows, pieces, num_rows, has_counts ? counts->data_ptr() : nullptr, words64,
+                            has_last ? last_id->data_ptr() : nullptr, static_cast<float>(lr), lr_word,
+                            static_cast<float>(bias_factor), bias_word, b1, omb1, b2, omb2, static_cast<float>(eps),
+                            static_cast<float>(weight_decay), CurrentStream(table));
+}
+
 // Extension (cuembed::PackRowsByOwner): the rank's compressed gradient into the fixed slots of the all-to-all.
 void cuembed_exchange_pack_op(const at::Tensor& ids, const at::Tensor& rows, const c10::optional<at::Tensor>& count,
                               const at::Tensor& cuts, const int64_t slot_capacity, const int64_t input_capacity,
@@ -1032,6 +1139,11 @@ TORCH_LIBRARY(cuembed_pyt, m) {
       "cuembed_sparse_row_update_(Tensor(a!) table, Tensor(b!)? state, Tensor ids, Tensor rows, str rule, float lr, "
       "float eps, Tensor? lr_device, int count, Tensor? counts, Tensor? last_id, int piece_rows, bool "
       "stochastic_rounding=False, int seed=0, int step=0, Tensor? step_device=None) -> ()");
+  m.def(
+      "cuembed_sparse_row_adam_(Tensor(a!) table, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, Tensor ids, Tensor rows, bool "
+      "rowwise, float lr, float bias_factor, float beta1, float beta2, float eps, float weight_decay, Tensor? lr_device, "
+      "Tensor? bias_factor_device, int count, Tensor? counts, Tensor? last_id, int piece_rows, bool "
+      "stochastic_rounding=False, int seed=0, int step=0, Tensor? step_device=None) -> ()");
   // 8-bit row-wise quantized tables (torch's fused layout), inference only
   m.def("quantize_rows(Tensor table) -> Tensor");
   m.def("dequantize_rows(Tensor qtable, Tensor? ids, ScalarType dtype) -> Tensor");
@@ -1071,6 +1183,7 @@ TORCH_LIBRARY_IMPL(cuembed_pyt, CUDA, m) {  // HIP tensors use the CUDA dispatch
   m.impl("cuembed_exchange_pack", cuembed_exchange_pack_op);
   m.impl("cuembed_exchange_merge", cuembed_exchange_merge_op);
   m.impl("cuembed_sparse_row_update_", cuembed_sparse_row_update_op);
+  m.impl("cuembed_sparse_row_adam_", cuembed_sparse_row_adam_op);
   m.impl("quantize_rows", quantize_rows_op);
   m.impl("dequantize_rows", dequantize_rows_op);
   m.impl("cuemb_embedding_quantized", cuemb_embedding_quantized_op);

@@ -72,6 +72,11 @@ def _define_python_ops():
     _lib.define("cuembed_sparse_row_update_(Tensor(a!) table, Tensor(b!)? state, Tensor ids, Tensor rows, str rule,"
                 " float lr, float eps, Tensor? lr_device, int count, Tensor? counts, Tensor? last_id, int piece_rows,"
                 " bool stochastic_rounding=False, int seed=0, int step=0, Tensor? step_device=None) -> ()")
+    _lib.define("cuembed_sparse_row_adam_(Tensor(a!) table, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, Tensor ids,"
+                " Tensor rows, bool rowwise, float lr, float bias_factor, float beta1, float beta2, float eps,"
+                " float weight_decay, Tensor? lr_device, Tensor? bias_factor_device, int count, Tensor? counts,"
+                " Tensor? last_id, int piece_rows, bool stochastic_rounding=False, int seed=0, int step=0,"
+                " Tensor? step_device=None) -> ()")
     _lib.define("quantize_rows(Tensor table) -> Tensor")
     _lib.define("dequantize_rows(Tensor qtable, Tensor? ids, ScalarType dtype) -> Tensor")
     _lib.define("cuemb_embedding_quantized(Tensor qtable, Tensor indices, Tensor? offsets, Tensor? weights, str mode,"
@@ -80,6 +85,7 @@ def _define_python_ops():
     _lib.impl("dequantize_rows", _dequantize_rows_impl, "CUDA")
     _lib.impl("cuemb_embedding_quantized", _embedding_quantized_impl, "CUDA")
     _lib.impl("cuembed_sparse_row_update_", _sparse_row_update_impl, "CUDA")
+    _lib.impl("cuembed_sparse_row_adam_", _sparse_row_adam_impl, "CUDA")
     _lib.impl("cuembed_decide_row_loads", _decide_row_loads_impl, "CUDA")
     _lib.impl("cuembed_embedding_forward_hinted", _forward_hinted_impl, "CUDA")
     _lib.impl("cuembed_bag_order_by_length", _bag_order_impl, "CUDA")
@@ -114,6 +120,8 @@ def _define_python_ops():
 #   cuembed_embedding_weight_grad             gradient w.r.t. the per-lookup weights
 #   cuembed_sparse_row_update_                the sparse optimizer step on a compressed gradient, in place (SGD, Adagrad,
 #                                             row-wise Adagrad; the entry count may stay on the device)
+#   cuembed_sparse_row_adam_                  the same for the Adam family (lazy Adam, row-wise Adam; decoupled weight
+#                                             decay; the bias factor may stay on the device)
 #   quantize_rows, dequantize_rows,           8-bit row-wise quantized tables in torch's own fused layout (inference
 #   cuemb_embedding_quantized                 only): the quantizer, its inverse, and the lookup on a fused table
 
@@ -262,6 +270,28 @@ def _sparse_row_update_impl(table, state, ids, rows, rule, lr, eps, lr_device, c
                            **kw)
 
 
+def _sparse_row_adam_impl(table, exp_avg, exp_avg_sq, ids, rows, rowwise, lr, bias_factor, beta1, beta2, eps,
+                          weight_decay, lr_device, bias_factor_device, count, counts, last_id, piece_rows,
+                          stochastic_rounding=False, seed=0, step=0, step_device=None):
+    _require((count >= 0) + (counts is not None) + (last_id is not None) <= 1,
+             "give at most one of count, counts and last_id")
+    if counts is not None and piece_rows > 0:
+        kw = dict(counts=counts, piece_rows=piece_rows)
+    elif counts is not None:
+        kw = dict(count=counts)                 # one word for all entries
+    elif last_id is not None:
+        kw = dict(last_id=last_id)
+    else:
+        kw = dict(count=count if count >= 0 else None)
+    if stochastic_rounding:     # (the schema's ints are signed 64-bit words: the same bits as the unsigned seed / step)
+        kw.update(stochastic_rounding=True, seed=seed % 2 ** 64,
+                  step=step % 2 ** 64 if step_device is None else step_device)
+    _ops.sparse_row_adam(table, ids, rows, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq,
+                         lr=lr if lr_device is None else lr_device,
+                         bias_factor=bias_factor if bias_factor_device is None else bias_factor_device,
+                         betas=(beta1, beta2), eps=eps, weight_decay=weight_decay, rowwise=rowwise, **kw)
+
+
 def _quantize_rows_impl(table):
     from . import quantized as _q
     return _q.quantize_rows(table.contiguous())
@@ -341,6 +371,29 @@ def cuembed_sparse_row_update_(table, ids, rows, rule, lr, state=None, eps=1e-8,
         return
     step_device = step if isinstance(step, torch.Tensor) else None
     torch.ops.cuembed_pyt.cuembed_sparse_row_update_(
+        *args, True, _signed_word("seed", seed), 0 if step_device is not None else _signed_word("step", step), step_device)
+
+
+def cuembed_sparse_row_adam_(table, ids, rows, *, exp_avg, exp_avg_sq, lr, bias_factor=1.0, betas=(0.9, 0.999), eps=1e-8,
+                             weight_decay=0.0, rowwise=False, count=None, last_id=None, counts=None, piece_rows=None,
+                             stochastic_rounding=False, seed=0, step=0):
+    """cuembed_amd.ops.sparse_row_adam as the torch op cuembed_pyt::cuembed_sparse_row_adam_ (in place on `table`,
+    `exp_avg` and `exp_avg_sq`; traces under torch.compile).  Same arguments."""
+    lr_device = lr if isinstance(lr, torch.Tensor) else None
+    bias_device = bias_factor if isinstance(bias_factor, torch.Tensor) else None
+    word = count if isinstance(count, torch.Tensor) else None
+    if word is not None and counts is not None:
+        raise ValueError("give at most one of count=, last_id= and counts=")
+    beta1, beta2 = betas
+    args = (table, exp_avg, exp_avg_sq, ids, rows, bool(rowwise), 0.0 if lr_device is not None else float(lr),
+            1.0 if bias_device is not None else float(bias_factor), float(beta1), float(beta2), float(eps),
+            float(weight_decay), lr_device, bias_device, -1 if (count is None or word is not None) else int(count),
+            counts if word is None else word, last_id, 0 if piece_rows is None else int(piece_rows))
+    if not stochastic_rounding:
+        torch.ops.cuembed_pyt.cuembed_sparse_row_adam_(*args)
+        return
+    step_device = step if isinstance(step, torch.Tensor) else None
+    torch.ops.cuembed_pyt.cuembed_sparse_row_adam_(
         *args, True, _signed_word("seed", seed), 0 if step_device is not None else _signed_word("step", step), step_device)
 
 
@@ -676,6 +729,13 @@ def _(indices, table_bytes, decision):
 @torch.library.register_fake("cuembed_pyt::cuembed_sparse_row_update_")
 def _(table, state, ids, rows, rule, lr, eps, lr_device=None, count=-1, counts=None, last_id=None, piece_rows=0,
       stochastic_rounding=False, seed=0, step=0, step_device=None):
+    return None
+
+
+@torch.library.register_fake("cuembed_pyt::cuembed_sparse_row_adam_")
+def _(table, exp_avg, exp_avg_sq, ids, rows, rowwise, lr, bias_factor, beta1, beta2, eps, weight_decay, lr_device=None,
+      bias_factor_device=None, count=-1, counts=None, last_id=None, piece_rows=0, stochastic_rounding=False, seed=0,
+      step=0, step_device=None):
     return None
 
 

@@ -742,6 +742,58 @@ def stochastic_round_array(elem_dtype, x, r16):
     return out.to(torch.int32) & 0xFFFF
 
 
+def _entry_counts(ids, count, last_id, counts, piece_rows):
+    """The count source of a sparse step, validated: (num_rows, count_words, words_are_64, pieces, piece_rows)."""
+    n = ids.numel()
+    if (count is not None) + (last_id is not None) + (counts is not None) > 1:
+        raise ValueError("give at most one of count=, last_id= and counts=")
+    if piece_rows is not None and counts is None:
+        raise ValueError("piece_rows goes with counts=")
+    num_rows, count_words, pieces, words64 = -1, None, 1, False
+    if counts is not None:
+        if not isinstance(counts, torch.Tensor) or counts.dtype not in _INDEX or counts.dim() != 1 or counts.numel() < 1:
+            raise TypeError("counts must be a 1-D int32 or int64 tensor, one word per piece")
+        pieces = counts.numel()
+        if piece_rows is None:
+            piece_rows = n // pieces
+        if piece_rows < 0 or pieces * piece_rows != n:
+            raise ValueError("ids must hold counts.numel() * piece_rows entries")
+        count_words, words64 = counts, counts.dtype == torch.int64
+    elif isinstance(count, torch.Tensor):
+        if count.dtype not in _INDEX or count.numel() != 1:
+            raise TypeError("count must be an int or a one-element int32 / int64 tensor")
+        count_words, words64, piece_rows = count, count.dtype == torch.int64, n
+    elif last_id is not None:
+        if not isinstance(last_id, torch.Tensor) or last_id.dtype != ids.dtype or last_id.numel() != 1:
+            raise TypeError("last_id must be a one-element tensor of ids' dtype")
+        piece_rows = n
+    else:
+        num_rows = n if count is None else int(count)
+        if num_rows < 0 or num_rows > n:
+            raise ValueError("count must be in [0, ids.numel()]")
+        piece_rows = n
+    return num_rows, count_words, words64, pieces, piece_rows
+
+
+def _rounding_step(table, stochastic_rounding, seed, step):
+    """seed / step of a stochastically rounded step, validated: (step, step_word)."""
+    step_word = None
+    if stochastic_rounding:
+        if table.dtype == torch.float32:
+            raise TypeError("stochastic_rounding is for float16 / bfloat16 tables: a float32 table is not rounded")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must be an int in [0, 2**64), got %r" % (seed,))
+        if isinstance(step, torch.Tensor):
+            if step.dtype != torch.int64 or step.numel() != 1:
+                raise TypeError("a device-side step must be a one-element int64 tensor")
+            step_word, step = step, 0
+        elif isinstance(step, bool) or not isinstance(step, int) or not 0 <= step < 2 ** 64:
+            raise ValueError("step must be an int in [0, 2**64) or a one-element int64 device tensor, got %r" % (step,))
+        if step_word is not None and step_word.device != table.device:
+            raise ValueError("step must be on the table's device (%s), got %s" % (table.device, step_word.device))
+    return step, step_word
+
+
 def sparse_row_update(table, ids, rows, *, rule, lr, state=None, eps=1e-8, count=None, last_id=None, counts=None,
                       piece_rows=None, stochastic_rounding=False, seed=0, step=0):
     """Sparse optimizer step (cuembed::SparseRowUpdate): for every valid entry k, table[ids[k], :] and the state of
@@ -807,47 +859,8 @@ def sparse_row_update(table, ids, rows, *, rule, lr, state=None, eps=1e-8, count
             raise TypeError("state must be float32, got %s" % state.dtype)
         if tuple(state.shape) != want:
             raise ValueError("rule=%r needs a state of shape %r, got %r" % (rule, want, tuple(state.shape)))
-    if (count is not None) + (last_id is not None) + (counts is not None) > 1:
-        raise ValueError("give at most one of count=, last_id= and counts=")
-    if piece_rows is not None and counts is None:
-        raise ValueError("piece_rows goes with counts=")
-    num_rows, count_words, pieces, words64 = -1, None, 1, False
-    if counts is not None:
-        if not isinstance(counts, torch.Tensor) or counts.dtype not in _INDEX or counts.dim() != 1 or counts.numel() < 1:
-            raise TypeError("counts must be a 1-D int32 or int64 tensor, one word per piece")
-        pieces = counts.numel()
-        if piece_rows is None:
-            piece_rows = n // pieces
-        if piece_rows < 0 or pieces * piece_rows != n:
-            raise ValueError("ids must hold counts.numel() * piece_rows entries")
-        count_words, words64 = counts, counts.dtype == torch.int64
-    elif isinstance(count, torch.Tensor):
-        if count.dtype not in _INDEX or count.numel() != 1:
-            raise TypeError("count must be an int or a one-element int32 / int64 tensor")
-        count_words, words64, piece_rows = count, count.dtype == torch.int64, n
-    elif last_id is not None:
-        if not isinstance(last_id, torch.Tensor) or last_id.dtype != ids.dtype or last_id.numel() != 1:
-            raise TypeError("last_id must be a one-element tensor of ids' dtype")
-        piece_rows = n
-    else:
-        num_rows = n if count is None else int(count)
-        if num_rows < 0 or num_rows > n:
-            raise ValueError("count must be in [0, ids.numel()]")
-        piece_rows = n
-    step_word = None
-    if stochastic_rounding:
-        if table.dtype == torch.float32:
-            raise TypeError("stochastic_rounding is for float16 / bfloat16 tables: a float32 table is not rounded")
-        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
-            raise ValueError("seed must be an int in [0, 2**64), got %r" % (seed,))
-        if isinstance(step, torch.Tensor):
-            if step.dtype != torch.int64 or step.numel() != 1:
-                raise TypeError("a device-side step must be a one-element int64 tensor")
-            step_word, step = step, 0
-        elif isinstance(step, bool) or not isinstance(step, int) or not 0 <= step < 2 ** 64:
-            raise ValueError("step must be an int in [0, 2**64) or a one-element int64 device tensor, got %r" % (step,))
-        if step_word is not None and step_word.device != table.device:
-            raise ValueError("step must be on the table's device (%s), got %s" % (table.device, step_word.device))
+    num_rows, count_words, words64, pieces, piece_rows = _entry_counts(ids, count, last_id, counts, piece_rows)
+    step, step_word = _rounding_step(table, stochastic_rounding, seed, step)
     lr_word = None
     if isinstance(lr, torch.Tensor):
         if lr.dtype != torch.float32 or lr.numel() != 1:
@@ -872,6 +885,143 @@ def sparse_row_update(table, ids, rows, *, rule, lr, state=None, eps=1e-8, count
                                              _ptr(rows), int(piece_rows), int(pieces), int(num_rows), _ptr(count_words),
                                              int(words64), _ptr(last_id), float(lr), _ptr(lr_word), float(eps),
                                              _stream(table))
+    return None
+
+
+# ---- sparse optimizer step, the Adam family ------------------------------------------------------------------------
+ADAM_RULES = {"adam": 0, "rowwise_adam": 1}
+
+
+def adam_bias_factor(step, betas=(0.9, 0.999)):
+    """c = sqrt(1 - beta2^step) / (1 - beta1^step), the bias factor of Adam's step `step` >= 1 as a Python float
+    (double arithmetic; sparse_row_adam rounds it once to fp32).  torch.optim.SparseAdam's step size is lr * c."""
+    if isinstance(step, bool) or not isinstance(step, int) or step < 1:
+        raise ValueError("step must be an int >= 1, got %r" % (step,))
+    beta1, beta2 = _check_betas(betas)
+    return (1.0 - beta2 ** step) ** 0.5 / (1.0 - beta1 ** step)
+
+
+def _check_betas(betas):
+    try:
+        beta1, beta2 = (float(b) for b in betas)
+    except (TypeError, ValueError):
+        raise ValueError("betas must be a pair of floats in [0, 1), got %r" % (betas,)) from None
+    if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0):
+        raise ValueError("betas must be a pair of floats in [0, 1), got %r" % (betas,))
+    return beta1, beta2
+
+
+def new_adam_clock(device="cuda"):
+    """The bias-factor clock of a run at step 0: (powers, bias_factor) = (float64 [3] holding (t, beta1^t, beta2^t) =
+    (0, 1, 1), float32 [1]) on `device`.  adam_clock_advance moves it one step on; bias_factor is what
+    sparse_row_adam(bias_factor=...) reads."""
+    powers = torch.tensor([0.0, 1.0, 1.0], dtype=torch.float64, device=device)
+    return powers, torch.ones((1,), dtype=torch.float32, device=device)
+
+
+def adam_clock_advance(powers, bias_factor, betas=(0.9, 0.999)):
+    """One step of the clock ON THE DEVICE (one single-thread launch on the current stream, nothing read back):
+    powers = (t, beta1^t, beta2^t) <- (t + 1, beta1^t * beta1, beta2^t * beta2) in fp64, and bias_factor[0] <-
+    sqrt(1 - beta2^t) / (1 - beta1^t) of the new t, computed in fp64 and rounded once to fp32.  Captured into a HIP graph
+    in front of sparse_row_adam, every replay is the next step."""
+    beta1, beta2 = _check_betas(betas)
+    if not isinstance(powers, torch.Tensor) or powers.dtype != torch.float64 or tuple(powers.shape) != (3,):
+        raise TypeError("powers must be a float64 tensor of 3 elements (new_adam_clock)")
+    if not isinstance(bias_factor, torch.Tensor) or bias_factor.dtype != torch.float32 or bias_factor.numel() != 1:
+        raise TypeError("bias_factor must be a one-element float32 tensor (new_adam_clock)")
+    _check_dev("powers", powers)
+    _check_dev("bias_factor", bias_factor, powers.device)
+    with torch.cuda.device(powers.device):
+        _lib.lib().cuembed_adam_clock_advance(_ptr(powers), _ptr(bias_factor), beta1, beta2, _stream(powers))
+    return None
+
+
+def sparse_row_adam(table, ids, rows, *, exp_avg, exp_avg_sq, lr, bias_factor=1.0, betas=(0.9, 0.999), eps=1e-8,
+                    weight_decay=0.0, rowwise=False, count=None, last_id=None, counts=None, piece_rows=None,
+                    stochastic_rounding=False, seed=0, step=0):
+    """Sparse Adam step (cuembed::SparseRowAdam): for every valid entry k, table[ids[k], :] and the moments of that row
+    are updated IN PLACE from the gradient row rows[k, :].  Rows that no valid entry names are neither read nor written
+    -- their moments do not decay, the "lazy" behaviour of torch.optim.SparseAdam.  fp32 arithmetic whatever the
+    table's dtype, one rounding to it at the store.  Returns None.  With c = bias_factor:
+
+        both rules        w <- w - (lr * weight_decay) * w              only if weight_decay != 0 (decoupled, AdamW style)
+                          m <- beta1 * m + (1 - beta1) * g              exp_avg fp32 [rows, width]
+        rowwise=False     v <- beta2 * v + (1 - beta2) * g^2            exp_avg_sq fp32 [rows, width]
+                          w <- w - (lr * c) * m / (sqrt(v) + eps)       (torch.optim.SparseAdam's formula)
+        rowwise=True      v_r <- beta2 * v_r + (1 - beta2) * mean_j(g_j^2)      exp_avg_sq fp32 [rows]: 4 * width + 4
+                          w_j <- w_j - (lr * c) / (sqrt(v_r) + eps) * m_j       bytes of state per row instead of 8 * width
+
+    bias_factor: adam_bias_factor(t, betas) of the step t >= 1 (1.0: no bias correction), as a float or as a one-element
+    fp32 device tensor that the kernel reads (adam_clock_advance keeps one current on the device).  lr: a float or a
+    one-element fp32 device tensor.  The kernel receives beta, 1 - beta (formed in double), eps and weight_decay each
+    rounded once to fp32, and forms lr * c with one fp32 multiplication.
+
+    (ids, rows), the count sources count= / last_id= / counts= with piece_rows=, the DISTINCT-rows contract and
+    stochastic_rounding / seed / step are those of sparse_row_update.  No form needs a host read-back."""
+    for name, t in (("table", table), ("ids", ids), ("rows", rows)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+    et = _elem_code("table", table)
+    it = _index_code("ids", ids)
+    if rows.dtype != table.dtype:
+        raise TypeError("rows must have the table's dtype (%s), got %s" % (table.dtype, rows.dtype))
+    if table.dim() != 2 or rows.dim() != 2 or rows.shape[1] != table.shape[1]:
+        raise ValueError("table must be [num_categories, width] and rows [entries, width]")
+    width = table.shape[1]
+    if (width * table.element_size()) % 4 != 0:
+        raise ValueError("the row size must be a multiple of 4 bytes")
+    n = ids.numel()
+    if ids.dim() != 1 or rows.shape[0] != n:
+        raise ValueError("ids must hold one entry per row of rows")
+    rule = "rowwise_adam" if rowwise else "adam"
+    wants = (("exp_avg", exp_avg, (table.shape[0], width)),
+             ("exp_avg_sq", exp_avg_sq, (table.shape[0],) if rowwise else (table.shape[0], width)))
+    for name, t, want in wants:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a float32 tensor of shape %r" % (name, want))
+        if t.dtype != torch.float32:
+            raise TypeError("%s must be float32, got %s" % (name, t.dtype))
+        if tuple(t.shape) != want:
+            raise ValueError("rule %r needs an %s of shape %r, got %r" % (rule, name, want, tuple(t.shape)))
+    beta1, beta2 = _check_betas(betas)
+    if not float(eps) >= 0.0:
+        raise ValueError("eps must not be negative, got %r" % (eps,))
+    if not float(weight_decay) >= 0.0:
+        raise ValueError("weight_decay must not be negative, got %r" % (weight_decay,))
+    num_rows, count_words, words64, pieces, piece_rows = _entry_counts(ids, count, last_id, counts, piece_rows)
+    step, step_word = _rounding_step(table, stochastic_rounding, seed, step)
+    lr_word = bias_word = None
+    if isinstance(lr, torch.Tensor):
+        if lr.dtype != torch.float32 or lr.numel() != 1:
+            raise TypeError("a device-side lr must be a one-element float32 tensor")
+        lr_word, lr = lr, 0.0
+    if isinstance(bias_factor, torch.Tensor):
+        if bias_factor.dtype != torch.float32 or bias_factor.numel() != 1:
+            raise TypeError("a device-side bias_factor must be a one-element float32 tensor")
+        bias_word, bias_factor = bias_factor, 1.0
+    _check_dev("table", table)
+    dev = table.device
+    for name, t in (("ids", ids), ("rows", rows), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq),
+                    ("count", count_words), ("last_id", last_id), ("lr", lr_word), ("bias_factor", bias_word),
+                    ("step", step_word)):
+        if t is not None:
+            _check_dev(name, t, dev)
+    # the narrowest lane is 4 bytes of the row: one fp32 element of state for a float32 table, two for a 16-bit one
+    state_align = 4 * (4 // table.element_size())
+    for name, t in (("exp_avg", exp_avg),) + ((("exp_avg_sq", exp_avg_sq),) if not rowwise else ()):
+        if t.data_ptr() % state_align != 0:
+            raise ValueError("%s must be %d-byte aligned for a %s table" % (name, state_align, table.dtype))
+    if n == 0:
+        return None
+    args = (_ptr(table), et, width, _ptr(exp_avg), _ptr(exp_avg_sq), ADAM_RULES[rule], _ptr(ids), it, _ptr(rows),
+            int(piece_rows), int(pieces), int(num_rows), _ptr(count_words), int(words64), _ptr(last_id), float(lr),
+            _ptr(lr_word), float(bias_factor), _ptr(bias_word), beta1, 1.0 - beta1, beta2, 1.0 - beta2, float(eps),
+            float(weight_decay))      # (ctypes rounds each double once to the C float)
+    with torch.cuda.device(dev):
+        if stochastic_rounding:
+            _lib.lib().cuembed_sparse_row_adam_stochastic(*args, seed, step, _ptr(step_word), _stream(table))
+        else:
+            _lib.lib().cuembed_sparse_row_adam(*args, _stream(table))
     return None
 
 

@@ -1,6 +1,7 @@
 """Sparse optimizers on the compressed gradient (an extension: the reference ends at the gradient).
 
-Two ways in, both ending in the same HIP kernel (cuembed_amd.ops.sparse_row_update):
+Two ways in, both ending in the same HIP kernels (cuembed_amd.ops.sparse_row_update; cuembed_amd.ops.sparse_row_adam for
+the Adam family):
 
     SparseUpdater(table, rule, lr)              owns the optimizer state and applies (ids, rows) gradients to the
         .apply(ids, rows, count=... | last_id=... | counts=..., piece_rows=...)      table in place;
@@ -22,7 +23,22 @@ Rules (fp32 arithmetic whatever the table's dtype, one rounding to it at the sto
     "adagrad"          s <- s + g^2;  w <- w - lr * g / (sqrt(s) + eps)      (torch.optim.Adagrad, lr_decay = 0,
                                                                               weight_decay = 0); fp32 state [rows, W]
     "rowwise_adagrad"  s_r <- s_r + mean_j(g_j^2);  w_j <- w_j - lr * g_j / (sqrt(s_r) + eps);  fp32 state [rows]
-No momentum, weight decay or lr_decay.
+No momentum, weight decay or lr_decay for these three.
+
+The Adam family has entries of its own (two state tensors, more hyper-parameters):
+
+    SparseAdamUpdater(table, lr, betas, eps, weight_decay, rowwise=False, bias_correction=True)
+        .apply(...) / .backward_and_apply(...)  as SparseUpdater's; owns exp_avg, exp_avg_sq (fp32) and a bias-factor clock
+                                                on the device that every apply advances there: still capturable;
+    SparseAdam / RowwiseAdam                    torch.optim.Optimizer subclasses for coalesced sparse gradients, with
+                                                torch.optim.SparseAdam's state keys ("step", "exp_avg", "exp_avg_sq").
+
+    "adam"          w <- w - (lr * weight_decay) * w  (if weight_decay != 0: decoupled, named rows only)
+                    m <- beta1 * m + (1 - beta1) * g;  v <- beta2 * v + (1 - beta2) * g^2       fp32 state 2 x [rows, W]
+                    w <- w - (lr * c) * m / (sqrt(v) + eps),  c = sqrt(1 - beta2^t) / (1 - beta1^t)
+                    (torch.optim.SparseAdam's formula; lazy: the moments of rows that are not named do not decay)
+    "rowwise_adam"  m as above;  v_r <- beta2 * v_r + (1 - beta2) * mean_j(g_j^2);  w_j <- w_j - (lr * c) / (sqrt(v_r) + eps) * m_j
+                    fp32 state [rows, W] + [rows]
 
 Stochastic rounding (stochastic_rounding=True, seed=...; float16 / bfloat16 tables): the rounding to the table's dtype
 goes up or down with the probability of the fp32 value's position between its neighbours, so that updates below half a
@@ -46,50 +62,10 @@ def _new_state(table, rule, initial_accumulator_value):
     return torch.full(shape, float(initial_accumulator_value), dtype=torch.float32, device=table.device)
 
 
-class SparseUpdater:
-    """Applies compressed gradients to `table` ([num_categories, width]; fp32, fp16 or bf16) in place and owns the
-    optimizer state (`.state`: None, fp32 [num_categories, width] or fp32 [num_categories]).
-
-    lr is a float or a one-element fp32 device tensor that the kernel reads (fill it to follow a schedule inside a
-    captured graph); assign `.lr` to change it.
-
-    stochastic_rounding=True (16-bit tables): every apply rounds stochastically with the bits of (seed, rounding_step),
-    where `.rounding_step` is an int64 device word that starts at 0 and is advanced on the device after every apply --
-    nothing is read back, so backward_and_apply stays capturable."""
-
-    def __init__(self, table, rule, lr, eps=1e-8, initial_accumulator_value=0.0, stochastic_rounding=False, seed=0):
-        if not isinstance(table, torch.Tensor) or table.dim() != 2:
-            raise TypeError("table must be a [num_categories, width] tensor")
-        if rule not in _ops.UPDATE_RULES:
-            raise ValueError("rule must be one of %r, got %r" % (sorted(_ops.UPDATE_RULES), rule))
-        if table.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise TypeError("table must be float32, float16 or bfloat16, got %s" % table.dtype)
-        if not table.is_contiguous():
-            raise ValueError("table must be contiguous")
-        self.table = table.detach()     # (a Parameter is updated through its data)
-        self.rule = rule
-        self.lr = lr
-        self.eps = float(eps)
-        self.state = _new_state(table, rule, initial_accumulator_value)
-        self._buffers = {}
-        self.stochastic_rounding = bool(stochastic_rounding)
-        self.seed = seed
-        self.rounding_step = None
-        if self.stochastic_rounding:
-            _check_rounding(table, seed)
-            self.rounding_step = torch.zeros((1,), dtype=torch.int64, device=table.device)
-
-    def apply(self, ids, rows, count=None, last_id=None, counts=None, piece_rows=None):
-        """table[ids[k]] (and its state) <- rule, for the valid entries of a COALESCED gradient (ids, rows): see
-        cuembed_amd.ops.sparse_row_update for the count sources.  Nothing is read back."""
-        if not self.stochastic_rounding:
-            _ops.sparse_row_update(self.table, ids, rows, rule=self.rule, lr=self.lr, state=self.state, eps=self.eps,
-                                   count=count, last_id=last_id, counts=counts, piece_rows=piece_rows)
-            return
-        _ops.sparse_row_update(self.table, ids, rows, rule=self.rule, lr=self.lr, state=self.state, eps=self.eps,
-                               count=count, last_id=last_id, counts=counts, piece_rows=piece_rows,
-                               stochastic_rounding=True, seed=self.seed, step=self.rounding_step)
-        self.rounding_step.add_(1)      # on the device, after the kernel in stream order: one apply = one step
+class _CompressedGradientStep:
+    """The index path shared by SparseUpdater and SparseAdamUpdater: the backward of a sum-pooled lookup into buffers this
+    object keeps, with the row count left on the device, handed to self.apply(ids, rows, last_id=...).  Needs
+    self.table and self._buffers = {}."""
 
     def _step_buffers(self, nnz, dtype, index_dtype, weighted):
         """Gradient rows / ids of min(nnz, num_categories) entries and the sort's workspace, kept between calls."""
@@ -135,6 +111,115 @@ class SparseUpdater:
         _ops.embedding_backward(out_grad, None, t_idx, t_sid, remap, t_w, grad_embedding=b["rows"],
                                 inverse_mapping=b["ids"])
         self.apply(b["ids"], b["rows"], last_id=remap[nnz - 1:])
+
+
+class SparseUpdater(_CompressedGradientStep):
+    """Applies compressed gradients to `table` ([num_categories, width]; fp32, fp16 or bf16) in place and owns the
+    optimizer state (`.state`: None, fp32 [num_categories, width] or fp32 [num_categories]).
+
+    lr is a float or a one-element fp32 device tensor that the kernel reads (fill it to follow a schedule inside a
+    captured graph); assign `.lr` to change it.
+
+    stochastic_rounding=True (16-bit tables): every apply rounds stochastically with the bits of (seed, rounding_step),
+    where `.rounding_step` is an int64 device word that starts at 0 and is advanced on the device after every apply --
+    nothing is read back, so backward_and_apply stays capturable."""
+
+    def __init__(self, table, rule, lr, eps=1e-8, initial_accumulator_value=0.0, stochastic_rounding=False, seed=0):
+        if not isinstance(table, torch.Tensor) or table.dim() != 2:
+            raise TypeError("table must be a [num_categories, width] tensor")
+        if rule not in _ops.UPDATE_RULES:
+            raise ValueError("rule must be one of %r, got %r" % (sorted(_ops.UPDATE_RULES), rule))
+        if table.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError("table must be float32, float16 or bfloat16, got %s" % table.dtype)
+        if not table.is_contiguous():
+            raise ValueError("table must be contiguous")
+        self.table = table.detach()     # (a Parameter is updated through its data)
+        self.rule = rule
+        self.lr = lr
+        self.eps = float(eps)
+        self.state = _new_state(table, rule, initial_accumulator_value)
+        self._buffers = {}
+        self.stochastic_rounding = bool(stochastic_rounding)
+        self.seed = seed
+        self.rounding_step = None
+        if self.stochastic_rounding:
+            _check_rounding(table, seed)
+            self.rounding_step = torch.zeros((1,), dtype=torch.int64, device=table.device)
+
+    def apply(self, ids, rows, count=None, last_id=None, counts=None, piece_rows=None):
+        """table[ids[k]] (and its state) <- rule, for the valid entries of a COALESCED gradient (ids, rows): see
+        cuembed_amd.ops.sparse_row_update for the count sources.  Nothing is read back."""
+        if not self.stochastic_rounding:
+            _ops.sparse_row_update(self.table, ids, rows, rule=self.rule, lr=self.lr, state=self.state, eps=self.eps,
+                                   count=count, last_id=last_id, counts=counts, piece_rows=piece_rows)
+            return
+        _ops.sparse_row_update(self.table, ids, rows, rule=self.rule, lr=self.lr, state=self.state, eps=self.eps,
+                               count=count, last_id=last_id, counts=counts, piece_rows=piece_rows,
+                               stochastic_rounding=True, seed=self.seed, step=self.rounding_step)
+        self.rounding_step.add_(1)      # on the device, after the kernel in stream order: one apply = one step
+
+
+class SparseAdamUpdater(_CompressedGradientStep):
+    """SparseUpdater's counterpart for the Adam family (cuembed_amd.ops.sparse_row_adam): applies compressed gradients to
+    `table` in place and owns the moments (`.exp_avg` fp32 [num_categories, width]; `.exp_avg_sq` the same, or fp32
+    [num_categories] with rowwise=True) and the bias-factor clock (`.powers` float64 [3] = (t, beta1^t, beta2^t),
+    `.bias_factor` float32 [1]), all on the table's device.
+
+    Every apply first advances the clock ON THE DEVICE and then updates with the bias factor the kernel reads from it,
+    so that a captured forward + backward_and_apply takes the next step at every replay.  bias_correction=False leaves
+    the factor at 1 (the clock still counts).  Only named rows are touched: the moments of other rows do not decay.
+    weight_decay is decoupled (AdamW style) and acts on the named rows only.  lr and stochastic_rounding / seed /
+    `.rounding_step` are SparseUpdater's."""
+
+    def __init__(self, table, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rowwise=False, bias_correction=True,
+                 stochastic_rounding=False, seed=0):
+        if not isinstance(table, torch.Tensor) or table.dim() != 2:
+            raise TypeError("table must be a [num_categories, width] tensor")
+        if table.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError("table must be float32, float16 or bfloat16, got %s" % table.dtype)
+        if not table.is_contiguous():
+            raise ValueError("table must be contiguous")
+        self.betas = _ops._check_betas(betas)
+        if not float(eps) >= 0.0 or not float(weight_decay) >= 0.0:
+            raise ValueError("eps and weight_decay must not be negative")
+        self.table = table.detach()     # (a Parameter is updated through its data)
+        self.lr = lr
+        self.eps = float(eps)
+        self.weight_decay = float(weight_decay)
+        self.rowwise = bool(rowwise)
+        self.bias_correction = bool(bias_correction)
+        self.exp_avg, self.exp_avg_sq = _new_moments(table, self.rowwise)
+        self.powers = torch.tensor([0.0, 1.0, 1.0], dtype=torch.float64, device=table.device)
+        self.bias_factor = torch.ones((1,), dtype=torch.float32, device=table.device)
+        self._one = None if self.bias_correction else torch.ones((1,), dtype=torch.float32, device=table.device)
+        self._buffers = {}
+        self.stochastic_rounding = bool(stochastic_rounding)
+        self.seed = seed
+        self.rounding_step = None
+        if self.stochastic_rounding:
+            _check_rounding(table, seed)
+            self.rounding_step = torch.zeros((1,), dtype=torch.int64, device=table.device)
+
+    def apply(self, ids, rows, count=None, last_id=None, counts=None, piece_rows=None):
+        """One Adam step on the valid entries of a COALESCED gradient (ids, rows): the clock moves on, then
+        cuembed_amd.ops.sparse_row_adam (see there for the count sources).  Nothing is read back."""
+        _ops.adam_clock_advance(self.powers, self.bias_factor, self.betas)
+        kw = {}
+        if self.stochastic_rounding:
+            kw = dict(stochastic_rounding=True, seed=self.seed, step=self.rounding_step)
+        _ops.sparse_row_adam(self.table, ids, rows, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, lr=self.lr,
+                             bias_factor=self.bias_factor if self.bias_correction else self._one, betas=self.betas,
+                             eps=self.eps, weight_decay=self.weight_decay, rowwise=self.rowwise, count=count,
+                             last_id=last_id, counts=counts, piece_rows=piece_rows, **kw)
+        if self.stochastic_rounding:
+            self.rounding_step.add_(1)      # on the device, after the kernel in stream order: one apply = one step
+
+
+def _new_moments(table, rowwise):
+    exp_avg = torch.zeros(tuple(table.shape), dtype=torch.float32, device=table.device)
+    exp_avg_sq = torch.zeros((table.shape[0],) if rowwise else tuple(table.shape), dtype=torch.float32,
+                             device=table.device)
+    return exp_avg, exp_avg_sq
 
 
 def _check_rounding(table, seed):
@@ -248,3 +333,95 @@ class RowwiseAdagrad(_SparseOptimizer):
     """Adagrad with ONE accumulator per table row (the mean of the row's squared gradient): 4 bytes of state per row
     instead of 4 * width."""
     _rule = "rowwise_adagrad"
+
+
+def _checked_sparse_grad(opt, g):
+    """The gradient of a parameter as (ids, rows), or the front ends' errors for dense and uncoalesced ones."""
+    if not g.is_sparse:
+        raise ValueError("%s needs a sparse gradient, got a dense one; accepted: %s" % (type(opt).__name__, _ACCEPTED))
+    if not _is_coalesced(g):
+        raise ValueError("%s needs a COALESCED sparse gradient (one entry per table row), got an uncoalesced "
+                         "one (sparse_grad='uncoalesced' / 'padded' / 'fastest'); accepted: %s"
+                         % (type(opt).__name__, _ACCEPTED))
+    if g.sparse_dim() != 1 or g.dense_dim() != 1:
+        raise ValueError("the gradient must have one sparse (row) and one dense (column) dimension")
+    return g._indices()[0].contiguous(), g._values().contiguous()
+
+
+class SparseAdam(torch.optim.Optimizer):
+    """torch.optim.SparseAdam on the rows of a coalesced sparse gradient, in one HIP launch per parameter: lazy (only
+    the named rows and their moments move), bias correction in the step size, eps added to sqrt(v); plus a decoupled
+    weight_decay on the named rows (0 = torch's optimizer).  The moments are fp32 whatever the table's dtype.
+
+    State per parameter, under torch.optim.SparseAdam's names: "step" (a Python int: step() reads the gradient's size
+    back anyway), "exp_avg", "exp_avg_sq" -- a state dict of torch's optimizer for an fp32 table loads here and the
+    reverse.  With stochastic_rounding=True the bits of step t are those of (seed, t - 1)."""
+    _rowwise = False
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, bias_correction=True,
+                 stochastic_rounding=False, seed=0):
+        if not isinstance(lr, torch.Tensor) and lr < 0.0:
+            raise ValueError("invalid learning rate: %r" % (lr,))
+        betas = _ops._check_betas(betas)
+        if eps < 0.0 or weight_decay < 0.0:
+            raise ValueError("eps and weight_decay must not be negative")
+        # (maximize: torch.optim.SparseAdam's step() looks it up in a group loaded from this optimizer's state dict)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, maximize=False,
+                                      bias_correction=bool(bias_correction),
+                                      stochastic_rounding=bool(stochastic_rounding), seed=seed))
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.dim() != 2:
+                    raise ValueError("every parameter must be a [num_categories, width] table")
+                if group["stochastic_rounding"]:
+                    _check_rounding(p, group["seed"])
+                st = self.state[p]
+                st["step"] = 0
+                st["exp_avg"], st["exp_avg_sq"] = _new_moments(p, self._rowwise)
+
+    def load_state_dict(self, state_dict):
+        """As torch's, except that the moments stay fp32 (torch casts optimizer state to the parameter's dtype, which
+        would round the moments of a 16-bit table) and "step" becomes a Python int again."""
+        super().load_state_dict(state_dict)
+        saved = state_dict["state"]
+        ids = [i for g in state_dict["param_groups"] for i in g["params"]]
+        params = [p for g in self.param_groups for p in g["params"]]
+        for i, p in zip(ids, params):
+            if i not in saved:
+                continue
+            for name in ("exp_avg", "exp_avg_sq"):
+                if name in saved[i]:
+                    self.state[p][name] = saved[i][name].detach().to(device=p.device, dtype=torch.float32).clone()
+            if "step" in saved[i]:
+                self.state[p]["step"] = int(saved[i]["step"])
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if group.get("maximize", False):
+                    raise ValueError("%s does not maximize: negate the loss" % type(self).__name__)
+                ids, rows = _checked_sparse_grad(self, p.grad)
+                st = self.state[p]
+                t = int(st["step"]) + 1
+                c = _ops.adam_bias_factor(t, group["betas"]) if group.get("bias_correction", True) else 1.0
+                kw = {}
+                if group.get("stochastic_rounding", False):
+                    kw = dict(stochastic_rounding=True, seed=group["seed"], step=t - 1)
+                _ops.sparse_row_adam(p.data, ids, rows, exp_avg=st["exp_avg"], exp_avg_sq=st["exp_avg_sq"],
+                                     lr=group["lr"], bias_factor=c, betas=group["betas"], eps=group["eps"],
+                                     weight_decay=group.get("weight_decay", 0.0), rowwise=self._rowwise, **kw)
+                st["step"] = t
+        return loss
+
+
+class RowwiseAdam(SparseAdam):
+    """SparseAdam with ONE second moment per table row (the running mean of the row's mean squared gradient): 4 * width +
+    4 bytes of state per row instead of 8 * width.  state[p]["exp_avg_sq"] is fp32 [num_categories]."""
+    _rowwise = True

@@ -535,6 +535,49 @@ void cuembed_stochastic_rounding_words(uint64_t seed, uint64_t step, int64_t row
 uint16_t cuembed_stochastic_round(int elem_type, float x, uint32_t r16);
 /* The same for n values on the host: out[i] = cuembed_stochastic_round(elem_type, x[i], r16[i]). */
 void cuembed_stochastic_round_array(int elem_type, const float* x, const uint32_t* r16, int64_t n, uint16_t* out);
+/* ---- sparse optimizer step, the Adam family (extension) --------------------------------------
+ * cuembed_sparse_row_adam (cuembed::SparseRowAdam, sparse_adam.hpp): for every valid entry k, table[ids[k], :]
+ * (elem_type, [num_categories, embed_width]) and the moments of row ids[k] are updated in place from rows[k, :]
+ * (elem_type).  Rows that no valid entry names are neither read nor written: their moments do not decay (the "lazy"
+ * behaviour of torch.optim.SparseAdam).  With g the gradient element, w the weight, m = exp_avg, v = exp_avg_sq:
+ *   both rules                w <- w - (lr * weight_decay) * w           only if weight_decay != 0 (decoupled, AdamW)
+ *                             m <- beta1 * m + one_minus_beta1 * g       exp_avg fp32 [num_categories, embed_width]
+ *   CUEMBED_ADAM              v <- beta2 * v + one_minus_beta2 * (g * g) exp_avg_sq fp32 [num_categories, embed_width]
+ *                             w <- w - ((lr * c) * m) / (sqrt(v) + eps)
+ *   CUEMBED_ROWWISE_ADAM      v_r <- beta2 * v_r + one_minus_beta2 * (sum_j(g_j^2) / embed_width)
+ *                                                                        exp_avg_sq fp32 [num_categories]
+ *                             w_j <- w_j - ((lr * c) / (sqrt(v_r) + eps)) * m_j
+ * Every operation written above is one fp32 operation, rounded once and never fused; the result is rounded once to the
+ * table's type at the store.  sum_j adds the squares of a lane's elements in column order and then the lanes' sums in a
+ * butterfly.  c = bias_factor is sqrt(1 - beta2^t) / (1 - beta1^t) of step t >= 1 (torch.optim.SparseAdam's formula: the
+ * correction goes into the step size, eps is added to sqrt(v)), or 1 for no bias correction.  The kernel multiplies with
+ * the fp32 values it is given: pass one_minus_beta = (float)(1.0 - (double)beta), formed in double and rounded once.
+ * lr_device / bias_factor_device != NULL: the value is read from that fp32 device word instead (cuembed_adam_clock_advance
+ * writes the latter).  Betas must lie in [0, 1), eps and weight_decay must not be negative.  The entries, the three count
+ * sources (num_rows / counts / last_id), the pieces and the DISTINCT-rows contract are those of
+ * cuembed_sparse_row_update.  One launch, no read-back. */
+enum { CUEMBED_ADAM = 0, CUEMBED_ROWWISE_ADAM = 1 };
+void cuembed_sparse_row_adam(void* table, int elem_type, int embed_width, float* exp_avg, float* exp_avg_sq, int rule,
+                             const void* ids, int index_type, const void* rows, int64_t piece_rows, int pieces,
+                             int64_t num_rows, const void* counts, int counts_are_int64, const void* last_id, float lr,
+                             const float* lr_device, float bias_factor, const float* bias_factor_device, float beta1,
+                             float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float weight_decay,
+                             cuembed_stream_t stream);
+/* cuembed_sparse_row_adam with STOCHASTIC ROUNDING of the one rounding to the table's type (elem_type CUEMBED_F16 or
+ * CUEMBED_BF16): the rule and the random bits of (seed, step, table row, column) are those of
+ * cuembed_sparse_row_update_stochastic; the fp32 arithmetic and the fp32 moments are those of cuembed_sparse_row_adam. */
+void cuembed_sparse_row_adam_stochastic(void* table, int elem_type, int embed_width, float* exp_avg, float* exp_avg_sq,
+                                        int rule, const void* ids, int index_type, const void* rows, int64_t piece_rows,
+                                        int pieces, int64_t num_rows, const void* counts, int counts_are_int64,
+                                        const void* last_id, float lr, const float* lr_device, float bias_factor,
+                                        const float* bias_factor_device, float beta1, float one_minus_beta1, float beta2,
+                                        float one_minus_beta2, float eps, float weight_decay, uint64_t seed,
+                                        uint64_t step, const int64_t* step_device, cuembed_stream_t stream);
+/* The bias-factor clock, advanced on the device (one single-thread launch, no read-back): powers, fp64[3] on the device
+ * holding (t, beta1^t, beta2^t) and starting at (0, 1, 1), becomes (t + 1, beta1^t * beta1, beta2^t * beta2) in fp64, and
+ * *bias_factor (fp32, on the device) = sqrt(1 - beta2^t) / (1 - beta1^t) of the new t, computed in fp64 and rounded once.
+ * Enqueued in front of cuembed_sparse_row_adam(bias_factor_device = bias_factor), a captured graph counts its replays. */
+void cuembed_adam_clock_advance(double* powers, float* bias_factor, double beta1, double beta2, cuembed_stream_t stream);
 /* ---- 8-bit row-wise quantized tables (extension; inference only) ---------------------------
  * The format is PyTorch's fused 8-bit row-wise layout (quantized::embedding_bag_byte_prepack): a row of embed_width
  * values is embed_width + 8 bytes -- embed_width uint8 codes, the row's fp32 scale, its fp32 bias, little endian --
