@@ -22,7 +22,9 @@
 #include <torch/csrc/autograd/custom_function.h>
 #include <torch/library.h>
 
+#include <cstdint>
 #include <cstdlib>
+#include <initializer_list>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -71,6 +73,24 @@ int Mode(const std::string& mode, bool allow_concat) {
   return CUEMBED_CONCAT;
 }
 
+// What the library's dispatchers (SplitRow, UpdateLaneBytes) would abort on, as exceptions: a row size or a data pointer
+// that is not a multiple of 4 bytes, and -- `limit_lanes`: the kernels that give every lane of a row a thread -- a row of
+// more than 1,024 lanes of the widest of 16 / 8 / 4 bytes that the row size and every pointer divide by.
+void CheckRowAlignment(const char* what, const int64_t width, const int64_t element_size,
+                       std::initializer_list<const void*> pointers, const bool limit_lanes) {
+  const int64_t row_bytes = width * element_size;
+  TORCH_CHECK(width > 0 && row_bytes % 4 == 0, "cuembed_pyt: the row size of ", what, " must be a multiple of 4 bytes");
+  uintptr_t bits = static_cast<uintptr_t>(row_bytes);
+  for (const void* p : pointers) {
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(p) % 4 == 0, "cuembed_pyt: ", what, " must be 4-byte aligned");
+    bits |= reinterpret_cast<uintptr_t>(p);
+  }
+  const int64_t lane_bytes = bits % 16 == 0 ? 16 : (bits % 8 == 0 ? 8 : 4);
+  TORCH_CHECK(!limit_lanes || row_bytes / lane_bytes <= 1024, "cuembed_pyt: ", what, ": a row of ", row_bytes,
+              " bytes needs ", row_bytes / lane_bytes, " lanes of ", lane_bytes,
+              " bytes, more than 1024; align the data to 16 bytes");
+}
+
 int IndexBits(const int64_t num_categories) {
   if (num_categories <= 0) return 0;
   int bits = 1;
@@ -104,6 +124,7 @@ at::Tensor ForwardImpl(const at::Tensor& params, const at::Tensor& indices, cons
   const at::Tensor w = ContiguousOrUndefined(weights);
   const int64_t batch = o.numel() - 1;
   TORCH_CHECK(batch >= 0, "cuembed_pyt: offsets must hold batch_size + 1 entries");
+  CheckRowAlignment("params", p.size(1), p.element_size(), {Ptr(p)}, true);
   at::Tensor out = at::empty({batch, p.size(1)}, p.options());
   if (sample_order.defined())
     TORCH_CHECK(sample_order.is_cuda() && sample_order.scalar_type() == at::kInt && sample_order.numel() == batch &&
@@ -266,6 +287,7 @@ at::Tensor cuembed_embedding_backward_op(const at::Tensor& y_grad, const int64_t
   const at::DeviceGuard guard(y_grad.device());
   const at::Tensor g = y_grad.contiguous(), ti = transpose_indices.contiguous(),
                    ts = transpose_sample_ids.contiguous(), tw = ContiguousOrUndefined(transpose_weights);
+  CheckRowAlignment("y_grad", g.size(1), g.element_size(), {Ptr(g)}, true);
   at::Tensor grad = at::zeros({num_categories, g.size(1)}, g.options());
   ::cuembed_embedding_backward(Ptr(g), elem, static_cast<int>(g.size(1)), static_cast<int>(num_categories),
                                static_cast<int>(ti.numel()), Ptr(ti), Ptr(ts), nullptr, idx, Ptr(tw),
@@ -340,6 +362,7 @@ std::tuple<at::Tensor, at::Tensor> cuembed_embedding_backward_compressed_op(
   const at::Tensor g = y_grad.contiguous(), ti = transpose_indices.contiguous(),
                    ts = transpose_sample_ids.contiguous(), tr = transpose_remapped_indices.contiguous(),
                    tw = ContiguousOrUndefined(transpose_weights);
+  CheckRowAlignment("y_grad", g.size(1), g.element_size(), {Ptr(g)}, true);
   at::Tensor grad = at::empty({num_unique, g.size(1)}, g.options());
   at::Tensor inv = at::empty({num_unique}, ti.options());
   const int width = static_cast<int>(g.size(1)), nnz = static_cast<int>(ti.numel());
@@ -365,6 +388,7 @@ at::Tensor cuembed_embedding_forward_fixed_op(const at::Tensor& params, const at
   const at::Tensor p = params.contiguous(), i = indices.contiguous(), w = ContiguousOrUndefined(weights);
   const int64_t batch = i.size(0), hot = i.size(1), width = p.size(1);
   TORCH_CHECK(hot > 0, "cuembed_pyt: hotness must be positive");
+  CheckRowAlignment("params", width, p.element_size(), {Ptr(p)}, true);
   at::Tensor out = m == CUEMBED_CONCAT ? at::empty({batch, hot, width}, p.options()) : at::empty({batch, width}, p.options());
   if (batch > 0)
     ::cuembed_embedding_forward(Ptr(p), elem, static_cast<int>(width), Ptr(i), idx, nullptr, 0, Ptr(w),
@@ -386,6 +410,8 @@ at::Tensor cuembed_embedding_weight_grad_op(const at::Tensor& params, const at::
   const at::DeviceGuard guard(params.device());
   const at::Tensor p = params.contiguous(), i = indices.contiguous(), o = offsets.contiguous(), g = y_grad.contiguous();
   const int64_t batch = o.numel() - 1;
+  TORCH_CHECK(p.dim() == 2, "cuembed_pyt: params must be [num_categories, embed_width]");
+  CheckRowAlignment("params / y_grad", p.size(1), p.element_size(), {Ptr(p), Ptr(g)}, true);
   at::Tensor out = at::empty({i.numel()}, p.options());
   if (batch > 0 && i.numel() > 0)
     ::cuembed_embedding_weight_grad(Ptr(p), elem, static_cast<int>(p.size(1)), Ptr(i), idx, Ptr(o), off, Ptr(g),
@@ -564,6 +590,7 @@ class CuEmbEmbeddingNode : public torch::autograd::Function<CuEmbEmbeddingNode> 
     const at::DeviceGuard guard(out_grad.device());
     out_grad = out_grad.contiguous();
     const int64_t width = out_grad.size(1);
+    CheckRowAlignment("the incoming gradient", width, out_grad.element_size(), {Ptr(out_grad)}, true);
     const int64_t nnz = saved[0].numel();
     TORCH_CHECK(nnz <= INT32_MAX, "cuembed_pyt: the number of lookups must fit an int");
     const at::Tensor weights = weighted ? saved[2].contiguous() : at::Tensor();
@@ -684,6 +711,7 @@ void cuembed_sparse_row_update_op(at::Tensor table, const c10::optional<at::Tens
                   rows.size(0) == ids.numel() && table.is_contiguous() && rows.is_contiguous() && ids.is_contiguous(),
               "cuembed_pyt: table [rows, width], rows [entries, width] and ids [entries] must be contiguous and agree");
   TORCH_CHECK((table.size(1) * table.element_size()) % 4 == 0, "cuembed_pyt: the row size must be a multiple of 4 bytes");
+  CheckRowAlignment("table / rows", table.size(1), table.element_size(), {table.data_ptr(), Ptr(rows)}, false);
   at::Tensor state = state_arg.has_value() ? *state_arg : at::Tensor();
   if (code == CUEMBED_UPDATE_SGD) {
     TORCH_CHECK(!state.defined(), "cuembed_pyt: rule 'sgd' takes no state");
@@ -693,6 +721,10 @@ void cuembed_sparse_row_update_op(at::Tensor table, const c10::optional<at::Tens
                                                     : (state.dim() == 1 && state.size(0) == table.size(0))),
                 "cuembed_pyt: the state must be a contiguous float32 GPU tensor, [rows, width] for 'adagrad', [rows] for "
                 "'rowwise_adagrad'");
+    // a lane moves at least 4 bytes of the table, so 4 / sizeof(element) accumulator words at a time
+    const uintptr_t state_align = 4 * (4 / static_cast<uintptr_t>(table.element_size()));
+    TORCH_CHECK(code != CUEMBED_UPDATE_ADAGRAD || reinterpret_cast<uintptr_t>(state.data_ptr()) % state_align == 0,
+                "cuembed_pyt: the state must be ", state_align, "-byte aligned for a ", table.scalar_type(), " table");
   }
   const bool has_counts = counts.has_value() && counts->defined();
   const bool has_last = last_id.has_value() && last_id->defined();
@@ -777,6 +809,7 @@ void cuembed_sparse_row_adam_op(at::Tensor table, at::Tensor exp_avg, at::Tensor
                   rows.size(0) == ids.numel() && table.is_contiguous() && rows.is_contiguous() && ids.is_contiguous(),
               "cuembed_pyt: table [rows, width], rows [entries, width] and ids [entries] must be contiguous and agree");
   TORCH_CHECK((table.size(1) * table.element_size()) % 4 == 0, "cuembed_pyt: the row size must be a multiple of 4 bytes");
+  CheckRowAlignment("table / rows", table.size(1), table.element_size(), {table.data_ptr(), Ptr(rows)}, false);
   TORCH_CHECK(exp_avg.defined() && exp_avg.is_cuda() && exp_avg.scalar_type() == at::kFloat && exp_avg.is_contiguous() &&
                   exp_avg.sizes() == table.sizes(),
               "cuembed_pyt: exp_avg must be a contiguous float32 GPU tensor of the table's shape");
@@ -948,6 +981,7 @@ void cuembed_exchange_merge_op(const at::Tensor& ids, const at::Tensor& rows, co
                 "cuembed_pyt: count must be a contiguous int64 word");
     count_ptr = static_cast<int64_t*>(count->data_ptr());
   }
+  CheckRowAlignment("rows / out_rows", width, rows.element_size(), {Ptr(rows), out_rows.data_ptr()}, true);
   const at::DeviceGuard guard(rows.device());
   const cuembed_stream_t stream = CurrentStream(rows);
   at::Tensor t_idx = at::empty_like(ids), t_pos = at::empty_like(ids), remap = at::empty_like(ids);
@@ -1001,6 +1035,13 @@ int64_t QuantizedWidth(const at::Tensor& qtable) {
   return width;
 }
 
+// ... and what DequantizeRows / PlanQuantizedForward would abort on: more than 1,024 lanes of QuantizedCodesPerLane codes
+void CheckQuantizedLanes(const at::Tensor& qtable, const int64_t width) {
+  const int64_t codes = (width % 8 == 0 && reinterpret_cast<uintptr_t>(qtable.data_ptr()) % 8 == 0) ? 8 : 4;
+  TORCH_CHECK(width / codes <= 1024, "cuembed_pyt: qtable: a row of ", width, " codes needs ", width / codes, " lanes of ",
+              codes, " bytes, more than 1024; align the table to 8 bytes");
+}
+
 at::Tensor quantize_rows_op(const at::Tensor& table) {
   CheckGpu(table, "table");
   const int elem = ElemCode(table, "table");
@@ -1008,6 +1049,7 @@ at::Tensor quantize_rows_op(const at::Tensor& table) {
               "cuembed_pyt: table must be [rows, width] with a width that is a multiple of 4");
   const at::DeviceGuard guard(table.device());
   const at::Tensor t = table.contiguous();
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "cuembed_pyt: table must be 16-byte aligned");
   at::Tensor out = at::empty({t.size(0), t.size(1) + 8}, t.options().dtype(at::kByte));
   if (t.size(0) > 0)
     ::cuembed_quantize_rows(Ptr(t), elem, static_cast<int>(t.size(1)), t.size(0), MutPtr(out), CurrentStream(t));
@@ -1016,6 +1058,7 @@ at::Tensor quantize_rows_op(const at::Tensor& table) {
 
 at::Tensor dequantize_rows_op(const at::Tensor& qtable, const c10::optional<at::Tensor>& ids, const at::ScalarType dtype) {
   const int64_t width = QuantizedWidth(qtable);
+  CheckQuantizedLanes(qtable, width);
   const int out_code = OutCode(dtype, "dtype");
   const at::DeviceGuard guard(qtable.device());
   at::Tensor i;
@@ -1043,6 +1086,7 @@ at::Tensor cuemb_embedding_quantized_op(const at::Tensor& qtable, const at::Tens
                                         const c10::optional<at::Tensor>& sample_order,
                                         const c10::optional<at::Tensor>& row_loads_device) {
   const int64_t width = QuantizedWidth(qtable);
+  CheckQuantizedLanes(qtable, width);
   const int out_code = OutCode(out_dtype, "out_dtype");
   CheckGpu(indices, "indices");
   const int idx = IndexCode(indices, "indices");

@@ -54,6 +54,65 @@ def _index_code(name, t):
     return _INDEX[t.dtype]
 
 
+MAX_LANES_PER_ROW = 1024   # detail::kMaxBlockThreads: a row is split over at most this many lanes
+
+
+def _check_alignment(name, data_ptr, element_size, width, others=(), state=(), codes=False, max_lanes=MAX_LANES_PER_ROW):
+    """The lane width the native dispatchers pick for these base pointers, or ValueError where they would abort.
+    Integers only (no tensors, no GPU).  Returns the bytes of the row one lane moves: 16, 8 or 4.
+
+        SplitRow (embedding_lookup.hpp) and UpdateLaneBytes (sparse_update.hpp): the widest of 16 / 8 / 4 that divides
+            the row size (width * element_size) AND every data pointer -- `data_ptr` and the (name, pointer) pairs in
+            `others`;
+        UpdateLaneBytes, per-element fp32 state (Adagrad's accumulator, Adam's moments; `state`, (name, pointer)
+            pairs): a lane's N = bytes / element_size elements move 4 * min(N, 4) bytes of state at a time, and the lane
+            is halved until the state pointers allow that;
+        QuantizedCodesPerLane (quantized_lookup.hpp; codes=True, element_size 1): 8 when the width and the table's base
+            divide by 8, else 4.
+
+    Rejected: a data pointer that is not 4-byte aligned, a state pointer that the narrowest lane cannot use, and
+    (max_lanes; None for the kernels that loop over a row) a row of more than max_lanes lanes of that width."""
+    pointers = ((name, int(data_ptr)),) + tuple((n, int(p)) for n, p in others)
+    row_bytes = int(width) * int(element_size)
+    if width <= 0 or row_bytes % 4 != 0:
+        raise ValueError("the row size must be a multiple of 4 bytes, got %d elements of %d" % (width, element_size))
+    for n, p in pointers:
+        if p % 4 != 0:
+            raise ValueError("%s must be 4-byte aligned: its data pointer is %d bytes past a 4-byte boundary (a 16-bit "
+                             "tensor viewed an odd number of elements in?)" % (n, p % 4))
+    if codes:
+        lane = 8 if (width % 8 == 0 and int(data_ptr) % 8 == 0) else 4
+    else:
+        bits = row_bytes
+        for _, p in pointers:
+            bits |= p
+        lane = 16 if bits % 16 == 0 else (8 if bits % 8 == 0 else 4)
+    if state:
+        def state_align(lane_bytes):
+            per_lane = lane_bytes // element_size
+            return 4 * min(per_lane, 4)
+        state_bits = 0
+        for _, p in state:
+            state_bits |= int(p)
+        while lane > 4 and state_bits % state_align(lane) != 0:
+            lane //= 2
+        for n, p in state:
+            if int(p) % state_align(lane) != 0:
+                raise ValueError("%s must be %d-byte aligned for a table of %d-byte elements: the narrowest lane moves "
+                                 "that much of it" % (n, state_align(4), element_size))
+    if max_lanes is not None and row_bytes // lane > max_lanes:
+        fits = [b for b in ((4, 8) if codes else (4, 8, 16)) if row_bytes % b == 0 and row_bytes // b <= max_lanes]
+        if not fits:
+            raise ValueError("%s: a row of %d bytes is more than %d lanes at every lane width its size allows"
+                             % (name, row_bytes, max_lanes))
+        need = fits[0]
+        worst = [n for n, p in pointers if p % need != 0]
+        raise ValueError("%s: a row of %d bytes needs %d lanes of %d bytes, more than %d; %d-byte aligned data (%s) "
+                         "would make it fit" % (name, row_bytes, row_bytes // lane, lane, max_lanes, need,
+                                                ", ".join(worst) if worst else "all pointers"))
+    return lane
+
+
 def set_forward_reduction_order(order):
     """"sequential" (default, bit-identical to the reference for every batch size) or "split"
     (small batches may split a sample's hotness loop over wavefronts; equal up to fp rounding)."""
@@ -197,6 +256,7 @@ def embedding_forward(params, indices, offsets=None, weights=None, batch_size=No
         _check_dev("out", out, dev)
         if out.dtype != params.dtype or out.numel() != batch_size * (num_hots if m == CONCAT else 1) * width:
             raise ValueError("out has the wrong dtype or size")
+    _check_alignment("params", params.data_ptr(), params.element_size(), width, others=(("out", out.data_ptr()),))
     if batch_size > 0:
         with torch.cuda.device(params.device):   # the launch must happen on the tensors' device
             _lib.lib().cuembed_embedding_forward_device_hints(
@@ -285,6 +345,10 @@ def embedding_weight_grad(params, indices, grad_y, offsets=None, batch_size=None
         batch_size = indices.numel() // num_hots
     if grad_y.shape[0] < batch_size:
         raise ValueError("grad_y must have one row per sample")
+    if params.dim() != 2:
+        raise ValueError("params must be [rows, width]")
+    _check_alignment("params", params.data_ptr(), params.element_size(), params.shape[1],
+                     others=(("grad_y", grad_y.data_ptr()),))
     out = torch.empty((indices.numel(),), dtype=params.dtype, device=dev)
     if batch_size > 0 and indices.numel() > 0:
         with torch.cuda.device(params.device):   # the launch must happen on the tensors' device
@@ -401,6 +465,8 @@ def embedding_backward(grad_y, num_grad_embedding_rows, transpose_indices, trans
             raise TypeError("block_row_ids must be int32 (uint32 bit patterns)")
     else:
         block_row_ids = None
+    _check_alignment("grad_y", grad_y.data_ptr(), grad_y.element_size(), width,
+                     others=(("grad_embedding", grad_embedding.data_ptr()),))
     if reference_sums:
         if unknown_rows or sample_blocks > 1:
             raise ValueError("reference_sums needs a host-known row count and a fully sorted order")
@@ -872,6 +938,9 @@ def sparse_row_update(table, ids, rows, *, rule, lr, state=None, eps=1e-8, count
                     ("lr", lr_word), ("step", step_word)):
         if t is not None:
             _check_dev(name, t, dev)
+    # (the update kernels loop over a row: no limit on its lanes)
+    _check_alignment("table", table.data_ptr(), table.element_size(), width, others=(("rows", rows.data_ptr()),),
+                     state=(("state", state.data_ptr()),) if rule == "adagrad" else (), max_lanes=None)
     if n == 0:
         return None
     with torch.cuda.device(dev):
@@ -1006,6 +1075,8 @@ def sparse_row_adam(table, ids, rows, *, exp_avg, exp_avg_sq, lr, bias_factor=1.
                     ("step", step_word)):
         if t is not None:
             _check_dev(name, t, dev)
+    _check_alignment("table", table.data_ptr(), table.element_size(), width, others=(("rows", rows.data_ptr()),),
+                     max_lanes=None)
     # the narrowest lane is 4 bytes of the row: one fp32 element of state for a float32 table, two for a 16-bit one
     state_align = 4 * (4 // table.element_size())
     for name, t in (("exp_avg", exp_avg),) + ((("exp_avg_sq", exp_avg_sq),) if not rowwise else ()):

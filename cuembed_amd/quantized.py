@@ -19,7 +19,7 @@ import ctypes
 import torch
 
 from . import _lib
-from .ops import _MODES, _ROW_LOADS, CONCAT, _check_dev, _elem_code, _index_code, _ptr, _stream
+from .ops import _MODES, _ROW_LOADS, CONCAT, _check_alignment, _check_dev, _elem_code, _index_code, _ptr, _stream
 
 TRAILER_BYTES = 8                                   # fp32 scale + fp32 bias
 _OUT = {torch.float32: 0, torch.float16: 1}
@@ -77,6 +77,8 @@ def quantize_rows(table, out=None):
         _check_dev("out", out, table.device)
         if out.dtype != torch.uint8 or tuple(out.shape) != (rows, width + TRAILER_BYTES) or out.data_ptr() % 4 != 0:
             raise ValueError("out must be a 4-byte aligned uint8 tensor [rows, width + 8]")
+    # (the quantizer's lane groups loop over a row: no limit on its lanes)
+    _check_alignment("out", out.data_ptr(), 1, width, codes=True, max_lanes=None)
     if rows > 0:
         with torch.cuda.device(table.device):
             _lib.lib().cuembed_quantize_rows(_ptr(table), et, width, rows, _ptr(out), _stream(table))
@@ -108,6 +110,7 @@ def dequantize_rows(qtable, ids=None, dtype=torch.float32, out=None):
         _check_dev("out", out, qtable.device)
         if out.dtype != dtype or out.numel() != n * width or out.data_ptr() % 16 != 0:
             raise ValueError("out has the wrong dtype, size or alignment (16 bytes)")
+    _check_alignment("qtable", qtable.data_ptr(), 1, width, codes=True)
     if n > 0:
         with torch.cuda.device(qtable.device):
             _lib.lib().cuembed_dequantize_rows(_ptr(qtable), width, _ptr(ids), it, n, _ptr(out), oc, _stream(qtable))
@@ -208,6 +211,7 @@ def embedding_forward_quantized(qtable, indices, offsets=None, weights=None, bat
             raise ValueError("out has the wrong dtype or size")
         if out.data_ptr() % 16 != 0:
             raise ValueError("out must be 16-byte aligned")
+    _check_alignment("qtable", qtable.data_ptr(), 1, width, codes=True)
     if batch_size > 0:
         with torch.cuda.device(dev):   # the launch must happen on the tensors' device
             _lib.lib().cuembed_embedding_forward_quantized(

@@ -166,6 +166,23 @@ def forward_split_bound(kind, exact, scale, hot):
     return EPS[kind] * np.abs(exact) + (h + 4.0) * 2.0 ** -24 * scale + SPACING[kind]
 
 
+def assert_split_forward_within_bound(kind, fp16_math, g, exact, scale, hot, ora, mean, label):
+    """What a forward under reduction_order="split" is held to (g, ora: the device's and the oracle's result as fp64).
+    fp32 partials: the per-element bound above, and zeros for empty bags.  fp16 partials (fp16_math): per-element
+    sensitivity is weak; per row, no more than twice the oracle's RMS error (a mean also scales the row by a
+    reciprocal rounded to fp16 once: EPS of the row's RMS)."""
+    if fp16_math:
+        rms = np.sqrt(((g - exact) ** 2).mean(axis=1))
+        rms_ora = np.sqrt(((ora - exact) ** 2).mean(axis=1))
+        recip = EPS["f16"] * np.sqrt((exact ** 2).mean(axis=1)) if mean else 0.0
+        assert np.all(rms <= 2.0 * rms_ora + recip + SPACING["f16"]), label
+        return
+    bound = forward_split_bound(kind, exact, scale, hot)
+    worst = np.unravel_index(np.argmax(np.abs(g - exact) - bound), g.shape)
+    assert np.all(np.abs(g - exact) <= bound), (label, worst, g[worst], exact[worst], bound[worst])
+    assert np.all(g[hot == 0] == 0)
+
+
 # ---- 16-bit conversions in numpy (round to nearest even), used by the host-side simulations ----
 def round_bf16(a):
     x = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)

@@ -195,6 +195,93 @@ def test_forward_meets_the_bound_on_every_element(ce, layout, width, hot):
     print("worst |got - exact| / bound: %.3f (%s, W=%d, H=%d)" % (worst, layout, width, hot))
 
 
+# (hotness, index type, weighted, output, width, lanes per row): a sample's indices (+ weights) exceed the 16 KiB staging
+# budget, so the kernel reads them through the wavefront shuffle (lanes | 64) or from global memory (9 lanes)
+UNSTAGED = [(1400, torch.int64, True, "f32", 64, 4), (1400, torch.int64, True, "f32", 36, 9),     # 12 B x 1400
+            (1700, torch.int64, True, "f16", 64, 4), (1700, torch.int64, True, "f16", 36, 9),     # 10 B x 1700
+            (4100, torch.int32, False, "f32", 256, 16), (4100, torch.int32, False, "f16", 256, 16)]   # 4 B x 4100
+
+
+@pytest.mark.parametrize("hot,idt,weighted,out,width,lanes", UNSTAGED,
+                         ids=lambda v: str(v).replace("torch.", "") if not isinstance(v, bool) else ("w" if v else "u"))
+def test_fixed_hotness_too_long_to_stage(ce, hot, idt, weighted, out, width, lanes):
+    """The fixed-hotness forward's two index sources besides LDS staging (begin = sample * num_hots): every element
+    inside pooled64's bound, and bit-identical to the CSR form of the same bags.  fp16 output: mean, or a sum whose
+    weights are scaled by 1 / H -- every exact value is checked to fit fp16 first."""
+    batch = 5 if hot < 4000 else 3
+    shape = ce.quantized_forward_launch_shape(idt, _TORCH[out], width, batch, hot, is_weighted=weighted, compute_units=0)
+    assert shape["staged"] is False and shape["lanes_per_row"] == lanes and shape["lds_bytes"] == 0
+    assert hot * (idt.itemsize + (_TORCH[out].itemsize if weighted else 0)) > 16 * 1024
+    rng = np.random.default_rng(hot + width)
+    q = ce.quantize_rows(torch.from_numpy(_tame_table(width, rows_per_regime=100, seed=hot)).to(DEV))
+    q_np = q.cpu().numpy()
+    idx_np = rng.integers(0, q_np.shape[0], batch * hot)
+    idx = torch.from_numpy(idx_np).to(DEV, idt)
+    off = torch.arange(0, batch * hot + 1, hot, device=DEV, dtype=idt)
+    for mode in ("sum", "mean"):
+        w_np = None
+        if weighted:
+            w_np = (rng.uniform(-1, 1, batch * hot) / (hot if out == "f16" else 1) if mode == "sum"
+                    else rng.uniform(0.25, 1.25, batch * hot)).astype(_NP[out])
+        elif out == "f16" and mode == "sum":
+            continue                                  # (4,100 unweighted values of up to 31 do not fit fp16: mean only)
+        exact, bound = R.pooled64(q_np, idx_np, num_hots=hot, weights=w_np, mode=mode, out=out)
+        if out == "f16":
+            assert np.abs(exact).max() < 65504.0       # finite in fp16, from the exact values alone
+        w = None if w_np is None else torch.from_numpy(w_np).to(DEV)
+        got = ce.embedding_forward_quantized(q, idx, num_hots=hot, weights=w, mode=mode, out_dtype=_TORCH[out])
+        got_np = got.float().cpu().numpy()
+        assert np.isfinite(got_np).all() and got_np.any()
+        ratio = R.worst_ratio(got_np, exact, bound)
+        print("worst |got - exact| / bound: %.3f (H=%d, W=%d, %s, %s)" % (ratio, hot, width, out, mode))
+        assert ratio <= 1.0, (hot, width, out, mode, ratio)
+        as_csr = ce.embedding_forward_quantized(q, idx, offsets=off, weights=w, mode=mode, out_dtype=_TORCH[out])
+        assert np.array_equal(_bits(got), _bits(as_csr)), (hot, width, out, mode)
+
+
+@pytest.mark.parametrize("out", ["f32", "f16"])
+@pytest.mark.parametrize("width", [36, 256])
+def test_weighted_mean_of_a_zero_weight_sum_is_zero(ce, width, out):
+    """Pairs of +w, -w (representable in the weight type) sum to exactly zero in any fp32 order: the mean of such a bag
+    is zeros, as the docstring promises, next to ordinary bags in the same batch -- fixed hotness and CSR."""
+    rng = np.random.default_rng(width)
+    q = ce.quantize_rows(torch.from_numpy(_tame_table(width, rows_per_regime=100, seed=5)).to(DEV))
+    q_np = q.cpu().numpy()
+
+    def weights_of(lengths, zero_bags):
+        parts = []
+        for s, n in enumerate(lengths):
+            w = rng.uniform(0.25, 1.25, n).astype(_NP[out])
+            if s in zero_bags:
+                assert n % 2 == 0 and n > 0
+                w[1::2] = -w[0::2]
+            parts.append(w)
+        return np.concatenate(parts)
+
+    batch, hot = 12, 6
+    layouts = [(np.full(batch, hot), {0, 5, 11}, None)]
+    lengths = np.array([4, 0, 7, 2, 9, 6, 0, 1, 30, 3, 8, 2])
+    layouts.append((lengths, {0, 3, 5, 8, 11}, np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)))
+    for lengths, zero_bags, off_np in layouts:
+        w_np = weights_of(lengths, zero_bags)
+        assert w_np.dtype == _NP[out]
+        idx_np = rng.integers(0, q_np.shape[0], int(lengths.sum()))
+        exact, bound = R.pooled64(q_np, idx_np, offsets=off_np, num_hots=0 if off_np is not None else hot, weights=w_np,
+                                  mode="mean", out=out)
+        zero = np.zeros(batch, dtype=bool)
+        zero[sorted(zero_bags)] = True
+        assert not exact[zero].any() and exact[~zero & (lengths > 0)].any(axis=1).all()
+        for idt in (torch.int32, torch.int64):
+            got = ce.embedding_forward_quantized(
+                q, torch.from_numpy(idx_np).to(DEV, idt), offsets=None if off_np is None else torch.from_numpy(off_np).to(DEV, idt),
+                weights=torch.from_numpy(w_np).to(DEV), num_hots=0 if off_np is not None else hot, mode="mean",
+                out_dtype=_TORCH[out])
+            got_np = got.float().cpu().numpy()
+            assert (got_np[zero] == 0.0).all(), (width, out, off_np is not None)          # exact zeros (of either sign)
+            assert R.worst_ratio(got_np, exact, bound) <= 1.0
+            assert got_np[~zero & (lengths > 0)].any(axis=1).all()
+
+
 # ---- order and determinism, bit for bit ------------------------------------------------------------------------------
 @pytest.mark.parametrize("width", [36, 256, 512])
 @pytest.mark.parametrize("weighted", [False, True])

@@ -132,19 +132,8 @@ def test_split_forward_per_element_bound(ce, oracle, kind, fp16_math, W):
                 want = oracle.embedding_forward(t_o, ids, o if csr else None, wo, num_hots=0 if csr else H, mode=mode,
                                                 fp16_math=fp16_math)
                 ora = oracle.from_bf16_bits(want).astype(np.float64) if kind == "bf16" else want.astype(np.float64)
-                label = (mode, weighted, csr)
-                if fp16_math:
-                    # fp16 partials: per-element sensitivity is weak; per row, no more than twice the oracle's RMS
-                    # (a mean also scales the row by a reciprocal rounded to fp16 once: EPS of the row's RMS)
-                    rms = np.sqrt(((g - exact) ** 2).mean(axis=1))
-                    rms_ora = np.sqrt(((ora - exact) ** 2).mean(axis=1))
-                    recip = X.EPS["f16"] * np.sqrt((exact ** 2).mean(axis=1)) if mode == "mean" else 0.0
-                    assert np.all(rms <= 2.0 * rms_ora + recip + X.SPACING["f16"]), label
-                    continue
-                bound = X.forward_split_bound(kind, exact, scale, hot)
-                worst = np.unravel_index(np.argmax(np.abs(g - exact) - bound), g.shape)
-                assert np.all(np.abs(g - exact) <= bound), (label, worst, g[worst], exact[worst], bound[worst])
-                assert np.all(g[hot == 0] == 0)
+                X.assert_split_forward_within_bound(kind, fp16_math, g, exact, scale, hot, ora, mode == "mean",
+                                                    (mode, weighted, csr))
     finally:
         ce.set_forward_reduction_order("sequential")
     assert ce.get_forward_reduction_order() == "sequential"
