@@ -4,7 +4,7 @@
 #ifndef CUEMBED_AMD_C_API_OPTIMIZER_ADAM_COMMON_HPP_
 #define CUEMBED_AMD_C_API_OPTIMIZER_ADAM_COMMON_HPP_
 
-#include "c_api_common.hpp"
+#include "c_api_optimizer_common.hpp"
 #include "cuembed/include/sparse_adam.hpp"
 
 namespace cuembed_c_api {
@@ -22,8 +22,7 @@ inline cuembed::SparseAdamOptions AdamOptions(int rule, int64_t piece_rows, int 
       std::cerr << "Check failed: unknown Adam rule at " << __FILE__ << ":" << __LINE__ << std::endl;
       std::abort();
   }
-  o.lr = lr;
-  o.lr_device = lr_device;
+  FillStepOptions(o, piece_rows, pieces, num_rows, counts, counts_are_int64, last_id, lr, lr_device);
   o.bias_factor = bias_factor;
   o.bias_factor_device = bias_factor_device;
   o.beta1 = beta1;
@@ -32,12 +31,6 @@ inline cuembed::SparseAdamOptions AdamOptions(int rule, int64_t piece_rows, int 
   o.one_minus_beta2 = one_minus_beta2;
   o.eps = eps;
   o.weight_decay = weight_decay;
-  o.piece_rows = piece_rows;
-  o.pieces = pieces;
-  o.num_rows = num_rows;
-  o.counts = counts;
-  o.counts_are_int64 = counts_are_int64 != 0;
-  o.last_id = last_id;
   return o;
 }
 

@@ -14,10 +14,7 @@ void cuembed_sparse_row_adam_stochastic(void* table, int elem_type, int embed_wi
   cuembed::SparseAdamOptions o = cuembed_c_api::AdamOptions(
       rule, piece_rows, pieces, num_rows, counts, counts_are_int64, last_id, lr, lr_device, bias_factor,
       bias_factor_device, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay);
-  o.stochastic_rounding = true;
-  o.rounding_seed = seed;
-  o.rounding_step = step;
-  o.rounding_step_device = step_device;
+  cuembed_c_api::FillStochasticRounding(o, seed, step, step_device);
 #define ADAM(E, I) \
   cuembed_c_api::Adam<E, I, cuembed::UpdateRoundings::kStochasticOnly>(table, exp_avg, exp_avg_sq, embed_width, ids, rows, o, stream)
   switch ((elem_type << 1) | index_type) {

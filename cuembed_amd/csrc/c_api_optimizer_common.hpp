@@ -8,6 +8,27 @@
 
 namespace cuembed_c_api {
 
+//! The fields that the options of every sparse step share (also c_api_optimizer_adam_common.hpp's).
+inline void FillStepOptions(cuembed::SparseStepOptions& o, int64_t piece_rows, int pieces, int64_t num_rows,
+                            const void* counts, int counts_are_int64, const void* last_id, float lr,
+                            const float* lr_device) {
+  o.lr = lr;
+  o.lr_device = lr_device;
+  o.piece_rows = piece_rows;
+  o.pieces = pieces;
+  o.num_rows = num_rows;
+  o.counts = counts;
+  o.counts_are_int64 = counts_are_int64 != 0;
+  o.last_id = last_id;
+}
+
+inline void FillStochasticRounding(cuembed::SparseStepOptions& o, uint64_t seed, uint64_t step, const int64_t* step_device) {
+  o.stochastic_rounding = true;
+  o.rounding_seed = seed;
+  o.rounding_step = step;
+  o.rounding_step_device = step_device;
+}
+
 inline cuembed::SparseUpdateOptions UpdateOptions(int rule, int64_t piece_rows, int pieces, int64_t num_rows,
                                                   const void* counts, int counts_are_int64, const void* last_id, float lr,
                                                   const float* lr_device, float eps) {
@@ -20,15 +41,8 @@ inline cuembed::SparseUpdateOptions UpdateOptions(int rule, int64_t piece_rows, 
       std::cerr << "Check failed: unknown update rule at " << __FILE__ << ":" << __LINE__ << std::endl;
       std::abort();
   }
-  o.lr = lr;
-  o.lr_device = lr_device;
+  FillStepOptions(o, piece_rows, pieces, num_rows, counts, counts_are_int64, last_id, lr, lr_device);
   o.eps = eps;
-  o.piece_rows = piece_rows;
-  o.pieces = pieces;
-  o.num_rows = num_rows;
-  o.counts = counts;
-  o.counts_are_int64 = counts_are_int64 != 0;
-  o.last_id = last_id;
   return o;
 }
 

@@ -13,10 +13,7 @@ void cuembed_sparse_row_update_stochastic(void* table, int elem_type, int embed_
                                           cuembed_stream_t stream) {
   cuembed::SparseUpdateOptions o = cuembed_c_api::UpdateOptions(rule, piece_rows, pieces, num_rows, counts,
                                                                 counts_are_int64, last_id, lr, lr_device, eps);
-  o.stochastic_rounding = true;
-  o.rounding_seed = seed;
-  o.rounding_step = step;
-  o.rounding_step_device = step_device;
+  cuembed_c_api::FillStochasticRounding(o, seed, step, step_device);
 #define UPD(E, I) \
   cuembed_c_api::Update<E, I, cuembed::UpdateRoundings::kStochasticOnly>(table, state, embed_width, ids, rows, o, stream)
   switch ((elem_type << 1) | index_type) {

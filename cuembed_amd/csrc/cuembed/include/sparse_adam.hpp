@@ -15,11 +15,9 @@
 
 namespace cuembed {
 
-//! Rule, hyper-parameters and the source of the entry count of one SparseRowAdam call.
-struct SparseAdamOptions {
+//! Rule, hyper-parameters and (SparseStepOptions) learning rate, entries, count source and rounding of one SparseRowAdam call.
+struct SparseAdamOptions : SparseStepOptions {
   AdamRule rule = AdamRule::kAdam;
-  float lr = 0.f;                             //!< learning rate, unless ...
-  const float* lr_device = nullptr;           //!< ... one fp32 word on the device holds it
   float bias_factor = 1.f;                    //!< c = sqrt(1 - beta2^t) / (1 - beta1^t) of step t (1: no correction), unless ...
   const float* bias_factor_device = nullptr;  //!< ... one fp32 word on the device holds it (AdamClockAdvance writes it)
   //! The kernel multiplies with these fp32 values as they are: form 1 - beta in double and round it once.
@@ -27,88 +25,7 @@ struct SparseAdamOptions {
   float beta2 = 0.999f, one_minus_beta2 = 0.001f;
   float eps = 1e-8f;                          //!< added to sqrt(v)
   float weight_decay = 0.f;                   //!< decoupled (AdamW): w <- w - (lr * weight_decay) * w on the named rows; 0: off
-  //! The entries are `pieces` blocks of `piece_rows` entries; entry j of piece p is valid iff j < count(p).
-  int64_t piece_rows = 0;
-  int pieces = 1;
-  //! Exactly one source of the counts (see SparseUpdateOptions):
-  int64_t num_rows = -1;
-  const void* counts = nullptr;
-  bool counts_are_int64 = false;
-  const void* last_id = nullptr;
-  //! Stochastic rounding of the one rounding to the table's type (see SparseUpdateOptions).
-  bool stochastic_rounding = false;
-  uint64_t rounding_seed = 0;
-  uint64_t rounding_step = 0;
-  const int64_t* rounding_step_device = nullptr;
 };
-
-namespace detail {
-
-//! Entries a lane group keeps in flight when a lane holds one slice per entry.  With the two moment packs of a slice
-//! next to its weights and gradient, two entries take 32 (fp32) to 48 (16-bit) registers of row data per lane: every
-//! instantiation stays free of scratch and at or above 4 waves per SIMD (profiles/sparse_adam_kernel_resources.txt).
-constexpr int kAdamEntriesInFlight = 2;
-
-template <typename ElemT, typename IndexT, int N, AdamRule kRule, bool kStochastic>
-inline void LaunchSparseRowAdam(ElemT* table, float* exp_avg, float* exp_avg_sq, const int width, const IndexT* ids,
-                                const ElemT* rows, const SparseAdamOptions& o, const UpdateCounts& counts,
-                                const hipStream_t stream) {
-  const UpdateShape s = PlanUpdate(width / N, o.piece_rows * o.pieces, CurrentDeviceShape());
-  UpdateRounding<kStochastic> rounding;
-  if constexpr (kStochastic) {
-    rounding.seed = o.rounding_seed;
-    rounding.step = o.rounding_step;
-    rounding.step_word = o.rounding_step_device;
-  }
-  AdamScalars h;
-  h.beta1 = o.beta1;
-  h.one_minus_beta1 = o.one_minus_beta1;
-  h.beta2 = o.beta2;
-  h.one_minus_beta2 = o.one_minus_beta2;
-  h.eps = o.eps;
-  h.weight_decay = o.weight_decay;
-#define CUEMBED_LAUNCH_ADAM(CHUNKS, ENTRIES)                                                                        \
-  SparseRowAdamKernel<ElemT, IndexT, N, kRule, CHUNKS, ENTRIES, kStochastic>                                        \
-      <<<dim3(s.grid), dim3(kUpdateBlockThreads), 0, stream>>>(ids, rows, table, exp_avg, exp_avg_sq, width,         \
-                                                               s.lanes_per_row, s.group, o.piece_rows, o.pieces,    \
-                                                               counts, o.lr, o.lr_device, o.bias_factor,            \
-                                                               o.bias_factor_device, h, rounding)
-  if (s.chunks == 1) CUEMBED_LAUNCH_ADAM(1, kAdamEntriesInFlight);
-  else if (s.chunks == kUpdateMaxChunks) CUEMBED_LAUNCH_ADAM(kUpdateMaxChunks, 1);
-  else CUEMBED_LAUNCH_ADAM(0, 1);
-#undef CUEMBED_LAUNCH_ADAM
-}
-
-template <typename ElemT, typename IndexT, int N, bool kStochastic>
-inline void LaunchSparseRowAdamRule(ElemT* table, float* exp_avg, float* exp_avg_sq, const int width, const IndexT* ids,
-                                    const ElemT* rows, const SparseAdamOptions& o, const UpdateCounts& counts,
-                                    const hipStream_t stream) {
-  switch (o.rule) {
-    case AdamRule::kAdam:
-      return LaunchSparseRowAdam<ElemT, IndexT, N, AdamRule::kAdam, kStochastic>(table, exp_avg, exp_avg_sq, width, ids, rows, o,
-                                                                                counts, stream);
-    case AdamRule::kRowwiseAdam:
-      return LaunchSparseRowAdam<ElemT, IndexT, N, AdamRule::kRowwiseAdam, kStochastic>(table, exp_avg, exp_avg_sq, width, ids,
-                                                                                       rows, o, counts, stream);
-  }
-  CUEMBED_ASSERT(false && "unknown Adam rule");
-}
-
-//! The lane width's instantiation: N = 16 / 8 / 4 bytes of ElemT.
-template <typename ElemT, typename IndexT, bool kStochastic>
-inline void LaunchSparseRowAdamBytes(const int bytes, ElemT* table, float* exp_avg, float* exp_avg_sq, const int width,
-                                     const IndexT* ids, const ElemT* rows, const SparseAdamOptions& o,
-                                     const UpdateCounts& counts, const hipStream_t stream) {
-  constexpr int kMaxN = 16 / static_cast<int>(sizeof(ElemT));
-  if (bytes == 16)
-    LaunchSparseRowAdamRule<ElemT, IndexT, kMaxN, kStochastic>(table, exp_avg, exp_avg_sq, width, ids, rows, o, counts, stream);
-  else if (bytes == 8)
-    LaunchSparseRowAdamRule<ElemT, IndexT, kMaxN / 2, kStochastic>(table, exp_avg, exp_avg_sq, width, ids, rows, o, counts, stream);
-  else
-    LaunchSparseRowAdamRule<ElemT, IndexT, kMaxN / 4, kStochastic>(table, exp_avg, exp_avg_sq, width, ids, rows, o, counts, stream);
-}
-
-}  // namespace detail
 
 /**
  * @brief Sparse Adam step: for every valid entry k, table[ids[k], :] and the moments of row ids[k] are updated in place
@@ -147,37 +64,37 @@ void SparseRowAdam(ElemT* table,
   static_assert(std::is_same<IndexT, int32_t>::value || std::is_same<IndexT, int64_t>::value,
                 "SparseRowAdam: ids must be int32_t or int64_t");
   using DevT = detail::DeviceElemT<ElemT>;
-  const int sources = (options.num_rows >= 0) + (options.counts != nullptr) + (options.last_id != nullptr);
-  CUEMBED_ASSERT(sources == 1);
-  CUEMBED_ASSERT(options.pieces >= 1 && options.piece_rows >= 0);
-  CUEMBED_ASSERT(options.pieces == 1 || options.counts != nullptr);   // several pieces: counts[pieces] on the device
-  if (options.num_rows >= 0) CUEMBED_ASSERT(options.num_rows <= options.piece_rows);
+  detail::CheckCountSource(options);
   CUEMBED_ASSERT(options.beta1 >= 0.f && options.beta1 < 1.f && options.beta2 >= 0.f && options.beta2 < 1.f);
   CUEMBED_ASSERT(options.eps >= 0.f && options.weight_decay >= 0.f);
-  constexpr bool kCanRoundStochastically = !std::is_same<ElemT, float>::value && kRoundings != UpdateRoundings::kNearestOnly;
-  CUEMBED_ASSERT(!options.stochastic_rounding || kCanRoundStochastically);
-  CUEMBED_ASSERT(options.stochastic_rounding || kRoundings != UpdateRoundings::kStochasticOnly);
-  if (options.piece_rows == 0 || options.num_rows == 0) return;
-  CUEMBED_ASSERT(table != nullptr && ids != nullptr && rows != nullptr);
+  if (!detail::CheckRoundingAndWork<ElemT, kRoundings>(options, table, ids, rows)) return;
   CUEMBED_ASSERT(exp_avg != nullptr && exp_avg_sq != nullptr);
   CUEMBED_ASSERT(reinterpret_cast<uintptr_t>(exp_avg_sq) % 4 == 0);
   const int bytes = detail::UpdateLaneBytes<DevT>(embed_width, table, rows, exp_avg, true,
                                                   options.rule == AdamRule::kAdam ? exp_avg_sq : nullptr);
-  detail::UpdateCounts counts;
-  counts.host_count = options.num_rows >= 0 ? options.num_rows : -1;
-  counts.count_words = options.counts;
-  counts.count_words_are_64 = options.counts_are_int64 ? 1 : 0;
-  counts.last_id = options.last_id;
+  const detail::UpdateCounts counts = detail::CountsOf(options);
+  const detail::AdamScalars h = {options.beta1, options.one_minus_beta1, options.beta2, options.one_minus_beta2,
+                                 options.eps, options.weight_decay};
   DevT* t = reinterpret_cast<DevT*>(table);
   const DevT* g = reinterpret_cast<const DevT*>(rows);
-  if constexpr (kCanRoundStochastically) {
-    if (options.stochastic_rounding)
-      return detail::LaunchSparseRowAdamBytes<DevT, IndexT, true>(bytes, t, exp_avg, exp_avg_sq, embed_width, ids, g, options,
-                                                                  counts, stream);
-  }
-  if constexpr (kRoundings != UpdateRoundings::kStochasticOnly)
-    detail::LaunchSparseRowAdamBytes<DevT, IndexT, false>(bytes, t, exp_avg, exp_avg_sq, embed_width, ids, g, options, counts,
-                                                          stream);
+  detail::DispatchUpdate<DevT, kRoundings>(
+      bytes, embed_width, options, [&](auto stochastic, auto n, auto chunks, const detail::UpdateShape& s) {
+        const auto with_rule = [&](auto rule) {
+          // entries in flight: two when a lane holds one slice per entry (WalkNamedRows)
+          constexpr int kChunks = decltype(chunks)::value;
+          detail::SparseRowAdamKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, kChunks,
+                                      kChunks == 1 ? 2 : 1, decltype(stochastic)::value>
+              <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), 0, stream>>>(
+                  ids, g, t, exp_avg, exp_avg_sq, embed_width, s.lanes_per_row, s.group, options.piece_rows,
+                  options.pieces, counts, options.lr, options.lr_device, options.bias_factor, options.bias_factor_device,
+                  h, detail::RoundingOf<decltype(stochastic)::value>(options));
+        };
+        switch (options.rule) {
+          case AdamRule::kAdam: return with_rule(std::integral_constant<AdamRule, AdamRule::kAdam>());
+          case AdamRule::kRowwiseAdam: return with_rule(std::integral_constant<AdamRule, AdamRule::kRowwiseAdam>());
+        }
+        CUEMBED_ASSERT(false && "unknown Adam rule");
+      });
 }
 
 /**

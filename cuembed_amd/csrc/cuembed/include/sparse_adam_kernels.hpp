@@ -1,10 +1,8 @@
 // MI355X (gfx950 / CDNA4) sparse optimizer step, the Adam family -- the kernels.
 //
-// The structure is SparseRowUpdateKernel's (sparse_update_kernels.hpp): one power-of-two lane group per gradient entry,
-// 16 / 8 / 4 bytes of the row per lane and slice, kChunks slices per lane in registers (1, 4, or 0 = a run-time loop),
-// the ids of an iteration first, then every load of the iteration, then the arithmetic and the stores; gradient rows
-// with non-temporal loads; the entry counts read on the device (UpdateCounts); no atomics on table data, so the valid
-// entries must name DISTINCT rows.  What is new is the state: two fp32 tensors.
+// The walk over the named rows is the one of every rule (WalkNamedRows, sparse_update_kernels.hpp: lane groups, slices,
+// entries in flight, device-side counts, DISTINCT rows).  What is Adam's is here: the scalars, the arithmetic of a slice
+// and of a row, the rule type that hands them to the walk, and the bias-factor clock.  The state is two fp32 tensors.
 //
 //   * kAdam: exp_avg and exp_avg_sq are [rows, width]; a lane moves 2 * N fp32 state elements per slice next to its N
 //     weights and N gradient elements (22 bytes per fp16 element against Adagrad's 14).
@@ -110,12 +108,32 @@ __device__ __forceinline__ float RowwiseAdamScale(float* v_of_row, const float b
   return z.step / Arith<float>::add(sqrtf(v_new), h.eps);
 }
 
+//! The two rules as the walk sees them (WalkNamedRows, sparse_update_kernels.hpp): exp_avg is per element; exp_avg_sq
+//! is per element (kAdam) or the row's word (kRowwiseAdam).
+template <AdamRule kRule>
+struct AdamStepRule {
+  static constexpr bool kRowState = kRule == AdamRule::kRowwiseAdam;
+  static constexpr int kStates = kRowState ? 1 : 2;
+  AdamStepSizes z;
+  AdamScalars h;
+  __device__ __forceinline__ float Row(float* word, const float before, const float sum, const int width,
+                                       const bool store) const {
+    return RowwiseAdamScale(word, before, sum, width, store, z, h);
+  }
+  template <typename ElemT, int N, typename RoundT>
+  __device__ __forceinline__ Pack<ElemT, N> Slice(const Pack<ElemT, N>& w, const Pack<ElemT, N>& g, StatePack<N>* s,
+                                                  const float row, const RoundT& round) const {
+    if constexpr (kRowState) return RowwiseAdamStep(w, g, s[0], row, z, h, round);
+    else return AdamStep(w, g, s[0], s[1], z, h, round);
+  }
+};
+
 /**
  * @brief table[ids[k], :] and the moments of row ids[k] <- rule(table[ids[k], :], rows[k, :]) for every valid entry k.
  *
  * Launch: as SparseRowUpdateKernel -- 1-D grid of kUpdateBlockThreads-thread workgroups, `group` (a power of two <= 64)
  * lanes per entry, lanes_per_row = width / N slices per row; kChunks >= 1 needs lanes_per_row <= kChunks * group.
- * kEntries (1 or 2) entries are in flight per group when kChunks == 1.
+ * kEntriesInFlight (1 or 2) entries are in flight per group when kChunks == 1.
  */
 template <typename ElemT, typename IndexT, int N, AdamRule kRule, int kChunks, int kEntriesInFlight, bool kStochastic = false>
 __global__ void __launch_bounds__(kUpdateBlockThreads)
@@ -125,128 +143,11 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
                         const UpdateCounts counts, const float lr_value, const float* __restrict__ lr_word,
                         const float bias_value, const float* __restrict__ bias_word, const AdamScalars h,
                         const UpdateRounding<kStochastic> rounding = UpdateRounding<kStochastic>()) {
-  static_assert(!kStochastic || sizeof(ElemT) == 2, "stochastic rounding is for the 16-bit table types");
-  static_assert(kEntriesInFlight == 1 || (kEntriesInFlight == 2 && kChunks == 1), "two entries in flight: one slice per lane");
-  using RoundT = SliceRounding<ElemT, N, kStochastic>;
-  constexpr bool kRowwise = kRule == AdamRule::kRowwiseAdam;
-  constexpr int kEntries = kEntriesInFlight;
-  constexpr int kSlices = kChunks == 0 ? 1 : kChunks;
-  AdamStepSizes z;
-  {
-    const float lr = lr_word != nullptr ? *lr_word : lr_value;
-    const float c = bias_word != nullptr ? *bias_word : bias_value;
-    z.step = Arith<float>::mul(lr, c);
-    z.decay = Arith<float>::mul(lr, h.weight_decay);
-    z.decays = h.weight_decay != 0.f;
-  }
-  uint64_t seed = 0, round_step = 0;
-  if constexpr (kStochastic) {
-    seed = rounding.seed;
-    round_step = rounding.step_word != nullptr ? static_cast<uint64_t>(*rounding.step_word) : rounding.step;
-  }
-  const int lane = static_cast<int>(threadIdx.x) & (group - 1);
-  const int groups_per_block = kUpdateBlockThreads / group;
-  const int64_t first = static_cast<int64_t>(blockIdx.x) * groups_per_block + static_cast<int>(threadIdx.x) / group;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * groups_per_block;
-
-  for (int piece = 0; piece < pieces; ++piece) {
-    const int64_t count = PieceCount<IndexT>(counts, piece, piece_rows);
-    const int64_t base = static_cast<int64_t>(piece) * piece_rows;
-    for (int64_t k = first; k < count; k += stride * kEntries) {
-      int64_t r[kEntries];
-      bool live[kEntries];
-#pragma unroll
-      for (int u = 0; u < kEntries; ++u) {
-        live[u] = k + u * stride < count;
-        r[u] = live[u] ? WidenIndex(ids[base + k + u * stride]) : 0;
-      }
-      if constexpr (kChunks == 0) {
-        // any width: slices lane, lane + group, ... one after the other
-        const ElemT* g_row = RowPtr(rows, base + k, width);
-        ElemT* w_row = const_cast<ElemT*>(RowPtr(table, r[0], width));
-        float* m_row = exp_avg + RowElems(r[0], width);
-        float scale = 0.f;
-        if constexpr (kRowwise) {
-          const float before = exp_avg_sq[r[0]];
-          float sum = 0.f;
-          for (int c = lane; c < lanes_per_row; c += group) sum = AddSquares(sum, LoadPack<ElemT, N>(g_row + c * N));
-          scale = RowwiseAdamScale(exp_avg_sq + r[0], before, GroupSum(sum, group), width, lane == 0, z, h);
-        }
-        for (int c = lane; c < lanes_per_row; c += group) {
-          const Pack<ElemT, N> g = kRowwise ? LoadPack<ElemT, N>(g_row + c * N) : LoadPackStreaming<ElemT, N>(g_row + c * N);
-          const Pack<ElemT, N> w = LoadPack<ElemT, N>(w_row + c * N);
-          StatePack<N> m = StatePack<N>::Load(m_row + c * N);
-          RoundT round;
-          if constexpr (kStochastic) round = RoundT(seed, round_step, r[0], c * N);
-          if constexpr (kRowwise) {
-            StorePack<ElemT, N>(w_row + c * N, RowwiseAdamStep(w, g, m, scale, z, h, round));
-          } else {
-            float* v_at = exp_avg_sq + RowElems(r[0], width) + c * N;
-            StatePack<N> v = StatePack<N>::Load(v_at);
-            StorePack<ElemT, N>(w_row + c * N, AdamStep(w, g, m, v, z, h, round));
-            v.Store(v_at);
-          }
-          m.Store(m_row + c * N);
-        }
-      } else {
-        Pack<ElemT, N> g[kEntries][kSlices], w[kEntries][kSlices];
-        StatePack<N> m[kEntries][kSlices];
-        StatePack<N> v[kRowwise ? 1 : kEntries][kRowwise ? 1 : kSlices];
-        bool has[kEntries][kSlices];
-        float row_v[kEntries];
-        RoundT round[kEntries][kSlices];
-#pragma unroll
-        for (int u = 0; u < kEntries; ++u) {
-          if constexpr (kRowwise) row_v[u] = live[u] ? exp_avg_sq[r[u]] : 0.f;
-#pragma unroll
-          for (int c = 0; c < kSlices; ++c) {
-            const int col = (lane + c * group) * N;
-            has[u][c] = live[u] && lane + c * group < lanes_per_row;
-            if (has[u][c]) {
-              g[u][c] = LoadPackStreaming<ElemT, N>(RowPtr(rows, base + k + u * stride, width) + col);
-              w[u][c] = LoadPack<ElemT, N>(RowPtr(table, r[u], width) + col);
-              m[u][c] = StatePack<N>::Load(exp_avg + RowElems(r[u], width) + col);
-              if constexpr (!kRowwise) v[u][c] = StatePack<N>::Load(exp_avg_sq + RowElems(r[u], width) + col);
-            }
-          }
-        }
-        if constexpr (kStochastic) {
-          // the random bits need nothing that was loaded: they are computed while the loads are in flight
-#pragma unroll
-          for (int u = 0; u < kEntries; ++u)
-#pragma unroll
-            for (int c = 0; c < kSlices; ++c)
-              if (has[u][c]) round[u][c] = RoundT(seed, round_step, r[u], (lane + c * group) * N);
-        }
-#pragma unroll
-        for (int u = 0; u < kEntries; ++u) {
-          float scale = 0.f;
-          if constexpr (kRowwise) {
-            // (a group whose second entry is past the count still takes part in the butterfly: its lanes are active)
-            float sum = 0.f;
-#pragma unroll
-            for (int c = 0; c < kSlices; ++c)
-              if (has[u][c]) sum = AddSquares(sum, g[u][c]);
-            sum = GroupSum(sum, group);
-            if (live[u]) scale = RowwiseAdamScale(exp_avg_sq + r[u], row_v[u], sum, width, lane == 0, z, h);
-          }
-#pragma unroll
-          for (int c = 0; c < kSlices; ++c) {
-            if (!has[u][c]) continue;
-            const int col = (lane + c * group) * N;
-            ElemT* w_at = const_cast<ElemT*>(RowPtr(table, r[u], width)) + col;
-            if constexpr (kRowwise) {
-              StorePack<ElemT, N>(w_at, RowwiseAdamStep(w[u][c], g[u][c], m[u][c], scale, z, h, round[u][c]));
-            } else {
-              StorePack<ElemT, N>(w_at, AdamStep(w[u][c], g[u][c], m[u][c], v[u][c], z, h, round[u][c]));
-              v[u][c].Store(exp_avg_sq + RowElems(r[u], width) + col);
-            }
-            m[u][c].Store(exp_avg + RowElems(r[u], width) + col);
-          }
-        }
-      }
-    }
-  }
+  const float lr = lr_word != nullptr ? *lr_word : lr_value;
+  const float c = bias_word != nullptr ? *bias_word : bias_value;
+  const AdamStepRule<kRule> rule{{Arith<float>::mul(lr, c), Arith<float>::mul(lr, h.weight_decay), h.weight_decay != 0.f}, h};
+  WalkNamedRows<ElemT, IndexT, N, kChunks, kEntriesInFlight, kStochastic>(
+      ids, rows, table, exp_avg, exp_avg_sq, width, lanes_per_row, group, piece_rows, pieces, counts, rounding, rule);
 }
 
 /**

@@ -21,12 +21,11 @@
 
 namespace cuembed {
 
-//! Rule, hyper-parameters and the source of the entry count of one SparseRowUpdate call.
-struct SparseUpdateOptions {
-  UpdateRule rule = UpdateRule::kSgd;
+//! What the options of every sparse step hold (SparseUpdateOptions below, SparseAdamOptions in sparse_adam.hpp): the
+//! learning rate, the entries and the source of their count, and the rounding of the store.
+struct SparseStepOptions {
   float lr = 0.f;                    //!< learning rate, unless ...
   const float* lr_device = nullptr;  //!< ... one fp32 word on the device holds it (a captured graph follows a schedule)
-  float eps = 1e-8f;                 //!< Adagrad rules: added to sqrt(state)
   //! The entries are `pieces` blocks of `piece_rows` entries; entry j of piece p is valid iff j < count(p).
   int64_t piece_rows = 0;            //!< capacity of one piece (rows of `ids` / `rows` per piece)
   int pieces = 1;
@@ -44,6 +43,12 @@ struct SparseUpdateOptions {
   uint64_t rounding_step = 0;                    //!< the step, unless ...
   const int64_t* rounding_step_device = nullptr; //!< ... one int64 word on the device holds it (advance it on the
                                                  //!< device and a replayed graph draws fresh bits)
+};
+
+//! Rule, hyper-parameters and the source of the entry count of one SparseRowUpdate call.
+struct SparseUpdateOptions : SparseStepOptions {
+  UpdateRule rule = UpdateRule::kSgd;
+  float eps = 1e-8f;                 //!< Adagrad rules: added to sqrt(state)
 };
 
 //! Which roundings a SparseRowUpdate instantiation carries kernels for.  The header API carries both; the C ABI splits
@@ -95,54 +100,73 @@ inline UpdateShape PlanUpdate(const int lanes_per_row, const int64_t total_entri
   return s;
 }
 
-template <typename ElemT, typename IndexT, int N, UpdateRule kRule, bool kStochastic>
-inline void LaunchSparseRowUpdate(ElemT* table, float* state, const int width, const IndexT* ids, const ElemT* rows,
-                                  const SparseUpdateOptions& o, const UpdateCounts& counts, const hipStream_t stream) {
-  const UpdateShape s = PlanUpdate(width / N, o.piece_rows * o.pieces, CurrentDeviceShape());
+//! Whether an instantiation carries the stochastic kernels of its table type.
+template <typename ElemT, UpdateRoundings kRoundings>
+constexpr bool kCanRoundStochastically = !std::is_same<ElemT, float>::value && kRoundings != UpdateRoundings::kNearestOnly;
+
+//! The checks that every sparse step makes, in this order: CheckCountSource, its own on the rule and the state, then
+//! CheckRoundingAndWork on the rounding and the buffers (false: there is nothing to do).
+inline void CheckCountSource(const SparseStepOptions& o) {
+  const int sources = (o.num_rows >= 0) + (o.counts != nullptr) + (o.last_id != nullptr);
+  CUEMBED_ASSERT(sources == 1);
+  CUEMBED_ASSERT(o.pieces >= 1 && o.piece_rows >= 0);
+  CUEMBED_ASSERT(o.pieces == 1 || o.counts != nullptr);   // several pieces: counts[pieces] on the device
+  if (o.num_rows >= 0) CUEMBED_ASSERT(o.num_rows <= o.piece_rows);
+}
+
+template <typename ElemT, UpdateRoundings kRoundings>
+inline bool CheckRoundingAndWork(const SparseStepOptions& o, const void* table, const void* ids, const void* rows) {
+  CUEMBED_ASSERT(!o.stochastic_rounding || (kCanRoundStochastically<ElemT, kRoundings>));
+  CUEMBED_ASSERT(o.stochastic_rounding || kRoundings != UpdateRoundings::kStochasticOnly);
+  if (o.piece_rows == 0 || o.num_rows == 0) return false;
+  CUEMBED_ASSERT(table != nullptr && ids != nullptr && rows != nullptr);
+  return true;
+}
+
+inline UpdateCounts CountsOf(const SparseStepOptions& o) {
+  UpdateCounts counts;
+  counts.host_count = o.num_rows >= 0 ? o.num_rows : -1;
+  counts.count_words = o.counts;
+  counts.count_words_are_64 = o.counts_are_int64 ? 1 : 0;
+  counts.last_id = o.last_id;
+  return counts;
+}
+
+template <bool kStochastic>
+inline UpdateRounding<kStochastic> RoundingOf(const SparseStepOptions& o) {
   UpdateRounding<kStochastic> rounding;
   if constexpr (kStochastic) {
     rounding.seed = o.rounding_seed;
     rounding.step = o.rounding_step;
     rounding.step_word = o.rounding_step_device;
   }
-#define CUEMBED_LAUNCH_UPDATE(CHUNKS)                                                                             \
-  SparseRowUpdateKernel<ElemT, IndexT, N, kRule, CHUNKS, kStochastic>                                             \
-      <<<dim3(s.grid), dim3(kUpdateBlockThreads), 0, stream>>>(ids, rows, table, state, width, s.lanes_per_row,   \
-                                                               s.group, o.piece_rows, o.pieces, counts, o.lr,     \
-                                                               o.lr_device, o.eps, rounding)
-  if (s.chunks == 1) CUEMBED_LAUNCH_UPDATE(1);
-  else if (s.chunks == kUpdateMaxChunks) CUEMBED_LAUNCH_UPDATE(kUpdateMaxChunks);
-  else CUEMBED_LAUNCH_UPDATE(0);
-#undef CUEMBED_LAUNCH_UPDATE
+  return rounding;
 }
 
-template <typename ElemT, typename IndexT, int N, bool kStochastic>
-inline void LaunchSparseRowUpdateRule(ElemT* table, float* state, const int width, const IndexT* ids, const ElemT* rows,
-                                      const SparseUpdateOptions& o, const UpdateCounts& counts, const hipStream_t stream) {
-  switch (o.rule) {
-    case UpdateRule::kSgd:
-      return LaunchSparseRowUpdate<ElemT, IndexT, N, UpdateRule::kSgd, kStochastic>(table, state, width, ids, rows, o, counts, stream);
-    case UpdateRule::kAdagrad:
-      return LaunchSparseRowUpdate<ElemT, IndexT, N, UpdateRule::kAdagrad, kStochastic>(table, state, width, ids, rows, o, counts,
-                                                                                       stream);
-    case UpdateRule::kRowwiseAdagrad:
-      return LaunchSparseRowUpdate<ElemT, IndexT, N, UpdateRule::kRowwiseAdagrad, kStochastic>(table, state, width, ids, rows, o,
-                                                                                              counts, stream);
-  }
-  CUEMBED_ASSERT(false && "unknown update rule");
-}
+template <int kValue>
+using Int = std::integral_constant<int, kValue>;
 
-//! The lane width's instantiation: N = 16 / 8 / 4 bytes of ElemT.
-template <typename ElemT, typename IndexT, bool kStochastic>
-inline void LaunchSparseRowUpdateBytes(const int bytes, ElemT* table, float* state, const int width, const IndexT* ids,
-                                       const ElemT* rows, const SparseUpdateOptions& o, const UpdateCounts& counts,
-                                       const hipStream_t stream) {
+//! From the options' rounding, the lane bytes and the plan to the instantiation: calls
+//! launch(stochastic, n, chunks, shape) with the first three as integral constants -- stochastic rounding or not,
+//! N = 16 / 8 / 4 bytes of ElemT per lane, slices per lane (1, kUpdateMaxChunks or 0) -- and the UpdateShape to launch.
+template <typename ElemT, UpdateRoundings kRoundings, typename LaunchT>
+inline void DispatchUpdate(const int bytes, const int width, const SparseStepOptions& o, const LaunchT& launch) {
   constexpr int kMaxN = 16 / static_cast<int>(sizeof(ElemT));
-  if (bytes == 16) LaunchSparseRowUpdateRule<ElemT, IndexT, kMaxN, kStochastic>(table, state, width, ids, rows, o, counts, stream);
-  else if (bytes == 8)
-    LaunchSparseRowUpdateRule<ElemT, IndexT, kMaxN / 2, kStochastic>(table, state, width, ids, rows, o, counts, stream);
-  else
-    LaunchSparseRowUpdateRule<ElemT, IndexT, kMaxN / 4, kStochastic>(table, state, width, ids, rows, o, counts, stream);
+  const auto with_rounding = [&](auto stochastic) {
+    const auto with_n = [&](auto n) {
+      const UpdateShape s = PlanUpdate(width / n, o.piece_rows * o.pieces, CurrentDeviceShape());
+      if (s.chunks == 1) launch(stochastic, n, Int<1>(), s);
+      else if (s.chunks == kUpdateMaxChunks) launch(stochastic, n, Int<kUpdateMaxChunks>(), s);
+      else launch(stochastic, n, Int<0>(), s);
+    };
+    if (bytes == 16) with_n(Int<kMaxN>());
+    else if (bytes == 8) with_n(Int<kMaxN / 2>());
+    else with_n(Int<kMaxN / 4>());
+  };
+  if constexpr (kCanRoundStochastically<ElemT, kRoundings>) {
+    if (o.stochastic_rounding) return with_rounding(std::true_type());
+  }
+  if constexpr (kRoundings != UpdateRoundings::kStochasticOnly) with_rounding(std::false_type());
 }
 
 }  // namespace detail
@@ -187,31 +211,30 @@ void SparseRowUpdate(ElemT* table,
   static_assert(std::is_same<IndexT, int32_t>::value || std::is_same<IndexT, int64_t>::value,
                 "SparseRowUpdate: ids must be int32_t or int64_t");
   using DevT = detail::DeviceElemT<ElemT>;
-  const int sources = (options.num_rows >= 0) + (options.counts != nullptr) + (options.last_id != nullptr);
-  CUEMBED_ASSERT(sources == 1);
-  CUEMBED_ASSERT(options.pieces >= 1 && options.piece_rows >= 0);
-  CUEMBED_ASSERT(options.pieces == 1 || options.counts != nullptr);   // several pieces: counts[pieces] on the device
-  if (options.num_rows >= 0) CUEMBED_ASSERT(options.num_rows <= options.piece_rows);
+  detail::CheckCountSource(options);
   CUEMBED_ASSERT((options.rule == UpdateRule::kSgd) == (state == nullptr));
-  constexpr bool kCanRoundStochastically = !std::is_same<ElemT, float>::value && kRoundings != UpdateRoundings::kNearestOnly;
-  CUEMBED_ASSERT(!options.stochastic_rounding || kCanRoundStochastically);
-  CUEMBED_ASSERT(options.stochastic_rounding || kRoundings != UpdateRoundings::kStochasticOnly);
-  if (options.piece_rows == 0 || options.num_rows == 0) return;
-  CUEMBED_ASSERT(table != nullptr && ids != nullptr && rows != nullptr);
+  if (!detail::CheckRoundingAndWork<ElemT, kRoundings>(options, table, ids, rows)) return;
   const int bytes = detail::UpdateLaneBytes<DevT>(embed_width, table, rows, state, options.rule == UpdateRule::kAdagrad);
-  detail::UpdateCounts counts;
-  counts.host_count = options.num_rows >= 0 ? options.num_rows : -1;
-  counts.count_words = options.counts;
-  counts.count_words_are_64 = options.counts_are_int64 ? 1 : 0;
-  counts.last_id = options.last_id;
+  const detail::UpdateCounts counts = detail::CountsOf(options);
   DevT* t = reinterpret_cast<DevT*>(table);
   const DevT* g = reinterpret_cast<const DevT*>(rows);
-  if constexpr (kCanRoundStochastically) {
-    if (options.stochastic_rounding)
-      return detail::LaunchSparseRowUpdateBytes<DevT, IndexT, true>(bytes, t, state, embed_width, ids, g, options, counts, stream);
-  }
-  if constexpr (kRoundings != UpdateRoundings::kStochasticOnly)
-    detail::LaunchSparseRowUpdateBytes<DevT, IndexT, false>(bytes, t, state, embed_width, ids, g, options, counts, stream);
+  detail::DispatchUpdate<DevT, kRoundings>(
+      bytes, embed_width, options, [&](auto stochastic, auto n, auto chunks, const detail::UpdateShape& s) {
+        const auto with_rule = [&](auto rule) {
+          detail::SparseRowUpdateKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, decltype(chunks)::value,
+                                        decltype(stochastic)::value>
+              <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), 0, stream>>>(
+                  ids, g, t, state, embed_width, s.lanes_per_row, s.group, options.piece_rows, options.pieces, counts,
+                  options.lr, options.lr_device, options.eps, detail::RoundingOf<decltype(stochastic)::value>(options));
+        };
+        switch (options.rule) {
+          case UpdateRule::kSgd: return with_rule(std::integral_constant<UpdateRule, UpdateRule::kSgd>());
+          case UpdateRule::kAdagrad: return with_rule(std::integral_constant<UpdateRule, UpdateRule::kAdagrad>());
+          case UpdateRule::kRowwiseAdagrad:
+            return with_rule(std::integral_constant<UpdateRule, UpdateRule::kRowwiseAdagrad>());
+        }
+        CUEMBED_ASSERT(false && "unknown update rule");
+      });
 }
 
 }  // namespace cuembed

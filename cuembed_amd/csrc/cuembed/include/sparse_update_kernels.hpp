@@ -22,6 +22,9 @@
 //     Entries at or past the count are ignored whatever they hold; a count above the capacity (the backward then
 //     wrote nothing) or below zero makes the piece empty.
 //   * The valid entries must name DISTINCT rows (a coalesced gradient): there are no atomics on table data.
+//   * All of this is ONE device function, WalkNamedRows, for the five rules (SGD, Adagrad, row-wise Adagrad here; Adam and
+//     row-wise Adam in sparse_adam_kernels.hpp).  A rule type tells it how many per-element fp32 state tensors a slice
+//     carries (0 / 1 / 2), whether the row has a state word of its own, and the arithmetic of a row and of a slice.
 #ifndef CUEMBED_INCLUDE_SPARSE_UPDATE_KERNELS_HPP_
 #define CUEMBED_INCLUDE_SPARSE_UPDATE_KERNELS_HPP_
 
@@ -181,29 +184,67 @@ __device__ __forceinline__ float RowwiseStep(float* state_of_row, const float be
   return lr / A::add(sqrtf(acc), eps);
 }
 
+//! What the walk needs to know of a rule (RuleT of WalkNamedRows):
+//!   kStates    per-element fp32 state tensors a slice carries next to its weights and gradient: 0, 1 or 2;
+//!   kRowState  whether there is one more state word per row, fed with the row's summed squared gradient;
+//!   Row(word, before, sum, width, store)   the per-row part: updates the word (lane 0 stores), returns the row's factor;
+//!   Slice(w, g, s, row, round)             the new weights of one slice; updates the slice's state packs s[] in place.
+//! The rules of SparseRowUpdateKernel; those of SparseRowAdamKernel are sparse_adam_kernels.hpp's AdamStepRule.
+template <UpdateRule kRule>
+struct UpdateStep {
+  static constexpr int kStates = kRule == UpdateRule::kAdagrad ? 1 : 0;
+  static constexpr bool kRowState = kRule == UpdateRule::kRowwiseAdagrad;
+  float lr, eps;
+  __device__ __forceinline__ float Row(float* word, const float before, const float sum, const int width,
+                                       const bool store) const {
+    return RowwiseStep(word, before, sum, width, store, lr, eps);
+  }
+  template <typename ElemT, int N, typename RoundT>
+  __device__ __forceinline__ Pack<ElemT, N> Slice(const Pack<ElemT, N>& w, const Pack<ElemT, N>& g, StatePack<N>* s,
+                                                  const float row, const RoundT& round) const {
+    if constexpr (kStates == 1) return AdagradStep(w, g, s[0], lr, eps, round);
+    else return ScaledStep(w, g, kRowState ? row : lr, round);
+  }
+};
+
+//! The per-element state packs of one slice, `at` elements into the rule's kStates tensors (written out per tensor: the
+//! pointers keep their __restrict__, which an array of them indexed in a loop loses).
+template <int kStates, int N>
+__device__ __forceinline__ void LoadStates(StatePack<N>* s, const float* state0, const float* state1, const int64_t at) {
+  if constexpr (kStates > 0) s[0] = StatePack<N>::Load(state0 + at);
+  if constexpr (kStates > 1) s[1] = StatePack<N>::Load(state1 + at);
+}
+template <int kStates, int N>
+__device__ __forceinline__ void StoreStates(const StatePack<N>* s, float* state0, float* state1, const int64_t at) {
+  if constexpr (kStates > 1) s[1].Store(state1 + at);
+  if constexpr (kStates > 0) s[0].Store(state0 + at);
+}
+
 /**
- * @brief table[ids[k], :] (and its state) <- rule(table[ids[k], :], rows[k, :]) for every valid entry k.
+ * @brief The one walk over the named rows: table[ids[k], :] and the state of row ids[k] <- rule(table[ids[k], :],
+ * rows[k, :]) for every valid entry k.  The body of both kernels below.
  *
- * Launch: 1-D grid of kUpdateBlockThreads-thread workgroups, `group` (a power of two <= 64) lanes per entry,
- * lanes_per_row = width / N slices per row; kChunks >= 1 needs lanes_per_row <= kChunks * group.
- * Entries: `pieces` blocks of `piece_rows` entries, entry j of piece p valid iff j < count(p).
- * kStochastic (16-bit ElemT only): the stores round stochastically with the bits of (rounding.seed, step).
+ * state0 / state1: the rule's kStates per-element tensors [rows, width], then (kRowState) its per-row words [rows].
+ * kEntries entries are in flight per group: 2 when a lane holds one slice per entry (kChunks == 1), else 1.  With the
+ * two moment packs of an Adam slice next to its weights and gradient, two entries take 32 (fp32) to 48 (16-bit)
+ * registers of row data per lane: every kChunks == 1 instantiation stays free of scratch and at or above 4 waves per
+ * SIMD (profiles/sparse_adam_kernel_resources.txt; the four-slice Adam bodies of the 16-bit types run at 2).
  */
-template <typename ElemT, typename IndexT, int N, UpdateRule kRule, int kChunks, bool kStochastic = false>
-__global__ void __launch_bounds__(kUpdateBlockThreads)
-    SparseRowUpdateKernel(const IndexT* __restrict__ ids, const ElemT* __restrict__ rows, ElemT* __restrict__ table,
-                          float* __restrict__ state, const int width, const int lanes_per_row, const int group,
-                          const int64_t piece_rows, const int pieces, const UpdateCounts counts, const float lr_value,
-                          const float* __restrict__ lr_word, const float eps,
-                          const UpdateRounding<kStochastic> rounding = UpdateRounding<kStochastic>()) {
+template <typename ElemT, typename IndexT, int N, int kChunks, int kEntries, bool kStochastic, typename RuleT>
+__device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, const ElemT* __restrict__ rows,
+                                              ElemT* __restrict__ table, float* __restrict__ state0,
+                                              float* __restrict__ state1, const int width, const int lanes_per_row,
+                                              const int group, const int64_t piece_rows, const int pieces,
+                                              const UpdateCounts& counts, const UpdateRounding<kStochastic>& rounding,
+                                              const RuleT& rule) {
   static_assert(!kStochastic || sizeof(ElemT) == 2, "stochastic rounding is for the 16-bit table types");
+  static_assert(kEntries == 1 || (kEntries == 2 && kChunks == 1), "two entries in flight: one slice per lane");
   using RoundT = SliceRounding<ElemT, N, kStochastic>;
-  constexpr bool kRowwise = kRule == UpdateRule::kRowwiseAdagrad;
-  constexpr bool kAdagrad = kRule == UpdateRule::kAdagrad;
-  // entries in flight per group: two when a lane holds one slice per entry
-  constexpr int kEntries = kChunks == 1 ? 2 : 1;
+  constexpr int kStates = RuleT::kStates;
+  constexpr bool kRowState = RuleT::kRowState;
+  constexpr int kHeld = kStates > 0 ? kStates : 1;
   constexpr int kSlices = kChunks == 0 ? 1 : kChunks;
-  const float lr = lr_word != nullptr ? *lr_word : lr_value;
+  float* const row_words = kStates == 0 ? state0 : state1;   // (only read if kRowState)
   uint64_t seed = 0, round_step = 0;
   if constexpr (kStochastic) {
     seed = rounding.seed;
@@ -226,41 +267,36 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
         r[u] = live[u] ? WidenIndex(ids[base + k + u * stride]) : 0;
       }
       if constexpr (kChunks == 0) {
-        // any width: slices lane, lane + group, ... one after the other
+        // any width: slices lane, lane + group, ... one after the other (a rule with a row word reads the gradient row
+        // twice, the second time out of the cache it has just been loaded into)
         const ElemT* g_row = RowPtr(rows, base + k, width);
         ElemT* w_row = const_cast<ElemT*>(RowPtr(table, r[0], width));
-        float step = lr;
-        if constexpr (kRowwise) {
-          const float before = state[r[0]];
+        float row = 0.f;
+        if constexpr (kRowState) {
+          const float before = row_words[r[0]];
           float sum = 0.f;
           for (int c = lane; c < lanes_per_row; c += group) sum = AddSquares(sum, LoadPack<ElemT, N>(g_row + c * N));
-          step = RowwiseStep(state + r[0], before, GroupSum(sum, group), width, lane == 0, lr, eps);
+          row = rule.Row(row_words + r[0], before, GroupSum(sum, group), width, lane == 0);
         }
         for (int c = lane; c < lanes_per_row; c += group) {
-          const Pack<ElemT, N> g = kRowwise ? LoadPack<ElemT, N>(g_row + c * N) : LoadPackStreaming<ElemT, N>(g_row + c * N);
+          const Pack<ElemT, N> g = kRowState ? LoadPack<ElemT, N>(g_row + c * N) : LoadPackStreaming<ElemT, N>(g_row + c * N);
           const Pack<ElemT, N> w = LoadPack<ElemT, N>(w_row + c * N);
-          if constexpr (kAdagrad) {
-            float* s_at = state + RowElems(r[0], width) + c * N;
-            StatePack<N> s = StatePack<N>::Load(s_at);
-            RoundT round;
-            if constexpr (kStochastic) round = RoundT(seed, round_step, r[0], c * N);
-            StorePack<ElemT, N>(w_row + c * N, AdagradStep(w, g, s, lr, eps, round));
-            s.Store(s_at);
-          } else {
-            RoundT round;
-            if constexpr (kStochastic) round = RoundT(seed, round_step, r[0], c * N);
-            StorePack<ElemT, N>(w_row + c * N, ScaledStep(w, g, step, round));
-          }
+          StatePack<N> s[kHeld];
+          LoadStates<kStates>(s, state0, state1, RowElems(r[0], width) + c * N);
+          RoundT round;
+          if constexpr (kStochastic) round = RoundT(seed, round_step, r[0], c * N);
+          StorePack<ElemT, N>(w_row + c * N, rule.Slice(w, g, s, row, round));
+          StoreStates<kStates>(s, state0, state1, RowElems(r[0], width) + c * N);
         }
       } else {
         Pack<ElemT, N> g[kEntries][kSlices], w[kEntries][kSlices];
-        StatePack<N> s[kAdagrad ? kEntries : 1][kAdagrad ? kSlices : 1];
+        StatePack<N> s[kEntries][kSlices][kHeld];
         bool has[kEntries][kSlices];
-        float row_state[kEntries];
+        float row_word[kEntries];
         RoundT round[kEntries][kSlices];
 #pragma unroll
         for (int u = 0; u < kEntries; ++u) {
-          if constexpr (kRowwise) row_state[u] = live[u] ? state[r[u]] : 0.f;
+          if constexpr (kRowState) row_word[u] = live[u] ? row_words[r[u]] : 0.f;
 #pragma unroll
           for (int c = 0; c < kSlices; ++c) {
             const int col = (lane + c * group) * N;
@@ -268,7 +304,7 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
             if (has[u][c]) {
               g[u][c] = LoadPackStreaming<ElemT, N>(RowPtr(rows, base + k + u * stride, width) + col);
               w[u][c] = LoadPack<ElemT, N>(RowPtr(table, r[u], width) + col);
-              if constexpr (kAdagrad) s[u][c] = StatePack<N>::Load(state + RowElems(r[u], width) + col);
+              LoadStates<kStates>(s[u][c], state0, state1, RowElems(r[u], width) + col);
             }
           }
         }
@@ -282,32 +318,48 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
         }
 #pragma unroll
         for (int u = 0; u < kEntries; ++u) {
-          float step = lr;
-          if constexpr (kRowwise) {
+          float row = 0.f;
+          if constexpr (kRowState) {
             // (a group whose second entry is past the count still takes part in the butterfly: its lanes are active)
             float sum = 0.f;
 #pragma unroll
             for (int c = 0; c < kSlices; ++c)
               if (has[u][c]) sum = AddSquares(sum, g[u][c]);
             sum = GroupSum(sum, group);
-            if (live[u]) step = RowwiseStep(state + r[u], row_state[u], sum, width, lane == 0, lr, eps);
+            if (live[u]) row = rule.Row(row_words + r[u], row_word[u], sum, width, lane == 0);
           }
 #pragma unroll
           for (int c = 0; c < kSlices; ++c) {
             if (!has[u][c]) continue;
             const int col = (lane + c * group) * N;
             ElemT* w_at = const_cast<ElemT*>(RowPtr(table, r[u], width)) + col;
-            if constexpr (kAdagrad) {
-              StorePack<ElemT, N>(w_at, AdagradStep(w[u][c], g[u][c], s[u][c], lr, eps, round[u][c]));
-              s[u][c].Store(state + RowElems(r[u], width) + col);
-            } else {
-              StorePack<ElemT, N>(w_at, ScaledStep(w[u][c], g[u][c], step, round[u][c]));
-            }
+            StorePack<ElemT, N>(w_at, rule.Slice(w[u][c], g[u][c], s[u][c], row, round[u][c]));
+            StoreStates<kStates>(s[u][c], state0, state1, RowElems(r[u], width) + col);
           }
         }
       }
     }
   }
+}
+
+/**
+ * @brief table[ids[k], :] (and its state) <- rule(table[ids[k], :], rows[k, :]) for every valid entry k.
+ *
+ * Launch: 1-D grid of kUpdateBlockThreads-thread workgroups, `group` (a power of two <= 64) lanes per entry,
+ * lanes_per_row = width / N slices per row; kChunks >= 1 needs lanes_per_row <= kChunks * group.
+ * Entries: `pieces` blocks of `piece_rows` entries, entry j of piece p valid iff j < count(p).
+ * kStochastic (16-bit ElemT only): the stores round stochastically with the bits of (rounding.seed, step).
+ */
+template <typename ElemT, typename IndexT, int N, UpdateRule kRule, int kChunks, bool kStochastic = false>
+__global__ void __launch_bounds__(kUpdateBlockThreads)
+    SparseRowUpdateKernel(const IndexT* __restrict__ ids, const ElemT* __restrict__ rows, ElemT* __restrict__ table,
+                          float* __restrict__ state, const int width, const int lanes_per_row, const int group,
+                          const int64_t piece_rows, const int pieces, const UpdateCounts counts, const float lr_value,
+                          const float* __restrict__ lr_word, const float eps,
+                          const UpdateRounding<kStochastic> rounding = UpdateRounding<kStochastic>()) {
+  const UpdateStep<kRule> rule{lr_word != nullptr ? *lr_word : lr_value, eps};
+  WalkNamedRows<ElemT, IndexT, N, kChunks, kChunks == 1 ? 2 : 1, kStochastic>(
+      ids, rows, table, state, nullptr, width, lanes_per_row, group, piece_rows, pieces, counts, rounding, rule);
 }
 
 }  // namespace detail

@@ -28,20 +28,22 @@ def main():
             cur = m.group(1)
             rows[cur] = {}
             continue
-        m = re.search(r"\s(VGPRs|AGPRs|SGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|"
+        m = re.search(r"\s(?:Total)?(VGPRs|AGPRs|SGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|"
                       r"LDS Size \[bytes/block\]|VGPRs Spill|SGPRs Spill): (\d+)", line)
         if m and cur:
             rows[cur][m.group(1).split(" [")[0]] = int(m.group(2))
     demangle = subprocess.run(["c++filt"] + list(rows), stdout=subprocess.PIPE, text=True)
     names = demangle.stdout.splitlines() if demangle.returncode == 0 else list(rows)
-    print("%-6s %-6s %-8s %-8s %-5s  %s" % ("VGPR", "SGPR", "scratch", "LDS", "occ", "kernel"))
+    print("%-6s %-6s %-8s %-8s %-8s %-8s %-5s  %s" % ("VGPR", "SGPR", "scratch", "Vspill", "Sspill", "LDS", "occ", "kernel"))
     for mangled, name in zip(rows, names):
         if want and not any(w in name for w in want):
             continue
         r = rows[mangled]
-        short = re.sub(r"\(.*$", "", name)
-        print("%-6s %-6s %-8s %-8s %-5s  %s" % (r.get("VGPRs"), r.get("SGPRs"), r.get("ScratchSize"),
-                                              r.get("LDS Size"), r.get("Occupancy"), short))
+        # without the parameter list (template arguments such as "(cuembed::AdamRule)0" stay)
+        short = name[:name.find(">(") + 1] if ">(" in name else re.sub(r"\(.*$", "", name)
+        print("%-6s %-6s %-8s %-8s %-8s %-8s %-5s  %s" % (r.get("VGPRs"), r.get("SGPRs"), r.get("ScratchSize"),
+                                                        r.get("VGPRs Spill"), r.get("SGPRs Spill"), r.get("LDS Size"),
+                                                        r.get("Occupancy"), short))
 
 
 if __name__ == "__main__":
