@@ -10,7 +10,8 @@ fingerprints hold on any device.  The fixture is written by this module run as a
     python tests/test_gpu_optimizer_step_bits.py --record [--commit ID] [--out FILE]
 
 on a build of the commit whose behaviour is to be kept; `recorded_from` names that commit.  A fingerprint that differs
-means that a kernel edit changed an operation or an order: fix the kernel, never the fixture."""
+means that a kernel edit changed an operation or an order: fix the kernel, never the fixture.  Every fingerprint is
+also reproduced on the CPU by an independent numpy-float32 statement of the contract (test_optimizer_bits_host.py)."""
 import functools
 import hashlib
 import json
