@@ -131,6 +131,30 @@ constexpr int kWideLoadCsrBatch = 1024;
 //! 256-thread workgroups still fit a CU's 160 KiB LDS.
 constexpr int kMaxStageBytes = 16 * 1024;
 
+//! Whether the lanes of a row are consecutive lanes of ONE wavefront (they can hand indices to each other across lanes).
+inline bool LanesDivideWave(const int lanes_per_row) { return lanes_per_row <= 64 && 64 % lanes_per_row == 0; }
+
+//! Where the lanes of a sum / mean launch find their indices (plain and quantized tables alike): calls
+//! launch(weighted, source) with both as compile-time constants (std::integral_constant).
+template <typename LaunchFn>
+inline void WithIndexSource(const bool staged, const int lanes_per_row, const bool weighted, LaunchFn launch) {
+  using S = IndexSource;
+  const auto with_weighted = [&](auto source) {
+    if (weighted) launch(std::true_type{}, source);
+    else launch(std::false_type{}, source);
+  };
+  if (staged) with_weighted(std::integral_constant<S, S::kLdsStaged>{});
+  else if (LanesDivideWave(lanes_per_row)) with_weighted(std::integral_constant<S, S::kWaveShuffle>{});
+  else with_weighted(std::integral_constant<S, S::kGlobal>{});
+}
+
+//! Fixed hotness: the samples per workgroup, `rows` halved until their indices (+ weights: `per_sample` bytes each) fit
+//! kMaxStageBytes of LDS, or 0 when not even one sample's do (the indices are then read from global memory).
+inline int StagedSamplesPerBlock(int rows, const size_t per_sample) {
+  while (rows > 1 && rows * per_sample > static_cast<size_t>(kMaxStageBytes)) rows /= 2;
+  return rows * per_sample <= static_cast<size_t>(kMaxStageBytes) ? rows : 0;
+}
+
 //! How a row is split over lanes and how many samples share a workgroup.
 struct RowSplit {
   int elems_per_lane;   //!< N: 16, 8 or 4 bytes worth of elements
@@ -187,15 +211,13 @@ inline ForwardLaunch PlanForward(const int embed_width, const void* params, cons
   if (!is_csr && !concat) {
     const size_t per_sample =
         static_cast<size_t>(num_hots) * (sizeof(IndexT) + (weighted ? sizeof(ElemT) : 0));
-    int rows = f.split.rows_per_block;
-    while (rows > 1 && rows * per_sample > static_cast<size_t>(kMaxStageBytes)) rows /= 2;
-    if (rows * per_sample <= static_cast<size_t>(kMaxStageBytes)) {
+    if (const int rows = StagedSamplesPerBlock(f.split.rows_per_block, per_sample)) {
       f.staged = true;
       f.split.rows_per_block = rows;
       f.stage_bytes = rows * per_sample;
     }
   }
-  if (is_csr && !concat && f.split.lanes_per_row <= 64 && 64 % f.split.lanes_per_row == 0) {
+  if (is_csr && !concat && LanesDivideWave(f.split.lanes_per_row)) {
     // CSR bags differ in length and nothing is shared inside a workgroup (no LDS, no barrier: the lanes of a bag hand
     // indices to each other across lanes): ONE wavefront per workgroup, so that a wavefront's slot is free as soon as
     // ITS bags are pooled instead of when the longest of a 256-thread workgroup's 8 bags is (C3: 0.187 -> 0.175 ms;
@@ -266,7 +288,7 @@ inline void LaunchGatherReduce(const ElemT* table, int width, const IndexT* indi
   const bool weighted = weights != nullptr;
   const bool stream_rows = options.row_loads == RowLoadPolicy::kStreaming;
   const int lanes = f.split.lanes_per_row;
-  const bool lanes_fit_waves = (lanes <= 64 && 64 % lanes == 0) || lanes == 128;
+  const bool lanes_fit_waves = LanesDivideWave(lanes) || lanes == 128;
   if (options.reduction_order == ReductionOrder::kAllowSplit && lanes_fit_waves &&
       static_cast<int64_t>(batch) * lanes / 64 < kSplitBelowWaves &&
       (offsets != nullptr || num_hots >= 8)) {
@@ -298,23 +320,12 @@ inline void LaunchGatherReduce(const ElemT* table, int width, const IndexT* indi
   }
   const dim3 block(f.split.lanes_per_row, f.split.rows_per_block, 1);
   const dim3 grid(f.grid, 1, 1);
-#define CUEMBED_LAUNCH_GR(W, SRC)                                                         \
-  GatherReduceKernel<ElemT, AccT, IndexT, OffsetT, N, W, SRC>                             \
-      <<<grid, block, f.stage_bytes, stream>>>(table, width, batch, indices, offsets,     \
-                                               num_hots, weights, is_mean, out, 1, stream_rows, \
-                                               offsets != nullptr ? options.sample_order : nullptr, \
-                                               options.row_loads_device)
-  if (f.staged) {
-    if (weighted) CUEMBED_LAUNCH_GR(true, IndexSource::kLdsStaged);
-    else CUEMBED_LAUNCH_GR(false, IndexSource::kLdsStaged);
-  } else if (64 % f.split.lanes_per_row == 0) {
-    if (weighted) CUEMBED_LAUNCH_GR(true, IndexSource::kWaveShuffle);
-    else CUEMBED_LAUNCH_GR(false, IndexSource::kWaveShuffle);
-  } else {
-    if (weighted) CUEMBED_LAUNCH_GR(true, IndexSource::kGlobal);
-    else CUEMBED_LAUNCH_GR(false, IndexSource::kGlobal);
-  }
-#undef CUEMBED_LAUNCH_GR
+  WithIndexSource(f.staged, lanes, weighted, [&](auto w, auto source) {
+    GatherReduceKernel<ElemT, AccT, IndexT, OffsetT, N, decltype(w)::value, decltype(source)::value>
+        <<<grid, block, f.stage_bytes, stream>>>(table, width, batch, indices, offsets, num_hots, weights, is_mean, out, 1,
+                                                 stream_rows, offsets != nullptr ? options.sample_order : nullptr,
+                                                 options.row_loads_device);
+  });
 }
 
 template <typename ElemT, typename IndexT, int N>

@@ -108,6 +108,95 @@ __device__ __forceinline__ const ElemT* RowPtr(const ElemT* base, const int64_t 
   return reinterpret_cast<const ElemT*>(reinterpret_cast<const char*>(base) + r * row_bytes);
 }
 
+//! The sample walk of GatherReduceKernel and GatherReduceQuantizedKernel: which lookups this thread pools, in which
+//! order.  block = (lanes of a row, samples); slot threadIdx.y of workgroup `block_id` pools sample
+//! block_id * blockDim.y + slot.  The walk hands that sample's lookups, in lookup order, to
+//! gather(count, index_at, weight_at) -- index_at(j) / weight_at(j), j < count, give lookup j's row id and weight (the
+//! contract of RowPool::Gather) -- once for kLdsStaged and kGlobal, once per chunk of blockDim.x lookups for
+//! kWaveShuffle.  It sets `sample` (the sample whose bag was walked = the output row) and `hot` (its lookups) and
+//! returns false for a thread without a sample -- after that thread has taken part in the staging barrier.
+//!   dynamic LDS (kLdsStaged only) = blockDim.y * num_hots * (sizeof(IndexT) [+ sizeof(WeightT) if weighted])
+template <IndexSource kSource, bool kWeighted, typename IndexT, typename OffsetT, typename WeightT, typename GatherFn>
+__device__ __forceinline__ bool WalkSample(const int64_t block_id, const int batch, const IndexT* __restrict__ indices,
+                                           const OffsetT* __restrict__ offsets,  // null => fixed hotness
+                                           const int num_hots, const WeightT* __restrict__ weights,
+                                           const int32_t* __restrict__ sample_order,  // CSR only, or null
+                                           int64_t& sample, int& hot, GatherFn gather) {
+  const int lane_x = threadIdx.x;
+  const int slot = threadIdx.y;
+  const int samples_per_block = blockDim.y;
+  sample = block_id * samples_per_block + slot;
+  hot = num_hots;
+  if constexpr (kSource == IndexSource::kLdsStaged) {
+    // ---- fixed hotness: the workgroup's indices (+weights) go through LDS once ----
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    IndexT* stage_idx = reinterpret_cast<IndexT*>(lds_raw);
+    WeightT* stage_w = reinterpret_cast<WeightT*>(stage_idx + samples_per_block * num_hots);
+    const int64_t first = block_id * samples_per_block * num_hots;
+    const int64_t remaining = static_cast<int64_t>(batch) * num_hots - first;
+    const int count = static_cast<int>(
+        remaining < static_cast<int64_t>(samples_per_block) * num_hots
+            ? remaining
+            : static_cast<int64_t>(samples_per_block) * num_hots);
+    const int tid = slot * blockDim.x + lane_x;
+    const int nthreads = blockDim.x * samples_per_block;
+    for (int i = tid; i < count; i += nthreads) {
+      stage_idx[i] = indices[first + i];
+      if constexpr (kWeighted) stage_w[i] = weights[first + i];
+    }
+    __syncthreads();
+    if (sample >= batch) return false;
+    const IndexT* my_idx = stage_idx + slot * num_hots;
+    const WeightT* my_w = stage_w + slot * num_hots;
+    gather(hot, [&](int j) { return WidenIndex(my_idx[j]); }, [&](int j) { return my_w[j]; });
+  } else {
+    if (sample >= batch) return false;
+    // scheduling hint: position p of the grid pools sample sample_order[p] (a permutation of the batch; e.g. bags by
+    // descending length, so that the bags of a wavefront and of neighbouring wavefronts are alike).  Only WHICH lanes
+    // pool a sample changes: its sum and its output row do not.
+    if (sample_order != nullptr) sample = sample_order[sample];
+    int64_t begin;
+    if (offsets != nullptr) {
+      begin = static_cast<int64_t>(offsets[sample]);
+      hot = static_cast<int>(static_cast<int64_t>(offsets[sample + 1]) - begin);
+    } else {
+      begin = sample * num_hots;
+    }
+    const IndexT* my_idx = indices + begin;
+    const WeightT* my_w = weights + begin;
+    if constexpr (kSource == IndexSource::kWaveShuffle) {
+      // ---- lanes_per_row divides 64: the lanes of a sample are consecutive lanes of ONE
+      // wavefront.  They fetch lanes_per_row indices (+weights) with one coalesced load
+      // and hand them to each other with cross-lane reads (ds_bpermute: no LDS storage,
+      // no barrier); the next chunk is fetched while the current one is being pooled.
+      const int group = blockDim.x;
+      IndexT cur_i = static_cast<IndexT>(0);
+      WeightT cur_w = static_cast<WeightT>(0);
+      if (lane_x < hot) {
+        cur_i = my_idx[lane_x];
+        if constexpr (kWeighted) cur_w = my_w[lane_x];
+      }
+      for (int c = 0; c < hot; c += group) {
+        IndexT next_i = static_cast<IndexT>(0);
+        WeightT next_w = static_cast<WeightT>(0);
+        if (c + group + lane_x < hot) {
+          next_i = my_idx[c + group + lane_x];
+          if constexpr (kWeighted) next_w = my_w[c + group + lane_x];
+        }
+        gather((hot - c < group) ? hot - c : group, [&](int j) { return WidenIndex(__shfl(cur_i, j, group)); },
+               [&](int j) { return ShuffleElem(cur_w, j, group); });
+        cur_i = next_i;
+        cur_w = next_w;
+      }
+    } else {
+      // ---- any row split: every lane reads its sample's index straight from global
+      // memory (one address per sample: a broadcast load that mostly hits L1).
+      gather(hot, [&](int j) { return WidenIndex(my_idx[j]); }, [&](int j) { return my_w[j]; });
+    }
+  }
+  return true;
+}
+
 //! Table-row load for RowLoadPolicy::kStreaming: non-temporal (`global_load_dwordx4 ... nt`), i.e. the row does not
 //! stay in L2.  Right when nothing is looked up twice (uniform indices at the C2 shape: 0.379 -> 0.355 ms, the
 //! rows no longer evict each other for nothing); wrong when rows are re-used (alpha = 1.15: 0.136 -> 0.222 ms,
@@ -205,6 +294,8 @@ struct RowPool {
   //! between batches.  `sched_barrier` pins "all loads first, then the adds": without it
   //! the compiler splits a batch (e.g. 5 + 3) to save registers.
   //! kStream: non-temporal row loads (RowLoadPolicy::kStreaming).
+  //! (QuantizedRowPool::Gather, quantized_rows_kernels.hpp, is the same batch loop on codes + trailers: kept apart on
+  //! purpose, docs/EXPERIMENTS.md)
   template <int kUnroll, bool kPipelined, bool kStream = false, typename IndexFn, typename WeightFn>
   __device__ __forceinline__ void Gather(const ElemT* lane_base, const int width, const int count,
                                          IndexFn index_at, WeightFn weight_at) {
@@ -292,17 +383,21 @@ struct RowPool {
   }
 };
 
-//! Epilogue of one pooled row: mean scaling (reference combiner, embedding_lookup_ops.cuh:273-285: scale by the
-//! reciprocal of the accumulated weight; zeros when that is 0), conversion, non-temporal store.
+//! The factor of a mean (reference combiner, embedding_lookup_ops.cuh:273-285): the reciprocal of the accumulated weight
+//! -- of the number of lookups when unweighted -- and 0 when that is 0.
+template <bool kWeighted>
+__device__ __forceinline__ float MeanFactor(float weight_sum, const int hot) {
+  if constexpr (!kWeighted) weight_sum = static_cast<float>(hot);
+  return (weight_sum == 0.f) ? 0.f : 1.0f / weight_sum;
+}
+
+//! Epilogue of one pooled row: mean scaling (MeanFactor), conversion, non-temporal store.
 template <typename ElemT, typename AccT, int N, bool kWeighted>
 __device__ __forceinline__ void FinishPooledRow(RowPool<ElemT, AccT, N, kWeighted>& pool, const int hot,
                                                 const bool is_mean, ElemT* dst) {
   using A = Arith<AccT>;
   if (is_mean) {
-    float weight_sum = pool.weight_sum;
-    if constexpr (!kWeighted) weight_sum = static_cast<float>(hot);
-    const float inv = (weight_sum == 0.f) ? 0.f : 1.0f / weight_sum;
-    const AccT scale = static_cast<AccT>(inv);
+    const AccT scale = static_cast<AccT>(MeanFactor<kWeighted>(pool.weight_sum, hot));
 #pragma unroll
     for (int e = 0; e < N; ++e) pool.acc[e] = A::mul(pool.acc[e], scale);
   }
@@ -342,98 +437,21 @@ GatherReduceKernel(const ElemT* __restrict__ table,
                    const bool stream_rows_host, // RowLoadPolicy::kStreaming: table rows are not kept in L2
                    const int32_t* __restrict__ sample_order = nullptr,    // ForwardOptions::sample_order (CSR only)
                    const uint32_t* __restrict__ row_loads_device = nullptr) {   // ForwardOptions::row_loads_device
-  using A = Arith<AccT>;
   // (the decision taken on the device, DecideRowLoads: one scalar load, the same value for every wavefront)
   const bool stream_rows = row_loads_device != nullptr ? (*row_loads_device != 0u) : stream_rows_host;
-  const int lane_x = threadIdx.x;
-  const int slot = threadIdx.y;
-  const int samples_per_block = blockDim.y;
   const ColumnSlice cs = ColumnSlice::Of(blockIdx.x, column_slices);
-  const int64_t block_id = cs.block;
-  int64_t sample = block_id * samples_per_block + slot;
-  const int64_t column0 = (static_cast<int64_t>(cs.slice) * blockDim.x + lane_x) * N;
+  const int64_t column0 = (static_cast<int64_t>(cs.slice) * blockDim.x + threadIdx.x) * N;
   const ElemT* lane_base = table + column0;
   RowPool<ElemT, AccT, N, kWeighted> pool;
-  int hot = num_hots;
-
-  if constexpr (kSource == IndexSource::kLdsStaged) {
-    // ---- fixed hotness: the workgroup's indices (+weights) go through LDS once ----
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    IndexT* stage_idx = reinterpret_cast<IndexT*>(lds_raw);
-    ElemT* stage_w = reinterpret_cast<ElemT*>(stage_idx + samples_per_block * num_hots);
-    const int64_t first = block_id * samples_per_block * num_hots;
-    const int64_t remaining = static_cast<int64_t>(batch) * num_hots - first;
-    const int count = static_cast<int>(
-        remaining < static_cast<int64_t>(samples_per_block) * num_hots
-            ? remaining
-            : static_cast<int64_t>(samples_per_block) * num_hots);
-    const int tid = slot * blockDim.x + lane_x;
-    const int nthreads = blockDim.x * samples_per_block;
-    for (int i = tid; i < count; i += nthreads) {
-      stage_idx[i] = indices[first + i];
-      if constexpr (kWeighted) stage_w[i] = weights[first + i];
-    }
-    __syncthreads();
-    if (sample >= batch) return;
-    const IndexT* my_idx = stage_idx + slot * num_hots;
-    const ElemT* my_w = stage_w + slot * num_hots;
-    const auto idx_at = [&](int j) { return WidenIndex(my_idx[j]); };
-    const auto w_at = [&](int j) { return my_w[j]; };
-    if (stream_rows) pool.template Gather<kUnroll, kPipelined, true>(lane_base, width, hot, idx_at, w_at);
-    else pool.template Gather<kUnroll, kPipelined, false>(lane_base, width, hot, idx_at, w_at);
-  } else {
-    if (sample >= batch) return;
-    // scheduling hint: position p of the grid pools sample sample_order[p] (a permutation of the batch; e.g. bags by
-    // descending length, so that the bags of a wavefront and of neighbouring wavefronts are alike).  Only WHICH lanes
-    // pool a sample changes: its sum and its output row do not.
-    if (sample_order != nullptr) sample = sample_order[sample];
-    int64_t begin;
-    if (offsets != nullptr) {
-      begin = static_cast<int64_t>(offsets[sample]);
-      hot = static_cast<int>(static_cast<int64_t>(offsets[sample + 1]) - begin);
-    } else {
-      begin = sample * num_hots;
-    }
-    const IndexT* my_idx = indices + begin;
-    const ElemT* my_w = weights + begin;
-    if constexpr (kSource == IndexSource::kWaveShuffle) {
-      // ---- lanes_per_row divides 64: the lanes of a sample are consecutive lanes of ONE
-      // wavefront.  They fetch lanes_per_row indices (+weights) with one coalesced load
-      // and hand them to each other with cross-lane reads (ds_bpermute: no LDS storage,
-      // no barrier); the next chunk is fetched while the current one is being pooled.
-      const int group = blockDim.x;
-      IndexT cur_i = static_cast<IndexT>(0);
-      ElemT cur_w = static_cast<ElemT>(0);
-      if (lane_x < hot) {
-        cur_i = my_idx[lane_x];
-        if constexpr (kWeighted) cur_w = my_w[lane_x];
-      }
-      for (int c = 0; c < hot; c += group) {
-        IndexT next_i = static_cast<IndexT>(0);
-        ElemT next_w = static_cast<ElemT>(0);
-        if (c + group + lane_x < hot) {
-          next_i = my_idx[c + group + lane_x];
-          if constexpr (kWeighted) next_w = my_w[c + group + lane_x];
-        }
-        const int n = (hot - c < group) ? hot - c : group;
-        const auto idx_at = [&](int j) { return WidenIndex(__shfl(cur_i, j, group)); };
-        const auto w_at = [&](int j) { return ShuffleElem(cur_w, j, group); };
-        if (stream_rows) pool.template Gather<kUnroll, kPipelined, true>(lane_base, width, n, idx_at, w_at);
-        else pool.template Gather<kUnroll, kPipelined, false>(lane_base, width, n, idx_at, w_at);
-        cur_i = next_i;
-        cur_w = next_w;
-      }
-    } else {
-      // ---- any row split: every lane reads its sample's index straight from global
-      // memory (one address per sample: a broadcast load that mostly hits L1).
-      const auto idx_at = [&](int j) { return WidenIndex(my_idx[j]); };
-      const auto w_at = [&](int j) { return my_w[j]; };
-      if (stream_rows) pool.template Gather<kUnroll, kPipelined, true>(lane_base, width, hot, idx_at, w_at);
-      else pool.template Gather<kUnroll, kPipelined, false>(lane_base, width, hot, idx_at, w_at);
-    }
-  }
-
-  // ---- epilogue -----------------------------------------------------------
+  const auto gather = [&](const int count, const auto index_at, const auto weight_at) {
+    if (stream_rows) pool.template Gather<kUnroll, kPipelined, true>(lane_base, width, count, index_at, weight_at);
+    else pool.template Gather<kUnroll, kPipelined, false>(lane_base, width, count, index_at, weight_at);
+  };
+  int64_t sample;
+  int hot;
+  if (!WalkSample<kSource, kWeighted>(cs.block, batch, indices, offsets, num_hots, weights, sample_order, sample, hot,
+                                      gather))
+    return;
   FinishPooledRow<ElemT, AccT, N, kWeighted>(pool, hot, is_mean, out + sample * width + column0);
 }
 

@@ -71,7 +71,7 @@ inline QuantizedForwardLaunch PlanQuantizedForward(const int width, const int co
   f.lanes_per_row = width / codes_per_lane;
   CUEMBED_ASSERT(f.lanes_per_row <= kMaxBlockThreads);
   const int lanes = f.lanes_per_row;
-  const bool lanes_fit_wave = lanes <= 64 && 64 % lanes == 0;
+  const bool lanes_fit_wave = LanesDivideWave(lanes);
   const int wave_rows = lanes_fit_wave ? 64 / lanes : 1;
   int rows = lanes >= kDefaultBlockThreads ? 1 : kDefaultBlockThreads / lanes;
   if (is_csr && lanes_fit_wave) rows = wave_rows;
@@ -81,9 +81,7 @@ inline QuantizedForwardLaunch PlanQuantizedForward(const int width, const int co
   f.staged = false;
   if (!is_csr) {
     const size_t per_sample = static_cast<size_t>(num_hots) * (index_bytes + (weighted ? weight_bytes : 0));
-    int fewer = rows;
-    while (fewer > 1 && fewer * per_sample > static_cast<size_t>(kMaxStageBytes)) fewer /= 2;
-    if (fewer * per_sample <= static_cast<size_t>(kMaxStageBytes)) {
+    if (const int fewer = StagedSamplesPerBlock(rows, per_sample)) {
       f.staged = true;
       rows = fewer;
       f.stage_bytes = rows * per_sample;
@@ -103,21 +101,12 @@ inline void LaunchGatherReduceQuantized(const uint8_t* table, const int width, c
   const bool stream_rows = options.row_loads == RowLoadPolicy::kStreaming;
   const dim3 block(f.lanes_per_row, f.rows_per_block, 1);
   const dim3 grid(f.grid, 1, 1);
-#define CUEMBED_LAUNCH_GRQ(W, SRC)                                                                              \
-  GatherReduceQuantizedKernel<OutT, IndexT, OffsetT, N, W, SRC><<<grid, block, f.stage_bytes, stream>>>(        \
-      table, width, batch, indices, offsets, num_hots, weights, is_mean, out, stream_rows,                      \
-      offsets != nullptr ? options.sample_order : nullptr, options.row_loads_device)
-  if (f.staged) {
-    if (weighted) CUEMBED_LAUNCH_GRQ(true, IndexSource::kLdsStaged);
-    else CUEMBED_LAUNCH_GRQ(false, IndexSource::kLdsStaged);
-  } else if (f.lanes_per_row <= 64 && 64 % f.lanes_per_row == 0) {
-    if (weighted) CUEMBED_LAUNCH_GRQ(true, IndexSource::kWaveShuffle);
-    else CUEMBED_LAUNCH_GRQ(false, IndexSource::kWaveShuffle);
-  } else {
-    if (weighted) CUEMBED_LAUNCH_GRQ(true, IndexSource::kGlobal);
-    else CUEMBED_LAUNCH_GRQ(false, IndexSource::kGlobal);
-  }
-#undef CUEMBED_LAUNCH_GRQ
+  WithIndexSource(f.staged, f.lanes_per_row, weighted, [&](auto w, auto source) {
+    GatherReduceQuantizedKernel<OutT, IndexT, OffsetT, N, decltype(w)::value, decltype(source)::value>
+        <<<grid, block, f.stage_bytes, stream>>>(table, width, batch, indices, offsets, num_hots, weights, is_mean, out,
+                                                 stream_rows, offsets != nullptr ? options.sample_order : nullptr,
+                                                 options.row_loads_device);
+  });
 }
 
 }  // namespace detail

@@ -10,10 +10,11 @@
 //   DequantizeRowsKernel          fused rows (all, or the rows a list of ids names) -> fp32 / fp16 [n, W]
 //   GatherReduceQuantizedKernel   sum / mean of looked-up rows, fixed hotness or CSR, optionally weighted
 //
-// The gather is GatherReduceKernel's mapping (gather_reduce_kernels.hpp) on 16-byte loads of CODES: one lane owns 16
-// codes (one global_load_dwordx4 at an 8-byte aligned address), a 256-value row is 16 lanes, a wavefront pools FOUR
-// samples, and four lookups per sample are in flight before the first is consumed (narrower lanes, 8 or 4 codes, where
-// the row does not divide into 16s: eight in flight).  Per lookup a lane spends 16 v_cvt_f32_ubyte and 8 v_pk_fma_f32.
+// The gather is GatherReduceKernel's sample walk (WalkSample, gather_reduce_kernels.hpp) and mapping on 16-byte loads
+// of CODES: one lane owns 16 codes (one global_load_dwordx4 at an 8-byte aligned address), a 256-value row is 16 lanes,
+// a wavefront pools FOUR samples, and four lookups per sample are in flight before the first is consumed (narrower
+// lanes, 8 or 4 codes, where the row does not divide into 16s: eight in flight).  Per lookup a lane spends 16
+// v_cvt_f32_ubyte and 8 v_pk_fma_f32.
 //   * scale and bias reach the lanes by ONE extra 8-byte load per lookup at an address all lanes of the row share
 //     (a broadcast inside the load unit: no cross-lane instruction, no LDS); its address is the code address plus a
 //     per-lane constant, so a lookup costs one id x row_bytes multiply, as in the fp16 kernel;
@@ -256,7 +257,8 @@ struct QuantizedRowPool {
 
   //! Pools `count` lookups in order; kUnroll code loads and as many trailer loads are issued back-to-back before the
   //! first is consumed (`sched_barrier` pins "all loads first"), the tail of a bag as one predicated batch (as
-  //! RowPool::Gather).
+  //! RowPool::Gather, gather_reduce_kernels.hpp: the same batch loop on rows, kept apart on purpose,
+  //! docs/EXPERIMENTS.md).
   //! lane_base = table + this lane's first code; the row's trailer is trailer_delta bytes behind the lane's codes
   //! (one 64-bit add on the address the codes are loaded from, instead of a second id x row_bytes multiply).
   template <int kUnroll, bool kStream, typename IndexFn, typename WeightFn>
@@ -327,94 +329,22 @@ GatherReduceQuantizedKernel(const uint8_t* __restrict__ table,
   using A = Arith<float>;
   const bool stream_rows = row_loads_device != nullptr ? (*row_loads_device != 0u) : stream_rows_host;
   const int lane_x = threadIdx.x;
-  const int slot = threadIdx.y;
-  const int samples_per_block = blockDim.y;
-  const int64_t block_id = blockIdx.x;
-  int64_t sample = block_id * samples_per_block + slot;
   const int row_bytes = width + kQuantizedTrailerBytes;
   const uint8_t* lane_base = table + lane_x * N;
   const int64_t trailer_delta = width - lane_x * N;
   QuantizedRowPool<OutT, N, kWeighted> pool;
-  int hot = num_hots;
+  const auto gather = [&](const int count, const auto index_at, const auto weight_at) {
+    if (stream_rows) pool.template Gather<kUnroll, true>(lane_base, trailer_delta, row_bytes, count, index_at, weight_at);
+    else pool.template Gather<kUnroll, false>(lane_base, trailer_delta, row_bytes, count, index_at, weight_at);
+  };
+  int64_t sample;
+  int hot;
+  if (!WalkSample<kSource, kWeighted>(blockIdx.x, batch, indices, offsets, num_hots, weights, sample_order, sample, hot,
+                                      gather))   // (the walk of GatherReduceKernel: gather_reduce_kernels.hpp)
+    return;
 
-  if constexpr (kSource == IndexSource::kLdsStaged) {
-    // ---- fixed hotness: the workgroup's indices (+weights) go through LDS once ----
-    extern __shared__ __attribute__((aligned(16))) unsigned char quantized_lds_raw[];
-    IndexT* stage_idx = reinterpret_cast<IndexT*>(quantized_lds_raw);
-    OutT* stage_w = reinterpret_cast<OutT*>(stage_idx + samples_per_block * num_hots);
-    const int64_t first = block_id * samples_per_block * num_hots;
-    const int64_t remaining = static_cast<int64_t>(batch) * num_hots - first;
-    const int count = static_cast<int>(
-        remaining < static_cast<int64_t>(samples_per_block) * num_hots
-            ? remaining
-            : static_cast<int64_t>(samples_per_block) * num_hots);
-    const int tid = slot * blockDim.x + lane_x;
-    const int nthreads = blockDim.x * samples_per_block;
-    for (int i = tid; i < count; i += nthreads) {
-      stage_idx[i] = indices[first + i];
-      if constexpr (kWeighted) stage_w[i] = weights[first + i];
-    }
-    __syncthreads();
-    if (sample >= batch) return;
-    const IndexT* my_idx = stage_idx + slot * num_hots;
-    const OutT* my_w = stage_w + slot * num_hots;
-    const auto idx_at = [&](int j) { return WidenIndex(my_idx[j]); };
-    const auto w_at = [&](int j) { return my_w[j]; };
-    if (stream_rows) pool.template Gather<kUnroll, true>(lane_base, trailer_delta, row_bytes, hot, idx_at, w_at);
-    else pool.template Gather<kUnroll, false>(lane_base, trailer_delta, row_bytes, hot, idx_at, w_at);
-  } else {
-    if (sample >= batch) return;
-    if (sample_order != nullptr) sample = sample_order[sample];   // which lanes pool a sample: never what they compute
-    int64_t begin;
-    if (offsets != nullptr) {
-      begin = static_cast<int64_t>(offsets[sample]);
-      hot = static_cast<int>(static_cast<int64_t>(offsets[sample + 1]) - begin);
-    } else {
-      begin = sample * num_hots;
-    }
-    const IndexT* my_idx = indices + begin;
-    const OutT* my_w = weights + begin;
-    if constexpr (kSource == IndexSource::kWaveShuffle) {
-      // ---- lanes_per_row divides 64: the lanes of a sample fetch lanes_per_row indices (+weights) with one coalesced
-      // load and hand them to each other with cross-lane reads; the next chunk is fetched while this one is pooled
-      const int group = blockDim.x;
-      IndexT cur_i = static_cast<IndexT>(0);
-      OutT cur_w = static_cast<OutT>(0);
-      if (lane_x < hot) {
-        cur_i = my_idx[lane_x];
-        if constexpr (kWeighted) cur_w = my_w[lane_x];
-      }
-      for (int c = 0; c < hot; c += group) {
-        IndexT next_i = static_cast<IndexT>(0);
-        OutT next_w = static_cast<OutT>(0);
-        if (c + group + lane_x < hot) {
-          next_i = my_idx[c + group + lane_x];
-          if constexpr (kWeighted) next_w = my_w[c + group + lane_x];
-        }
-        const int n = (hot - c < group) ? hot - c : group;
-        const auto idx_at = [&](int j) { return WidenIndex(__shfl(cur_i, j, group)); };
-        const auto w_at = [&](int j) { return ShuffleElem(cur_w, j, group); };
-        if (stream_rows) pool.template Gather<kUnroll, true>(lane_base, trailer_delta, row_bytes, n, idx_at, w_at);
-        else pool.template Gather<kUnroll, false>(lane_base, trailer_delta, row_bytes, n, idx_at, w_at);
-        cur_i = next_i;
-        cur_w = next_w;
-      }
-    } else {
-      // ---- any row split: every lane reads its sample's index straight from global memory (a broadcast load)
-      const auto idx_at = [&](int j) { return WidenIndex(my_idx[j]); };
-      const auto w_at = [&](int j) { return my_w[j]; };
-      if (stream_rows) pool.template Gather<kUnroll, true>(lane_base, trailer_delta, row_bytes, hot, idx_at, w_at);
-      else pool.template Gather<kUnroll, false>(lane_base, trailer_delta, row_bytes, hot, idx_at, w_at);
-    }
-  }
-
-  // ---- epilogue: the bag's bias once, mean scaling (the combiner of FinishPooledRow), one rounding to OutT ----
-  float inv = 1.f;
-  if (is_mean) {
-    float weight_sum = pool.weight_sum;
-    if constexpr (!kWeighted) weight_sum = static_cast<float>(hot);
-    inv = (weight_sum == 0.f) ? 0.f : 1.0f / weight_sum;
-  }
+  // ---- epilogue: the bag's bias once, mean scaling (MeanFactor, as FinishPooledRow), one rounding to OutT ----
+  const float inv = is_mean ? MeanFactor<kWeighted>(pool.weight_sum, hot) : 1.f;
   float v[N];
 #pragma unroll
   for (int e = 0; e < N; ++e) {

@@ -7,6 +7,9 @@
 //   * RowPool::Gather                : every lookup pooled exactly once and IN ORDER for every count around the unroll
 //                                      and pipelining boundaries (0 .. 40 lookups), plain and weighted, both load kinds;
 //   * FinishPooledRow                : mean = multiply by the reciprocal of the weight sum, zeros for an empty bag;
+//   * WalkSample                     : every lookup of a thread's sample handed to the callback exactly once and IN ORDER,
+//                                      for the three index sources, fixed hotness and CSR bags of 0 .. 2 x group + 1
+//                                      lookups, with a sample order, a partial last workgroup;
 //   * AccumulateRow                  : the backward's fp32 partial sums of fp16 rows, weighted and not;
 //   * PackRowsByOwner / FinishOwnerPiece (exchange_transforms.hpp, the header API itself): range starts, slots, padding
 //                                      ids, untouched slack, the flag word; the piece's count, zeroed row, tail.
@@ -211,6 +214,107 @@ static void Pooling(const char* name) {
   }
 }
 
+// ---- the sample walk -------------------------------------------------------------------------------------------------
+// Every thread records the (row id, weight) sequence the walk hands to its callback, the sample and the lookup count it
+// reports; the host compares with the bag of the sample that thread's slot stands for.
+template <IndexSource kSource, bool kWeighted, typename IndexT>
+__global__ void WalkKernel(const int batch, const IndexT* indices, const IndexT* offsets, const int num_hots,
+                           const float* weights, const int32_t* sample_order, const int capacity, int64_t* seen_id,
+                           float* seen_w, int* seen_count, int64_t* seen_sample, int* seen_hot) {
+  const size_t thread = (static_cast<size_t>(blockIdx.x) * blockDim.y + threadIdx.y) * blockDim.x + threadIdx.x;
+  int n = 0;
+  const auto record = [&](const int count, const auto index_at, const auto weight_at) {
+    for (int j = 0; j < count; ++j, ++n) {
+      const int64_t r = index_at(j);      // (a cross-lane read for kWaveShuffle: every lane of the group makes it)
+      const float w = kWeighted ? weight_at(j) : 0.f;
+      if (n < capacity) {
+        seen_id[thread * capacity + n] = r;
+        seen_w[thread * capacity + n] = w;
+      }
+    }
+  };
+  int64_t sample = -1;
+  int hot = -1;
+  const bool has_sample = WalkSample<kSource, kWeighted>(static_cast<int64_t>(blockIdx.x), batch, indices, offsets,
+                                                         num_hots, weights, sample_order, sample, hot, record);
+  seen_count[thread] = has_sample ? n : -1;
+  seen_sample[thread] = sample;
+  seen_hot[thread] = hot;
+}
+
+template <IndexSource kSource, bool kWeighted, typename IndexT>
+static void Walk(const char* name, const int group, const bool csr, const bool ordered) {
+  const int per_block = 256 / group;                     // samples per workgroup
+  const int lengths = 2 * group + 2;                     // CSR bags of 0 .. 2 * group + 1 lookups
+  const int batch = std::max(lengths, per_block) + per_block / 2 + 1;   // more than one workgroup, the last one partial
+  const int num_hots = csr ? 0 : 2 * group + 1;         // staged: 512 + 256 / group entries, three passes of the staging loop
+  std::mt19937 rng(17 + group);
+  std::vector<IndexT> offsets(batch + 1, 0);
+  for (int s = 0; s < batch; ++s) offsets[s + 1] = offsets[s] + (csr ? s % lengths : num_hots);
+  const int nnz = static_cast<int>(offsets[batch]);
+  std::vector<IndexT> indices(nnz);
+  std::vector<float> weights(nnz);
+  for (int i = 0; i < nnz; ++i) {
+    indices[i] = static_cast<IndexT>(sizeof(IndexT) == 8 ? (int64_t{1} << 33) + rng() : rng() & 0x7fffffffu);
+    weights[i] = static_cast<float>(rng() % 1000) / 16.f;
+  }
+  std::vector<int32_t> order(batch);
+  for (int s = 0; s < batch; ++s) order[s] = s;
+  std::shuffle(order.begin(), order.end(), rng);
+  const int blocks = (batch + per_block - 1) / per_block;
+  const size_t threads = static_cast<size_t>(blocks) * 256;
+  const int capacity = csr ? lengths - 1 : num_hots;     // the longest bag
+  const DeviceArray<IndexT> d_idx(indices), d_off(offsets);
+  const DeviceArray<float> d_w(weights);
+  const DeviceArray<int32_t> d_order(order);
+  DeviceArray<int64_t> d_id(threads * capacity), d_sample(threads);
+  DeviceArray<float> d_seen_w(threads * capacity);
+  DeviceArray<int> d_count(threads), d_hot(threads);
+  const size_t lds = kSource != IndexSource::kLdsStaged
+                         ? 0
+                         : static_cast<size_t>(per_block) * num_hots * (sizeof(IndexT) + sizeof(float));
+  WalkKernel<kSource, kWeighted, IndexT><<<blocks, dim3(group, per_block, 1), lds>>>(
+      batch, d_idx.ptr, csr ? d_off.ptr : nullptr, num_hots, d_w.ptr, ordered ? d_order.ptr : nullptr, capacity, d_id.ptr,
+      d_seen_w.ptr, d_count.ptr, d_sample.ptr, d_hot.ptr);
+  HIP_OK(hipDeviceSynchronize());
+  const auto id = d_id.Download(), sample = d_sample.Download();
+  const auto w = d_seen_w.Download();
+  const auto count = d_count.Download(), hot = d_hot.Download();
+  for (size_t t = 0; t < threads; ++t) {
+    const int position = static_cast<int>(t / group);    // of the thread's slot in the grid
+    if (position >= batch) {
+      CHECK(count[t] == -1, "%s group %d: thread %zu has no sample but walked %d lookups", name, group, t, count[t]);
+      continue;
+    }
+    const int s = ordered ? order[position] : position;
+    const int begin = static_cast<int>(offsets[s]), len = static_cast<int>(offsets[s + 1]) - begin;
+    CHECK(sample[t] == s && hot[t] == len && count[t] == len,
+          "%s group %d: thread %zu walked sample %lld, %d of %d lookups, host sample %d of %d", name, group, t,
+          (long long)sample[t], count[t], hot[t], s, len);
+    for (int j = 0; j < len && j < count[t]; ++j) {
+      CHECK(id[t * capacity + j] == static_cast<int64_t>(indices[begin + j]),
+            "%s group %d: thread %zu lookup %d is row %lld, host %lld", name, group, t, j,
+            (long long)id[t * capacity + j], (long long)indices[begin + j]);
+      if (kWeighted)
+        CHECK(SameBits(w[t * capacity + j], weights[begin + j]), "%s group %d: thread %zu lookup %d weight %g, host %g",
+              name, group, t, j, w[t * capacity + j], weights[begin + j]);
+    }
+  }
+}
+
+template <typename IndexT, bool kWeighted>
+static void Walks(const char* name) {
+  for (const int group : {1, 4, 64}) {
+    Walk<IndexSource::kLdsStaged, kWeighted, IndexT>(name, group, false, false);
+    for (const bool csr : {false, true})
+      for (const bool ordered : {false, true}) {
+        if (ordered && !csr) continue;                    // a sample order is a hint for CSR batches
+        Walk<IndexSource::kWaveShuffle, kWeighted, IndexT>(name, group, csr, ordered);
+        Walk<IndexSource::kGlobal, kWeighted, IndexT>(name, group, csr, ordered);
+      }
+  }
+}
+
 // ---- the backward's partial sums -------------------------------------------------------------------------------------
 template <typename GradT, int N, bool kWeighted>
 __global__ void AccumulateKernel(const GradT* rows, const float* weights, const int count, float* out) {
@@ -362,6 +466,10 @@ int main() {
   Pooling<_Float16, _Float16, 8, false, 8, false, false>("f16 rows, fp16 accumulate (fp16_math)");
   Pooling<_Float16, _Float16, 8, true, 16, false, false>("f16 rows weighted, fp16 accumulate, unroll 16");
   Pooling<_Float16, float, 2, true, 8, false, false>("f16 rows weighted, 4-byte lanes");
+  Walks<int32_t, false>("walk: i32 ids");
+  Walks<int32_t, true>("walk: i32 ids, weighted");
+  Walks<int64_t, false>("walk: i64 ids");
+  Walks<int64_t, true>("walk: i64 ids, weighted");
   BackwardPartialSums<_Float16, 8, false>("fp16 grad_y rows, fp32 partial sums");
   BackwardPartialSums<_Float16, 8, true>("fp16 grad_y rows x weight, fp32 partial sums");
   BackwardPartialSums<float, 4, true>("fp32 grad_y rows x weight");

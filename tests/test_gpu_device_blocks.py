@@ -1,7 +1,8 @@
 """Unit tests of the gather / scatter building blocks ON THE DEVICE (tests/cpp/device_blocks_unit.hip): the counterpart
 of the reference's tests/test_embedding_ops.cu:121-374 (Addresser, Combiner, IndexLoader, GradAddresser, GradCombiner unit
 tests) for the blocks this design is made of -- WidenIndex / RowElems / RowPtr, ColumnSlice, Pack + Arith + RowPool (Add,
-Gather around every unroll / pipelining boundary, both load kinds), FinishPooledRow (mean, empty bag), AccumulateRow --
+Gather around every unroll / pipelining boundary, both load kinds), FinishPooledRow (mean, empty bag), WalkSample (every
+lookup of a thread's sample handed over once and in order, for the three index sources), AccumulateRow --
 each instantiated in a small kernel and compared bit for bit with the same single-rounding operations on the host."""
 import subprocess
 
