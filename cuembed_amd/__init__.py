@@ -25,5 +25,7 @@ from .ops import (CONCAT, MEAN, SUM, ComputeCompressedGradIndices, EmbeddingBack
                   adam_bias_factor, new_adam_clock, adam_clock_advance, ADAM_RULES)
 from .quantized import (QuantizedEmbeddingBag, dequantize_rows, embedding_forward_quantized,  # noqa: F401
                         quantize_rows, quantized_forward_launch_shape, quantized_row_bytes)
+from .grouped import (EmbeddingBagGroup, QuantizedEmbeddingBagGroup, TableGroup,  # noqa: F401
+                      embedding_forward_grouped, embedding_forward_quantized_grouped, grouped_forward_launch_shape)
 
 __version__ = "0.1.0"

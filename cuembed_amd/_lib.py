@@ -152,6 +152,14 @@ def _declare(L):
                                                       _VP]
     L.cuembed_quantized_forward_launch_shape.restype = None
     L.cuembed_quantized_forward_launch_shape.argtypes = [_I, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]
+    L.cuembed_embedding_forward_grouped.restype = None
+    L.cuembed_embedding_forward_grouped.argtypes = [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, _I, _VP, _I, _VP,
+                                                    _VP]
+    L.cuembed_embedding_forward_quantized_grouped.restype = None
+    L.cuembed_embedding_forward_quantized_grouped.argtypes = [_VP, _VP, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, _I, _VP,
+                                                              _I, _I, _VP, _VP]
+    L.cuembed_grouped_forward_launch_shape.restype = None
+    L.cuembed_grouped_forward_launch_shape.argtypes = [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]
     L.cuembed_peek_last_error.restype = _I
     L.cuembed_peek_last_error.argtypes = []
     L.cuembed_version.restype = ctypes.c_char_p

@@ -115,6 +115,8 @@ __device__ __forceinline__ const ElemT* RowPtr(const ElemT* base, const int64_t 
 //! contract of RowPool::Gather) -- once for kLdsStaged and kGlobal, once per chunk of blockDim.x lookups for
 //! kWaveShuffle.  It sets `sample` (the sample whose bag was walked = the output row) and `hot` (its lookups) and
 //! returns false for a thread without a sample -- after that thread has taken part in the staging barrier.
+//! `sample` is final, sample_order applied, before the walk first calls gather, in all three branches: the gather
+//! callback may therefore read `sample` by reference (grouped_gather_kernels.hpp takes its table from it).
 //!   dynamic LDS (kLdsStaged only) = blockDim.y * num_hots * (sizeof(IndexT) [+ sizeof(WeightT) if weighted])
 template <IndexSource kSource, bool kWeighted, typename IndexT, typename OffsetT, typename WeightT, typename GatherFn>
 __device__ __forceinline__ bool WalkSample(const int64_t block_id, const int batch, const IndexT* __restrict__ indices,

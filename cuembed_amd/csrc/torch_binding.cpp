@@ -1136,6 +1136,130 @@ at::Tensor cuemb_embedding_quantized_op(const at::Tensor& qtable, const at::Tens
   return out;
 }
 
+// ---- a GROUP of tables pooled in one launch (extension; forward only: no autograd formula).  `tables` keeps the
+// tensors (and gives the host copy of their base pointers, which the library reads for the access width); `table_ptrs`
+// is the caller's int64 device tensor of the same pointers, built once (cuembed_amd.TableGroup), which the kernel reads.
+// offsets given: CSR, num_tables * batch + 1 entries; absent: fixed hotness, indices is [num_tables, batch, hotness].
+// Returns [batch, num_tables, width].
+
+struct GroupedCall {
+  std::vector<const void*> host_ptrs;
+  at::Tensor i, o, w, order;
+  int idx = CUEMBED_I32, off = CUEMBED_I32;
+  int64_t batch = 0, hot = 0;
+};
+
+GroupedCall CheckGroupedCall(const at::TensorList tables, const at::Tensor& table_ptrs, const at::Tensor& indices,
+                             const c10::optional<at::Tensor>& offsets, const c10::optional<at::Tensor>& weights,
+                             const at::ScalarType weight_type, const int64_t row_loads,
+                             const c10::optional<at::Tensor>& sample_order) {
+  GroupedCall c;
+  const int64_t num_tables = static_cast<int64_t>(tables.size());
+  TORCH_CHECK(num_tables >= 1, "cuembed_pyt: a group needs at least one table");
+  for (const at::Tensor& t : tables) {
+    CheckGpu(t, "tables");
+    TORCH_CHECK(t.dim() == 2 && t.is_contiguous() && t.scalar_type() == tables[0].scalar_type() &&
+                    t.size(1) == tables[0].size(1) && t.device() == tables[0].device(),
+                "cuembed_pyt: the tables of a group must be contiguous [rows, width] of one dtype, width and device");
+    TORCH_CHECK(!(at::GradMode::is_enabled() && t.requires_grad()),
+                "cuembed_pyt: a table requires grad: the grouped forward is forward only");
+    c.host_ptrs.push_back(t.data_ptr());
+  }
+  TORCH_CHECK(table_ptrs.is_cuda() && table_ptrs.device() == tables[0].device() && table_ptrs.scalar_type() == at::kLong &&
+                  table_ptrs.is_contiguous() && table_ptrs.numel() == num_tables,
+              "cuembed_pyt: table_ptrs must be the contiguous int64 tensor of the tables' data pointers on their device");
+  CheckGpu(indices, "indices");
+  c.idx = IndexCode(indices, "indices");
+  TORCH_CHECK(row_loads >= -1 && row_loads <= 1, "cuembed_pyt: row_loads must be -1, 0 or 1");
+  c.i = indices.contiguous();
+  const bool csr = offsets.has_value() && offsets->defined();
+  if (csr) {
+    CheckGpu(*offsets, "offsets");
+    c.off = IndexCode(*offsets, "offsets");
+    c.o = offsets->contiguous();
+    TORCH_CHECK(c.o.numel() >= 1 && (c.o.numel() - 1) % num_tables == 0,
+                "cuembed_pyt: offsets must hold num_tables * batch_size + 1 entries");
+    c.batch = (c.o.numel() - 1) / num_tables;
+  } else {
+    TORCH_CHECK(c.i.dim() == 3 && c.i.size(0) == num_tables && c.i.size(2) > 0,
+                "cuembed_pyt: without offsets, indices must be [num_tables, batch, hotness]");
+    c.batch = c.i.size(1);
+    c.hot = c.i.size(2);
+  }
+  TORCH_CHECK(num_tables * c.batch <= INT32_MAX, "cuembed_pyt: num_tables * batch_size must fit a 32-bit int");
+  if (weights.has_value() && weights->defined()) {
+    CheckGpu(*weights, "weights");
+    TORCH_CHECK(weights->scalar_type() == weight_type, "cuembed_pyt: weights have the wrong dtype");
+    TORCH_CHECK(weights->numel() >= c.i.numel(), "cuembed_pyt: weights must have one entry per index");
+    c.w = weights->contiguous();
+  }
+  if (sample_order.has_value() && sample_order->defined()) {
+    c.order = *sample_order;
+    TORCH_CHECK(csr && c.order.is_cuda() && c.order.scalar_type() == at::kInt &&
+                    c.order.numel() == num_tables * c.batch && c.order.is_contiguous(),
+                "cuembed_pyt: sample_order (CSR only) must be a contiguous int32 permutation of the bags on the GPU");
+  }
+  return c;
+}
+
+int GroupedMode(const std::string& mode) {
+  TORCH_CHECK(mode == "sum" || mode == "mean", "cuembed_pyt: mode must be 'sum' or 'mean'");
+  return mode == "sum" ? CUEMBED_SUM : CUEMBED_MEAN;
+}
+
+at::Tensor cuemb_embedding_grouped_op(const at::TensorList tables, const at::Tensor& table_ptrs, const at::Tensor& indices,
+                                      const c10::optional<at::Tensor>& offsets, const c10::optional<at::Tensor>& weights,
+                                      const std::string& mode, const int64_t row_loads,
+                                      const c10::optional<at::Tensor>& sample_order) {
+  const int m = GroupedMode(mode);
+  TORCH_CHECK(!tables.empty(), "cuembed_pyt: a group needs at least one table");
+  const int elem = ElemCode(tables[0], "tables");
+  const at::DeviceGuard guard(tables[0].device());
+  const GroupedCall c =
+      CheckGroupedCall(tables, table_ptrs, indices, offsets, weights, tables[0].scalar_type(), row_loads, sample_order);
+  const int64_t num_tables = static_cast<int64_t>(tables.size()), width = tables[0].size(1);
+  at::Tensor out = at::empty({c.batch, num_tables, width}, tables[0].options());
+  uintptr_t bits = 0;
+  for (const void* p : c.host_ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+  CheckRowAlignment("tables", width, tables[0].element_size(), {reinterpret_cast<const void*>(bits), Ptr(out)}, true);
+  if (c.batch > 0)
+    ::cuembed_embedding_forward_grouped(c.host_ptrs.data(), static_cast<const void* const*>(table_ptrs.data_ptr()),
+                                        static_cast<int>(num_tables), elem, static_cast<int>(width), Ptr(c.i), c.idx,
+                                        Ptr(c.o), c.off, Ptr(c.w), static_cast<int>(c.batch), static_cast<int>(c.hot), m,
+                                        MutPtr(out), static_cast<int>(row_loads),
+                                        static_cast<const int32_t*>(Ptr(c.order)), CurrentStream(out));
+  return out;
+}
+
+at::Tensor cuemb_embedding_quantized_grouped_op(const at::TensorList qtables, const at::Tensor& table_ptrs,
+                                                const at::Tensor& indices, const c10::optional<at::Tensor>& offsets,
+                                                const c10::optional<at::Tensor>& weights, const std::string& mode,
+                                                const at::ScalarType out_dtype, const int64_t row_loads,
+                                                const c10::optional<at::Tensor>& sample_order) {
+  const int m = GroupedMode(mode);
+  TORCH_CHECK(!qtables.empty(), "cuembed_pyt: a group needs at least one table");
+  const int out_code = OutCode(out_dtype, "out_dtype");
+  int64_t width = 0;
+  uintptr_t bits = 0;
+  for (const at::Tensor& t : qtables) {
+    width = QuantizedWidth(t);
+    bits |= reinterpret_cast<uintptr_t>(t.data_ptr());
+  }
+  TORCH_CHECK(width / ((width % 8 == 0 && bits % 8 == 0) ? 8 : 4) <= 1024,
+              "cuembed_pyt: qtables: a row of ", width, " codes needs more than 1024 lanes; align the tables to 8 bytes");
+  const at::DeviceGuard guard(qtables[0].device());
+  const GroupedCall c = CheckGroupedCall(qtables, table_ptrs, indices, offsets, weights, out_dtype, row_loads, sample_order);
+  const int64_t num_tables = static_cast<int64_t>(qtables.size());
+  at::Tensor out = at::empty({c.batch, num_tables, width}, qtables[0].options().dtype(out_dtype));
+  if (c.batch > 0)
+    ::cuembed_embedding_forward_quantized_grouped(
+        c.host_ptrs.data(), static_cast<const void* const*>(table_ptrs.data_ptr()), static_cast<int>(num_tables),
+        static_cast<int>(width), Ptr(c.i), c.idx, Ptr(c.o), c.off, Ptr(c.w), static_cast<int>(c.batch),
+        static_cast<int>(c.hot), m, MutPtr(out), out_code, static_cast<int>(row_loads),
+        static_cast<const int32_t*>(Ptr(c.order)), CurrentStream(out));
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(cuembed_pyt, m) {
@@ -1194,6 +1318,13 @@ TORCH_LIBRARY(cuembed_pyt, m) {
   m.def(
       "cuemb_embedding_quantized(Tensor qtable, Tensor indices, Tensor? offsets, Tensor? weights, str mode, ScalarType "
       "out_dtype, int row_loads, Tensor? sample_order, Tensor? row_loads_device) -> Tensor");
+  // a group of tables of one width and dtype pooled in one launch -> [batch, num_tables, width]; forward only
+  m.def(
+      "cuemb_embedding_grouped(Tensor[] tables, Tensor table_ptrs, Tensor idx, Tensor? offsets, Tensor? weights, str mode, "
+      "int row_loads=-1, Tensor? sample_order=None) -> Tensor");
+  m.def(
+      "cuemb_embedding_quantized_grouped(Tensor[] qtables, Tensor table_ptrs, Tensor idx, Tensor? offsets, Tensor? weights, "
+      "str mode, ScalarType out_dtype, int row_loads=-1, Tensor? sample_order=None) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(cuembed_pyt, Autograd, m) {
@@ -1231,4 +1362,6 @@ TORCH_LIBRARY_IMPL(cuembed_pyt, CUDA, m) {  // HIP tensors use the CUDA dispatch
   m.impl("quantize_rows", quantize_rows_op);
   m.impl("dequantize_rows", dequantize_rows_op);
   m.impl("cuemb_embedding_quantized", cuemb_embedding_quantized_op);
+  m.impl("cuemb_embedding_grouped", cuemb_embedding_grouped_op);
+  m.impl("cuemb_embedding_quantized_grouped", cuemb_embedding_quantized_grouped_op);
 }

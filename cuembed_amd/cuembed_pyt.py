@@ -81,6 +81,12 @@ def _define_python_ops():
     _lib.define("dequantize_rows(Tensor qtable, Tensor? ids, ScalarType dtype) -> Tensor")
     _lib.define("cuemb_embedding_quantized(Tensor qtable, Tensor indices, Tensor? offsets, Tensor? weights, str mode,"
                 " ScalarType out_dtype, int row_loads, Tensor? sample_order, Tensor? row_loads_device) -> Tensor")
+    _lib.define("cuemb_embedding_grouped(Tensor[] tables, Tensor table_ptrs, Tensor idx, Tensor? offsets, Tensor? weights,"
+                " str mode, int row_loads=-1, Tensor? sample_order=None) -> Tensor")
+    _lib.define("cuemb_embedding_quantized_grouped(Tensor[] qtables, Tensor table_ptrs, Tensor idx, Tensor? offsets,"
+                " Tensor? weights, str mode, ScalarType out_dtype, int row_loads=-1, Tensor? sample_order=None) -> Tensor")
+    _lib.impl("cuemb_embedding_grouped", _embedding_grouped_impl, "CUDA")
+    _lib.impl("cuemb_embedding_quantized_grouped", _embedding_quantized_grouped_impl, "CUDA")
     _lib.impl("quantize_rows", _quantize_rows_impl, "CUDA")
     _lib.impl("dequantize_rows", _dequantize_rows_impl, "CUDA")
     _lib.impl("cuemb_embedding_quantized", _embedding_quantized_impl, "CUDA")
@@ -124,6 +130,8 @@ def _define_python_ops():
 #                                             decay; the bias factor may stay on the device)
 #   quantize_rows, dequantize_rows,           8-bit row-wise quantized tables in torch's own fused layout (inference
 #   cuemb_embedding_quantized                 only): the quantizer, its inverse, and the lookup on a fused table
+#   cuemb_embedding_grouped,                  a group of tables of one width and dtype pooled in ONE launch into
+#   cuemb_embedding_quantized_grouped         [batch, tables, width] (forward only: no autograd formula)
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
 _INTS = (torch.int64, torch.int32)
@@ -313,6 +321,33 @@ def _embedding_quantized_impl(qtable, indices, offsets, weights, mode, out_dtype
         sample_order=sample_order, row_loads_device=row_loads_device)
 
 
+def _grouped_group(tables, table_ptrs):
+    from . import grouped as _g
+    return _g.TableGroup(tables, table_ptrs=table_ptrs)     # the caller's device pointers: nothing is copied here
+
+
+def _embedding_grouped_impl(tables, table_ptrs, idx, offsets, weights, mode, row_loads=-1, sample_order=None):
+    from . import grouped as _g
+    if offsets is None:
+        _require(idx.dim() == 3, "without offsets, idx must be [num_tables, batch, hotness]")
+    return _g.embedding_forward_grouped(
+        _grouped_group(tables, table_ptrs), idx.contiguous(), None if offsets is None else offsets.contiguous(),
+        None if weights is None else weights.contiguous(), num_hots=0 if offsets is not None else idx.shape[2], mode=mode,
+        row_loads={-1: None, 0: "default", 1: "streaming"}[int(row_loads)], sample_order=sample_order)
+
+
+def _embedding_quantized_grouped_impl(qtables, table_ptrs, idx, offsets, weights, mode, out_dtype, row_loads=-1,
+                                      sample_order=None):
+    from . import grouped as _g
+    if offsets is None:
+        _require(idx.dim() == 3, "without offsets, idx must be [num_tables, batch, hotness]")
+    return _g.embedding_forward_quantized_grouped(
+        _grouped_group(qtables, table_ptrs), idx.contiguous(), None if offsets is None else offsets.contiguous(),
+        None if weights is None else weights.contiguous(), num_hots=0 if offsets is not None else idx.shape[2], mode=mode,
+        out_dtype=out_dtype, row_loads={-1: None, 0: "default", 1: "streaming"}[int(row_loads)],
+        sample_order=sample_order)
+
+
 def _compress_impl(transpose_indices):
     _require(transpose_indices.is_cuda and transpose_indices.dtype in _INTS, "indices must be int tensors on the GPU")
     return _ops.compute_compressed_grad_indices(transpose_indices.contiguous())
@@ -418,6 +453,33 @@ def cuemb_embedding_quantized(qtable, idx, offsets=None, weights=None, mode="sum
         decision = _policy.row_loads_device(qtable, idx)
     return torch.ops.cuembed_pyt.cuemb_embedding_quantized(qtable, idx, offsets, weights, mode, out_dtype, -1, order,
                                                            decision)
+
+
+def _forward_only(tables, weights):
+    if torch.is_grad_enabled() and (any(t.requires_grad for t in tables) or
+                                    (weights is not None and weights.requires_grad)):
+        raise RuntimeError("cuembed_pyt: the grouped forward is forward only: a table (or the weights) requires grad; "
+                           "call it under torch.no_grad() or detach")
+
+
+def cuemb_embedding_grouped(group, idx, offsets=None, weights=None, mode="sum", row_loads=None, sample_order=None):
+    """cuembed_amd.embedding_forward_grouped as the torch op cuembed_pyt::cuemb_embedding_grouped: `group` is a
+    cuembed_amd.TableGroup (the tables and the device tensor of their base pointers, built once); CSR with `offsets`
+    (num_tables * batch + 1 entries) or fixed hotness with idx [num_tables, batch, hotness].  Returns [batch, num_tables,
+    width].  Forward only: the op has no autograd formula."""
+    _forward_only(group.tables, weights)
+    return torch.ops.cuembed_pyt.cuemb_embedding_grouped(list(group.tables), group.table_ptrs, idx, offsets, weights, mode,
+                                                         _ops._ROW_LOADS[row_loads], sample_order)
+
+
+def cuemb_embedding_quantized_grouped(group, idx, offsets=None, weights=None, mode="sum", out_dtype=torch.float16,
+                                      row_loads=None, sample_order=None):
+    """cuembed_amd.embedding_forward_quantized_grouped as the torch op cuembed_pyt::cuemb_embedding_quantized_grouped
+    (a TableGroup of fused 8-bit tables).  Inference only."""
+    _forward_only(group.tables, weights)
+    return torch.ops.cuembed_pyt.cuemb_embedding_quantized_grouped(list(group.tables), group.table_ptrs, idx, offsets,
+                                                                   weights, mode, out_dtype, _ops._ROW_LOADS[row_loads],
+                                                                   sample_order)
 
 
 def cuembed_forward(params, idx, offsets, weights, hints=None):
@@ -761,6 +823,25 @@ def _(qtable, indices, offsets=None, weights=None, mode="sum", out_dtype=torch.f
     else:
         shape = (indices.shape[0], width)
     return torch.empty(shape, device=qtable.device, dtype=out_dtype)
+
+
+def _grouped_fake_shape(tables, idx, offsets, width):
+    if offsets is not None:
+        return ((offsets.shape[0] - 1) // len(tables), len(tables), width)
+    return (idx.shape[1], len(tables), width)
+
+
+@torch.library.register_fake("cuembed_pyt::cuemb_embedding_grouped")
+def _(tables, table_ptrs, idx, offsets=None, weights=None, mode="sum", row_loads=-1, sample_order=None):
+    return torch.empty(_grouped_fake_shape(tables, idx, offsets, tables[0].shape[1]), device=tables[0].device,
+                       dtype=tables[0].dtype)
+
+
+@torch.library.register_fake("cuembed_pyt::cuemb_embedding_quantized_grouped")
+def _(qtables, table_ptrs, idx, offsets=None, weights=None, mode="sum", out_dtype=torch.float16, row_loads=-1,
+      sample_order=None):
+    return torch.empty(_grouped_fake_shape(qtables, idx, offsets, qtables[0].shape[1] - 8), device=qtables[0].device,
+                       dtype=out_dtype)
 
 
 @torch.library.register_fake("cuembed_pyt::cuembed_embedding_forward_hinted")

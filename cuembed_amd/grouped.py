@@ -1,0 +1,324 @@
+"""The forward on a GROUP of embedding tables in one launch (an extension: forward only, sum / mean only).
+
+A model with T tables calls embedding_forward T times and stacks the results; here the bags of T tables of one width
+and dtype lie one table after the other and one kernel pools them all:
+
+    bag g = t * B + b        table t, sample b (B samples per table; the table-major order of FBGEMM's table-batched op)
+    CSR                      one indices[nnz], one offsets[T * B + 1], optional weights[nnz]
+    fixed hotness            indices [T, B, H] (offsets=None, num_hots=H), the same H for every table
+    out                      [B, T, W], contiguous -- torch.stack(per_table_results, dim=1), with the same bits
+
+    TableGroup(tables)                          the tables + their base pointers on the host and (built once) on the device
+    embedding_forward_grouped(group, ...)       embedding_forward on a group of fp32 / fp16 / bf16 tables
+    embedding_forward_quantized_grouped(...)    embedding_forward_quantized on a group of fused 8-bit tables
+    grouped_forward_launch_shape(...)           the launch shape (host arithmetic)
+    EmbeddingBagGroup, QuantizedEmbeddingBagGroup   a group with a mode: bag(idx, offsets, weights)
+
+Every function validates its arguments and raises before any launch; the kernels run on torch's current stream
+(cuembed::EmbeddingForwardGrouped / EmbeddingForwardQuantizedGrouped through the C ABI).  No host read-back, no copy per
+call, no allocation inside the library: with `out=` given a call can be captured into a HIP graph.  Nothing here is
+differentiable: a table that requires grad while grad mode is on is an error (a grouped backward does not exist yet).
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+from .ops import _ELEM, _INDEX, _MODES, _ROW_LOADS, MEAN, SUM, _check_alignment, _check_dev, _index_code, _ptr, _stream
+from .quantized import TRAILER_BYTES, _check_qtable, _out_code, quantize_rows
+
+INT_MAX = 2 ** 31 - 1
+_SOURCES = ("lds_staged", "wave_shuffle", "global")
+
+
+class TableGroup:
+    """T >= 1 tables of one device, dtype and width (their row counts may differ): all 2-D float32 / float16 / bfloat16
+    [rows_t, W], or all fused 8-bit tables, uint8 [rows_t, W + 8].  Holds the tensors (so that the pointers stay
+    valid), their base pointers on the host, and `table_ptrs`, ONE int64 device tensor of the same pointers that the
+    kernel reads -- built here, once: no host-to-device copy per call.  A tensor whose storage is replaced later
+    (`table.data = ...`) needs a new TableGroup; updating rows in place does not."""
+
+    def __init__(self, tables, table_ptrs=None):
+        tables = list(tables)
+        if not tables:
+            raise ValueError("a TableGroup needs at least one table")
+        for t in tables:
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("every table must be a torch.Tensor")
+        first = tables[0]
+        self.quantized = first.dtype == torch.uint8
+        if self.quantized:
+            self.width = _check_qtable(first)
+        else:
+            if first.dtype not in _ELEM:
+                raise TypeError("tables must be float32, float16 or bfloat16 (or fused uint8 rows), got %s" % first.dtype)
+            if first.dim() != 2:
+                raise ValueError("every table must be [rows, width]")
+            self.width = first.shape[1]
+        for k, t in enumerate(tables):
+            if t.dtype != first.dtype:
+                raise TypeError("table %d is %s, table 0 is %s: one dtype per group" % (k, t.dtype, first.dtype))
+            if t.dim() != 2 or t.shape[1] != first.shape[1]:
+                raise ValueError("table %d is %s, table 0 has rows of %d: one width per group"
+                                 % (k, tuple(t.shape), first.shape[1]))
+            if t.device != first.device:
+                raise ValueError("table %d is on %s, table 0 on %s: one device per group" % (k, t.device, first.device))
+            if not t.is_contiguous():
+                raise ValueError("table %d must be contiguous" % k)
+        self.tables = tuple(tables)
+        self.device = first.device
+        self.dtype = first.dtype
+        self.host_ptrs = tuple(int(t.data_ptr()) for t in tables)
+        self._host_array = (ctypes.c_void_p * len(tables))(*self.host_ptrs)
+        if table_ptrs is None:   # (a CPU group can be built and inspected; calls need the GPU)
+            table_ptrs = torch.tensor(self.host_ptrs, dtype=torch.int64, device=self.device)
+        elif (not isinstance(table_ptrs, torch.Tensor) or table_ptrs.dtype != torch.int64 or
+              table_ptrs.numel() != len(tables) or table_ptrs.device != self.device or not table_ptrs.is_contiguous()):
+            # (an earlier group's tensor for the same tables; its values stay on the device, unread)
+            raise ValueError("table_ptrs must be the contiguous int64 tensor of the tables' data pointers on their device")
+        self.table_ptrs = table_ptrs
+
+    def __len__(self):
+        return len(self.tables)
+
+    @property
+    def num_tables(self):
+        return len(self.tables)
+
+    def lane_bytes(self, out_ptr=0):
+        """Bytes of a row one lane moves (16, 8 or 4; codes per lane for fused tables before the 16-code widening): the
+        least aligned table -- and `out_ptr` -- decide for the whole group.  ValueError where the library would abort."""
+        ptr = 0
+        for p in self.host_ptrs:
+            ptr |= p
+        if self.quantized:
+            return _check_alignment("tables", ptr, 1, self.width, codes=True)
+        return _check_alignment("tables", ptr, self.tables[0].element_size(), self.width, others=(("out", out_ptr),))
+
+
+def _as_group(group):
+    return group if isinstance(group, TableGroup) else TableGroup(group)
+
+
+def _check_no_grad(group, weights):
+    if torch.is_grad_enabled():
+        for k, t in enumerate(group.tables):
+            if t.requires_grad:
+                raise RuntimeError("table %d requires grad: the grouped forward is forward only (call it under "
+                                   "torch.no_grad() or detach the tables)" % k)
+        if weights is not None and weights.requires_grad:
+            raise RuntimeError("weights require grad: the grouped forward is forward only")
+
+
+def _grouped_call(group, indices, offsets, weights, batch_size, num_hots, mode, row_loads, sample_order, out,
+                  row_loads_device, weight_dtype, out_dtype):
+    """Validates one grouped call (everything that does not need the GPU first) and returns
+    (B, mode code, index code, offset code, out)."""
+    if mode not in ("sum", "mean", SUM, MEAN):
+        raise ValueError("mode must be 'sum' or 'mean': the grouped forward has no concat and no max")
+    if row_loads not in _ROW_LOADS:
+        raise ValueError("row_loads: None, 'default' or 'streaming'")
+    if row_loads_device is not None:
+        raise ValueError("row_loads_device is not taken by the grouped forward: the decision is per table and nothing "
+                         "carries one per table yet; pass row_loads= for the whole group")
+    m = _MODES[mode]
+    T = group.num_tables
+    if not isinstance(indices, torch.Tensor):
+        raise TypeError("indices must be a torch.Tensor")
+    it = _index_code("indices", indices)
+    _check_no_grad(group, weights)
+    if not ((offsets is not None and num_hots == 0) or (offsets is None and num_hots > 0)):
+        raise ValueError("either CSR (offsets given, num_hots == 0) or fixed hotness (offsets None, num_hots > 0)")
+    ot = 0
+    if offsets is not None:
+        if not isinstance(offsets, torch.Tensor):
+            raise TypeError("offsets must be a torch.Tensor")
+        ot = _index_code("offsets", offsets)
+        if batch_size is None:
+            if (offsets.numel() - 1) % T or offsets.numel() < 1:
+                raise ValueError("offsets must hold num_tables * batch_size + 1 entries: %d - 1 is not a multiple of %d "
+                                 "tables" % (offsets.numel(), T))
+            batch_size = (offsets.numel() - 1) // T
+        if batch_size < 0 or offsets.numel() != T * batch_size + 1:
+            raise ValueError("offsets must hold num_tables * batch_size + 1 = %d entries, got %d"
+                             % (T * batch_size + 1, offsets.numel()))
+    else:
+        if batch_size is None:
+            if indices.numel() % (T * num_hots):
+                raise ValueError("indices.numel() is not a multiple of num_tables * num_hots")
+            batch_size = indices.numel() // (T * num_hots)
+        if batch_size < 0 or indices.numel() != T * batch_size * num_hots:
+            raise ValueError("indices must hold num_tables * batch_size * num_hots entries")
+    if T * batch_size > INT_MAX:
+        raise ValueError("num_tables * batch_size = %d does not fit a 32-bit int" % (T * batch_size))
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor):
+            raise TypeError("weights must be a torch.Tensor")
+        if weights.dtype != weight_dtype:
+            raise TypeError("weights must be %s, got %s" % (weight_dtype, weights.dtype))
+        if weights.numel() < indices.numel():
+            raise ValueError("weights must have one entry per index")
+    if sample_order is not None and offsets is None:
+        raise ValueError("sample_order is a hint for CSR batches (bags of different lengths)")
+    # ---- the call is in order: now the devices
+    dev = group.device
+    _check_dev("tables[0]", group.tables[0])
+    _check_dev("indices", indices, dev)
+    if offsets is not None:
+        _check_dev("offsets", offsets, dev)
+    if weights is not None:
+        _check_dev("weights", weights, dev)
+    if sample_order is not None:
+        _check_dev("sample_order", sample_order, dev)
+        if sample_order.dtype != torch.int32 or sample_order.numel() != T * batch_size:
+            raise ValueError("sample_order must be a contiguous int32 permutation of range(num_tables * batch_size)")
+    if out is None:
+        out = torch.empty((batch_size, T, group.width), dtype=out_dtype, device=dev)
+    else:
+        _check_dev("out", out, dev)
+        if out.dtype != out_dtype or out.numel() != batch_size * T * group.width:
+            raise ValueError("out must be a contiguous %s tensor [batch_size, num_tables, width]" % out_dtype)
+    return batch_size, m, it, ot, out
+
+
+def embedding_forward_grouped(group, indices, offsets=None, weights=None, batch_size=None, num_hots=0, mode="sum",
+                              row_loads=None, sample_order=None, out=None, row_loads_device=None):
+    """out[b, t] = combine_j weights[.] * group.tables[t][indices[.]] over the lookups of bag t * batch_size + b, for all
+    tables of a TableGroup (or a list of tables: a TableGroup is then built, with its one host-to-device copy) in ONE
+    launch.  Returns [batch_size, num_tables, width] of the tables' dtype -- torch.stack([embedding_forward(table_t,
+    ...)], dim=1), bit for bit.
+
+    CSR: offsets[num_tables * batch_size + 1] over one indices[nnz]; fixed hotness: offsets=None, num_hots=H, indices
+    [num_tables, batch_size, H].  The ids of table t's bags are rows of table t.  mode "sum" | "mean"; weights (optional)
+    in the tables' dtype; fp32 accumulation in lookup order; empty bags give zeros.  row_loads ("default" | "streaming" |
+    None, one value for the group) and sample_order (CSR only: an int32 permutation of the num_tables * batch_size bags,
+    bag_order_by_length(offsets)) are scheduling hints that change no bit.  row_loads_device must stay None."""
+    group = _as_group(group)
+    if group.quantized:
+        raise TypeError("a group of fused 8-bit tables is looked up with embedding_forward_quantized_grouped")
+    B, m, it, ot, out = _grouped_call(group, indices, offsets, weights, batch_size, num_hots, mode, row_loads,
+                                      sample_order, out, row_loads_device, group.dtype, group.dtype)
+    group.lane_bytes(out.data_ptr())
+    if B > 0:
+        with torch.cuda.device(group.device):   # the launch must happen on the tensors' device
+            _lib.lib().cuembed_embedding_forward_grouped(
+                group._host_array, _ptr(group.table_ptrs), group.num_tables, _ELEM[group.dtype], group.width,
+                _ptr(indices), it, _ptr(offsets), ot, _ptr(weights), B, num_hots, m, _ptr(out), _ROW_LOADS[row_loads],
+                _ptr(sample_order), _stream(out))
+    return out
+
+
+def embedding_forward_quantized_grouped(group, indices, offsets=None, weights=None, batch_size=None, num_hots=0,
+                                        mode="sum", out_dtype=torch.float16, row_loads=None, sample_order=None, out=None,
+                                        row_loads_device=None):
+    """embedding_forward_grouped on a TableGroup of fused 8-bit tables (uint8 [rows_t, W + 8], torch's
+    embedding_bag_byte_prepack layout): returns [batch_size, num_tables, W] of out_dtype (float16 or float32) --
+    torch.stack([embedding_forward_quantized(qtable_t, ...)], dim=1), bit for bit.  `weights` have the output's dtype."""
+    group = _as_group(group)
+    if not group.quantized:
+        raise TypeError("embedding_forward_quantized_grouped takes fused uint8 tables [rows, width + 8]")
+    oc = _out_code("out_dtype", out_dtype)
+    B, m, it, ot, out = _grouped_call(group, indices, offsets, weights, batch_size, num_hots, mode, row_loads,
+                                      sample_order, out, row_loads_device, out_dtype, out_dtype)
+    if out.data_ptr() % 16 != 0:
+        raise ValueError("out must be 16-byte aligned")
+    group.lane_bytes()
+    if B > 0:
+        with torch.cuda.device(group.device):
+            _lib.lib().cuembed_embedding_forward_quantized_grouped(
+                group._host_array, _ptr(group.table_ptrs), group.num_tables, group.width, _ptr(indices), it,
+                _ptr(offsets), ot, _ptr(weights), B, num_hots, m, _ptr(out), oc, _ROW_LOADS[row_loads],
+                _ptr(sample_order), _stream(out))
+    return out
+
+
+def grouped_forward_launch_shape(elem_dtype, index_dtype, embed_width, num_tables, batch_size, num_hots, is_csr=False,
+                                 is_weighted=False, quantized=False, compute_units=256, xcds=8):
+    """Launch shape of a grouped forward for aligned buffers (pure host arithmetic; compute_units / xcds describe the
+    device for quantized groups, whose plan depends on it: 0 = ask the current device).  elem_dtype: the tables' dtype,
+    or with quantized=True the output's.  grid = ceil(num_tables * batch_size / samples_per_block); index_source is
+    "lds_staged", "wave_shuffle" or "global"."""
+    if index_dtype not in _INDEX:
+        raise TypeError("index dtype must be int32 or int64, got %s" % index_dtype)
+    if quantized:
+        ec = _out_code("elem_dtype", elem_dtype)
+    else:
+        if elem_dtype not in _ELEM:
+            raise TypeError("elem_dtype must be float32, float16 or bfloat16, got %s" % elem_dtype)
+        ec = _ELEM[elem_dtype]
+    if num_tables < 1 or batch_size < 0 or num_tables * batch_size > INT_MAX:
+        raise ValueError("num_tables >= 1, batch_size >= 0 and num_tables * batch_size must fit a 32-bit int")
+    if embed_width <= 0 or (embed_width * (1 if quantized else elem_dtype.itemsize)) % 4:
+        raise ValueError("the row size must be a multiple of 4 bytes")
+    out = (ctypes.c_int * 7)()
+    _lib.lib().cuembed_grouped_forward_launch_shape(int(bool(quantized)), ec, _INDEX[index_dtype], int(embed_width),
+                                                    int(num_tables), int(batch_size), int(num_hots), int(is_csr),
+                                                    int(is_weighted), int(compute_units), int(xcds), out)
+    return dict(elems_per_lane=out[0], lanes_per_row=out[1], samples_per_block=out[2], grid=out[3], lds_bytes=out[4],
+                staged=out[5] == 1, index_source=_SOURCES[out[6]])
+
+
+class EmbeddingBagGroup:
+    """A TableGroup with a mode and the call shape of nn.EmbeddingBag: bags(idx, offsets, weights) with CSR offsets
+    (num_tables * batch + 1 entries), or bags(idx) with idx [num_tables, batch, hotness].  Returns [batch, num_tables,
+    width].  Forward only."""
+
+    def __init__(self, tables, mode="sum"):
+        if mode not in ("sum", "mean"):
+            raise ValueError("mode must be 'sum' or 'mean'")
+        self.group = _as_group(tables)
+        if self.group.quantized:
+            raise TypeError("fused 8-bit tables go into a QuantizedEmbeddingBagGroup")
+        self.mode = mode
+
+    @property
+    def num_tables(self):
+        return self.group.num_tables
+
+    @property
+    def embedding_dim(self):
+        return self.group.width
+
+    def __call__(self, idx, offsets=None, weights=None, sample_order=None, out=None):
+        hot = 0
+        if offsets is None:
+            if idx.dim() != 3:
+                raise ValueError("without offsets, idx must be [num_tables, batch, hotness]")
+            hot = idx.shape[2]
+        return embedding_forward_grouped(self.group, idx, offsets, weights, num_hots=hot, mode=self.mode,
+                                         sample_order=sample_order, out=out)
+
+
+class QuantizedEmbeddingBagGroup:
+    """EmbeddingBagGroup on fused 8-bit tables; from_float quantizes fp32 / fp16 / bf16 tables on the device."""
+
+    def __init__(self, qtables, mode="sum", out_dtype=torch.float16):
+        if mode not in ("sum", "mean"):
+            raise ValueError("mode must be 'sum' or 'mean'")
+        _out_code("out_dtype", out_dtype)
+        self.group = _as_group(qtables)
+        if not self.group.quantized:
+            raise TypeError("QuantizedEmbeddingBagGroup takes fused uint8 tables; see from_float")
+        self.mode = mode
+        self.out_dtype = out_dtype
+
+    @classmethod
+    def from_float(cls, tables, mode="sum", out_dtype=torch.float16):
+        return cls([quantize_rows(t.detach()) for t in tables], mode=mode, out_dtype=out_dtype)
+
+    @property
+    def num_tables(self):
+        return self.group.num_tables
+
+    @property
+    def embedding_dim(self):
+        return self.group.width
+
+    def __call__(self, idx, offsets=None, weights=None, sample_order=None, out=None):
+        hot = 0
+        if offsets is None:
+            if idx.dim() != 3:
+                raise ValueError("without offsets, idx must be [num_tables, batch, hotness]")
+            hot = idx.shape[2]
+        return embedding_forward_quantized_grouped(self.group, idx, offsets, weights, num_hots=hot, mode=self.mode,
+                                                   out_dtype=self.out_dtype, sample_order=sample_order, out=out)

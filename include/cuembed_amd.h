@@ -608,6 +608,41 @@ void cuembed_embedding_forward_quantized(const void* qtable, int embed_width, co
  * indices are staged in LDS.  compute_units > 0 describes the device (with xcds); <= 0: the current device. */
 void cuembed_quantized_forward_launch_shape(int index_type, int out_type, int embed_width, int batch_size, int num_hots,
                                             int is_csr, int is_weighted, int compute_units, int xcds, int* out);
+/* ---- a GROUP of tables pooled in one launch (extension; forward only, sum / mean only) -----
+ * num_tables >= 1 tables on one device, of one element type (or all fused 8-bit) and one embed_width; their row counts
+ * may differ.  Bag g = t * batch_per_table + b belongs to table t and sample b (table-major).  CSR: one indices[nnz],
+ * one offsets[num_tables * batch_per_table + 1], optional weights[nnz]; fixed hotness (offsets == NULL): indices
+ * [num_tables, batch_per_table, num_hots].  ret is [batch_per_table, num_tables, embed_width], contiguous: bag (t, b)
+ * at ret + (b * num_tables + t) * embed_width -- the per-table results stacked on dimension 1, with the bits of
+ * num_tables single-table calls.  num_tables * batch_per_table <= INT_MAX.
+ * The caller builds the table base pointers twice, once: tables_host (host memory; read by the library for the access
+ * width -- the least aligned table decides for the group) and tables_device (device memory; read by the kernel).  The
+ * library never reads device memory on the host, copies nothing per call and allocates nothing.
+ * row_load_policy (-1 = the process-wide default, 0 default, 1 streaming; one value for the group) and sample_order (CSR
+ * only: a permutation of the num_tables * batch_per_table bags, e.g. cuembed_bag_order_by_length on the combined
+ * offsets) are scheduling hints and change no bit.  Misuse aborts like everywhere else. */
+/* cuembed::EmbeddingForwardGrouped: tables, weights and ret of elem_type; fp32 accumulation in lookup order. */
+void cuembed_embedding_forward_grouped(const void* const* tables_host, const void* const* tables_device, int num_tables,
+                                       int elem_type, int embed_width, const void* indices, int index_type,
+                                       const void* offsets, int offset_type, const void* weights, int batch_per_table,
+                                       int num_hots, int mode, void* ret, int row_load_policy,
+                                       const int32_t* sample_order, cuembed_stream_t stream);
+/* cuembed::EmbeddingForwardQuantizedGrouped: fused 8-bit tables (at least 4-byte aligned); weights and ret of out_type
+ * (CUEMBED_F32 or CUEMBED_F16), ret 16-byte aligned. */
+void cuembed_embedding_forward_quantized_grouped(const void* const* tables_host, const void* const* tables_device,
+                                                 int num_tables, int embed_width, const void* indices, int index_type,
+                                                 const void* offsets, int offset_type, const void* weights,
+                                                 int batch_per_table, int num_hots, int mode, void* ret, int out_type,
+                                                 int row_load_policy, const int32_t* sample_order,
+                                                 cuembed_stream_t stream);
+/* Launch shape of a grouped forward for aligned buffers (no launch; host arithmetic only when compute_units > 0 or
+ * quantized == 0): quantized != 0: fused tables, elem_type = the output's type.  out[0] = elements (codes) per lane,
+ * out[1] = lanes per row, out[2] = bags per workgroup, out[3] = grid size = ceil(num_tables * batch_per_table / out[2]),
+ * out[4] = dynamic LDS bytes, out[5] = 1 when the indices are staged in LDS, out[6] = where the lanes find their
+ * indices: 0 = staged in LDS, 1 = cross-lane reads, 2 = global loads. */
+void cuembed_grouped_forward_launch_shape(int quantized, int elem_type, int index_type, int embed_width, int num_tables,
+                                          int batch_per_table, int num_hots, int is_csr, int is_weighted,
+                                          int compute_units, int xcds, int* out);
 /* hipPeekAtLastError() as an int (0 = hipSuccess); launches themselves never
  * report errors, exactly like the reference. */
 int cuembed_peek_last_error(void);
