@@ -160,6 +160,10 @@ def _declare(L):
                                                               _I, _I, _VP, _VP]
     L.cuembed_grouped_forward_launch_shape.restype = None
     L.cuembed_grouped_forward_launch_shape.argtypes = [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]
+    L.cuembed_grouped_backward_keys.restype = None
+    L.cuembed_grouped_backward_keys.argtypes = [_VP, _I, _VP, _I, _VP, _I, _I, _I, _L, _VP, _VP, _I, _VP]
+    L.cuembed_grouped_table_cuts.restype = None
+    L.cuembed_grouped_table_cuts.argtypes = [_VP, _I, _L, _L, _VP, _I, _VP, _VP, _I, _VP, _VP]
     L.cuembed_peek_last_error.restype = _I
     L.cuembed_peek_last_error.argtypes = []
     L.cuembed_version.restype = ctypes.c_char_p

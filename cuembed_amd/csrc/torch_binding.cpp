@@ -1260,6 +1260,73 @@ at::Tensor cuemb_embedding_quantized_grouped_op(const at::TensorList qtables, co
   return out;
 }
 
+// ---- the backward of a group: keys + sample ids in front of the single-table pipeline, table cuts behind it ----------
+// idx / offsets as in cuemb_embedding_grouped; row_base = the int64 device tensor of num_tables + 1 exclusive prefix sums
+// of the tables' row counts (cuembed_amd.TableGroup.row_base_device).  narrow: int32 results (the caller knows that the
+// group has fewer than 2^31 rows), else int64.  Returns (keys, sample_ids), nnz entries each.
+std::tuple<at::Tensor, at::Tensor> cuembed_grouped_backward_keys_op(const at::Tensor& indices,
+                                                                    const c10::optional<at::Tensor>& offsets,
+                                                                    const at::Tensor& row_base, const int64_t num_tables,
+                                                                    const int64_t batch, const int64_t num_hots,
+                                                                    const bool narrow) {
+  CheckGpu(indices, "indices");
+  CheckGpu(row_base, "row_base");
+  const int idx = IndexCode(indices, "indices");
+  TORCH_CHECK(num_tables >= 1 && batch >= 0 && num_tables * batch <= INT32_MAX,
+              "cuembed_pyt: num_tables >= 1, batch >= 0 and num_tables * batch must fit a 32-bit int");
+  TORCH_CHECK(row_base.scalar_type() == at::kLong && row_base.is_contiguous() && row_base.numel() == num_tables + 1 &&
+                  row_base.device() == indices.device(),
+              "cuembed_pyt: row_base must be the contiguous int64 tensor of num_tables + 1 row offsets on the indices' device");
+  const at::DeviceGuard guard(indices.device());
+  const at::Tensor i = indices.contiguous();
+  const int64_t nnz = i.numel();
+  TORCH_CHECK(nnz <= INT32_MAX, "cuembed_pyt: nnz must fit an int");
+  at::Tensor o;
+  int off = CUEMBED_I32;
+  if (offsets.has_value() && offsets->defined()) {
+    CheckGpu(*offsets, "offsets");
+    off = IndexCode(*offsets, "offsets");
+    o = offsets->contiguous();
+    TORCH_CHECK(num_hots == 0 && o.numel() == num_tables * batch + 1,
+                "cuembed_pyt: CSR: num_hots = 0 and offsets of num_tables * batch + 1 entries");
+  } else {
+    TORCH_CHECK(num_hots > 0 && nnz == num_tables * batch * num_hots,
+                "cuembed_pyt: fixed hotness: num_hots > 0 and num_tables * batch * num_hots indices");
+  }
+  const at::TensorOptions options = i.options().dtype(narrow ? at::kInt : at::kLong);
+  at::Tensor keys = at::empty({nnz}, options), sample_ids = at::empty({nnz}, options);
+  if (nnz > 0)
+    ::cuembed_grouped_backward_keys(Ptr(i), idx, Ptr(o), off, static_cast<const int64_t*>(row_base.data_ptr()),
+                                    static_cast<int>(num_tables), static_cast<int>(batch), static_cast<int>(num_hots), nnz,
+                                    MutPtr(keys), MutPtr(sample_ids), narrow ? CUEMBED_I32 : CUEMBED_I64, CurrentStream(i));
+  return std::make_tuple(keys, sample_ids);
+}
+
+// ids: the ascending global ids of a group's compressed gradient; count_word: one device word, the entry count (int32 /
+// int64) or, with last_id = true, the last id (ids' dtype; count = last id + 1).  Returns the int64 cuts[num_tables + 1].
+at::Tensor cuembed_grouped_table_cuts_op(const at::Tensor& ids, const at::Tensor& count_word, const at::Tensor& row_base,
+                                         const bool last_id) {
+  CheckGpu(ids, "ids");
+  CheckGpu(count_word, "count_word");
+  CheckGpu(row_base, "row_base");
+  const int idx = IndexCode(ids, "ids");
+  const int word = IndexCode(count_word, "count_word");
+  TORCH_CHECK(count_word.numel() == 1 && count_word.device() == ids.device(),
+              "cuembed_pyt: count_word must be one word on the ids' device");
+  TORCH_CHECK(!last_id || count_word.scalar_type() == ids.scalar_type(), "cuembed_pyt: a last id has the ids' dtype");
+  TORCH_CHECK(row_base.scalar_type() == at::kLong && row_base.is_contiguous() && row_base.dim() == 1 &&
+                  row_base.numel() >= 2 && row_base.device() == ids.device(),
+              "cuembed_pyt: row_base must be the contiguous int64 tensor of num_tables + 1 row offsets on the ids' device");
+  const at::DeviceGuard guard(ids.device());
+  const at::Tensor i = ids.contiguous();
+  at::Tensor cuts = at::empty({row_base.numel()}, row_base.options());
+  ::cuembed_grouped_table_cuts(Ptr(i), idx, i.numel(), 0, last_id ? nullptr : Ptr(count_word), word == CUEMBED_I64 ? 1 : 0,
+                               last_id ? Ptr(count_word) : nullptr, static_cast<const int64_t*>(row_base.data_ptr()),
+                               static_cast<int>(row_base.numel() - 1), static_cast<int64_t*>(cuts.data_ptr()),
+                               CurrentStream(i));
+  return cuts;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(cuembed_pyt, m) {
@@ -1325,6 +1392,11 @@ TORCH_LIBRARY(cuembed_pyt, m) {
   m.def(
       "cuemb_embedding_quantized_grouped(Tensor[] qtables, Tensor table_ptrs, Tensor idx, Tensor? offsets, Tensor? weights, "
       "str mode, ScalarType out_dtype, int row_loads=-1, Tensor? sample_order=None) -> Tensor");
+  // the backward of a group: the keys in front of the single-table pipeline, the table boundaries behind it
+  m.def(
+      "cuembed_grouped_backward_keys(Tensor idx, Tensor? offsets, Tensor row_base, int num_tables, int batch, int "
+      "num_hots, bool narrow) -> (Tensor, Tensor)");
+  m.def("cuembed_grouped_table_cuts(Tensor ids, Tensor count_word, Tensor row_base, bool last_id=False) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(cuembed_pyt, Autograd, m) {
@@ -1364,4 +1436,6 @@ TORCH_LIBRARY_IMPL(cuembed_pyt, CUDA, m) {  // HIP tensors use the CUDA dispatch
   m.impl("cuemb_embedding_quantized", cuemb_embedding_quantized_op);
   m.impl("cuemb_embedding_grouped", cuemb_embedding_grouped_op);
   m.impl("cuemb_embedding_quantized_grouped", cuemb_embedding_quantized_grouped_op);
+  m.impl("cuembed_grouped_backward_keys", cuembed_grouped_backward_keys_op);
+  m.impl("cuembed_grouped_table_cuts", cuembed_grouped_table_cuts_op);
 }

@@ -85,6 +85,11 @@ def _define_python_ops():
                 " str mode, int row_loads=-1, Tensor? sample_order=None) -> Tensor")
     _lib.define("cuemb_embedding_quantized_grouped(Tensor[] qtables, Tensor table_ptrs, Tensor idx, Tensor? offsets,"
                 " Tensor? weights, str mode, ScalarType out_dtype, int row_loads=-1, Tensor? sample_order=None) -> Tensor")
+    _lib.define("cuembed_grouped_backward_keys(Tensor idx, Tensor? offsets, Tensor row_base, int num_tables, int batch,"
+                " int num_hots, bool narrow) -> (Tensor, Tensor)")
+    _lib.define("cuembed_grouped_table_cuts(Tensor ids, Tensor count_word, Tensor row_base, bool last_id=False) -> Tensor")
+    _lib.impl("cuembed_grouped_backward_keys", _grouped_backward_keys_impl, "CUDA")
+    _lib.impl("cuembed_grouped_table_cuts", _grouped_table_cuts_impl, "CUDA")
     _lib.impl("cuemb_embedding_grouped", _embedding_grouped_impl, "CUDA")
     _lib.impl("cuemb_embedding_quantized_grouped", _embedding_quantized_grouped_impl, "CUDA")
     _lib.impl("quantize_rows", _quantize_rows_impl, "CUDA")
@@ -132,6 +137,10 @@ def _define_python_ops():
 #   cuemb_embedding_quantized                 only): the quantizer, its inverse, and the lookup on a fused table
 #   cuemb_embedding_grouped,                  a group of tables of one width and dtype pooled in ONE launch into
 #   cuemb_embedding_quantized_grouped         [batch, tables, width] (forward only: no autograd formula)
+#   cuembed_grouped_backward_keys,            the backward of a group through ONE sort and ONE scatter-add: global row
+#   cuembed_grouped_table_cuts                keys + output-row sample ids in front of the single-table pipeline, the
+#                                             table boundaries of the compressed gradient behind it
+#                                             (cuemb_embedding_grouped_trainable is the autograd surface over them)
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
 _INTS = (torch.int64, torch.int32)
@@ -348,6 +357,40 @@ def _embedding_quantized_grouped_impl(qtables, table_ptrs, idx, offsets, weights
         sample_order=sample_order)
 
 
+def _grouped_backward_keys_impl(idx, offsets, row_base, num_tables, batch, num_hots, narrow):
+    _require(idx.is_cuda and row_base.is_cuda and idx.dtype in _INTS, "idx must be an int tensor on the GPU")
+    _require(row_base.dtype == torch.int64 and row_base.numel() == num_tables + 1 and row_base.is_contiguous(),
+             "row_base must be the contiguous int64 tensor of num_tables + 1 row offsets")
+    _require(num_tables >= 1 and batch >= 0 and num_tables * batch < 2 ** 31, "num_tables * batch must fit a 32-bit int")
+    idx = idx.contiguous()
+    nnz = idx.numel()
+    if offsets is not None:
+        _require(offsets.is_cuda and offsets.dtype in _INTS and num_hots == 0 and offsets.numel() == num_tables * batch + 1,
+                 "CSR: num_hots = 0 and offsets of num_tables * batch + 1 entries")
+        offsets = offsets.contiguous()
+    else:
+        _require(num_hots > 0 and nnz == num_tables * batch * num_hots,
+                 "fixed hotness: num_hots > 0 and num_tables * batch * num_hots indices")
+    kd = torch.int32 if narrow else torch.int64
+    keys = torch.empty((nnz,), dtype=kd, device=idx.device)
+    sample_ids = torch.empty((nnz,), dtype=kd, device=idx.device)
+    if nnz > 0:
+        from . import _lib as _clib
+        with torch.cuda.device(idx.device):
+            _clib.lib().cuembed_grouped_backward_keys(
+                _ops._ptr(idx), _ops._INDEX[idx.dtype], _ops._ptr(offsets),
+                0 if offsets is None else _ops._INDEX[offsets.dtype], _ops._ptr(row_base), int(num_tables), int(batch),
+                int(num_hots), nnz, _ops._ptr(keys), _ops._ptr(sample_ids), _ops._INDEX[kd], _ops._stream(idx))
+    return keys, sample_ids
+
+
+def _grouped_table_cuts_impl(ids, count_word, row_base, last_id=False):
+    from . import grouped_backward as _gb
+    _require(ids.is_cuda and count_word.is_cuda and row_base.is_cuda, "tensors must be on the GPU")
+    kw = dict(last_id=count_word) if last_id else dict(count=count_word)
+    return _gb.grouped_table_cuts(ids.contiguous(), row_base, **kw)
+
+
 def _compress_impl(transpose_indices):
     _require(transpose_indices.is_cuda and transpose_indices.dtype in _INTS, "indices must be int tensors on the GPU")
     return _ops.compute_compressed_grad_indices(transpose_indices.contiguous())
@@ -480,6 +523,164 @@ def cuemb_embedding_quantized_grouped(group, idx, offsets=None, weights=None, mo
     return torch.ops.cuembed_pyt.cuemb_embedding_quantized_grouped(list(group.tables), group.table_ptrs, idx, offsets,
                                                                    weights, mode, out_dtype, _ops._ROW_LOADS[row_loads],
                                                                    sample_order)
+
+
+def _grouped_batch(num_tables, idx, offsets):
+    """(batch, hotness) of a grouped call: CSR offsets of num_tables * batch + 1 entries, or idx [num_tables, batch, hot]."""
+    if offsets is not None:
+        if offsets.numel() < 1 or (offsets.numel() - 1) % num_tables:
+            raise ValueError("offsets must hold num_tables * batch + 1 entries")
+        return (offsets.numel() - 1) // num_tables, 0
+    if idx.dim() != 3 or idx.shape[0] != num_tables or idx.shape[2] < 1:
+        raise ValueError("without offsets, idx must be [num_tables, batch, hotness]")
+    return idx.shape[1], idx.shape[2]
+
+
+def _empty_sparse(rows, width, dtype, device):
+    return torch.sparse_coo_tensor(torch.empty((1, 0), dtype=torch.int64, device=device),
+                                   torch.empty((0, width), dtype=dtype, device=device), size=(rows, width),
+                                   is_coalesced=True)
+
+
+class _CuEmbGrouped(torch.autograd.Function):
+    """cuemb_embedding_grouped_trainable: the grouped forward, and the backward of all tables through one sort and one
+    scatter-add.  `params` is (group.flat,) for a one-storage group, else the group's tables."""
+
+    @staticmethod
+    def forward(ctx, group, idx, offsets, weights, sparse_grad, row_loads, sample_order, *params):
+        ctx.save_for_backward(idx, offsets, weights)
+        ctx.group = group
+        ctx.sparse_grad = sparse_grad
+        tables = [t.detach() for t in group.tables]
+        return torch.ops.cuembed_pyt.cuemb_embedding_grouped(tables, group.table_ptrs, idx, offsets, weights, "sum",
+                                                             _ops._ROW_LOADS[row_loads], sample_order)
+
+    @staticmethod
+    def backward(ctx, out_grad):
+        idx, offsets, weights = ctx.saved_tensors
+        group, kind = ctx.group, ctx.sparse_grad
+        T, width, total, base = group.num_tables, group.width, group.total_rows, group.row_base
+        one_storage = group.flat is not None
+        wanted = ctx.needs_input_grad[7:]
+        batch, hot = _grouped_batch(T, idx, offsets)
+        nnz = idx.numel()
+        dev, dtype = out_grad.device, out_grad.dtype
+        grad_2d = out_grad.contiguous().view(batch * T, width)
+        head = (None,) * 7
+
+        def per_table(make):
+            return head + tuple(make(t) if wanted[t] else None for t in range(T))
+
+        if nnz == 0:
+            if kind is False:
+                dense = torch.zeros((total, width), dtype=dtype, device=dev)
+                return head + (dense,) if one_storage else per_table(lambda t: dense[base[t]:base[t + 1]])
+            if one_storage:
+                return head + (_empty_sparse(total, width, dtype, dev),)
+            return per_table(lambda t: _empty_sparse(base[t + 1] - base[t], width, dtype, dev))
+        # ---- one key launch, one sort, (one remap,) one scatter-add for all tables
+        keys, sample_ids = torch.ops.cuembed_pyt.cuembed_grouped_backward_keys(idx, offsets, group.row_base_device, T,
+                                                                               batch, hot, total < 2 ** 31)
+        w = None if weights is None else weights.reshape(-1)
+        t_keys, t_sids, t_w = cuembed_transpose_sample_ids(sample_ids, keys, w, total)
+        t_w = t_w if t_w.numel() else None
+        if kind is False:
+            dense = cuembed_embedding_backward(grad_2d, total, t_keys, t_sids, t_w)
+            return head + (dense,) if one_storage else per_table(lambda t: dense[base[t]:base[t + 1]])
+        remap = torch.ops.cuembed_pyt.cuembed_compute_compressed_grad_indices(t_keys)
+        if one_storage and kind is True:      # the count is read back once, after everything is enqueued
+            num_unique = int(remap[-1].item()) + 1
+            rows, inv = torch.ops.cuembed_pyt.cuembed_embedding_backward_compressed(grad_2d, num_unique, t_keys, t_sids,
+                                                                                    remap, t_w)
+            return head + (torch.sparse_coo_tensor(inv.to(torch.int64).unsqueeze(0), rows, size=(total, width),
+                                                   is_coalesced=True),)
+        capacity = min(nnz, total)
+        rows = torch.empty((capacity, width), dtype=dtype, device=dev)
+        inv = torch.empty((capacity,), dtype=t_keys.dtype, device=dev)
+        _ops.embedding_backward(grad_2d, None, t_keys, t_sids, remap, t_w, grad_embedding=rows, inverse_mapping=inv,
+                                pad_to_capacity=one_storage)
+        if one_storage:                        # "padded": nothing is read back, the step can be captured
+            return head + (torch.sparse_coo_tensor(inv.to(torch.int64).unsqueeze(0), rows, size=(total, width),
+                                                   is_coalesced=False),)
+        # separate tensors, sparse: ONE read-back, of the num_tables + 1 cuts
+        cuts = torch.ops.cuembed_pyt.cuembed_grouped_table_cuts(inv, remap[-1:], group.row_base_device, True).tolist()
+
+        def table_grad(t):
+            lo, hi = cuts[t], cuts[t + 1]
+            return torch.sparse_coo_tensor((inv[lo:hi].to(torch.int64) - base[t]).unsqueeze(0), rows[lo:hi],
+                                           size=(base[t + 1] - base[t], width), is_coalesced=True)
+        return per_table(table_grad)
+
+
+def cuemb_embedding_grouped_trainable(group, idx, offsets=None, weights=None, sparse_grad=False, row_loads=None,
+                                      sample_order=None):
+    """cuemb_embedding_grouped (sum pooling, [batch, num_tables, width]) on a cuembed_amd.TableGroup that is TRAINED: the
+    forward is the grouped op, the backward runs ONE key launch, ONE sort and ONE scatter-add for all tables
+    (cuembed_amd.grouped_backward) instead of one single-table chain per table.  A Python autograd.Function over the
+    torch ops cuembed_grouped_backward_keys / cuembed_grouped_table_cuts and the single-table pipeline's.
+
+    A one-storage group (TableGroup.allocate / from_flat; group.flat requires grad) is differentiated with respect to
+    group.flat, which gets ONE gradient with global row ids:
+        sparse_grad=False      a dense [total_rows, width] gradient;
+        sparse_grad=True       a COALESCED sparse COO tensor of exactly the distinct rows (the count is read back once);
+        sparse_grad="padded"   padded to min(lookups, total_rows) entries (is_coalesced=False) as in cuemb_embedding:
+                               nothing is read back, the step can be captured into a HIP graph.
+    A group of separate tensors: every table that requires grad gets its own gradient, the others none:
+        sparse_grad=False      dense views of one [total_rows, width] buffer;
+        sparse_grad=True       one coalesced sparse COO tensor per table, after ONE read-back of the table cuts;
+        sparse_grad="padded"   ValueError: the tables' segments have no fixed size.
+    The weight gradient is not taken (weights.requires_grad raises).  With grad mode off, or nothing requiring grad, the
+    call is just the forward."""
+    if not (sparse_grad is False or sparse_grad is True or sparse_grad == "padded"):
+        raise ValueError("sparse_grad must be False, True or 'padded', got %r" % (sparse_grad,))
+    if group.quantized:
+        raise TypeError("a group of fused 8-bit tables is inference only: cuemb_embedding_quantized_grouped")
+    if weights is not None and weights.requires_grad:
+        raise ValueError("the grouped backward does not take the weight gradient: detach the weights")
+    one_storage = group.flat is not None
+    if sparse_grad == "padded" and not one_storage:
+        raise ValueError("sparse_grad='padded' needs a one-storage group (TableGroup.allocate / from_flat): the "
+                         "per-table segments of a compressed gradient have no fixed size")
+    params = (group.flat,) if one_storage else tuple(group.tables)
+    if not torch.is_grad_enabled() or not any(p.requires_grad for p in params):
+        return torch.ops.cuembed_pyt.cuemb_embedding_grouped([t.detach() for t in group.tables], group.table_ptrs, idx,
+                                                             offsets, weights, "sum", _ops._ROW_LOADS[row_loads],
+                                                             sample_order)
+    return _CuEmbGrouped.apply(group, idx, offsets, weights, sparse_grad, row_loads, sample_order, *params)
+
+
+class TrainableEmbeddingBagGroup(torch.nn.Module):
+    """A TableGroup that is trained, with EmbeddingBagGroup's call shape (sum pooling): bags(idx, offsets, weights) with
+    CSR offsets, or bags(idx) with idx [num_tables, batch, hotness]; returns [batch, num_tables, width] and
+    differentiates through cuemb_embedding_grouped_trainable.  parameters() yields group.flat of a one-storage group,
+    else the tables, where they are nn.Parameters."""
+
+    def __init__(self, group, sparse_grad=False):
+        super().__init__()
+        if not (sparse_grad is False or sparse_grad is True or sparse_grad == "padded"):
+            raise ValueError("sparse_grad must be False, True or 'padded', got %r" % (sparse_grad,))
+        if group.quantized:
+            raise TypeError("a group of fused 8-bit tables is inference only")
+        if sparse_grad == "padded" and group.flat is None:
+            raise ValueError("sparse_grad='padded' needs a one-storage group (TableGroup.allocate / from_flat)")
+        self.group = group
+        self.sparse_grad = sparse_grad
+        if isinstance(group.flat, torch.nn.Parameter):
+            self.weight = group.flat
+        elif group.flat is None:
+            self.tables = torch.nn.ParameterList([t for t in group.tables if isinstance(t, torch.nn.Parameter)])
+
+    @property
+    def num_tables(self):
+        return self.group.num_tables
+
+    @property
+    def embedding_dim(self):
+        return self.group.width
+
+    def forward(self, idx, offsets=None, weights=None, sample_order=None):
+        return cuemb_embedding_grouped_trainable(self.group, idx, offsets, weights, sparse_grad=self.sparse_grad,
+                                                 sample_order=sample_order)
 
 
 def cuembed_forward(params, idx, offsets, weights, hints=None):
@@ -842,6 +1043,17 @@ def _(qtables, table_ptrs, idx, offsets=None, weights=None, mode="sum", out_dtyp
       sample_order=None):
     return torch.empty(_grouped_fake_shape(qtables, idx, offsets, qtables[0].shape[1] - 8), device=qtables[0].device,
                        dtype=out_dtype)
+
+
+@torch.library.register_fake("cuembed_pyt::cuembed_grouped_backward_keys")
+def _(idx, offsets, row_base, num_tables, batch, num_hots, narrow):
+    flat = dict(device=idx.device, dtype=torch.int32 if narrow else torch.int64)
+    return torch.empty((idx.numel(),), **flat), torch.empty((idx.numel(),), **flat)
+
+
+@torch.library.register_fake("cuembed_pyt::cuembed_grouped_table_cuts")
+def _(ids, count_word, row_base, last_id=False):
+    return torch.empty((row_base.shape[0],), device=ids.device, dtype=torch.int64)
 
 
 @torch.library.register_fake("cuembed_pyt::cuembed_embedding_forward_hinted")

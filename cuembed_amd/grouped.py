@@ -17,7 +17,10 @@ and dtype lie one table after the other and one kernel pools them all:
 Every function validates its arguments and raises before any launch; the kernels run on torch's current stream
 (cuembed::EmbeddingForwardGrouped / EmbeddingForwardQuantizedGrouped through the C ABI).  No host read-back, no copy per
 call, no allocation inside the library: with `out=` given a call can be captured into a HIP graph.  Nothing here is
-differentiable: a table that requires grad while grad mode is on is an error (a grouped backward does not exist yet).
+differentiable: a table that requires grad while grad mode is on is an error.  A group is trained through
+cuembed_amd.grouped_backward (embedding_backward_grouped: one sort and one scatter-add for all tables) and, with
+autograd, cuembed_amd.cuembed_pyt.cuemb_embedding_grouped_trainable; TableGroup.allocate / from_flat put a group into
+one storage so that the sparse optimizers apply to it as they are.
 """
 import ctypes
 
@@ -77,6 +80,67 @@ class TableGroup:
             # (an earlier group's tensor for the same tables; its values stay on the device, unread)
             raise ValueError("table_ptrs must be the contiguous int64 tensor of the tables' data pointers on their device")
         self.table_ptrs = table_ptrs
+        self.row_counts = tuple(int(t.shape[0]) for t in tables)
+        self.flat = None                 # the one storage of allocate() / from_flat(); None for separate tensors
+        self._row_base_device = None
+
+    @property
+    def row_base(self):
+        """Host tuple of num_tables + 1 ints: the exclusive prefix sum of row_counts; row_base[-1] = total_rows.  Table
+        t owns the global rows [row_base[t], row_base[t + 1]) of the tables laid end to end."""
+        base = [0]
+        for n in self.row_counts:
+            base.append(base[-1] + n)
+        return tuple(base)
+
+    @property
+    def total_rows(self):
+        return sum(self.row_counts)
+
+    @property
+    def row_base_device(self):
+        """row_base as ONE int64 device tensor of num_tables + 1 entries, which the grouped backward's kernels read --
+        built at the first use, once."""
+        if self._row_base_device is None:
+            self._row_base_device = torch.tensor(self.row_base, dtype=torch.int64, device=self.device)
+        return self._row_base_device
+
+    @classmethod
+    def from_flat(cls, flat, row_counts):
+        """A group whose tables are row slices of ONE [total_rows, width] tensor the caller owns: table t is
+        flat[row_base[t]:row_base[t + 1]], so a global row id of the grouped backward is directly a row of `flat` and a
+        sparse optimizer step on `flat` (cuembed_amd.sparse_row_update, sparse_row_adam, cuembed_amd.optim) trains the
+        whole group.  `flat` may be an nn.Parameter: the views (and the pointer table) are taken from flat.detach(),
+        `flat` itself is kept as group.flat -- what cuemb_embedding_grouped_trainable differentiates with respect to.
+        Float tables only.  A slice's base is only row-aligned (rows_t * width * itemsize bytes past the previous one):
+        lane_bytes() already narrows the whole group to the least aligned pointer, so nothing else is needed."""
+        if not isinstance(flat, torch.Tensor):
+            raise TypeError("flat must be a torch.Tensor")
+        if flat.dtype not in _ELEM:
+            raise TypeError("a one-storage group holds float32, float16 or bfloat16 tables (a quantized group is a list "
+                            "of fused tables), got %s" % flat.dtype)
+        if flat.dim() != 2 or not flat.is_contiguous():
+            raise ValueError("flat must be a contiguous [total_rows, width] tensor")
+        counts = [int(n) for n in row_counts]
+        if not counts or any(n < 0 for n in counts) or sum(counts) != flat.shape[0]:
+            raise ValueError("row_counts must be non-negative and sum to flat.shape[0] = %d" % flat.shape[0])
+        base, data, views = 0, flat.detach(), []
+        for n in counts:
+            views.append(data[base:base + n])
+            base += n
+        group = cls(views)
+        group.flat = flat
+        return group
+
+    @classmethod
+    def allocate(cls, row_counts, width, dtype=torch.float32, device="cuda"):
+        """from_flat on ONE new zero-filled [sum(row_counts), width] tensor (group.flat)."""
+        if dtype not in _ELEM:
+            raise TypeError("a one-storage group holds float32, float16 or bfloat16 tables, got %s" % dtype)
+        counts = [int(n) for n in row_counts]
+        if not counts or any(n < 0 for n in counts) or width <= 0:
+            raise ValueError("row_counts must be non-negative and width positive")
+        return cls.from_flat(torch.zeros((sum(counts), int(width)), dtype=dtype, device=device), counts)
 
     def __len__(self):
         return len(self.tables)

@@ -1,0 +1,265 @@
+"""The backward on a GROUP of embedding tables: one sort and one scatter-add for all tables (an extension).
+
+The group of cuembed_amd.grouped -- T tables of one width and dtype, bag g = t * B + b, out [B, T, W] -- is trained
+through the single-table pipeline, fed the right keys:
+
+    keys[p]       = row_base[t] + indices[p]     a row of the tables laid end to end (row_base: group.row_base)
+    sample_ids[p] = b * T + t                    the lookup's row in out[B, T, W] viewed as [B * T, W]
+
+    grouped_backward_keys(group, ...)            both arrays in ONE launch (cuembed::GroupedBackwardKeys)
+    embedding_backward_grouped(group, grad_y, ...)   keys -> transpose -> remap -> embedding_backward: the gradient of
+                                                 all tables, dense ([total_rows, W] + per-table views) or compressed
+    GroupedGrad                                  the compressed gradient: global ids, rows, the device-side count
+    grouped_table_cuts(ids, row_base, ...)       where each table's entries begin (cuembed::GroupedTableCuts)
+
+The gradient comes out sorted by table, then by row.  For a ONE-STORAGE group (TableGroup.allocate / from_flat) the
+global ids are directly rows of group.flat, so the sparse optimizers apply as they are, with no read-back:
+
+    g = embedding_backward_grouped(group, grad_y, idx, offsets)
+    sparse_row_update(group.flat, g.ids, g.rows, rule="sgd", lr=lr, last_id=g.last_id)      # or sparse_row_adam, or a
+                                                                                            # cuembed_amd.optim updater
+The sort is stable, so inside one table row the lookups keep the order of the single-table pipeline: on exactly
+representable data, and with reference_sums=True on any data, the result has the bits of T single-table calls.  With
+the default arithmetic the segment cuts of the scatter-add move with the position in the combined stream: the same
+sums, associated differently.
+
+Everything validates before any launch and runs on torch's current stream.  The fixed-hotness path materialises the
+sample ids, which transpose_fixed_hotness avoids for one table.
+"""
+import torch
+
+from . import _lib
+from .grouped import INT_MAX, _as_group
+from .ops import _INDEX, _check_dev, _index_code, _ptr, _stream, embedding_backward, transpose
+
+
+def _layout(group, indices, offsets, batch_size, num_hots):
+    """The bag layout of one grouped call, validated without the GPU: (batch_size, nnz)."""
+    T = group.num_tables
+    if not isinstance(indices, torch.Tensor):
+        raise TypeError("indices must be a torch.Tensor")
+    _index_code("indices", indices)
+    if not ((offsets is not None and num_hots == 0) or (offsets is None and num_hots > 0)):
+        raise ValueError("either CSR (offsets given, num_hots == 0) or fixed hotness (offsets None, num_hots > 0)")
+    if offsets is not None:
+        if not isinstance(offsets, torch.Tensor):
+            raise TypeError("offsets must be a torch.Tensor")
+        _index_code("offsets", offsets)
+        if batch_size is None:
+            if (offsets.numel() - 1) % T or offsets.numel() < 1:
+                raise ValueError("offsets must hold num_tables * batch_size + 1 entries: %d - 1 is not a multiple of %d "
+                                 "tables" % (offsets.numel(), T))
+            batch_size = (offsets.numel() - 1) // T
+        if batch_size < 0 or offsets.numel() != T * batch_size + 1:
+            raise ValueError("offsets must hold num_tables * batch_size + 1 = %d entries, got %d"
+                             % (T * batch_size + 1, offsets.numel()))
+    else:
+        if batch_size is None:
+            if indices.numel() % (T * num_hots):
+                raise ValueError("indices.numel() is not a multiple of num_tables * num_hots")
+            batch_size = indices.numel() // (T * num_hots)
+        if batch_size < 0 or indices.numel() != T * batch_size * num_hots:
+            raise ValueError("indices must hold num_tables * batch_size * num_hots entries")
+    if T * batch_size > INT_MAX:
+        raise ValueError("num_tables * batch_size = %d does not fit a 32-bit int" % (T * batch_size))
+    nnz = indices.numel()
+    if nnz > INT_MAX:
+        raise ValueError("%d lookups: the backward pipeline takes at most 2^31 - 1" % nnz)
+    return batch_size, nnz
+
+
+def _float_group(group):
+    group = _as_group(group)
+    if group.quantized:
+        raise TypeError("a group of fused 8-bit tables has no backward: quantized tables are inference only")
+    return group
+
+
+def _key_dtype(group, key_dtype):
+    total = group.total_rows
+    if key_dtype is None:
+        return torch.int32 if total < 2 ** 31 else torch.int64
+    if key_dtype not in _INDEX:
+        raise TypeError("key_dtype must be int32 or int64, got %s" % (key_dtype,))
+    if key_dtype == torch.int32 and total >= 2 ** 31:
+        raise ValueError("int32 keys need fewer than 2^31 rows in the group, it has %d" % total)
+    return key_dtype
+
+
+def grouped_backward_keys(group, indices, offsets=None, batch_size=None, num_hots=0, key_dtype=None, out=None):
+    """(keys, sample_ids) of a group's lookups in ONE launch: for lookup p of bag t * batch_size + b,
+    keys[p] = group.row_base[t] + indices[p] and sample_ids[p] = b * num_tables + t.  CSR (offsets[num_tables *
+    batch_size + 1]) or fixed hotness (offsets=None, num_hots=H, indices [num_tables, batch_size, H]), int32 or int64
+    indices and offsets in any combination.  key_dtype: the dtype of both results, the index type of the backward
+    pipeline; None = int32 whenever the group has fewer than 2^31 rows (whatever the indices' dtype: the arrays are
+    written fresh, so narrowing is free), else int64; int32 with 2^31 rows or more is a ValueError.  out: optional
+    (keys, sample_ids) buffers of nnz entries.  Ids outside [0, rows_t) are a contract violation, as in the forward."""
+    group = _float_group(group)
+    batch_size, nnz = _layout(group, indices, offsets, batch_size, num_hots)
+    kd = _key_dtype(group, key_dtype)
+    if out is not None:
+        if not (isinstance(out, (tuple, list)) and len(out) == 2 and all(isinstance(o, torch.Tensor) for o in out)):
+            raise TypeError("out must be a (keys, sample_ids) pair of tensors")
+        for name, o in zip(("out[0]", "out[1]"), out):
+            if o.dtype != kd or o.numel() != nnz:
+                raise ValueError("%s must hold %d entries of %s" % (name, nnz, kd))
+    # ---- the call is in order: now the devices
+    dev = group.device
+    _check_dev("tables[0]", group.tables[0])
+    _check_dev("indices", indices, dev)
+    if offsets is not None:
+        _check_dev("offsets", offsets, dev)
+    if out is None:
+        keys = torch.empty((nnz,), dtype=kd, device=dev)
+        sample_ids = torch.empty((nnz,), dtype=kd, device=dev)
+    else:
+        keys, sample_ids = out
+        _check_dev("out[0]", keys, dev)
+        _check_dev("out[1]", sample_ids, dev)
+    if nnz > 0:
+        with torch.cuda.device(dev):   # the launch must happen on the tensors' device
+            _lib.lib().cuembed_grouped_backward_keys(
+                _ptr(indices), _INDEX[indices.dtype], _ptr(offsets), 0 if offsets is None else _INDEX[offsets.dtype],
+                _ptr(group.row_base_device), group.num_tables, int(batch_size), int(num_hots), nnz, _ptr(keys),
+                _ptr(sample_ids), _INDEX[kd], _stream(indices))
+    return keys, sample_ids
+
+
+def grouped_table_cuts(ids, row_base, count=None, last_id=None):
+    """cuts[t] = the number of valid entries of the ascending global ids `ids` that are < row_base[t]: an int64 device
+    tensor of num_tables + 1 entries, cuts[0] = 0, cuts[-1] = the count; table t owns the entries [cuts[t], cuts[t + 1]).
+    row_base: the int64 device tensor group.row_base_device.  The count, as sparse_row_update takes it: count=int (None:
+    all entries), count=tensor (one int32 / int64 device word) or last_id=tensor (one word of ids' dtype, count =
+    last_id + 1).  A count below zero or above ids.numel() gives all-zero cuts.  No read-back."""
+    if not isinstance(ids, torch.Tensor) or not isinstance(row_base, torch.Tensor):
+        raise TypeError("ids and row_base must be torch.Tensors")
+    it = _index_code("ids", ids)
+    if row_base.dtype != torch.int64 or row_base.dim() != 1 or row_base.numel() < 2:
+        raise TypeError("row_base must be the int64 tensor of num_tables + 1 entries (group.row_base_device)")
+    if count is not None and last_id is not None:
+        raise ValueError("give at most one of count= and last_id=")
+    n = ids.numel()
+    host_count, word, word64 = n, None, False
+    if isinstance(count, torch.Tensor):
+        if count.dtype not in _INDEX or count.numel() != 1:
+            raise TypeError("count must be an int or a one-element int32 / int64 tensor")
+        word, word64 = count, count.dtype == torch.int64
+    elif count is not None:
+        host_count = int(count)
+        if host_count < 0 or host_count > n:
+            raise ValueError("count must be in [0, ids.numel()]")
+    if last_id is not None and (not isinstance(last_id, torch.Tensor) or last_id.dtype != ids.dtype or
+                                last_id.numel() != 1):
+        raise TypeError("last_id must be a one-element tensor of ids' dtype")
+    _check_dev("ids", ids)
+    dev = ids.device
+    _check_dev("row_base", row_base, dev)
+    for name, t in (("count", word), ("last_id", last_id)):
+        if t is not None:
+            _check_dev(name, t, dev)
+    cuts = torch.empty((row_base.numel(),), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.lib().cuembed_grouped_table_cuts(_ptr(ids), it, n, host_count, _ptr(word), int(word64), _ptr(last_id),
+                                              _ptr(row_base), row_base.numel() - 1, _ptr(cuts), _stream(ids))
+    return cuts
+
+
+class GroupedGrad:
+    """The compressed gradient of a group, nothing read back:
+
+        ids        ascending GLOBAL row ids (group.row_base[t] + the row of table t), `capacity` entries of room
+        rows       [capacity, width] gradient rows, rows[k] belongs to ids[k]
+        last_id    one device word of ids' dtype: the entry count is last_id + 1 (sparse_row_update's last_id=)
+        row_base   group.row_base (host tuple)
+        capacity   min(nnz, total_rows): always enough for a fully sorted order
+
+    Entries at and past the count hold nothing.  For a one-storage group (ids, rows, last_id) is a gradient of
+    group.flat as the sparse optimizers take it."""
+
+    def __init__(self, ids, rows, last_id, row_base, row_base_device):
+        self.ids = ids
+        self.rows = rows
+        self.last_id = last_id
+        self.row_base = tuple(row_base)
+        self.row_base_device = row_base_device
+        self.capacity = ids.numel()
+
+    def table_cuts(self):
+        """The int64 device tensor of num_tables + 1 cuts (grouped_table_cuts): table t owns [cuts[t], cuts[t + 1])."""
+        return grouped_table_cuts(self.ids, self.row_base_device, last_id=self.last_id)
+
+    def per_table(self):
+        """[(local_ids_t, rows_t)] for every table, with ONE read-back (the num_tables + 1 cuts): local_ids_t =
+        ids[cut_t:cut_t+1] - row_base[t], the ascending rows of table t that were looked up; rows_t is a view."""
+        cuts = self.table_cuts().tolist()
+        return [(self.ids[cuts[t]:cuts[t + 1]] - self.row_base[t], self.rows[cuts[t]:cuts[t + 1]])
+                for t in range(len(self.row_base) - 1)]
+
+
+def _check_grad_y(group, grad_y, batch_size):
+    if not isinstance(grad_y, torch.Tensor):
+        raise TypeError("grad_y must be a torch.Tensor")
+    if grad_y.dtype != group.dtype:
+        raise TypeError("grad_y must have the tables' dtype (%s), got %s" % (group.dtype, grad_y.dtype))
+    want = (batch_size, group.num_tables, group.width)
+    if tuple(grad_y.shape) != want:
+        raise ValueError("grad_y must be [batch_size, num_tables, width] = %r, got %r" % (want, tuple(grad_y.shape)))
+    if not grad_y.is_contiguous():
+        raise ValueError("grad_y must be contiguous")
+
+
+def embedding_backward_grouped(group, grad_y, indices, offsets=None, weights=None, batch_size=None, num_hots=0,
+                               dense=False, reference_sums=False):
+    """The gradient of ALL tables of a group from grad_y [batch_size, num_tables, width] (contiguous, the tables' dtype),
+    the gradient of embedding_forward_grouped(mode="sum")'s result: grouped_backward_keys, ONE transpose (bounded by
+    total_rows, so the sort skips the zero digits) with the remap, ONE embedding_backward on grad_y viewed as
+    [batch_size * num_tables, width].  indices / offsets / weights / num_hots as in the forward.  (The remap is the
+    transpose's own fourth result, compute_compressed_grad_indices' values from the same call: up to 4,096 lookups the
+    whole index work after the keys is then one launch.)
+
+    dense=True    returns (grad, views): ONE zero-initialised [total_rows, width] buffer and its per-table row slices
+                  views[t] = grad[row_base[t]:row_base[t + 1]].  reference_sums=True (dense only: it needs a host-known
+                  row count) sums in the gradient's own type in lookup order, like the CPU reference.
+    dense=False   returns a GroupedGrad: global ids, rows and the device-side count in buffers of min(nnz, total_rows)
+                  entries; the scatter-add runs with num_grad_embedding_rows=None, so its capacity check and the
+                  overflow word (capacity_overflowed()) apply.  No read-back."""
+    group = _float_group(group)
+    batch_size, nnz = _layout(group, indices, offsets, batch_size, num_hots)
+    _check_grad_y(group, grad_y, batch_size)
+    if reference_sums and not dense:
+        raise ValueError("reference_sums needs a host-known row count: dense=True only")
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor):
+            raise TypeError("weights must be a torch.Tensor")
+        if weights.dtype != group.dtype:
+            raise TypeError("weights must be %s, got %s" % (group.dtype, weights.dtype))
+        if weights.numel() < nnz:
+            raise ValueError("weights must have one entry per index")
+    # ---- the call is in order: now the devices
+    dev = group.device
+    _check_dev("tables[0]", group.tables[0])
+    _check_dev("grad_y", grad_y, dev)
+    if weights is not None:
+        _check_dev("weights", weights, dev)
+        weights = weights.reshape(-1)[:nnz]
+    total, width = group.total_rows, group.width
+    grad_2d = grad_y.view(batch_size * group.num_tables, width)
+    keys, sample_ids = grouped_backward_keys(group, indices, offsets, batch_size, num_hots)
+    if dense:
+        grad = torch.zeros((total, width), dtype=group.dtype, device=dev)
+        if nnz > 0:
+            t_keys, t_sids, t_w = transpose(sample_ids, keys, weights, num_categories=total)
+            embedding_backward(grad_2d, total, t_keys, t_sids, None, t_w, skip_grad_init=True, grad_embedding=grad,
+                               reference_sums=reference_sums)
+        base = group.row_base
+        return grad, tuple(grad[base[t]:base[t + 1]] for t in range(group.num_tables))
+    capacity = min(nnz, total)
+    rows = torch.empty((capacity, width), dtype=group.dtype, device=dev)
+    ids = torch.empty((capacity,), dtype=keys.dtype, device=dev)
+    if capacity == 0:
+        last_id = torch.full((1,), -1, dtype=keys.dtype, device=dev)
+    else:
+        t_keys, t_sids, t_w, remap = transpose(sample_ids, keys, weights, num_categories=total, remapped=True)
+        embedding_backward(grad_2d, None, t_keys, t_sids, remap, t_w, grad_embedding=rows, inverse_mapping=ids)
+        last_id = remap[-1:]
+    return GroupedGrad(ids, rows, last_id, group.row_base, group.row_base_device)

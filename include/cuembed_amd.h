@@ -643,6 +643,32 @@ void cuembed_embedding_forward_quantized_grouped(const void* const* tables_host,
 void cuembed_grouped_forward_launch_shape(int quantized, int elem_type, int index_type, int embed_width, int num_tables,
                                           int batch_per_table, int num_hots, int is_csr, int is_weighted,
                                           int compute_units, int xcds, int* out);
+/* ---- the backward of a group (extension): one sort and one scatter-add for all its tables -----
+ * The group above is trained through the single-table pipeline, fed the right keys.  row_base[num_tables + 1] is the
+ * exclusive prefix sum of the tables' row counts: int64, DEVICE memory, built once by the caller; row_base[num_tables]
+ * = total_rows.  Call sequence (all on one stream, nothing allocated, nothing read back):
+ *   cuembed_grouped_backward_keys        keys + sample ids of all lookups
+ *   cuembed_transpose[_remapped]         rows = sample_ids, cols = keys, index_bits = ceil(log2(total_rows))
+ *   cuembed_compute_compressed_grad_indices   (compressed gradient only, unless the transpose gave the remap)
+ *   cuembed_embedding_backward[_bounded] grad_y = the gradient of ret viewed as [batch_per_table * num_tables, width]
+ *   cuembed_grouped_table_cuts           where each table's entries begin in the compressed gradient
+ * The gradient is that of the tables laid end to end, sorted by table, then by row; for tables that are row slices of
+ * ONE allocation it is directly a gradient of that allocation (cuembed_sparse_row_update applies unchanged). */
+/* cuembed::GroupedBackwardKeys: for lookup p of bag t * batch_per_table + b, keys[p] = row_base[t] + indices[p] and
+ * sample_ids[p] = b * num_tables + t, both of key_type (CUEMBED_I32 needs total_rows < 2^31; independent of index_type).
+ * CSR: offsets[num_tables * batch_per_table + 1] of offset_type, num_hots = 0; fixed hotness: offsets = NULL, num_hots
+ * > 0.  nnz = the number of lookups, <= INT_MAX.  Ids outside their table are a contract violation. */
+void cuembed_grouped_backward_keys(const void* indices, int index_type, const void* offsets, int offset_type,
+                                   const int64_t* row_base, int num_tables, int batch_per_table, int num_hots,
+                                   int64_t nnz, void* keys, void* sample_ids, int key_type, cuembed_stream_t stream);
+/* cuembed::GroupedTableCuts: cuts[t] (int64, device, num_tables + 1 entries) = the number of valid entries of the
+ * ascending global ids inverse_mapping (index_type) that are < row_base[t]; cuts[num_tables] = the count.  The count:
+ * count_word (device; one int32 word, or int64 with count_word_is_64), else last_id (device; one word of index_type,
+ * count = last_id + 1: transpose_remapped_indices + nnz - 1), else the host value count.  capacity = the entries
+ * inverse_mapping has room for; a count outside [0, capacity] gives all-zero cuts. */
+void cuembed_grouped_table_cuts(const void* inverse_mapping, int index_type, int64_t capacity, int64_t count,
+                                const void* count_word, int count_word_is_64, const void* last_id,
+                                const int64_t* row_base, int num_tables, int64_t* cuts, cuembed_stream_t stream);
 /* hipPeekAtLastError() as an int (0 = hipSuccess); launches themselves never
  * report errors, exactly like the reference. */
 int cuembed_peek_last_error(void);
