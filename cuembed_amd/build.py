@@ -289,7 +289,7 @@ def build_sort_unit_test(force=False):
 
 def build_device_blocks_test(force=False):
     """Compiles tests/cpp/device_blocks_unit.hip: unit tests of the gather / scatter building blocks (addressing, column
-    slices, Pack / Arith / RowPool, FinishPooledRow, AccumulateRow) instantiated in small kernels and compared with host
+    slices, Pack / Arith / RowPool, FinishPooledRow, the backward's RunSum, staging and chaining) instantiated in small kernels and compared with host
     recomputation, bit for bit.  Needs a GPU to RUN (tests/test_gpu_device_blocks.py)."""
     src = os.path.join(ROOT, "tests", "cpp", "device_blocks_unit.hip")
     exe = os.path.join(ROOT, "tests", "cpp", "device_blocks_unit")

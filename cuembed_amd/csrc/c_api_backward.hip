@@ -29,15 +29,6 @@ cuembed::detail::DeviceShape ShapeFrom(int compute_units, int xcds, int64_t l2_b
   if (l2_bytes_per_xcd > 0) dev.l2_bytes_per_xcd = static_cast<size_t>(l2_bytes_per_xcd);
   return dev;
 }
-
-template <typename ElemT, int N>
-cuembed::detail::ScatterShape PlanFor(int index_type, int width, int64_t nnz, bool weighted,
-                                      const cuembed::detail::RowSplit& split,
-                                      const cuembed::detail::DeviceShape& dev) {
-  return index_type == CUEMBED_I32
-             ? cuembed::detail::PlanScatter<ElemT, int32_t, N>(width, nnz, split, weighted, dev)
-             : cuembed::detail::PlanScatter<ElemT, int64_t, N>(width, nnz, split, weighted, dev);
-}
 }  // namespace
 
 extern "C" {
@@ -161,18 +152,12 @@ void cuembed_device_shape(int* out) {
 void cuembed_backward_launch_shape(int elem_type, int index_type, int embed_width, int64_t nnz, int is_weighted,
                                    int compute_units, int xcds, int* out) {
   const cuembed::detail::DeviceShape dev = ShapeFrom(compute_units, xcds, 0);
-  cuembed::detail::ScatterShape s;
-  if (elem_type == CUEMBED_F32) {
-    const auto split = cuembed::detail::SplitRow<float>(embed_width, nullptr, nullptr);
-    s = split.elems_per_lane == 4   ? PlanFor<float, 4>(index_type, embed_width, nnz, is_weighted != 0, split, dev)
-        : split.elems_per_lane == 2 ? PlanFor<float, 2>(index_type, embed_width, nnz, is_weighted != 0, split, dev)
-                                    : PlanFor<float, 1>(index_type, embed_width, nnz, is_weighted != 0, split, dev);
-  } else {  // 2-byte elements (fp16 and bf16 plan identically)
-    const auto split = cuembed::detail::SplitRow<_Float16>(embed_width, nullptr, nullptr);
-    s = split.elems_per_lane == 8   ? PlanFor<_Float16, 8>(index_type, embed_width, nnz, is_weighted != 0, split, dev)
-        : split.elems_per_lane == 4 ? PlanFor<_Float16, 4>(index_type, embed_width, nnz, is_weighted != 0, split, dev)
-                                    : PlanFor<_Float16, 2>(index_type, embed_width, nnz, is_weighted != 0, split, dev);
-  }
+  (void)index_type;   // ids are staged as 32 bits whatever their type: the plan does not depend on it
+  const bool f32 = elem_type == CUEMBED_F32;   // (fp16 and bf16 plan identically)
+  const auto split = f32 ? cuembed::detail::SplitRow<float>(embed_width, nullptr, nullptr)
+                         : cuembed::detail::SplitRow<_Float16>(embed_width, nullptr, nullptr);
+  const cuembed::detail::ScatterShape s =
+      cuembed::detail::PlanScatter(embed_width, nnz, split, is_weighted != 0, f32 ? 4 : 2, dev);
   out[0] = s.slices;
   out[1] = s.lanes;
   out[2] = s.segments_per_block;

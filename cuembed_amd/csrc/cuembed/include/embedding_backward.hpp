@@ -95,19 +95,21 @@ struct ScatterShape {
   }
 };
 
-template <typename GradT, typename IndexT, int N>
+//! `elem_bytes`: the size of a gradient element; the lane width is split.elems_per_lane.
 inline ScatterShape PlanScatter(const int width, const int64_t nnz, const RowSplit split, const bool weighted,
-                                const DeviceShape& dev) {
+                                const int elem_bytes, const DeviceShape& dev) {
   ScatterShape s;
   s.xcds = dev.xcds;
-  s.slices = ChooseColumnSlices(static_cast<size_t>(width) * sizeof(GradT), split.lanes_per_row, nnz, dev);
+  s.slices = ChooseColumnSlices(static_cast<size_t>(width) * elem_bytes, split.lanes_per_row, nnz, dev);
   s.lanes = split.lanes_per_row / s.slices;  // lanes of one column slice
   s.segments_per_block = s.lanes >= kDefaultBlockThreads ? 1 : kDefaultBlockThreads / s.lanes;
   s.segment_len = ChooseSegmentLen(nnz, split.lanes_per_row, dev);
+  const auto stage_bytes = [&] {
+    return ScatterStage::Of(s.segments_per_block, s.segment_len, s.lanes, split.elems_per_lane, weighted, elem_bytes).bytes;
+  };
   // Keep the staged COO triples of one workgroup within the LDS budget: shorten the
   // segments first (down to 32 lookups), then put fewer segments in a workgroup.
-  while (ScatterStageBytes<GradT, IndexT>(s.segments_per_block, s.segment_len, s.lanes, N, weighted) >
-         static_cast<size_t>(kMaxScatterStageBytes)) {
+  while (stage_bytes() > static_cast<unsigned>(kMaxScatterStageBytes)) {
     if (s.segment_len > 32) s.segment_len /= 2;
     else if (s.segments_per_block > 1) s.segments_per_block /= 2;
     else if (s.segment_len > kMinSegmentLen) s.segment_len /= 2;
@@ -116,55 +118,70 @@ inline ScatterShape PlanScatter(const int width, const int64_t nnz, const RowSpl
   s.segment_len = s.segment_len < 8 ? 8 : s.segment_len & ~7;
   s.nz_blocks = s.NzBlocks(nnz);
   s.grid_blocks = s.GridBlocks(s.nz_blocks);
-  s.lds = ScatterStageBytes<GradT, IndexT>(s.segments_per_block, s.segment_len, s.lanes, N, weighted);
+  s.lds = stage_bytes();
   return s;
 }
 
-//! `sample_block_len` > 0: the COO is a sample-blocked order (blocked_order.hpp) -- consecutive blocks of that many
-//! lookups, each sorted on its own, row ids from ComputeCompressedGradIndicesBlocked -- and every block gets its own
-//! stream-ordered launch (a run whose row an earlier block stored is added to it).  0: one launch over everything.
-template <typename GradT, typename IndexT, int N>
-inline void LaunchScatterAdd(const GradT* grad_y, int width, const IndexT* rows,
-                             const IndexT* sample_ids, const GradT* weights, int64_t nnz,
-                             GradT* grad_out, RowSplit split, hipStream_t stream,
-                             const bool zero_shared /* compressed gradient: zero only what needs it, see below */,
-                             const int64_t zero_rows /* ... and the rows from the last id up to here (<= 0: none) */,
-                             const IndexT* run_ids, IndexT* inverse_mapping /* compressed gradient only */,
-                             const int64_t sample_block_len = 0, const uint32_t* block_row_ids = nullptr,
-                             const int64_t capacity_rows = 0, uint32_t* capacity_overflow = nullptr,
-                             const bool pad_to_capacity = false) {
+//! One backward call as LaunchScatterAdd takes it.
+template <typename GradT, typename IndexT>
+struct ScatterRequest {
+  const GradT* grad_y;          //!< the sorted COO and what it gathers from
+  int width;
+  const IndexT *rows, *sample_ids;   //!< gradient rows: remapped or raw ids (sample-blocked order: pair numbers)
+  const GradT* weights;
+  int64_t nnz;
+  RowSplit split;
+  GradT* grad_out;              //!< the outputs; a compressed gradient also names its rows:
+  const IndexT* run_ids;        //!< the table row of every lookup ...
+  IndexT* inverse_mapping;      //!< ... and where the row of every run goes
+  bool zero_shared;             //!< compressed gradient: zero only what needs it (ZeroSharedAndTailRowsKernel) ...
+  int64_t zero_rows;            //!< ... and the rows from the last id up to here (<= 0: none)
+  //! > 0: the COO is a sample-blocked order (blocked_order.hpp) -- consecutive blocks of that many lookups, each
+  //! sorted on its own, row ids from ComputeCompressedGradIndicesBlocked -- and every block gets its own
+  //! stream-ordered launch (a run whose row an earlier block stored is added to it).  0: one launch over everything.
+  int64_t sample_block_len;
+  const uint32_t* block_row_ids;   //!< the pair -> gradient row table of that order
+  int64_t capacity_rows;           //!< > 0: rows the outputs hold, checked on the device ...
+  uint32_t* capacity_overflow;     //!< ... and the word that is raised when they do not suffice
+  bool pad_to_capacity;            //!< name the zeroed rows past the count (NamePaddedRowsKernel)
+  hipStream_t stream;
+};
+
+template <int N, typename GradT, typename IndexT>
+inline void LaunchScatterAdd(const ScatterRequest<GradT, IndexT>& r) {
   const DeviceShape dev = CurrentDeviceShape();
-  const ScatterShape s = PlanScatter<GradT, IndexT, N>(width, nnz, split, weights != nullptr, dev);
+  const ScatterShape s = PlanScatter(r.width, r.nnz, r.split, r.weights != nullptr, static_cast<int>(sizeof(GradT)), dev);
   const dim3 block(s.lanes, s.segments_per_block, 1);
   const int block_len = s.segments_per_block * s.segment_len;
-  const bool blocked = sample_block_len > 0 && sample_block_len < nnz;
-  const int64_t launch_len = blocked ? sample_block_len : nnz;
-  const int launches = static_cast<int>((nnz + launch_len - 1) / launch_len);
-  const uint32_t* pair_rows = blocked ? block_row_ids : nullptr;
-  if (zero_shared) {
-    const int64_t tail_blocks = ZeroTailBlocks(zero_rows, dev);
+  const bool blocked = r.sample_block_len > 0 && r.sample_block_len < r.nnz;
+  const int64_t launch_len = blocked ? r.sample_block_len : r.nnz;
+  const int launches = static_cast<int>((r.nnz + launch_len - 1) / launch_len);
+  const uint32_t* pair_rows = blocked ? r.block_row_ids : nullptr;
+  if (r.zero_shared) {
+    const int64_t tail_blocks = ZeroTailBlocks(r.zero_rows, dev);
     const int64_t per_launch = s.NzBlocks(launch_len);
     ZeroSharedAndTailRowsKernel<GradT, IndexT>
-        <<<static_cast<unsigned>(per_launch * launches + tail_blocks), 256, 0, stream>>>(
-            rows, nnz, block_len, per_launch, launch_len, launches, width, zero_rows, grad_out, pair_rows,
-            capacity_rows, pad_to_capacity);
+        <<<static_cast<unsigned>(per_launch * launches + tail_blocks), 256, 0, r.stream>>>(
+            r.rows, r.nnz, block_len, per_launch, launch_len, launches, r.width, r.zero_rows, r.grad_out, pair_rows,
+            r.capacity_rows);
   }
   int seg_shift = -1;
   if ((s.segment_len & (s.segment_len - 1)) == 0)
     for (seg_shift = 0; (1 << seg_shift) < s.segment_len; ++seg_shift) {}
   for (int p = 0; p < launches; ++p) {
     const int64_t first = p * launch_len;
-    const int64_t count = first + launch_len < nnz ? launch_len : nnz - first;
+    const int64_t count = first + launch_len < r.nnz ? launch_len : r.nnz - first;
     const dim3 grid(static_cast<unsigned>(s.GridBlocks(s.NzBlocks(count))), 1, 1);
-    const IndexT* run_ids_p = run_ids != nullptr ? run_ids + first : nullptr;
+    const IndexT* run_ids_p = r.run_ids != nullptr ? r.run_ids + first : nullptr;
 #define CUEMBED_LAUNCH_SCATTER(W, BLK, WIN)                                                                       \
-  SegmentedScatterAddKernel<GradT, IndexT, N, W, BLK, WIN><<<grid, block, s.lds, stream>>>(                         \
-      grad_y, width, rows + first, sample_ids + first, (W) ? weights + first : weights, count, s.segment_len,        \
-      seg_shift, grad_out, s.slices, s.xcds, run_ids_p, inverse_mapping, pair_rows, capacity_rows, capacity_overflow)
+  SegmentedScatterAddKernel<GradT, IndexT, N, W, BLK, WIN><<<grid, block, s.lds, r.stream>>>(                       \
+      r.grad_y, r.width, r.rows + first, r.sample_ids + first, (W) ? r.weights + first : r.weights, count,          \
+      s.segment_len, seg_shift, r.grad_out, s.slices, s.xcds, run_ids_p, r.inverse_mapping, pair_rows,              \
+      r.capacity_rows, r.capacity_overflow)
     const bool adds_to_rows = blocked && p > 0;   // (the first block finds nothing stored yet: plain kernel)
     // window depth: column-sliced launches gather mostly from L2 (short window, more wavefronts); unsliced ones miss
     const bool short_window = s.slices > 1 || adds_to_rows;
-    if (weights != nullptr) {
+    if (r.weights != nullptr) {
       if (adds_to_rows) CUEMBED_LAUNCH_SCATTER(true, true, kBackwardWindowHits);
       else if (short_window) CUEMBED_LAUNCH_SCATTER(true, false, kBackwardWindowHits);
       else CUEMBED_LAUNCH_SCATTER(true, false, kBackwardWindowMisses);
@@ -175,10 +192,10 @@ inline void LaunchScatterAdd(const GradT* grad_y, int width, const IndexT* rows,
     }
 #undef CUEMBED_LAUNCH_SCATTER
   }
-  if (pad_to_capacity && zero_rows > 0) {   // the zeroed rows past the count get their row ids (see NamePaddedRowsKernel)
-    const int64_t blocks = (zero_rows + 255) / 256;
-    NamePaddedRowsKernel<IndexT><<<static_cast<unsigned>(blocks < 1024 ? blocks : 1024), 256, 0, stream>>>(
-        rows, nnz, inverse_mapping, zero_rows);
+  if (r.pad_to_capacity && r.zero_rows > 0) {   // the zeroed rows past the count get their row ids (see NamePaddedRowsKernel)
+    const int64_t blocks = (r.zero_rows + 255) / 256;
+    NamePaddedRowsKernel<IndexT><<<static_cast<unsigned>(blocks < 1024 ? blocks : 1024), 256, 0, r.stream>>>(
+        r.rows, r.nnz, r.inverse_mapping, r.zero_rows);
   }
 }
 
@@ -304,26 +321,12 @@ void EmbeddingBackward(const GradT* grad_y,
     }
   }
 
-  const IndexT* run_ids = compressed ? transpose_indices : nullptr;  // inverse mapping is written by the scatter
-  const ElemT* gy = reinterpret_cast<const ElemT*>(grad_y);
-  const ElemT* w = reinterpret_cast<const ElemT*>(transpose_weights);
-  ElemT* out = reinterpret_cast<ElemT*>(grad_embedding);
-  constexpr int kMaxN = 16 / static_cast<int>(sizeof(ElemT));
-  if (split.elems_per_lane == kMaxN)
-    detail::LaunchScatterAdd<ElemT, IndexT, kMaxN>(gy, embed_width, rows, transpose_sample_ids, w, nnz, out, split,
-                                                   stream, zero_shared, zero_rows, run_ids, inverse_mapping,
-                                                   sample_block_len, block_row_ids, capacity_rows, capacity_overflow,
-                                                   pad_to_capacity);
-  else if (split.elems_per_lane == kMaxN / 2)
-    detail::LaunchScatterAdd<ElemT, IndexT, kMaxN / 2>(gy, embed_width, rows, transpose_sample_ids, w, nnz, out,
-                                                       split, stream, zero_shared, zero_rows, run_ids, inverse_mapping,
-                                                       sample_block_len, block_row_ids, capacity_rows,
-                                                       capacity_overflow, pad_to_capacity);
-  else
-    detail::LaunchScatterAdd<ElemT, IndexT, kMaxN / 4>(gy, embed_width, rows, transpose_sample_ids, w, nnz, out,
-                                                       split, stream, zero_shared, zero_rows, run_ids, inverse_mapping,
-                                                       sample_block_len, block_row_ids, capacity_rows,
-                                                       capacity_overflow, pad_to_capacity);
+  const detail::ScatterRequest<ElemT, IndexT> request{
+      reinterpret_cast<const ElemT*>(grad_y), embed_width, rows, transpose_sample_ids,
+      reinterpret_cast<const ElemT*>(transpose_weights), nnz, split, reinterpret_cast<ElemT*>(grad_embedding),
+      compressed ? transpose_indices : nullptr /* inverse mapping is written by the scatter */, inverse_mapping,
+      zero_shared, zero_rows, sample_block_len, block_row_ids, capacity_rows, capacity_overflow, pad_to_capacity, stream};
+  detail::WithLaneWidth<ElemT>(split.elems_per_lane, [&](auto n) { detail::LaunchScatterAdd<decltype(n)::value>(request); });
 }
 
 /**
@@ -372,25 +375,22 @@ void EmbeddingBackwardReferenceSums(const GradT* grad_y,
   const dim3 block(lanes, groups, 1);
   const int64_t spans = (static_cast<int64_t>(nnz) + detail::kReferenceSpan - 1) / detail::kReferenceSpan;
   const dim3 plain_grid(static_cast<unsigned>((spans + groups - 1) / groups), 1, 1);
-  constexpr int kMaxN = 16 / static_cast<int>(sizeof(ElemT));
   // runs of 256 lookups and more are walked by the whole workgroup out of LDS (see the kernel); 0: shape without that path
   const size_t row_bytes = static_cast<size_t>(embed_width) * sizeof(ElemT);
   const int chunk = detail::ReferenceLongRun(row_bytes, lanes, groups).chunk_rows;
-  const size_t lds = chunk > 0 ? 2 * static_cast<size_t>(chunk) * (row_bytes + sizeof(ElemT)) : 0;
+  static_assert(sizeof(ElemT) <= detail::kReferenceRowSlack, "ReferenceLongRun budgets less than the stage needs");
+  const size_t lds = chunk > 0 ? detail::ReferenceStageOf(chunk, row_bytes, sizeof(ElemT)).bytes : 0;
+  CUEMBED_ASSERT(lds <= detail::kReferenceStageBudget);
   const dim3 grid(chunk > 0 ? 2 * plain_grid.x : plain_grid.x, 1, 1);      // (long-run half first, then the short runs)
-#define CUEMBED_LAUNCH_REFERENCE(NN)                                                                               \
-  do {                                                                                                             \
-    if (w != nullptr)                                                                                              \
-      detail::ReferenceSumsScatterKernel<ElemT, IndexT, NN, true><<<grid, block, lds, stream>>>(                    \
-          gy, embed_width, rows, transpose_sample_ids, w, nnz, out, skip_grad_init, run_ids, inverse_mapping, chunk); \
-    else                                                                                                           \
-      detail::ReferenceSumsScatterKernel<ElemT, IndexT, NN, false><<<grid, block, lds, stream>>>(                   \
-          gy, embed_width, rows, transpose_sample_ids, w, nnz, out, skip_grad_init, run_ids, inverse_mapping, chunk); \
-  } while (0)
-  if (split.elems_per_lane == kMaxN) CUEMBED_LAUNCH_REFERENCE(kMaxN);
-  else if (split.elems_per_lane == kMaxN / 2) CUEMBED_LAUNCH_REFERENCE(kMaxN / 2);
-  else CUEMBED_LAUNCH_REFERENCE(kMaxN / 4);
-#undef CUEMBED_LAUNCH_REFERENCE
+  detail::WithLaneWidth<ElemT>(split.elems_per_lane, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    if (w != nullptr)
+      detail::ReferenceSumsScatterKernel<ElemT, IndexT, N, true><<<grid, block, lds, stream>>>(
+          gy, embed_width, rows, transpose_sample_ids, w, nnz, out, skip_grad_init, run_ids, inverse_mapping, chunk);
+    else
+      detail::ReferenceSumsScatterKernel<ElemT, IndexT, N, false><<<grid, block, lds, stream>>>(
+          gy, embed_width, rows, transpose_sample_ids, w, nnz, out, skip_grad_init, run_ids, inverse_mapping, chunk);
+  });
 }
 
 }  // namespace cuembed

@@ -186,6 +186,16 @@ inline RowSplit SplitRow(const int embed_width, const void* p0, const void* p1) 
   return s;
 }
 
+//! fn(std::integral_constant<int, N>{}) for N = elems_per_lane: the lane widths SplitRow<ElemT> can return (16, 8 or
+//! 4 bytes worth of elements).
+template <typename ElemT, typename Fn>
+inline void WithLaneWidth(const int elems_per_lane, Fn&& fn) {
+  constexpr int kMaxN = 16 / static_cast<int>(sizeof(ElemT));
+  if (elems_per_lane == kMaxN) fn(std::integral_constant<int, kMaxN>{});
+  else if (elems_per_lane == kMaxN / 2) fn(std::integral_constant<int, kMaxN / 2>{});
+  else fn(std::integral_constant<int, kMaxN / 4>{});
+}
+
 //! Complete launch description of one forward call.
 struct ForwardLaunch {
   RowSplit split;

@@ -247,25 +247,11 @@ __device__ __forceinline__ void StorePackStreaming(ElemT* p, const Pack<ElemT, N
   __builtin_nontemporal_store(*reinterpret_cast<const raw_t*>(&v), reinterpret_cast<raw_t*>(p));
 }
 
-//! acc[e] += float(row.v[e]) [* wf] -- one IEEE fp32 add (and one multiply) per element, as
-//! everywhere in this library.
-//! (Measured and rejected for fp16 rows: v_fma_mix_f32, which converts, multiplies and adds in one
+//! Running state of one lane while it pools the rows of its sample.
+//! (Measured and rejected for fp16 rows, here and in the backward's RunSum: v_fma_mix_f32, which converts, multiplies and adds in one
 //! instruction and is bit-identical because the product of two fp16 values is exact in fp32.  It
 //! halves the instruction count but not the time: C2 forward 0.139 -> 0.185 ms, i.e. the mixed-
 //! precision FMA issues well below the rate of v_cvt_f32_f16 + v_add_f32 on gfx950.)
-template <typename GradT, int N, bool kWeighted>
-__device__ __forceinline__ void AccumulateRow(float (&acc)[N], const Pack<GradT, N>& row, const float wf) {
-  using A = Arith<float>;
-  if constexpr (kWeighted) {
-#pragma unroll
-    for (int e = 0; e < N; ++e) acc[e] = A::add(acc[e], A::mul(static_cast<float>(row.v[e]), wf));
-  } else {
-#pragma unroll
-    for (int e = 0; e < N; ++e) acc[e] = A::add(acc[e], static_cast<float>(row.v[e]));
-  }
-}
-
-//! Running state of one lane while it pools the rows of its sample.
 template <typename ElemT, typename AccT, int N, bool kWeighted>
 struct RowPool {
   using A = Arith<AccT>;

@@ -88,71 +88,450 @@ constexpr int kPackedPad = 4;
 constexpr uint32_t kRunEndBit = 0x80000000u;
 //! Bit 30 of a staged sample id (sample-blocked order only): "an earlier block already stored the row of this run".
 constexpr uint32_t kSharedRunBit = 0x40000000u;
-
-//! LDS needed by SegmentedScatterAddKernel for `segments_per_block` segments of
-//! `segment_len` lookups handled by `lanes_per_row` lanes each:
-//!   row ids for [first - 1, last + 1] (two sentinels), sample ids, weights (if any),
-//!   one fp32 partial row per segment (head run; the tail run's re-uses the id area) and their bookkeeping.
-template <typename GradT, typename IndexT>
-__host__ __device__ inline size_t ScatterStageBytes(int segments_per_block, int segment_len,
-                                                    int lanes_per_row, int elems_per_lane,
-                                                    bool weighted) {
-  // ids are staged as 32-bit whatever IndexT is: nnz and num_grad_embedding_rows are `int` in the
-  // API (embedding_lookup.cuh:423-435), so every row id and sample id fits.  Every segment has its
-  // own padded slice: a wavefront reads the SAME position of 8 different
-  // segments at a time, and with a power-of-two stride all 8 would hit one LDS bank.
-  const size_t segs = static_cast<size_t>(segments_per_block);
-  size_t bytes = (segs * (segment_len + 2) * sizeof(int32_t) + 15) / 16 * 16;   // row ids
-  bytes += segs * (segment_len + kPackedPad) * sizeof(uint32_t);                // packed sample ids
-  bytes = (bytes + 15) / 16 * 16;
-  if (weighted) bytes += segs * (segment_len + 2) * sizeof(GradT);
-  bytes = (bytes + 15) / 16 * 16;
-  // one fp32 partial row per segment for the run that came in (written during the walk) ...
-  const size_t partial = segs * lanes_per_row * elems_per_lane * sizeof(float);
-  // ... and one for the run that goes on, which is parked AFTER the walk on top of the staged ids
-  // (dead by then): the staging area is as large as the larger of the two
-  if (bytes < partial) bytes = partial;
-  bytes += partial;
-  bytes += segs * (2 * sizeof(int64_t) + sizeof(int));
-  return (bytes + 15) / 16 * 16;
-}
+//! Lookups per thread and round of the staging: all their loads are requested before the first one is used (the
+//! blocked order adds a dependent table lookup per lookup; one at a time, a thread's 8 lookups at C4 would pay
+//! 8 x 2 memory latencies before the walk can start)
+constexpr int kStageBatch = 4;
 
 enum : int { kPartHead = 1, kPartTail = 2, kPartWhole = 4 };
 
+//! The LDS of one workgroup of SegmentedScatterAddKernel, as byte offsets: the host sizes the launch from `bytes`, the
+//! kernel carves its regions from the same object.  `segments` segments of `segment_len` lookups, walked by `lanes`
+//! lanes (of ONE column slice) with `n` elements each.
+//! Ids are staged as 32-bit whatever the index type is: nnz and num_grad_embedding_rows are `int` in the API
+//! (embedding_lookup.cuh:423-435), so every row id and sample id fits.  Every segment has its own padded slice -- a
+//! wavefront reads the SAME position of 8 different segments at a time, and with a power-of-two stride all 8 would hit
+//! one LDS bank: strides that are no multiples of the 64 banks.
+struct ScatterStage {
+  int row_stride;          //!< segment_len + 2: the lookup before, the segment's row ids (or weights), the lookup after
+  int packed_stride;       //!< segment_len + kPackedPad
+  unsigned rows;           //!< int32 [segments][row_stride]
+  unsigned packed;         //!< uint32 [segments][packed_stride]: sample id | kRunEndBit | kSharedRunBit
+  unsigned weights;        //!< GradT [segments][row_stride], weighted launches only
+  unsigned head_partials;  //!< float [segments][n][lanes]: the run that came in from before, parked during the walk
+  //! float [segments][n][lanes]: the run that goes on, parked AFTER every walk of the workgroup is over ON TOP of the
+  //! staged ids, which nobody reads any more -- the id area is as large as the larger of the two
+  unsigned tail_partials;
+  unsigned partial_rows;   //!< int64 [segments][2]: the rows of the head and the tail partial
+  unsigned flags;          //!< int [segments]: kPartHead | kPartTail | kPartWhole
+  unsigned bytes;          //!< the dynamic LDS of the launch
+
+  __host__ __device__ static unsigned Up16(const unsigned b) { return (b + 15u) / 16u * 16u; }
+  __host__ __device__ static ScatterStage Of(const int segments, const int segment_len, const int lanes, const int n,
+                                             const bool weighted, const int elem_bytes) {
+    ScatterStage s;
+    const unsigned segs = static_cast<unsigned>(segments);
+    s.row_stride = segment_len + 2;
+    s.packed_stride = segment_len + kPackedPad;
+    s.rows = s.tail_partials = 0;
+    s.packed = Up16(segs * s.row_stride * 4u);
+    s.weights = Up16(s.packed + segs * s.packed_stride * 4u);
+    unsigned ids_end = Up16(s.weights + (weighted ? segs * s.row_stride * static_cast<unsigned>(elem_bytes) : 0u));
+    const unsigned partial = segs * static_cast<unsigned>(lanes) * static_cast<unsigned>(n) * 4u;
+    if (ids_end < partial) ids_end = partial;
+    s.head_partials = ids_end;
+    s.partial_rows = s.head_partials + partial;
+    s.flags = s.partial_rows + segs * 16u;
+    s.bytes = Up16(s.flags + segs * 4u);
+    return s;
+  }
+};
+
+//! The regions of a ScatterStage as pointers into the workgroup's LDS.
+template <typename GradT>
+struct ScatterStageView {
+  int32_t* rows;
+  uint32_t* packed;
+  GradT* weights;
+  float *head_partials, *tail_partials;
+  int64_t* partial_rows;
+  int* flags;
+  int row_stride, packed_stride;
+  __device__ __forceinline__ ScatterStageView(unsigned char* lds, const ScatterStage& s)
+      : rows(reinterpret_cast<int32_t*>(lds + s.rows)), packed(reinterpret_cast<uint32_t*>(lds + s.packed)),
+        weights(reinterpret_cast<GradT*>(lds + s.weights)), head_partials(reinterpret_cast<float*>(lds + s.head_partials)),
+        tail_partials(reinterpret_cast<float*>(lds + s.tail_partials)),
+        partial_rows(reinterpret_cast<int64_t*>(lds + s.partial_rows)), flags(reinterpret_cast<int*>(lds + s.flags)),
+        row_stride(s.row_stride), packed_stride(s.packed_stride) {}
+};
+
+//! Where a thread stands: lane `lane_x` of the `lanes` that walk segment `seg` of the workgroup's `segments`; the
+//! workgroup's lookups are [block_begin, block_begin + block_len) of the launch's nnz.
+struct ScatterPlace {
+  int lane_x, lanes, seg, segments, segment_len, segment_shift, block_len;
+  int64_t block_begin, nnz;
+  __device__ __forceinline__ int SegmentOf(const int e) const {
+    return segment_shift >= 0 ? e >> segment_shift : e / segment_len;
+  }
+};
+
+//! The running fp32 sum of one run on the N elements of a lane, and the arithmetic of one lookup: convert, multiply by
+//! the weight in fp32 (weighted only), add -- one unfused IEEE operation each.  The sum lives in register PAIRS:
+//! v_pk_add_f32 adds a pair per instruction and a pair is cleared by one 64-bit move.
+template <typename GradT, int N, bool kWeighted>
+struct RunSum {
+  typedef float __attribute__((ext_vector_type(2))) pair_t;
+  static constexpr int kPairs = (N + 1) / 2;
+  pair_t acc[kPairs];
+
+  __device__ __forceinline__ void Zero() {
+#pragma unroll
+    for (int j = 0; j < kPairs; ++j) acc[j] = pair_t{0.f, 0.f};
+  }
+  __device__ __forceinline__ void Restart() {   // after a flush: one move per pair
+#pragma unroll
+    for (int j = 0; j < kPairs; ++j) asm("v_mov_b64 %0, 0" : "=v"(acc[j]));
+  }
+  //! f = float(row) [* float(w)], paired
+  __device__ __forceinline__ static void Term(const Pack<GradT, N>& row, const GradT& w, pair_t (&f)[kPairs]) {
+#pragma unroll
+    for (int e = 0; e < 2 * kPairs; ++e) {
+      float x = 0.f;
+      if (e < N) {
+        x = static_cast<float>(row.v[e < N ? e : 0]);
+        if constexpr (kWeighted) x = Arith<float>::mul(x, static_cast<float>(w));
+      }
+      if (e & 1) f[e / 2].y = x; else f[e / 2].x = x;
+    }
+  }
+  __device__ __forceinline__ void Add(const pair_t (&f)[kPairs]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int j = 0; j < kPairs; ++j) acc[j] = acc[j] + f[j];
+  }
+  //! One lookup.  (The walk calls Term and Add itself: it requests the next gather between the two.)
+  __device__ __forceinline__ void Accumulate(const Pack<GradT, N>& row, const GradT& w) {
+    pair_t f[kPairs];
+    Term(row, w, f);
+    Add(f);
+  }
+  __device__ __forceinline__ void Unpair(float (&dst)[N]) const {
+#pragma unroll
+    for (int e = 0; e < N; ++e) dst[e] = (e & 1) ? acc[e / 2].y : acc[e / 2].x;
+  }
+};
+
+//! Staging.  The workgroup's COO triples are ONE contiguous range of the sorted arrays: all threads copy it with fully
+//! coalesced loads (consecutive threads, consecutive lookups) into the per-segment padded slices.  The run structure
+//! is decided HERE, once per lookup, not in the walk: a staged sample id carries kRunEndBit when the next lookup
+//! belongs to another row (sample ids are non-negative 32-bit values: nnz and the batch are `int` in the API).
+//! Positions past nnz hold sample 0 without the bit: their lanes gather a valid row and never flush it.
+//! Sample-blocked order: `rows` holds pair numbers, block_row_ids[pair] the gradient row | kSharedRowBit; a run with
+//! that bit gets kSharedRunBit (sample ids are < 2^30 in a blocked order).
+template <typename GradT, typename IndexT, bool kWeighted, bool kBlocked>
+__device__ __forceinline__ void StageLookups(const ScatterStageView<GradT>& st, const ScatterPlace& at,
+                                             const IndexT* __restrict__ rows, const IndexT* __restrict__ sample_ids,
+                                             const GradT* __restrict__ weights, const uint32_t* __restrict__ block_row_ids) {
+  const int tid = at.seg * at.lanes + at.lane_x;
+  const int threads = at.lanes * at.segments;
+  for (int e0 = tid; e0 < at.block_len; e0 += threads * kStageBatch) {
+    int32_t r[kStageBatch], r_next[kStageBatch];
+    uint32_t sid[kStageBatch];
+    GradT wv[kStageBatch];
+#pragma unroll
+    for (int q = 0; q < kStageBatch; ++q) {
+      const int64_t g = at.block_begin + e0 + q * threads;
+      const bool in = e0 + q * threads < at.block_len && g < at.nnz;
+      r[q] = in ? static_cast<int32_t>(rows[g]) : -1;
+      r_next[q] = (in && g + 1 < at.nnz) ? static_cast<int32_t>(rows[g + 1]) : -1;
+      sid[q] = in ? static_cast<uint32_t>(static_cast<int32_t>(sample_ids[g])) : 0u;
+      if constexpr (kWeighted) wv[q] = in ? weights[g] : static_cast<GradT>(0);
+    }
+    int32_t row[kStageBatch];
+#pragma unroll
+    for (int q = 0; q < kStageBatch; ++q) {
+      row[q] = r[q];
+      if (block_row_ids != nullptr && r[q] >= 0) row[q] = static_cast<int32_t>(block_row_ids[r[q]]);
+    }
+#pragma unroll
+    for (int q = 0; q < kStageBatch; ++q) {
+      const int e = e0 + q * threads;
+      if (e < at.block_len) {
+        const int s = at.SegmentOf(e);
+        const int i = e - s * at.segment_len;
+        uint32_t pk = 0;
+        if (r[q] >= 0) {
+          pk = sid[q] | (r_next[q] != r[q] ? kRunEndBit : 0u);
+          if constexpr (kBlocked) {
+            if (static_cast<uint32_t>(row[q]) & kSharedRowBit) pk |= kSharedRunBit;
+          }
+          if constexpr (kWeighted) st.weights[s * st.row_stride + i] = wv[q];
+        }
+        st.rows[s * st.row_stride + 1 + i] = row[q];
+        st.packed[s * st.packed_stride + i] = pk;
+      }
+    }
+  }
+}
+
+//! Sample-blocked order: the rows that will be read and added to were written by another launch and come from HBM.
+//! Touch this slice's lines of them now -- all requests of the workgroup in flight together, one wait -- so that the
+//! reads in the walk, which sit in the in-order return queue of the gathers, find them in L2.  Every thread looks at
+//! the lookups it staged itself (no barrier needed); lookups without such a row touch line 0 of the gradient.
+//! `slice0`: the first element of this column slice in row 0 of the gradient.
+template <typename GradT, int N>
+__device__ __forceinline__ void WarmSharedRows(const ScatterStageView<GradT>& st, const ScatterPlace& at,
+                                               const GradT* __restrict__ slice0_elems, const int width) {
+  const int tid = at.seg * at.lanes + at.lane_x;
+  const int threads = at.lanes * at.segments;
+  uint32_t warmed = 0;
+  const int slice_bytes = at.lanes * N * static_cast<int>(sizeof(GradT));
+  const char* slice0 = reinterpret_cast<const char*>(slice0_elems);
+  for (int e0 = tid; e0 < at.block_len; e0 += threads * kStageBatch) {
+    const char* line[kStageBatch];
+#pragma unroll
+    for (int q = 0; q < kStageBatch; ++q) {
+      const int e = e0 + q * threads;
+      line[q] = slice0;
+      if (e < at.block_len) {
+        const int s = at.SegmentOf(e);
+        const int i = e - s * at.segment_len;
+        const uint32_t pk = st.packed[s * st.packed_stride + i];
+        if ((pk & (kRunEndBit | kSharedRunBit)) == (kRunEndBit | kSharedRunBit))
+          line[q] = slice0 + static_cast<int64_t>(static_cast<uint32_t>(st.rows[s * st.row_stride + 1 + i]) & ~kSharedRowBit) *
+                                 (static_cast<int64_t>(width) * static_cast<int64_t>(sizeof(GradT)));
+      }
+    }
+    for (int b = 0; b < slice_bytes; b += 128) {
+#pragma unroll
+      for (int q = 0; q < kStageBatch; ++q) warmed |= *reinterpret_cast<const uint32_t*>(line[q] + b);
+    }
+  }
+  asm volatile("" ::"v"(warmed));   // (keeps the loads; the next barrier waits for them)
+}
+
+//! The two sentinels of every segment, after a barrier: the lookup before and after it is a neighbour's staged id,
+//! or -- at the two ends of the workgroup's range -- one more element of the sorted array (-1 outside it).
+template <typename GradT, typename IndexT>
+__device__ __forceinline__ void StageSentinels(const ScatterStageView<GradT>& st, const ScatterPlace& at,
+                                               const IndexT* __restrict__ rows, const uint32_t* __restrict__ block_row_ids) {
+  if (at.lane_x != 0) return;
+  int32_t* seg_rows = st.rows + at.seg * st.row_stride;
+  const int64_t before = at.block_begin - 1, after = at.block_begin + at.block_len;
+  auto row_at = [&](const int64_t g) {
+    const int32_t r = static_cast<int32_t>(rows[g]);
+    return block_row_ids != nullptr ? static_cast<int32_t>(block_row_ids[r]) : r;
+  };
+  seg_rows[0] = at.seg > 0 ? st.rows[(at.seg - 1) * st.row_stride + at.segment_len]
+                           : ((before >= 0 && before < at.nnz) ? row_at(before) : -1);
+  seg_rows[at.segment_len + 1] = at.seg + 1 < at.segments ? st.rows[(at.seg + 1) * st.row_stride + 1]
+                                                          : (after < at.nnz ? row_at(after) : -1);
+}
+
+//! Compressed gradient: inverse_mapping[dense id] = table row id, written at the first lookup of every run (the
+//! reference's CompactSparseIndicesKernel, embedding_lookup_kernels.cuh:289-302, is a separate launch over all nnz;
+//! here the dense ids are already in LDS and only the run heads load their table row id).
+template <typename GradT, typename IndexT>
+__device__ __forceinline__ void NameRuns(const ScatterStageView<GradT>& st, const ScatterPlace& at, const uint32_t id_mask,
+                                         const IndexT* __restrict__ run_ids, IndexT* __restrict__ inverse_mapping) {
+  const int32_t* seg_rows = st.rows + at.seg * st.row_stride;
+  const int64_t seg_begin = at.block_begin + static_cast<int64_t>(at.seg) * at.segment_len;
+  for (int i = at.lane_x; i < at.segment_len; i += at.lanes) {
+    const int64_t g = seg_begin + i;
+    if (g < at.nnz && seg_rows[1 + i] != seg_rows[i])
+      inverse_mapping[static_cast<uint32_t>(seg_rows[1 + i]) & id_mask] = run_ids[g];
+  }
+}
+
+//! The walk of one segment in nz order: every lane group runs the SAME segment_len iterations (uniform loop, scalar
+//! branches).  kWindow gathers stay in flight for the whole walk: the row of lookup i + K is requested as soon as the
+//! registers of lookup i have been converted (a rolling window, not load-8 / wait / add-8).  A run inside the segment
+//! ends in a plain store; the first run, when it came in from before, is parked in head_partials; the last run, when
+//! it goes on, after a barrier in tail_partials.  `lane_src` / `lane_dst`: this lane's elements of row 0.
+template <typename GradT, int N, bool kWeighted, bool kBlocked, int kWindow>
+__device__ __forceinline__ void WalkSegment(const ScatterStageView<GradT>& st, const ScatterPlace& at,
+                                            const GradT* __restrict__ lane_src, GradT* __restrict__ lane_dst, const int width) {
+  using A = Arith<float>;
+  using Sum = RunSum<GradT, N, kWeighted>;
+  constexpr uint32_t shared_row_bit = kBlocked ? kSharedRowBit : 0u;
+  constexpr uint32_t id_mask = ~shared_row_bit;   // staged ids keep the bit (equal inside a run); addresses drop it
+  const int seg = at.seg, lane_x = at.lane_x, lanes = at.lanes, segment_len = at.segment_len;
+  const int32_t* my_rows = st.rows + seg * st.row_stride + 1;  // my_rows[-1] = lookup before the segment
+  const uint32_t* my_pk = st.packed + seg * st.packed_stride;
+  const GradT* my_w = st.weights + seg * st.row_stride;
+  typedef uint32_t __attribute__((ext_vector_type(4))) word4_t;
+  constexpr int K = kWindow;
+  static_assert(K % 4 == 0, "packed ids are fetched four at a time");
+
+  // A run is "shared" when it also has lookups in a neighbouring segment (-1 sentinels and positions past nnz never count)
+  bool first_pending = my_rows[0] >= 0 && my_rows[-1] == my_rows[0];   // the first run came in from before
+  const bool tail_shared = my_rows[segment_len - 1] >= 0 && my_rows[segment_len] == my_rows[segment_len - 1];
+
+  Sum sum;
+  sum.Zero();
+  auto note = [&](const int slot, const int64_t row, const int flag) {
+    if (lane_x == 0) {
+      st.partial_rows[seg * 2 + slot] = row;
+      st.flags[seg] |= flag;
+    }
+  };
+  auto park = [&](float* partials) {
+    float a[N];
+    sum.Unpair(a);
+#pragma unroll
+    for (int e = 0; e < N; ++e) partials[(seg * N + e) * lanes + lane_x] = a[e];
+  };
+  auto fetch_ids = [&](uint32_t (&dst)[K], const int i0) {
+#pragma unroll
+    for (int q = 0; q < K / 4; ++q) {
+      const word4_t v = *reinterpret_cast<const word4_t*>(my_pk + i0 + 4 * q);
+      dst[4 * q + 0] = v.x; dst[4 * q + 1] = v.y; dst[4 * q + 2] = v.z; dst[4 * q + 3] = v.w;
+    }
+  };
+  // rows in flight are held as raw dwords (one register tuple per lookup, re-used by the request that replaces it)
+  typedef uint32_t __attribute__((ext_vector_type(sizeof(Pack<GradT, N>) / 4))) raw_t;
+  constexpr uint32_t kSampleMask = kBlocked ? ~(kRunEndBit | kSharedRunBit) : ~kRunEndBit;
+  auto gather = [&](const uint32_t packed) {
+    return *reinterpret_cast<const raw_t*>(RowPtr(lane_src, static_cast<int64_t>(packed & kSampleMask), width));
+  };
+  // Sample-blocked order: a run whose row an earlier block (an earlier launch) already stored is ADDED to it -- a
+  // read-modify-write, not an atomic (13.7 M dword atomics at C4 cost 0.1 ms; the 55 MB they touch are 10 us of
+  // traffic).  The old row is requested TOGETHER with the gather of the run's last lookup, kWindow
+  // lookups ahead of its use, into a register tuple of its own per window slot: loads return in order, so it is
+  // there when that lookup is consumed and the window never drains for it (a read issued at the run's end and
+  // awaited at the next one made the compiler wait for vmcnt(1): 0.177 instead of 0.119 ms per block).
+  raw_t old[kBlocked ? K : 1];
+  auto request_old = [&](const uint32_t packed, const int pos, raw_t& into) {
+    if constexpr (kBlocked) {
+      if ((packed & (kRunEndBit | kSharedRunBit)) == (kRunEndBit | kSharedRunBit))
+        into = *reinterpret_cast<const raw_t*>(
+            RowPtr(lane_dst, static_cast<int64_t>(static_cast<uint32_t>(my_rows[pos]) & id_mask), width));
+    }
+  };
+
+  raw_t g[K];
+  uint32_t cur[K], nxt[K];
+  fetch_ids(cur, 0);
+#pragma unroll
+  for (int u = 0; u < K; ++u) {
+    g[u] = gather(cur[u]);
+    request_old(cur[u], u, old[kBlocked ? u : 0]);
+  }
+  auto batch = [&](const int i, auto more_tag) {
+    constexpr bool kMore = decltype(more_tag)::value;
+    if constexpr (kMore) fetch_ids(nxt, i + K);
+    GradT w[K];
+    if constexpr (kWeighted) {
+#pragma unroll
+      for (int u = 0; u < K; ++u) w[u] = my_w[i + u];
+    }
+#pragma unroll
+    for (int u = 0; u < K; ++u) {
+      typename Sum::pair_t f[Sum::kPairs];
+      Sum::Term(__builtin_bit_cast(Pack<GradT, N>, g[u]), w[u], f);
+      if constexpr (kMore) {
+        __builtin_amdgcn_sched_barrier(0);   // the registers of lookup i are free: request i + K into them
+        g[u] = gather(nxt[u]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      sum.Add(f);
+      if (static_cast<int32_t>(cur[u]) < 0) {   // kRunEndBit: the run ends with this lookup
+        const uint32_t flagged = static_cast<uint32_t>(my_rows[i + u]);
+        if (first_pending) {   // its first lookups are in earlier segments
+          park(st.head_partials);
+          note(0, static_cast<int64_t>(flagged), kPartHead);
+        } else {
+          GradT* dst = const_cast<GradT*>(RowPtr(lane_dst, static_cast<int64_t>(flagged & id_mask), width));
+          float a[N];
+          sum.Unpair(a);
+          if constexpr (kBlocked) {
+            if (flagged & shared_row_bit) {   // an earlier block stored this row: add what it holds
+              const Pack<GradT, N> was = __builtin_bit_cast(Pack<GradT, N>, old[u]);
+#pragma unroll
+              for (int e = 0; e < N; ++e) a[e] = A::add(static_cast<float>(was.v[e]), a[e]);
+            }
+          }
+          FlushStore<GradT, N>(dst, a);
+        }
+        first_pending = false;
+        sum.Restart();
+      }
+      if constexpr (kBlocked && kMore) request_old(nxt[u], i + K + u, old[u]);   // (the slot is free again)
+    }
+    if constexpr (kMore) {
+#pragma unroll
+      for (int u = 0; u < K; ++u) cur[u] = nxt[u];
+    }
+  };
+  int i = 0;
+  for (; i + K < segment_len; i += K) batch(i, std::true_type{});
+  batch(i, std::false_type{});   // the last K lookups: nothing left to request
+  if (tail_shared)   // the last run goes on into the next segment (kPartWhole: it also came in)
+    note(1, static_cast<int64_t>(static_cast<uint32_t>(my_rows[segment_len - 1])), kPartTail | (first_pending ? kPartWhole : 0));
+  __syncthreads();   // nobody reads the staged ids any more: tail_partials lies on top of them
+  if (tail_shared) park(st.tail_partials);
+}
+
+//! The parked partials of neighbouring segments that belong to the same row are chained and summed in nz order by
+//! the segment that ends the chain.  A chain that stays inside the workgroup is written with a plain store; only a
+//! chain that crosses the workgroup boundary uses float atomics -- at most two atomic flushes per workgroup.
+template <typename GradT, int N, bool kBlocked>
+__device__ __forceinline__ void ChainPartials(const ScatterStageView<GradT>& st, const ScatterPlace& at,
+                                              GradT* __restrict__ lane_dst, const int width) {
+  using A = Arith<float>;
+  constexpr uint32_t shared_row_bit = kBlocked ? kSharedRowBit : 0u;
+  constexpr uint32_t id_mask = ~shared_row_bit;
+  const int seg = at.seg, lane_x = at.lane_x, lanes = at.lanes;
+  const int flags = st.flags[seg];
+  const int64_t remaining = at.nnz - at.block_begin;
+  const int last_seg = static_cast<int>(
+      remaining >= at.block_len ? at.segments - 1 : (remaining + at.segment_len - 1) / at.segment_len - 1);
+  auto add_part = [&](float (&sum)[N], int s, const float* partials) {
+    const float* p = partials + static_cast<size_t>(s) * N * lanes;
+#pragma unroll
+    for (int e = 0; e < N; ++e) sum[e] = A::add(sum[e], p[e * lanes + lane_x]);
+  };
+  if (flags & kPartHead) {
+    // a run that came in from earlier segments ends in this one
+    float sum[N];
+#pragma unroll
+    for (int e = 0; e < N; ++e) sum[e] = 0.f;
+    int k = seg - 1;
+    while (k >= 0 && (st.flags[k] & kPartWhole)) --k;
+    const bool from_previous_block = k < 0;
+    for (int m = from_previous_block ? 0 : k; m < seg; ++m) add_part(sum, m, st.tail_partials);
+    add_part(sum, seg, st.head_partials);
+    const uint32_t flagged = static_cast<uint32_t>(st.partial_rows[seg * 2 + 0]);
+    GradT* dst = lane_dst + static_cast<int64_t>(flagged & id_mask) * width;
+    // (sample-blocked order: an earlier block stored this row -> add to it.  An atomic, not a read-modify-write: this
+    // is the end of the workgroup, a read would be waited for in full, and there is at most one chain per segment)
+    if (from_previous_block || (flagged & shared_row_bit)) FlushAtomic<N>(dst, sum);
+    else FlushStore<GradT, N>(dst, sum);
+  }
+  if ((flags & kPartTail) && seg == last_seg) {
+    // the workgroup's last run goes on into the next workgroup
+    float sum[N];
+#pragma unroll
+    for (int e = 0; e < N; ++e) sum[e] = 0.f;
+    int k = seg;
+    while (k >= 0 && (st.flags[k] & kPartWhole)) --k;
+    for (int m = k < 0 ? 0 : k; m <= seg; ++m) add_part(sum, m, st.tail_partials);
+    FlushAtomic<N>(lane_dst + static_cast<int64_t>(static_cast<uint32_t>(st.partial_rows[seg * 2 + 1]) & id_mask) * width, sum);
+  }
+}
+
 //! block = (lanes_per_row, segments_per_block); grid = ceil(num_segments / segments_per_block)
-//! dynamic LDS = ScatterStageBytes(...).
+//! dynamic LDS = ScatterStage::Of(...).bytes.
 //!
-//! 1. The workgroup's segments are consecutive, so their COO triples form ONE contiguous
-//!    range of the sorted arrays: it is copied into LDS with coalesced loads once; the walk
-//!    reads ids from LDS and only the grad_y row gathers stay on the global-memory path.
-//!    Where runs end is decided here, once per lookup (kRunEndBit of the staged sample id).
-//! 2. Each segment is walked in nz order by `lanes_per_row` lanes: a uniform loop over a rolling
-//!    window of kWindow gathers (lookup i + K is requested into the registers of lookup
-//!    i as soon as those are converted), fp32 partial sums in register pairs.  A run that lies
-//!    inside the segment ends in a plain vector store.  The partial sums of the segment's FIRST
-//!    run (when it continues from the previous segment) and LAST run (when it continues into
-//!    the next one) are parked in LDS instead.
+//! 1. StageLookups, StageSentinels; 2. WalkSegment (see there).
 //! 2b. XCD-aware column slices (`column_slices` > 1): grad_y (batch x width) is usually larger
 //!    than one XCD's 4 MiB L2 but far smaller than the 256 MiB Infinity Cache, so every L2
 //!    would stream all of it from the fabric.  Workgroup b (which runs on XCD b % 8) therefore
 //!    only handles column slice (b % 8) % slices of its lookups: each L2 then holds 1/slices of
 //!    grad_y and the same random-row gather was measured 1.47x faster (8.4 -> 12.3 TB/s with 4
 //!    slices of 128 B).  The price is that the COO triples are staged once per slice.
-//! 3. After a barrier the parked partials of neighbouring segments that belong to the same
-//!    row are chained and summed in nz order by the segment that ends the chain.  A chain that
-//!    stays inside the workgroup is written with a plain store; only a chain that crosses the
-//!    workgroup boundary uses float atomics -- at most two atomic flushes per workgroup.
-//!    Device-scope atomics to one address serialise at roughly 0.5 us each on MI355X (the
-//!    XCD L2s are not coherent, so they execute memory-side); a row with a 65,528-lookup run
-//!    would otherwise be hit by 512 of them and alone take longer than the rest of the kernel.
+//! 3. ChainPartials, after a barrier.  Device-scope atomics to one address serialise at roughly 0.5 us each on
+//!    MI355X (the XCD L2s are not coherent, so they execute memory-side); a row with a 65,528-lookup run would
+//!    otherwise be hit by 512 of them and alone take longer than the rest of the kernel.
 //! 4. Sample-blocked order (block_row_ids != nullptr; blocked_order.hpp): `rows` holds (block, table row) pair
 //!    numbers and block_row_ids[pair] the gradient row, with kSharedRowBit when an EARLIER block -- an earlier launch
 //!    on the same stream -- already stored that row (ComputeCompressedGradIndicesBlocked); the staging translates.
 //!    The first block has no such rows and runs the plain kernel; the later ones run the kBlocked variant, in which
 //!    a run with the bit is ADDED to what is there: a read-modify-write when the run lies inside this workgroup (nobody else
 //!    touches the row during this launch), the usual float atomics when it crosses workgroups.  The rows to be read
-//!    are requested once while staging (they were written by another launch and come from HBM; that brings their
-//!    lines into this XCD's L2) and again with the gather of the run's last lookup (see `old` below).
+//!    are requested once while staging (WarmSharedRows) and again with the gather of the run's last lookup.
+//!    (kBlocked is a template parameter, not a run-time flag: the registers of the read-modify-write would cost the
+//!    reference-order kernel a wavefront per SIMD.)
 template <typename GradT, typename IndexT, int N, bool kWeighted, bool kBlocked = false, int kWindow = kBackwardWindowHits>
 __global__ void __launch_bounds__(kMaxBlockThreads)
 SegmentedScatterAddKernel(const GradT* __restrict__ grad_y,
@@ -171,19 +550,13 @@ SegmentedScatterAddKernel(const GradT* __restrict__ grad_y,
                           const uint32_t* __restrict__ block_row_ids,   // sample-blocked order: pair number -> row | bit
                           const int64_t capacity_rows,               // > 0: rows that grad_out / inverse_mapping hold
                           uint32_t* __restrict__ capacity_overflow) {  // ... and the word that says "not enough"
-  // (a template parameter, not a run-time flag: the registers of the read-modify-write would cost the
-  // reference-order kernel a wavefront per SIMD)
-  constexpr uint32_t shared_row_bit = kBlocked ? kSharedRowBit : 0u;
-  using A = Arith<float>;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  const int lane_x = threadIdx.x;
-  const int lanes = blockDim.x;  // lanes of ONE column slice
-  const int seg = threadIdx.y;
-  const int segments_per_block = blockDim.y;
+  const int lanes = blockDim.x, segments_per_block = blockDim.y;  // (lanes of ONE column slice)
   const int block_len = segments_per_block * segment_len;
   const ColumnSlice cs = ColumnSlice::Of(blockIdx.x, column_slices, xcds);
-  const int64_t block_begin = cs.block * block_len;
-  if (block_begin >= nnz) return;  // the grid is rounded up to whole rounds of `xcds` workgroups
+  const ScatterPlace at{static_cast<int>(threadIdx.x), lanes, static_cast<int>(threadIdx.y), segments_per_block,
+                        segment_len, segment_shift, block_len, cs.block * block_len, nnz};
+  if (at.block_begin >= nnz) return;  // the grid is rounded up to whole rounds of `xcds` workgroups
   if (capacity_rows > 0) {
     // Compressed gradient whose row count only the device knows (num_grad_embedding_rows < 0): the ids ascend through
     // the sorted COO of this launch, so its LAST lookup holds the largest gradient row.  If the caller's buffers are
@@ -197,347 +570,23 @@ SegmentedScatterAddKernel(const GradT* __restrict__ grad_y,
       return;
     }
   }
-  const int64_t column0 = (static_cast<int64_t>(cs.slice) * lanes + lane_x) * N;
-  const uint32_t id_mask = ~shared_row_bit;   // staged ids keep the bit (equal inside a run); addresses drop it
+  const ScatterStageView<GradT> st(lds_raw, ScatterStage::Of(segments_per_block, segment_len, lanes, N, kWeighted,
+                                                             static_cast<int>(sizeof(GradT))));
+  const int64_t slice0 = static_cast<int64_t>(cs.slice) * lanes * N;   // first column of this workgroup's slice
 
-  // ---- LDS carve-up (must match ScatterStageBytes) ----
-  // per segment: rows [segment_len + 2] = (lookup before, the segment's row ids, lookup after);
-  // packed sample ids [segment_len + kPackedPad]; weights [segment_len + 2] -- strides that are not
-  // multiples of the 64 LDS banks, so the 8 segments of a wavefront read from different banks
-  const int row_stride = segment_len + 2;
-  const int pk_stride = segment_len + kPackedPad;
-  const int w_stride = segment_len + 2;
-  int32_t* st_rows = reinterpret_cast<int32_t*>(lds_raw);
-  size_t off = (static_cast<size_t>(segments_per_block) * row_stride * sizeof(int32_t) + 15) / 16 * 16;
-  uint32_t* st_pk = reinterpret_cast<uint32_t*>(lds_raw + off);
-  off = (off + static_cast<size_t>(segments_per_block) * pk_stride * sizeof(uint32_t) + 15) / 16 * 16;
-  GradT* st_w = reinterpret_cast<GradT*>(lds_raw + off);
-  if (kWeighted) off += static_cast<size_t>(segments_per_block) * w_stride * sizeof(GradT);
-  off = (off + 15) / 16 * 16;
-  const size_t partial_bytes = static_cast<size_t>(segments_per_block) * lanes * N * sizeof(float);
-  if (off < partial_bytes) off = partial_bytes;                     // (the id area also holds the tail partials, below)
-  float* part_head = reinterpret_cast<float*>(lds_raw + off);       // [seg][N][lanes]: run that came in from before
-  float* part_tail = reinterpret_cast<float*>(lds_raw);             // [seg][N][lanes]: run that goes on; ALIASES the staged ids
-  off += partial_bytes;
-  int64_t* part_row = reinterpret_cast<int64_t*>(lds_raw + off);   // [seg][2]
-  off += static_cast<size_t>(segments_per_block) * 2 * sizeof(int64_t);
-  int* part_flags = reinterpret_cast<int*>(lds_raw + off);         // [seg]
-
-  {
-    // The workgroup's COO triples are ONE contiguous range of the sorted arrays: all threads copy it
-    // with fully coalesced loads (consecutive threads, consecutive lookups) into the per-segment
-    // padded slices.  The run structure is decided HERE, once per lookup, not in the walk: a staged
-    // sample id carries kRunEndBit when the next lookup belongs to another row (sample ids are
-    // non-negative 32-bit values: nnz and the batch are `int` in the API).  Positions past nnz
-    // hold sample 0 without the bit: their lanes gather a valid row and never flush it.
-    const int tid = seg * lanes + lane_x;
-    const int threads = lanes * segments_per_block;
-    // kStageBatch lookups per thread and round: all their loads are requested before the first one is used (the
-    // blocked order adds a dependent table lookup per lookup; one at a time, a thread's 8 lookups at C4 would pay
-    // 8 x 2 memory latencies before the walk can start)
-    constexpr int kStageBatch = 4;
-    for (int e0 = tid; e0 < block_len; e0 += threads * kStageBatch) {
-      int32_t r[kStageBatch], r_next[kStageBatch];
-      uint32_t sid[kStageBatch];
-      GradT wv[kStageBatch];
-#pragma unroll
-      for (int q = 0; q < kStageBatch; ++q) {
-        const int64_t g = block_begin + e0 + q * threads;
-        const bool in = e0 + q * threads < block_len && g < nnz;
-        r[q] = in ? static_cast<int32_t>(rows[g]) : -1;
-        r_next[q] = (in && g + 1 < nnz) ? static_cast<int32_t>(rows[g + 1]) : -1;
-        sid[q] = in ? static_cast<uint32_t>(static_cast<int32_t>(sample_ids[g])) : 0u;
-        if constexpr (kWeighted) wv[q] = in ? weights[g] : static_cast<GradT>(0);
-      }
-      int32_t row[kStageBatch];
-#pragma unroll
-      for (int q = 0; q < kStageBatch; ++q) {
-        row[q] = r[q];
-        if (block_row_ids != nullptr && r[q] >= 0)   // sample-blocked order: pair number -> gradient row | kSharedRowBit
-          row[q] = static_cast<int32_t>(block_row_ids[r[q]]);
-      }
-#pragma unroll
-      for (int q = 0; q < kStageBatch; ++q) {
-        const int e = e0 + q * threads;
-        if (e < block_len) {
-          const int s = segment_shift >= 0 ? e >> segment_shift : e / segment_len;
-          const int i = e - s * segment_len;
-          uint32_t pk = 0;
-          if (r[q] >= 0) {
-            pk = sid[q] | (r_next[q] != r[q] ? kRunEndBit : 0u);
-            if constexpr (kBlocked) {   // (sample ids are < 2^30 in a blocked order)
-              if (static_cast<uint32_t>(row[q]) & shared_row_bit) pk |= kSharedRunBit;
-            }
-            if constexpr (kWeighted) st_w[s * w_stride + i] = wv[q];
-          }
-          st_rows[s * row_stride + 1 + i] = row[q];
-          st_pk[s * pk_stride + i] = pk;
-        }
-      }
-    }
-    if constexpr (kBlocked) {
-      // The rows that will be read and added to were written by another launch and come from HBM.  Touch this
-      // slice's lines of them now -- all requests of the workgroup in flight together, one wait -- so that the reads
-      // in the walk, which sit in the in-order return queue of the gathers, find them in L2.  Every thread looks at
-      // the lookups it staged itself (no barrier needed); lookups without such a row touch line 0 of the gradient.
-      uint32_t warmed = 0;
-      const int slice_bytes = lanes * N * static_cast<int>(sizeof(GradT));
-      const char* slice0 = reinterpret_cast<const char*>(grad_out + static_cast<int64_t>(cs.slice) * lanes * N);
-      for (int e0 = tid; e0 < block_len; e0 += threads * kStageBatch) {
-        const char* line[kStageBatch];
-#pragma unroll
-        for (int q = 0; q < kStageBatch; ++q) {
-          const int e = e0 + q * threads;
-          line[q] = slice0;
-          if (e < block_len) {
-            const int s = segment_shift >= 0 ? e >> segment_shift : e / segment_len;
-            const int i = e - s * segment_len;
-            const uint32_t pk = st_pk[s * pk_stride + i];
-            if ((pk & (kRunEndBit | kSharedRunBit)) == (kRunEndBit | kSharedRunBit))
-              line[q] = slice0 + static_cast<int64_t>(static_cast<uint32_t>(st_rows[s * row_stride + 1 + i]) & id_mask) *
-                                     (static_cast<int64_t>(width) * static_cast<int64_t>(sizeof(GradT)));
-          }
-        }
-        for (int b = 0; b < slice_bytes; b += 128) {
-#pragma unroll
-          for (int q = 0; q < kStageBatch; ++q) warmed |= *reinterpret_cast<const uint32_t*>(line[q] + b);
-        }
-      }
-      asm volatile("" ::"v"(warmed));   // (keeps the loads; the barrier below waits for them)
-    }
-    if (lane_x == 0) part_flags[seg] = 0;
-    __syncthreads();
-    // the lookup before and after every segment: a neighbour's staged id, or -- at the two ends of
-    // the workgroup's range -- one more element of the sorted array (-1 outside it)
-    if (lane_x == 0) {
-      int32_t* seg_rows = st_rows + seg * row_stride;
-      const int64_t before = block_begin - 1, after = block_begin + block_len;
-      auto row_at = [&](const int64_t g) {
-        const int32_t r = static_cast<int32_t>(rows[g]);
-        return block_row_ids != nullptr ? static_cast<int32_t>(block_row_ids[r]) : r;
-      };
-      seg_rows[0] = seg > 0 ? st_rows[(seg - 1) * row_stride + segment_len]
-                            : ((before >= 0 && before < nnz) ? row_at(before) : -1);
-      seg_rows[segment_len + 1] = seg + 1 < segments_per_block
-                                      ? st_rows[(seg + 1) * row_stride + 1]
-                                      : (after < nnz ? row_at(after) : -1);
-    }
-  }
+  StageLookups<GradT, IndexT, kWeighted, kBlocked>(st, at, rows, sample_ids, weights, block_row_ids);
+  if constexpr (kBlocked) WarmSharedRows<GradT, N>(st, at, grad_out + slice0, width);
+  if (at.lane_x == 0) st.flags[at.seg] = 0;
   __syncthreads();
-  // Compressed gradient: inverse_mapping[dense id] = table row id, written at the first lookup of
-  // every run (the reference's CompactSparseIndicesKernel, embedding_lookup_kernels.cuh:289-302, is
-  // a separate launch over all nnz; here the dense ids are already in LDS and only the run heads
-  // load their table row id).
-  if (run_ids != nullptr && cs.slice == 0) {
-    const int32_t* seg_rows = st_rows + seg * row_stride;
-    const int64_t seg_begin = block_begin + static_cast<int64_t>(seg) * segment_len;
-    for (int i = lane_x; i < segment_len; i += lanes) {
-      const int64_t g = seg_begin + i;
-      if (g < nnz && seg_rows[1 + i] != seg_rows[i])
-        inverse_mapping[static_cast<uint32_t>(seg_rows[1 + i]) & id_mask] = run_ids[g];
-    }
-  }
-  const int seg_off = seg * segment_len;  // offset of this segment inside the block
-  const int64_t begin = block_begin + seg_off;
-  const bool active = begin < nnz;
-  const GradT* lane_src = grad_y + column0;
-  GradT* lane_dst = grad_out + column0;
-
-  {
-    // ---- the walk: every lane group runs the SAME segment_len iterations (uniform loop, scalar
-    // branches); what differs per segment is only where runs end.
-    const int32_t* my_rows = st_rows + seg * row_stride + 1;  // my_rows[-1] = lookup before the segment
-    const uint32_t* my_pk = st_pk + seg * pk_stride;
-    const GradT* my_w = st_w + seg * w_stride;
-    typedef uint32_t __attribute__((ext_vector_type(4))) word4_t;
-    constexpr int K = kWindow;
-    static_assert(K % 4 == 0, "packed ids are fetched four at a time");
-
-    // A run is "shared" when it also has lookups in a neighbouring segment (the -1 sentinels and
-    // the -1 of positions past nnz never count).
-    bool first_pending = my_rows[0] >= 0 && my_rows[-1] == my_rows[0];   // the first run came in from before
-    const bool tail_shared = my_rows[segment_len - 1] >= 0 && my_rows[segment_len] == my_rows[segment_len - 1];
-
-    // the running sum lives in register PAIRS: v_pk_add_f32 adds a pair per instruction and a
-    // pair is cleared by one 64-bit move
-    typedef float __attribute__((ext_vector_type(2))) pair_t;
-    constexpr int kPairs = (N + 1) / 2;
-    pair_t acc[kPairs];
-#pragma unroll
-    for (int j = 0; j < kPairs; ++j) acc[j] = pair_t{0.f, 0.f};
-    auto unpair = [&](float (&dst)[N]) {
-#pragma unroll
-      for (int e = 0; e < N; ++e) dst[e] = (e & 1) ? acc[e / 2].y : acc[e / 2].x;
-    };
-
-    auto note = [&](const int slot, const int64_t row, const int flag) {
-      if (lane_x == 0) {
-        part_row[seg * 2 + slot] = row;
-        part_flags[seg] |= flag;
-      }
-    };
-    auto park_head = [&](const int64_t row) {   // the run that came in from earlier segments ends here
-      float a[N];
-      unpair(a);
-#pragma unroll
-      for (int e = 0; e < N; ++e) part_head[(seg * N + e) * lanes + lane_x] = a[e];
-      note(0, row, kPartHead);
-    };
-    auto fetch_ids = [&](uint32_t (&dst)[K], const int i0) {
-#pragma unroll
-      for (int q = 0; q < K / 4; ++q) {
-        const word4_t v = *reinterpret_cast<const word4_t*>(my_pk + i0 + 4 * q);
-        dst[4 * q + 0] = v.x; dst[4 * q + 1] = v.y; dst[4 * q + 2] = v.z; dst[4 * q + 3] = v.w;
-      }
-    };
-    // rows in flight are held as raw dwords (one register tuple per lookup, re-used by the
-    // request that replaces it), not as N separate elements
-    typedef uint32_t __attribute__((ext_vector_type(sizeof(Pack<GradT, N>) / 4))) raw_t;
-    constexpr uint32_t kSampleMask = kBlocked ? ~(kRunEndBit | kSharedRunBit) : ~kRunEndBit;
-    auto gather = [&](const uint32_t packed) {
-      return *reinterpret_cast<const raw_t*>(RowPtr(lane_src, static_cast<int64_t>(packed & kSampleMask), width));
-    };
-    // Sample-blocked order: a run whose row an earlier block (an earlier launch) already stored is ADDED to it -- a
-    // read-modify-write, not an atomic (13.7 M dword atomics at C4 cost 0.1 ms; the 55 MB they touch are 10 us of
-    // traffic).  The old row is requested TOGETHER with the gather of the run's last lookup, kWindow
-    // lookups ahead of its use, into a register tuple of its own per window slot: loads return in order, so it is
-    // there when that lookup is consumed and the window never drains for it (a read issued at the run's end and
-    // awaited at the next one made the compiler wait for vmcnt(1): 0.177 instead of 0.119 ms per block).
-    raw_t old[kBlocked ? K : 1];
-    auto request_old = [&](const uint32_t packed, const int pos, raw_t& into) {
-      if constexpr (kBlocked) {
-        if ((packed & (kRunEndBit | kSharedRunBit)) == (kRunEndBit | kSharedRunBit))
-          into = *reinterpret_cast<const raw_t*>(
-              RowPtr(lane_dst, static_cast<int64_t>(static_cast<uint32_t>(my_rows[pos]) & id_mask), width));
-      }
-    };
-
-    // kWindow gathers stay in flight for the whole walk: the row of lookup i + K is
-    // requested as soon as the registers of lookup i have been converted (a rolling window, not
-    // load-8 / wait / add-8: the wave's own arithmetic overlaps its own memory latency).
-    raw_t g[K];
-    uint32_t cur[K], nxt[K];
-    fetch_ids(cur, 0);
-#pragma unroll
-    for (int u = 0; u < K; ++u) {
-      g[u] = gather(cur[u]);
-      request_old(cur[u], u, old[kBlocked ? u : 0]);
-    }
-    auto batch = [&](const int i, auto more_tag) {
-      constexpr bool kMore = decltype(more_tag)::value;
-      if constexpr (kMore) fetch_ids(nxt, i + K);
-      GradT w[K];
-      if constexpr (kWeighted) {
-#pragma unroll
-        for (int u = 0; u < K; ++u) w[u] = my_w[i + u];
-      }
-#pragma unroll
-      for (int u = 0; u < K; ++u) {
-        pair_t f[kPairs];
-        const Pack<GradT, N> row_u = __builtin_bit_cast(Pack<GradT, N>, g[u]);
-#pragma unroll
-        for (int e = 0; e < 2 * kPairs; ++e) {
-          float x = 0.f;
-          if (e < N) {
-            x = static_cast<float>(row_u.v[e < N ? e : 0]);
-            if constexpr (kWeighted) x = A::mul(x, static_cast<float>(w[u]));
-          }
-          if (e & 1) f[e / 2].y = x; else f[e / 2].x = x;
-        }
-        if constexpr (kMore) {
-          __builtin_amdgcn_sched_barrier(0);   // the registers of lookup i are free: request i + K into them
-          g[u] = gather(nxt[u]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        {
-#pragma clang fp contract(off)
-#pragma unroll
-          for (int j = 0; j < kPairs; ++j) acc[j] = acc[j] + f[j];
-        }
-        if (static_cast<int32_t>(cur[u]) < 0) {   // kRunEndBit: the run ends with this lookup
-          const uint32_t flagged = static_cast<uint32_t>(my_rows[i + u]);
-          if (first_pending) {
-            park_head(static_cast<int64_t>(flagged));   // its first lookups are in earlier segments
-          } else {
-            GradT* dst = const_cast<GradT*>(RowPtr(lane_dst, static_cast<int64_t>(flagged & id_mask), width));
-            float a[N];
-            unpair(a);
-            if constexpr (kBlocked) {
-              if (flagged & shared_row_bit) {   // an earlier block stored this row: add what it holds
-                const Pack<GradT, N> was = __builtin_bit_cast(Pack<GradT, N>, old[u]);
-#pragma unroll
-                for (int e = 0; e < N; ++e) a[e] = A::add(static_cast<float>(was.v[e]), a[e]);
-              }
-            }
-            FlushStore<GradT, N>(dst, a);
-          }
-          first_pending = false;
-#pragma unroll
-          for (int j = 0; j < kPairs; ++j) asm("v_mov_b64 %0, 0" : "=v"(acc[j]));   // one move per pair
-        }
-        if constexpr (kBlocked && kMore) request_old(nxt[u], i + K + u, old[u]);   // (the slot is free again)
-      }
-      if constexpr (kMore) {
-#pragma unroll
-        for (int u = 0; u < K; ++u) cur[u] = nxt[u];
-      }
-    };
-    int i = 0;
-    for (; i + K < segment_len; i += K) batch(i, std::true_type{});
-    batch(i, std::false_type{});   // the last K lookups: nothing left to request
-    // The segment's last run goes on into the next segment (kPartWhole: it also came in): its
-    // partial stays in registers until every walk of the workgroup is over, then it is parked on
-    // top of the staged ids, which nobody reads any more.
-    if (tail_shared)
-      note(1, static_cast<int64_t>(static_cast<uint32_t>(my_rows[segment_len - 1])), kPartTail | (first_pending ? kPartWhole : 0));
-    __syncthreads();
-    if (tail_shared) {
-      float a[N];
-      unpair(a);
-#pragma unroll
-      for (int e = 0; e < N; ++e) part_tail[(seg * N + e) * lanes + lane_x] = a[e];
-    }
-  }
+  StageSentinels<GradT, IndexT>(st, at, rows, block_row_ids);
   __syncthreads();
-  if (!active) return;
-
-  // ---- chain the parked partials (see 3. above) ----
-  const int flags = part_flags[seg];
-  const int64_t remaining = nnz - block_begin;
-  const int last_seg = static_cast<int>(
-      remaining >= block_len ? segments_per_block - 1 : (remaining + segment_len - 1) / segment_len - 1);
-  auto add_part = [&](float (&sum)[N], int s, int slot) {
-    const float* p = (slot == 0 ? part_head : part_tail) + static_cast<size_t>(s) * N * lanes;
-#pragma unroll
-    for (int e = 0; e < N; ++e) sum[e] = A::add(sum[e], p[e * lanes + lane_x]);
-  };
-  if (flags & kPartHead) {
-    // a run that came in from earlier segments ends in this one
-    float sum[N];
-#pragma unroll
-    for (int e = 0; e < N; ++e) sum[e] = 0.f;
-    int k = seg - 1;
-    while (k >= 0 && (part_flags[k] & kPartWhole)) --k;
-    const bool from_previous_block = k < 0;
-    for (int m = from_previous_block ? 0 : k; m < seg; ++m) add_part(sum, m, 1);
-    add_part(sum, seg, 0);
-    const uint32_t flagged = static_cast<uint32_t>(part_row[seg * 2 + 0]);
-    GradT* dst = lane_dst + static_cast<int64_t>(flagged & id_mask) * width;
-    // (sample-blocked order: an earlier block stored this row -> add to it.  An atomic, not a read-modify-write: this
-    // is the end of the workgroup, a read would be waited for in full, and there is at most one chain per segment)
-    if (from_previous_block || (flagged & shared_row_bit)) FlushAtomic<N>(dst, sum);
-    else FlushStore<GradT, N>(dst, sum);
-  }
-  if ((flags & kPartTail) && seg == last_seg) {
-    // the workgroup's last run goes on into the next workgroup
-    float sum[N];
-#pragma unroll
-    for (int e = 0; e < N; ++e) sum[e] = 0.f;
-    int k = seg;
-    while (k >= 0 && (part_flags[k] & kPartWhole)) --k;
-    for (int m = k < 0 ? 0 : k; m <= seg; ++m) add_part(sum, m, 1);
-    FlushAtomic<N>(lane_dst + static_cast<int64_t>(static_cast<uint32_t>(part_row[seg * 2 + 1]) & id_mask) * width, sum);
-  }
+  if (run_ids != nullptr && cs.slice == 0)
+    NameRuns<GradT, IndexT>(st, at, kBlocked ? ~kSharedRowBit : ~0u, run_ids, inverse_mapping);
+  const int64_t column0 = slice0 + static_cast<int64_t>(at.lane_x) * N;
+  WalkSegment<GradT, N, kWeighted, kBlocked, kWindow>(st, at, grad_y + column0, grad_out + column0, width);
+  __syncthreads();
+  if (at.block_begin + at.seg * segment_len >= nnz) return;   // a segment past the end has nothing parked
+  ChainPartials<GradT, N, kBlocked>(st, at, grad_out + column0, width);
 }
 
 //! Zero-initialisation for a COMPRESSED gradient without touching all of it.  With dense row
@@ -590,8 +639,7 @@ ZeroSharedAndTailRowsKernel(const IndexT* __restrict__ rows, const int64_t nnz, 
                             const int64_t blocks_per_sample_block, const int64_t sample_block_len,
                             const int sample_blocks, const int width, const int64_t num_rows,
                             GradT* __restrict__ grad_out, const uint32_t* __restrict__ block_row_ids,
-                            const int64_t capacity_rows,
-                            const bool pad_tail /* padded gradient: the rows past the last id are zeroed up to num_rows */) {
+                            const int64_t capacity_rows) {
   // sample-blocked order: `rows` holds pair numbers, block_row_ids[pair] the gradient row | kSharedRowBit
   auto row_of = [&](const int64_t g) -> int64_t {
     const uint32_t r = static_cast<uint32_t>(rows[g]);
@@ -628,7 +676,6 @@ ZeroSharedAndTailRowsKernel(const IndexT* __restrict__ rows, const int64_t nnz, 
   char* const p0 = reinterpret_cast<char*>(grad_out + (last_id + 1) * width);
   char* const p1 = reinterpret_cast<char*>(grad_out + num_rows * width);
   if (p0 >= p1) return;
-  (void)pad_tail;   // (the tail's row ids are written after the scatter: NamePaddedRowsKernel)
   char* a0 = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(p0) + 15) & ~uintptr_t{15});
   char* a1 = reinterpret_cast<char*>(reinterpret_cast<uintptr_t>(p1) & ~uintptr_t{15});
   if (a0 > p1) a0 = p1;
@@ -674,6 +721,17 @@ constexpr int kReferenceMaxPer = 2;           //!< rows of a chunk per gather gr
 //! Long-run path: which lane groups of a workgroup chain and which gather.  The wavefront(s) of group 0 run the chain
 //! (ReferenceChainSplit of its groups share it, the rest of that wavefront idles: work of theirs would be executed by
 //! the chain wavefront too); every other group gathers `per` rows of each chunk.
+//! LDS of the long-run path: the rows [2][chunk_rows][width] at 0, their weights [2][chunk_rows] at `weights`; the host
+//! sizes the launch from `bytes`.  ReferenceLongRun budgets kReferenceStageBudget bytes at row_bytes +
+//! kReferenceRowSlack per row and buffer: an element is never larger than the slack, so the budget covers `bytes`.
+struct ReferenceStage { size_t weights, bytes; };
+__host__ __device__ inline ReferenceStage ReferenceStageOf(const int chunk_rows, const size_t row_bytes, const size_t elem_bytes) {
+  const size_t rows = 2 * static_cast<size_t>(chunk_rows) * row_bytes;
+  return ReferenceStage{rows, rows + 2 * static_cast<size_t>(chunk_rows) * elem_bytes};
+}
+constexpr size_t kReferenceStageBudget = size_t{62} << 10;
+constexpr size_t kReferenceRowSlack = 8;
+
 struct ReferenceLongRunShape {
   int chain_groups;   //!< groups in the chain wavefront(s): lanes < 64 -> 64 / lanes, else 1
   int gather_groups;  //!< the rest
@@ -689,7 +747,7 @@ __host__ __device__ inline ReferenceLongRunShape ReferenceLongRun(const size_t r
   if (s.gather_groups < 1) return s;
   // two LDS buffers (+ their weights) within 62 KB -- below the 64 KB a workgroup gets without asking: the barrier and
   // the bookkeeping of a chunk are paid once per chunk, so a chunk should be as long as LDS allows (512-byte rows: 60)
-  const size_t max_rows = (size_t{62} << 10) / (2 * (row_bytes + 8));
+  const size_t max_rows = kReferenceStageBudget / (2 * (row_bytes + kReferenceRowSlack));
   s.per = static_cast<int>(max_rows / static_cast<size_t>(s.gather_groups));
   if (s.per > kReferenceMaxPer) s.per = kReferenceMaxPer;
   if (s.per < 1) return s;
@@ -952,7 +1010,8 @@ ReferenceSumsScatterKernel(const GradT* __restrict__ grad_y, const int width, co
   const bool gathers = static_cast<int>(threadIdx.y) >= shape.chain_groups;
   const int gi = static_cast<int>(threadIdx.y) - shape.chain_groups;      // this gather group's number
   GradT* stage = reinterpret_cast<GradT*>(reference_lds);      // [2][chunk_rows][width]
-  GradT* stage_w = stage + 2 * static_cast<size_t>(chunk_rows) * width;   // [2][chunk_rows]
+  GradT* stage_w = reinterpret_cast<GradT*>(   // [2][chunk_rows]
+      reference_lds + ReferenceStageOf(chunk_rows, static_cast<size_t>(width) * sizeof(GradT), sizeof(GradT)).weights);
   GradT* dst = grad_out + static_cast<int64_t>(row) * width + chain_column;
   Pack<GradT, N> sum;                        // the chain's state lives in GradT: it is rounded to it at every step anyway
 #pragma unroll                               // (its first N / split elements are this lane's)

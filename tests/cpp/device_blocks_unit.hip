@@ -10,7 +10,12 @@
 //   * WalkSample                     : every lookup of a thread's sample handed to the callback exactly once and IN ORDER,
 //                                      for the three index sources, fixed hotness and CSR bags of 0 .. 2 x group + 1
 //                                      lookups, with a sample order, a partial last workgroup;
-//   * AccumulateRow                  : the backward's fp32 partial sums of fp16 rows, weighted and not;
+//   * RunSum::Accumulate             : the per-lookup arithmetic of the backward's walk -- fp32 partial sums of fp16 rows,
+//                                      weighted and not;
+//   * StageLookups / StageSentinels / WalkSegment / ChainPartials over one ScatterStage: what the backward's staging
+//                                      leaves in LDS (row ids, sentinels, run-end bits, weights) and what the walk and the
+//                                      chaining of parked partials make of a run through three segments and of one into the
+//                                      next workgroup;
 //   * PackRowsByOwner / FinishOwnerPiece (exchange_transforms.hpp, the header API itself): range starts, slots, padding
 //                                      ids, untouched slack, the flag word; the piece's count, zeroed row, tail.
 // Small kernels instantiate the blocks directly (one wavefront each); the host recomputes with the same
@@ -318,15 +323,16 @@ static void Walks(const char* name) {
 // ---- the backward's partial sums -------------------------------------------------------------------------------------
 template <typename GradT, int N, bool kWeighted>
 __global__ void AccumulateKernel(const GradT* rows, const float* weights, const int count, float* out) {
-  float acc[N];
-#pragma unroll
-  for (int e = 0; e < N; ++e) acc[e] = 0.f;
+  RunSum<GradT, N, kWeighted> sum;      // what the walk of SegmentedScatterAddKernel keeps per run
+  sum.Zero();
   for (int j = 0; j < count; ++j) {
     Pack<GradT, N> row;
 #pragma unroll
     for (int e = 0; e < N; ++e) row.v[e] = rows[j * N + e];
-    AccumulateRow<GradT, N, kWeighted>(acc, row, weights[j]);
+    sum.Accumulate(row, static_cast<GradT>(weights[j]));    // (the weights are GradT values held as float)
   }
+  float acc[N];
+  sum.Unpair(acc);
 #pragma unroll
   for (int e = 0; e < N; ++e) out[e] = acc[e];
 }
@@ -353,6 +359,98 @@ static void BackwardPartialSums(const char* name) {
       acc = Arith<float>::add(acc, kWeighted ? Arith<float>::mul(x, weights[j]) : x);
     }
     CHECK(SameBits(got[e], acc), "%s: element %d: %g, host %g", name, e, got[e], acc);
+  }
+}
+
+// ---- the backward's staging and chaining ---------------------------------------------------------------------------------
+// ONE workgroup of three segments of 8 lookups (two lanes of two fp32 elements, weighted) runs the phases of
+// SegmentedScatterAddKernel on the first 24 of 30 sorted lookups: what the staging left in LDS is copied out, the walk
+// and the chaining write the gradient.  Runs: [0, 3) inside segment 0; [3, 21) through all three segments (a tail
+// partial, a whole segment, a head partial); [21, 22); [22, 28) into the next workgroup (an atomic onto zero).
+constexpr int kStageLanes = 2, kStageN = 2, kStageSegments = 3, kStageSegmentLen = 8, kStageNnz = 30;
+
+template <int kWindow>
+__global__ void StageChainKernel(const float* __restrict__ grad_y, const int width, const int* __restrict__ rows,
+                                 const int* __restrict__ sample_ids, const float* __restrict__ weights,
+                                 float* __restrict__ grad_out, int32_t* seen_rows, uint32_t* seen_packed,
+                                 float* seen_weights) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char stage_lds[];
+  const ScatterPlace at{static_cast<int>(threadIdx.x), kStageLanes, static_cast<int>(threadIdx.y), kStageSegments,
+                        kStageSegmentLen, 3, kStageSegments * kStageSegmentLen, 0, kStageNnz};
+  const ScatterStageView<float> st(stage_lds, ScatterStage::Of(kStageSegments, kStageSegmentLen, kStageLanes, kStageN, true, 4));
+  StageLookups<float, int, true, false>(st, at, rows, sample_ids, weights, nullptr);
+  if (at.lane_x == 0) st.flags[at.seg] = 0;
+  __syncthreads();
+  StageSentinels<float, int>(st, at, rows, nullptr);
+  __syncthreads();
+  if (at.lane_x == 0) {
+    for (int i = 0; i < st.row_stride; ++i) seen_rows[at.seg * st.row_stride + i] = st.rows[at.seg * st.row_stride + i];
+    for (int i = 0; i < kStageSegmentLen; ++i) {
+      seen_packed[at.seg * kStageSegmentLen + i] = st.packed[at.seg * st.packed_stride + i];
+      seen_weights[at.seg * kStageSegmentLen + i] = st.weights[at.seg * st.row_stride + i];
+    }
+  }
+  const int column0 = at.lane_x * kStageN;
+  WalkSegment<float, kStageN, true, false, kWindow>(st, at, grad_y + column0, grad_out + column0, width);
+  __syncthreads();
+  ChainPartials<float, kStageN, false>(st, at, grad_out + column0, width);
+}
+
+template <int kWindow>
+static void StagingAndChaining(const char* name) {
+  using A = Arith<float>;
+  const int width = kStageLanes * kStageN, batch = 16, len = kStageSegmentLen, in_block = kStageSegments * len;
+  std::mt19937 rng(23);
+  std::uniform_real_distribution<float> val(-3.f, 3.f), wgt(0.f, 1.f);
+  std::vector<int> rows(kStageNnz), sids(kStageNnz);
+  std::vector<float> weights(kStageNnz), grad_y(static_cast<size_t>(batch) * width);
+  for (int g = 0; g < kStageNnz; ++g) {
+    rows[g] = g < 3 ? 0 : g < 21 ? 1 : g < 22 ? 2 : g < 28 ? 3 : 4;
+    sids[g] = static_cast<int>(rng() % batch);
+    weights[g] = wgt(rng);
+  }
+  for (auto& x : grad_y) x = val(rng);
+  std::vector<float> before(5 * width, 7.f);
+  for (int c = 0; c < width; ++c) before[3 * width + c] = 0.f;       // the row that receives the atomic
+  const ScatterStage layout = ScatterStage::Of(kStageSegments, len, kStageLanes, kStageN, true, 4);
+  CHECK(layout.tail_partials == layout.rows && layout.head_partials >= layout.weights + kStageSegments * (len + 2) * 4 &&
+            layout.bytes >= layout.flags + kStageSegments * 4,
+        "%s: the regions of the stage overlap", name);
+  const DeviceArray<float> d_gy(grad_y), d_w(weights);
+  const DeviceArray<int> d_rows(rows), d_sids(sids);
+  DeviceArray<float> d_out(before), d_seen_w(in_block);
+  DeviceArray<int32_t> d_seen_rows(kStageSegments * (len + 2));
+  DeviceArray<uint32_t> d_seen_pk(in_block);
+  StageChainKernel<kWindow><<<1, dim3(kStageLanes, kStageSegments, 1), layout.bytes>>>(
+      d_gy.ptr, width, d_rows.ptr, d_sids.ptr, d_w.ptr, d_out.ptr, d_seen_rows.ptr, d_seen_pk.ptr, d_seen_w.ptr);
+  HIP_OK(hipDeviceSynchronize());
+  const auto seen_rows = d_seen_rows.Download();
+  const auto seen_pk = d_seen_pk.Download();
+  const auto seen_w = d_seen_w.Download();
+  const auto got = d_out.Download();
+  for (int s = 0; s < kStageSegments; ++s)
+    for (int i = -1; i <= len; ++i) {        // the lookup before the segment, its own, the lookup after
+      const int g = s * len + i;
+      const int want = g < 0 ? -1 : rows[g];
+      CHECK(seen_rows[s * (len + 2) + 1 + i] == want, "%s: staged row %d of segment %d is %d, host %d", name, i, s,
+            seen_rows[s * (len + 2) + 1 + i], want);
+    }
+  for (int g = 0; g < in_block; ++g) {
+    const uint32_t want = static_cast<uint32_t>(sids[g]) | (rows[g + 1] != rows[g] ? kRunEndBit : 0u);
+    CHECK(seen_pk[g] == want, "%s: staged sample id %d is %08x, host %08x", name, g, seen_pk[g], want);
+    CHECK(SameBits(seen_w[g], weights[g]), "%s: staged weight %d", name, g);
+  }
+  // the sum of lookups [from, to) in nz order, starting from zero: what a segment holds for a run, or parks
+  const auto part = [&](const int from, const int to, const int c) {
+    float acc = 0.f;
+    for (int g = from; g < to; ++g) acc = A::add(acc, A::mul(grad_y[static_cast<size_t>(sids[g]) * width + c], weights[g]));
+    return acc;
+  };
+  for (int c = 0; c < width; ++c) {
+    const float chained = A::add(A::add(A::add(0.f, part(3, 8, c)), part(8, 16, c)), part(16, 21, c));
+    const float want[5] = {part(0, 3, c), chained, part(21, 22, c), A::add(0.f, part(22, 24, c)), 7.f};
+    for (int r = 0; r < 5; ++r)
+      CHECK(SameBits(got[r * width + c], want[r]), "%s: row %d column %d: %g, host %g", name, r, c, got[r * width + c], want[r]);
   }
 }
 
@@ -473,6 +571,8 @@ int main() {
   BackwardPartialSums<_Float16, 8, false>("fp16 grad_y rows, fp32 partial sums");
   BackwardPartialSums<_Float16, 8, true>("fp16 grad_y rows x weight, fp32 partial sums");
   BackwardPartialSums<float, 4, true>("fp32 grad_y rows x weight");
+  StagingAndChaining<4>("stage and chain, window of 4");
+  StagingAndChaining<8>("stage and chain, window of 8");
   ExchangePack<int32_t>("pack: 8 owners, i32 ids", 8, 5000, 700, -1, 16);
   ExchangePack<int64_t>("pack: 3 owners, i64 ids, a device-side count", 3, 4000, 1500, 3100, 5);
   ExchangePack<int64_t>("pack: a slot that overflows", 4, 3000, 600, -1, 8);

@@ -2,7 +2,8 @@
 of the reference's tests/test_embedding_ops.cu:121-374 (Addresser, Combiner, IndexLoader, GradAddresser, GradCombiner unit
 tests) for the blocks this design is made of -- WidenIndex / RowElems / RowPtr, ColumnSlice, Pack + Arith + RowPool (Add,
 Gather around every unroll / pipelining boundary, both load kinds), FinishPooledRow (mean, empty bag), WalkSample (every
-lookup of a thread's sample handed over once and in order, for the three index sources), AccumulateRow --
+lookup of a thread's sample handed over once and in order, for the three index sources), the backward's RunSum (the
+per-lookup arithmetic of its walk) and its staging, walk and chaining of parked partials over one ScatterStage --
 each instantiated in a small kernel and compared bit for bit with the same single-rounding operations on the host."""
 import subprocess
 

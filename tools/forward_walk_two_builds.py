@@ -9,7 +9,7 @@ the two sides' spreads (max - min over the rounds).
 
     python tools/forward_walk_two_builds.py OTHER_LIBCUEMBED_AMD_SO [--out FILE]
 """
-import ctypes, json, os, sys
+import json, os, sys
 import numpy as np
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,38 +17,19 @@ if len(sys.argv) < 2:
     sys.exit(__doc__)
 sys.path.insert(0, ROOT)
 import cuembed_amd as ce
-from cuembed_amd import _lib, harness
+from cuembed_amd import harness
 import bench
-import benchmarks.quantized_forward_benchmark as B
+from tools import two_builds
 
-new = _lib.lib()
-par = ctypes.CDLL(os.path.abspath(sys.argv[1]))
-_lib._declare(par)
-LIBS = {"parent": par, "new": new}      # "parent": the other build; "new": this tree's
+LIBS = two_builds.load(sys.argv[1])     # "parent": the other build; "new": this tree's
 CALLS, ROUNDS, WARMUP = 100, 9, 5
 dev = torch.device("cuda")
 out = {"tool": "tools/forward_walk_two_builds.py", "device": torch.cuda.get_device_name(0), "calls_per_round": CALLS,
-       "rounds": ROUNDS, "criterion": "|median(new) - median(parent)| <= max(spread(new), spread(parent))", "shapes": {}}
+       "rounds": ROUNDS, "criterion": two_builds.CRITERION, "shapes": {}}
 
 
 def compare(key, call, result):
-    def side(name):
-        def fn():
-            _lib._lib = LIBS[name]
-            call()
-        return fn
-    bits = {}
-    for name in LIBS:                    # the two builds compute the same bits
-        side(name)()
-        bits[name] = result.clone()
-    assert torch.equal(bits["parent"].view(torch.uint8), bits["new"].view(torch.uint8)), key
-    got = B.alternate(torch, {"parent": side("parent"), "new": side("new")}, CALLS, ROUNDS, WARMUP)
-    _lib._lib = new
-    got["difference_of_medians_ms"] = got["new"]["ms"] - got["parent"]["ms"]
-    got["accepted"] = abs(got["difference_of_medians_ms"]) <= max(got["new"]["spread"], got["parent"]["spread"])
-    out["shapes"][key] = got
-    print(key, {k: (round(s["ms"], 4), round(s["spread"], 4)) for k, s in got.items() if isinstance(s, dict)},
-          "accepted" if got["accepted"] else "BEYOND THE SPREAD", flush=True)
+    two_builds.compare(LIBS, out["shapes"], key, call, result, CALLS, ROUNDS, WARMUP)
 
 
 ncat, W, H, batch = 10_000_000, 256, 64, 65536

@@ -5,20 +5,18 @@ five rules").  Each side swaps the loaded library under cuembed_amd.ops and make
 
     python tools/optimizer_step_two_builds.py OTHER_LIBCUEMBED_AMD_SO [--out FILE]
 """
-import ctypes, json, os, sys
+import json, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if len(sys.argv) < 2:
     sys.exit(__doc__)
 sys.path.insert(0, ROOT)
 import cuembed_amd as ce
-from cuembed_amd import _lib, harness
+from cuembed_amd import harness
 import benchmarks.optimizer_step_benchmark as B
+from tools import two_builds
 
-new = _lib.lib()
-par = ctypes.CDLL(os.path.abspath(sys.argv[1]))
-_lib._declare(par)
-LIBS = {"parent": par, "new": new}      # "parent": the other build; "new": this tree's
+LIBS = two_builds.load(sys.argv[1])     # "parent": the other build; "new": this tree's
 ncat, W, H, batch = 10_000_000, 256, 64, 65536
 dev = torch.device("cuda")
 out = {"device": torch.cuda.get_device_name(0), "calls_per_round": 100, "rounds": 5, "sides": {}}
@@ -43,13 +41,7 @@ for dtype, rule, stochastic in ((torch.float32, "adagrad", False), (torch.float1
         state = torch.zeros((ncat, W) if rule == "adagrad" else (ncat,), dtype=torch.float32, device=dev)
         call = lambda: ce.sparse_row_update(table, ids, rows, rule=rule, lr=1e-3, state=state, last_id=last_id, **kw)
 
-    def side(name):
-        def fn():
-            _lib._lib = LIBS[name]
-            call()
-        return fn
-    got = B.alternate(torch, {"parent": side("parent"), "new": side("new")}, 100, 5, 5)
-    _lib._lib = new
+    got = two_builds.alternate(LIBS, call, 100, 5, 5)
     key = "C4 %s %s%s" % (str(dtype).replace("torch.", ""), rule, " stochastic" if stochastic else "")
     got["separable"] = B.faster(got["parent"], got["new"]) or B.faster(got["new"], got["parent"])
     out["sides"][key] = got
