@@ -1,0 +1,173 @@
+#!/usr/bin/env python3
+"""Times the forward on a HOST-resident fp16 table (pinned memory, read over PCIe) four ways on one GPU:
+
+    (a) host        CachedHostTable.forward(use_cache=False): every row over PCIe
+    (b) static      CachedHostTable with cache_most_frequent() computed ONCE, on the first epoch's indices
+    (c) dynamic     DynamicRowCache.forward in steady state: prefetch (sort, probe, place, row exchange) + translate +
+                    forward, every step
+    (d) device      embedding_forward on a device-resident copy of the table (what the cache can at best approach)
+
+The index stream is a power law (alpha = 1.15, the reference generator's inverse-CDF recipe, drawn on the device) over
+ranks; rank -> row is an affine permutation whose shift is RE-DRAWN every `--redraw` steps, so the hot set moves: (b)'s
+rows go cold after the first epoch, (c) follows.  Every side walks the same pre-generated batches in the same order.
+
+Per side: `--rounds` rounds of one pass over all `--steps` batches, one pair of device events around the pass; the
+figure is ms per step, median and min over the rounds with the spread (max - min) next to it.  A side is called faster
+only when its slowest round beats the other's fastest.  Hit rates: (c) from the cache's device counters over the timed
+passes (distinct rows), (b) from slot_of_row per epoch (lookups).
+
+    python benchmarks/dynamic_row_cache_benchmark.py --out profiles/dynamic_row_cache_timing.json [--commit ID]
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def power_law_ranks(torch, rows, count, alpha, generator):
+    """Ranks in [0, rows) with P(rank) ~ (rank + 1) ** -alpha: x = (u * (rows ** (1 - alpha) - 1) + 1) ** (1 / (1 -
+    alpha)), rank = floor(x) - 1 (the reference generator's recipe, in float64 on the device)."""
+    u = torch.rand((count,), dtype=torch.float64, device="cuda", generator=generator)
+    x = (u * (float(rows) ** (1.0 - alpha) - 1.0) + 1.0) ** (1.0 / (1.0 - alpha))
+    return (x.floor().long() - 1).clamp_(0, rows - 1)
+
+
+def make_batches(torch, a):
+    """`steps` batches [batch, hotness] int32; the rank -> row shift changes every `redraw` steps."""
+    g = torch.Generator(device="cuda")
+    g.manual_seed(a.seed)
+    stride = 2_654_435_761 % a.rows | 1          # odd; rows is checked to be a power of two, so this is a permutation
+    batches, shifts = [], []
+    for step in range(a.steps):
+        if step % a.redraw == 0:
+            shifts.append(int(torch.randint(0, a.rows, (1,), generator=g, device="cuda").item()))
+        ranks = power_law_ranks(torch, a.rows, a.batch * a.hotness, a.alpha, g)
+        batches.append(((ranks * stride + shifts[-1]) % a.rows).to(torch.int32).reshape(a.batch, a.hotness))
+    return batches
+
+
+def time_pass(torch, fn, batches):
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for idx in batches:
+        fn(idx)
+    stop.record()
+    stop.synchronize()
+    return start.elapsed_time(stop) / len(batches)
+
+
+def summarise(v):
+    return dict(ms=statistics.median(v), min=min(v), max=max(v), spread=max(v) - min(v), rounds=v)
+
+
+def commit_id(given):
+    if given:
+        return given
+    try:
+        return subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stdout=subprocess.PIPE,
+                              stderr=subprocess.DEVNULL, text=True, check=True).stdout.strip()
+    except Exception:  # noqa: BLE001 - a source tree without its history
+        return "unknown"
+
+
+def main():
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--rows", type=int, default=1 << 22, help="table rows (a power of two)")
+    p.add_argument("--width", type=int, default=128)
+    p.add_argument("--batch", type=int, default=16384)
+    p.add_argument("--hotness", type=int, default=32)
+    p.add_argument("--num_sets", type=int, default=4096, help="sets of 64 ways: the cache holds 64 * num_sets rows")
+    p.add_argument("--alpha", type=float, default=1.15)
+    p.add_argument("--steps", type=int, default=40, help="batches per pass")
+    p.add_argument("--redraw", type=int, default=10, help="the hot set is re-drawn every this many steps")
+    p.add_argument("--rounds", type=int, default=5)
+    p.add_argument("--seed", type=int, default=1)
+    p.add_argument("--out", default=None, help="write the JSON here as well")
+    p.add_argument("--commit", default=None, help="commit the tree was built from (default: git rev-parse)")
+    a = p.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("dynamic_row_cache_benchmark: needs a GPU (there is nothing to time without one)")
+    if a.rows & (a.rows - 1):
+        sys.exit("--rows must be a power of two (the rank -> row map is an affine permutation mod rows)")
+    import cuembed_amd as ce
+    from cuembed_amd.row_cache import CachedHostTable, DynamicRowCache
+
+    torch.manual_seed(a.seed)
+    device_table = torch.empty((a.rows, a.width), dtype=torch.float16, device="cuda").uniform_(-1, 1)
+    host_table = torch.empty((a.rows, a.width), dtype=torch.float16).pin_memory()
+    host_table.copy_(device_table)
+    batches = make_batches(torch, a)
+    capacity = 64 * a.num_sets
+    static = CachedHostTable(host_table, "cuda", capacity_rows=capacity)
+    static.cache_most_frequent(torch.cat([b.reshape(-1) for b in batches[:a.redraw]]))
+    dynamic = DynamicRowCache(host_table, "cuda", num_sets=a.num_sets)
+    out = torch.empty((a.batch, a.width), dtype=torch.float16, device="cuda")
+    sides = {
+        "host": lambda idx: static.forward(idx, num_hots=a.hotness, use_cache=False, out=out),
+        "static": lambda idx: static.forward(idx, num_hots=a.hotness, out=out),
+        "dynamic": lambda idx: dynamic.forward(idx, num_hots=a.hotness, out=out),
+        "device": lambda idx: ce.embedding_forward(device_table, idx, num_hots=a.hotness, out=out),
+    }
+    # every side gives the device table's bits
+    want = ce.embedding_forward(device_table, batches[0], num_hots=a.hotness)
+    for name, fn in sides.items():
+        assert torch.equal(fn(batches[0]), want), name
+    # warm-up: one pass each (the dynamic cache reaches its steady state: the pass ends where the next one begins)
+    for fn in sides.values():
+        time_pass(torch, fn, batches)
+    before = dynamic.stats()
+    samples = {name: [] for name in sides}
+    for _ in range(a.rounds):
+        for name, fn in sides.items():
+            samples[name].append(time_pass(torch, fn, batches))
+    after = dynamic.stats()
+    got = {name: summarise(v) for name, v in samples.items()}
+
+    distinct = (after["hits"] - before["hits"]) + (after["misses"] - before["misses"])
+    dynamic_rates = dict(distinct_rows_per_step=distinct / (a.rounds * a.steps),
+                         hit_rate_of_distinct_rows=(after["hits"] - before["hits"]) / max(distinct, 1),
+                         evictions_per_step=(after["evictions"] - before["evictions"]) / (a.rounds * a.steps),
+                         unplaced_per_step=(after["unplaced"] - before["unplaced"]) / (a.rounds * a.steps))
+    lookup_hits = {"static": [], "dynamic_after_prefetch": []}
+    for epoch in range(0, a.steps, a.redraw):
+        idx = batches[epoch + a.redraw // 2].reshape(-1).long()
+        lookup_hits["static"].append(float((static.slot_of_row[idx] >= 0).float().mean()))
+        dynamic.prefetch(batches[epoch + a.redraw // 2])
+        lookup_hits["dynamic_after_prefetch"].append(float((dynamic.slot_of_row[idx] >= 0).float().mean()))
+
+    def faster(x, y):
+        return got[x]["max"] < got[y]["min"]
+
+    report = dict(tool="benchmarks/dynamic_row_cache_benchmark.py", commit=commit_id(a.commit),
+                  device=torch.cuda.get_device_name(0), torch=torch.__version__,
+                  shape=dict(rows=a.rows, width=a.width, dtype="float16", batch=a.batch, hotness=a.hotness, alpha=a.alpha,
+                             steps_per_pass=a.steps, hot_set_redrawn_every=a.redraw, cache_rows=capacity,
+                             num_sets=a.num_sets, table_bytes=a.rows * a.width * 2, cache_bytes=capacity * a.width * 2),
+                  rounds=a.rounds, ms_per_step=got, dynamic_cache=dynamic_rates, share_of_lookups_served_from_hbm=lookup_hits,
+                  dynamic_over_host=got["dynamic"]["ms"] / got["host"]["ms"],
+                  dynamic_over_device=got["dynamic"]["ms"] / got["device"]["ms"],
+                  dynamic_over_static=got["dynamic"]["ms"] / got["static"]["ms"],
+                  dynamic_faster_than_host_beyond_the_spread=faster("dynamic", "host"),
+                  host_faster_than_dynamic_beyond_the_spread=faster("host", "dynamic"),
+                  dynamic_faster_than_static_beyond_the_spread=faster("dynamic", "static"),
+                  static_faster_than_dynamic_beyond_the_spread=faster("static", "dynamic"))
+    for name in sides:
+        print("%-8s %.4f ms / step (min %.4f, spread %.4f)" % (name, got[name]["ms"], got[name]["min"], got[name]["spread"]),
+              flush=True)
+    text = json.dumps(report, indent=1)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    print(json.dumps(dict(summary={k: got[k]["ms"] for k in got}, dynamic=dynamic_rates,
+                          dynamic_over_host=report["dynamic_over_host"], dynamic_over_device=report["dynamic_over_device"])))
+
+
+if __name__ == "__main__":
+    main()

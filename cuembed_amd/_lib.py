@@ -86,6 +86,16 @@ def _declare(L):
     L.cuembed_translate_indices_for_row_cache.restype = None
     L.cuembed_translate_indices_for_row_cache.argtypes = [_VP, _I, ctypes.c_int64, _VP, ctypes.c_int64, ctypes.c_int64,
                                                           _VP, _VP]
+    _cache = [_VP, _VP, ctypes.c_int64, ctypes.c_int64, _I, _VP, _VP, _VP, _VP, _VP]
+    L.cuembed_row_cache_workspace_bytes.restype = ctypes.c_size_t
+    L.cuembed_row_cache_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, _I]
+    L.cuembed_row_cache_prefetch.restype = None
+    L.cuembed_row_cache_prefetch.argtypes = _cache + [_VP, _I, ctypes.c_int64, ctypes.c_int64, _VP, _I, _VP, _I, _VP,
+                                                      ctypes.POINTER(ctypes.c_size_t), _VP]
+    L.cuembed_row_cache_flush.restype = None
+    L.cuembed_row_cache_flush.argtypes = _cache + [_VP]
+    L.cuembed_cache_set_of.restype = _I
+    L.cuembed_cache_set_of.argtypes = [ctypes.c_int64, _I]
     L.cuembed_compute_compressed_grad_indices.restype = None
     L.cuembed_compute_compressed_grad_indices.argtypes = [_VP, _I, _I, _VP, _VP,
                                                           ctypes.POINTER(ctypes.c_size_t), _VP]

@@ -23,7 +23,7 @@ OBJ_DIR = os.path.join(PKG, "build")
 UNITS = ["c_api_forward.hip", "c_api_backward.hip", "c_api_transforms.hip", "c_api_exchange.hip",
          "c_api_optimizer.hip", "c_api_optimizer_stochastic.hip", "c_api_optimizer_adam.hip",
          "c_api_optimizer_adam_stochastic.hip", "c_api_quantized.hip", "c_api_grouped.hip",
-         "c_api_grouped_backward.hip"]
+         "c_api_grouped_backward.hip", "c_api_row_cache.hip"]
 ARCH = "gfx950"
 
 HIPCC_FLAGS = [

@@ -12,7 +12,15 @@ params + int64(index) * width, so an index of (cache_rows - params) / width + sl
 rewritten with one small kernel (slot_of_row[] lookup) and the unmodified forward kernel then reads
 cached rows from HBM and only the others over PCIe.  Results are bit-identical to running on the
 table itself as long as the cached copies are current: there is no staleness guard, the caller must
-call refresh() after updating table rows.  Lookup indices outside the table are passed through untouched."""
+call refresh() after updating table rows.  Lookup indices outside the table are passed through untouched.
+
+DynamicRowCache (below) is the cache that manages itself: set-associative, LRU, write-back, filled and evicted on the
+device from each batch's own indices, so that a host-resident table can be read AND trained with no host read-back:
+
+    cache = DynamicRowCache(table, device="cuda:0", num_sets=16384)              # 64 ways per set: 1,048,576 rows
+    out = cache.forward(indices, num_hots=64)                                    # prefetch + translate + forward
+    cache.apply_sgd(inverse_mapping, grad_embedding, lr=0.1, last_id=remapped[-1:])   # sparse SGD step through the cache
+    cache.flush()                                                                # dirty rows back to the host table"""
 import ctypes
 
 import torch
@@ -115,3 +123,209 @@ class CachedHostTable:
                     _ops._ptr(offsets), ot, _ops._ptr(weights), batch_size, num_hots, m, 0, _ops._ptr(out),
                     _ops._stream(idx))
         return out
+
+
+WAYS = 64    # cuembed::kRowCacheWays: one wavefront owns one set, lane = way
+_MASK64 = (1 << 64) - 1
+_MIX1, _MIX2 = 0x9E3779B97F4A7C15, 0xD6E8FEB86659FD93
+#: names of the cache's device words (cuembed::RowCacheWord), in order
+STAT_WORDS = ("clock", "hits", "misses", "evictions", "write_backs", "unplaced", "moves", "batch_count", "overflow")
+
+
+def cache_set_of(row, num_sets):
+    """The set of a table row (cuembed::CacheSetOf, mirrored on the host): two multiply / xor-shift rounds of the 64-bit
+    row id, reduced to [0, num_sets) by multiply-shift, so num_sets need not be a power of two:
+
+        h = row * 0x9E3779B97F4A7C15;  h ^= h >> 32;  h *= 0xD6E8FEB86659FD93;  h ^= h >> 32      (mod 2**64)
+        set = ((h >> 32) * num_sets) >> 32
+
+    `row`: an int (returns an int) or anything numpy makes an integer array of (returns an int64 array)."""
+    num_sets = int(num_sets)
+    if not 1 <= num_sets <= 1 << 24:
+        raise ValueError("num_sets must be in [1, 2**24], got %d" % num_sets)
+    if isinstance(row, int):
+        h = ((row & _MASK64) * _MIX1) & _MASK64
+        h ^= h >> 32
+        h = (h * _MIX2) & _MASK64
+        h ^= h >> 32
+        return ((h >> 32) * num_sets) >> 32
+    import numpy as np
+    h = np.asarray(row).astype(np.int64).astype(np.uint64) * np.uint64(_MIX1)      # (array arithmetic wraps mod 2**64)
+    h ^= h >> np.uint64(32)
+    h *= np.uint64(_MIX2)
+    h ^= h >> np.uint64(32)
+    return (((h >> np.uint64(32)) * np.uint64(num_sets)) >> np.uint64(32)).astype(np.int64)
+
+
+class DynamicRowCache(CachedHostTable):
+    """Device-managed cache of a host-resident table: `num_sets` sets of 64 ways (capacity_rows = 64 * num_sets) in HBM,
+    LRU per set, write-back.  All state lives on the device -- tags int64 [S, 64] (-1 = empty), stamps uint32 [S, 64]
+    (0 = never used), dirty uint8 [S, 64], slot_of_row int32 [rows], a clock word (first value 1) and counter words --
+    and every call but stats() is stream-ordered with no host read-back.
+
+    prefetch(indices, for_update=False), with t the clock and D the distinct rows of `indices` inside [0, rows):
+      1. hits first: every resident row of D gets stamp = t; a row of this batch is never evicted by this batch;
+      2. then the misses of each set (cache_set_of) in ascending row id: each takes the way with the smallest
+         (stamp, way) among ways with stamp < t; if there is none the row stays uncached and `unplaced` goes up by one;
+      3. placing a row: a valid dirty victim is stored to the host table, slot_of_row[old] = -1, the new row is loaded
+         host -> cache, tag / stamp / slot_of_row are set and dirty = for_update;
+      4. for_update=True marks resident hits dirty too;
+      5. clock += 1.
+    Indices outside the table are ignored by prefetch and passed through by translate.
+
+    A set holds at most 64 rows of one batch: size the cache so that no set sees more; rows that
+    do not fit are served from the host table over PCIe -- reads and updates alike -- so nothing is ever wrong or lost,
+    only slower, and stats()["unplaced"] says how often.
+
+    The cached copy of a dirty row is the only current one: read the host table only after flush() and a synchronise."""
+
+    def __init__(self, host_table, device="cuda", num_sets=1024):
+        if not isinstance(host_table, torch.Tensor):
+            raise TypeError("host_table must be a torch.Tensor")
+        if host_table.dtype not in _ops._ELEM:
+            raise TypeError("table must be float32, float16 or bfloat16")
+        if isinstance(num_sets, bool) or not isinstance(num_sets, int):
+            raise TypeError("num_sets must be an int")
+        if not 1 <= num_sets <= 1 << 24:
+            raise ValueError("num_sets must be in [1, 2**24], got %d" % num_sets)
+        if host_table.dim() != 2 or not host_table.is_contiguous() or host_table.shape[0] < 1:
+            raise ValueError("host_table must be a contiguous 2-D tensor with at least one row")
+        if (host_table.shape[1] * host_table.element_size()) % 4:
+            raise ValueError("row size must be a multiple of 4 bytes")
+        if host_table.is_cuda or not host_table.is_pinned():
+            raise ValueError("host_table must live in PINNED host memory (tensor.pin_memory())")
+        super().__init__(host_table, device=device, capacity_rows=WAYS * num_sets)
+        self.num_sets = num_sets
+        self.capacity_rows = WAYS * num_sets
+        self.row_bytes = self.width * host_table.element_size()
+        self.tags = torch.full((num_sets, WAYS), -1, dtype=torch.int64, device=self.device)
+        self.stamps = torch.zeros((num_sets, WAYS), dtype=torch.int32, device=self.device).view(torch.uint32)
+        self.dirty = torch.zeros((num_sets, WAYS), dtype=torch.uint8, device=self.device)
+        self.words = torch.tensor([1] + [0] * 15, dtype=torch.int64).to(self.device)
+        self._work = None
+
+    # the caller-managed policy of the base class would bypass tags / stamps / dirty
+    def cache_rows(self, row_ids):
+        raise RuntimeError("DynamicRowCache fills itself from the batches it sees: use prefetch() / forward()")
+
+    cache_most_frequent = cache_rows
+
+    def refresh(self):
+        raise RuntimeError("DynamicRowCache is write-back: use flush() / invalidate()")
+
+    def _state(self):
+        p = ctypes.c_void_p
+        return (p(self.table.data_ptr()), p(self.cache.data_ptr()), self.row_bytes, self.rows, self.num_sets,
+                p(self.tags.data_ptr()), p(self.stamps.data_ptr()), p(self.dirty.data_ptr()),
+                p(self.slot_of_row.data_ptr()), p(self.words.data_ptr()))
+
+    def _counts(self, ids, count, last_id):
+        """(num_valid, count word, word is int64, last_id word) of a prefetch, validated."""
+        if count is not None and last_id is not None:
+            raise ValueError("give at most one of count= and last_id=")
+        n = ids.numel()
+        if isinstance(count, torch.Tensor):
+            if count.dtype not in _ops._INDEX or count.numel() != 1:
+                raise TypeError("count must be an int or a one-element int32 / int64 tensor")
+            _ops._check_dev("count", count, self.device)
+            return -1, count, count.dtype == torch.int64, None
+        if last_id is not None:
+            if not isinstance(last_id, torch.Tensor) or last_id.dtype != ids.dtype or last_id.numel() != 1:
+                raise TypeError("last_id must be a one-element tensor of the indices' dtype")
+            _ops._check_dev("last_id", last_id, self.device)
+            return -1, None, False, last_id
+        num_valid = n if count is None else int(count)
+        if not 0 <= num_valid <= n:
+            raise ValueError("count must be in [0, indices.numel()]")
+        return num_valid, None, False, None
+
+    def prefetch(self, indices, for_update=False, count=None, last_id=None):
+        """Make the rows that `indices` (int32 / int64 device tensor, any shape) name resident -- the contract is in the
+        class docstring.  Only the first `count` entries (an int, or a one-element device tensor) or last_id + 1 entries
+        (a one-element device tensor of the indices' dtype) count; default: all.  Returns None; no read-back."""
+        _ops._check_dev("indices", indices, self.device)
+        it = _ops._index_code("indices", indices)
+        num_valid, count_word, word64, last_word = self._counts(indices, count, last_id)
+        n = indices.numel()
+        if n > 2 ** 31 - 1:
+            raise ValueError("at most 2**31 - 1 lookups per prefetch")
+        L = _lib.lib()
+        need = int(L.cuembed_row_cache_workspace_bytes(n, self.rows, self.num_sets))
+        if self._work is None or self._work.numel() < need:
+            self._work = torch.empty((max(need, 1),), dtype=torch.uint8, device=self.device)
+        lwork = ctypes.c_size_t(self._work.numel())
+        with torch.cuda.device(self.device):
+            L.cuembed_row_cache_prefetch(*self._state(), _ops._ptr(indices), it, n, num_valid, _ops._ptr(count_word),
+                                         int(word64), _ops._ptr(last_word), int(bool(for_update)),
+                                         ctypes.c_void_p(self._work.data_ptr()), ctypes.byref(lwork),
+                                         _ops._stream(indices))
+        return None
+
+    def forward(self, indices, offsets=None, weights=None, batch_size=None, num_hots=0, mode="sum", use_cache=True,
+                out=None):
+        """prefetch(indices) + translate + EmbeddingForward on the host table's base pointer: bit-identical to
+        embedding_forward on a device copy of the table.  use_cache=False reads every row from the host table without
+        touching the cache (dirty rows are then stale there until flush())."""
+        if mode not in _ops._MODES:
+            raise ValueError("mode must be 'sum', 'mean' or 'concat'")
+        if use_cache:
+            self.prefetch(indices)
+        return super().forward(indices, offsets=offsets, weights=weights, batch_size=batch_size, num_hots=num_hots,
+                               mode=mode, use_cache=use_cache, out=out)
+
+    def apply_sgd(self, ids, rows, lr, count=None, last_id=None):
+        """Sparse SGD step through the cache: table[ids[k], :] -= lr * rows[k, :] for every valid entry k of the
+        compressed gradient (ids, rows) = (inverse_mapping, grad_embedding) of embedding_backward; count / last_id as
+        for sparse_row_update (device-side, no read-back).  prefetch(ids, for_update=True) first, so resident rows
+        are updated in HBM and marked dirty; rows their set has no way for are updated in place in the host table
+        over PCIe: no update is dropped.  ids must name distinct rows (a coalesced gradient).  lr: a float or a
+        one-element float32 device tensor."""
+        for name, t in (("ids", ids), ("rows", rows)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s must be a torch.Tensor" % name)
+        _ops._index_code("ids", ids)
+        if rows.dtype != self.table.dtype:
+            raise TypeError("rows must have the table's dtype (%s), got %s" % (self.table.dtype, rows.dtype))
+        if ids.dim() != 1 or rows.dim() != 2 or rows.shape[1] != self.width or rows.shape[0] != ids.numel():
+            raise ValueError("ids must be [entries] and rows [entries, width]")
+        lr_word = None
+        if isinstance(lr, torch.Tensor):
+            if lr.dtype != torch.float32 or lr.numel() != 1:
+                raise TypeError("a device-side lr must be a one-element float32 tensor")
+            lr_word, lr = lr, 0.0
+            _ops._check_dev("lr", lr_word, self.device)
+        _ops._check_dev("rows", rows, self.device)
+        _ops._check_alignment("table", self.table.data_ptr(), self.table.element_size(), self.width,
+                              others=(("rows", rows.data_ptr()),), max_lanes=None)
+        self.prefetch(ids, for_update=True, count=count, last_id=last_id)
+        n = ids.numel()
+        if n == 0:
+            return None
+        translated = self.translate(ids)
+        # the count of valid entries as the prefetch resolved it on the device: one int64 word
+        resolved = self.words[STAT_WORDS.index("batch_count"):STAT_WORDS.index("batch_count") + 1]
+        with torch.cuda.device(self.device):
+            _lib.lib().cuembed_sparse_row_update(
+                ctypes.c_void_p(self.table.data_ptr()), _ops._ELEM[self.table.dtype], self.width, None, 0,
+                _ops._ptr(translated), _ops._INDEX[torch.int64], _ops._ptr(rows), n, 1, -1, _ops._ptr(resolved), 1, None,
+                float(lr), _ops._ptr(lr_word), 0.0, _ops._stream(ids))
+        return None
+
+    def flush(self):
+        """Store every dirty cached row to the host table and clear the dirty bytes (stream-ordered: synchronise
+        before reading the table on the host)."""
+        with torch.cuda.device(self.device):
+            _lib.lib().cuembed_row_cache_flush(
+                *self._state(), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+
+    def invalidate(self):
+        """Drop every cached row WITHOUT writing dirty ones back.  The clock and the counters go on."""
+        self.tags.fill_(-1)
+        self.stamps.view(torch.int32).zero_()
+        self.dirty.zero_()
+        self.slot_of_row.fill_(-1)
+
+    def stats(self):
+        """The device counters as a dict (STAT_WORDS).  The only call that synchronises."""
+        words = self.words.cpu().tolist()
+        return dict(zip(STAT_WORDS, words))

@@ -348,6 +348,34 @@ void cuembed_translate_indices_for_row_cache(const void* indices, int index_type
                                              int64_t cache_row_offset, int64_t* translated,
                                              cuembed_stream_t stream);
 
+/* ---- extension: device-managed row cache (cuembed::RowCachePrefetch / RowCacheFlush, row_cache.hpp) ----
+ * A set-associative LRU write-back cache behind the hook above: num_sets sets of 64 ways in the device buffer
+ * cache_rows ([num_sets * 64] rows of row_bytes bytes, a whole number of rows away from `table`), filled and evicted on
+ * the device from a batch's own indices.  Device state, owned by the caller: tags int64 [num_sets * 64] (-1 = empty),
+ * stamps uint32 [num_sets * 64] (0 = never used), dirty uint8 [num_sets * 64], slot_of_row int32 [num_rows] (-1 = not
+ * cached; what cuembed_translate_indices_for_row_cache reads), words uint64 [16]: [0] clock (set it to 1 first),
+ * [1] hits, [2] misses, [3] evictions, [4] write-backs, [5] unplaced rows, [6] moves of the running prefetch,
+ * [7] valid lookups of the last prefetch, [8] overflow flag.
+ * cuembed_row_cache_prefetch, with t the clock and D the distinct rows of the valid lookups inside [0, num_rows):
+ * hits first (every resident row of D gets stamp t, and its dirty byte when for_update), then the misses of each set
+ * in ascending row id, each taking the way with the smallest (stamp, way) among ways with stamp < t -- none: the row
+ * stays uncached, words[5] += 1 --; a valid dirty victim is stored to the table before the new row is loaded; then
+ * clock += 1.  Valid lookups: the first num_valid (>= 0, host-known; else pass -1), or *count (one device word, int32,
+ * or int64 with count_is_int64 != 0), or *last_id + 1 (one device word of index_type); a count outside [0, nnz] counts
+ * as 0.  work == NULL: *lwork receives the bytes needed (cuembed_row_cache_workspace_bytes), nothing runs.
+ * cuembed_row_cache_flush stores every dirty row to the table and clears the dirty bytes.  cuembed_cache_set_of is
+ * the set of a row (host arithmetic).  Stream-ordered, no read-back. */
+size_t cuembed_row_cache_workspace_bytes(int64_t nnz, int64_t num_rows, int num_sets);
+void cuembed_row_cache_prefetch(void* table, void* cache_rows, int64_t row_bytes, int64_t num_rows, int num_sets,
+                                int64_t* tags, uint32_t* stamps, void* dirty, int32_t* slot_of_row, uint64_t* words,
+                                const void* indices, int index_type, int64_t nnz, int64_t num_valid, const void* count,
+                                int count_is_int64, const void* last_id, int for_update, char* work, size_t* lwork,
+                                cuembed_stream_t stream);
+void cuembed_row_cache_flush(void* table, void* cache_rows, int64_t row_bytes, int64_t num_rows, int num_sets,
+                             int64_t* tags, uint32_t* stamps, void* dirty, int32_t* slot_of_row, uint64_t* words,
+                             cuembed_stream_t stream);
+int cuembed_cache_set_of(int64_t row, int num_sets);
+
 /* ---- extension: gradient w.r.t. the per-lookup weights ---------------------- */
 /* grad_weights[s, j] = dot(params[indices[s, j], :], grad_y[s, :]); one entry per lookup;
  * index layouts as in cuembed_embedding_forward (cuembed::EmbeddingWeightGrad). */
