@@ -17,6 +17,23 @@ only when its slowest round beats the other's fastest.  Hit rates: (c) from the 
 passes (distinct rows), (b) from slot_of_row per epoch (lookups).
 
     python benchmarks/dynamic_row_cache_benchmark.py --out profiles/dynamic_row_cache_timing.json [--commit ID]
+
+--leg train times a TRAINING step instead -- forward, compressed backward (count on the device) and row-wise Adagrad --
+on the same stream, in three arrangements:
+
+    cache       DynamicRowCache(rule="rowwise_adagrad"): forward and apply_update through the cache, the state on the
+                cache slots
+    host        table and state addressed directly in pinned host memory: the forward and the sparse step read and
+                write every row over PCIe
+    device      table and state on the device (what the cache can at best approach)
+
+Same protocol: a warm-up pass each, then `--rounds` interleaved rounds of one pass, ms per step as median [min, max].  For
+every pair the verdict is "faster beyond the spread" (the slowest round of one beats the fastest of the other), "slower"
+(the reverse) or "the same within the spread".  Before the timed passes the three arrangements run a few steps on SHARED
+gradients (one backward per step); whether their forward outputs, tables and states then hold the same bits (after the
+cache's flush) is recorded.
+
+    python benchmarks/dynamic_row_cache_benchmark.py --leg train --out profiles/row_cache_state_timing.json [--commit ID]
 """
 import argparse
 import json
@@ -75,6 +92,122 @@ def commit_id(given):
         return "unknown"
 
 
+def verdict(x, y):
+    """How side x did against side y, from their rounds."""
+    if x["max"] < y["min"]:
+        return "faster beyond the spread"
+    if y["max"] < x["min"]:
+        return "slower"
+    return "the same within the spread"
+
+
+def training_leg(torch, ce, a, batches, host_table, device_table):
+    """Forward + backward + row-wise Adagrad per step, through the cache, directly in host memory and on the device."""
+    import ctypes
+    from cuembed_amd import _lib, ops
+    from cuembed_amd.row_cache import CachedHostTable, DynamicRowCache
+    rule, lr, eps = "rowwise_adagrad", 0.01, 1e-8
+    cap = a.batch * a.hotness
+    direct_table = torch.empty_like(host_table).pin_memory()
+    direct_table.copy_(host_table)
+    direct_state = torch.zeros((a.rows,), dtype=torch.float32).pin_memory()
+    device_state = torch.zeros((a.rows,), dtype=torch.float32, device="cuda")
+    cache = DynamicRowCache(host_table, "cuda", num_sets=a.num_sets, rule=rule, eps=eps)
+    reader = CachedHostTable(direct_table, "cuda", capacity_rows=1)          # (its forward with use_cache=False)
+    g = torch.Generator(device="cuda")
+    g.manual_seed(a.seed + 1)
+    grad_y = (torch.randn((a.batch, a.width), device="cuda", generator=g) * 0.1).to(torch.float16)
+    out = torch.empty((a.batch, a.width), dtype=torch.float16, device="cuda")
+    grad = torch.empty((cap, a.width), dtype=torch.float16, device="cuda")
+    inv = torch.empty((cap,), dtype=torch.int32, device="cuda")
+
+    def backward(idx):
+        t_idx, t_sid, _, remap = ce.transpose_fixed_hotness(idx, a.batch, a.hotness, num_categories=a.rows, remapped=True)
+        ce.embedding_backward(grad_y, None, t_idx, t_sid, remap, grad_embedding=grad, inverse_mapping=inv)
+        return remap[-1:]
+
+    # every arrangement as (forward, update of the compressed gradient in grad / inv with its last id)
+    def host_update(last):
+        # ops.sparse_row_update takes device tensors only: the same entry point on the pinned tensors' pointers
+        _lib.lib().cuembed_sparse_row_update(
+            ctypes.c_void_p(direct_table.data_ptr()), ops._ELEM[torch.float16], a.width,
+            ctypes.c_void_p(direct_state.data_ptr()), ops.UPDATE_RULES[rule], ops._ptr(inv), ops._INDEX[torch.int32],
+            ops._ptr(grad), cap, 1, -1, None, 0, ops._ptr(last), lr, None, eps, ops._stream(last))
+
+    parts = {
+        "cache": (lambda idx: cache.forward(idx, num_hots=a.hotness, out=out),
+                  lambda last: cache.apply_update(inv, grad, lr, last_id=last)),
+        "host": (lambda idx: reader.forward(idx, num_hots=a.hotness, use_cache=False, out=out), host_update),
+        "device": (lambda idx: ce.embedding_forward(device_table, idx, num_hots=a.hotness, out=out),
+                   lambda last: ce.sparse_row_update(device_table, inv, grad, rule=rule, state=device_state, lr=lr, eps=eps,
+                                                     last_id=last)),
+    }
+
+    def step_of(name):
+        forward, update = parts[name]
+
+        def step(idx):
+            forward(idx)
+            update(backward(idx))
+        return step
+
+    sides = {name: step_of(name) for name in parts}
+    # before anything is timed: the three arrangements on SHARED gradients (one backward per step: its sums of
+    # duplicates go through atomics, so two calls need not give the same bits) pool and train the same bits.  The
+    # steps cross a re-draw of the hot set, so the cache evicts dirty rows and writes them back on the way.
+    checked = batches[:min(len(batches), a.redraw + 2)]
+    same_forward = True
+    for idx in checked:
+        pooled = []
+        for forward, _ in parts.values():
+            forward(idx)
+            pooled.append(out.clone())
+        same_forward = same_forward and bool(torch.equal(pooled[0], pooled[1]) and torch.equal(pooled[0], pooled[2]))
+        last = backward(idx)
+        for _, update in parts.values():
+            update(last)
+    cache.flush()
+    torch.cuda.synchronize()
+    same_bits = bool(same_forward and torch.equal(host_table, direct_table) and
+                     torch.equal(host_table, device_table.cpu()) and torch.equal(cache.state, direct_state) and
+                     torch.equal(cache.state, device_state.cpu()))
+    for fn in sides.values():          # warm-up; the cache reaches its steady state
+        time_pass(torch, fn, batches)
+    before = cache.stats()
+    samples = {name: [] for name in sides}
+    for _ in range(a.rounds):
+        for name, fn in sides.items():
+            samples[name].append(time_pass(torch, fn, batches))
+    after = cache.stats()
+    got = {name: summarise(v) for name, v in samples.items()}
+    steps = a.rounds * a.steps
+    per_step = {k: (after[k] - before[k]) / steps for k in ("hits", "misses", "evictions", "write_backs", "unplaced")}
+    distinct = per_step["hits"] + per_step["misses"]
+    capacity = 64 * a.num_sets
+    report = dict(tool="benchmarks/dynamic_row_cache_benchmark.py --leg train", commit=commit_id(a.commit),
+                  device=torch.cuda.get_device_name(0), torch=torch.__version__,
+                  step="forward + compressed backward (count on the device) + row-wise Adagrad",
+                  shape=dict(rows=a.rows, width=a.width, dtype="float16", batch=a.batch, hotness=a.hotness, alpha=a.alpha,
+                             steps_per_pass=a.steps, hot_set_redrawn_every=a.redraw, cache_rows=capacity,
+                             num_sets=a.num_sets, table_bytes=a.rows * a.width * 2, state_bytes=a.rows * 4,
+                             cache_bytes=capacity * (a.width * 2 + 4)),
+                  rounds=a.rounds, ms_per_step=got,
+                  cache_per_step=dict(per_step, hit_rate_of_distinct_rows=per_step["hits"] / max(distinct, 1e-9)),
+                  cache_against_host=verdict(got["cache"], got["host"]),
+                  cache_against_device=verdict(got["cache"], got["device"]),
+                  host_against_device=verdict(got["host"], got["device"]),
+                  same_bits_on_shared_gradients=dict(steps=len(checked), forward_outputs_tables_and_states_equal=same_bits))
+    for name in sides:
+        print("%-8s %.4f ms / step [%.4f, %.4f]" % (name, got[name]["ms"], got[name]["min"], got[name]["max"]), flush=True)
+    text = json.dumps(report, indent=1)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    print(json.dumps(dict(summary={k: got[k]["ms"] for k in got}, cache_against_host=report["cache_against_host"],
+                          cache_against_device=report["cache_against_device"], same_bits=same_bits)))
+
+
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--rows", type=int, default=1 << 22, help="table rows (a power of two)")
@@ -87,6 +220,8 @@ def main():
     p.add_argument("--redraw", type=int, default=10, help="the hot set is re-drawn every this many steps")
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--seed", type=int, default=1)
+    p.add_argument("--leg", choices=("forward", "train"), default="forward",
+                   help="forward: the four forwards (default); train: forward + backward + row-wise Adagrad, three ways")
     p.add_argument("--out", default=None, help="write the JSON here as well")
     p.add_argument("--commit", default=None, help="commit the tree was built from (default: git rev-parse)")
     a = p.parse_args()
@@ -103,6 +238,8 @@ def main():
     host_table = torch.empty((a.rows, a.width), dtype=torch.float16).pin_memory()
     host_table.copy_(device_table)
     batches = make_batches(torch, a)
+    if a.leg == "train":
+        return training_leg(torch, ce, a, batches, host_table, device_table)
     capacity = 64 * a.num_sets
     static = CachedHostTable(host_table, "cuda", capacity_rows=capacity)
     static.cache_most_frequent(torch.cat([b.reshape(-1) for b in batches[:a.redraw]]))

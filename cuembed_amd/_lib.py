@@ -94,6 +94,11 @@ def _declare(L):
                                                       ctypes.POINTER(ctypes.c_size_t), _VP]
     L.cuembed_row_cache_flush.restype = None
     L.cuembed_row_cache_flush.argtypes = _cache + [_VP]
+    _plane = [_VP, _VP, ctypes.c_int64]   # state, state_cache, state_row_bytes
+    L.cuembed_row_cache_prefetch_with_state.restype = None
+    L.cuembed_row_cache_prefetch_with_state.argtypes = list(L.cuembed_row_cache_prefetch.argtypes) + _plane
+    L.cuembed_row_cache_flush_with_state.restype = None
+    L.cuembed_row_cache_flush_with_state.argtypes = list(L.cuembed_row_cache_flush.argtypes) + _plane
     L.cuembed_cache_set_of.restype = _I
     L.cuembed_cache_set_of.argtypes = [ctypes.c_int64, _I]
     L.cuembed_compute_compressed_grad_indices.restype = None
@@ -131,6 +136,8 @@ def _declare(L):
     L.cuembed_sparse_row_update.restype = None
     L.cuembed_sparse_row_update.argtypes = [_VP, _I, _I, _VP, _I, _VP, _I, _VP, _L, _I, _L, _VP, _I, _VP, ctypes.c_float,
                                             _VP, ctypes.c_float, _VP]
+    L.cuembed_sparse_row_update_placed.restype = None
+    L.cuembed_sparse_row_update_placed.argtypes = list(L.cuembed_sparse_row_update.argtypes) + [_VP]
     _U = ctypes.c_uint64
     L.cuembed_sparse_row_update_stochastic.restype = None
     L.cuembed_sparse_row_update_stochastic.argtypes = [_VP, _I, _I, _VP, _I, _VP, _I, _VP, _L, _I, _L, _VP, _I, _VP,

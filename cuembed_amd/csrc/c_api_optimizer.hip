@@ -25,6 +25,29 @@ void cuembed_sparse_row_update(void* table, int elem_type, int embed_width, floa
 #undef UPD
 }
 
+void cuembed_sparse_row_update_placed(void* table, int elem_type, int embed_width, float* state, int rule,
+                                      const void* ids, int index_type, const void* rows, int64_t piece_rows, int pieces,
+                                      int64_t num_rows, const void* counts, int counts_are_int64, const void* last_id,
+                                      float lr, const float* lr_device, float eps, cuembed_stream_t stream,
+                                      const int64_t* state_ids) {
+  const cuembed::SparseUpdateOptions o = cuembed_c_api::UpdateOptions(rule, piece_rows, pieces, num_rows, counts,
+                                                                      counts_are_int64, last_id, lr, lr_device, eps);
+#define UPD(E, I)                                                                                                  \
+  cuembed::SparseRowUpdate<E, I, cuembed::UpdateRoundings::kNearestOnly>(                                          \
+      static_cast<E*>(table), state, embed_width, static_cast<const I*>(ids), static_cast<const E*>(rows), o,      \
+      cuembed_c_api::Stream(stream), state_ids)
+  switch ((elem_type << 1) | index_type) {
+    case 0: UPD(float, int32_t); break;
+    case 1: UPD(float, int64_t); break;
+    case 2: UPD(__half, int32_t); break;
+    case 3: UPD(__half, int64_t); break;
+    case 4: UPD(__hip_bfloat16, int32_t); break;
+    case 5: UPD(__hip_bfloat16, int64_t); break;
+    default: CUEMBED_C_API_BAD_TYPE();
+  }
+#undef UPD
+}
+
 void cuembed_sparse_row_update_launch_shape(int elem_type, int embed_width, int64_t total_entries, int compute_units,
                                             int* out) {
   cuembed::detail::DeviceShape dev =

@@ -9,7 +9,8 @@ using cuembed_c_api::Stream;
 namespace {
 
 cuembed::RowCache CacheOf(void* table, void* cache_rows, int64_t row_bytes, int64_t num_rows, int num_sets,
-                          int64_t* tags, uint32_t* stamps, void* dirty, int32_t* slot_of_row, uint64_t* words) {
+                          int64_t* tags, uint32_t* stamps, void* dirty, int32_t* slot_of_row, uint64_t* words,
+                          float* state = nullptr, float* state_cache = nullptr, int64_t state_row_bytes = 0) {
   cuembed::RowCache c;
   c.table = table;
   c.cache_rows = cache_rows;
@@ -21,24 +22,15 @@ cuembed::RowCache CacheOf(void* table, void* cache_rows, int64_t row_bytes, int6
   c.dirty = static_cast<uint8_t*>(dirty);
   c.slot_of_row = slot_of_row;
   c.words = reinterpret_cast<unsigned long long*>(words);
+  c.state = state;
+  c.state_cache = state_cache;
+  c.state_row_bytes = state_row_bytes;
   return c;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t cuembed_row_cache_workspace_bytes(int64_t nnz, int64_t num_rows, int num_sets) {
-  return cuembed::RowCacheWorkspaceBytes(nnz, num_rows, num_sets);
-}
-
-void cuembed_row_cache_prefetch(void* table, void* cache_rows, int64_t row_bytes, int64_t num_rows, int num_sets,
-                                int64_t* tags, uint32_t* stamps, void* dirty, int32_t* slot_of_row, uint64_t* words,
-                                const void* indices, int index_type, int64_t nnz, int64_t num_valid, const void* count,
-                                int count_is_int64, const void* last_id, int for_update, char* work, size_t* lwork,
-                                cuembed_stream_t stream) {
-  const cuembed::RowCache c = CacheOf(table, cache_rows, row_bytes, num_rows, num_sets, tags, stamps, dirty, slot_of_row,
-                                      words);
+void Prefetch(const cuembed::RowCache& c, const void* indices, int index_type, int64_t nnz, int64_t num_valid,
+              const void* count, int count_is_int64, const void* last_id, int for_update, char* work, size_t* lwork,
+              cuembed_stream_t stream) {
   cuembed::RowCacheCounts counts;
   counts.num_valid = num_valid;
   counts.count = count;
@@ -54,11 +46,49 @@ void cuembed_row_cache_prefetch(void* table, void* cache_rows, int64_t row_bytes
     CUEMBED_C_API_BAD_TYPE();
 }
 
+}  // namespace
+
+extern "C" {
+
+size_t cuembed_row_cache_workspace_bytes(int64_t nnz, int64_t num_rows, int num_sets) {
+  return cuembed::RowCacheWorkspaceBytes(nnz, num_rows, num_sets);
+}
+
+void cuembed_row_cache_prefetch(void* table, void* cache_rows, int64_t row_bytes, int64_t num_rows, int num_sets,
+                                int64_t* tags, uint32_t* stamps, void* dirty, int32_t* slot_of_row, uint64_t* words,
+                                const void* indices, int index_type, int64_t nnz, int64_t num_valid, const void* count,
+                                int count_is_int64, const void* last_id, int for_update, char* work, size_t* lwork,
+                                cuembed_stream_t stream) {
+  Prefetch(CacheOf(table, cache_rows, row_bytes, num_rows, num_sets, tags, stamps, dirty, slot_of_row, words), indices,
+           index_type, nnz, num_valid, count, count_is_int64, last_id, for_update, work, lwork, stream);
+}
+
+void cuembed_row_cache_prefetch_with_state(void* table, void* cache_rows, int64_t row_bytes, int64_t num_rows,
+                                           int num_sets, int64_t* tags, uint32_t* stamps, void* dirty,
+                                           int32_t* slot_of_row, uint64_t* words, const void* indices, int index_type,
+                                           int64_t nnz, int64_t num_valid, const void* count, int count_is_int64,
+                                           const void* last_id, int for_update, char* work, size_t* lwork,
+                                           cuembed_stream_t stream, float* state, float* state_cache,
+                                           int64_t state_row_bytes) {
+  Prefetch(CacheOf(table, cache_rows, row_bytes, num_rows, num_sets, tags, stamps, dirty, slot_of_row, words, state,
+                   state_cache, state_row_bytes),
+           indices, index_type, nnz, num_valid, count, count_is_int64, last_id, for_update, work, lwork, stream);
+}
+
 void cuembed_row_cache_flush(void* table, void* cache_rows, int64_t row_bytes, int64_t num_rows, int num_sets,
                              int64_t* tags, uint32_t* stamps, void* dirty, int32_t* slot_of_row, uint64_t* words,
                              cuembed_stream_t stream) {
   cuembed::RowCacheFlush(CacheOf(table, cache_rows, row_bytes, num_rows, num_sets, tags, stamps, dirty, slot_of_row,
                                  words),
+                         Stream(stream));
+}
+
+void cuembed_row_cache_flush_with_state(void* table, void* cache_rows, int64_t row_bytes, int64_t num_rows, int num_sets,
+                                        int64_t* tags, uint32_t* stamps, void* dirty, int32_t* slot_of_row,
+                                        uint64_t* words, cuembed_stream_t stream, float* state, float* state_cache,
+                                        int64_t state_row_bytes) {
+  cuembed::RowCacheFlush(CacheOf(table, cache_rows, row_bytes, num_rows, num_sets, tags, stamps, dirty, slot_of_row,
+                                 words, state, state_cache, state_row_bytes),
                          Stream(stream));
 }
 

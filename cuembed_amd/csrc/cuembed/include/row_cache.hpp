@@ -5,7 +5,9 @@
 //
 // make a device buffer of num_sets x 64 rows a set-associative LRU write-back cache of a table that lives outside this
 // GPU's HBM.  The cache buffer differs from the table by a whole number of rows, so TranslateIndicesForRowCache +
-// EmbeddingForward (or SparseRowUpdate) on the TABLE's base pointer reach the cached rows unchanged.  Everything is
+// EmbeddingForward (or SparseRowUpdate) on the TABLE's base pointer reach the cached rows unchanged.  An optimizer's fp32
+// state can ride on the same slots as a second plane (RowCache::state): it is translated with its own row offset and
+// handed to SparseRowUpdate as `state_ids`.  Everything is
 // stream-ordered and nothing is read back; the kernels and the state they keep are in row_cache_kernels.hpp.
 #ifndef CUEMBED_INCLUDE_ROW_CACHE_HPP_
 #define CUEMBED_INCLUDE_ROW_CACHE_HPP_
@@ -41,6 +43,11 @@ struct RowCache {
   uint8_t* dirty = nullptr;      //!< [num_sets * 64]
   int32_t* slot_of_row = nullptr;  //!< [num_rows], -1 = not cached
   unsigned long long* words = nullptr;   //!< [kCacheWords]; words[kCacheClock] starts at 1
+  //! The optional state plane: fp32 optimizer state that rides on the cache slots and moves with its row on every
+  //! fill (forward-only fills too: a later for_update hit uses the cached state), dirty eviction and flush.
+  float* state = nullptr;        //!< [num_rows, width] (Adagrad) or [num_rows] (row-wise Adagrad), pinned host memory
+  float* state_cache = nullptr;  //!< [num_sets * 64, ...] in HBM; (state_cache - state) % state_row_bytes == 0
+  int64_t state_row_bytes = 0;   //!< 0 = no state plane; else 4 * width or 4
 };
 
 //! Which lookups of `indices` count: exactly one source, as for SparseRowUpdate.
@@ -125,25 +132,40 @@ inline void CheckRowCache(const RowCache& c) {
   CUEMBED_ASSERT((reinterpret_cast<intptr_t>(c.cache_rows) - reinterpret_cast<intptr_t>(c.table)) % c.row_bytes == 0);
   CUEMBED_ASSERT(c.tags != nullptr && c.stamps != nullptr && c.dirty != nullptr && c.slot_of_row != nullptr &&
                  c.words != nullptr);
+  if (c.state_row_bytes != 0) {
+    CUEMBED_ASSERT(c.state_row_bytes > 0 && c.state_row_bytes % 4 == 0);
+    CUEMBED_ASSERT(c.state != nullptr && c.state_cache != nullptr);
+    CUEMBED_ASSERT(reinterpret_cast<uintptr_t>(c.state) % 4 == 0);
+    CUEMBED_ASSERT((reinterpret_cast<intptr_t>(c.state_cache) - reinterpret_cast<intptr_t>(c.state)) %
+                       c.state_row_bytes == 0);
+  }
 }
 
-//! The mover on `capacity` entries: 16-byte lanes wherever the row size and the table's base allow, 8 or 4 otherwise
-//! (the cache's rows are whole rows away from the table's, so they are aligned alike).
-inline void LaunchCacheMove(const RowCache& c, const CacheMove* moves, const int64_t capacity, const hipStream_t stream) {
-  if (capacity <= 0) return;
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(c.table) | static_cast<uintptr_t>(c.row_bytes);
+//! The mover on `capacity` entries of one plane (`home`: the plane's rows outside the cache, `cached`: its slots):
+//! 16-byte lanes wherever the row size and the plane's base allow, 8 or 4 otherwise (the cached rows are whole rows
+//! away from the home rows, so they are aligned alike).  A 4-byte row is one lane.
+inline void LaunchPlaneMove(const RowCache& c, void* home, void* cached, const int64_t row_bytes, const bool commit,
+                            const CacheMove* moves, const int64_t capacity, const hipStream_t stream) {
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(home) | static_cast<uintptr_t>(row_bytes);
   const int bytes = bits % 16 == 0 ? 16 : (bits % 8 == 0 ? 8 : 4);
-  const int lanes_per_row = static_cast<int>(c.row_bytes / bytes);
+  const int lanes_per_row = static_cast<int>(row_bytes / bytes);
   const UpdateShape s = PlanUpdate(lanes_per_row, capacity, CurrentDeviceShape());
-  char* table = static_cast<char*>(c.table);
-  char* cache = static_cast<char*>(c.cache_rows);
 #define CUEMBED_MOVE(LANE)                                                                                       \
   CacheMoveKernel<LANE><<<dim3(s.grid), dim3(kCacheBlockThreads), 0, stream>>>(                                 \
-      moves, capacity, c.tags, c.dirty, table, cache, c.row_bytes, lanes_per_row, s.group, c.words)
+      moves, capacity, c.tags, c.dirty, static_cast<char*>(home), static_cast<char*>(cached), row_bytes,         \
+      lanes_per_row, s.group, commit ? 1 : 0, c.words)
   if (bytes == 16) CUEMBED_MOVE(uint4);
   else if (bytes == 8) CUEMBED_MOVE(uint2);
   else CUEMBED_MOVE(uint32_t);
 #undef CUEMBED_MOVE
+}
+
+//! The row exchange of every plane: the state plane first, the table's last, in stream order -- the last launch alone
+//! clears the dirty bytes of a flush and counts its write-backs (CacheMoveKernel).
+inline void LaunchCacheMove(const RowCache& c, const CacheMove* moves, const int64_t capacity, const hipStream_t stream) {
+  if (capacity <= 0) return;
+  if (c.state_row_bytes != 0) LaunchPlaneMove(c, c.state, c.state_cache, c.state_row_bytes, false, moves, capacity, stream);
+  LaunchPlaneMove(c, c.table, c.cache_rows, c.row_bytes, true, moves, capacity, stream);
 }
 
 }  // namespace detail
@@ -162,7 +184,9 @@ inline size_t RowCacheWorkspaceBytes(const int64_t nnz, const int64_t num_rows, 
  *   2. then the misses of each set in ascending row id: each takes the way with the smallest (stamp, way) among ways
  *      with stamp < t; if there is none the row stays uncached and the `unplaced` word is raised by one;
  *   3. placing a row stores a valid dirty victim to the table, clears the victim's slot_of_row, loads the new row from
- *      the table, and sets tag, stamp = t, slot_of_row and dirty = for_update;
+ *      the table, and sets tag, stamp = t, slot_of_row and dirty = for_update; with a state plane
+ *      (c.state_row_bytes != 0) the victim's state row is stored and the new row's state row loaded with them,
+ *      whatever for_update says;
  *   4. clock += 1.
  * Lookups outside the table are ignored.  A count outside [0, nnz] counts as 0.
  *
@@ -230,7 +254,8 @@ void RowCachePrefetch(const RowCache& c,
   detail::CacheClockKernel<<<1, 1, 0, stream>>>(c.words);
 }
 
-//! Store every dirty cached row to the table and clear the dirty bytes (the same mover over all slots).
+//! Store every dirty cached row (and its state row) to the table and clear the dirty bytes (the same mover over all
+//! slots).
 inline void RowCacheFlush(const RowCache& c, const hipStream_t stream = 0) {
   detail::CheckRowCache(c);
   detail::LaunchCacheMove(c, nullptr, static_cast<int64_t>(c.num_sets) * kRowCacheWays, stream);

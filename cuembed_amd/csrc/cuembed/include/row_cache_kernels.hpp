@@ -17,7 +17,8 @@
 //                        distinct resident row gets stamp = clock (and its dirty byte)
 //     CachePlaceKernel   a wavefront per set walks its segment of the DISTINCT keys, 64 per step, and places the rows
 //                        that are not resident: victim = min (stamp, way) among ways with stamp < clock
-//     CacheMoveKernel    flat over the move list: dirty victim cache -> table, then new row table -> cache
+//     CacheMoveKernel    flat over the move list: dirty victim cache -> table, then new row table -> cache; with a
+//                        state plane (RowCache::state) once more before that, for the state rows of the same entries
 //     CacheClockKernel   clock += 1
 // Every loop is bounded by a kernel argument (the lookups of the batch, the ways, the lanes of a row) or by a device
 // count clamped to the capacity of the buffer it walks.  Rows are addressed in 64 bits throughout.
@@ -287,12 +288,17 @@ __global__ void __launch_bounds__(kCacheBlockThreads)
  *       entries need no order among themselves.
  *   moves == nullptr (flush): entry k is slot k of `capacity` slots; a valid dirty slot goes cache -> table and its
  *       dirty byte is cleared.
+ * The kernel moves ONE PLANE of the cache: the table's rows, or the optimizer state that rides on the same slots
+ * (`table` / `cache` / `row_bytes` are then the state's; a 4-byte state row is one uint32_t lane, group = 1).  A flush
+ * decides from dirty[k], so the planes are flushed one launch after the other in stream order and only the last one --
+ * `commit` != 0, the table's -- clears the dirty bytes and counts the write-backs: one dirty byte covers both planes
+ * and the counters count rows, not planes.  The move list is read-only here, so a prefetch needs no such switch.
  */
 template <typename LaneT>
 __global__ void __launch_bounds__(kCacheBlockThreads)
     CacheMoveKernel(const CacheMove* __restrict__ moves, const int64_t capacity, const int64_t* __restrict__ tags,
                     uint8_t* __restrict__ dirty, char* __restrict__ table, char* __restrict__ cache,
-                    const int64_t row_bytes, const int lanes_per_row, const int group,
+                    const int64_t row_bytes, const int lanes_per_row, const int group, const int commit,
                     unsigned long long* __restrict__ words) {
   const int lane = static_cast<int>(threadIdx.x) & (group - 1);
   const int groups_per_block = kCacheBlockThreads / group;
@@ -318,7 +324,7 @@ __global__ void __launch_bounds__(kCacheBlockThreads)
       old_row = tags[k];
       // (lane 0 reads the byte it clears below; the others get its value)
       write_back = __shfl(lane == 0 ? static_cast<int>(dirty[k]) : 0, 0, group) != 0 && old_row >= 0;
-      if (lane == 0 && write_back) {
+      if (lane == 0 && write_back && commit) {
         dirty[k] = 0;
         ++flushed;
       }

@@ -1,10 +1,12 @@
 // MI355X (gfx950 / CDNA4) sparse optimizer step -- host API (an extension: the reference ends at the gradient).
 //
 //   cuembed::SparseRowUpdate<ElemT, IndexT>(table, state, embed_width, ids, rows, options, stream)
+//   cuembed::SparseRowUpdate<ElemT, IndexT>(table, state, embed_width, ids, rows, options, stream, state_ids)
 //
 // consumes the compressed gradient that EmbeddingBackward (or the sparse-gradient exchange) produced -- `ids` naming
 // table rows, `rows` their gradient rows -- and updates the named rows of `table` in place.  The number of valid
-// entries may live on the device, so a step that ends in this call needs no host read-back.
+// entries may live on the device, so a step that ends in this call needs no host read-back.  With `state_ids` the state
+// of entry k is addressed by a second id (a table behind the row cache keeps weights and state in two planes).
 #ifndef CUEMBED_INCLUDE_SPARSE_UPDATE_HPP_
 #define CUEMBED_INCLUDE_SPARSE_UPDATE_HPP_
 
@@ -234,6 +236,53 @@ void SparseRowUpdate(ElemT* table,
             return with_rule(std::integral_constant<UpdateRule, UpdateRule::kRowwiseAdagrad>());
         }
         CUEMBED_ASSERT(false && "unknown update rule");
+      });
+}
+
+/**
+ * @brief The same step with the state in a place of its own: entry k updates table[ids[k], :] as above, but reads and
+ * writes its state at row state_ids[k] of `state` -- the per-element accumulator at state[state_ids[k], :] (kAdagrad),
+ * the row word at state[state_ids[k]] (kRowwiseAdagrad).  For a table behind the row cache (row_cache.hpp), whose
+ * weights and state are cached in two planes: `ids` are the batch's ids translated with the table plane's row offset,
+ * `state_ids` the same ids translated with the state plane's, and both reach cached rows through the base pointers of
+ * the host tensors.  Same walk, same launch shape, same arithmetic and the same bits as the call above on tensors that
+ * hold the same values.  The valid entries must name distinct rows in both id arrays.
+ *
+ * state_ids == nullptr is the call above.  Otherwise the rule must have a state (not kSgd) and the rounding is to
+ * nearest: the bits of stochastic rounding are named by the table row, which a translated id is not.
+ */
+template <typename ElemT, typename IndexT, UpdateRoundings kRoundings = UpdateRoundings::kBoth>
+void SparseRowUpdate(ElemT* table,
+                     float* state,
+                     const int embed_width,
+                     const IndexT* ids,
+                     const ElemT* rows,
+                     const SparseUpdateOptions& options,
+                     const hipStream_t stream,
+                     const int64_t* state_ids) {
+  if (state_ids == nullptr)
+    return SparseRowUpdate<ElemT, IndexT, kRoundings>(table, state, embed_width, ids, rows, options, stream);
+  static_assert(kRoundings != UpdateRoundings::kStochasticOnly, "a placed state is updated with round to nearest");
+  using DevT = detail::DeviceElemT<ElemT>;
+  detail::CheckCountSource(options);
+  CUEMBED_ASSERT(options.rule != UpdateRule::kSgd && state != nullptr);
+  CUEMBED_ASSERT(!options.stochastic_rounding);
+  if (!detail::CheckRoundingAndWork<ElemT, UpdateRoundings::kNearestOnly>(options, table, ids, rows)) return;
+  const int bytes = detail::UpdateLaneBytes<DevT>(embed_width, table, rows, state, options.rule == UpdateRule::kAdagrad);
+  const detail::UpdateCounts counts = detail::CountsOf(options);
+  DevT* t = reinterpret_cast<DevT*>(table);
+  const DevT* g = reinterpret_cast<const DevT*>(rows);
+  detail::DispatchUpdate<DevT, UpdateRoundings::kNearestOnly>(
+      bytes, embed_width, options, [&](auto, auto n, auto chunks, const detail::UpdateShape& s) {
+        const auto with_rule = [&](auto rule) {
+          detail::SparseRowUpdatePlacedKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value,
+                                              decltype(chunks)::value>
+              <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), 0, stream>>>(
+                  ids, state_ids, g, t, state, embed_width, s.lanes_per_row, s.group, options.piece_rows, options.pieces,
+                  counts, options.lr, options.lr_device, options.eps);
+        };
+        if (options.rule == UpdateRule::kAdagrad) with_rule(std::integral_constant<UpdateRule, UpdateRule::kAdagrad>());
+        else with_rule(std::integral_constant<UpdateRule, UpdateRule::kRowwiseAdagrad>());
       });
 }
 

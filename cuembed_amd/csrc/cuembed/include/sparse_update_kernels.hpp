@@ -220,24 +220,37 @@ __device__ __forceinline__ void StoreStates(const StatePack<N>* s, float* state0
   if constexpr (kStates > 0) s[0].Store(state0 + at);
 }
 
+//! The row that addresses an entry's state: the table row, or (kPlaced) the entry's own place for it.
+template <bool kPlaced>
+__device__ __forceinline__ int64_t StateRow(const int64_t table_row, const int64_t placed_row) {
+  if constexpr (kPlaced) return placed_row;
+  else return table_row;
+}
+
 /**
  * @brief The one walk over the named rows: table[ids[k], :] and the state of row ids[k] <- rule(table[ids[k], :],
  * rows[k, :]) for every valid entry k.  The body of both kernels below.
  *
  * state0 / state1: the rule's kStates per-element tensors [rows, width], then (kRowState) its per-row words [rows].
+ * kPlaced: entry k's state -- the per-element packs and the row word -- is addressed by state_ids[k] instead of ids[k];
+ * the weights still go by ids[k].  That is what a state plane behind the row cache needs (row_cache.hpp): one translated
+ * id cannot reach both the cached weights and the cached state.  A separate instantiation: without kPlaced nothing of
+ * state_ids is compiled in.
  * kEntries entries are in flight per group: 2 when a lane holds one slice per entry (kChunks == 1), else 1.  With the
  * two moment packs of an Adam slice next to its weights and gradient, two entries take 32 (fp32) to 48 (16-bit)
  * registers of row data per lane: every kChunks == 1 instantiation stays free of scratch and at or above 4 waves per
  * SIMD (profiles/sparse_adam_kernel_resources.txt; the four-slice Adam bodies of the 16-bit types run at 2).
  */
-template <typename ElemT, typename IndexT, int N, int kChunks, int kEntries, bool kStochastic, typename RuleT>
+template <typename ElemT, typename IndexT, int N, int kChunks, int kEntries, bool kStochastic, bool kPlaced = false,
+          typename RuleT>
 __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, const ElemT* __restrict__ rows,
                                               ElemT* __restrict__ table, float* __restrict__ state0,
                                               float* __restrict__ state1, const int width, const int lanes_per_row,
                                               const int group, const int64_t piece_rows, const int pieces,
                                               const UpdateCounts& counts, const UpdateRounding<kStochastic>& rounding,
-                                              const RuleT& rule) {
+                                              const RuleT& rule, const int64_t* __restrict__ state_ids = nullptr) {
   static_assert(!kStochastic || sizeof(ElemT) == 2, "stochastic rounding is for the 16-bit table types");
+  static_assert(!(kPlaced && kStochastic), "the rounding bits are named by the table row: no second place for them");
   static_assert(kEntries == 1 || (kEntries == 2 && kChunks == 1), "two entries in flight: one slice per lane");
   using RoundT = SliceRounding<ElemT, N, kStochastic>;
   constexpr int kStates = RuleT::kStates;
@@ -266,6 +279,14 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
         live[u] = k + u * stride < count;
         r[u] = live[u] ? WidenIndex(ids[base + k + u * stride]) : 0;
       }
+      // where entry u's state lives: row r[u] like the weights, or (kPlaced) a row of its own.  (Plain values handed to
+      // StateRow, nothing that takes the address of r[]: the instantiations without kPlaced compile to what they were.)
+      int64_t placed[kEntries];
+#pragma unroll
+      for (int u = 0; u < kEntries; ++u) {
+        if constexpr (kPlaced) placed[u] = live[u] ? state_ids[base + k + u * stride] : 0;
+        else placed[u] = 0;
+      }
       if constexpr (kChunks == 0) {
         // any width: slices lane, lane + group, ... one after the other (a rule with a row word reads the gradient row
         // twice, the second time out of the cache it has just been loaded into)
@@ -273,20 +294,20 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
         ElemT* w_row = const_cast<ElemT*>(RowPtr(table, r[0], width));
         float row = 0.f;
         if constexpr (kRowState) {
-          const float before = row_words[r[0]];
+          const float before = row_words[StateRow<kPlaced>(r[0], placed[0])];
           float sum = 0.f;
           for (int c = lane; c < lanes_per_row; c += group) sum = AddSquares(sum, LoadPack<ElemT, N>(g_row + c * N));
-          row = rule.Row(row_words + r[0], before, GroupSum(sum, group), width, lane == 0);
+          row = rule.Row(row_words + StateRow<kPlaced>(r[0], placed[0]), before, GroupSum(sum, group), width, lane == 0);
         }
         for (int c = lane; c < lanes_per_row; c += group) {
           const Pack<ElemT, N> g = kRowState ? LoadPack<ElemT, N>(g_row + c * N) : LoadPackStreaming<ElemT, N>(g_row + c * N);
           const Pack<ElemT, N> w = LoadPack<ElemT, N>(w_row + c * N);
           StatePack<N> s[kHeld];
-          LoadStates<kStates>(s, state0, state1, RowElems(r[0], width) + c * N);
+          LoadStates<kStates>(s, state0, state1, RowElems(StateRow<kPlaced>(r[0], placed[0]), width) + c * N);
           RoundT round;
           if constexpr (kStochastic) round = RoundT(seed, round_step, r[0], c * N);
           StorePack<ElemT, N>(w_row + c * N, rule.Slice(w, g, s, row, round));
-          StoreStates<kStates>(s, state0, state1, RowElems(r[0], width) + c * N);
+          StoreStates<kStates>(s, state0, state1, RowElems(StateRow<kPlaced>(r[0], placed[0]), width) + c * N);
         }
       } else {
         Pack<ElemT, N> g[kEntries][kSlices], w[kEntries][kSlices];
@@ -296,7 +317,7 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
         RoundT round[kEntries][kSlices];
 #pragma unroll
         for (int u = 0; u < kEntries; ++u) {
-          if constexpr (kRowState) row_word[u] = live[u] ? row_words[r[u]] : 0.f;
+          if constexpr (kRowState) row_word[u] = live[u] ? row_words[StateRow<kPlaced>(r[u], placed[u])] : 0.f;
 #pragma unroll
           for (int c = 0; c < kSlices; ++c) {
             const int col = (lane + c * group) * N;
@@ -304,7 +325,7 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
             if (has[u][c]) {
               g[u][c] = LoadPackStreaming<ElemT, N>(RowPtr(rows, base + k + u * stride, width) + col);
               w[u][c] = LoadPack<ElemT, N>(RowPtr(table, r[u], width) + col);
-              LoadStates<kStates>(s[u][c], state0, state1, RowElems(r[u], width) + col);
+              LoadStates<kStates>(s[u][c], state0, state1, RowElems(StateRow<kPlaced>(r[u], placed[u]), width) + col);
             }
           }
         }
@@ -326,7 +347,8 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
             for (int c = 0; c < kSlices; ++c)
               if (has[u][c]) sum = AddSquares(sum, g[u][c]);
             sum = GroupSum(sum, group);
-            if (live[u]) row = rule.Row(row_words + r[u], row_word[u], sum, width, lane == 0);
+            if (live[u])
+              row = rule.Row(row_words + StateRow<kPlaced>(r[u], placed[u]), row_word[u], sum, width, lane == 0);
           }
 #pragma unroll
           for (int c = 0; c < kSlices; ++c) {
@@ -334,7 +356,7 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
             const int col = (lane + c * group) * N;
             ElemT* w_at = const_cast<ElemT*>(RowPtr(table, r[u], width)) + col;
             StorePack<ElemT, N>(w_at, rule.Slice(w[u][c], g[u][c], s[u][c], row, round[u][c]));
-            StoreStates<kStates>(s[u][c], state0, state1, RowElems(r[u], width) + col);
+            StoreStates<kStates>(s[u][c], state0, state1, RowElems(StateRow<kPlaced>(r[u], placed[u]), width) + col);
           }
         }
       }
@@ -360,6 +382,22 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
   const UpdateStep<kRule> rule{lr_word != nullptr ? *lr_word : lr_value, eps};
   WalkNamedRows<ElemT, IndexT, N, kChunks, kChunks == 1 ? 2 : 1, kStochastic>(
       ids, rows, table, state, nullptr, width, lanes_per_row, group, piece_rows, pieces, counts, rounding, rule);
+}
+
+//! The same step with the state in a place of its own: entry k's weights at table[ids[k], :], its state at row
+//! state_ids[k] of `state` (WalkNamedRows' kPlaced).  Round to nearest only.
+template <typename ElemT, typename IndexT, int N, UpdateRule kRule, int kChunks>
+__global__ void __launch_bounds__(kUpdateBlockThreads)
+    SparseRowUpdatePlacedKernel(const IndexT* __restrict__ ids, const int64_t* __restrict__ state_ids,
+                                const ElemT* __restrict__ rows, ElemT* __restrict__ table, float* __restrict__ state,
+                                const int width, const int lanes_per_row, const int group, const int64_t piece_rows,
+                                const int pieces, const UpdateCounts counts, const float lr_value,
+                                const float* __restrict__ lr_word, const float eps) {
+  static_assert(kRule != UpdateRule::kSgd, "SGD has no state to place");
+  const UpdateStep<kRule> rule{lr_word != nullptr ? *lr_word : lr_value, eps};
+  WalkNamedRows<ElemT, IndexT, N, kChunks, kChunks == 1 ? 2 : 1, false, true>(
+      ids, rows, table, state, nullptr, width, lanes_per_row, group, piece_rows, pieces, counts, UpdateRounding<false>(),
+      rule, state_ids);
 }
 
 }  // namespace detail

@@ -20,7 +20,10 @@ device from each batch's own indices, so that a host-resident table can be read 
     cache = DynamicRowCache(table, device="cuda:0", num_sets=16384)              # 64 ways per set: 1,048,576 rows
     out = cache.forward(indices, num_hots=64)                                    # prefetch + translate + forward
     cache.apply_sgd(inverse_mapping, grad_embedding, lr=0.1, last_id=remapped[-1:])   # sparse SGD step through the cache
-    cache.flush()                                                                # dirty rows back to the host table"""
+    cache.flush()                                                                # dirty rows back to the host table
+
+With rule="adagrad" / "rowwise_adagrad" the optimizer's fp32 state rides on the cache slots as a second plane and
+cache.apply_update(...) is that rule's step through the cache; cache.state is the host side of the state."""
 import ctypes
 
 import torch
@@ -81,6 +84,10 @@ class CachedHostTable:
 
     def translate(self, indices):
         """indices (int32 / int64 device tensor) -> int64 indices that address cached rows in HBM."""
+        return self._translate(indices, self.cache_row_offset)
+
+    def _translate(self, indices, row_offset):
+        """translate() for a plane whose slots lie `row_offset` of its rows from its home tensor."""
         _ops._check_dev("indices", indices, self.device)
         it = _ops._index_code("indices", indices)
         out = torch.empty(indices.shape, dtype=torch.int64, device=self.device)
@@ -88,7 +95,7 @@ class CachedHostTable:
             with torch.cuda.device(self.device):
                 _lib.lib().cuembed_translate_indices_for_row_cache(
                     ctypes.c_void_p(indices.data_ptr()), it, indices.numel(), ctypes.c_void_p(self.slot_of_row.data_ptr()),
-                    self.rows, self.cache_row_offset, ctypes.c_void_p(out.data_ptr()), _ops._stream(indices))
+                    self.rows, row_offset, ctypes.c_void_p(out.data_ptr()), _ops._stream(indices))
         return out
 
     def forward(self, indices, offsets=None, weights=None, batch_size=None, num_hots=0, mode="sum", use_cache=True,
@@ -177,9 +184,20 @@ class DynamicRowCache(CachedHostTable):
     do not fit are served from the host table over PCIe -- reads and updates alike -- so nothing is ever wrong or lost,
     only slower, and stats()["unplaced"] says how often.
 
-    The cached copy of a dirty row is the only current one: read the host table only after flush() and a synchronise."""
+    The cached copy of a dirty row is the only current one: read the host table only after flush() and a synchronise.
 
-    def __init__(self, host_table, device="cuda", num_sets=1024):
+    rule="adagrad" / "rowwise_adagrad" (ops.UPDATE_RULES) gives the cache a STATE PLANE: the rule's fp32 state -- `state`,
+    a pinned contiguous float32 host tensor [rows, width] resp. [rows], allocated and filled with
+    initial_accumulator_value when None, exposed as cache.state -- is cached slot for slot next to the rows, in a device
+    buffer a whole number of state rows away from the host tensor.  A state row moves with its table row: host -> cache
+    on EVERY fill (a forward-only fill too: a later update that hits uses the cached state), cache -> host when a dirty
+    row is evicted or flushed; one dirty byte covers both planes, the counters count rows.  apply_update() is the rule's
+    step through the cache.  Like the table, cache.state is current only after flush() and a synchronise.  Per-element
+    Adagrad triples the bytes that the fill of a 16-bit row moves over PCIe (2 * width of row, 4 * width of state):
+    row-wise Adagrad, four bytes a row, is the rule to prefer behind the cache."""
+
+    def __init__(self, host_table, device="cuda", num_sets=1024, rule="sgd", state=None, initial_accumulator_value=0.0,
+                 eps=1e-8):
         if not isinstance(host_table, torch.Tensor):
             raise TypeError("host_table must be a torch.Tensor")
         if host_table.dtype not in _ops._ELEM:
@@ -192,9 +210,42 @@ class DynamicRowCache(CachedHostTable):
             raise ValueError("host_table must be a contiguous 2-D tensor with at least one row")
         if (host_table.shape[1] * host_table.element_size()) % 4:
             raise ValueError("row size must be a multiple of 4 bytes")
+        if not isinstance(rule, str) or rule not in _ops.UPDATE_RULES:
+            raise ValueError("rule must be one of %r, got %r" % (sorted(_ops.UPDATE_RULES), rule))
+        state_shape = {"sgd": None, "adagrad": tuple(host_table.shape), "rowwise_adagrad": (host_table.shape[0],)}[rule]
+        if state is not None:
+            if rule == "sgd":
+                raise ValueError("rule='sgd' takes no state")
+            if not isinstance(state, torch.Tensor):
+                raise TypeError("state must be a torch.Tensor")
+            if state.dtype != torch.float32:
+                raise TypeError("state must be float32, got %s" % state.dtype)
+            if tuple(state.shape) != state_shape or not state.is_contiguous():
+                raise ValueError("rule=%r needs a contiguous state of shape %r, got %r" % (rule, state_shape,
+                                                                                         tuple(state.shape)))
+            if state.is_cuda or not state.is_pinned():
+                raise ValueError("state must live in PINNED host memory (tensor.pin_memory())")
         if host_table.is_cuda or not host_table.is_pinned():
             raise ValueError("host_table must live in PINNED host memory (tensor.pin_memory())")
         super().__init__(host_table, device=device, capacity_rows=WAYS * num_sets)
+        self.rule, self.eps = rule, float(eps)
+        self.state = self.state_cache = None
+        self.state_row_bytes = self.state_row_offset = 0
+        if state_shape is not None:
+            if state is None:
+                state = torch.full(state_shape, float(initial_accumulator_value), dtype=torch.float32).pin_memory()
+            self.state = state
+            # the cached plane, like the rows: over-allocate by one state row and start where
+            # (state_cache - state) % state_row_bytes == 0
+            per_row = self.width if rule == "adagrad" else 1
+            self.state_row_bytes = 4 * per_row
+            slots = WAYS * num_sets
+            self._raw_state = torch.empty(((slots + 1) * self.state_row_bytes,), dtype=torch.uint8, device=self.device)
+            shift = (state.data_ptr() - self._raw_state.data_ptr()) % self.state_row_bytes
+            plane = self._raw_state[shift:shift + slots * self.state_row_bytes].view(torch.float32)
+            self.state_cache = plane.view(slots, self.width) if rule == "adagrad" else plane
+            assert (self.state_cache.data_ptr() - state.data_ptr()) % self.state_row_bytes == 0
+            self.state_row_offset = (self.state_cache.data_ptr() - state.data_ptr()) // self.state_row_bytes
         self.num_sets = num_sets
         self.capacity_rows = WAYS * num_sets
         self.row_bytes = self.width * host_table.element_size()
@@ -218,6 +269,10 @@ class DynamicRowCache(CachedHostTable):
         return (p(self.table.data_ptr()), p(self.cache.data_ptr()), self.row_bytes, self.rows, self.num_sets,
                 p(self.tags.data_ptr()), p(self.stamps.data_ptr()), p(self.dirty.data_ptr()),
                 p(self.slot_of_row.data_ptr()), p(self.words.data_ptr()))
+
+    def _plane(self):
+        p = ctypes.c_void_p
+        return (p(self.state.data_ptr()), p(self.state_cache.data_ptr()), self.state_row_bytes)
 
     def _counts(self, ids, count, last_id):
         """(num_valid, count word, word is int64, last_id word) of a prefetch, validated."""
@@ -254,11 +309,14 @@ class DynamicRowCache(CachedHostTable):
         if self._work is None or self._work.numel() < need:
             self._work = torch.empty((max(need, 1),), dtype=torch.uint8, device=self.device)
         lwork = ctypes.c_size_t(self._work.numel())
+        args = self._state() + (_ops._ptr(indices), it, n, num_valid, _ops._ptr(count_word), int(word64),
+                                _ops._ptr(last_word), int(bool(for_update)), ctypes.c_void_p(self._work.data_ptr()),
+                                ctypes.byref(lwork), _ops._stream(indices))
         with torch.cuda.device(self.device):
-            L.cuembed_row_cache_prefetch(*self._state(), _ops._ptr(indices), it, n, num_valid, _ops._ptr(count_word),
-                                         int(word64), _ops._ptr(last_word), int(bool(for_update)),
-                                         ctypes.c_void_p(self._work.data_ptr()), ctypes.byref(lwork),
-                                         _ops._stream(indices))
+            if self.state is None:
+                L.cuembed_row_cache_prefetch(*args)
+            else:
+                L.cuembed_row_cache_prefetch_with_state(*(args + self._plane()))
         return None
 
     def forward(self, indices, offsets=None, weights=None, batch_size=None, num_hots=0, mode="sum", use_cache=True,
@@ -280,6 +338,20 @@ class DynamicRowCache(CachedHostTable):
         are updated in HBM and marked dirty; rows their set has no way for are updated in place in the host table
         over PCIe: no update is dropped.  ids must name distinct rows (a coalesced gradient).  lr: a float or a
         one-element float32 device tensor."""
+        if self.rule != "sgd":
+            raise RuntimeError("this cache trains with rule=%r: use apply_update()" % self.rule)
+        self._apply(ids, rows, lr, count, last_id)
+
+    def apply_update(self, ids, rows, lr, count=None, last_id=None):
+        """The cache's rule through the cache: for every valid entry k of the compressed gradient (ids, rows), row
+        ids[k] of the table and its state are updated by `rule` (ops.sparse_row_update's arithmetic, eps from the
+        constructor) -- arguments as for apply_sgd, which this is on a rule="sgd" cache.  prefetch(ids,
+        for_update=True) first; then the ids are translated twice, once per plane, and one launch of the sparse step
+        updates resident rows and their state in HBM.  Rows their set has no way for are updated in place in the host
+        table AND the host state over PCIe: no update is dropped.  Round to nearest; no read-back."""
+        self._apply(ids, rows, lr, count, last_id)
+
+    def _apply(self, ids, rows, lr, count, last_id):
         for name, t in (("ids", ids), ("rows", rows)):
             if not isinstance(t, torch.Tensor):
                 raise TypeError("%s must be a torch.Tensor" % name)
@@ -296,7 +368,8 @@ class DynamicRowCache(CachedHostTable):
             _ops._check_dev("lr", lr_word, self.device)
         _ops._check_dev("rows", rows, self.device)
         _ops._check_alignment("table", self.table.data_ptr(), self.table.element_size(), self.width,
-                              others=(("rows", rows.data_ptr()),), max_lanes=None)
+                              others=(("rows", rows.data_ptr()),),
+                              state=(("state", self.state.data_ptr()),) if self.rule == "adagrad" else (), max_lanes=None)
         self.prefetch(ids, for_update=True, count=count, last_id=last_id)
         n = ids.numel()
         if n == 0:
@@ -304,22 +377,32 @@ class DynamicRowCache(CachedHostTable):
         translated = self.translate(ids)
         # the count of valid entries as the prefetch resolved it on the device: one int64 word
         resolved = self.words[STAT_WORDS.index("batch_count"):STAT_WORDS.index("batch_count") + 1]
+        args = (ctypes.c_void_p(self.table.data_ptr()), _ops._ELEM[self.table.dtype], self.width, _ops._ptr(self.state),
+                _ops.UPDATE_RULES[self.rule], _ops._ptr(translated), _ops._INDEX[torch.int64], _ops._ptr(rows), n, 1, -1,
+                _ops._ptr(resolved), 1, None, float(lr), _ops._ptr(lr_word), self.eps if self.state is not None else 0.0,
+                _ops._stream(ids))
+        if self.state is None:
+            with torch.cuda.device(self.device):
+                _lib.lib().cuembed_sparse_row_update(*args)
+            return None
+        state_ids = self._translate(ids, self.state_row_offset)
         with torch.cuda.device(self.device):
-            _lib.lib().cuembed_sparse_row_update(
-                ctypes.c_void_p(self.table.data_ptr()), _ops._ELEM[self.table.dtype], self.width, None, 0,
-                _ops._ptr(translated), _ops._INDEX[torch.int64], _ops._ptr(rows), n, 1, -1, _ops._ptr(resolved), 1, None,
-                float(lr), _ops._ptr(lr_word), 0.0, _ops._stream(ids))
+            _lib.lib().cuembed_sparse_row_update_placed(*(args + (_ops._ptr(state_ids),)))
         return None
 
     def flush(self):
         """Store every dirty cached row to the host table and clear the dirty bytes (stream-ordered: synchronise
         before reading the table on the host)."""
+        args = self._state() + (ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream),)
         with torch.cuda.device(self.device):
-            _lib.lib().cuembed_row_cache_flush(
-                *self._state(), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+            if self.state is None:
+                _lib.lib().cuembed_row_cache_flush(*args)
+            else:
+                _lib.lib().cuembed_row_cache_flush_with_state(*(args + self._plane()))
 
     def invalidate(self):
-        """Drop every cached row WITHOUT writing dirty ones back.  The clock and the counters go on."""
+        """Drop every cached row (and its cached state) WITHOUT writing dirty ones back.  The clock and the counters go
+        on."""
         self.tags.fill_(-1)
         self.stamps.view(torch.int32).zero_()
         self.dirty.zero_()

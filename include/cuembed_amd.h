@@ -375,6 +375,24 @@ void cuembed_row_cache_flush(void* table, void* cache_rows, int64_t row_bytes, i
                              int64_t* tags, uint32_t* stamps, void* dirty, int32_t* slot_of_row, uint64_t* words,
                              cuembed_stream_t stream);
 int cuembed_cache_set_of(int64_t row, int num_sets);
+/* The same two calls for a cache with a STATE PLANE: fp32 optimizer state that rides on the cache slots.  state: the
+ * host side (pinned), [num_rows] rows of state_row_bytes bytes -- 4 * width for Adagrad's accumulator, 4 for row-wise
+ * Adagrad's word --; state_cache: [num_sets * 64] such rows in HBM, a whole number of state rows away from `state`.
+ * A state row moves with its table row: host -> cache on every fill (for_update or not), cache -> host when a dirty
+ * row is evicted or flushed.  One dirty byte covers both planes and the counters count rows, not planes.
+ * cuembed_translate_indices_for_row_cache with cache_row_offset = (state_cache - state) / state_row_bytes gives the
+ * state_ids of cuembed_sparse_row_update_placed.  state_row_bytes == 0: no state plane, the calls above. */
+void cuembed_row_cache_prefetch_with_state(void* table, void* cache_rows, int64_t row_bytes, int64_t num_rows,
+                                           int num_sets, int64_t* tags, uint32_t* stamps, void* dirty,
+                                           int32_t* slot_of_row, uint64_t* words, const void* indices, int index_type,
+                                           int64_t nnz, int64_t num_valid, const void* count, int count_is_int64,
+                                           const void* last_id, int for_update, char* work, size_t* lwork,
+                                           cuembed_stream_t stream, float* state, float* state_cache,
+                                           int64_t state_row_bytes);
+void cuembed_row_cache_flush_with_state(void* table, void* cache_rows, int64_t row_bytes, int64_t num_rows, int num_sets,
+                                        int64_t* tags, uint32_t* stamps, void* dirty, int32_t* slot_of_row,
+                                        uint64_t* words, cuembed_stream_t stream, float* state, float* state_cache,
+                                        int64_t state_row_bytes);
 
 /* ---- extension: gradient w.r.t. the per-lookup weights ---------------------- */
 /* grad_weights[s, j] = dot(params[indices[s, j], :], grad_y[s, :]); one entry per lookup;
@@ -531,6 +549,16 @@ void cuembed_sparse_row_update(void* table, int elem_type, int embed_width, floa
                                int index_type, const void* rows, int64_t piece_rows, int pieces, int64_t num_rows,
                                const void* counts, int counts_are_int64, const void* last_id, float lr,
                                const float* lr_device, float eps, cuembed_stream_t stream);
+/* The same step with the state in a place of its own: entry k updates table[ids[k], :] but reads and writes its state
+ * at row state_ids[k] of `state` (the accumulator row for CUEMBED_UPDATE_ADAGRAD, the row word for
+ * CUEMBED_UPDATE_ROWWISE_ADAGRAD).  For a table behind the row cache with a state plane: ids and state_ids are the
+ * batch's ids translated with the two planes' row offsets.  Same walk, same bits.  state_ids == NULL: the call above;
+ * otherwise the rule must have a state. */
+void cuembed_sparse_row_update_placed(void* table, int elem_type, int embed_width, float* state, int rule,
+                                      const void* ids, int index_type, const void* rows, int64_t piece_rows, int pieces,
+                                      int64_t num_rows, const void* counts, int counts_are_int64, const void* last_id,
+                                      float lr, const float* lr_device, float eps, cuembed_stream_t stream,
+                                      const int64_t* state_ids);
 /* Launch shape of cuembed_sparse_row_update for aligned buffers (no launch): out[0] = bytes per lane, out[1] = lanes
  * per row, out[2] = lanes per entry (a power of two <= 64), out[3] = row slices a lane holds at once (0 = run-time
  * loop), out[4] = grid size.  compute_units <= 0: the current device. */
