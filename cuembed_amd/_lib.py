@@ -181,6 +181,10 @@ def _declare(L):
     L.cuembed_grouped_backward_keys.argtypes = [_VP, _I, _VP, _I, _VP, _I, _I, _I, _L, _VP, _VP, _I, _VP]
     L.cuembed_grouped_table_cuts.restype = None
     L.cuembed_grouped_table_cuts.argtypes = [_VP, _I, _L, _L, _VP, _I, _VP, _VP, _I, _VP, _VP]
+    L.cuembed_embedding_weight_grad_grouped.restype = None
+    L.cuembed_embedding_weight_grad_grouped.argtypes = [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, _VP, _VP]
+    L.cuembed_grouped_mean_scale.restype = None
+    L.cuembed_grouped_mean_scale.argtypes = [_VP, _I, _I, _VP, _I, _VP, _I, _I, _I, _VP, _VP]
     L.cuembed_peek_last_error.restype = _I
     L.cuembed_peek_last_error.argtypes = []
     L.cuembed_version.restype = ctypes.c_char_p

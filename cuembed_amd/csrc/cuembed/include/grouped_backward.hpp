@@ -15,6 +15,13 @@
 // and for tables that ARE row slices of one allocation the keys are directly rows of that allocation -- the sparse
 // optimizer step (sparse_update.hpp, sparse_adam.hpp) applies to it unchanged.  The sort is stable, so inside one
 // table row the lookups keep the order of the single-table pipeline.
+//
+// That pipeline is the backward of SUM pooling with respect to the tables.  Two more launches cover the rest
+// (grouped_train_kernels.hpp):
+//
+//   GroupedMeanScale(grad_y, ...)              mean pooling: grad_y times each bag's mean factor, then the pipeline above
+//   EmbeddingWeightGradGrouped(...)            the gradient of a weighted sum with respect to the per-lookup weights
+//
 // Every function runs on the caller's stream, allocates nothing and reads nothing back.
 #ifndef CUEMBED_INCLUDE_GROUPED_BACKWARD_HPP_
 #define CUEMBED_INCLUDE_GROUPED_BACKWARD_HPP_
@@ -26,6 +33,8 @@
 
 #include "cuembed/include/cuembed_assert.hpp"
 #include "cuembed/include/grouped_backward_kernels.hpp"
+#include "cuembed/include/grouped_lookup.hpp"
+#include "cuembed/include/grouped_train_kernels.hpp"
 
 namespace cuembed {
 
@@ -108,6 +117,97 @@ void GroupedTableCuts(const IndexT* inverse_mapping,
   detail::GroupedTableCutsKernel<IndexT><<<1, 256, 0, stream>>>(inverse_mapping, capacity, count, count_word,
                                                                count_word_is_64 ? 1 : 0, last_id, row_base, num_tables,
                                                                cuts);
+}
+
+/**
+ * @brief Gradient of a weighted sum-forward of a GROUP with respect to the per-lookup weights, in one launch:
+ * for lookup p of bag t * batch_per_table + b, grad_weights[p] = dot(tables[t][indices[p], :], grad_y[b, t, :]) in fp32,
+ * rounded once.  Bit-identical to num_tables calls of EmbeddingWeightGrad on grad_y[:, t, :] made contiguous.
+ *
+ * The argument contract is EmbeddingForwardGrouped's: `tables_host` (HOST memory, read here: the least aligned table
+ * and grad_y decide the access width) and `tables_device` (the same pointers in DEVICE memory, read by the kernel);
+ * CSR (offsets[num_tables * batch_per_table + 1], num_hots == 0) or fixed hotness (offsets == nullptr, indices
+ * [num_tables, batch_per_table, num_hots]); grad_y [batch_per_table, num_tables, embed_width] contiguous; grad_weights
+ * has the layout of indices.  Asynchronous on `stream`, allocates nothing, reads nothing back.
+ */
+template <typename InputT, typename IndexT, typename OffsetT>
+void EmbeddingWeightGradGrouped(const InputT* const* tables_host,
+                                const InputT* const* tables_device,
+                                const int num_tables,
+                                const int embed_width,
+                                const IndexT* indices,
+                                const OffsetT* offsets,
+                                const InputT* grad_y,
+                                const int batch_per_table,
+                                const int num_hots,
+                                InputT* grad_weights,
+                                const hipStream_t stream = 0) {
+  using ElemT = detail::DeviceElemT<GetElemT<InputT>>;
+  CUEMBED_ASSERT(tables_host != nullptr && tables_device != nullptr);
+  CUEMBED_ASSERT((offsets != nullptr && num_hots == 0) || (offsets == nullptr && num_hots > 0));
+  const int batch = detail::GroupedBatch(num_tables, batch_per_table);
+  if (batch <= 0) return;
+  CUEMBED_ASSERT(indices != nullptr && grad_y != nullptr && grad_weights != nullptr);
+  const void* bits = detail::GroupAlignmentBits(reinterpret_cast<const void* const*>(tables_host), num_tables);
+  const detail::RowSplit split = detail::SplitRow<ElemT>(embed_width, bits, grad_y);
+  int group = 1;
+  while (group < split.lanes_per_row && group < 64) group *= 2;
+  const int bags_per_block = detail::kDefaultBlockThreads / group;
+  const dim3 block(group, bags_per_block, 1);
+  const dim3 grid((batch + bags_per_block - 1) / bags_per_block, 1, 1);
+  const ElemT* const* tables = reinterpret_cast<const ElemT* const*>(tables_device);
+  const ElemT* gy = reinterpret_cast<const ElemT*>(grad_y);
+  ElemT* gw = reinterpret_cast<ElemT*>(grad_weights);
+  detail::WithLaneWidth<ElemT>(split.elems_per_lane, [&](auto n) {
+    detail::WeightGradGroupedKernel<ElemT, IndexT, OffsetT, decltype(n)::value><<<grid, block, 0, stream>>>(
+        tables, batch_per_table, num_tables, embed_width, batch, indices, offsets, num_hots, gy, gw);
+  });
+}
+
+/**
+ * @brief grad_y of a MEAN-pooled group -> grad_y of the equivalent sum-pooled one, in one launch:
+ * out[b, t, :] = InputT(float(grad_y[b, t, :]) * f), f the forward's own mean factor of bag t * batch_per_table + b --
+ * 1 / length, or with `weights` 1 / the fp32 sum of the bag's weights; 0 when that denominator is 0.  The backward
+ * of a sum-pooled group (GroupedBackwardKeys ... EmbeddingBackward) on `out` is then the backward of the mean.
+ *
+ * CSR (offsets[num_tables * batch_per_table + 1], num_hots == 0) or fixed hotness (offsets == nullptr, num_hots > 0:
+ * every bag has num_hots lookups; weighted bags still sum their weights).  weights: the layout of the indices, or
+ * nullptr.  grad_y and out are [batch_per_table, num_tables, embed_width] contiguous; out may be grad_y.
+ * Asynchronous on `stream`, allocates nothing, reads nothing back.
+ */
+template <typename InputT, typename OffsetT>
+void GroupedMeanScale(const InputT* grad_y,
+                      const OffsetT* offsets,
+                      const InputT* weights,
+                      const int num_tables,
+                      const int batch_per_table,
+                      const int embed_width,
+                      const int num_hots,
+                      InputT* out,
+                      const hipStream_t stream = 0) {
+  using ElemT = detail::DeviceElemT<GetElemT<InputT>>;
+  CUEMBED_ASSERT((offsets != nullptr && num_hots == 0) || (offsets == nullptr && num_hots > 0));
+  const int rows = detail::GroupedBatch(num_tables, batch_per_table);
+  if (rows <= 0) return;
+  CUEMBED_ASSERT(grad_y != nullptr && out != nullptr);
+  const detail::RowSplit split = detail::SplitRow<ElemT>(embed_width, grad_y, out);
+  int group = 1;
+  while (group < split.lanes_per_row && group < 64) group *= 2;
+  const int rows_per_block = detail::kDefaultBlockThreads / group;
+  const dim3 block(group, rows_per_block, 1);
+  const dim3 grid((rows + rows_per_block - 1) / rows_per_block, 1, 1);
+  const ElemT* gy = reinterpret_cast<const ElemT*>(grad_y);
+  const ElemT* w = reinterpret_cast<const ElemT*>(weights);
+  ElemT* o = reinterpret_cast<ElemT*>(out);
+  detail::WithLaneWidth<ElemT>(split.elems_per_lane, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    if (w != nullptr)
+      detail::GroupedMeanScaleKernel<ElemT, OffsetT, N, true><<<grid, block, 0, stream>>>(
+          gy, offsets, w, batch_per_table, num_tables, embed_width, rows, num_hots, o);
+    else
+      detail::GroupedMeanScaleKernel<ElemT, OffsetT, N, false><<<grid, block, 0, stream>>>(
+          gy, offsets, w, batch_per_table, num_tables, embed_width, rows, num_hots, o);
+  });
 }
 
 }  // namespace cuembed

@@ -1327,6 +1327,77 @@ at::Tensor cuembed_grouped_table_cuts_op(const at::Tensor& ids, const at::Tensor
   return cuts;
 }
 
+// ---- a group beyond sum pooling with table gradients: the per-lookup weight gradient and the mean's scale ---------
+// tables / table_ptrs / idx / offsets as in cuemb_embedding_grouped; y_grad [batch, num_tables, width] of the tables'
+// dtype.  Returns the gradient of a weighted SUM-forward with respect to the weights, in the shape of idx.
+at::Tensor cuembed_grouped_weight_grad_op(const at::TensorList tables, const at::Tensor& table_ptrs,
+                                          const at::Tensor& indices, const c10::optional<at::Tensor>& offsets,
+                                          const at::Tensor& y_grad) {
+  TORCH_CHECK(!tables.empty(), "cuembed_pyt: a group needs at least one table");
+  const int elem = ElemCode(tables[0], "tables");
+  const at::DeviceGuard guard(tables[0].device());
+  const GroupedCall c =
+      CheckGroupedCall(tables, table_ptrs, indices, offsets, c10::nullopt, tables[0].scalar_type(), -1, c10::nullopt);
+  const int64_t num_tables = static_cast<int64_t>(tables.size()), width = tables[0].size(1);
+  CheckGpu(y_grad, "y_grad");
+  TORCH_CHECK(y_grad.scalar_type() == tables[0].scalar_type() && y_grad.dim() == 3 && y_grad.size(0) == c.batch &&
+                  y_grad.size(1) == num_tables && y_grad.size(2) == width && y_grad.device() == tables[0].device(),
+              "cuembed_pyt: y_grad must be [batch, num_tables, width] of the tables' dtype on their device");
+  const at::Tensor g = y_grad.contiguous();
+  uintptr_t bits = 0;
+  for (const void* p : c.host_ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+  CheckRowAlignment("tables / y_grad", width, tables[0].element_size(), {reinterpret_cast<const void*>(bits), Ptr(g)}, true);
+  at::Tensor out = at::empty(c.i.sizes(), tables[0].options());
+  if (c.batch > 0 && c.i.numel() > 0)
+    ::cuembed_embedding_weight_grad_grouped(c.host_ptrs.data(), static_cast<const void* const*>(table_ptrs.data_ptr()),
+                                            static_cast<int>(num_tables), elem, static_cast<int>(width), Ptr(c.i), c.idx,
+                                            Ptr(c.o), c.off, Ptr(g), static_cast<int>(c.batch), static_cast<int>(c.hot),
+                                            MutPtr(out), CurrentStream(out));
+  return out;
+}
+
+// y_grad [batch, num_tables, width] of a MEAN-pooled group times each bag's mean factor: the y_grad of the equivalent
+// sum-pooled group (a new tensor).  offsets given: CSR, num_tables * batch + 1 entries, hotness = 0; absent: every bag
+// has `hotness` lookups.  weights: one per lookup, of y_grad's dtype (the mean is then over the weights).
+at::Tensor cuembed_grouped_mean_scale_op(const at::Tensor& y_grad, const c10::optional<at::Tensor>& offsets,
+                                         const c10::optional<at::Tensor>& weights, const int64_t num_tables,
+                                         const int64_t hotness) {
+  CheckGpu(y_grad, "y_grad");
+  const int elem = ElemCode(y_grad, "y_grad");
+  TORCH_CHECK(num_tables >= 1 && y_grad.dim() == 3 && y_grad.size(1) == num_tables,
+              "cuembed_pyt: y_grad must be [batch, num_tables, width]");
+  const int64_t batch = y_grad.size(0), width = y_grad.size(2);
+  TORCH_CHECK(num_tables * batch <= INT32_MAX, "cuembed_pyt: num_tables * batch must fit a 32-bit int");
+  const at::DeviceGuard guard(y_grad.device());
+  const at::Tensor g = y_grad.contiguous();
+  at::Tensor o, w;
+  int off = CUEMBED_I32;
+  int64_t nnz = num_tables * batch * hotness;
+  if (offsets.has_value() && offsets->defined()) {
+    CheckGpu(*offsets, "offsets");
+    off = IndexCode(*offsets, "offsets");
+    o = offsets->contiguous();
+    TORCH_CHECK(hotness == 0 && o.numel() == num_tables * batch + 1 && o.device() == g.device(),
+                "cuembed_pyt: CSR: hotness = 0 and offsets of num_tables * batch + 1 entries on y_grad's device");
+    nnz = -1;   // (known on the device only)
+  } else {
+    TORCH_CHECK(hotness > 0, "cuembed_pyt: fixed hotness: hotness > 0");
+  }
+  if (weights.has_value() && weights->defined()) {
+    CheckGpu(*weights, "weights");
+    TORCH_CHECK(weights->scalar_type() == g.scalar_type() && weights->device() == g.device() &&
+                    (nnz < 0 || weights->numel() >= nnz),
+                "cuembed_pyt: weights must have one entry per lookup, of y_grad's dtype, on its device");
+    w = weights->contiguous();
+  }
+  at::Tensor out = at::empty_like(g);
+  CheckRowAlignment("y_grad", width, g.element_size(), {Ptr(g), Ptr(out)}, true);
+  if (batch > 0 && width > 0)
+    ::cuembed_grouped_mean_scale(Ptr(g), elem, static_cast<int>(width), Ptr(o), off, Ptr(w), static_cast<int>(num_tables),
+                                 static_cast<int>(batch), static_cast<int>(hotness), MutPtr(out), CurrentStream(g));
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(cuembed_pyt, m) {
@@ -1397,6 +1468,9 @@ TORCH_LIBRARY(cuembed_pyt, m) {
       "cuembed_grouped_backward_keys(Tensor idx, Tensor? offsets, Tensor row_base, int num_tables, int batch, int "
       "num_hots, bool narrow) -> (Tensor, Tensor)");
   m.def("cuembed_grouped_table_cuts(Tensor ids, Tensor count_word, Tensor row_base, bool last_id=False) -> Tensor");
+  // a group beyond sum pooling with table gradients: the per-lookup weight gradient, the scale of a mean's y_grad
+  m.def("cuembed_grouped_weight_grad(Tensor[] tables, Tensor table_ptrs, Tensor idx, Tensor? offsets, Tensor y_grad) -> Tensor");
+  m.def("cuembed_grouped_mean_scale(Tensor y_grad, Tensor? offsets, Tensor? weights, int num_tables, int hotness) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(cuembed_pyt, Autograd, m) {
@@ -1438,4 +1512,6 @@ TORCH_LIBRARY_IMPL(cuembed_pyt, CUDA, m) {  // HIP tensors use the CUDA dispatch
   m.impl("cuemb_embedding_quantized_grouped", cuemb_embedding_quantized_grouped_op);
   m.impl("cuembed_grouped_backward_keys", cuembed_grouped_backward_keys_op);
   m.impl("cuembed_grouped_table_cuts", cuembed_grouped_table_cuts_op);
+  m.impl("cuembed_grouped_weight_grad", cuembed_grouped_weight_grad_op);
+  m.impl("cuembed_grouped_mean_scale", cuembed_grouped_mean_scale_op);
 }

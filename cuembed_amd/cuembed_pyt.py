@@ -88,6 +88,12 @@ def _define_python_ops():
     _lib.define("cuembed_grouped_backward_keys(Tensor idx, Tensor? offsets, Tensor row_base, int num_tables, int batch,"
                 " int num_hots, bool narrow) -> (Tensor, Tensor)")
     _lib.define("cuembed_grouped_table_cuts(Tensor ids, Tensor count_word, Tensor row_base, bool last_id=False) -> Tensor")
+    _lib.define("cuembed_grouped_weight_grad(Tensor[] tables, Tensor table_ptrs, Tensor idx, Tensor? offsets,"
+                " Tensor y_grad) -> Tensor")
+    _lib.define("cuembed_grouped_mean_scale(Tensor y_grad, Tensor? offsets, Tensor? weights, int num_tables, int hotness)"
+                " -> Tensor")
+    _lib.impl("cuembed_grouped_weight_grad", _grouped_weight_grad_impl, "CUDA")
+    _lib.impl("cuembed_grouped_mean_scale", _grouped_mean_scale_impl, "CUDA")
     _lib.impl("cuembed_grouped_backward_keys", _grouped_backward_keys_impl, "CUDA")
     _lib.impl("cuembed_grouped_table_cuts", _grouped_table_cuts_impl, "CUDA")
     _lib.impl("cuemb_embedding_grouped", _embedding_grouped_impl, "CUDA")
@@ -141,6 +147,9 @@ def _define_python_ops():
 #   cuembed_grouped_table_cuts                keys + output-row sample ids in front of the single-table pipeline, the
 #                                             table boundaries of the compressed gradient behind it
 #                                             (cuemb_embedding_grouped_trainable is the autograd surface over them)
+#   cuembed_grouped_weight_grad,              a trained group beyond sum pooling with table gradients: the gradient with
+#   cuembed_grouped_mean_scale                respect to the per-lookup weights in ONE launch, and the launch that turns
+#                                             the y_grad of a mean-pooled group into that of the sum-pooled one
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
 _INTS = (torch.int64, torch.int32)
@@ -391,6 +400,45 @@ def _grouped_table_cuts_impl(ids, count_word, row_base, last_id=False):
     return _gb.grouped_table_cuts(ids.contiguous(), row_base, **kw)
 
 
+def _grouped_weight_grad_impl(tables, table_ptrs, idx, offsets, y_grad):
+    from . import grouped_backward as _gb
+    if offsets is None:
+        _require(idx.dim() == 3, "without offsets, idx must be [num_tables, batch, hotness]")
+    _require(y_grad.dim() == 3, "y_grad must be [batch, num_tables, width]")
+    return _gb.embedding_weight_grad_grouped(
+        _grouped_group(tables, table_ptrs), y_grad.contiguous(), idx.contiguous(),
+        None if offsets is None else offsets.contiguous(), num_hots=0 if offsets is not None else idx.shape[2])
+
+
+def _grouped_mean_scale_impl(y_grad, offsets, weights, num_tables, hotness):
+    from . import _lib as _clib
+    _require(y_grad.is_cuda and y_grad.dtype in _FLOATS and y_grad.dim() == 3 and y_grad.shape[1] == num_tables >= 1,
+             "y_grad must be a float [batch, num_tables, width] tensor on the GPU")
+    batch, width = y_grad.shape[0], y_grad.shape[2]
+    _require(num_tables * batch < 2 ** 31, "num_tables * batch must fit a 32-bit int")
+    y_grad = y_grad.contiguous()
+    if offsets is not None:
+        _require(offsets.is_cuda and offsets.dtype in _INTS and hotness == 0 and offsets.numel() == num_tables * batch + 1,
+                 "CSR: hotness = 0 and offsets of num_tables * batch + 1 entries")
+        offsets = offsets.contiguous()
+    else:
+        _require(hotness > 0, "fixed hotness: hotness > 0")
+    if weights is not None:
+        _require(weights.is_cuda and weights.dtype == y_grad.dtype and
+                 (offsets is not None or weights.numel() >= num_tables * batch * hotness),
+                 "weights must have one entry per lookup, of y_grad's dtype")
+        weights = weights.contiguous()
+    out = torch.empty_like(y_grad)
+    if y_grad.numel() > 0:
+        _ops._check_alignment("y_grad", y_grad.data_ptr(), y_grad.element_size(), width, others=(("out", out.data_ptr()),))
+        with torch.cuda.device(y_grad.device):
+            _clib.lib().cuembed_grouped_mean_scale(
+                _ops._ptr(y_grad), _ops._ELEM[y_grad.dtype], int(width), _ops._ptr(offsets),
+                0 if offsets is None else _ops._INDEX[offsets.dtype], _ops._ptr(weights), int(num_tables), int(batch),
+                int(hotness), _ops._ptr(out), _ops._stream(y_grad))
+    return out
+
+
 def _compress_impl(transpose_indices):
     _require(transpose_indices.is_cuda and transpose_indices.dtype in _INTS, "indices must be int tensors on the GPU")
     return _ops.compute_compressed_grad_indices(transpose_indices.contiguous())
@@ -547,12 +595,15 @@ class _CuEmbGrouped(torch.autograd.Function):
     scatter-add.  `params` is (group.flat,) for a one-storage group, else the group's tables."""
 
     @staticmethod
-    def forward(ctx, group, idx, offsets, weights, sparse_grad, row_loads, sample_order, *params):
+    def forward(ctx, group, idx, offsets, weights, sparse_grad, row_loads, sample_order, mode, weight_grad, *params):
         ctx.save_for_backward(idx, offsets, weights)
         ctx.group = group
         ctx.sparse_grad = sparse_grad
+        ctx.mode = mode
+        ctx.weight_grad = weight_grad
         tables = [t.detach() for t in group.tables]
-        return torch.ops.cuembed_pyt.cuemb_embedding_grouped(tables, group.table_ptrs, idx, offsets, weights, "sum",
+        w = None if weights is None else weights.detach()
+        return torch.ops.cuembed_pyt.cuemb_embedding_grouped(tables, group.table_ptrs, idx, offsets, w, mode,
                                                              _ops._ROW_LOADS[row_loads], sample_order)
 
     @staticmethod
@@ -561,12 +612,28 @@ class _CuEmbGrouped(torch.autograd.Function):
         group, kind = ctx.group, ctx.sparse_grad
         T, width, total, base = group.num_tables, group.width, group.total_rows, group.row_base
         one_storage = group.flat is not None
-        wanted = ctx.needs_input_grad[7:]
+        wanted = ctx.needs_input_grad[9:]
         batch, hot = _grouped_batch(T, idx, offsets)
         nnz = idx.numel()
         dev, dtype = out_grad.device, out_grad.dtype
-        grad_2d = out_grad.contiguous().view(batch * T, width)
-        head = (None,) * 7
+        out_grad = out_grad.contiguous()
+        w_grad = None
+        if ctx.weight_grad and ctx.needs_input_grad[3]:     # (sum pooling: the entry point refuses the mean)
+            w_grad = torch.ops.cuembed_pyt.cuembed_grouped_weight_grad([t.detach() for t in group.tables],
+                                                                       group.table_ptrs, idx, offsets, out_grad)
+            if weights.numel() == nnz:
+                w_grad = w_grad.view(weights.shape)
+            else:                                           # (more weights than lookups: the spare ones took no part)
+                spare = torch.zeros(weights.shape, dtype=dtype, device=dev)
+                spare.view(-1)[:nnz] = w_grad.view(-1)
+                w_grad = spare
+        head = (None, None, None, w_grad) + (None,) * 5
+        if not any(wanted):
+            return head + (None,) * len(wanted)
+        if ctx.mode == "mean" and nnz > 0:
+            out_grad = torch.ops.cuembed_pyt.cuembed_grouped_mean_scale(
+                out_grad, offsets, None if weights is None else weights.detach(), T, hot)
+        grad_2d = out_grad.view(batch * T, width)
 
         def per_table(make):
             return head + tuple(make(t) if wanted[t] else None for t in range(T))
@@ -581,7 +648,7 @@ class _CuEmbGrouped(torch.autograd.Function):
         # ---- one key launch, one sort, (one remap,) one scatter-add for all tables
         keys, sample_ids = torch.ops.cuembed_pyt.cuembed_grouped_backward_keys(idx, offsets, group.row_base_device, T,
                                                                                batch, hot, total < 2 ** 31)
-        w = None if weights is None else weights.reshape(-1)
+        w = None if weights is None else weights.detach().reshape(-1)
         t_keys, t_sids, t_w = cuembed_transpose_sample_ids(sample_ids, keys, w, total)
         t_w = t_w if t_w.numel() else None
         if kind is False:
@@ -612,9 +679,16 @@ class _CuEmbGrouped(torch.autograd.Function):
         return per_table(table_grad)
 
 
+def _check_grouped_training(mode, weight_grad):
+    if mode not in ("sum", "mean"):
+        raise ValueError("mode must be 'sum' or 'mean', got %r: a trained group has no other pooling" % (mode,))
+    if not isinstance(weight_grad, bool):
+        raise ValueError("weight_grad must be True or False, got %r" % (weight_grad,))
+
+
 def cuemb_embedding_grouped_trainable(group, idx, offsets=None, weights=None, sparse_grad=False, row_loads=None,
-                                      sample_order=None):
-    """cuemb_embedding_grouped (sum pooling, [batch, num_tables, width]) on a cuembed_amd.TableGroup that is TRAINED: the
+                                      sample_order=None, mode="sum", weight_grad=False):
+    """cuemb_embedding_grouped (sum or mean pooling, [batch, num_tables, width]) on a cuembed_amd.TableGroup that is TRAINED: the
     forward is the grouped op, the backward runs ONE key launch, ONE sort and ONE scatter-add for all tables
     (cuembed_amd.grouped_backward) instead of one single-table chain per table.  A Python autograd.Function over the
     torch ops cuembed_grouped_backward_keys / cuembed_grouped_table_cuts and the single-table pipeline's.
@@ -629,42 +703,60 @@ def cuemb_embedding_grouped_trainable(group, idx, offsets=None, weights=None, sp
         sparse_grad=False      dense views of one [total_rows, width] buffer;
         sparse_grad=True       one coalesced sparse COO tensor per table, after ONE read-back of the table cuts;
         sparse_grad="padded"   ValueError: the tables' segments have no fixed size.
-    The weight gradient is not taken (weights.requires_grad raises).  With grad mode off, or nothing requiring grad, the
-    call is just the forward."""
+    mode="mean" pools with the mean (nn.EmbeddingBag's default; with weights, the sum divided by the bag's summed
+    weights, as the grouped forward does): the backward multiplies out_grad by each bag's mean factor in ONE more launch
+    (cuembed_grouped_mean_scale) and runs the same chain; every sparse_grad form works as for the sum.
+    weight_grad=True also differentiates a SUM with respect to `weights` where they require grad -- nn.EmbeddingBag's
+    per_sample_weights gradient, in ONE launch for all tables (cuembed_grouped_weight_grad) -- even when no table
+    requires grad.  It is opt-in: it reads every looked-up row a second time in the backward.  By default the weight
+    gradient is not taken (weights.requires_grad raises).  The weight gradient of a weighted MEAN needs the forward's
+    output and is not provided: mode="mean" with weight_grad=True and weights that require grad raises.
+    With grad mode off, or nothing requiring grad, the call is just the forward."""
     if not (sparse_grad is False or sparse_grad is True or sparse_grad == "padded"):
         raise ValueError("sparse_grad must be False, True or 'padded', got %r" % (sparse_grad,))
+    _check_grouped_training(mode, weight_grad)
     if group.quantized:
         raise TypeError("a group of fused 8-bit tables is inference only: cuemb_embedding_quantized_grouped")
-    if weights is not None and weights.requires_grad:
-        raise ValueError("the grouped backward does not take the weight gradient: detach the weights")
+    weights_need_grad = weights is not None and weights.requires_grad
+    if weights_need_grad and not weight_grad:
+        raise ValueError("the grouped backward does not take the weight gradient: detach the weights, or pass "
+                         "weight_grad=True (sum pooling only: one more pass over the looked-up rows)")
+    if weights_need_grad and mode == "mean":
+        raise ValueError("the weight gradient of a weighted mean, (<x_j, g> - <y, g>) / S, needs the forward's output and "
+                         "is not provided: weight_grad=True takes mode='sum' only; detach the weights")
     one_storage = group.flat is not None
     if sparse_grad == "padded" and not one_storage:
         raise ValueError("sparse_grad='padded' needs a one-storage group (TableGroup.allocate / from_flat): the "
                          "per-table segments of a compressed gradient have no fixed size")
     params = (group.flat,) if one_storage else tuple(group.tables)
-    if not torch.is_grad_enabled() or not any(p.requires_grad for p in params):
+    if not torch.is_grad_enabled() or not (any(p.requires_grad for p in params) or weights_need_grad):
         return torch.ops.cuembed_pyt.cuemb_embedding_grouped([t.detach() for t in group.tables], group.table_ptrs, idx,
-                                                             offsets, weights, "sum", _ops._ROW_LOADS[row_loads],
-                                                             sample_order)
-    return _CuEmbGrouped.apply(group, idx, offsets, weights, sparse_grad, row_loads, sample_order, *params)
+                                                             offsets, None if weights is None else weights.detach(),
+                                                             mode, _ops._ROW_LOADS[row_loads], sample_order)
+    return _CuEmbGrouped.apply(group, idx, offsets, weights, sparse_grad, row_loads, sample_order, mode, weight_grad,
+                               *params)
 
 
 class TrainableEmbeddingBagGroup(torch.nn.Module):
-    """A TableGroup that is trained, with EmbeddingBagGroup's call shape (sum pooling): bags(idx, offsets, weights) with
-    CSR offsets, or bags(idx) with idx [num_tables, batch, hotness]; returns [batch, num_tables, width] and
+    """A TableGroup that is trained, with EmbeddingBagGroup's call shape (mode "sum" or "mean"): bags(idx, offsets,
+    weights) with CSR offsets, or bags(idx) with idx [num_tables, batch, hotness]; returns [batch, num_tables, width] and
     differentiates through cuemb_embedding_grouped_trainable.  parameters() yields group.flat of a one-storage group,
-    else the tables, where they are nn.Parameters."""
+    else the tables, where they are nn.Parameters.  weight_grad=True (sum pooling) also gives weights that require grad
+    their gradient."""
 
-    def __init__(self, group, sparse_grad=False):
+    def __init__(self, group, sparse_grad=False, mode="sum", weight_grad=False):
         super().__init__()
         if not (sparse_grad is False or sparse_grad is True or sparse_grad == "padded"):
             raise ValueError("sparse_grad must be False, True or 'padded', got %r" % (sparse_grad,))
+        _check_grouped_training(mode, weight_grad)
         if group.quantized:
             raise TypeError("a group of fused 8-bit tables is inference only")
         if sparse_grad == "padded" and group.flat is None:
             raise ValueError("sparse_grad='padded' needs a one-storage group (TableGroup.allocate / from_flat)")
         self.group = group
         self.sparse_grad = sparse_grad
+        self.mode = mode
+        self.weight_grad = weight_grad
         if isinstance(group.flat, torch.nn.Parameter):
             self.weight = group.flat
         elif group.flat is None:
@@ -680,7 +772,7 @@ class TrainableEmbeddingBagGroup(torch.nn.Module):
 
     def forward(self, idx, offsets=None, weights=None, sample_order=None):
         return cuemb_embedding_grouped_trainable(self.group, idx, offsets, weights, sparse_grad=self.sparse_grad,
-                                                 sample_order=sample_order)
+                                                 sample_order=sample_order, mode=self.mode, weight_grad=self.weight_grad)
 
 
 def cuembed_forward(params, idx, offsets, weights, hints=None):
@@ -1054,6 +1146,16 @@ def _(idx, offsets, row_base, num_tables, batch, num_hots, narrow):
 @torch.library.register_fake("cuembed_pyt::cuembed_grouped_table_cuts")
 def _(ids, count_word, row_base, last_id=False):
     return torch.empty((row_base.shape[0],), device=ids.device, dtype=torch.int64)
+
+
+@torch.library.register_fake("cuembed_pyt::cuembed_grouped_weight_grad")
+def _(tables, table_ptrs, idx, offsets, y_grad):
+    return torch.empty(idx.shape, device=tables[0].device, dtype=tables[0].dtype)
+
+
+@torch.library.register_fake("cuembed_pyt::cuembed_grouped_mean_scale")
+def _(y_grad, offsets, weights, num_tables, hotness):
+    return torch.empty(y_grad.shape, device=y_grad.device, dtype=y_grad.dtype)
 
 
 @torch.library.register_fake("cuembed_pyt::cuembed_embedding_forward_hinted")

@@ -30,7 +30,7 @@ import torch
 
 from . import _lib
 from .grouped import INT_MAX, _as_group
-from .ops import _INDEX, _check_dev, _index_code, _ptr, _stream, embedding_backward, transpose
+from .ops import _ELEM, _INDEX, _check_alignment, _check_dev, _index_code, _ptr, _stream, embedding_backward, transpose
 
 
 def _layout(group, indices, offsets, batch_size, num_hots):
@@ -208,14 +208,121 @@ def _check_grad_y(group, grad_y, batch_size):
         raise ValueError("grad_y must be contiguous")
 
 
+def _check_weights(group, weights, nnz):
+    if not isinstance(weights, torch.Tensor):
+        raise TypeError("weights must be a torch.Tensor")
+    if weights.dtype != group.dtype:
+        raise TypeError("weights must be %s, got %s" % (group.dtype, weights.dtype))
+    if weights.numel() < nnz:
+        raise ValueError("weights must have one entry per index")
+
+
+def _mean_scale(group, grad_y, offsets, weights, batch_size, num_hots, out):
+    """The launch of grouped_mean_scale, everything validated and on the device."""
+    with torch.cuda.device(grad_y.device):
+        _lib.lib().cuembed_grouped_mean_scale(
+            _ptr(grad_y), _ELEM[grad_y.dtype], group.width, _ptr(offsets),
+            0 if offsets is None else _INDEX[offsets.dtype], _ptr(weights), group.num_tables, int(batch_size),
+            int(num_hots), _ptr(out), _stream(grad_y))
+    return out
+
+
+def grouped_mean_scale(group, grad_y, offsets=None, weights=None, num_hots=0, out=None):
+    """grad_y [batch_size, num_tables, width] of a MEAN-pooled group times each bag's mean factor -- the grad_y of the
+    equivalent sum-pooled group -- in ONE launch (cuembed::GroupedMeanScale): out[b, t, :] = grad_y[b, t, :] * f with one
+    fp32 multiply and one rounding per element, f the forward's own factor of bag t * batch_size + b: 1 / its length,
+    or with `weights` (one per lookup, the tables' dtype) 1 / the fp32 sum of its weights; 0 when that is 0.  CSR
+    (offsets[num_tables * batch_size + 1]) or fixed hotness (offsets=None, num_hots=H).  out: a contiguous tensor of
+    grad_y's shape and dtype, which may be grad_y itself (in place); None allocates one."""
+    group = _float_group(group)
+    if not isinstance(grad_y, torch.Tensor) or grad_y.dim() != 3:
+        raise ValueError("grad_y must be a [batch_size, num_tables, width] torch.Tensor")
+    batch_size = grad_y.shape[0]
+    _check_grad_y(group, grad_y, batch_size)
+    T = group.num_tables
+    if not ((offsets is not None and num_hots == 0) or (offsets is None and num_hots > 0)):
+        raise ValueError("either CSR (offsets given, num_hots == 0) or fixed hotness (offsets None, num_hots > 0)")
+    if offsets is not None:
+        if not isinstance(offsets, torch.Tensor):
+            raise TypeError("offsets must be a torch.Tensor")
+        _index_code("offsets", offsets)
+        if offsets.numel() != T * batch_size + 1:
+            raise ValueError("offsets must hold num_tables * batch_size + 1 = %d entries, got %d"
+                             % (T * batch_size + 1, offsets.numel()))
+    if T * batch_size > INT_MAX:
+        raise ValueError("num_tables * batch_size = %d does not fit a 32-bit int" % (T * batch_size))
+    if weights is not None:
+        _check_weights(group, weights, 0 if offsets is not None else T * batch_size * num_hots)
+    if out is not None:
+        if not isinstance(out, torch.Tensor):
+            raise TypeError("out must be a torch.Tensor")
+        if out.dtype != grad_y.dtype or tuple(out.shape) != tuple(grad_y.shape) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous tensor of grad_y's shape and dtype")
+    # ---- the call is in order: now the devices
+    _check_dev("grad_y", grad_y)
+    dev = grad_y.device
+    if offsets is not None:
+        _check_dev("offsets", offsets, dev)
+    if weights is not None:
+        _check_dev("weights", weights, dev)
+    if out is None:
+        out = torch.empty_like(grad_y)
+    else:
+        _check_dev("out", out, dev)
+    if grad_y.numel() == 0:
+        return out
+    _check_alignment("grad_y", grad_y.data_ptr(), grad_y.element_size(), group.width, others=(("out", out.data_ptr()),))
+    return _mean_scale(group, grad_y, offsets, weights, batch_size, num_hots, out)
+
+
+def embedding_weight_grad_grouped(group, grad_y, indices, offsets=None, batch_size=None, num_hots=0, out=None):
+    """The gradient of a weighted SUM-forward of a group with respect to the per-lookup weights, in ONE launch
+    (cuembed::EmbeddingWeightGradGrouped): for lookup p of bag t * batch_size + b, grad_w[p] = <tables[t][indices[p], :],
+    grad_y[b, t, :]> in fp32, rounded once to the tables' dtype -- the bits of num_tables calls of embedding_weight_grad
+    on grad_y[:, t, :].contiguous().  grad_y [batch_size, num_tables, width], contiguous, the tables' dtype; indices /
+    offsets / num_hots as in the forward.  Returns a tensor of indices' shape; out: an optional contiguous buffer of
+    indices.numel() entries of the tables' dtype.  It reads every looked-up row once more."""
+    group = _float_group(group)
+    batch_size, nnz = _layout(group, indices, offsets, batch_size, num_hots)
+    _check_grad_y(group, grad_y, batch_size)
+    if out is not None:
+        if not isinstance(out, torch.Tensor):
+            raise TypeError("out must be a torch.Tensor")
+        if out.dtype != group.dtype or out.numel() != nnz or not out.is_contiguous():
+            raise ValueError("out must be a contiguous tensor of %d entries of %s" % (nnz, group.dtype))
+    # ---- the call is in order: now the devices
+    dev = group.device
+    _check_dev("tables[0]", group.tables[0])
+    _check_dev("grad_y", grad_y, dev)
+    _check_dev("indices", indices, dev)
+    if offsets is not None:
+        _check_dev("offsets", offsets, dev)
+    if out is None:
+        out = torch.empty(indices.shape, dtype=group.dtype, device=dev)
+    else:
+        _check_dev("out", out, dev)
+    group.lane_bytes(grad_y.data_ptr())
+    if nnz > 0:
+        with torch.cuda.device(dev):
+            _lib.lib().cuembed_embedding_weight_grad_grouped(
+                group._host_array, _ptr(group.table_ptrs), group.num_tables, _ELEM[group.dtype], group.width,
+                _ptr(indices), _INDEX[indices.dtype], _ptr(offsets), 0 if offsets is None else _INDEX[offsets.dtype],
+                _ptr(grad_y), int(batch_size), int(num_hots), _ptr(out), _stream(indices))
+    return out
+
+
 def embedding_backward_grouped(group, grad_y, indices, offsets=None, weights=None, batch_size=None, num_hots=0,
-                               dense=False, reference_sums=False):
+                               dense=False, reference_sums=False, mode="sum"):
     """The gradient of ALL tables of a group from grad_y [batch_size, num_tables, width] (contiguous, the tables' dtype),
-    the gradient of embedding_forward_grouped(mode="sum")'s result: grouped_backward_keys, ONE transpose (bounded by
+    the gradient of embedding_forward_grouped(mode=mode)'s result: grouped_backward_keys, ONE transpose (bounded by
     total_rows, so the sort skips the zero digits) with the remap, ONE embedding_backward on grad_y viewed as
     [batch_size * num_tables, width].  indices / offsets / weights / num_hots as in the forward.  (The remap is the
     transpose's own fourth result, compute_compressed_grad_indices' values from the same call: up to 4,096 lookups the
     whole index work after the keys is then one launch.)
+
+    mode="sum"    the pipeline above, as it is.
+    mode="mean"   one launch in front of it (grouped_mean_scale) multiplies grad_y, into a new buffer, by each bag's mean
+                  factor; the pipeline then runs unchanged on that.
 
     dense=True    returns (grad, views): ONE zero-initialised [total_rows, width] buffer and its per-table row slices
                   views[t] = grad[row_base[t]:row_base[t + 1]].  reference_sums=True (dense only: it needs a host-known
@@ -226,15 +333,12 @@ def embedding_backward_grouped(group, grad_y, indices, offsets=None, weights=Non
     group = _float_group(group)
     batch_size, nnz = _layout(group, indices, offsets, batch_size, num_hots)
     _check_grad_y(group, grad_y, batch_size)
+    if mode not in ("sum", "mean"):
+        raise ValueError("mode must be 'sum' or 'mean', got %r: the grouped backward has no other pooling" % (mode,))
     if reference_sums and not dense:
         raise ValueError("reference_sums needs a host-known row count: dense=True only")
     if weights is not None:
-        if not isinstance(weights, torch.Tensor):
-            raise TypeError("weights must be a torch.Tensor")
-        if weights.dtype != group.dtype:
-            raise TypeError("weights must be %s, got %s" % (group.dtype, weights.dtype))
-        if weights.numel() < nnz:
-            raise ValueError("weights must have one entry per index")
+        _check_weights(group, weights, nnz)
     # ---- the call is in order: now the devices
     dev = group.device
     _check_dev("tables[0]", group.tables[0])
@@ -243,6 +347,11 @@ def embedding_backward_grouped(group, grad_y, indices, offsets=None, weights=Non
         _check_dev("weights", weights, dev)
         weights = weights.reshape(-1)[:nnz]
     total, width = group.total_rows, group.width
+    if mode == "mean" and nnz > 0:
+        if offsets is not None:
+            _check_dev("offsets", offsets, dev)
+        _check_alignment("grad_y", grad_y.data_ptr(), grad_y.element_size(), width)
+        grad_y = _mean_scale(group, grad_y, offsets, weights, batch_size, num_hots, torch.empty_like(grad_y))
     grad_2d = grad_y.view(batch_size * group.num_tables, width)
     keys, sample_ids = grouped_backward_keys(group, indices, offsets, batch_size, num_hots)
     if dense:

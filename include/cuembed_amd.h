@@ -725,6 +725,25 @@ void cuembed_grouped_backward_keys(const void* indices, int index_type, const vo
 void cuembed_grouped_table_cuts(const void* inverse_mapping, int index_type, int64_t capacity, int64_t count,
                                 const void* count_word, int count_word_is_64, const void* last_id,
                                 const int64_t* row_base, int num_tables, int64_t* cuts, cuembed_stream_t stream);
+/* cuembed::EmbeddingWeightGradGrouped: the gradient of a weighted SUM-forward of a group with respect to the per-lookup
+ * weights, in one launch: for lookup p of bag t * batch_per_table + b, grad_weights[p] = dot(tables[t][indices[p], :],
+ * grad_y[b, t, :]) in fp32, rounded once -- the bits of num_tables calls of cuembed_embedding_weight_grad.  tables_host /
+ * tables_device, indices and offsets as in cuembed_embedding_forward_grouped; grad_y [batch_per_table, num_tables,
+ * embed_width] contiguous and grad_weights (the layout of indices) of elem_type. */
+void cuembed_embedding_weight_grad_grouped(const void* const* tables_host, const void* const* tables_device,
+                                           int num_tables, int elem_type, int embed_width, const void* indices,
+                                           int index_type, const void* offsets, int offset_type, const void* grad_y,
+                                           int batch_per_table, int num_hots, void* grad_weights,
+                                           cuembed_stream_t stream);
+/* cuembed::GroupedMeanScale: grad_y of a MEAN-pooled group -> grad_y of the equivalent sum-pooled one, in one launch:
+ * out[b, t, :] = grad_y[b, t, :] * f (one fp32 multiply, one rounding), f = 1 / the length of bag t * batch_per_table +
+ * b, or with weights (elem_type, the layout of the indices) 1 / the fp32 sum of the bag's weights; 0 when that is 0.
+ * CSR: offsets[num_tables * batch_per_table + 1] of offset_type, num_hots = 0; fixed hotness: offsets = NULL, num_hots
+ * > 0.  grad_y and out: [batch_per_table, num_tables, embed_width] of elem_type, contiguous; out may be grad_y.  The
+ * sequence above, run on out, is then the backward of the mean. */
+void cuembed_grouped_mean_scale(const void* grad_y, int elem_type, int embed_width, const void* offsets,
+                                int offset_type, const void* weights, int num_tables, int batch_per_table, int num_hots,
+                                void* out, cuembed_stream_t stream);
 /* hipPeekAtLastError() as an int (0 = hipSuccess); launches themselves never
  * report errors, exactly like the reference. */
 int cuembed_peek_last_error(void);
