@@ -86,6 +86,10 @@ def _declare(L):
     L.cuembed_translate_indices_for_row_cache.restype = None
     L.cuembed_translate_indices_for_row_cache.argtypes = [_VP, _I, ctypes.c_int64, _VP, ctypes.c_int64, ctypes.c_int64,
                                                           _VP, _VP]
+    L.cuembed_translate_indices_for_row_cache_planes.restype = None
+    L.cuembed_translate_indices_for_row_cache_planes.argtypes = [_VP, _I, ctypes.c_int64, _VP, ctypes.c_int64,
+                                                                 ctypes.c_int64, _VP, ctypes.c_int64, _VP, ctypes.c_int64,
+                                                                 _VP, _VP]
     _cache = [_VP, _VP, ctypes.c_int64, ctypes.c_int64, _I, _VP, _VP, _VP, _VP, _VP]
     L.cuembed_row_cache_workspace_bytes.restype = ctypes.c_size_t
     L.cuembed_row_cache_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, _I]
@@ -99,6 +103,10 @@ def _declare(L):
     L.cuembed_row_cache_prefetch_with_state.argtypes = list(L.cuembed_row_cache_prefetch.argtypes) + _plane
     L.cuembed_row_cache_flush_with_state.restype = None
     L.cuembed_row_cache_flush_with_state.argtypes = list(L.cuembed_row_cache_flush.argtypes) + _plane
+    L.cuembed_row_cache_prefetch_with_states.restype = None    # ... + state2, state2_cache, state2_row_bytes
+    L.cuembed_row_cache_prefetch_with_states.argtypes = list(L.cuembed_row_cache_prefetch.argtypes) + _plane + _plane
+    L.cuembed_row_cache_flush_with_states.restype = None
+    L.cuembed_row_cache_flush_with_states.argtypes = list(L.cuembed_row_cache_flush.argtypes) + _plane + _plane
     L.cuembed_cache_set_of.restype = _I
     L.cuembed_cache_set_of.argtypes = [ctypes.c_int64, _I]
     L.cuembed_compute_compressed_grad_indices.restype = None
@@ -154,6 +162,8 @@ def _declare(L):
     _adam = [_VP, _I, _I, _VP, _VP, _I, _VP, _I, _VP, _L, _I, _L, _VP, _I, _VP, _F, _VP, _F, _VP, _F, _F, _F, _F, _F, _F]
     L.cuembed_sparse_row_adam.restype = None
     L.cuembed_sparse_row_adam.argtypes = _adam + [_VP]
+    L.cuembed_sparse_row_adam_placed.restype = None
+    L.cuembed_sparse_row_adam_placed.argtypes = _adam + [_VP, _VP, _VP]    # ... + exp_avg_ids, exp_avg_sq_ids
     L.cuembed_sparse_row_adam_stochastic.restype = None
     L.cuembed_sparse_row_adam_stochastic.argtypes = _adam + [_U, _U, _VP, _VP]
     L.cuembed_adam_clock_advance.restype = None

@@ -288,6 +288,30 @@ def build_row_cache_state_test(force=False):
     return exe
 
 
+def build_row_cache_adam_test(force=False):
+    """Compiles tests/cpp/row_cache_adam_kat.hip: cuembed::RowCachePrefetch / RowCacheFlush with two state planes,
+    cuembed::TranslateIndicesForRowCachePlanes and cuembed::SparseRowAdam with placed moments through the header-only API
+    against a host recomputation on exactly representable data.  Needs a GPU to RUN (tests/test_gpu_cpp_row_cache_adam.py)."""
+    src = os.path.join(ROOT, "tests", "cpp", "row_cache_adam_kat.hip")
+    exe = os.path.join(ROOT, "tests", "cpp", "row_cache_adam_kat")
+    stamp = exe + ".stamp"
+    deps = [src]
+    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
+        deps += [os.path.join(dirpath, f) for f in files]
+    digest = _digest_files(deps)
+    if not force and os.path.exists(exe) and os.path.exists(stamp):
+        with open(stamp) as f:
+            if f.read().strip() == digest:
+                return exe
+    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-munsafe-fp-atomics", "-I" + CSRC, src, "-o", exe]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("hipcc failed for tests/cpp/row_cache_adam_kat.hip:\n" + r.stdout)
+    with open(stamp, "w") as f:
+        f.write(digest)
+    return exe
+
+
 def build_grouped_train_test(force=False):
     """Compiles tests/cpp/grouped_train_kat.hip: cuembed::EmbeddingWeightGradGrouped and cuembed::GroupedMeanScale through
     the header-only API on a three-table group against a host recomputation on exactly representable data.  Needs a GPU

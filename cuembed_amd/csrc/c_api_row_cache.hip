@@ -10,7 +10,8 @@ namespace {
 
 cuembed::RowCache CacheOf(void* table, void* cache_rows, int64_t row_bytes, int64_t num_rows, int num_sets,
                           int64_t* tags, uint32_t* stamps, void* dirty, int32_t* slot_of_row, uint64_t* words,
-                          float* state = nullptr, float* state_cache = nullptr, int64_t state_row_bytes = 0) {
+                          float* state = nullptr, float* state_cache = nullptr, int64_t state_row_bytes = 0,
+                          float* state2 = nullptr, float* state2_cache = nullptr, int64_t state2_row_bytes = 0) {
   cuembed::RowCache c;
   c.table = table;
   c.cache_rows = cache_rows;
@@ -25,6 +26,9 @@ cuembed::RowCache CacheOf(void* table, void* cache_rows, int64_t row_bytes, int6
   c.state = state;
   c.state_cache = state_cache;
   c.state_row_bytes = state_row_bytes;
+  c.state2 = state2;
+  c.state2_cache = state2_cache;
+  c.state2_row_bytes = state2_row_bytes;
   return c;
 }
 
@@ -89,6 +93,29 @@ void cuembed_row_cache_flush_with_state(void* table, void* cache_rows, int64_t r
                                         int64_t state_row_bytes) {
   cuembed::RowCacheFlush(CacheOf(table, cache_rows, row_bytes, num_rows, num_sets, tags, stamps, dirty, slot_of_row,
                                  words, state, state_cache, state_row_bytes),
+                         Stream(stream));
+}
+
+void cuembed_row_cache_prefetch_with_states(void* table, void* cache_rows, int64_t row_bytes, int64_t num_rows,
+                                            int num_sets, int64_t* tags, uint32_t* stamps, void* dirty,
+                                            int32_t* slot_of_row, uint64_t* words, const void* indices, int index_type,
+                                            int64_t nnz, int64_t num_valid, const void* count, int count_is_int64,
+                                            const void* last_id, int for_update, char* work, size_t* lwork,
+                                            cuembed_stream_t stream, float* state, float* state_cache,
+                                            int64_t state_row_bytes, float* state2, float* state2_cache,
+                                            int64_t state2_row_bytes) {
+  Prefetch(CacheOf(table, cache_rows, row_bytes, num_rows, num_sets, tags, stamps, dirty, slot_of_row, words, state,
+                   state_cache, state_row_bytes, state2, state2_cache, state2_row_bytes),
+           indices, index_type, nnz, num_valid, count, count_is_int64, last_id, for_update, work, lwork, stream);
+}
+
+void cuembed_row_cache_flush_with_states(void* table, void* cache_rows, int64_t row_bytes, int64_t num_rows,
+                                         int num_sets, int64_t* tags, uint32_t* stamps, void* dirty,
+                                         int32_t* slot_of_row, uint64_t* words, cuembed_stream_t stream, float* state,
+                                         float* state_cache, int64_t state_row_bytes, float* state2,
+                                         float* state2_cache, int64_t state2_row_bytes) {
+  cuembed::RowCacheFlush(CacheOf(table, cache_rows, row_bytes, num_rows, num_sets, tags, stamps, dirty, slot_of_row,
+                                 words, state, state_cache, state_row_bytes, state2, state2_cache, state2_row_bytes),
                          Stream(stream));
 }
 

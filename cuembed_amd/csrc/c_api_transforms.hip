@@ -132,6 +132,24 @@ void cuembed_translate_indices_for_row_cache(const void* indices, int index_type
     CUEMBED_C_API_BAD_TYPE();
 }
 
+void cuembed_translate_indices_for_row_cache_planes(const void* indices, int index_type, int64_t nnz,
+                                                    const int32_t* slot_of_row, int64_t num_rows,
+                                                    int64_t cache_row_offset0, int64_t* translated0,
+                                                    int64_t cache_row_offset1, int64_t* translated1,
+                                                    int64_t cache_row_offset2, int64_t* translated2,
+                                                    cuembed_stream_t stream) {
+  if (index_type == CUEMBED_I32)
+    cuembed::TranslateIndicesForRowCachePlanes<int32_t>(static_cast<const int32_t*>(indices), nnz, slot_of_row, num_rows,
+                                                        cache_row_offset0, translated0, cache_row_offset1, translated1,
+                                                        cache_row_offset2, translated2, Stream(stream));
+  else if (index_type == CUEMBED_I64)
+    cuembed::TranslateIndicesForRowCachePlanes<int64_t>(static_cast<const int64_t*>(indices), nnz, slot_of_row, num_rows,
+                                                        cache_row_offset0, translated0, cache_row_offset1, translated1,
+                                                        cache_row_offset2, translated2, Stream(stream));
+  else
+    CUEMBED_C_API_BAD_TYPE();
+}
+
 void cuembed_compute_compressed_grad_indices(const void* indices, int nnz, int index_type,
                                              void* remapped_indices, char* work, size_t* lwork,
                                              cuembed_stream_t stream) {

@@ -130,6 +130,38 @@ TranslateForRowCacheKernel(const IndexT* __restrict__ indices, const int64_t cou
   }
 }
 
+//! The same translation for up to three planes of one cache (TranslateIndicesForRowCachePlanes): one read of
+//! slot_of_row per index, outP[i] = slot >= 0 ? offsetP + slot : idx[i] for every outP that is not null.
+template <typename IndexT>
+__global__ void __launch_bounds__(256)
+TranslateForRowCachePlanesKernel(const IndexT* __restrict__ indices, const int64_t count,
+                                 const int32_t* __restrict__ slot_of_row, const int64_t num_rows,
+                                 const int64_t offset0, int64_t* __restrict__ out0, const int64_t offset1,
+                                 int64_t* __restrict__ out1, const int64_t offset2, int64_t* __restrict__ out2) {
+  const int64_t base =
+      static_cast<int64_t>(blockIdx.x) * blockDim.x * kSequenceItemsPerThread + threadIdx.x;
+  int64_t row[kSequenceItemsPerThread];
+  int32_t slot[kSequenceItemsPerThread];
+#pragma unroll
+  for (int k = 0; k < kSequenceItemsPerThread; ++k) {   // all index loads, then all table loads, in flight together
+    const int64_t t = base + static_cast<int64_t>(k) * blockDim.x;
+    row[k] = t < count ? static_cast<int64_t>(indices[t]) : 0;
+  }
+#pragma unroll
+  for (int k = 0; k < kSequenceItemsPerThread; ++k) {
+    const int64_t t = base + static_cast<int64_t>(k) * blockDim.x;
+    slot[k] = (t < count && row[k] >= 0 && row[k] < num_rows) ? slot_of_row[row[k]] : -1;
+  }
+#pragma unroll
+  for (int k = 0; k < kSequenceItemsPerThread; ++k) {
+    const int64_t t = base + static_cast<int64_t>(k) * blockDim.x;
+    if (t >= count) continue;
+    if (out0 != nullptr) out0[t] = slot[k] >= 0 ? offset0 + slot[k] : row[k];
+    if (out1 != nullptr) out1[t] = slot[k] >= 0 ? offset1 + slot[k] : row[k];
+    if (out2 != nullptr) out2[t] = slot[k] >= 0 ? offset2 + slot[k] : row[k];
+  }
+}
+
 }  // namespace detail
 }  // namespace cuembed
 

@@ -124,6 +124,36 @@ void TranslateIndicesForRowCache(const IndexT* indices,
 }
 
 /**
+ * @brief TranslateIndicesForRowCache for up to three planes of one cache in ONE launch: a table behind the row cache
+ * whose optimizer state rides on the cache slots (row_cache.hpp) has a cached plane per tensor -- the rows, and one or
+ * two state tensors -- each a whole number of ITS rows away from its home tensor, so the same batch of ids is wanted
+ * once per plane with that plane's row offset.  slot_of_row is read once per index;
+ *     translatedP[i] = slot_of_row[indices[i]] >= 0 ? cache_row_offsetP + slot_of_row[indices[i]] : indices[i]   (int64)
+ * for P = 0, 1, 2.  A null output is skipped (its offset is not used).  Per output the semantics are exactly those of
+ * TranslateIndicesForRowCache: indices outside [0, num_rows) are copied through unchanged.
+ */
+template <typename IndexT>
+void TranslateIndicesForRowCachePlanes(const IndexT* indices,
+                                       const int64_t nnz,
+                                       const int32_t* slot_of_row,
+                                       const int64_t num_rows,
+                                       const int64_t cache_row_offset0,
+                                       int64_t* translated0,
+                                       const int64_t cache_row_offset1,
+                                       int64_t* translated1,
+                                       const int64_t cache_row_offset2,
+                                       int64_t* translated2,
+                                       const hipStream_t stream = 0) {
+  if (nnz <= 0 || (translated0 == nullptr && translated1 == nullptr && translated2 == nullptr)) return;
+  const int threads = detail::kIndexBlockThreads;
+  const int64_t per_block = static_cast<int64_t>(threads) * detail::kSequenceItemsPerThread;
+  detail::TranslateForRowCachePlanesKernel<IndexT>
+      <<<static_cast<unsigned>((nnz + per_block - 1) / per_block), threads, 0, stream>>>(
+          indices, nnz, slot_of_row, num_rows, cache_row_offset0, translated0, cache_row_offset1, translated1,
+          cache_row_offset2, translated2);
+}
+
+/**
  * @brief Reorder sample-major COO lookups into index-major order: a STABLE sort
  * of (rows[i] [, weights[i]]) by the key cols[i].
  *

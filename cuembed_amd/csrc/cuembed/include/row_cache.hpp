@@ -7,8 +7,9 @@
 // GPU's HBM.  The cache buffer differs from the table by a whole number of rows, so TranslateIndicesForRowCache +
 // EmbeddingForward (or SparseRowUpdate) on the TABLE's base pointer reach the cached rows unchanged.  An optimizer's fp32
 // state can ride on the same slots as a second plane (RowCache::state): it is translated with its own row offset and
-// handed to SparseRowUpdate as `state_ids`.  Everything is
-// stream-ordered and nothing is read back; the kernels and the state they keep are in row_cache_kernels.hpp.
+// handed to SparseRowUpdate as `state_ids`.  The Adam family has two such planes (RowCache::state2): one launch of
+// TranslateIndicesForRowCachePlanes translates the ids for all three and SparseRowAdam takes the two state ids.
+// Everything is stream-ordered and nothing is read back; the kernels and the state they keep are in row_cache_kernels.hpp.
 #ifndef CUEMBED_INCLUDE_ROW_CACHE_HPP_
 #define CUEMBED_INCLUDE_ROW_CACHE_HPP_
 
@@ -48,6 +49,11 @@ struct RowCache {
   float* state = nullptr;        //!< [num_rows, width] (Adagrad) or [num_rows] (row-wise Adagrad), pinned host memory
   float* state_cache = nullptr;  //!< [num_sets * 64, ...] in HBM; (state_cache - state) % state_row_bytes == 0
   int64_t state_row_bytes = 0;   //!< 0 = no state plane; else 4 * width or 4
+  //! The optional SECOND state plane, moved exactly like the first (the Adam family: `state` is exp_avg, `state2`
+  //! exp_avg_sq).  Only together with the first.
+  float* state2 = nullptr;        //!< [num_rows, width] (Adam) or [num_rows] (row-wise Adam), pinned host memory
+  float* state2_cache = nullptr;  //!< [num_sets * 64, ...] in HBM; (state2_cache - state2) % state2_row_bytes == 0
+  int64_t state2_row_bytes = 0;   //!< 0 = no second plane; else 4 * width or 4
 };
 
 //! Which lookups of `indices` count: exactly one source, as for SparseRowUpdate.
@@ -139,6 +145,14 @@ inline void CheckRowCache(const RowCache& c) {
     CUEMBED_ASSERT((reinterpret_cast<intptr_t>(c.state_cache) - reinterpret_cast<intptr_t>(c.state)) %
                        c.state_row_bytes == 0);
   }
+  if (c.state2_row_bytes != 0) {
+    CUEMBED_ASSERT(c.state_row_bytes != 0);   // a second plane only next to a first
+    CUEMBED_ASSERT(c.state2_row_bytes > 0 && c.state2_row_bytes % 4 == 0);
+    CUEMBED_ASSERT(c.state2 != nullptr && c.state2_cache != nullptr);
+    CUEMBED_ASSERT(reinterpret_cast<uintptr_t>(c.state2) % 4 == 0);
+    CUEMBED_ASSERT((reinterpret_cast<intptr_t>(c.state2_cache) - reinterpret_cast<intptr_t>(c.state2)) %
+                       c.state2_row_bytes == 0);
+  }
 }
 
 //! The mover on `capacity` entries of one plane (`home`: the plane's rows outside the cache, `cached`: its slots):
@@ -160,10 +174,12 @@ inline void LaunchPlaneMove(const RowCache& c, void* home, void* cached, const i
 #undef CUEMBED_MOVE
 }
 
-//! The row exchange of every plane: the state plane first, the table's last, in stream order -- the last launch alone
-//! clears the dirty bytes of a flush and counts its write-backs (CacheMoveKernel).
+//! The row exchange of every plane: the second state plane, the first, then the table's, in stream order -- the last
+//! launch alone commits: it clears the dirty bytes of a flush and counts its write-backs (CacheMoveKernel).
 inline void LaunchCacheMove(const RowCache& c, const CacheMove* moves, const int64_t capacity, const hipStream_t stream) {
   if (capacity <= 0) return;
+  if (c.state2_row_bytes != 0)
+    LaunchPlaneMove(c, c.state2, c.state2_cache, c.state2_row_bytes, false, moves, capacity, stream);
   if (c.state_row_bytes != 0) LaunchPlaneMove(c, c.state, c.state_cache, c.state_row_bytes, false, moves, capacity, stream);
   LaunchPlaneMove(c, c.table, c.cache_rows, c.row_bytes, true, moves, capacity, stream);
 }
@@ -186,7 +202,7 @@ inline size_t RowCacheWorkspaceBytes(const int64_t nnz, const int64_t num_rows, 
  *   3. placing a row stores a valid dirty victim to the table, clears the victim's slot_of_row, loads the new row from
  *      the table, and sets tag, stamp = t, slot_of_row and dirty = for_update; with a state plane
  *      (c.state_row_bytes != 0) the victim's state row is stored and the new row's state row loaded with them,
- *      whatever for_update says;
+ *      whatever for_update says, and likewise the rows of a second state plane (c.state2_row_bytes != 0);
  *   4. clock += 1.
  * Lookups outside the table are ignored.  A count outside [0, nnz] counts as 0.
  *
@@ -254,7 +270,7 @@ void RowCachePrefetch(const RowCache& c,
   detail::CacheClockKernel<<<1, 1, 0, stream>>>(c.words);
 }
 
-//! Store every dirty cached row (and its state row) to the table and clear the dirty bytes (the same mover over all
+//! Store every dirty cached row (and its state rows) to the table and clear the dirty bytes (the same mover over all
 //! slots).
 inline void RowCacheFlush(const RowCache& c, const hipStream_t stream = 0) {
   detail::CheckRowCache(c);

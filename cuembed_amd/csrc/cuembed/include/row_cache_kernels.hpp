@@ -18,7 +18,8 @@
 //     CachePlaceKernel   a wavefront per set walks its segment of the DISTINCT keys, 64 per step, and places the rows
 //                        that are not resident: victim = min (stamp, way) among ways with stamp < clock
 //     CacheMoveKernel    flat over the move list: dirty victim cache -> table, then new row table -> cache; with a
-//                        state plane (RowCache::state) once more before that, for the state rows of the same entries
+//                        state plane (RowCache::state, ::state2) once more per plane before that, for the state rows
+//                        of the same entries
 //     CacheClockKernel   clock += 1
 // Every loop is bounded by a kernel argument (the lookups of the batch, the ways, the lanes of a row) or by a device
 // count clamped to the capacity of the buffer it walks.  Rows are addressed in 64 bits throughout.
@@ -291,8 +292,8 @@ __global__ void __launch_bounds__(kCacheBlockThreads)
  * The kernel moves ONE PLANE of the cache: the table's rows, or the optimizer state that rides on the same slots
  * (`table` / `cache` / `row_bytes` are then the state's; a 4-byte state row is one uint32_t lane, group = 1).  A flush
  * decides from dirty[k], so the planes are flushed one launch after the other in stream order and only the last one --
- * `commit` != 0, the table's -- clears the dirty bytes and counts the write-backs: one dirty byte covers both planes
- * and the counters count rows, not planes.  The move list is read-only here, so a prefetch needs no such switch.
+ * `commit` != 0, the table's -- clears the dirty bytes and counts the write-backs: one dirty byte covers all planes
+ * (there may be two state planes) and the counters count rows, not planes.  The move list is read-only here, so a prefetch needs no such switch.
  */
 template <typename LaneT>
 __global__ void __launch_bounds__(kCacheBlockThreads)

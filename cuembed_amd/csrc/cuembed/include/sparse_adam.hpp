@@ -2,10 +2,13 @@
 // gradient).
 //
 //   cuembed::SparseRowAdam<ElemT, IndexT>(table, exp_avg, exp_avg_sq, embed_width, ids, rows, options, stream)
+//   cuembed::SparseRowAdam<ElemT, IndexT>(table, exp_avg, exp_avg_sq, embed_width, ids, rows, options, stream,
+//                                         exp_avg_ids, exp_avg_sq_ids)
 //   cuembed::AdamClockAdvance(powers, bias_factor, beta1, beta2, stream)
 //
 // SparseRowAdam consumes the compressed gradient like SparseRowUpdate (sparse_update.hpp) and keeps two fp32 moments per
-// named row; AdamClockAdvance keeps the bias factor of the step in a device word, so that a captured step needs the host
+// named row; with exp_avg_ids / exp_avg_sq_ids the moments of entry k are addressed by ids of their own (a table behind
+// the row cache keeps weights and moments in three planes); AdamClockAdvance keeps the bias factor of the step in a device word, so that a captured step needs the host
 // for neither the entry count nor the step number.
 #ifndef CUEMBED_INCLUDE_SPARSE_ADAM_HPP_
 #define CUEMBED_INCLUDE_SPARSE_ADAM_HPP_
@@ -94,6 +97,72 @@ void SparseRowAdam(ElemT* table,
           case AdamRule::kRowwiseAdam: return with_rule(std::integral_constant<AdamRule, AdamRule::kRowwiseAdam>());
         }
         CUEMBED_ASSERT(false && "unknown Adam rule");
+      });
+}
+
+namespace detail {
+//! Entries in flight of the placed Adam kernels whose lanes hold one slice per entry (WalkNamedRows' kEntries).
+constexpr int kAdamPlacedEntriesInFlight = 2;
+}  // namespace detail
+
+/**
+ * @brief The same step with the moments in places of their own: entry k updates table[ids[k], :] as above, but reads
+ * and writes its first moment at row exp_avg_ids[k] of `exp_avg` and its second at row exp_avg_sq_ids[k] of `exp_avg_sq`
+ * (kAdam: a row of embed_width elements; kRowwiseAdam: the row's one word).  For a table behind the row cache
+ * (row_cache.hpp) whose weights and moments are cached in three planes: `ids`, `exp_avg_ids` and `exp_avg_sq_ids` are the
+ * batch's ids translated with the three planes' row offsets (TranslateIndicesForRowCachePlanes), and each reaches cached
+ * rows through the base pointer of its host tensor.  The two moments need an id each: they are separate allocations,
+ * so their planes' row offsets differ, and row-wise their row sizes do.  Lane bytes, launch shape and dispatch are those
+ * of the call above: the same walk, the same arithmetic and the same bits on tensors that hold the same values.  The
+ * valid entries must name distinct rows in all three id arrays.
+ *
+ * Both id arrays nullptr is the call above.  Otherwise both are required and the rounding is to nearest (the bits of
+ * stochastic rounding are named by the table row, which a translated id is not); one array alone, or stochastic
+ * rounding, aborts with the failed condition.
+ */
+template <typename ElemT, typename IndexT, UpdateRoundings kRoundings = UpdateRoundings::kBoth>
+void SparseRowAdam(ElemT* table,
+                   float* exp_avg,
+                   float* exp_avg_sq,
+                   const int embed_width,
+                   const IndexT* ids,
+                   const ElemT* rows,
+                   const SparseAdamOptions& options,
+                   const hipStream_t stream,
+                   const int64_t* exp_avg_ids,
+                   const int64_t* exp_avg_sq_ids) {
+  if (exp_avg_ids == nullptr && exp_avg_sq_ids == nullptr)
+    return SparseRowAdam<ElemT, IndexT, kRoundings>(table, exp_avg, exp_avg_sq, embed_width, ids, rows, options, stream);
+  static_assert(kRoundings != UpdateRoundings::kStochasticOnly, "placed moments are updated with round to nearest");
+  using DevT = detail::DeviceElemT<ElemT>;
+  detail::CheckCountSource(options);
+  CUEMBED_ASSERT(options.beta1 >= 0.f && options.beta1 < 1.f && options.beta2 >= 0.f && options.beta2 < 1.f);
+  CUEMBED_ASSERT(options.eps >= 0.f && options.weight_decay >= 0.f);
+  CUEMBED_ASSERT(exp_avg_ids != nullptr && exp_avg_sq_ids != nullptr);
+  CUEMBED_ASSERT(!options.stochastic_rounding);
+  if (!detail::CheckRoundingAndWork<ElemT, UpdateRoundings::kNearestOnly>(options, table, ids, rows)) return;
+  CUEMBED_ASSERT(exp_avg != nullptr && exp_avg_sq != nullptr);
+  CUEMBED_ASSERT(reinterpret_cast<uintptr_t>(exp_avg_sq) % 4 == 0);
+  const int bytes = detail::UpdateLaneBytes<DevT>(embed_width, table, rows, exp_avg, true,
+                                                  options.rule == AdamRule::kAdam ? exp_avg_sq : nullptr);
+  const detail::UpdateCounts counts = detail::CountsOf(options);
+  const detail::AdamScalars h = {options.beta1, options.one_minus_beta1, options.beta2, options.one_minus_beta2,
+                                 options.eps, options.weight_decay};
+  DevT* t = reinterpret_cast<DevT*>(table);
+  const DevT* g = reinterpret_cast<const DevT*>(rows);
+  detail::DispatchUpdate<DevT, UpdateRoundings::kNearestOnly>(
+      bytes, embed_width, options, [&](auto, auto n, auto chunks, const detail::UpdateShape& s) {
+        const auto with_rule = [&](auto rule) {
+          constexpr int kChunks = decltype(chunks)::value;
+          detail::SparseRowAdamPlacedKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, kChunks,
+                                            kChunks == 1 ? detail::kAdamPlacedEntriesInFlight : 1>
+              <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), 0, stream>>>(
+                  ids, exp_avg_ids, exp_avg_sq_ids, g, t, exp_avg, exp_avg_sq, embed_width, s.lanes_per_row, s.group,
+                  options.piece_rows, options.pieces, counts, options.lr, options.lr_device, options.bias_factor,
+                  options.bias_factor_device, h);
+        };
+        if (options.rule == AdamRule::kAdam) with_rule(std::integral_constant<AdamRule, AdamRule::kAdam>());
+        else with_rule(std::integral_constant<AdamRule, AdamRule::kRowwiseAdam>());
       });
 }
 

@@ -207,17 +207,20 @@ struct UpdateStep {
   }
 };
 
-//! The per-element state packs of one slice, `at` elements into the rule's kStates tensors (written out per tensor: the
-//! pointers keep their __restrict__, which an array of them indexed in a loop loses).
+//! The per-element state packs of one slice, `at0` / `at1` elements into the rule's kStates tensors (written out per
+//! tensor: the pointers keep their __restrict__, which an array of them indexed in a loop loses).  The two offsets differ
+//! only in a walk with two placed ids.
 template <int kStates, int N>
-__device__ __forceinline__ void LoadStates(StatePack<N>* s, const float* state0, const float* state1, const int64_t at) {
-  if constexpr (kStates > 0) s[0] = StatePack<N>::Load(state0 + at);
-  if constexpr (kStates > 1) s[1] = StatePack<N>::Load(state1 + at);
+__device__ __forceinline__ void LoadStates(StatePack<N>* s, const float* state0, const float* state1, const int64_t at0,
+                                           const int64_t at1) {
+  if constexpr (kStates > 0) s[0] = StatePack<N>::Load(state0 + at0);
+  if constexpr (kStates > 1) s[1] = StatePack<N>::Load(state1 + at1);
 }
 template <int kStates, int N>
-__device__ __forceinline__ void StoreStates(const StatePack<N>* s, float* state0, float* state1, const int64_t at) {
-  if constexpr (kStates > 1) s[1].Store(state1 + at);
-  if constexpr (kStates > 0) s[0].Store(state0 + at);
+__device__ __forceinline__ void StoreStates(const StatePack<N>* s, float* state0, float* state1, const int64_t at0,
+                                            const int64_t at1) {
+  if constexpr (kStates > 1) s[1].Store(state1 + at1);
+  if constexpr (kStates > 0) s[0].Store(state0 + at0);
 }
 
 //! The row that addresses an entry's state: the table row, or (kPlaced) the entry's own place for it.
@@ -225,6 +228,13 @@ template <bool kPlaced>
 __device__ __forceinline__ int64_t StateRow(const int64_t table_row, const int64_t placed_row) {
   if constexpr (kPlaced) return placed_row;
   else return table_row;
+}
+//! The row that addresses an entry in `state1`: like state0's, or (kPlacedTwice) a second place of its own.
+template <bool kPlaced, bool kPlacedTwice>
+__device__ __forceinline__ int64_t State1Row(const int64_t table_row, const int64_t placed_row,
+                                             const int64_t placed1_row) {
+  if constexpr (kPlacedTwice) return placed1_row;
+  else return StateRow<kPlaced>(table_row, placed_row);
 }
 
 /**
@@ -236,21 +246,28 @@ __device__ __forceinline__ int64_t StateRow(const int64_t table_row, const int64
  * the weights still go by ids[k].  That is what a state plane behind the row cache needs (row_cache.hpp): one translated
  * id cannot reach both the cached weights and the cached state.  A separate instantiation: without kPlaced nothing of
  * state_ids is compiled in.
+ * kPlacedTwice (with kPlaced, a rule with a state1): state0 still goes by state_ids[k], but state1 -- the second
+ * per-element tensor, or the row words of a rule that keeps them there -- goes by state1_ids[k].  That is what the Adam
+ * family behind the cache needs: exp_avg and exp_avg_sq are two allocations, each with a cached plane a whole number of
+ * ITS rows away, so their row offsets differ (and, row-wise, their row sizes: 4 * width against 4 bytes).  Again a
+ * separate instantiation: without kPlacedTwice nothing of state1_ids is compiled in.
  * kEntries entries are in flight per group: 2 when a lane holds one slice per entry (kChunks == 1), else 1.  With the
  * two moment packs of an Adam slice next to its weights and gradient, two entries take 32 (fp32) to 48 (16-bit)
  * registers of row data per lane: every kChunks == 1 instantiation stays free of scratch and at or above 4 waves per
  * SIMD (profiles/sparse_adam_kernel_resources.txt; the four-slice Adam bodies of the 16-bit types run at 2).
  */
 template <typename ElemT, typename IndexT, int N, int kChunks, int kEntries, bool kStochastic, bool kPlaced = false,
-          typename RuleT>
+          bool kPlacedTwice = false, typename RuleT>
 __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, const ElemT* __restrict__ rows,
                                               ElemT* __restrict__ table, float* __restrict__ state0,
                                               float* __restrict__ state1, const int width, const int lanes_per_row,
                                               const int group, const int64_t piece_rows, const int pieces,
                                               const UpdateCounts& counts, const UpdateRounding<kStochastic>& rounding,
-                                              const RuleT& rule, const int64_t* __restrict__ state_ids = nullptr) {
+                                              const RuleT& rule, const int64_t* __restrict__ state_ids = nullptr,
+                                              const int64_t* __restrict__ state1_ids = nullptr) {
   static_assert(!kStochastic || sizeof(ElemT) == 2, "stochastic rounding is for the 16-bit table types");
   static_assert(!(kPlaced && kStochastic), "the rounding bits are named by the table row: no second place for them");
+  static_assert(!kPlacedTwice || (kPlaced && RuleT::kStates >= 1), "a second placed id is for a rule with a state1");
   static_assert(kEntries == 1 || (kEntries == 2 && kChunks == 1), "two entries in flight: one slice per lane");
   using RoundT = SliceRounding<ElemT, N, kStochastic>;
   constexpr int kStates = RuleT::kStates;
@@ -258,6 +275,11 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
   constexpr int kHeld = kStates > 0 ? kStates : 1;
   constexpr int kSlices = kChunks == 0 ? 1 : kChunks;
   float* const row_words = kStates == 0 ? state0 : state1;   // (only read if kRowState)
+  // the row of an entry's row word: it lives in state0 and goes by state0's row, or in state1 and goes by state1's
+  const auto word_row = [](const int64_t table_row, const int64_t placed_row, const int64_t placed1_row) {
+    if constexpr (kStates == 0) return StateRow<kPlaced>(table_row, placed_row);
+    else return State1Row<kPlaced, kPlacedTwice>(table_row, placed_row, placed1_row);
+  };
   uint64_t seed = 0, round_step = 0;
   if constexpr (kStochastic) {
     seed = rounding.seed;
@@ -287,6 +309,12 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
         if constexpr (kPlaced) placed[u] = live[u] ? state_ids[base + k + u * stride] : 0;
         else placed[u] = 0;
       }
+      int64_t placed1[kEntries];   // (kPlacedTwice: where entry u's state1 lives)
+#pragma unroll
+      for (int u = 0; u < kEntries; ++u) {
+        if constexpr (kPlacedTwice) placed1[u] = live[u] ? state1_ids[base + k + u * stride] : 0;
+        else placed1[u] = 0;
+      }
       if constexpr (kChunks == 0) {
         // any width: slices lane, lane + group, ... one after the other (a rule with a row word reads the gradient row
         // twice, the second time out of the cache it has just been loaded into)
@@ -294,20 +322,22 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
         ElemT* w_row = const_cast<ElemT*>(RowPtr(table, r[0], width));
         float row = 0.f;
         if constexpr (kRowState) {
-          const float before = row_words[StateRow<kPlaced>(r[0], placed[0])];
+          const float before = row_words[word_row(r[0], placed[0], placed1[0])];
           float sum = 0.f;
           for (int c = lane; c < lanes_per_row; c += group) sum = AddSquares(sum, LoadPack<ElemT, N>(g_row + c * N));
-          row = rule.Row(row_words + StateRow<kPlaced>(r[0], placed[0]), before, GroupSum(sum, group), width, lane == 0);
+          row = rule.Row(row_words + word_row(r[0], placed[0], placed1[0]), before, GroupSum(sum, group), width, lane == 0);
         }
         for (int c = lane; c < lanes_per_row; c += group) {
           const Pack<ElemT, N> g = kRowState ? LoadPack<ElemT, N>(g_row + c * N) : LoadPackStreaming<ElemT, N>(g_row + c * N);
           const Pack<ElemT, N> w = LoadPack<ElemT, N>(w_row + c * N);
           StatePack<N> s[kHeld];
-          LoadStates<kStates>(s, state0, state1, RowElems(StateRow<kPlaced>(r[0], placed[0]), width) + c * N);
+          LoadStates<kStates>(s, state0, state1, RowElems(StateRow<kPlaced>(r[0], placed[0]), width) + c * N,
+                              RowElems(State1Row<kPlaced, kPlacedTwice>(r[0], placed[0], placed1[0]), width) + c * N);
           RoundT round;
           if constexpr (kStochastic) round = RoundT(seed, round_step, r[0], c * N);
           StorePack<ElemT, N>(w_row + c * N, rule.Slice(w, g, s, row, round));
-          StoreStates<kStates>(s, state0, state1, RowElems(StateRow<kPlaced>(r[0], placed[0]), width) + c * N);
+          StoreStates<kStates>(s, state0, state1, RowElems(StateRow<kPlaced>(r[0], placed[0]), width) + c * N,
+                               RowElems(State1Row<kPlaced, kPlacedTwice>(r[0], placed[0], placed1[0]), width) + c * N);
         }
       } else {
         Pack<ElemT, N> g[kEntries][kSlices], w[kEntries][kSlices];
@@ -317,7 +347,7 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
         RoundT round[kEntries][kSlices];
 #pragma unroll
         for (int u = 0; u < kEntries; ++u) {
-          if constexpr (kRowState) row_word[u] = live[u] ? row_words[StateRow<kPlaced>(r[u], placed[u])] : 0.f;
+          if constexpr (kRowState) row_word[u] = live[u] ? row_words[word_row(r[u], placed[u], placed1[u])] : 0.f;
 #pragma unroll
           for (int c = 0; c < kSlices; ++c) {
             const int col = (lane + c * group) * N;
@@ -325,7 +355,8 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
             if (has[u][c]) {
               g[u][c] = LoadPackStreaming<ElemT, N>(RowPtr(rows, base + k + u * stride, width) + col);
               w[u][c] = LoadPack<ElemT, N>(RowPtr(table, r[u], width) + col);
-              LoadStates<kStates>(s[u][c], state0, state1, RowElems(StateRow<kPlaced>(r[u], placed[u]), width) + col);
+              LoadStates<kStates>(s[u][c], state0, state1, RowElems(StateRow<kPlaced>(r[u], placed[u]), width) + col,
+                                  RowElems(State1Row<kPlaced, kPlacedTwice>(r[u], placed[u], placed1[u]), width) + col);
             }
           }
         }
@@ -348,7 +379,7 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
               if (has[u][c]) sum = AddSquares(sum, g[u][c]);
             sum = GroupSum(sum, group);
             if (live[u])
-              row = rule.Row(row_words + StateRow<kPlaced>(r[u], placed[u]), row_word[u], sum, width, lane == 0);
+              row = rule.Row(row_words + word_row(r[u], placed[u], placed1[u]), row_word[u], sum, width, lane == 0);
           }
 #pragma unroll
           for (int c = 0; c < kSlices; ++c) {
@@ -356,7 +387,8 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
             const int col = (lane + c * group) * N;
             ElemT* w_at = const_cast<ElemT*>(RowPtr(table, r[u], width)) + col;
             StorePack<ElemT, N>(w_at, rule.Slice(w[u][c], g[u][c], s[u][c], row, round[u][c]));
-            StoreStates<kStates>(s[u][c], state0, state1, RowElems(StateRow<kPlaced>(r[u], placed[u]), width) + col);
+            StoreStates<kStates>(s[u][c], state0, state1, RowElems(StateRow<kPlaced>(r[u], placed[u]), width) + col,
+                                  RowElems(State1Row<kPlaced, kPlacedTwice>(r[u], placed[u], placed1[u]), width) + col);
           }
         }
       }

@@ -23,7 +23,11 @@ device from each batch's own indices, so that a host-resident table can be read 
     cache.flush()                                                                # dirty rows back to the host table
 
 With rule="adagrad" / "rowwise_adagrad" the optimizer's fp32 state rides on the cache slots as a second plane and
-cache.apply_update(...) is that rule's step through the cache; cache.state is the host side of the state."""
+cache.apply_update(...) is that rule's step through the cache; cache.state is the host side of the state.
+
+AdamRowCache is the same cache for the Adam family: the two moments ride on the cache slots as two state planes, and
+cache.apply_update(...) is SparseAdamUpdater.apply through the cache (clock, prefetch, one translate for the three
+planes, one placed Adam launch)."""
 import ctypes
 
 import torch
@@ -164,6 +168,27 @@ def cache_set_of(row, num_sets):
     return (((h >> np.uint64(32)) * np.uint64(num_sets)) >> np.uint64(32)).astype(np.int64)
 
 
+def _check_table_arguments(host_table, num_sets):
+    """What a device-managed cache asks of its table and its size, short of where the table lives."""
+    if not isinstance(host_table, torch.Tensor):
+        raise TypeError("host_table must be a torch.Tensor")
+    if host_table.dtype not in _ops._ELEM:
+        raise TypeError("table must be float32, float16 or bfloat16")
+    if isinstance(num_sets, bool) or not isinstance(num_sets, int):
+        raise TypeError("num_sets must be an int")
+    if not 1 <= num_sets <= 1 << 24:
+        raise ValueError("num_sets must be in [1, 2**24], got %d" % num_sets)
+    if host_table.dim() != 2 or not host_table.is_contiguous() or host_table.shape[0] < 1:
+        raise ValueError("host_table must be a contiguous 2-D tensor with at least one row")
+    if (host_table.shape[1] * host_table.element_size()) % 4:
+        raise ValueError("row size must be a multiple of 4 bytes")
+
+
+def _check_pinned(name, t):
+    if t.is_cuda or not t.is_pinned():
+        raise ValueError("%s must live in PINNED host memory (tensor.pin_memory())" % name)
+
+
 class DynamicRowCache(CachedHostTable):
     """Device-managed cache of a host-resident table: `num_sets` sets of 64 ways (capacity_rows = 64 * num_sets) in HBM,
     LRU per set, write-back.  All state lives on the device -- tags int64 [S, 64] (-1 = empty), stamps uint32 [S, 64]
@@ -198,18 +223,7 @@ class DynamicRowCache(CachedHostTable):
 
     def __init__(self, host_table, device="cuda", num_sets=1024, rule="sgd", state=None, initial_accumulator_value=0.0,
                  eps=1e-8):
-        if not isinstance(host_table, torch.Tensor):
-            raise TypeError("host_table must be a torch.Tensor")
-        if host_table.dtype not in _ops._ELEM:
-            raise TypeError("table must be float32, float16 or bfloat16")
-        if isinstance(num_sets, bool) or not isinstance(num_sets, int):
-            raise TypeError("num_sets must be an int")
-        if not 1 <= num_sets <= 1 << 24:
-            raise ValueError("num_sets must be in [1, 2**24], got %d" % num_sets)
-        if host_table.dim() != 2 or not host_table.is_contiguous() or host_table.shape[0] < 1:
-            raise ValueError("host_table must be a contiguous 2-D tensor with at least one row")
-        if (host_table.shape[1] * host_table.element_size()) % 4:
-            raise ValueError("row size must be a multiple of 4 bytes")
+        _check_table_arguments(host_table, num_sets)
         if not isinstance(rule, str) or rule not in _ops.UPDATE_RULES:
             raise ValueError("rule must be one of %r, got %r" % (sorted(_ops.UPDATE_RULES), rule))
         state_shape = {"sgd": None, "adagrad": tuple(host_table.shape), "rowwise_adagrad": (host_table.shape[0],)}[rule]
@@ -223,8 +237,7 @@ class DynamicRowCache(CachedHostTable):
             if tuple(state.shape) != state_shape or not state.is_contiguous():
                 raise ValueError("rule=%r needs a contiguous state of shape %r, got %r" % (rule, state_shape,
                                                                                          tuple(state.shape)))
-            if state.is_cuda or not state.is_pinned():
-                raise ValueError("state must live in PINNED host memory (tensor.pin_memory())")
+            _check_pinned("state", state)
         if host_table.is_cuda or not host_table.is_pinned():
             raise ValueError("host_table must live in PINNED host memory (tensor.pin_memory())")
         super().__init__(host_table, device=device, capacity_rows=WAYS * num_sets)
@@ -235,17 +248,8 @@ class DynamicRowCache(CachedHostTable):
             if state is None:
                 state = torch.full(state_shape, float(initial_accumulator_value), dtype=torch.float32).pin_memory()
             self.state = state
-            # the cached plane, like the rows: over-allocate by one state row and start where
-            # (state_cache - state) % state_row_bytes == 0
-            per_row = self.width if rule == "adagrad" else 1
-            self.state_row_bytes = 4 * per_row
-            slots = WAYS * num_sets
-            self._raw_state = torch.empty(((slots + 1) * self.state_row_bytes,), dtype=torch.uint8, device=self.device)
-            shift = (state.data_ptr() - self._raw_state.data_ptr()) % self.state_row_bytes
-            plane = self._raw_state[shift:shift + slots * self.state_row_bytes].view(torch.float32)
-            self.state_cache = plane.view(slots, self.width) if rule == "adagrad" else plane
-            assert (self.state_cache.data_ptr() - state.data_ptr()) % self.state_row_bytes == 0
-            self.state_row_offset = (self.state_cache.data_ptr() - state.data_ptr()) // self.state_row_bytes
+            self.state_row_bytes = 4 * (self.width if rule == "adagrad" else 1)
+            self._raw_state, self.state_cache, self.state_row_offset = self._plane_behind(state, WAYS * num_sets)
         self.num_sets = num_sets
         self.capacity_rows = WAYS * num_sets
         self.row_bytes = self.width * host_table.element_size()
@@ -270,9 +274,30 @@ class DynamicRowCache(CachedHostTable):
                 p(self.tags.data_ptr()), p(self.stamps.data_ptr()), p(self.dirty.data_ptr()),
                 p(self.slot_of_row.data_ptr()), p(self.words.data_ptr()))
 
+    def _plane_behind(self, home, slots):
+        """(raw buffer, cached plane, row offset) of a state tensor `home` ([rows, width] or [rows] float32): `slots`
+        of its rows on the device, like the cached table rows -- over-allocated by one row so that the plane can start
+        where (plane - home) % row_bytes == 0, row_offset = (plane - home) / row_bytes."""
+        row_bytes = 4 * (home.shape[1] if home.dim() == 2 else 1)
+        raw = torch.empty(((slots + 1) * row_bytes,), dtype=torch.uint8, device=self.device)
+        shift = (home.data_ptr() - raw.data_ptr()) % row_bytes
+        plane = raw[shift:shift + slots * row_bytes].view(torch.float32)
+        if home.dim() == 2:
+            plane = plane.view(slots, home.shape[1])
+        assert (plane.data_ptr() - home.data_ptr()) % row_bytes == 0
+        return raw, plane, (plane.data_ptr() - home.data_ptr()) // row_bytes
+
     def _plane(self):
         p = ctypes.c_void_p
         return (p(self.state.data_ptr()), p(self.state_cache.data_ptr()), self.state_row_bytes)
+
+    def _call_with_planes(self, name, args):
+        """The entry point `name` of the cache's planes: the table's alone, or with the state plane."""
+        with torch.cuda.device(self.device):
+            if self.state is None:
+                getattr(_lib.lib(), name)(*args)
+            else:
+                getattr(_lib.lib(), name + "_with_state")(*(args + self._plane()))
 
     def _counts(self, ids, count, last_id):
         """(num_valid, count word, word is int64, last_id word) of a prefetch, validated."""
@@ -312,11 +337,7 @@ class DynamicRowCache(CachedHostTable):
         args = self._state() + (_ops._ptr(indices), it, n, num_valid, _ops._ptr(count_word), int(word64),
                                 _ops._ptr(last_word), int(bool(for_update)), ctypes.c_void_p(self._work.data_ptr()),
                                 ctypes.byref(lwork), _ops._stream(indices))
-        with torch.cuda.device(self.device):
-            if self.state is None:
-                L.cuembed_row_cache_prefetch(*args)
-            else:
-                L.cuembed_row_cache_prefetch_with_state(*(args + self._plane()))
+        self._call_with_planes("cuembed_row_cache_prefetch", args)
         return None
 
     def forward(self, indices, offsets=None, weights=None, batch_size=None, num_hots=0, mode="sum", use_cache=True,
@@ -351,7 +372,8 @@ class DynamicRowCache(CachedHostTable):
         table AND the host state over PCIe: no update is dropped.  Round to nearest; no read-back."""
         self._apply(ids, rows, lr, count, last_id)
 
-    def _apply(self, ids, rows, lr, count, last_id):
+    def _check_step(self, ids, rows, lr):
+        """The arguments of a step, validated: (lr as a float, lr as a device word or None)."""
         for name, t in (("ids", ids), ("rows", rows)):
             if not isinstance(t, torch.Tensor):
                 raise TypeError("%s must be a torch.Tensor" % name)
@@ -367,6 +389,10 @@ class DynamicRowCache(CachedHostTable):
             lr_word, lr = lr, 0.0
             _ops._check_dev("lr", lr_word, self.device)
         _ops._check_dev("rows", rows, self.device)
+        return lr, lr_word
+
+    def _apply(self, ids, rows, lr, count, last_id):
+        lr, lr_word = self._check_step(ids, rows, lr)
         _ops._check_alignment("table", self.table.data_ptr(), self.table.element_size(), self.width,
                               others=(("rows", rows.data_ptr()),),
                               state=(("state", self.state.data_ptr()),) if self.rule == "adagrad" else (), max_lanes=None)
@@ -394,11 +420,7 @@ class DynamicRowCache(CachedHostTable):
         """Store every dirty cached row to the host table and clear the dirty bytes (stream-ordered: synchronise
         before reading the table on the host)."""
         args = self._state() + (ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream),)
-        with torch.cuda.device(self.device):
-            if self.state is None:
-                _lib.lib().cuembed_row_cache_flush(*args)
-            else:
-                _lib.lib().cuembed_row_cache_flush_with_state(*(args + self._plane()))
+        self._call_with_planes("cuembed_row_cache_flush", args)
 
     def invalidate(self):
         """Drop every cached row (and its cached state) WITHOUT writing dirty ones back.  The clock and the counters go
@@ -412,3 +434,110 @@ class DynamicRowCache(CachedHostTable):
         """The device counters as a dict (STAT_WORDS).  The only call that synchronises."""
         words = self.words.cpu().tolist()
         return dict(zip(STAT_WORDS, words))
+
+
+class AdamRowCache(DynamicRowCache):
+    """DynamicRowCache for a table trained with the Adam family: lazy Adam (torch.optim.SparseAdam's formula) or, with
+    rowwise=True, row-wise Adam -- optim.SparseAdamUpdater's counterpart for a table in pinned host memory, as
+    DynamicRowCache(rule="adagrad") is SparseUpdater's.  The result is bit for bit the table and the moments that
+    SparseAdamUpdater produces on device copies (round to nearest; there is no stochastic rounding through the cache).
+
+    The moments live in pinned host memory like the table -- cache.exp_avg float32 [rows, width], cache.exp_avg_sq
+    float32 [rows, width], or [rows] with rowwise=True: the shapes SparseAdamUpdater owns; zero-filled and pinned when not
+    given -- and are cached slot for slot next to the rows as TWO STATE PLANES (cache.exp_avg_cache,
+    cache.exp_avg_sq_cache), each a whole number of its own rows away from its host tensor.  Both moment rows move with
+    their table row: host -> cache on EVERY fill (a forward-only fill too), cache -> host when a dirty row is evicted
+    or flushed; one dirty byte covers all three planes, the counters count rows, and placement is DynamicRowCache's.
+    Like the table, the moments are current on the host only after flush() and a synchronise; invalidate() drops the
+    cached ones without write-back.
+
+    The bias-factor clock is SparseAdamUpdater's and lives on the device: cache.powers float64 [3] = (t, beta1^t,
+    beta2^t), starting at (0, 1, 1), and cache.bias_factor float32 [1].  apply_update() advances it on every call.
+
+    What a fill costs over PCIe, for a 16-bit row of width W: 2 * W + 8 * W bytes with lazy Adam (the row and two
+    moment rows: five times the row), 2 * W + 4 * W + 4 bytes with row-wise Adam (the row, exp_avg's row and one word).
+    Row-wise Adam is the rule to prefer behind the cache for that reason."""
+
+    def __init__(self, host_table, device="cuda", num_sets=1024, rowwise=False, betas=(0.9, 0.999), eps=1e-8,
+                 weight_decay=0.0, bias_correction=True, exp_avg=None, exp_avg_sq=None):
+        _check_table_arguments(host_table, num_sets)
+        betas = _ops._check_betas(betas)
+        if not float(eps) >= 0.0 or not float(weight_decay) >= 0.0:
+            raise ValueError("eps and weight_decay must not be negative")
+        rowwise = bool(rowwise)
+        rows, width = host_table.shape
+        shapes = dict(exp_avg=(rows, width), exp_avg_sq=(rows,) if rowwise else (rows, width))
+        for name, t in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s must be a torch.Tensor" % name)
+            if t.dtype != torch.float32:
+                raise TypeError("%s must be float32, got %s" % (name, t.dtype))
+            if tuple(t.shape) != shapes[name] or not t.is_contiguous():
+                raise ValueError("rowwise=%r needs a contiguous %s of shape %r, got %r" % (rowwise, name, shapes[name],
+                                                                                         tuple(t.shape)))
+            _check_pinned(name, t)
+        super().__init__(host_table, device=device, num_sets=num_sets, eps=eps)
+        self.rule = "rowwise_adam" if rowwise else "adam"        # (apply_sgd points to apply_update)
+        self.rowwise, self.betas, self.weight_decay = rowwise, betas, float(weight_decay)
+        self.bias_correction = bool(bias_correction)
+        self.exp_avg = torch.zeros(shapes["exp_avg"], dtype=torch.float32).pin_memory() if exp_avg is None else exp_avg
+        self.exp_avg_sq = (torch.zeros(shapes["exp_avg_sq"], dtype=torch.float32).pin_memory() if exp_avg_sq is None
+                           else exp_avg_sq)
+        slots = WAYS * num_sets
+        self._raw_exp_avg, self.exp_avg_cache, self.exp_avg_row_offset = self._plane_behind(self.exp_avg, slots)
+        self._raw_exp_avg_sq, self.exp_avg_sq_cache, self.exp_avg_sq_row_offset = self._plane_behind(self.exp_avg_sq, slots)
+        self.powers, self.bias_factor = _ops.new_adam_clock(self.device)
+        self._one = None if self.bias_correction else torch.ones((1,), dtype=torch.float32, device=self.device)
+        self._placed = None
+
+    def _call_with_planes(self, name, args):
+        p = ctypes.c_void_p
+        planes = (p(self.exp_avg.data_ptr()), p(self.exp_avg_cache.data_ptr()), 4 * self.width,
+                  p(self.exp_avg_sq.data_ptr()), p(self.exp_avg_sq_cache.data_ptr()), 4 if self.rowwise else 4 * self.width)
+        with torch.cuda.device(self.device):
+            getattr(_lib.lib(), name + "_with_states")(*(args + planes))
+
+    def apply_update(self, ids, rows, lr, count=None, last_id=None):
+        """One Adam step through the cache, call for call SparseAdamUpdater.apply: for every valid entry k of the
+        compressed gradient (ids, rows) -- arguments as for DynamicRowCache.apply_sgd -- row ids[k] of the table and
+        its two moments are updated by ops.sparse_row_adam's arithmetic.  In order: the clock advances on the device
+        (on EVERY call, also one with no entries or count=0); prefetch(ids, for_update=True); ONE launch translates
+        the ids for the three planes; ONE launch of the sparse Adam step with placed moments updates resident rows and
+        their moments in HBM, with the count the prefetch resolved.  Rows their set has no way for are updated in
+        place in the host table AND both host moments over PCIe: no update is dropped.  lr: a float or a one-element
+        float32 device tensor.  bias_correction=False feeds a constant 1 (the clock still counts).  Round to nearest;
+        no read-back."""
+        lr, lr_word = self._check_step(ids, rows, lr)
+        state = (("exp_avg", self.exp_avg.data_ptr()),)
+        if not self.rowwise:
+            state += (("exp_avg_sq", self.exp_avg_sq.data_ptr()),)
+        _ops._check_alignment("table", self.table.data_ptr(), self.table.element_size(), self.width,
+                              others=(("rows", rows.data_ptr()),), state=state, max_lanes=None)
+        _ops.adam_clock_advance(self.powers, self.bias_factor, self.betas)
+        self.prefetch(ids, for_update=True, count=count, last_id=last_id)
+        n = ids.numel()
+        if n == 0:
+            return None
+        if self._placed is None or self._placed.shape[1] < n:
+            self._placed = torch.empty((3, n), dtype=torch.int64, device=self.device)
+        placed = [self._placed[k, :n] for k in range(3)]
+        # the count of valid entries as the prefetch resolved it on the device: one int64 word
+        resolved = self.words[STAT_WORDS.index("batch_count"):STAT_WORDS.index("batch_count") + 1]
+        beta1, beta2 = self.betas
+        bias = self.bias_factor if self.bias_correction else self._one
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            L.cuembed_translate_indices_for_row_cache_planes(
+                _ops._ptr(ids), _ops._INDEX[ids.dtype], n, _ops._ptr(self.slot_of_row), self.rows,
+                self.cache_row_offset, _ops._ptr(placed[0]), self.exp_avg_row_offset, _ops._ptr(placed[1]),
+                self.exp_avg_sq_row_offset, _ops._ptr(placed[2]), _ops._stream(ids))
+            L.cuembed_sparse_row_adam_placed(
+                ctypes.c_void_p(self.table.data_ptr()), _ops._ELEM[self.table.dtype], self.width,
+                ctypes.c_void_p(self.exp_avg.data_ptr()), ctypes.c_void_p(self.exp_avg_sq.data_ptr()),
+                _ops.ADAM_RULES[self.rule], _ops._ptr(placed[0]), _ops._INDEX[torch.int64], _ops._ptr(rows), n, 1, -1,
+                _ops._ptr(resolved), 1, None, float(lr), _ops._ptr(lr_word), 1.0, _ops._ptr(bias), beta1, 1.0 - beta1,
+                beta2, 1.0 - beta2, self.eps, self.weight_decay, _ops._stream(ids), _ops._ptr(placed[1]),
+                _ops._ptr(placed[2]))
+        return None

@@ -347,6 +347,17 @@ void cuembed_translate_indices_for_row_cache(const void* indices, int index_type
                                              const int32_t* slot_of_row, int64_t num_rows,
                                              int64_t cache_row_offset, int64_t* translated,
                                              cuembed_stream_t stream);
+/* The same translation for up to three planes of one cache in ONE launch (cuembed::TranslateIndicesForRowCachePlanes):
+ * a table behind the device-managed row cache whose optimizer state rides on the cache slots has a cached plane per
+ * tensor, each a whole number of its own rows away from its home tensor.  slot_of_row is read once per index and
+ * translatedP[i] = slot >= 0 ? cache_row_offsetP + slot : indices[i] for P = 0, 1, 2; a NULL output is skipped.  Per
+ * output exactly the call above: indices outside [0, num_rows) pass through unchanged. */
+void cuembed_translate_indices_for_row_cache_planes(const void* indices, int index_type, int64_t nnz,
+                                                    const int32_t* slot_of_row, int64_t num_rows,
+                                                    int64_t cache_row_offset0, int64_t* translated0,
+                                                    int64_t cache_row_offset1, int64_t* translated1,
+                                                    int64_t cache_row_offset2, int64_t* translated2,
+                                                    cuembed_stream_t stream);
 
 /* ---- extension: device-managed row cache (cuembed::RowCachePrefetch / RowCacheFlush, row_cache.hpp) ----
  * A set-associative LRU write-back cache behind the hook above: num_sets sets of 64 ways in the device buffer
@@ -393,6 +404,26 @@ void cuembed_row_cache_flush_with_state(void* table, void* cache_rows, int64_t r
                                         int64_t* tags, uint32_t* stamps, void* dirty, int32_t* slot_of_row,
                                         uint64_t* words, cuembed_stream_t stream, float* state, float* state_cache,
                                         int64_t state_row_bytes);
+/* The same two calls for a cache with TWO state planes (the Adam family: state = exp_avg, state2 = exp_avg_sq, 4 * width
+ * bytes a row, or 4 for row-wise Adam's word).  state2 / state2_cache are laid out and moved exactly like state /
+ * state_cache: with its table row on every fill, every dirty eviction and every flush, the second plane first, then the
+ * first, then the table's rows; the table's move alone clears the dirty bytes and counts the write-backs.  One dirty
+ * byte covers all planes, the counters count rows.  cuembed_translate_indices_for_row_cache_planes gives the three id
+ * arrays of cuembed_sparse_row_adam_placed.  state2_row_bytes == 0: one plane, the calls above; a second plane without
+ * a first (state_row_bytes == 0) aborts. */
+void cuembed_row_cache_prefetch_with_states(void* table, void* cache_rows, int64_t row_bytes, int64_t num_rows,
+                                            int num_sets, int64_t* tags, uint32_t* stamps, void* dirty,
+                                            int32_t* slot_of_row, uint64_t* words, const void* indices, int index_type,
+                                            int64_t nnz, int64_t num_valid, const void* count, int count_is_int64,
+                                            const void* last_id, int for_update, char* work, size_t* lwork,
+                                            cuembed_stream_t stream, float* state, float* state_cache,
+                                            int64_t state_row_bytes, float* state2, float* state2_cache,
+                                            int64_t state2_row_bytes);
+void cuembed_row_cache_flush_with_states(void* table, void* cache_rows, int64_t row_bytes, int64_t num_rows,
+                                         int num_sets, int64_t* tags, uint32_t* stamps, void* dirty,
+                                         int32_t* slot_of_row, uint64_t* words, cuembed_stream_t stream, float* state,
+                                         float* state_cache, int64_t state_row_bytes, float* state2,
+                                         float* state2_cache, int64_t state2_row_bytes);
 
 /* ---- extension: gradient w.r.t. the per-lookup weights ---------------------- */
 /* grad_weights[s, j] = dot(params[indices[s, j], :], grad_y[s, :]); one entry per lookup;
@@ -619,6 +650,19 @@ void cuembed_sparse_row_adam(void* table, int elem_type, int embed_width, float*
                              const float* lr_device, float bias_factor, const float* bias_factor_device, float beta1,
                              float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float weight_decay,
                              cuembed_stream_t stream);
+/* The same step with the moments in places of their own: entry k updates table[ids[k], :] but reads and writes its
+ * first moment at row exp_avg_ids[k] of exp_avg and its second at row exp_avg_sq_ids[k] of exp_avg_sq (CUEMBED_ADAM: a
+ * row of embed_width elements; CUEMBED_ROWWISE_ADAM: the row's word).  For a table behind the row cache with two state
+ * planes: the three id arrays are the batch's ids translated with the three planes' row offsets.  Round to nearest;
+ * same lane bytes, launch shape and walk as the call above, hence the same bits.  Both id arrays NULL: the call above;
+ * exactly one of them NULL aborts. */
+void cuembed_sparse_row_adam_placed(void* table, int elem_type, int embed_width, float* exp_avg, float* exp_avg_sq,
+                                    int rule, const void* ids, int index_type, const void* rows, int64_t piece_rows,
+                                    int pieces, int64_t num_rows, const void* counts, int counts_are_int64,
+                                    const void* last_id, float lr, const float* lr_device, float bias_factor,
+                                    const float* bias_factor_device, float beta1, float one_minus_beta1, float beta2,
+                                    float one_minus_beta2, float eps, float weight_decay, cuembed_stream_t stream,
+                                    const int64_t* exp_avg_ids, const int64_t* exp_avg_sq_ids);
 /* cuembed_sparse_row_adam with STOCHASTIC ROUNDING of the one rounding to the table's type (elem_type CUEMBED_F16 or
  * CUEMBED_BF16): the rule and the random bits of (seed, step, table row, column) are those of
  * cuembed_sparse_row_update_stochastic; the fp32 arithmetic and the fp32 moments are those of cuembed_sparse_row_adam. */
