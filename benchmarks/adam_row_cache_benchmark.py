@@ -18,6 +18,10 @@ cache's flush) is recorded.  A fill moves 2 * W + 8 * W bytes of a 16-bit row wi
 row-wise Adam; the report states both next to the timings.
 
     python benchmarks/adam_row_cache_benchmark.py --out profiles/row_cache_adam_timing.json [--commit ID]
+
+--stochastic-rounding times the step THROUGH THE CACHE with its two roundings instead (dynamic_row_cache_benchmark.py's
+rounding_legs): `nearest`, AdamRowCache, against `stochastic`, AdamRowCache(stochastic_rounding=True); the bit check's
+other side is optim.SparseAdamUpdater(stochastic_rounding=True) with the same seed on a device copy.
 """
 import argparse
 import ctypes
@@ -150,6 +154,23 @@ def one_rule(torch, ce, a, batches, source_table, rowwise):
                 same_bits_on_shared_gradients=dict(steps=len(checked), forward_outputs_tables_and_moments_equal=same_bits))
 
 
+def one_rule_roundings(torch, ce, a, batches, source_table, rowwise):
+    """--stochastic-rounding: one rule through the cache, to nearest and stochastically."""
+    from cuembed_amd.optim import SparseAdamUpdater
+    from cuembed_amd.row_cache import AdamRowCache
+
+    def make_cache(stochastic):
+        kw = dict(stochastic_rounding=True, seed=a.seed) if stochastic else {}
+        return AdamRowCache(pinned_copy(torch, source_table), "cuda", num_sets=a.num_sets, rowwise=rowwise, betas=BETAS,
+                            eps=EPS, **kw)
+
+    got = D.rounding_legs(torch, ce, a, batches, make_cache,
+                          lambda: SparseAdamUpdater(source_table.clone(), LR, betas=BETAS, eps=EPS, rowwise=rowwise,
+                                                    stochastic_rounding=True, seed=a.seed), LR)
+    return dict(step="forward + compressed backward (count on the device) + %s, through the cache"
+                     % ("row-wise Adam" if rowwise else "lazy Adam"), **got)
+
+
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--rows", type=int, default=1 << 22, help="table rows (a power of two)")
@@ -163,6 +184,8 @@ def main():
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--rule", choices=("both", "adam", "rowwise_adam"), default="both")
+    p.add_argument("--stochastic-rounding", action="store_true",
+                   help="the step through the cache with round to nearest against stochastic rounding")
     p.add_argument("--out", default=None, help="write the JSON here as well")
     p.add_argument("--commit", default=None, help="commit the tree was built from (default: git rev-parse)")
     a = p.parse_args()
@@ -178,11 +201,13 @@ def main():
     batches = D.make_batches(torch, a)
     rules = {}
     for rule in (("adam", "rowwise_adam") if a.rule == "both" else (a.rule,)):
-        rules[rule] = one_rule(torch, ce, a, batches, source_table, rowwise=rule == "rowwise_adam")
+        rules[rule] = (one_rule_roundings if a.stochastic_rounding else one_rule)(torch, ce, a, batches, source_table,
+                                                                                   rowwise=rule == "rowwise_adam")
         gc.collect()                       # the pinned tables and moments of one rule go before the next one's come
         torch.cuda.empty_cache()
     capacity = 64 * a.num_sets
-    report = dict(tool="benchmarks/adam_row_cache_benchmark.py", commit=D.commit_id(a.commit),
+    tool = "benchmarks/adam_row_cache_benchmark.py" + (" --stochastic-rounding" if a.stochastic_rounding else "")
+    report = dict(tool=tool, commit=D.commit_id(a.commit),
                   device=torch.cuda.get_device_name(0), torch=torch.__version__,
                   shape=dict(rows=a.rows, width=a.width, dtype="float16", batch=a.batch, hotness=a.hotness, alpha=a.alpha,
                              steps_per_pass=a.steps, hot_set_redrawn_every=a.redraw, cache_rows=capacity,
@@ -193,6 +218,12 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             f.write(text + "\n")
+    if a.stochastic_rounding:
+        print(json.dumps({rule: dict(summary={k: v["ms"] for k, v in r["ms_per_step"].items()},
+                                     stochastic_against_nearest=r["stochastic_against_nearest"],
+                                     same_bits=r["same_bits_as_the_stochastic_updater"]["forward_outputs_and_tables_equal"])
+                          for rule, r in rules.items()}))
+        return
     print(json.dumps({rule: dict(summary={k: r["ms_per_step"][k]["ms"] for k in r["ms_per_step"]},
                                  cache_against_host=r["cache_against_host"],
                                  cache_against_device=r["cache_against_device"],

@@ -34,6 +34,13 @@ gradients (one backward per step); whether their forward outputs, tables and sta
 cache's flush) is recorded.
 
     python benchmarks/dynamic_row_cache_benchmark.py --leg train --out profiles/row_cache_state_timing.json [--commit ID]
+
+--leg train --stochastic-rounding times the same training step THROUGH THE CACHE with its two roundings instead: `nearest`,
+DynamicRowCache(rule="rowwise_adagrad"), against `stochastic`, the same cache with stochastic_rounding=True (the named
+step: one more id array, and one widening launch for the int32 ids).  Same table, stream, cache size, warm-up and
+interleaved rounds; the verdict is worded the same way.  Before the timed passes the stochastic cache and
+optim.SparseUpdater(stochastic_rounding=True) with the same seed on a device copy run a few steps on shared gradients;
+whether they then hold the same bits is recorded.
 """
 import argparse
 import json
@@ -99,6 +106,90 @@ def verdict(x, y):
     if y["max"] < x["min"]:
         return "slower"
     return "the same within the spread"
+
+
+def rounding_legs(torch, ce, a, batches, make_cache, make_updater, lr):
+    """--stochastic-rounding: the training step through the cache with round to nearest and with stochastic rounding.
+    make_cache(stochastic) -> a cache on a pinned table of its own; make_updater() -> the stochastic updater on a device
+    copy, the bit check's other side.  Returns the report of one rule."""
+    cap = a.batch * a.hotness
+    caches = {"nearest": make_cache(False), "stochastic": make_cache(True)}
+    updater = make_updater()
+    g = torch.Generator(device="cuda")
+    g.manual_seed(a.seed + 1)
+    grad_y = (torch.randn((a.batch, a.width), device="cuda", generator=g) * 0.1).to(torch.float16)
+    out = torch.empty((a.batch, a.width), dtype=torch.float16, device="cuda")
+    grad = torch.empty((cap, a.width), dtype=torch.float16, device="cuda")
+    inv = torch.empty((cap,), dtype=torch.int32, device="cuda")
+
+    def backward(idx):
+        t_idx, t_sid, _, remap = ce.transpose_fixed_hotness(idx, a.batch, a.hotness, num_categories=a.rows, remapped=True)
+        ce.embedding_backward(grad_y, None, t_idx, t_sid, remap, grad_embedding=grad, inverse_mapping=inv)
+        return remap[-1:]
+
+    def step_of(cache):
+        def step(idx):
+            cache.forward(idx, num_hots=a.hotness, out=out)
+            cache.apply_update(inv, grad, lr, last_id=backward(idx))
+        return step
+
+    # before anything is timed: the stochastic cache and the stochastic updater on SHARED gradients, across a re-draw
+    checked = batches[:min(len(batches), a.redraw + 2)]
+    same_bits = True
+    for idx in checked:
+        caches["stochastic"].forward(idx, num_hots=a.hotness, out=out)
+        same_bits = same_bits and bool(torch.equal(out, ce.embedding_forward(updater.table, idx, num_hots=a.hotness)))
+        last = backward(idx)
+        caches["stochastic"].apply_update(inv, grad, lr, last_id=last)
+        updater.apply(inv, grad, last_id=last)
+    caches["stochastic"].flush()
+    torch.cuda.synchronize()
+    same_bits = bool(same_bits and torch.equal(caches["stochastic"].table, updater.table.cpu()) and
+                     int(caches["stochastic"].rounding_step) == int(updater.rounding_step) == len(checked))
+    del updater
+    sides = {name: step_of(cache) for name, cache in caches.items()}
+    for fn in sides.values():          # warm-up; the caches reach their steady state
+        time_pass(torch, fn, batches)
+    samples = {name: [] for name in sides}
+    for _ in range(a.rounds):
+        for name, fn in sides.items():
+            samples[name].append(time_pass(torch, fn, batches))
+    got = {name: summarise(v) for name, v in samples.items()}
+    for name in sides:
+        print("%-10s %.4f ms / step [%.4f, %.4f]" % (name, got[name]["ms"], got[name]["min"], got[name]["max"]), flush=True)
+    return dict(ms_per_step=got, stochastic_against_nearest=verdict(got["stochastic"], got["nearest"]),
+                same_bits_as_the_stochastic_updater=dict(steps=len(checked), forward_outputs_and_tables_equal=same_bits))
+
+
+def stochastic_training_leg(torch, ce, a, batches, host_table, device_table):
+    """--leg train --stochastic-rounding: row-wise Adagrad through the cache, to nearest and stochastically."""
+    from cuembed_amd.optim import SparseUpdater
+    from cuembed_amd.row_cache import DynamicRowCache
+    rule, lr, eps = "rowwise_adagrad", 0.01, 1e-8
+
+    def make_cache(stochastic):
+        table = torch.empty_like(host_table).pin_memory()
+        table.copy_(host_table)
+        kw = dict(stochastic_rounding=True, seed=a.seed) if stochastic else {}
+        return DynamicRowCache(table, "cuda", num_sets=a.num_sets, rule=rule, eps=eps, **kw)
+
+    got = rounding_legs(torch, ce, a, batches, make_cache,
+                        lambda: SparseUpdater(device_table, rule, lr, eps=eps, stochastic_rounding=True, seed=a.seed), lr)
+    capacity = 64 * a.num_sets
+    report = dict(tool="benchmarks/dynamic_row_cache_benchmark.py --leg train --stochastic-rounding",
+                  commit=commit_id(a.commit), device=torch.cuda.get_device_name(0), torch=torch.__version__,
+                  step="forward + compressed backward (count on the device) + row-wise Adagrad, through the cache",
+                  shape=dict(rows=a.rows, width=a.width, dtype="float16", batch=a.batch, hotness=a.hotness, alpha=a.alpha,
+                             steps_per_pass=a.steps, hot_set_redrawn_every=a.redraw, cache_rows=capacity,
+                             num_sets=a.num_sets, table_bytes=a.rows * a.width * 2), rounds=a.rounds, **got)
+    text = json.dumps(report, indent=1)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    print(json.dumps(dict(summary={k: v["ms"] for k, v in got["ms_per_step"].items()},
+                          stochastic_against_nearest=got["stochastic_against_nearest"],
+                          same_bits=got["same_bits_as_the_stochastic_updater"]["forward_outputs_and_tables_equal"])))
 
 
 def training_leg(torch, ce, a, batches, host_table, device_table):
@@ -222,6 +313,8 @@ def main():
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--leg", choices=("forward", "train"), default="forward",
                    help="forward: the four forwards (default); train: forward + backward + row-wise Adagrad, three ways")
+    p.add_argument("--stochastic-rounding", action="store_true",
+                   help="with --leg train: the step through the cache with round to nearest against stochastic rounding")
     p.add_argument("--out", default=None, help="write the JSON here as well")
     p.add_argument("--commit", default=None, help="commit the tree was built from (default: git rev-parse)")
     a = p.parse_args()
@@ -238,6 +331,10 @@ def main():
     host_table = torch.empty((a.rows, a.width), dtype=torch.float16).pin_memory()
     host_table.copy_(device_table)
     batches = make_batches(torch, a)
+    if a.stochastic_rounding and a.leg != "train":
+        sys.exit("--stochastic-rounding goes with --leg train")
+    if a.leg == "train" and a.stochastic_rounding:
+        return stochastic_training_leg(torch, ce, a, batches, host_table, device_table)
     if a.leg == "train":
         return training_leg(torch, ce, a, batches, host_table, device_table)
     capacity = 64 * a.num_sets

@@ -150,6 +150,8 @@ def _declare(L):
     L.cuembed_sparse_row_update_stochastic.restype = None
     L.cuembed_sparse_row_update_stochastic.argtypes = [_VP, _I, _I, _VP, _I, _VP, _I, _VP, _L, _I, _L, _VP, _I, _VP,
                                                        ctypes.c_float, _VP, ctypes.c_float, _U, _U, _VP, _VP]
+    L.cuembed_sparse_row_update_placed_stochastic.restype = None     # ... + state_ids, row_names
+    L.cuembed_sparse_row_update_placed_stochastic.argtypes = list(L.cuembed_sparse_row_update_stochastic.argtypes) + [_VP, _VP]
     L.cuembed_stochastic_rounding_words.restype = None
     L.cuembed_stochastic_rounding_words.argtypes = [_U, _U, _L, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
     L.cuembed_stochastic_round.restype = ctypes.c_uint16
@@ -166,6 +168,8 @@ def _declare(L):
     L.cuembed_sparse_row_adam_placed.argtypes = _adam + [_VP, _VP, _VP]    # ... + exp_avg_ids, exp_avg_sq_ids
     L.cuembed_sparse_row_adam_stochastic.restype = None
     L.cuembed_sparse_row_adam_stochastic.argtypes = _adam + [_U, _U, _VP, _VP]
+    L.cuembed_sparse_row_adam_placed_stochastic.restype = None       # ... + exp_avg_ids, exp_avg_sq_ids, row_names
+    L.cuembed_sparse_row_adam_placed_stochastic.argtypes = _adam + [_U, _U, _VP, _VP, _VP, _VP, _VP]
     L.cuembed_adam_clock_advance.restype = None
     L.cuembed_adam_clock_advance.argtypes = [_VP, _VP, ctypes.c_double, ctypes.c_double, _VP]
     L.cuembed_quantized_row_bytes.restype = _L

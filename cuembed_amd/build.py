@@ -22,7 +22,8 @@ HARNESS_PATH = os.path.join(LIB_DIR, "libcuembed_harness.so")
 OBJ_DIR = os.path.join(PKG, "build")
 UNITS = ["c_api_forward.hip", "c_api_backward.hip", "c_api_transforms.hip", "c_api_exchange.hip",
          "c_api_optimizer.hip", "c_api_optimizer_stochastic.hip", "c_api_optimizer_adam.hip",
-         "c_api_optimizer_adam_stochastic.hip", "c_api_quantized.hip", "c_api_grouped.hip",
+         "c_api_optimizer_adam_stochastic.hip", "c_api_optimizer_placed_stochastic.hip",
+         "c_api_optimizer_adam_placed_stochastic.hip", "c_api_quantized.hip", "c_api_grouped.hip",
          "c_api_grouped_backward.hip", "c_api_row_cache.hip"]
 ARCH = "gfx950"
 
@@ -307,6 +308,31 @@ def build_row_cache_adam_test(force=False):
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed for tests/cpp/row_cache_adam_kat.hip:\n" + r.stdout)
+    with open(stamp, "w") as f:
+        f.write(digest)
+    return exe
+
+
+def build_row_cache_stochastic_test(force=False):
+    """Compiles tests/cpp/row_cache_stochastic_kat.hip: cuembed::RowCachePrefetch / RowCacheFlush with one and two state
+    planes, cuembed::TranslateIndicesForRowCachePlanes and cuembed::SparseRowUpdate / SparseRowAdam with row_names
+    (stochastic rounding behind the cache) through the header-only API against a host recomputation with
+    stochastic_rounding.hpp's host functions.  Needs a GPU to RUN (tests/test_gpu_cpp_row_cache_stochastic.py)."""
+    src = os.path.join(ROOT, "tests", "cpp", "row_cache_stochastic_kat.hip")
+    exe = os.path.join(ROOT, "tests", "cpp", "row_cache_stochastic_kat")
+    stamp = exe + ".stamp"
+    deps = [src]
+    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
+        deps += [os.path.join(dirpath, f) for f in files]
+    digest = _digest_files(deps)
+    if not force and os.path.exists(exe) and os.path.exists(stamp):
+        with open(stamp) as f:
+            if f.read().strip() == digest:
+                return exe
+    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-munsafe-fp-atomics", "-I" + CSRC, src, "-o", exe]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("hipcc failed for tests/cpp/row_cache_stochastic_kat.hip:\n" + r.stdout)
     with open(stamp, "w") as f:
         f.write(digest)
     return exe

@@ -1,0 +1,37 @@
+// C ABI: the sparse Adam step with stochastic rounding behind the row cache (16-bit tables) = the named instantiations
+// of cuembed::SparseRowAdam (placed moments, rounding bits named by the table rows), in a unit of their own so that they
+// compile next to the other optimizer units.
+#include "c_api_optimizer_adam_common.hpp"
+
+extern "C" {
+
+void cuembed_sparse_row_adam_placed_stochastic(void* table, int elem_type, int embed_width, float* exp_avg,
+                                               float* exp_avg_sq, int rule, const void* ids, int index_type,
+                                               const void* rows, int64_t piece_rows, int pieces, int64_t num_rows,
+                                               const void* counts, int counts_are_int64, const void* last_id, float lr,
+                                               const float* lr_device, float bias_factor,
+                                               const float* bias_factor_device, float beta1, float one_minus_beta1,
+                                               float beta2, float one_minus_beta2, float eps, float weight_decay,
+                                               uint64_t seed, uint64_t step, const int64_t* step_device,
+                                               cuembed_stream_t stream, const int64_t* exp_avg_ids,
+                                               const int64_t* exp_avg_sq_ids, const int64_t* row_names) {
+  cuembed::SparseAdamOptions o = cuembed_c_api::AdamOptions(
+      rule, piece_rows, pieces, num_rows, counts, counts_are_int64, last_id, lr, lr_device, bias_factor,
+      bias_factor_device, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay);
+  cuembed_c_api::FillStochasticRounding(o, seed, step, step_device);
+  // (the named step alone: without names the call is cuembed_sparse_row_adam_stochastic's, and aborts here)
+#define ADAM(E, I)                                                                                                 \
+  cuembed::detail::SparseRowAdamNamed<E, I, cuembed::UpdateRoundings::kStochasticOnly>(                            \
+      static_cast<E*>(table), exp_avg, exp_avg_sq, embed_width, static_cast<const I*>(ids), static_cast<const E*>(rows), \
+      o, cuembed_c_api::Stream(stream), exp_avg_ids, exp_avg_sq_ids, row_names)
+  switch ((elem_type << 1) | index_type) {
+    case 2: ADAM(__half, int32_t); break;
+    case 3: ADAM(__half, int64_t); break;
+    case 4: ADAM(__hip_bfloat16, int32_t); break;
+    case 5: ADAM(__hip_bfloat16, int64_t); break;
+    default: CUEMBED_C_API_BAD_TYPE();   // (float tables have no rounding to randomise)
+  }
+#undef ADAM
+}
+
+}  // extern "C"

@@ -1,0 +1,33 @@
+// C ABI: the sparse optimizer step with stochastic rounding behind the row cache (16-bit tables) = the named
+// instantiations of cuembed::SparseRowUpdate (placed state, rounding bits named by the table rows), in a unit of their
+// own so that they compile next to the other optimizer units.
+#include "c_api_optimizer_common.hpp"
+
+extern "C" {
+
+void cuembed_sparse_row_update_placed_stochastic(void* table, int elem_type, int embed_width, float* state, int rule,
+                                                 const void* ids, int index_type, const void* rows, int64_t piece_rows,
+                                                 int pieces, int64_t num_rows, const void* counts, int counts_are_int64,
+                                                 const void* last_id, float lr, const float* lr_device, float eps,
+                                                 uint64_t seed, uint64_t step, const int64_t* step_device,
+                                                 cuembed_stream_t stream, const int64_t* state_ids,
+                                                 const int64_t* row_names) {
+  cuembed::SparseUpdateOptions o = cuembed_c_api::UpdateOptions(rule, piece_rows, pieces, num_rows, counts,
+                                                                counts_are_int64, last_id, lr, lr_device, eps);
+  cuembed_c_api::FillStochasticRounding(o, seed, step, step_device);
+  // (the named step alone: without names the call is cuembed_sparse_row_update_stochastic's, and aborts here)
+#define UPD(E, I)                                                                                                  \
+  cuembed::detail::SparseRowUpdateNamed<E, I, cuembed::UpdateRoundings::kStochasticOnly>(                          \
+      static_cast<E*>(table), state, embed_width, static_cast<const I*>(ids), static_cast<const E*>(rows), o,      \
+      cuembed_c_api::Stream(stream), state_ids, row_names)
+  switch ((elem_type << 1) | index_type) {
+    case 2: UPD(__half, int32_t); break;
+    case 3: UPD(__half, int64_t); break;
+    case 4: UPD(__hip_bfloat16, int32_t); break;
+    case 5: UPD(__hip_bfloat16, int64_t); break;
+    default: CUEMBED_C_API_BAD_TYPE();   // (float tables have no rounding to randomise)
+  }
+#undef UPD
+}
+
+}  // extern "C"

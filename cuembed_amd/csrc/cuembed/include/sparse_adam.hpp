@@ -4,11 +4,14 @@
 //   cuembed::SparseRowAdam<ElemT, IndexT>(table, exp_avg, exp_avg_sq, embed_width, ids, rows, options, stream)
 //   cuembed::SparseRowAdam<ElemT, IndexT>(table, exp_avg, exp_avg_sq, embed_width, ids, rows, options, stream,
 //                                         exp_avg_ids, exp_avg_sq_ids)
+//   cuembed::SparseRowAdam<ElemT, IndexT>(table, exp_avg, exp_avg_sq, embed_width, ids, rows, options, stream,
+//                                         exp_avg_ids, exp_avg_sq_ids, row_names)
 //   cuembed::AdamClockAdvance(powers, bias_factor, beta1, beta2, stream)
 //
 // SparseRowAdam consumes the compressed gradient like SparseRowUpdate (sparse_update.hpp) and keeps two fp32 moments per
 // named row; with exp_avg_ids / exp_avg_sq_ids the moments of entry k are addressed by ids of their own (a table behind
-// the row cache keeps weights and moments in three planes); AdamClockAdvance keeps the bias factor of the step in a device word, so that a captured step needs the host
+// the row cache keeps weights and moments in three planes), and with row_names the bits of stochastic rounding are named
+// by the table rows that the translated ids no longer are; AdamClockAdvance keeps the bias factor of the step in a device word, so that a captured step needs the host
 // for neither the entry count nor the step number.
 #ifndef CUEMBED_INCLUDE_SPARSE_ADAM_HPP_
 #define CUEMBED_INCLUDE_SPARSE_ADAM_HPP_
@@ -117,8 +120,9 @@ constexpr int kAdamPlacedEntriesInFlight = 2;
  * valid entries must name distinct rows in all three id arrays.
  *
  * Both id arrays nullptr is the call above.  Otherwise both are required and the rounding is to nearest (the bits of
- * stochastic rounding are named by the table row, which a translated id is not); one array alone, or stochastic
- * rounding, aborts with the failed condition.
+ * stochastic rounding are named by the table row, which a translated id is not: the overload with `row_names` below
+ * carries the table rows and rounds stochastically); one array alone, or stochastic rounding, aborts with the failed
+ * condition.
  */
 template <typename ElemT, typename IndexT, UpdateRoundings kRoundings = UpdateRoundings::kBoth>
 void SparseRowAdam(ElemT* table,
@@ -164,6 +168,94 @@ void SparseRowAdam(ElemT* table,
         if (options.rule == AdamRule::kAdam) with_rule(std::integral_constant<AdamRule, AdamRule::kAdam>());
         else with_rule(std::integral_constant<AdamRule, AdamRule::kRowwiseAdam>());
       });
+}
+
+namespace detail {
+//! Entries in flight of the named (placed, stochastic) Adam kernels whose lanes hold one slice per entry: those of
+//! their placed siblings (profiles/sparse_update_placed_stochastic_kernel_resources.txt).
+template <AdamRule kRule, int N>
+constexpr int kAdamNamedEntriesInFlight = kAdamPlacedEntriesInFlight;
+
+//! The named step itself (row_names != nullptr): the body of the overload below, and what a translation unit that wants
+//! the named kernels alone calls.
+template <typename ElemT, typename IndexT, UpdateRoundings kRoundings>
+void SparseRowAdamNamed(ElemT* table, float* exp_avg, float* exp_avg_sq, const int embed_width, const IndexT* ids,
+                        const ElemT* rows, const SparseAdamOptions& options, const hipStream_t stream,
+                        const int64_t* exp_avg_ids, const int64_t* exp_avg_sq_ids, const int64_t* row_names) {
+  using DevT = DeviceElemT<ElemT>;
+  CUEMBED_ASSERT(row_names != nullptr);
+  CheckCountSource(options);
+  CUEMBED_ASSERT(options.beta1 >= 0.f && options.beta1 < 1.f && options.beta2 >= 0.f && options.beta2 < 1.f);
+  CUEMBED_ASSERT(options.eps >= 0.f && options.weight_decay >= 0.f);
+  CUEMBED_ASSERT(exp_avg_ids != nullptr && exp_avg_sq_ids != nullptr);
+  CUEMBED_ASSERT(options.stochastic_rounding);
+  CUEMBED_ASSERT(sizeof(ElemT) == 2);
+  if (!CheckRoundingAndWork<ElemT, kRoundings>(options, table, ids, rows)) return;
+  CUEMBED_ASSERT(exp_avg != nullptr && exp_avg_sq != nullptr);
+  CUEMBED_ASSERT(reinterpret_cast<uintptr_t>(exp_avg_sq) % 4 == 0);
+  if constexpr (kCanRoundStochastically<ElemT, kRoundings>) {
+    const int bytes = UpdateLaneBytes<DevT>(embed_width, table, rows, exp_avg, true,
+                                            options.rule == AdamRule::kAdam ? exp_avg_sq : nullptr);
+    const UpdateCounts counts = CountsOf(options);
+    const AdamScalars h = {options.beta1, options.one_minus_beta1, options.beta2, options.one_minus_beta2,
+                           options.eps, options.weight_decay};
+    DevT* t = reinterpret_cast<DevT*>(table);
+    const DevT* g = reinterpret_cast<const DevT*>(rows);
+    DispatchUpdate<DevT, UpdateRoundings::kStochasticOnly>(
+        bytes, embed_width, options, [&](auto, auto n, auto chunks, const UpdateShape& s) {
+          const auto with_rule = [&](auto rule) {
+            constexpr int kChunks = decltype(chunks)::value;
+            constexpr int kInFlight =
+                kChunks == 1 ? kAdamNamedEntriesInFlight<decltype(rule)::value, decltype(n)::value> : 1;
+            SparseRowAdamNamedKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, kChunks, kInFlight>
+                <<<dim3(s.grid), dim3(kUpdateBlockThreads), 0, stream>>>(
+                    ids, exp_avg_ids, exp_avg_sq_ids, row_names, g, t, exp_avg, exp_avg_sq, embed_width, s.lanes_per_row,
+                    s.group, options.piece_rows, options.pieces, counts, options.lr, options.lr_device,
+                    options.bias_factor, options.bias_factor_device, h, RoundingOf<true>(options));
+          };
+          if (options.rule == AdamRule::kAdam) with_rule(std::integral_constant<AdamRule, AdamRule::kAdam>());
+          else with_rule(std::integral_constant<AdamRule, AdamRule::kRowwiseAdam>());
+        });
+  }
+}
+}  // namespace detail
+
+/**
+ * @brief The placed step with stochastic rounding: entry k updates table[ids[k], :] and its moments at rows
+ * exp_avg_ids[k] / exp_avg_sq_ids[k] as above, and the one rounding to ElemT draws the bits of (seed, step,
+ * row_names[k], column).  For a table behind the row cache: the three id arrays are translated and name slots,
+ * `row_names` are the batch's own ids -- the table rows -- so that a row rounds with the same bits wherever the cache
+ * has put it, and the result is bit for bit that of the unplaced stochastic call on tensors that hold the same values.
+ * Lane bytes, plan and dispatch are that call's.
+ *
+ * row_names == nullptr is the call above (which refuses stochastic rounding with placed ids).  With names,
+ * options.stochastic_rounding must be set, ElemT must be a 16-bit type and both moment id arrays are required.  The
+ * valid entries must name distinct rows in every id array.  Misuse aborts with the failed condition.
+ */
+template <typename ElemT, typename IndexT, UpdateRoundings kRoundings = UpdateRoundings::kBoth>
+void SparseRowAdam(ElemT* table,
+                   float* exp_avg,
+                   float* exp_avg_sq,
+                   const int embed_width,
+                   const IndexT* ids,
+                   const ElemT* rows,
+                   const SparseAdamOptions& options,
+                   const hipStream_t stream,
+                   const int64_t* exp_avg_ids,
+                   const int64_t* exp_avg_sq_ids,
+                   const int64_t* row_names) {
+  if (row_names == nullptr) {
+    if constexpr (kRoundings == UpdateRoundings::kStochasticOnly) {
+      // (placed ids without names: round to nearest, not in this instantiation)
+      CUEMBED_ASSERT(exp_avg_ids == nullptr && exp_avg_sq_ids == nullptr);
+      return SparseRowAdam<ElemT, IndexT, kRoundings>(table, exp_avg, exp_avg_sq, embed_width, ids, rows, options, stream);
+    } else {
+      return SparseRowAdam<ElemT, IndexT, kRoundings>(table, exp_avg, exp_avg_sq, embed_width, ids, rows, options, stream,
+                                                      exp_avg_ids, exp_avg_sq_ids);
+    }
+  }
+  detail::SparseRowAdamNamed<ElemT, IndexT, kRoundings>(table, exp_avg, exp_avg_sq, embed_width, ids, rows, options, stream,
+                                                        exp_avg_ids, exp_avg_sq_ids, row_names);
 }
 
 /**

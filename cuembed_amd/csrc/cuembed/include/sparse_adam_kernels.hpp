@@ -154,8 +154,8 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
  * @brief The same step with the moments in places of their own: entry k's weights at table[ids[k], :], its first moment
  * at row exp_avg_ids[k] of `exp_avg`, its second at row exp_avg_sq_ids[k] of `exp_avg_sq` -- a row of `width` elements
  * (kAdam) or the row's one word (kRowwiseAdam).  WalkNamedRows' kPlaced + kPlacedTwice: what a table behind the row
- * cache with two state planes launches (row_cache.hpp).  Round to nearest only: the bits of stochastic rounding are named
- * by the table row, which a translated id is not.  Same launch as SparseRowAdamKernel.
+ * cache with two state planes launches (row_cache.hpp).  Round to nearest; SparseRowAdamNamedKernel rounds
+ * stochastically.  Same launch as SparseRowAdamKernel.
  */
 template <typename ElemT, typename IndexT, int N, AdamRule kRule, int kChunks, int kEntriesInFlight, bool kStochastic = false>
 __global__ void __launch_bounds__(kUpdateBlockThreads)
@@ -173,6 +173,29 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
   WalkNamedRows<ElemT, IndexT, N, kChunks, kEntriesInFlight, false, true, true>(
       ids, rows, table, exp_avg, exp_avg_sq, width, lanes_per_row, group, piece_rows, pieces, counts,
       UpdateRounding<false>(), rule, exp_avg_ids, exp_avg_sq_ids);
+}
+
+/**
+ * @brief The placed step with stochastic rounding: as SparseRowAdamPlacedKernel, and the rounding bits of entry k are
+ * those of table row row_names[k] (WalkNamedRows' kNamed): a translated id is not the table row, so the walk carries the
+ * rows next to the three placed ids.  16-bit tables only.  Same launch as SparseRowAdamKernel.
+ */
+template <typename ElemT, typename IndexT, int N, AdamRule kRule, int kChunks, int kEntriesInFlight>
+__global__ void __launch_bounds__(kUpdateBlockThreads)
+    SparseRowAdamNamedKernel(const IndexT* __restrict__ ids, const int64_t* __restrict__ exp_avg_ids,
+                             const int64_t* __restrict__ exp_avg_sq_ids, const int64_t* __restrict__ row_names,
+                             const ElemT* __restrict__ rows, ElemT* __restrict__ table, float* __restrict__ exp_avg,
+                             float* __restrict__ exp_avg_sq, const int width, const int lanes_per_row, const int group,
+                             const int64_t piece_rows, const int pieces, const UpdateCounts counts,
+                             const float lr_value, const float* __restrict__ lr_word, const float bias_value,
+                             const float* __restrict__ bias_word, const AdamScalars h,
+                             const UpdateRounding<true> rounding) {
+  const float lr = lr_word != nullptr ? *lr_word : lr_value;
+  const float c = bias_word != nullptr ? *bias_word : bias_value;
+  const AdamStepRule<kRule> rule{{Arith<float>::mul(lr, c), Arith<float>::mul(lr, h.weight_decay), h.weight_decay != 0.f}, h};
+  WalkNamedRows<ElemT, IndexT, N, kChunks, kEntriesInFlight, true, true, true, true>(
+      ids, rows, table, exp_avg, exp_avg_sq, width, lanes_per_row, group, piece_rows, pieces, counts, rounding, rule,
+      exp_avg_ids, exp_avg_sq_ids, row_names);
 }
 
 /**

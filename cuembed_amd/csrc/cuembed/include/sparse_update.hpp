@@ -2,11 +2,13 @@
 //
 //   cuembed::SparseRowUpdate<ElemT, IndexT>(table, state, embed_width, ids, rows, options, stream)
 //   cuembed::SparseRowUpdate<ElemT, IndexT>(table, state, embed_width, ids, rows, options, stream, state_ids)
+//   cuembed::SparseRowUpdate<ElemT, IndexT>(table, state, embed_width, ids, rows, options, stream, state_ids, row_names)
 //
 // consumes the compressed gradient that EmbeddingBackward (or the sparse-gradient exchange) produced -- `ids` naming
 // table rows, `rows` their gradient rows -- and updates the named rows of `table` in place.  The number of valid
 // entries may live on the device, so a step that ends in this call needs no host read-back.  With `state_ids` the state
-// of entry k is addressed by a second id (a table behind the row cache keeps weights and state in two planes).
+// of entry k is addressed by a second id (a table behind the row cache keeps weights and state in two planes); with
+// `row_names` the bits of stochastic rounding are named by a third, the table row, which a translated id is not.
 #ifndef CUEMBED_INCLUDE_SPARSE_UPDATE_HPP_
 #define CUEMBED_INCLUDE_SPARSE_UPDATE_HPP_
 
@@ -249,7 +251,8 @@ void SparseRowUpdate(ElemT* table,
  * hold the same values.  The valid entries must name distinct rows in both id arrays.
  *
  * state_ids == nullptr is the call above.  Otherwise the rule must have a state (not kSgd) and the rounding is to
- * nearest: the bits of stochastic rounding are named by the table row, which a translated id is not.
+ * nearest: the bits of stochastic rounding are named by the table row, which a translated id is not -- the overload
+ * with `row_names` below carries the table rows next to the placed ids and rounds stochastically.
  */
 template <typename ElemT, typename IndexT, UpdateRoundings kRoundings = UpdateRoundings::kBoth>
 void SparseRowUpdate(ElemT* table,
@@ -284,6 +287,80 @@ void SparseRowUpdate(ElemT* table,
         if (options.rule == UpdateRule::kAdagrad) with_rule(std::integral_constant<UpdateRule, UpdateRule::kAdagrad>());
         else with_rule(std::integral_constant<UpdateRule, UpdateRule::kRowwiseAdagrad>());
       });
+}
+
+namespace detail {
+//! The named step itself (row_names != nullptr): the body of the overload below, and what a translation unit that wants
+//! the named kernels alone calls.
+template <typename ElemT, typename IndexT, UpdateRoundings kRoundings>
+void SparseRowUpdateNamed(ElemT* table, float* state, const int embed_width, const IndexT* ids, const ElemT* rows,
+                          const SparseUpdateOptions& options, const hipStream_t stream, const int64_t* state_ids,
+                          const int64_t* row_names) {
+  using DevT = DeviceElemT<ElemT>;
+  CUEMBED_ASSERT(row_names != nullptr);
+  CheckCountSource(options);
+  CUEMBED_ASSERT(options.stochastic_rounding);
+  CUEMBED_ASSERT(sizeof(ElemT) == 2);
+  if (options.rule == UpdateRule::kSgd) CUEMBED_ASSERT(state == nullptr && state_ids == nullptr);
+  else CUEMBED_ASSERT(state != nullptr && state_ids != nullptr);
+  if (!CheckRoundingAndWork<ElemT, kRoundings>(options, table, ids, rows)) return;
+  if constexpr (kCanRoundStochastically<ElemT, kRoundings>) {
+    const int bytes = UpdateLaneBytes<DevT>(embed_width, table, rows, state, options.rule == UpdateRule::kAdagrad);
+    const UpdateCounts counts = CountsOf(options);
+    DevT* t = reinterpret_cast<DevT*>(table);
+    const DevT* g = reinterpret_cast<const DevT*>(rows);
+    DispatchUpdate<DevT, UpdateRoundings::kStochasticOnly>(
+        bytes, embed_width, options, [&](auto, auto n, auto chunks, const UpdateShape& s) {
+          const auto with_rule = [&](auto rule) {
+            SparseRowUpdateNamedKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, decltype(chunks)::value>
+                <<<dim3(s.grid), dim3(kUpdateBlockThreads), 0, stream>>>(
+                    ids, state_ids, row_names, g, t, state, embed_width, s.lanes_per_row, s.group, options.piece_rows,
+                    options.pieces, counts, options.lr, options.lr_device, options.eps, RoundingOf<true>(options));
+          };
+          switch (options.rule) {
+            case UpdateRule::kSgd: return with_rule(std::integral_constant<UpdateRule, UpdateRule::kSgd>());
+            case UpdateRule::kAdagrad: return with_rule(std::integral_constant<UpdateRule, UpdateRule::kAdagrad>());
+            case UpdateRule::kRowwiseAdagrad:
+              return with_rule(std::integral_constant<UpdateRule, UpdateRule::kRowwiseAdagrad>());
+          }
+          CUEMBED_ASSERT(false && "unknown update rule");
+        });
+  }
+}
+}  // namespace detail
+
+/**
+ * @brief The placed step with stochastic rounding: entry k updates table[ids[k], :] and its state at row state_ids[k]
+ * as above, and the one rounding to ElemT draws the bits of (seed, step, row_names[k], column).  For a table behind the
+ * row cache: `ids` and `state_ids` are translated and name slots, `row_names` are the batch's own ids -- the table rows
+ * -- so that a row rounds with the same bits wherever the cache has put it, and the result is bit for bit that of the
+ * unplaced stochastic call on tensors that hold the same values.  Lane bytes, plan and dispatch are that call's.
+ *
+ * row_names == nullptr is the call above (which refuses stochastic rounding with placed ids).  With names,
+ * options.stochastic_rounding must be set and ElemT must be a 16-bit type; kSgd takes state == nullptr and
+ * state_ids == nullptr (the table plane only), every other rule requires state_ids.  The valid entries must name
+ * distinct rows in every id array.  Misuse aborts with the failed condition.
+ */
+template <typename ElemT, typename IndexT, UpdateRoundings kRoundings = UpdateRoundings::kBoth>
+void SparseRowUpdate(ElemT* table,
+                     float* state,
+                     const int embed_width,
+                     const IndexT* ids,
+                     const ElemT* rows,
+                     const SparseUpdateOptions& options,
+                     const hipStream_t stream,
+                     const int64_t* state_ids,
+                     const int64_t* row_names) {
+  if (row_names == nullptr) {
+    if constexpr (kRoundings == UpdateRoundings::kStochasticOnly) {
+      CUEMBED_ASSERT(state_ids == nullptr);   // (placed ids without names: round to nearest, not in this instantiation)
+      return SparseRowUpdate<ElemT, IndexT, kRoundings>(table, state, embed_width, ids, rows, options, stream);
+    } else {
+      return SparseRowUpdate<ElemT, IndexT, kRoundings>(table, state, embed_width, ids, rows, options, stream, state_ids);
+    }
+  }
+  detail::SparseRowUpdateNamed<ElemT, IndexT, kRoundings>(table, state, embed_width, ids, rows, options, stream, state_ids,
+                                                          row_names);
 }
 
 }  // namespace cuembed

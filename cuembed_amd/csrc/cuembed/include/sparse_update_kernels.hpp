@@ -229,6 +229,12 @@ __device__ __forceinline__ int64_t StateRow(const int64_t table_row, const int64
   if constexpr (kPlaced) return placed_row;
   else return table_row;
 }
+//! The row that names an entry's rounding bits: the table row, or (kNamed) the name the entry carries for them.
+template <bool kNamed>
+__device__ __forceinline__ int64_t RoundingRow(const int64_t table_row, const int64_t named_row) {
+  if constexpr (kNamed) return named_row;
+  else return table_row;
+}
 //! The row that addresses an entry in `state1`: like state0's, or (kPlacedTwice) a second place of its own.
 template <bool kPlaced, bool kPlacedTwice>
 __device__ __forceinline__ int64_t State1Row(const int64_t table_row, const int64_t placed_row,
@@ -251,22 +257,30 @@ __device__ __forceinline__ int64_t State1Row(const int64_t table_row, const int6
  * family behind the cache needs: exp_avg and exp_avg_sq are two allocations, each with a cached plane a whole number of
  * ITS rows away, so their row offsets differ (and, row-wise, their row sizes: 4 * width against 4 bytes).  Again a
  * separate instantiation: without kPlacedTwice nothing of state1_ids is compiled in.
+ * kNamed (with kStochastic): the rounding bits of entry k are those of (seed, step, row_names[k], column) instead of
+ * (seed, step, ids[k], column); weights and states are addressed as without it.  That is what stochastic rounding behind
+ * the cache needs: the bits belong to the TABLE ROW, and a translated id -- a slot plus a plane's row offset -- is not
+ * one, so the walk carries the table rows next to the placed ids.  A placed stochastic walk must therefore be named.
+ * The names are loaded with the ids, before the row data, and the Philox calls stay where they are (kChunks >= 1: while
+ * the row loads are in flight).  Again a separate instantiation: without kNamed nothing of row_names is compiled in.
  * kEntries entries are in flight per group: 2 when a lane holds one slice per entry (kChunks == 1), else 1.  With the
  * two moment packs of an Adam slice next to its weights and gradient, two entries take 32 (fp32) to 48 (16-bit)
  * registers of row data per lane: every kChunks == 1 instantiation stays free of scratch and at or above 4 waves per
  * SIMD (profiles/sparse_adam_kernel_resources.txt; the four-slice Adam bodies of the 16-bit types run at 2).
  */
 template <typename ElemT, typename IndexT, int N, int kChunks, int kEntries, bool kStochastic, bool kPlaced = false,
-          bool kPlacedTwice = false, typename RuleT>
+          bool kPlacedTwice = false, bool kNamed = false, typename RuleT>
 __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, const ElemT* __restrict__ rows,
                                               ElemT* __restrict__ table, float* __restrict__ state0,
                                               float* __restrict__ state1, const int width, const int lanes_per_row,
                                               const int group, const int64_t piece_rows, const int pieces,
                                               const UpdateCounts& counts, const UpdateRounding<kStochastic>& rounding,
                                               const RuleT& rule, const int64_t* __restrict__ state_ids = nullptr,
-                                              const int64_t* __restrict__ state1_ids = nullptr) {
+                                              const int64_t* __restrict__ state1_ids = nullptr,
+                                              const int64_t* __restrict__ row_names = nullptr) {
   static_assert(!kStochastic || sizeof(ElemT) == 2, "stochastic rounding is for the 16-bit table types");
-  static_assert(!(kPlaced && kStochastic), "the rounding bits are named by the table row: no second place for them");
+  static_assert(!kNamed || kStochastic, "row names name rounding bits: only a stochastic walk carries them");
+  static_assert(!(kPlaced && kStochastic) || kNamed, "a placed, stochastic walk must be named");
   static_assert(!kPlacedTwice || (kPlaced && RuleT::kStates >= 1), "a second placed id is for a rule with a state1");
   static_assert(kEntries == 1 || (kEntries == 2 && kChunks == 1), "two entries in flight: one slice per lane");
   using RoundT = SliceRounding<ElemT, N, kStochastic>;
@@ -315,6 +329,12 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
         if constexpr (kPlacedTwice) placed1[u] = live[u] ? state1_ids[base + k + u * stride] : 0;
         else placed1[u] = 0;
       }
+      int64_t named[kEntries];     // (kNamed: the row that names entry u's rounding bits)
+#pragma unroll
+      for (int u = 0; u < kEntries; ++u) {
+        if constexpr (kNamed) named[u] = live[u] ? row_names[base + k + u * stride] : 0;
+        else named[u] = 0;
+      }
       if constexpr (kChunks == 0) {
         // any width: slices lane, lane + group, ... one after the other (a rule with a row word reads the gradient row
         // twice, the second time out of the cache it has just been loaded into)
@@ -334,7 +354,7 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
           LoadStates<kStates>(s, state0, state1, RowElems(StateRow<kPlaced>(r[0], placed[0]), width) + c * N,
                               RowElems(State1Row<kPlaced, kPlacedTwice>(r[0], placed[0], placed1[0]), width) + c * N);
           RoundT round;
-          if constexpr (kStochastic) round = RoundT(seed, round_step, r[0], c * N);
+          if constexpr (kStochastic) round = RoundT(seed, round_step, RoundingRow<kNamed>(r[0], named[0]), c * N);
           StorePack<ElemT, N>(w_row + c * N, rule.Slice(w, g, s, row, round));
           StoreStates<kStates>(s, state0, state1, RowElems(StateRow<kPlaced>(r[0], placed[0]), width) + c * N,
                                RowElems(State1Row<kPlaced, kPlacedTwice>(r[0], placed[0], placed1[0]), width) + c * N);
@@ -366,7 +386,8 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
           for (int u = 0; u < kEntries; ++u)
 #pragma unroll
             for (int c = 0; c < kSlices; ++c)
-              if (has[u][c]) round[u][c] = RoundT(seed, round_step, r[u], (lane + c * group) * N);
+              if (has[u][c])
+                round[u][c] = RoundT(seed, round_step, RoundingRow<kNamed>(r[u], named[u]), (lane + c * group) * N);
         }
 #pragma unroll
         for (int u = 0; u < kEntries; ++u) {
@@ -417,7 +438,7 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
 }
 
 //! The same step with the state in a place of its own: entry k's weights at table[ids[k], :], its state at row
-//! state_ids[k] of `state` (WalkNamedRows' kPlaced).  Round to nearest only.
+//! state_ids[k] of `state` (WalkNamedRows' kPlaced).  Round to nearest; SparseRowUpdateNamedKernel rounds stochastically.
 template <typename ElemT, typename IndexT, int N, UpdateRule kRule, int kChunks>
 __global__ void __launch_bounds__(kUpdateBlockThreads)
     SparseRowUpdatePlacedKernel(const IndexT* __restrict__ ids, const int64_t* __restrict__ state_ids,
@@ -430,6 +451,26 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
   WalkNamedRows<ElemT, IndexT, N, kChunks, kChunks == 1 ? 2 : 1, false, true>(
       ids, rows, table, state, nullptr, width, lanes_per_row, group, piece_rows, pieces, counts, UpdateRounding<false>(),
       rule, state_ids);
+}
+
+/**
+ * @brief The stochastic step behind the row cache: entry k's weights at table[ids[k], :], its state (a rule that has
+ * one) at row state_ids[k] of `state`, and its rounding bits those of table row row_names[k] (WalkNamedRows' kNamed,
+ * with kPlaced for every rule but SGD, which has no state and takes state_ids == nullptr).  16-bit tables only.  Same
+ * launch and the same entries in flight as SparseRowUpdateKernel.
+ */
+template <typename ElemT, typename IndexT, int N, UpdateRule kRule, int kChunks>
+__global__ void __launch_bounds__(kUpdateBlockThreads)
+    SparseRowUpdateNamedKernel(const IndexT* __restrict__ ids, const int64_t* __restrict__ state_ids,
+                               const int64_t* __restrict__ row_names, const ElemT* __restrict__ rows,
+                               ElemT* __restrict__ table, float* __restrict__ state, const int width,
+                               const int lanes_per_row, const int group, const int64_t piece_rows, const int pieces,
+                               const UpdateCounts counts, const float lr_value, const float* __restrict__ lr_word,
+                               const float eps, const UpdateRounding<true> rounding) {
+  const UpdateStep<kRule> rule{lr_word != nullptr ? *lr_word : lr_value, eps};
+  WalkNamedRows<ElemT, IndexT, N, kChunks, kChunks == 1 ? 2 : 1, true, kRule != UpdateRule::kSgd, false, true>(
+      ids, rows, table, state, nullptr, width, lanes_per_row, group, piece_rows, pieces, counts, rounding, rule,
+      state_ids, nullptr, row_names);
 }
 
 }  // namespace detail

@@ -27,13 +27,19 @@ cache.apply_update(...) is that rule's step through the cache; cache.state is th
 
 AdamRowCache is the same cache for the Adam family: the two moments ride on the cache slots as two state planes, and
 cache.apply_update(...) is SparseAdamUpdater.apply through the cache (clock, prefetch, one translate for the three
-planes, one placed Adam launch)."""
+planes, one placed Adam launch).
+
+Both take stochastic_rounding=True, seed=... for a float16 / bfloat16 table: the step through the cache then rounds
+stochastically with the bits of (seed, cache.rounding_step, TABLE ROW, column) -- the step carries the batch's own ids
+next to the translated ones to name them -- and gives, bit for bit, what optim.SparseUpdater / SparseAdamUpdater with
+stochastic_rounding=True and the same seed give on device copies."""
 import ctypes
 
 import torch
 
 from . import _lib
 from . import ops as _ops
+from .optim import _check_rounding
 
 
 class CachedHostTable:
@@ -219,11 +225,19 @@ class DynamicRowCache(CachedHostTable):
     row is evicted or flushed; one dirty byte covers both planes, the counters count rows.  apply_update() is the rule's
     step through the cache.  Like the table, cache.state is current only after flush() and a synchronise.  Per-element
     Adagrad triples the bytes that the fill of a 16-bit row moves over PCIe (2 * width of row, 4 * width of state):
-    row-wise Adagrad, four bytes a row, is the rule to prefer behind the cache."""
+    row-wise Adagrad, four bytes a row, is the rule to prefer behind the cache.
+
+    stochastic_rounding=True, seed=... (float16 / bfloat16 tables; optim.SparseUpdater's arguments, checks and
+    messages): apply_update() / apply_sgd() round stochastically with the bits of (seed, rounding_step, table row,
+    column).  cache.rounding_step is an int64 device word that starts at 0 and is advanced on the device after every
+    apply_update() / apply_sgd(), also one with no entries or count=0; fill it to resume a run.  It is None without
+    stochastic rounding.  Where a row sits -- which slot, or the host table -- does not show in its bits."""
 
     def __init__(self, host_table, device="cuda", num_sets=1024, rule="sgd", state=None, initial_accumulator_value=0.0,
-                 eps=1e-8):
+                 eps=1e-8, stochastic_rounding=False, seed=0):
         _check_table_arguments(host_table, num_sets)
+        if stochastic_rounding:
+            _check_rounding(host_table, seed)
         if not isinstance(rule, str) or rule not in _ops.UPDATE_RULES:
             raise ValueError("rule must be one of %r, got %r" % (sorted(_ops.UPDATE_RULES), rule))
         state_shape = {"sgd": None, "adagrad": tuple(host_table.shape), "rowwise_adagrad": (host_table.shape[0],)}[rule]
@@ -258,6 +272,9 @@ class DynamicRowCache(CachedHostTable):
         self.dirty = torch.zeros((num_sets, WAYS), dtype=torch.uint8, device=self.device)
         self.words = torch.tensor([1] + [0] * 15, dtype=torch.int64).to(self.device)
         self._work = None
+        self.stochastic_rounding, self.seed = bool(stochastic_rounding), seed
+        self.rounding_step = (torch.zeros((1,), dtype=torch.int64, device=self.device) if self.stochastic_rounding
+                              else None)
 
     # the caller-managed policy of the base class would bypass tags / stamps / dirty
     def cache_rows(self, row_ids):
@@ -369,7 +386,13 @@ class DynamicRowCache(CachedHostTable):
         constructor) -- arguments as for apply_sgd, which this is on a rule="sgd" cache.  prefetch(ids,
         for_update=True) first; then the ids are translated twice, once per plane, and one launch of the sparse step
         updates resident rows and their state in HBM.  Rows their set has no way for are updated in place in the host
-        table AND the host state over PCIe: no update is dropped.  Round to nearest; no read-back."""
+        table AND the host state over PCIe: no update is dropped.  No read-back.
+
+        The one rounding to the table's type is to nearest, or, on a cache with stochastic_rounding=True, stochastic
+        with the bits of (seed, rounding_step, table row, column): the launch is then the named step, which carries
+        the caller's ids as int64 next to the translated ones to name the bits (int64 ids are passed as they are,
+        int32 ids cost one elementwise widening launch), and rounding_step is advanced on the device afterwards -- on
+        every call, like SparseUpdater.apply."""
         self._apply(ids, rows, lr, count, last_id)
 
     def _check_step(self, ids, rows, lr):
@@ -399,7 +422,7 @@ class DynamicRowCache(CachedHostTable):
         self.prefetch(ids, for_update=True, count=count, last_id=last_id)
         n = ids.numel()
         if n == 0:
-            return None
+            return self._advance_rounding_step()
         translated = self.translate(ids)
         # the count of valid entries as the prefetch resolved it on the device: one int64 word
         resolved = self.words[STAT_WORDS.index("batch_count"):STAT_WORDS.index("batch_count") + 1]
@@ -407,13 +430,32 @@ class DynamicRowCache(CachedHostTable):
                 _ops.UPDATE_RULES[self.rule], _ops._ptr(translated), _ops._INDEX[torch.int64], _ops._ptr(rows), n, 1, -1,
                 _ops._ptr(resolved), 1, None, float(lr), _ops._ptr(lr_word), self.eps if self.state is not None else 0.0,
                 _ops._stream(ids))
+        state_ids = None if self.state is None else self._translate(ids, self.state_row_offset)
+        if self.stochastic_rounding:
+            names = self._row_names(ids)
+            with torch.cuda.device(self.device):
+                _lib.lib().cuembed_sparse_row_update_placed_stochastic(
+                    *(args[:-1] + (self.seed, 0, _ops._ptr(self.rounding_step), args[-1], _ops._ptr(state_ids),
+                                   _ops._ptr(names))))
+            return self._advance_rounding_step()
         if self.state is None:
             with torch.cuda.device(self.device):
                 _lib.lib().cuembed_sparse_row_update(*args)
             return None
-        state_ids = self._translate(ids, self.state_row_offset)
         with torch.cuda.device(self.device):
             _lib.lib().cuembed_sparse_row_update_placed(*(args + (_ops._ptr(state_ids),)))
+        return None
+
+    @staticmethod
+    def _row_names(ids):
+        """The table rows that name the rounding bits of a step's entries: the caller's ids as int64 (int64 ids as
+        they are; int32 ids through one elementwise widening launch)."""
+        return ids if ids.dtype == torch.int64 else ids.to(torch.int64)
+
+    def _advance_rounding_step(self):
+        """One apply = one step of the rounding bits: on the device, after the step in stream order."""
+        if self.stochastic_rounding:
+            self.rounding_step.add_(1)
         return None
 
     def flush(self):
@@ -440,7 +482,8 @@ class AdamRowCache(DynamicRowCache):
     """DynamicRowCache for a table trained with the Adam family: lazy Adam (torch.optim.SparseAdam's formula) or, with
     rowwise=True, row-wise Adam -- optim.SparseAdamUpdater's counterpart for a table in pinned host memory, as
     DynamicRowCache(rule="adagrad") is SparseUpdater's.  The result is bit for bit the table and the moments that
-    SparseAdamUpdater produces on device copies (round to nearest; there is no stochastic rounding through the cache).
+    SparseAdamUpdater produces on device copies -- with round to nearest, or, with stochastic_rounding=True and the same
+    seed, with stochastic rounding: cache.rounding_step is DynamicRowCache's.
 
     The moments live in pinned host memory like the table -- cache.exp_avg float32 [rows, width], cache.exp_avg_sq
     float32 [rows, width], or [rows] with rowwise=True: the shapes SparseAdamUpdater owns; zero-filled and pinned when not
@@ -459,8 +502,10 @@ class AdamRowCache(DynamicRowCache):
     Row-wise Adam is the rule to prefer behind the cache for that reason."""
 
     def __init__(self, host_table, device="cuda", num_sets=1024, rowwise=False, betas=(0.9, 0.999), eps=1e-8,
-                 weight_decay=0.0, bias_correction=True, exp_avg=None, exp_avg_sq=None):
+                 weight_decay=0.0, bias_correction=True, exp_avg=None, exp_avg_sq=None, stochastic_rounding=False, seed=0):
         _check_table_arguments(host_table, num_sets)
+        if stochastic_rounding:
+            _check_rounding(host_table, seed)
         betas = _ops._check_betas(betas)
         if not float(eps) >= 0.0 or not float(weight_decay) >= 0.0:
             raise ValueError("eps and weight_decay must not be negative")
@@ -478,7 +523,8 @@ class AdamRowCache(DynamicRowCache):
                 raise ValueError("rowwise=%r needs a contiguous %s of shape %r, got %r" % (rowwise, name, shapes[name],
                                                                                          tuple(t.shape)))
             _check_pinned(name, t)
-        super().__init__(host_table, device=device, num_sets=num_sets, eps=eps)
+        super().__init__(host_table, device=device, num_sets=num_sets, eps=eps, stochastic_rounding=stochastic_rounding,
+                         seed=seed)
         self.rule = "rowwise_adam" if rowwise else "adam"        # (apply_sgd points to apply_update)
         self.rowwise, self.betas, self.weight_decay = rowwise, betas, float(weight_decay)
         self.bias_correction = bool(bias_correction)
@@ -507,8 +553,13 @@ class AdamRowCache(DynamicRowCache):
         the ids for the three planes; ONE launch of the sparse Adam step with placed moments updates resident rows and
         their moments in HBM, with the count the prefetch resolved.  Rows their set has no way for are updated in
         place in the host table AND both host moments over PCIe: no update is dropped.  lr: a float or a one-element
-        float32 device tensor.  bias_correction=False feeds a constant 1 (the clock still counts).  Round to nearest;
-        no read-back."""
+        float32 device tensor.  bias_correction=False feeds a constant 1 (the clock still counts).  No read-back.
+
+        The rounding is to nearest, or, on a cache with stochastic_rounding=True, stochastic with the bits of (seed,
+        rounding_step, table row, column): the launch is then the named placed step, which carries the caller's ids
+        as int64 next to the three translated arrays (int64 ids as they are, int32 ids through one elementwise
+        widening launch), and rounding_step is advanced on the device afterwards -- on every call, like
+        SparseAdamUpdater.apply."""
         lr, lr_word = self._check_step(ids, rows, lr)
         state = (("exp_avg", self.exp_avg.data_ptr()),)
         if not self.rowwise:
@@ -519,7 +570,7 @@ class AdamRowCache(DynamicRowCache):
         self.prefetch(ids, for_update=True, count=count, last_id=last_id)
         n = ids.numel()
         if n == 0:
-            return None
+            return self._advance_rounding_step()
         if self._placed is None or self._placed.shape[1] < n:
             self._placed = torch.empty((3, n), dtype=torch.int64, device=self.device)
         placed = [self._placed[k, :n] for k in range(3)]
@@ -533,11 +584,16 @@ class AdamRowCache(DynamicRowCache):
                 _ops._ptr(ids), _ops._INDEX[ids.dtype], n, _ops._ptr(self.slot_of_row), self.rows,
                 self.cache_row_offset, _ops._ptr(placed[0]), self.exp_avg_row_offset, _ops._ptr(placed[1]),
                 self.exp_avg_sq_row_offset, _ops._ptr(placed[2]), _ops._stream(ids))
-            L.cuembed_sparse_row_adam_placed(
-                ctypes.c_void_p(self.table.data_ptr()), _ops._ELEM[self.table.dtype], self.width,
-                ctypes.c_void_p(self.exp_avg.data_ptr()), ctypes.c_void_p(self.exp_avg_sq.data_ptr()),
-                _ops.ADAM_RULES[self.rule], _ops._ptr(placed[0]), _ops._INDEX[torch.int64], _ops._ptr(rows), n, 1, -1,
-                _ops._ptr(resolved), 1, None, float(lr), _ops._ptr(lr_word), 1.0, _ops._ptr(bias), beta1, 1.0 - beta1,
-                beta2, 1.0 - beta2, self.eps, self.weight_decay, _ops._stream(ids), _ops._ptr(placed[1]),
-                _ops._ptr(placed[2]))
-        return None
+            step = (ctypes.c_void_p(self.table.data_ptr()), _ops._ELEM[self.table.dtype], self.width,
+                    ctypes.c_void_p(self.exp_avg.data_ptr()), ctypes.c_void_p(self.exp_avg_sq.data_ptr()),
+                    _ops.ADAM_RULES[self.rule], _ops._ptr(placed[0]), _ops._INDEX[torch.int64], _ops._ptr(rows), n, 1, -1,
+                    _ops._ptr(resolved), 1, None, float(lr), _ops._ptr(lr_word), 1.0, _ops._ptr(bias), beta1,
+                    1.0 - beta1, beta2, 1.0 - beta2, self.eps, self.weight_decay)
+            if self.stochastic_rounding:
+                names = self._row_names(ids)
+                L.cuembed_sparse_row_adam_placed_stochastic(
+                    *(step + (self.seed, 0, _ops._ptr(self.rounding_step), _ops._stream(ids), _ops._ptr(placed[1]),
+                              _ops._ptr(placed[2]), _ops._ptr(names))))
+            else:
+                L.cuembed_sparse_row_adam_placed(*(step + (_ops._stream(ids), _ops._ptr(placed[1]), _ops._ptr(placed[2]))))
+        return self._advance_rounding_step()

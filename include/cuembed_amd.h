@@ -615,6 +615,23 @@ void cuembed_sparse_row_update_stochastic(void* table, int elem_type, int embed_
                                           const void* last_id, float lr, const float* lr_device, float eps,
                                           uint64_t seed, uint64_t step, const int64_t* step_device,
                                           cuembed_stream_t stream);
+/* cuembed_sparse_row_update_stochastic BEHIND THE ROW CACHE: entry k updates table[ids[k], :] and, for a rule with a
+ * state, the state at row state_ids[k] of `state` (as cuembed_sparse_row_update_placed), and the one rounding to the
+ * table's type draws the bits of (seed, step, row_names[k], column): `ids` / `state_ids` are the batch's ids translated
+ * with the planes' row offsets and name cache slots, `row_names` ([pieces * piece_rows] int64) are the batch's own ids,
+ * the table rows, so that a row rounds with the same bits wherever the cache has put it.  Lane bytes, launch shape and
+ * walk are those of cuembed_sparse_row_update_stochastic, and so are the bits on tensors that hold the same values.
+ * row_names must not be NULL (without names the call is cuembed_sparse_row_update_stochastic).  CUEMBED_UPDATE_SGD takes
+ * state == NULL and state_ids == NULL (the table plane only); the other rules require both.  elem_type CUEMBED_F16 or
+ * CUEMBED_BF16.  The valid entries must name distinct rows in every id array.  Misuse aborts with the failed condition.
+ * One launch, no read-back. */
+void cuembed_sparse_row_update_placed_stochastic(void* table, int elem_type, int embed_width, float* state, int rule,
+                                                 const void* ids, int index_type, const void* rows, int64_t piece_rows,
+                                                 int pieces, int64_t num_rows, const void* counts, int counts_are_int64,
+                                                 const void* last_id, float lr, const float* lr_device, float eps,
+                                                 uint64_t seed, uint64_t step, const int64_t* step_device,
+                                                 cuembed_stream_t stream, const int64_t* state_ids,
+                                                 const int64_t* row_names);
 /* The specification above as host code (no launch, no device): out[0..3] = the four Philox output words of the call
  * for (seed, step, row, column_group) ... */
 void cuembed_stochastic_rounding_words(uint64_t seed, uint64_t step, int64_t row, uint32_t column_group, uint32_t* out);
@@ -673,6 +690,22 @@ void cuembed_sparse_row_adam_stochastic(void* table, int elem_type, int embed_wi
                                         const float* bias_factor_device, float beta1, float one_minus_beta1, float beta2,
                                         float one_minus_beta2, float eps, float weight_decay, uint64_t seed,
                                         uint64_t step, const int64_t* step_device, cuembed_stream_t stream);
+/* cuembed_sparse_row_adam_stochastic BEHIND THE ROW CACHE: the moments of entry k at rows exp_avg_ids[k] /
+ * exp_avg_sq_ids[k] (as cuembed_sparse_row_adam_placed), and the rounding bits those of (seed, step, row_names[k], column)
+ * -- row_names ([pieces * piece_rows] int64) are the batch's own ids, the table rows, next to the three translated id
+ * arrays.  Lane bytes, launch shape and walk are those of cuembed_sparse_row_adam_stochastic, and so are the bits on
+ * tensors that hold the same values.  exp_avg_ids, exp_avg_sq_ids and row_names must not be NULL; elem_type CUEMBED_F16
+ * or CUEMBED_BF16.  Misuse aborts with the failed condition.  One launch, no read-back. */
+void cuembed_sparse_row_adam_placed_stochastic(void* table, int elem_type, int embed_width, float* exp_avg,
+                                               float* exp_avg_sq, int rule, const void* ids, int index_type,
+                                               const void* rows, int64_t piece_rows, int pieces, int64_t num_rows,
+                                               const void* counts, int counts_are_int64, const void* last_id, float lr,
+                                               const float* lr_device, float bias_factor,
+                                               const float* bias_factor_device, float beta1, float one_minus_beta1,
+                                               float beta2, float one_minus_beta2, float eps, float weight_decay,
+                                               uint64_t seed, uint64_t step, const int64_t* step_device,
+                                               cuembed_stream_t stream, const int64_t* exp_avg_ids,
+                                               const int64_t* exp_avg_sq_ids, const int64_t* row_names);
 /* The bias-factor clock, advanced on the device (one single-thread launch, no read-back): powers, fp64[3] on the device
  * holding (t, beta1^t, beta2^t) and starting at (0, 1, 1), becomes (t + 1, beta1^t * beta1, beta2^t * beta2) in fp64, and
  * *bias_factor (fp32, on the device) = sqrt(1 - beta2^t) / (1 - beta1^t) of the new t, computed in fp64 and rounded once.
