@@ -36,7 +36,16 @@
  *     passed as void pointers here;
  *   - Transpose / ComputeCompressedGradIndices are two-phase: call with
  *     work == NULL to receive the scratch size in *lwork, then again with a
- *     scratch buffer of at least that size.
+ *     scratch buffer of at least that size.  The same holds for every other
+ *     call with `work` / `lwork` parameters (the sample-blocked and remapped
+ *     transposes, cuembed_bag_order_by_length, cuembed_row_cache_prefetch*).
+ *     `work` may hold anything on entry -- nothing has to be zeroed, and a buffer
+ *     may be re-used between calls of any size and type -- and its contents after
+ *     the call are unspecified.  No byte outside [work, work + queried size) and
+ *     outside the named outputs is written, and inputs are never written.  `work`
+ *     must be aligned to 8 bytes (hipMalloc gives 256): every region inside it
+ *     starts at a multiple of 256 bytes from `work`, and the widest access made
+ *     to one is a 64-bit word.
  *
  * Suffix grammar:  _{f32|f16|bf16}  element type of table / gradient / weights
  *                  _{i32|i64}  lookup-index and sample-id type

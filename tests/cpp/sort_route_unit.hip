@@ -14,6 +14,8 @@
 #include <random>
 #include <vector>
 
+#include <hip/hip_fp16.h>
+
 #include "cuembed/include/radix_sort_kernels.hpp"
 
 using namespace cuembed::detail;
@@ -143,12 +145,40 @@ static void Plans() {
   }
 }
 
+// The Python wrappers query ONCE with all key bits (transpose_workspace_bytes -> cuembed_transpose) and then call the
+// bounded entry points with index_bits: the plan of all bits must cover the plan of every smaller key_bits, for both
+// key widths and every payload combination the C ABI instantiates.
+template <typename KeyT, typename V1, typename V2>
+static void AllBitsCover(const char* what) {
+  constexpr int kAll = static_cast<int>(8 * sizeof(KeyT));
+  for (size_t n : {size_t{1}, size_t{4096}, size_t{4097}, size_t{229376}, size_t{229377}, size_t{1} << 20}) {
+    const RadixSortPlan<KeyT, V1, V2> all(n, kAll);
+    for (int key_bits = 1; key_bits <= 64; ++key_bits) {
+      // (the entry points clamp a bound at or beyond the key's width to all bits: Transpose, index_transforms.hpp)
+      const RadixSortPlan<KeyT, V1, V2> bounded(n, key_bits < kAll ? key_bits : kAll);
+      CHECK(all.total >= bounded.total, "%s n %zu: all bits %zu bytes, %d bits %zu bytes", what, n, all.total, key_bits,
+            bounded.total);
+      CHECK(bounded.total >= RunHeadScanWorkBytes(n), "%s n %zu key_bits %d: the run-head scan fits", what, n, key_bits);
+    }
+  }
+}
+
+static void AllBitsCoverEveryBound() {
+  AllBitsCover<uint32_t, int32_t, NoPayload>("i32");
+  AllBitsCover<uint32_t, int32_t, float>("i32 f32");
+  AllBitsCover<uint32_t, int32_t, __half>("i32 f16");
+  AllBitsCover<uint64_t, int64_t, NoPayload>("i64");
+  AllBitsCover<uint64_t, int64_t, float>("i64 f32");
+  AllBitsCover<uint64_t, int64_t, __half>("i64 f16");
+}
+
 int main() {
   Routes();
   NarrowDecisions();
   Quotients();
   TileMaps();
   Plans();
+  AllBitsCoverEveryBound();
   if (g_fail) {
     std::fprintf(stderr, "%d checks failed\n", g_fail);
     return 1;
