@@ -199,6 +199,12 @@ def _declare(L):
     L.cuembed_embedding_weight_grad_grouped.argtypes = [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, _VP, _VP]
     L.cuembed_grouped_mean_scale.restype = None
     L.cuembed_grouped_mean_scale.argtypes = [_VP, _I, _I, _VP, _I, _VP, _I, _I, _I, _VP, _VP]
+    L.cuembed_sparse_row_update_grouped.restype = None
+    L.cuembed_sparse_row_update_grouped.argtypes = [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _I, _VP, _L, _L, _VP, _I,
+                                                    _VP, _F, _VP, _F, _VP]
+    L.cuembed_sparse_row_adam_grouped.restype = None
+    L.cuembed_sparse_row_adam_grouped.argtypes = [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _I, _VP, _L, _L,
+                                                  _VP, _I, _VP, _F, _VP, _F, _VP, _F, _F, _F, _F, _F, _F, _VP]
     L.cuembed_peek_last_error.restype = _I
     L.cuembed_peek_last_error.argtypes = []
     L.cuembed_version.restype = ctypes.c_char_p

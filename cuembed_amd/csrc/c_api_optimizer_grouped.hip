@@ -1,0 +1,95 @@
+// C ABI: the sparse optimizer step on a group of separate table tensors = explicit instantiations of
+// cuembed::SparseRowUpdateGrouped / SparseRowAdamGrouped (round to nearest; an extension: the reference ends at the
+// gradient and takes one table).
+#include "c_api_optimizer_adam_common.hpp"
+#include "cuembed/include/grouped_sparse_update.hpp"
+
+namespace {
+
+template <typename ElemT, typename IndexT>
+void UpdateGrouped(const void* const* tables_host, const void* const* tables_device, const void* const* state_host,
+                   const void* const* state_device, int num_tables, const int64_t* row_base, int embed_width,
+                   const void* ids, const void* rows, int64_t total_entries, const cuembed::SparseUpdateOptions& options,
+                   cuembed_stream_t stream) {
+  cuembed::SparseRowUpdateGrouped<ElemT, IndexT>(
+      reinterpret_cast<const ElemT* const*>(tables_host),
+      reinterpret_cast<ElemT* const*>(const_cast<void* const*>(reinterpret_cast<const void* const*>(tables_device))),
+      reinterpret_cast<const float* const*>(state_host),
+      reinterpret_cast<float* const*>(const_cast<void* const*>(reinterpret_cast<const void* const*>(state_device))),
+      num_tables, row_base, embed_width, static_cast<const IndexT*>(ids), static_cast<const ElemT*>(rows), total_entries,
+      options, cuembed_c_api::Stream(stream));
+}
+
+template <typename ElemT, typename IndexT>
+void AdamGrouped(const void* const* tables_host, const void* const* tables_device, const void* const* exp_avg_host,
+                 const void* const* exp_avg_device, const void* const* exp_avg_sq_host,
+                 const void* const* exp_avg_sq_device, int num_tables, const int64_t* row_base, int embed_width,
+                 const void* ids, const void* rows, int64_t total_entries, const cuembed::SparseAdamOptions& options,
+                 cuembed_stream_t stream) {
+  const auto mut = [](const void* const* p) {
+    return reinterpret_cast<float* const*>(const_cast<void* const*>(reinterpret_cast<const void* const*>(p)));
+  };
+  cuembed::SparseRowAdamGrouped<ElemT, IndexT>(
+      reinterpret_cast<const ElemT* const*>(tables_host),
+      reinterpret_cast<ElemT* const*>(const_cast<void* const*>(reinterpret_cast<const void* const*>(tables_device))),
+      reinterpret_cast<const float* const*>(exp_avg_host), mut(exp_avg_device),
+      reinterpret_cast<const float* const*>(exp_avg_sq_host), mut(exp_avg_sq_device), num_tables, row_base, embed_width,
+      static_cast<const IndexT*>(ids), static_cast<const ElemT*>(rows), total_entries, options,
+      cuembed_c_api::Stream(stream));
+}
+
+}  // namespace
+
+extern "C" {
+
+void cuembed_sparse_row_update_grouped(const void* const* tables_host, const void* const* tables_device,
+                                       const void* const* state_host, const void* const* state_device, int num_tables,
+                                       int elem_type, int embed_width, const int64_t* row_base, int rule, const void* ids,
+                                       int index_type, const void* rows, int64_t total_entries, int64_t num_rows,
+                                       const void* count_word, int count_word_is_64, const void* last_id, float lr,
+                                       const float* lr_device, float eps, cuembed_stream_t stream) {
+  const cuembed::SparseUpdateOptions o = cuembed_c_api::UpdateOptions(rule, total_entries, 1, num_rows, count_word,
+                                                                      count_word_is_64, last_id, lr, lr_device, eps);
+#define UPD(E, I)                                                                                                  \
+  UpdateGrouped<E, I>(tables_host, tables_device, state_host, state_device, num_tables, row_base, embed_width, ids, \
+                      rows, total_entries, o, stream)
+  switch ((elem_type << 1) | index_type) {
+    case 0: UPD(float, int32_t); break;
+    case 1: UPD(float, int64_t); break;
+    case 2: UPD(__half, int32_t); break;
+    case 3: UPD(__half, int64_t); break;
+    case 4: UPD(__hip_bfloat16, int32_t); break;
+    case 5: UPD(__hip_bfloat16, int64_t); break;
+    default: CUEMBED_C_API_BAD_TYPE();
+  }
+#undef UPD
+}
+
+void cuembed_sparse_row_adam_grouped(const void* const* tables_host, const void* const* tables_device,
+                                     const void* const* exp_avg_host, const void* const* exp_avg_device,
+                                     const void* const* exp_avg_sq_host, const void* const* exp_avg_sq_device,
+                                     int num_tables, int elem_type, int embed_width, const int64_t* row_base, int rule,
+                                     const void* ids, int index_type, const void* rows, int64_t total_entries,
+                                     int64_t num_rows, const void* count_word, int count_word_is_64, const void* last_id,
+                                     float lr, const float* lr_device, float bias_factor, const float* bias_factor_device,
+                                     float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float eps,
+                                     float weight_decay, cuembed_stream_t stream) {
+  const cuembed::SparseAdamOptions o = cuembed_c_api::AdamOptions(
+      rule, total_entries, 1, num_rows, count_word, count_word_is_64, last_id, lr, lr_device, bias_factor,
+      bias_factor_device, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay);
+#define ADAM(E, I)                                                                                                \
+  AdamGrouped<E, I>(tables_host, tables_device, exp_avg_host, exp_avg_device, exp_avg_sq_host, exp_avg_sq_device, \
+                    num_tables, row_base, embed_width, ids, rows, total_entries, o, stream)
+  switch ((elem_type << 1) | index_type) {
+    case 0: ADAM(float, int32_t); break;
+    case 1: ADAM(float, int64_t); break;
+    case 2: ADAM(__half, int32_t); break;
+    case 3: ADAM(__half, int64_t); break;
+    case 4: ADAM(__hip_bfloat16, int32_t); break;
+    case 5: ADAM(__hip_bfloat16, int64_t); break;
+    default: CUEMBED_C_API_BAD_TYPE();
+  }
+#undef ADAM
+}
+
+}  // extern "C"

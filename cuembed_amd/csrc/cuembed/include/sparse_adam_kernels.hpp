@@ -199,6 +199,27 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
 }
 
 /**
+ * @brief The same step on a GROUP of separate table tensors: ids[k] is a global row of the tables laid end to end, and
+ * entry k updates row ids[k] - row_base[t] of tables[t] and of that table's two moment tensors (WalkNamedRows' kGrouped;
+ * grouped.state0 = the exp_avg bases, grouped.state1 = the exp_avg_sq bases).  Round to nearest.  Same launch as
+ * SparseRowAdamKernel, plus GroupedLdsWords(num_tables, 2) * 8 bytes of dynamic LDS.
+ */
+template <typename ElemT, typename IndexT, int N, AdamRule kRule, int kChunks, int kEntriesInFlight>
+__global__ void __launch_bounds__(kUpdateBlockThreads)
+    SparseRowAdamGroupedKernel(const IndexT* __restrict__ ids, const ElemT* __restrict__ rows,
+                               const GroupedTables<true> grouped, const int width, const int lanes_per_row,
+                               const int group, const int64_t piece_rows, const int pieces, const UpdateCounts counts,
+                               const float lr_value, const float* __restrict__ lr_word, const float bias_value,
+                               const float* __restrict__ bias_word, const AdamScalars h) {
+  const float lr = lr_word != nullptr ? *lr_word : lr_value;
+  const float c = bias_word != nullptr ? *bias_word : bias_value;
+  const AdamStepRule<kRule> rule{{Arith<float>::mul(lr, c), Arith<float>::mul(lr, h.weight_decay), h.weight_decay != 0.f}, h};
+  WalkNamedRows<ElemT, IndexT, N, kChunks, kEntriesInFlight, false, false, false, false, true>(
+      ids, rows, nullptr, nullptr, nullptr, width, lanes_per_row, group, piece_rows, pieces, counts,
+      UpdateRounding<false>(), rule, nullptr, nullptr, nullptr, grouped);
+}
+
+/**
  * @brief The bias-factor clock: one thread advances (t, beta1^t, beta2^t) in fp64 and writes
  * c = sqrt(1 - beta2^t) / (1 - beta1^t), computed in fp64 and rounded once, to the fp32 word the update kernel reads.
  * Launch <<<1, 1>>>.  The running products carry a relative error of about t * 2^-53.  (A template so that the header

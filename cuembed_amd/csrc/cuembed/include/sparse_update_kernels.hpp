@@ -25,6 +25,9 @@
 //   * All of this is ONE device function, WalkNamedRows, for the five rules (SGD, Adagrad, row-wise Adagrad here; Adam and
 //     row-wise Adam in sparse_adam_kernels.hpp).  A rule type tells it how many per-element fp32 state tensors a slice
 //     carries (0 / 1 / 2), whether the row has a state word of its own, and the arithmetic of a row and of a slice.
+//   * The tables may be a GROUP of separate tensors (kGrouped; host API: grouped_sparse_update.hpp): the ids are then
+//     global rows of the tables laid end to end and the walk finds each entry's table itself, from row_base and the base
+//     pointers staged in LDS.
 #ifndef CUEMBED_INCLUDE_SPARSE_UPDATE_KERNELS_HPP_
 #define CUEMBED_INCLUDE_SPARSE_UPDATE_KERNELS_HPP_
 
@@ -243,6 +246,85 @@ __device__ __forceinline__ int64_t State1Row(const int64_t table_row, const int6
   else return StateRow<kPlaced>(table_row, placed_row);
 }
 
+//! A pointer into GLOBAL memory that is written through, typed as one (grouped_gather_kernels.hpp's GlobalPtr for the
+//! forward): a pointer that was read from memory is a generic pointer to the compiler, and row traffic through it would
+//! be flat_load / flat_store instead of global_load / global_store.
+template <typename T>
+using GlobalRowPtr = T __attribute__((address_space(1))) *;
+
+//! What a walk over a GROUP of separate table tensors needs (WalkNamedRows' kGrouped): the base pointers of the T tables
+//! and of their state tensors, and where each table begins in the rows laid end to end.  An empty kernel argument
+//! without kGrouped.
+template <bool kGrouped>
+struct GroupedTables {};
+template <>
+struct GroupedTables<true> {
+  const void* const* tables;     //!< [num_tables] table bases, in device memory
+  const float* const* state0;    //!< [num_tables] bases of the rule's first state tensor, or nullptr (no state)
+  const float* const* state1;    //!< [num_tables] bases of its second, or nullptr
+  const int64_t* row_base;       //!< [num_tables + 1] in device memory, ascending, row_base[0] = 0
+  int num_tables;
+};
+
+//! Dynamic LDS of a grouped walk, in 8-byte words: row_base[T + 1], then the T table bases, then the T bases of each
+//! state tensor the rule has.
+constexpr int GroupedLdsWords(const int num_tables, const int state_tensors) {
+  return num_tables + 1 + num_tables * (1 + state_tensors);
+}
+//! The most tables a grouped step takes: 32 KiB of LDS with two state tensors.
+constexpr int kGroupedMaxTables = 1023;
+
+//! Where one entry's weights and state live.  Without kGrouped: in the walk's own table / state0 / state1, nothing is
+//! kept and every accessor hands its argument back.  With kGrouped: in the tensors of the table that owns the entry's
+//! global row, found by Resolve; the accessors ignore their argument.
+template <typename ElemT, bool kGrouped, bool kUsesState0, bool kUsesState1>
+struct EntryPlace {
+  __device__ __forceinline__ ElemT* Table(ElemT* table) const { return table; }
+  __device__ __forceinline__ float* State0(float* state0) const { return state0; }
+  __device__ __forceinline__ float* State1(float* state1) const { return state1; }
+};
+template <typename ElemT, bool kUsesState0, bool kUsesState1>
+struct EntryPlace<ElemT, true, kUsesState0, kUsesState1> {
+  GlobalRowPtr<ElemT> table;
+  GlobalRowPtr<float> state0, state1;
+  __device__ __forceinline__ ElemT* Table(ElemT*) const { return (ElemT*)table; }
+  __device__ __forceinline__ float* State0(float*) const { return (float*)state0; }
+  __device__ __forceinline__ float* State1(float*) const { return (float*)state1; }
+
+  //! The group's words from device memory into LDS (GroupedLdsWords), by the whole workgroup, with the barrier.  Every
+  //! thread of the workgroup must call it.
+  static __device__ __forceinline__ void Stage(int64_t* words, const GroupedTables<true>& g) {
+    const int T = g.num_tables;
+    for (int i = threadIdx.x; i <= T; i += kUpdateBlockThreads) words[i] = g.row_base[i];
+    for (int i = threadIdx.x; i < T; i += kUpdateBlockThreads) {
+      words[T + 1 + i] = static_cast<int64_t>(reinterpret_cast<uintptr_t>(g.tables[i]));
+      if constexpr (kUsesState0) words[2 * T + 1 + i] = static_cast<int64_t>(reinterpret_cast<uintptr_t>(g.state0[i]));
+      if constexpr (kUsesState1)
+        words[(kUsesState0 ? 3 : 2) * T + 1 + i] = static_cast<int64_t>(reinterpret_cast<uintptr_t>(g.state1[i]));
+    }
+    __syncthreads();
+  }
+
+  //! The table t with row_base[t] <= row < row_base[t + 1], by binary search over the staged row_base (the LAST such t:
+  //! a table without rows owns nothing); `row` becomes the row inside that table.  LDS reads only: they are counted
+  //! apart from the global loads in flight and do not wait for them.  Any `row` gives a t in [0, T).
+  __device__ __forceinline__ void Resolve(const int64_t* words, const int T, int64_t& row) {
+    int t = 0;
+    for (int n = T; n > 1;) {
+      const int half = n >> 1;
+      if (words[t + half] <= row) t += half;
+      n -= half;
+    }
+    row -= words[t];
+    table = (GlobalRowPtr<ElemT>)reinterpret_cast<ElemT*>(static_cast<uintptr_t>(words[T + 1 + t]));
+    if constexpr (kUsesState0)
+      state0 = (GlobalRowPtr<float>)reinterpret_cast<float*>(static_cast<uintptr_t>(words[2 * T + 1 + t]));
+    if constexpr (kUsesState1)
+      state1 = (GlobalRowPtr<float>)reinterpret_cast<float*>(
+          static_cast<uintptr_t>(words[(kUsesState0 ? 3 : 2) * T + 1 + t]));
+  }
+};
+
 /**
  * @brief The one walk over the named rows: table[ids[k], :] and the state of row ids[k] <- rule(table[ids[k], :],
  * rows[k, :]) for every valid entry k.  The body of both kernels below.
@@ -263,13 +345,23 @@ __device__ __forceinline__ int64_t State1Row(const int64_t table_row, const int6
  * one, so the walk carries the table rows next to the placed ids.  A placed stochastic walk must therefore be named.
  * The names are loaded with the ids, before the row data, and the Philox calls stay where they are (kChunks >= 1: while
  * the row loads are in flight).  Again a separate instantiation: without kNamed nothing of row_names is compiled in.
+ * kGrouped (never with kPlaced, round to nearest only): the tables are `grouped.num_tables` SEPARATE tensors and ids[k] is
+ * a global row of the tables laid end to end (grouped_backward.hpp's keys).  `table`, `state0` and `state1` are not read;
+ * entry k's table t is the one with row_base[t] <= ids[k] < row_base[t + 1], its weights are at tables[t] + (ids[k] -
+ * row_base[t]) * width and each of its state planes at states[t] + (ids[k] - row_base[t]) * (width, or 1 for the row
+ * words).  The workgroup stages row_base and the base pointers in LDS once (GroupedLdsWords of dynamic LDS); an entry is
+ * then resolved with LDS reads alone (EntryPlace::Resolve), which with kChunks >= 1 happens after the entry's gradient
+ * loads are issued: LDS reads have a counter of their own, so the search does not wait for the rows in flight, and a
+ * search through global memory would (loads return in order).  The pointers stay in a global-address-space type, so
+ * row traffic is global_load / global_store as in every other walk.  Again a separate instantiation: without kGrouped
+ * every accessor of EntryPlace hands its argument back and nothing of `grouped` is compiled in.
  * kEntries entries are in flight per group: 2 when a lane holds one slice per entry (kChunks == 1), else 1.  With the
  * two moment packs of an Adam slice next to its weights and gradient, two entries take 32 (fp32) to 48 (16-bit)
  * registers of row data per lane: every kChunks == 1 instantiation stays free of scratch and at or above 4 waves per
  * SIMD (profiles/sparse_adam_kernel_resources.txt; the four-slice Adam bodies of the 16-bit types run at 2).
  */
 template <typename ElemT, typename IndexT, int N, int kChunks, int kEntries, bool kStochastic, bool kPlaced = false,
-          bool kPlacedTwice = false, bool kNamed = false, typename RuleT>
+          bool kPlacedTwice = false, bool kNamed = false, bool kGrouped = false, typename RuleT>
 __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, const ElemT* __restrict__ rows,
                                               ElemT* __restrict__ table, float* __restrict__ state0,
                                               float* __restrict__ state1, const int width, const int lanes_per_row,
@@ -277,8 +369,10 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
                                               const UpdateCounts& counts, const UpdateRounding<kStochastic>& rounding,
                                               const RuleT& rule, const int64_t* __restrict__ state_ids = nullptr,
                                               const int64_t* __restrict__ state1_ids = nullptr,
-                                              const int64_t* __restrict__ row_names = nullptr) {
+                                              const int64_t* __restrict__ row_names = nullptr,
+                                              const GroupedTables<kGrouped>& grouped = GroupedTables<kGrouped>()) {
   static_assert(!kStochastic || sizeof(ElemT) == 2, "stochastic rounding is for the 16-bit table types");
+  static_assert(!kGrouped || (!kPlaced && !kStochastic), "a grouped walk is neither placed nor stochastic");
   static_assert(!kNamed || kStochastic, "row names name rounding bits: only a stochastic walk carries them");
   static_assert(!(kPlaced && kStochastic) || kNamed, "a placed, stochastic walk must be named");
   static_assert(!kPlacedTwice || (kPlaced && RuleT::kStates >= 1), "a second placed id is for a rule with a state1");
@@ -288,7 +382,10 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
   constexpr bool kRowState = RuleT::kRowState;
   constexpr int kHeld = kStates > 0 ? kStates : 1;
   constexpr int kSlices = kChunks == 0 ? 1 : kChunks;
-  float* const row_words = kStates == 0 ? state0 : state1;   // (only read if kRowState)
+  // where an entry's weights and state live: the walk's own tensors, or (kGrouped) those of the entry's table
+  using PlaceT = EntryPlace<ElemT, kGrouped, kStates >= 1 || kRowState, kStates == 2 || (kStates == 1 && kRowState)>;
+  // the tensor of the row words (only read if kRowState)
+  const auto row_words_at = [&](const PlaceT& at) { return kStates == 0 ? at.State0(state0) : at.State1(state1); };
   // the row of an entry's row word: it lives in state0 and goes by state0's row, or in state1 and goes by state1's
   const auto word_row = [](const int64_t table_row, const int64_t placed_row, const int64_t placed1_row) {
     if constexpr (kStates == 0) return StateRow<kPlaced>(table_row, placed_row);
@@ -298,6 +395,14 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
   if constexpr (kStochastic) {
     seed = rounding.seed;
     round_step = rounding.step_word != nullptr ? static_cast<uint64_t>(*rounding.step_word) : rounding.step;
+  }
+  const int64_t* group_words = nullptr;   // (kGrouped: row_base and the base pointers, staged in LDS)
+  int num_tables = 0;
+  if constexpr (kGrouped) {
+    extern __shared__ int64_t grouped_lds_words[];
+    PlaceT::Stage(grouped_lds_words, grouped);
+    group_words = grouped_lds_words;
+    num_tables = grouped.num_tables;
   }
   const int lane = static_cast<int>(threadIdx.x) & (group - 1);
   const int groups_per_block = kUpdateBlockThreads / group;
@@ -339,7 +444,10 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
         // any width: slices lane, lane + group, ... one after the other (a rule with a row word reads the gradient row
         // twice, the second time out of the cache it has just been loaded into)
         const ElemT* g_row = RowPtr(rows, base + k, width);
-        ElemT* w_row = const_cast<ElemT*>(RowPtr(table, r[0], width));
+        PlaceT at;
+        if constexpr (kGrouped) at.Resolve(group_words, num_tables, r[0]);   // (r[0]: from here the row in its table)
+        float* const row_words = row_words_at(at);
+        ElemT* w_row = const_cast<ElemT*>(RowPtr(at.Table(table), r[0], width));
         float row = 0.f;
         if constexpr (kRowState) {
           const float before = row_words[word_row(r[0], placed[0], placed1[0])];
@@ -351,12 +459,12 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
           const Pack<ElemT, N> g = kRowState ? LoadPack<ElemT, N>(g_row + c * N) : LoadPackStreaming<ElemT, N>(g_row + c * N);
           const Pack<ElemT, N> w = LoadPack<ElemT, N>(w_row + c * N);
           StatePack<N> s[kHeld];
-          LoadStates<kStates>(s, state0, state1, RowElems(StateRow<kPlaced>(r[0], placed[0]), width) + c * N,
+          LoadStates<kStates>(s, at.State0(state0), at.State1(state1), RowElems(StateRow<kPlaced>(r[0], placed[0]), width) + c * N,
                               RowElems(State1Row<kPlaced, kPlacedTwice>(r[0], placed[0], placed1[0]), width) + c * N);
           RoundT round;
           if constexpr (kStochastic) round = RoundT(seed, round_step, RoundingRow<kNamed>(r[0], named[0]), c * N);
           StorePack<ElemT, N>(w_row + c * N, rule.Slice(w, g, s, row, round));
-          StoreStates<kStates>(s, state0, state1, RowElems(StateRow<kPlaced>(r[0], placed[0]), width) + c * N,
+          StoreStates<kStates>(s, at.State0(state0), at.State1(state1), RowElems(StateRow<kPlaced>(r[0], placed[0]), width) + c * N,
                                RowElems(State1Row<kPlaced, kPlacedTwice>(r[0], placed[0], placed1[0]), width) + c * N);
         }
       } else {
@@ -365,17 +473,35 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
         bool has[kEntries][kSlices];
         float row_word[kEntries];
         RoundT round[kEntries][kSlices];
+        PlaceT at[kEntries];
+        if constexpr (kGrouped) {
+          // the gradient rows need nothing but k: their loads go first, and every entry's table is found while they are
+          // in flight (r[u]: from here the row in its table)
+#pragma unroll
+          for (int u = 0; u < kEntries; ++u)
+#pragma unroll
+            for (int c = 0; c < kSlices; ++c) {
+              has[u][c] = live[u] && lane + c * group < lanes_per_row;
+              if (has[u][c])
+                g[u][c] = LoadPackStreaming<ElemT, N>(RowPtr(rows, base + k + u * stride, width) + (lane + c * group) * N);
+            }
+#pragma unroll
+          for (int u = 0; u < kEntries; ++u) at[u].Resolve(group_words, num_tables, r[u]);
+        }
 #pragma unroll
         for (int u = 0; u < kEntries; ++u) {
-          if constexpr (kRowState) row_word[u] = live[u] ? row_words[word_row(r[u], placed[u], placed1[u])] : 0.f;
+          if constexpr (kRowState)
+            row_word[u] = live[u] ? row_words_at(at[u])[word_row(r[u], placed[u], placed1[u])] : 0.f;
 #pragma unroll
           for (int c = 0; c < kSlices; ++c) {
             const int col = (lane + c * group) * N;
-            has[u][c] = live[u] && lane + c * group < lanes_per_row;
+            if constexpr (!kGrouped) has[u][c] = live[u] && lane + c * group < lanes_per_row;
             if (has[u][c]) {
-              g[u][c] = LoadPackStreaming<ElemT, N>(RowPtr(rows, base + k + u * stride, width) + col);
-              w[u][c] = LoadPack<ElemT, N>(RowPtr(table, r[u], width) + col);
-              LoadStates<kStates>(s[u][c], state0, state1, RowElems(StateRow<kPlaced>(r[u], placed[u]), width) + col,
+              if constexpr (!kGrouped)
+                g[u][c] = LoadPackStreaming<ElemT, N>(RowPtr(rows, base + k + u * stride, width) + col);
+              w[u][c] = LoadPack<ElemT, N>(RowPtr(at[u].Table(table), r[u], width) + col);
+              LoadStates<kStates>(s[u][c], at[u].State0(state0), at[u].State1(state1),
+                                  RowElems(StateRow<kPlaced>(r[u], placed[u]), width) + col,
                                   RowElems(State1Row<kPlaced, kPlacedTwice>(r[u], placed[u], placed1[u]), width) + col);
             }
           }
@@ -400,15 +526,17 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
               if (has[u][c]) sum = AddSquares(sum, g[u][c]);
             sum = GroupSum(sum, group);
             if (live[u])
-              row = rule.Row(row_words + word_row(r[u], placed[u], placed1[u]), row_word[u], sum, width, lane == 0);
+              row = rule.Row(row_words_at(at[u]) + word_row(r[u], placed[u], placed1[u]), row_word[u], sum, width,
+                             lane == 0);
           }
 #pragma unroll
           for (int c = 0; c < kSlices; ++c) {
             if (!has[u][c]) continue;
             const int col = (lane + c * group) * N;
-            ElemT* w_at = const_cast<ElemT*>(RowPtr(table, r[u], width)) + col;
+            ElemT* w_at = const_cast<ElemT*>(RowPtr(at[u].Table(table), r[u], width)) + col;
             StorePack<ElemT, N>(w_at, rule.Slice(w[u][c], g[u][c], s[u][c], row, round[u][c]));
-            StoreStates<kStates>(s[u][c], state0, state1, RowElems(StateRow<kPlaced>(r[u], placed[u]), width) + col,
+            StoreStates<kStates>(s[u][c], at[u].State0(state0), at[u].State1(state1),
+                                 RowElems(StateRow<kPlaced>(r[u], placed[u]), width) + col,
                                   RowElems(State1Row<kPlaced, kPlacedTwice>(r[u], placed[u], placed1[u]), width) + col);
           }
         }
@@ -471,6 +599,24 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
   WalkNamedRows<ElemT, IndexT, N, kChunks, kChunks == 1 ? 2 : 1, true, kRule != UpdateRule::kSgd, false, true>(
       ids, rows, table, state, nullptr, width, lanes_per_row, group, piece_rows, pieces, counts, rounding, rule,
       state_ids, nullptr, row_names);
+}
+
+/**
+ * @brief The same step on a GROUP of separate table tensors: ids[k] is a global row of the tables laid end to end, and
+ * entry k updates row ids[k] - row_base[t] of tables[t] and of that table's state tensor (WalkNamedRows' kGrouped).
+ * Round to nearest.  Same launch as SparseRowUpdateKernel, plus GroupedLdsWords(num_tables, the rule's state tensors)
+ * * 8 bytes of dynamic LDS.  grouped.state0 holds the bases of the rule's one state tensor (nullptr for SGD).
+ */
+template <typename ElemT, typename IndexT, int N, UpdateRule kRule, int kChunks, int kEntriesInFlight>
+__global__ void __launch_bounds__(kUpdateBlockThreads)
+    SparseRowUpdateGroupedKernel(const IndexT* __restrict__ ids, const ElemT* __restrict__ rows,
+                                 const GroupedTables<true> grouped, const int width, const int lanes_per_row,
+                                 const int group, const int64_t piece_rows, const int pieces, const UpdateCounts counts,
+                                 const float lr_value, const float* __restrict__ lr_word, const float eps) {
+  const UpdateStep<kRule> rule{lr_word != nullptr ? *lr_word : lr_value, eps};
+  WalkNamedRows<ElemT, IndexT, N, kChunks, kEntriesInFlight, false, false, false, false, true>(
+      ids, rows, nullptr, nullptr, nullptr, width, lanes_per_row, group, piece_rows, pieces, counts,
+      UpdateRounding<false>(), rule, nullptr, nullptr, nullptr, grouped);
 }
 
 }  // namespace detail

@@ -894,6 +894,190 @@ void cuembed_sparse_row_adam_op(at::Tensor table, at::Tensor exp_avg, at::Tensor
                             static_cast<float>(weight_decay), CurrentStream(table));
 }
 
+// ---- the optimizer step on a group of SEPARATE table tensors, in one launch (cuembed::SparseRowUpdateGrouped /
+// SparseRowAdamGrouped).  tables / table_ptrs as in cuemb_embedding_grouped; row_base the int64 device tensor of
+// num_tables + 1 exclusive prefix sums of the row counts; ids GLOBAL rows of the tables laid end to end (the compressed
+// gradient of the grouped backward), rows their gradient rows.  Each state list holds one float32 tensor per table and
+// comes with the int64 device tensor of its base pointers, built once by the caller.  Valid entries, at most one of:
+// count >= 0 (host-known), count_word (one int32 / int64 device word), last_id (one word of ids' dtype, count = last_id +
+// 1); none: every entry.  Round to nearest: stochastic_rounding = True is refused.  Nothing is read back.
+
+struct GroupedStep {
+  std::vector<const void*> table_host;
+  int elem = CUEMBED_F32, idx = CUEMBED_I32, words64 = 0;
+  int64_t num_rows = -1;
+  const void* count_word = nullptr;
+  const void* last_id = nullptr;
+  const float* lr_word = nullptr;
+};
+
+// One state list of a grouped step: `per_element` [rows_t, width] tensors, else [rows_t]; returns the host pointers.
+std::vector<const void*> CheckGroupedStates(const at::TensorList tables, const at::TensorList states,
+                                            const c10::optional<at::Tensor>& ptrs, const bool per_element, const char* name) {
+  TORCH_CHECK(states.size() == tables.size(), "cuembed_pyt: ", name, " must hold one tensor per table");
+  std::vector<const void*> host;
+  for (size_t t = 0; t < tables.size(); ++t) {
+    const at::Tensor& s = states[t];
+    TORCH_CHECK(s.defined() && s.is_cuda() && s.device() == tables[0].device() && s.scalar_type() == at::kFloat &&
+                    s.is_contiguous() &&
+                    (per_element ? s.sizes() == tables[t].sizes() : (s.dim() == 1 && s.size(0) == tables[t].size(0))),
+                "cuembed_pyt: ", name, "[", t, "] must be a contiguous float32 GPU tensor, ",
+                per_element ? "of its table's shape" : "one word per row of its table");
+    host.push_back(s.data_ptr());
+  }
+  TORCH_CHECK(ptrs.has_value() && ptrs->defined() && ptrs->is_cuda() && ptrs->device() == tables[0].device() &&
+                  ptrs->scalar_type() == at::kLong && ptrs->is_contiguous() &&
+                  ptrs->numel() == static_cast<int64_t>(tables.size()),
+              "cuembed_pyt: ", name, " needs the contiguous int64 tensor of its data pointers on the tables' device");
+  return host;
+}
+
+GroupedStep CheckGroupedStep(const at::TensorList tables, const at::Tensor& table_ptrs, const at::Tensor& row_base,
+                             const at::Tensor& ids, const at::Tensor& rows, const c10::optional<at::Tensor>& lr_device,
+                             const int64_t count, const c10::optional<at::Tensor>& count_word,
+                             const c10::optional<at::Tensor>& last_id, const bool stochastic_rounding) {
+  GroupedStep c;
+  TORCH_CHECK(!stochastic_rounding, "cuembed_pyt: stochastic rounding on a grouped step does not exist: round to nearest");
+  const int64_t num_tables = static_cast<int64_t>(tables.size());
+  TORCH_CHECK(num_tables >= 1 && num_tables <= 1023, "cuembed_pyt: a grouped step takes 1 to 1023 tables");
+  c.elem = ElemCode(tables[0], "tables");
+  for (const at::Tensor& t : tables) {
+    CheckGpu(t, "tables");
+    TORCH_CHECK(t.dim() == 2 && t.is_contiguous() && t.scalar_type() == tables[0].scalar_type() &&
+                    t.size(1) == tables[0].size(1) && t.device() == tables[0].device(),
+                "cuembed_pyt: the tables of a group must be contiguous [rows, width] of one dtype, width and device");
+    c.table_host.push_back(t.data_ptr());
+  }
+  const auto on_device = [&](const at::Tensor& t) { return t.is_cuda() && t.device() == tables[0].device(); };
+  TORCH_CHECK(on_device(table_ptrs) && table_ptrs.scalar_type() == at::kLong && table_ptrs.is_contiguous() &&
+                  table_ptrs.numel() == num_tables,
+              "cuembed_pyt: table_ptrs must be the contiguous int64 tensor of the tables' data pointers on their device");
+  TORCH_CHECK(on_device(row_base) && row_base.scalar_type() == at::kLong && row_base.is_contiguous() &&
+                  row_base.numel() == num_tables + 1,
+              "cuembed_pyt: row_base must be the contiguous int64 tensor of num_tables + 1 prefix sums on the tables' device");
+  CheckGpu(ids, "ids");
+  CheckGpu(rows, "rows");
+  c.idx = IndexCode(ids, "ids");
+  TORCH_CHECK(rows.scalar_type() == tables[0].scalar_type(), "cuembed_pyt: rows must have the tables' dtype");
+  TORCH_CHECK(rows.dim() == 2 && rows.size(1) == tables[0].size(1) && ids.dim() == 1 && rows.size(0) == ids.numel() &&
+                  rows.is_contiguous() && ids.is_contiguous() && on_device(ids) && on_device(rows),
+              "cuembed_pyt: rows [entries, width] and ids [entries] must be contiguous, agree and be on the tables' device");
+  TORCH_CHECK((rows.size(1) * rows.element_size()) % 4 == 0, "cuembed_pyt: the row size must be a multiple of 4 bytes");
+  const bool has_word = count_word.has_value() && count_word->defined();
+  const bool has_last = last_id.has_value() && last_id->defined();
+  TORCH_CHECK((count >= 0) + has_word + has_last <= 1, "cuembed_pyt: give at most one of count, count_word and last_id");
+  if (has_word) {
+    CheckGpu(*count_word, "count_word");
+    c.words64 = IndexCode(*count_word, "count_word") == CUEMBED_I64;
+    TORCH_CHECK(count_word->numel() == 1 && on_device(*count_word), "cuembed_pyt: count_word must be one word on the tables' device");
+    c.count_word = count_word->data_ptr();
+  } else if (has_last) {
+    CheckGpu(*last_id, "last_id");
+    TORCH_CHECK(last_id->scalar_type() == ids.scalar_type() && last_id->numel() == 1 && on_device(*last_id),
+                "cuembed_pyt: last_id must be one word of ids' dtype on the tables' device");
+    c.last_id = last_id->data_ptr();
+  } else {
+    c.num_rows = count >= 0 ? count : ids.numel();
+    TORCH_CHECK(c.num_rows <= ids.numel(), "cuembed_pyt: count exceeds the entries");
+  }
+  if (lr_device.has_value() && lr_device->defined()) {
+    CheckGpu(*lr_device, "lr_device");
+    TORCH_CHECK(lr_device->scalar_type() == at::kFloat && lr_device->numel() == 1 && on_device(*lr_device),
+                "cuembed_pyt: lr_device must be one float32 word on the tables' device");
+    c.lr_word = static_cast<const float*>(lr_device->data_ptr());
+  }
+  return c;
+}
+
+// The lane width the library will pick must exist: 4-byte aligned data, and per-element state that the narrowest lane
+// (4 bytes of the row: 4 / sizeof(element) fp32 words) can move.
+void CheckGroupedAlignment(const GroupedStep& c, const at::Tensor& rows, const int64_t element_size,
+                           const std::vector<const std::vector<const void*>*>& per_element_states) {
+  uintptr_t bits = reinterpret_cast<uintptr_t>(rows.data_ptr());
+  for (const void* p : c.table_host) bits |= reinterpret_cast<uintptr_t>(p);
+  TORCH_CHECK(bits % 4 == 0, "cuembed_pyt: tables and rows must be 4-byte aligned");
+  const uintptr_t state_align = 4 * (4 / static_cast<uintptr_t>(element_size));
+  for (const auto* host : per_element_states)
+    for (const void* p : *host)
+      TORCH_CHECK(reinterpret_cast<uintptr_t>(p) % state_align == 0, "cuembed_pyt: per-element state must be ", state_align,
+                  "-byte aligned for tables of ", element_size, "-byte elements");
+}
+
+void cuembed_sparse_row_update_grouped_op(const at::TensorList tables, const at::Tensor& table_ptrs,
+                                          const at::TensorList states, const c10::optional<at::Tensor>& state_ptrs,
+                                          const at::Tensor& row_base, const at::Tensor& ids, const at::Tensor& rows,
+                                          const std::string& rule, const double lr, const double eps,
+                                          const c10::optional<at::Tensor>& lr_device, const int64_t count,
+                                          const c10::optional<at::Tensor>& count_word,
+                                          const c10::optional<at::Tensor>& last_id, const bool stochastic_rounding) {
+  const int code = rule == "sgd" ? CUEMBED_UPDATE_SGD
+                   : rule == "adagrad" ? CUEMBED_UPDATE_ADAGRAD
+                   : rule == "rowwise_adagrad" ? CUEMBED_UPDATE_ROWWISE_ADAGRAD : -1;
+  TORCH_CHECK(code >= 0, "cuembed_pyt: rule must be 'sgd', 'adagrad' or 'rowwise_adagrad'");
+  TORCH_CHECK(!tables.empty(), "cuembed_pyt: a group needs at least one table");
+  const GroupedStep c =
+      CheckGroupedStep(tables, table_ptrs, row_base, ids, rows, lr_device, count, count_word, last_id, stochastic_rounding);
+  std::vector<const void*> state_host;
+  if (code == CUEMBED_UPDATE_SGD) {
+    TORCH_CHECK(states.empty(), "cuembed_pyt: rule 'sgd' takes no states");
+  } else {
+    state_host = CheckGroupedStates(tables, states, state_ptrs, code == CUEMBED_UPDATE_ADAGRAD, "states");
+  }
+  std::vector<const std::vector<const void*>*> per_element;
+  if (code == CUEMBED_UPDATE_ADAGRAD) per_element.push_back(&state_host);
+  CheckGroupedAlignment(c, rows, tables[0].element_size(), per_element);
+  if (ids.numel() == 0) return;
+  const at::DeviceGuard guard(tables[0].device());
+  const bool stateful = code != CUEMBED_UPDATE_SGD;
+  ::cuembed_sparse_row_update_grouped(
+      c.table_host.data(), static_cast<const void* const*>(table_ptrs.data_ptr()), stateful ? state_host.data() : nullptr,
+      stateful ? static_cast<const void* const*>(state_ptrs->data_ptr()) : nullptr, static_cast<int>(tables.size()),
+      c.elem, static_cast<int>(rows.size(1)), static_cast<const int64_t*>(row_base.data_ptr()), code, Ptr(ids), c.idx,
+      Ptr(rows), ids.numel(), c.num_rows, c.count_word, c.words64, c.last_id, static_cast<float>(lr), c.lr_word,
+      static_cast<float>(eps), CurrentStream(rows));
+}
+
+void cuembed_sparse_row_adam_grouped_op(const at::TensorList tables, const at::Tensor& table_ptrs,
+                                        const at::TensorList exp_avg, const at::Tensor& exp_avg_ptrs,
+                                        const at::TensorList exp_avg_sq, const at::Tensor& exp_avg_sq_ptrs,
+                                        const at::Tensor& row_base, const at::Tensor& ids, const at::Tensor& rows,
+                                        const bool rowwise, const double lr, const double bias_factor, const double beta1,
+                                        const double beta2, const double eps, const double weight_decay,
+                                        const c10::optional<at::Tensor>& lr_device,
+                                        const c10::optional<at::Tensor>& bias_factor_device, const int64_t count,
+                                        const c10::optional<at::Tensor>& count_word,
+                                        const c10::optional<at::Tensor>& last_id, const bool stochastic_rounding) {
+  TORCH_CHECK(!tables.empty(), "cuembed_pyt: a group needs at least one table");
+  const GroupedStep c =
+      CheckGroupedStep(tables, table_ptrs, row_base, ids, rows, lr_device, count, count_word, last_id, stochastic_rounding);
+  const std::vector<const void*> m_host = CheckGroupedStates(tables, exp_avg, exp_avg_ptrs, true, "exp_avg");
+  const std::vector<const void*> v_host = CheckGroupedStates(tables, exp_avg_sq, exp_avg_sq_ptrs, !rowwise, "exp_avg_sq");
+  std::vector<const std::vector<const void*>*> per_element = {&m_host};
+  if (!rowwise) per_element.push_back(&v_host);
+  CheckGroupedAlignment(c, rows, tables[0].element_size(), per_element);
+  TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "cuembed_pyt: betas must lie in [0, 1)");
+  TORCH_CHECK(eps >= 0.0 && weight_decay >= 0.0, "cuembed_pyt: eps and weight_decay must not be negative");
+  const float* bias_word = nullptr;
+  if (bias_factor_device.has_value() && bias_factor_device->defined()) {
+    CheckGpu(*bias_factor_device, "bias_factor_device");
+    TORCH_CHECK(bias_factor_device->scalar_type() == at::kFloat && bias_factor_device->numel() == 1 &&
+                    bias_factor_device->device() == tables[0].device(),
+                "cuembed_pyt: bias_factor_device must be one float32 word on the tables' device");
+    bias_word = static_cast<const float*>(bias_factor_device->data_ptr());
+  }
+  if (ids.numel() == 0) return;
+  const at::DeviceGuard guard(tables[0].device());
+  ::cuembed_sparse_row_adam_grouped(
+      c.table_host.data(), static_cast<const void* const*>(table_ptrs.data_ptr()), m_host.data(),
+      static_cast<const void* const*>(exp_avg_ptrs.data_ptr()), v_host.data(),
+      static_cast<const void* const*>(exp_avg_sq_ptrs.data_ptr()), static_cast<int>(tables.size()), c.elem,
+      static_cast<int>(rows.size(1)), static_cast<const int64_t*>(row_base.data_ptr()),
+      rowwise ? CUEMBED_ROWWISE_ADAM : CUEMBED_ADAM, Ptr(ids), c.idx, Ptr(rows), ids.numel(), c.num_rows, c.count_word,
+      c.words64, c.last_id, static_cast<float>(lr), c.lr_word, static_cast<float>(bias_factor), bias_word,
+      static_cast<float>(beta1), static_cast<float>(1.0 - beta1), static_cast<float>(beta2),
+      static_cast<float>(1.0 - beta2), static_cast<float>(eps), static_cast<float>(weight_decay), CurrentStream(rows));
+}
+
 // Extension (cuembed::PackRowsByOwner): the rank's compressed gradient into the fixed slots of the all-to-all.
 void cuembed_exchange_pack_op(const at::Tensor& ids, const at::Tensor& rows, const c10::optional<at::Tensor>& count,
                               const at::Tensor& cuts, const int64_t slot_capacity, const int64_t input_capacity,
@@ -1450,6 +1634,16 @@ TORCH_LIBRARY(cuembed_pyt, m) {
       "rowwise, float lr, float bias_factor, float beta1, float beta2, float eps, float weight_decay, Tensor? lr_device, "
       "Tensor? bias_factor_device, int count, Tensor? counts, Tensor? last_id, int piece_rows, bool "
       "stochastic_rounding=False, int seed=0, int step=0, Tensor? step_device=None) -> ()");
+  // the same steps on a group of separate table tensors, in one launch each
+  m.def(
+      "cuembed_sparse_row_update_grouped(Tensor(a!)[] tables, Tensor table_ptrs, Tensor(b!)[] states, Tensor? state_ptrs, "
+      "Tensor row_base, Tensor ids, Tensor rows, str rule, float lr, float eps, Tensor? lr_device, int count, Tensor? "
+      "count_word, Tensor? last_id, bool stochastic_rounding=False) -> ()");
+  m.def(
+      "cuembed_sparse_row_adam_grouped(Tensor(a!)[] tables, Tensor table_ptrs, Tensor(b!)[] exp_avg, Tensor exp_avg_ptrs, "
+      "Tensor(c!)[] exp_avg_sq, Tensor exp_avg_sq_ptrs, Tensor row_base, Tensor ids, Tensor rows, bool rowwise, float lr, "
+      "float bias_factor, float beta1, float beta2, float eps, float weight_decay, Tensor? lr_device, Tensor? "
+      "bias_factor_device, int count, Tensor? count_word, Tensor? last_id, bool stochastic_rounding=False) -> ()");
   // 8-bit row-wise quantized tables (torch's fused layout), inference only
   m.def("quantize_rows(Tensor table) -> Tensor");
   m.def("dequantize_rows(Tensor qtable, Tensor? ids, ScalarType dtype) -> Tensor");
@@ -1505,6 +1699,8 @@ TORCH_LIBRARY_IMPL(cuembed_pyt, CUDA, m) {  // HIP tensors use the CUDA dispatch
   m.impl("cuembed_exchange_merge", cuembed_exchange_merge_op);
   m.impl("cuembed_sparse_row_update_", cuembed_sparse_row_update_op);
   m.impl("cuembed_sparse_row_adam_", cuembed_sparse_row_adam_op);
+  m.impl("cuembed_sparse_row_update_grouped", cuembed_sparse_row_update_grouped_op);
+  m.impl("cuembed_sparse_row_adam_grouped", cuembed_sparse_row_adam_grouped_op);
   m.impl("quantize_rows", quantize_rows_op);
   m.impl("dequantize_rows", dequantize_rows_op);
   m.impl("cuemb_embedding_quantized", cuemb_embedding_quantized_op);

@@ -77,6 +77,14 @@ def _define_python_ops():
                 " float weight_decay, Tensor? lr_device, Tensor? bias_factor_device, int count, Tensor? counts,"
                 " Tensor? last_id, int piece_rows, bool stochastic_rounding=False, int seed=0, int step=0,"
                 " Tensor? step_device=None) -> ()")
+    _lib.define("cuembed_sparse_row_update_grouped(Tensor(a!)[] tables, Tensor table_ptrs, Tensor(b!)[] states,"
+                " Tensor? state_ptrs, Tensor row_base, Tensor ids, Tensor rows, str rule, float lr, float eps,"
+                " Tensor? lr_device, int count, Tensor? count_word, Tensor? last_id, bool stochastic_rounding=False) -> ()")
+    _lib.define("cuembed_sparse_row_adam_grouped(Tensor(a!)[] tables, Tensor table_ptrs, Tensor(b!)[] exp_avg,"
+                " Tensor exp_avg_ptrs, Tensor(c!)[] exp_avg_sq, Tensor exp_avg_sq_ptrs, Tensor row_base, Tensor ids,"
+                " Tensor rows, bool rowwise, float lr, float bias_factor, float beta1, float beta2, float eps,"
+                " float weight_decay, Tensor? lr_device, Tensor? bias_factor_device, int count, Tensor? count_word,"
+                " Tensor? last_id, bool stochastic_rounding=False) -> ()")
     _lib.define("quantize_rows(Tensor table) -> Tensor")
     _lib.define("dequantize_rows(Tensor qtable, Tensor? ids, ScalarType dtype) -> Tensor")
     _lib.define("cuemb_embedding_quantized(Tensor qtable, Tensor indices, Tensor? offsets, Tensor? weights, str mode,"
@@ -103,6 +111,8 @@ def _define_python_ops():
     _lib.impl("cuemb_embedding_quantized", _embedding_quantized_impl, "CUDA")
     _lib.impl("cuembed_sparse_row_update_", _sparse_row_update_impl, "CUDA")
     _lib.impl("cuembed_sparse_row_adam_", _sparse_row_adam_impl, "CUDA")
+    _lib.impl("cuembed_sparse_row_update_grouped", _sparse_row_update_grouped_impl, "CUDA")
+    _lib.impl("cuembed_sparse_row_adam_grouped", _sparse_row_adam_grouped_impl, "CUDA")
     _lib.impl("cuembed_decide_row_loads", _decide_row_loads_impl, "CUDA")
     _lib.impl("cuembed_embedding_forward_hinted", _forward_hinted_impl, "CUDA")
     _lib.impl("cuembed_bag_order_by_length", _bag_order_impl, "CUDA")
@@ -139,6 +149,8 @@ def _define_python_ops():
 #                                             row-wise Adagrad; the entry count may stay on the device)
 #   cuembed_sparse_row_adam_                  the same for the Adam family (lazy Adam, row-wise Adam; decoupled weight
 #                                             decay; the bias factor may stay on the device)
+#   cuembed_sparse_row_update_grouped,        both steps on a group of SEPARATE table tensors, in one launch each: the
+#   cuembed_sparse_row_adam_grouped           kernel finds every entry's table itself (global row ids, row_base)
 #   quantize_rows, dequantize_rows,           8-bit row-wise quantized tables in torch's own fused layout (inference
 #   cuemb_embedding_quantized                 only): the quantizer, its inverse, and the lookup on a fused table
 #   cuemb_embedding_grouped,                  a group of tables of one width and dtype pooled in ONE launch into
@@ -316,6 +328,35 @@ def _sparse_row_adam_impl(table, exp_avg, exp_avg_sq, ids, rows, rowwise, lr, bi
                          lr=lr if lr_device is None else lr_device,
                          bias_factor=bias_factor if bias_factor_device is None else bias_factor_device,
                          betas=(beta1, beta2), eps=eps, weight_decay=weight_decay, rowwise=rowwise, **kw)
+
+
+def _grouped_count(count, count_word, last_id):
+    _require((count >= 0) + (count_word is not None) + (last_id is not None) <= 1,
+             "give at most one of count, count_word and last_id")
+    if count_word is not None:
+        return dict(count=count_word)
+    if last_id is not None:
+        return dict(last_id=last_id)
+    return dict(count=count if count >= 0 else None)
+
+
+def _sparse_row_update_grouped_impl(tables, table_ptrs, states, state_ptrs, row_base, ids, rows, rule, lr, eps, lr_device,
+                                    count, count_word, last_id, stochastic_rounding=False):
+    from . import grouped as _g, grouped_backward as _gb
+    _gb.sparse_row_update_grouped(_g.TableGroup(tables, table_ptrs=table_ptrs), ids, rows, rule=rule,
+                                  lr=lr if lr_device is None else lr_device, states=list(states) or None, eps=eps,
+                                  stochastic_rounding=stochastic_rounding, **_grouped_count(count, count_word, last_id))
+
+
+def _sparse_row_adam_grouped_impl(tables, table_ptrs, exp_avg, exp_avg_ptrs, exp_avg_sq, exp_avg_sq_ptrs, row_base, ids,
+                                  rows, rowwise, lr, bias_factor, beta1, beta2, eps, weight_decay, lr_device,
+                                  bias_factor_device, count, count_word, last_id, stochastic_rounding=False):
+    from . import grouped as _g, grouped_backward as _gb
+    _gb.sparse_row_adam_grouped(_g.TableGroup(tables, table_ptrs=table_ptrs), ids, rows, exp_avg=list(exp_avg),
+                                exp_avg_sq=list(exp_avg_sq), lr=lr if lr_device is None else lr_device,
+                                bias_factor=bias_factor if bias_factor_device is None else bias_factor_device,
+                                betas=(beta1, beta2), eps=eps, weight_decay=weight_decay, rowwise=rowwise,
+                                stochastic_rounding=stochastic_rounding, **_grouped_count(count, count_word, last_id))
 
 
 def _quantize_rows_impl(table):
@@ -521,6 +562,45 @@ def cuembed_sparse_row_adam_(table, ids, rows, *, exp_avg, exp_avg_sq, lr, bias_
     step_device = step if isinstance(step, torch.Tensor) else None
     torch.ops.cuembed_pyt.cuembed_sparse_row_adam_(
         *args, True, _signed_word("seed", seed), 0 if step_device is not None else _signed_word("step", step), step_device)
+
+
+def _grouped_step_args(group, count, last_id):
+    from . import grouped as _g
+    group = _g._as_group(group)
+    word = count if isinstance(count, torch.Tensor) else None
+    return group, -1 if (count is None or word is not None) else int(count), word
+
+
+def cuembed_sparse_row_update_grouped(group, ids, rows, *, rule, lr, states=None, eps=1e-8, count=None, last_id=None,
+                                      stochastic_rounding=False):
+    """cuembed_amd.sparse_row_update_grouped as the torch op cuembed_pyt::cuembed_sparse_row_update_grouped (in place on the
+    group's tables and on `states`; traces under torch.compile).  Same arguments."""
+    from . import grouped_backward as _gb
+    group, host_count, word = _grouped_step_args(group, count, last_id)
+    lr_device = lr if isinstance(lr, torch.Tensor) else None
+    state_ptrs = None if not states else _gb._state_ptrs(group, states)[1]
+    torch.ops.cuembed_pyt.cuembed_sparse_row_update_grouped(
+        list(group.tables), group.table_ptrs, list(states or ()), state_ptrs, group.row_base_device, ids, rows, rule,
+        0.0 if lr_device is not None else float(lr), float(eps), lr_device, host_count, word, last_id,
+        bool(stochastic_rounding))
+
+
+def cuembed_sparse_row_adam_grouped(group, ids, rows, *, exp_avg, exp_avg_sq, lr, bias_factor=1.0, betas=(0.9, 0.999),
+                                    eps=1e-8, weight_decay=0.0, rowwise=False, count=None, last_id=None,
+                                    stochastic_rounding=False):
+    """cuembed_amd.sparse_row_adam_grouped as the torch op cuembed_pyt::cuembed_sparse_row_adam_grouped (in place on the
+    group's tables, `exp_avg` and `exp_avg_sq`; traces under torch.compile).  Same arguments."""
+    from . import grouped_backward as _gb
+    group, host_count, word = _grouped_step_args(group, count, last_id)
+    lr_device = lr if isinstance(lr, torch.Tensor) else None
+    bias_device = bias_factor if isinstance(bias_factor, torch.Tensor) else None
+    beta1, beta2 = betas
+    torch.ops.cuembed_pyt.cuembed_sparse_row_adam_grouped(
+        list(group.tables), group.table_ptrs, list(exp_avg), _gb._state_ptrs(group, exp_avg)[1], list(exp_avg_sq),
+        _gb._state_ptrs(group, exp_avg_sq)[1], group.row_base_device, ids, rows, bool(rowwise),
+        0.0 if lr_device is not None else float(lr), 1.0 if bias_device is not None else float(bias_factor), float(beta1),
+        float(beta2), float(eps), float(weight_decay), lr_device, bias_device, host_count, word, last_id,
+        bool(stochastic_rounding))
 
 
 def quantize_rows(table):
@@ -1091,6 +1171,19 @@ def _(table, state, ids, rows, rule, lr, eps, lr_device=None, count=-1, counts=N
 def _(table, exp_avg, exp_avg_sq, ids, rows, rowwise, lr, bias_factor, beta1, beta2, eps, weight_decay, lr_device=None,
       bias_factor_device=None, count=-1, counts=None, last_id=None, piece_rows=0, stochastic_rounding=False, seed=0,
       step=0, step_device=None):
+    return None
+
+
+@torch.library.register_fake("cuembed_pyt::cuembed_sparse_row_update_grouped")
+def _(tables, table_ptrs, states, state_ptrs, row_base, ids, rows, rule, lr, eps, lr_device=None, count=-1,
+      count_word=None, last_id=None, stochastic_rounding=False):
+    return None
+
+
+@torch.library.register_fake("cuembed_pyt::cuembed_sparse_row_adam_grouped")
+def _(tables, table_ptrs, exp_avg, exp_avg_ptrs, exp_avg_sq, exp_avg_sq_ptrs, row_base, ids, rows, rowwise, lr,
+      bias_factor, beta1, beta2, eps, weight_decay, lr_device=None, bias_factor_device=None, count=-1, count_word=None,
+      last_id=None, stochastic_rounding=False):
     return None
 
 

@@ -83,6 +83,7 @@ class TableGroup:
         self.row_counts = tuple(int(t.shape[0]) for t in tables)
         self.flat = None                 # the one storage of allocate() / from_flat(); None for separate tensors
         self._row_base_device = None
+        self._state_ptr_arrays = {}      # the pointer arrays of per-table optimizer state (grouped_backward._state_ptrs)
 
     @property
     def row_base(self):

@@ -18,6 +18,11 @@ global ids are directly rows of group.flat, so the sparse optimizers apply as th
     g = embedding_backward_grouped(group, grad_y, idx, offsets)
     sparse_row_update(group.flat, g.ids, g.rows, rule="sgd", lr=lr, last_id=g.last_id)      # or sparse_row_adam, or a
                                                                                             # cuembed_amd.optim updater
+For a group of SEPARATE tensors (one parameter per table, as most models hold them) the same gradient is applied in ONE
+launch by the grouped step, which finds each entry's table on the device -- no cuts, no read-back, capturable:
+
+    sparse_row_update_grouped(group, g.ids, g.rows, rule="sgd", lr=lr, last_id=g.last_id)   # or sparse_row_adam_grouped, or
+                                                                                            # cuembed_amd.optim.GroupSparseUpdater
 The sort is stable, so inside one table row the lookups keep the order of the single-table pipeline: on exactly
 representable data, and with reference_sums=True on any data, the result has the bits of T single-table calls.  With
 the default arithmetic the segment cuts of the scatter-add move with the position in the combined stream: the same
@@ -26,11 +31,14 @@ sums, associated differently.
 Everything validates before any launch and runs on torch's current stream.  The fixed-hotness path materialises the
 sample ids, which transpose_fixed_hotness avoids for one table.
 """
+import ctypes
+
 import torch
 
 from . import _lib
 from .grouped import INT_MAX, _as_group
-from .ops import _ELEM, _INDEX, _check_alignment, _check_dev, _index_code, _ptr, _stream, embedding_backward, transpose
+from .ops import (ADAM_RULES, UPDATE_RULES, _ELEM, _INDEX, _check_alignment, _check_betas, _check_dev, _entry_counts,
+                  _index_code, _ptr, _stream, embedding_backward, transpose)
 
 
 def _layout(group, indices, offsets, batch_size, num_hots):
@@ -372,3 +380,180 @@ def embedding_backward_grouped(group, grad_y, indices, offsets=None, weights=Non
         embedding_backward(grad_2d, None, t_keys, t_sids, remap, t_w, grad_embedding=rows, inverse_mapping=ids)
         last_id = remap[-1:]
     return GroupedGrad(ids, rows, last_id, group.row_base, group.row_base_device)
+
+
+# ---- the optimizer step on a group of separate tensors (cuembed::SparseRowUpdateGrouped / SparseRowAdamGrouped) ------
+MAX_GROUPED_STEP_TABLES = 1023   # detail::kGroupedMaxTables: row_base and the base pointers are staged in 32 KiB of LDS
+
+
+def _step_group(group, ids, rows, stochastic_rounding):
+    """What both grouped steps check first, without the GPU: the group, ids and rows.  Returns (group, index code, n)."""
+    group = _as_group(group)
+    if group.quantized:
+        raise TypeError("a group of fused 8-bit tables has no optimizer step: quantized tables are inference only")
+    if stochastic_rounding:
+        raise ValueError("stochastic rounding on a grouped step does not exist: its bits are named by the table row, which "
+                         "a global row is not; round to nearest, or step table by table (GroupedGrad.per_table)")
+    if group.num_tables > MAX_GROUPED_STEP_TABLES:
+        raise ValueError("a grouped step takes at most %d tables, the group has %d"
+                         % (MAX_GROUPED_STEP_TABLES, group.num_tables))
+    for name, t in (("ids", ids), ("rows", rows)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+    it = _index_code("ids", ids)
+    if rows.dtype != group.dtype:
+        raise TypeError("rows must have the tables' dtype (%s), got %s" % (group.dtype, rows.dtype))
+    if rows.dim() != 2 or rows.shape[1] != group.width:
+        raise ValueError("rows must be [entries, width = %d], got %r" % (group.width, tuple(rows.shape)))
+    if (group.width * rows.element_size()) % 4 != 0:
+        raise ValueError("the row size must be a multiple of 4 bytes")
+    if ids.dim() != 1 or rows.shape[0] != ids.numel():
+        raise ValueError("ids must hold one entry per row of rows: %d ids, %d rows" % (ids.numel(), rows.shape[0]))
+    return group, it, ids.numel()
+
+
+def _check_group_states(group, name, states, rowwise):
+    """`states`: a sequence of num_tables float32 tensors, [rows_t, width] or (rowwise) [rows_t]."""
+    if isinstance(states, torch.Tensor) or not isinstance(states, (list, tuple)):
+        raise TypeError("%s must be a sequence of %d float32 tensors, one per table" % (name, group.num_tables))
+    if len(states) != group.num_tables:
+        raise ValueError("%s must hold one tensor per table: the group has %d tables, got %d"
+                         % (name, group.num_tables, len(states)))
+    for t, (s, n) in enumerate(zip(states, group.row_counts)):
+        want = (n,) if rowwise else (n, group.width)
+        if not isinstance(s, torch.Tensor):
+            raise TypeError("%s[%d] must be a float32 tensor of shape %r" % (name, t, want))
+        if s.dtype != torch.float32:
+            raise TypeError("%s[%d] must be float32, got %s" % (name, t, s.dtype))
+        if tuple(s.shape) != want:
+            raise ValueError("%s[%d] must have shape %r, got %r" % (name, t, want, tuple(s.shape)))
+    return tuple(states)
+
+
+def _state_ptrs(group, states):
+    """(host array, device tensor, OR of the pointers) of the base pointers of one state tensor per table.  The device
+    tensor is built ONCE per set of tensors and kept on the group, next to table_ptrs: a step copies nothing."""
+    ptrs = tuple(int(s.data_ptr()) for s in states)
+    cache = group._state_ptr_arrays
+    hit = cache.get(ptrs)
+    if hit is None:
+        if len(cache) >= 16:    # (state tensors that came and went)
+            cache.clear()
+        bits = 0
+        for p in ptrs:
+            bits |= p
+        hit = cache[ptrs] = ((ctypes.c_void_p * len(ptrs))(*ptrs),
+                             torch.tensor(ptrs, dtype=torch.int64, device=group.device), bits)
+    return hit
+
+
+def _word(name, value, dtype):
+    """A hyper-parameter as (float, device word): one-element tensors are read by the kernel."""
+    if isinstance(value, torch.Tensor):
+        if value.dtype != dtype or value.numel() != 1:
+            raise TypeError("a device-side %s must be a one-element %s tensor" % (name, dtype))
+        return 0.0, value
+    return float(value), None
+
+
+def _step_devices(group, named):
+    _check_dev("tables[0]", group.tables[0])
+    for name, t in named:
+        if t is not None:
+            _check_dev(name, t, group.device)
+
+
+def sparse_row_update_grouped(group, ids, rows, *, rule, lr, states=None, eps=1e-8, count=None, last_id=None,
+                              stochastic_rounding=False):
+    """sparse_row_update on a group of SEPARATE table tensors, in ONE launch (cuembed::SparseRowUpdateGrouped): (ids, rows)
+    is the compressed gradient of the group -- GroupedGrad's ids, GLOBAL rows of the tables laid end to end, distinct and
+    inside [0, group.total_rows) wherever valid -- and for every valid entry k the kernel finds the table t with
+    row_base[t] <= ids[k] < row_base[t + 1] itself and updates row ids[k] - row_base[t] of group.tables[t] and of states[t]
+    in place from rows[k].  Rows that no valid entry names keep their bits.  Returns None.
+
+        rule="sgd"              states=None
+        rule="adagrad"          states: num_tables float32 tensors [rows_t, width]
+        rule="rowwise_adagrad"  states: num_tables float32 tensors [rows_t]
+
+    The rules, lr (a float or a one-element fp32 device tensor), eps and the count sources count=int | count=tensor |
+    last_id=tensor are sparse_row_update's; a count below zero or above ids.numel() applies nothing.  The least aligned
+    table (and, for "adagrad", state tensor) decides the lane width for the whole group, and the result has the bits of
+    num_tables sparse_row_update calls at that lane width.  Round to nearest: stochastic_rounding=True is an error.
+    Everything is validated before the launch; nothing is read back, so the call can be captured into a HIP graph (the
+    pointer arrays of `states` are built at the first call with these tensors and kept on the group)."""
+    group, it, n = _step_group(group, ids, rows, stochastic_rounding)
+    if rule not in UPDATE_RULES:
+        raise ValueError("rule must be one of %r, got %r" % (sorted(UPDATE_RULES), rule))
+    if rule == "sgd":
+        if states is not None:
+            raise ValueError("rule='sgd' takes no states")
+    else:
+        states = _check_group_states(group, "states", states, rule == "rowwise_adagrad")
+    num_rows, count_word, words64, _, _ = _entry_counts(ids, count, last_id, None, None)
+    lr, lr_word = _word("lr", lr, torch.float32)
+    # ---- the call is in order: now the devices
+    _step_devices(group, (("ids", ids), ("rows", rows), ("count", count_word), ("last_id", last_id), ("lr", lr_word)) +
+                  tuple(("states[%d]" % t, s) for t, s in enumerate(states or ())))
+    host = dev = None
+    state_bits = ()
+    if states is not None:
+        host, dev, bits = _state_ptrs(group, states)
+        state_bits = (("states", bits),) if rule == "adagrad" else ()
+    _check_alignment("tables", _or(group.host_ptrs), rows.element_size(), group.width,
+                     others=(("rows", rows.data_ptr()),), state=state_bits, max_lanes=None)
+    if n == 0:
+        return None
+    with torch.cuda.device(group.device):
+        _lib.lib().cuembed_sparse_row_update_grouped(
+            group._host_array, _ptr(group.table_ptrs), host, _ptr(dev), group.num_tables, _ELEM[group.dtype], group.width,
+            _ptr(group.row_base_device), UPDATE_RULES[rule], _ptr(ids), it, _ptr(rows), n, int(num_rows), _ptr(count_word),
+            int(words64), _ptr(last_id), lr, _ptr(lr_word), float(eps), _stream(rows))
+    return None
+
+
+def sparse_row_adam_grouped(group, ids, rows, *, exp_avg, exp_avg_sq, lr, bias_factor=1.0, betas=(0.9, 0.999), eps=1e-8,
+                            weight_decay=0.0, rowwise=False, count=None, last_id=None, stochastic_rounding=False):
+    """sparse_row_adam on a group of SEPARATE table tensors, in ONE launch (cuembed::SparseRowAdamGrouped): as
+    sparse_row_update_grouped, with exp_avg a sequence of num_tables float32 tensors [rows_t, width] and exp_avg_sq one of
+    [rows_t, width] tensors, or with rowwise=True of [rows_t] tensors.  lr, bias_factor (a float or a one-element fp32
+    device tensor: adam_clock_advance's word, one clock for the group), betas, eps, weight_decay (decoupled, named rows
+    only) and the formulas are sparse_row_adam's; the result has the bits of num_tables sparse_row_adam calls at the
+    group's lane width.  Round to nearest: stochastic_rounding=True is an error.  Nothing is read back."""
+    group, it, n = _step_group(group, ids, rows, stochastic_rounding)
+    exp_avg = _check_group_states(group, "exp_avg", exp_avg, False)
+    exp_avg_sq = _check_group_states(group, "exp_avg_sq", exp_avg_sq, bool(rowwise))
+    beta1, beta2 = _check_betas(betas)
+    if not float(eps) >= 0.0:
+        raise ValueError("eps must not be negative, got %r" % (eps,))
+    if not float(weight_decay) >= 0.0:
+        raise ValueError("weight_decay must not be negative, got %r" % (weight_decay,))
+    num_rows, count_word, words64, _, _ = _entry_counts(ids, count, last_id, None, None)
+    lr, lr_word = _word("lr", lr, torch.float32)
+    bias_factor, bias_word = _word("bias_factor", bias_factor, torch.float32)
+    # ---- the call is in order: now the devices
+    _step_devices(group, (("ids", ids), ("rows", rows), ("count", count_word), ("last_id", last_id), ("lr", lr_word),
+                          ("bias_factor", bias_word)) +
+                  tuple(("exp_avg[%d]" % t, s) for t, s in enumerate(exp_avg)) +
+                  tuple(("exp_avg_sq[%d]" % t, s) for t, s in enumerate(exp_avg_sq)))
+    m_host, m_dev, m_bits = _state_ptrs(group, exp_avg)
+    v_host, v_dev, v_bits = _state_ptrs(group, exp_avg_sq)
+    _check_alignment("tables", _or(group.host_ptrs), rows.element_size(), group.width,
+                     others=(("rows", rows.data_ptr()),),
+                     state=(("exp_avg", m_bits),) + ((("exp_avg_sq", v_bits),) if not rowwise else ()), max_lanes=None)
+    if n == 0:
+        return None
+    with torch.cuda.device(group.device):
+        _lib.lib().cuembed_sparse_row_adam_grouped(
+            group._host_array, _ptr(group.table_ptrs), m_host, _ptr(m_dev), v_host, _ptr(v_dev), group.num_tables,
+            _ELEM[group.dtype], group.width, _ptr(group.row_base_device),
+            ADAM_RULES["rowwise_adam" if rowwise else "adam"], _ptr(ids), it, _ptr(rows), n, int(num_rows),
+            _ptr(count_word), int(words64), _ptr(last_id), lr, _ptr(lr_word), bias_factor, _ptr(bias_word), beta1,
+            1.0 - beta1, beta2, 1.0 - beta2, float(eps), float(weight_decay), _stream(rows))
+    return None
+
+
+def _or(pointers):
+    bits = 0
+    for p in pointers:
+        bits |= p
+    return bits

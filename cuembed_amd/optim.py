@@ -40,6 +40,15 @@ The Adam family has entries of its own (two state tensors, more hyper-parameters
     "rowwise_adam"  m as above;  v_r <- beta2 * v_r + (1 - beta2) * mean_j(g_j^2);  w_j <- w_j - (lr * c) / (sqrt(v_r) + eps) * m_j
                     fp32 state [rows, W] + [rows]
 
+A GROUP of tables held as separate tensors (cuembed_amd.grouped.TableGroup) is stepped in ONE launch, whatever the
+number of tables, by
+
+    GroupSparseUpdater(group, rule, lr) / GroupSparseAdamUpdater(group, lr, ...)
+        .apply(grad)                            a GroupedGrad (cuembed_amd.grouped_backward.embedding_backward_grouped);
+        .backward_and_apply(grad_y, idx, offsets, weights, mode)     the grouped backward in its compressed form + the
+                                                step: no read-back, so forward + backward_and_apply can be captured.
+                                                They own one state tensor (Adam: two) per table; round to nearest only.
+
 Stochastic rounding (stochastic_rounding=True, seed=...; float16 / bfloat16 tables): the rounding to the table's dtype
 goes up or down with the probability of the fp32 value's position between its neighbours, so that updates below half a
 unit in the last place are kept on average instead of being rounded away at every step.  The bits are a pure function
@@ -49,6 +58,8 @@ after every apply, so a captured graph draws fresh bits at every replay) or in t
 """
 import torch
 
+from . import grouped as _grouped
+from . import grouped_backward as _grouped_backward
 from . import ops as _ops
 
 _ACCEPTED = ("the coalesced sparse COO gradient of cuemb_embedding(..., sparse_grad=True | 'reference' | 'blocked'); "
@@ -213,6 +224,111 @@ class SparseAdamUpdater(_CompressedGradientStep):
                              last_id=last_id, counts=counts, piece_rows=piece_rows, **kw)
         if self.stochastic_rounding:
             self.rounding_step.add_(1)      # on the device, after the kernel in stream order: one apply = one step
+
+
+class _GroupedGradientStep:
+    """The index path shared by GroupSparseUpdater and GroupSparseAdamUpdater: the grouped backward in its compressed form
+    -- global ids, rows, the count left on the device -- handed to self.apply(grad).  Needs self.group."""
+
+    def _init_group(self, group, stochastic_rounding):
+        group = _grouped._as_group(group)
+        if group.quantized:
+            raise TypeError("a group of fused 8-bit tables has no optimizer step: quantized tables are inference only")
+        if stochastic_rounding:
+            raise ValueError("stochastic rounding on a grouped step does not exist: use one SparseUpdater / "
+                             "SparseAdamUpdater per table (or a one-storage group's flat tensor) for it")
+        self.group = group
+
+    def backward_and_apply(self, grad_y, idx, offsets=None, weights=None, mode="sum"):
+        """The backward of out = embedding_forward_grouped(group, idx, offsets, weights, mode=mode) and the step, in one
+        go: embedding_backward_grouped(dense=False) -- keys, ONE sort, ONE scatter-add, the entry count left on the device
+        -- then the grouped step, which reads the count itself.  grad_y [batch, num_tables, width] of the tables' dtype;
+        idx [nnz] with offsets [num_tables * batch + 1] (CSR), or idx [num_tables, batch, hotness] with offsets=None.  No
+        host read-back: forward + backward_and_apply on separate tensors can be captured into a HIP graph."""
+        hot = 0
+        if offsets is None:
+            if idx.dim() != 3:
+                raise ValueError("without offsets, idx must be [num_tables, batch, hotness]")
+            hot = idx.shape[2]
+        grad = _grouped_backward.embedding_backward_grouped(self.group, grad_y, idx, offsets, weights, num_hots=hot,
+                                                            mode=mode)
+        self.apply(grad)
+        return grad
+
+    def _check_grad(self, grad):
+        if not isinstance(grad, _grouped_backward.GroupedGrad):
+            raise TypeError("apply takes the GroupedGrad of embedding_backward_grouped(dense=False), got %s"
+                            % type(grad).__name__)
+        if grad.row_base != self.group.row_base:
+            raise ValueError("the gradient belongs to a group with other row counts")
+
+
+class GroupSparseUpdater(_GroupedGradientStep):
+    """SparseUpdater for a TableGroup (or a list of tables) of SEPARATE tensors: applies a GroupedGrad to all tables in ONE
+    launch (cuembed_amd.grouped_backward.sparse_row_update_grouped) and owns the state, `.states`: None ("sgd") or one
+    fp32 tensor per table, [rows_t, width] ("adagrad") or [rows_t] ("rowwise_adagrad").  lr: a float or a one-element
+    fp32 device tensor; assign `.lr` to change it.  Round to nearest: stochastic_rounding=True is an error.  Works on a
+    one-storage group as well (its tables are views of group.flat)."""
+
+    def __init__(self, group, rule, lr, eps=1e-8, initial_accumulator_value=0.0, stochastic_rounding=False):
+        if rule not in _ops.UPDATE_RULES:
+            raise ValueError("rule must be one of %r, got %r" % (sorted(_ops.UPDATE_RULES), rule))
+        self._init_group(group, stochastic_rounding)
+        self.rule = rule
+        self.lr = lr
+        self.eps = float(eps)
+        self.states = None
+        if rule != "sgd":
+            self.states = tuple(_new_state(t, rule, initial_accumulator_value) for t in self.group.tables)
+            if self.group.device.type == "cuda":     # the pointer arrays, now: the first apply may be under capture
+                _grouped_backward._state_ptrs(self.group, self.states)
+                self.group.row_base_device
+
+    def apply(self, grad):
+        """tables[t][r] (and its state) <- rule, for the valid entries of a GroupedGrad.  Nothing is read back."""
+        self._check_grad(grad)
+        _grouped_backward.sparse_row_update_grouped(self.group, grad.ids, grad.rows, rule=self.rule, lr=self.lr,
+                                                    states=self.states, eps=self.eps, last_id=grad.last_id)
+
+
+class GroupSparseAdamUpdater(_GroupedGradientStep):
+    """SparseAdamUpdater for a TableGroup of SEPARATE tensors: one launch for the clock, one for all tables
+    (cuembed_amd.grouped_backward.sparse_row_adam_grouped).  Owns `.exp_avg` and `.exp_avg_sq`, one fp32 tensor per table
+    each ([rows_t, width]; exp_avg_sq [rows_t] with rowwise=True), and ONE bias-factor clock for the group (`.powers`,
+    `.bias_factor`), which every apply advances on the device: a captured step takes the next step at every replay.
+    bias_correction=False leaves the factor at 1.  Round to nearest: stochastic_rounding=True is an error."""
+
+    def __init__(self, group, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rowwise=False, bias_correction=True,
+                 stochastic_rounding=False):
+        self.betas = _ops._check_betas(betas)
+        if not float(eps) >= 0.0 or not float(weight_decay) >= 0.0:
+            raise ValueError("eps and weight_decay must not be negative")
+        self._init_group(group, stochastic_rounding)
+        self.lr = lr
+        self.eps = float(eps)
+        self.weight_decay = float(weight_decay)
+        self.rowwise = bool(rowwise)
+        self.bias_correction = bool(bias_correction)
+        moments = [_new_moments(t, self.rowwise) for t in self.group.tables]
+        self.exp_avg = tuple(m for m, _ in moments)
+        self.exp_avg_sq = tuple(v for _, v in moments)
+        dev = self.group.device
+        self.powers = torch.tensor([0.0, 1.0, 1.0], dtype=torch.float64, device=dev)
+        self.bias_factor = torch.ones((1,), dtype=torch.float32, device=dev)
+        self._one = None if self.bias_correction else torch.ones((1,), dtype=torch.float32, device=dev)
+        if dev.type == "cuda":     # the pointer arrays, now: the first apply may be under capture
+            _grouped_backward._state_ptrs(self.group, self.exp_avg)
+            _grouped_backward._state_ptrs(self.group, self.exp_avg_sq)
+            self.group.row_base_device
+
+    def apply(self, grad):
+        """One Adam step on the valid entries of a GroupedGrad: the clock moves on, then the grouped step."""
+        self._check_grad(grad)
+        _ops.adam_clock_advance(self.powers, self.bias_factor, self.betas)
+        _grouped_backward.sparse_row_adam_grouped(
+            self.group, grad.ids, grad.rows, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, lr=self.lr,
+            bias_factor=self.bias_factor if self.bias_correction else self._one, betas=self.betas, eps=self.eps,
+            weight_decay=self.weight_decay, rowwise=self.rowwise, last_id=grad.last_id)
 
 
 def _new_moments(table, rowwise):

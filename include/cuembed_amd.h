@@ -830,6 +830,38 @@ void cuembed_embedding_weight_grad_grouped(const void* const* tables_host, const
 void cuembed_grouped_mean_scale(const void* grad_y, int elem_type, int embed_width, const void* offsets,
                                 int offset_type, const void* weights, int num_tables, int batch_per_table, int num_hots,
                                 void* out, cuembed_stream_t stream);
+/* ---- extension: the sparse optimizer step on a group of SEPARATE table tensors, in one launch ---------------------------
+ * cuembed::SparseRowUpdateGrouped: cuembed_sparse_row_update on num_tables tables of elem_type and embed_width that are
+ * separate allocations.  ids (index_type) are GLOBAL rows of the tables laid end to end -- the compressed gradient of
+ * the sequence above --, rows their gradient rows; the kernel finds the table t of an entry itself (row_base[t] <= id <
+ * row_base[t + 1]; row_base: int64, DEVICE memory, num_tables + 1 entries) and updates row id - row_base[t] of tables[t]
+ * and of that table's state tensor.  tables_host / tables_device as in cuembed_embedding_forward_grouped (the host copy
+ * is read for the access width: the least aligned table decides for the group); state_host / state_device likewise hold
+ * the bases of the fp32 state tensors: both NULL for CUEMBED_UPDATE_SGD, [rows_t, embed_width] each for
+ * CUEMBED_UPDATE_ADAGRAD (host copy required), [rows_t] each for CUEMBED_UPDATE_ROWWISE_ADAGRAD (host copy not read).
+ * total_entries = the room of ids / rows.  The count, exactly one source: num_rows >= 0 on the host, else count_word
+ * (device; one int32 word, or int64 with count_word_is_64), else last_id (device; one word of index_type, count =
+ * last_id + 1); a count outside [0, total_entries] applies nothing.  Round to nearest.  num_tables <= 1023.  Nothing
+ * is allocated or read back. */
+void cuembed_sparse_row_update_grouped(const void* const* tables_host, const void* const* tables_device,
+                                       const void* const* state_host, const void* const* state_device, int num_tables,
+                                       int elem_type, int embed_width, const int64_t* row_base, int rule, const void* ids,
+                                       int index_type, const void* rows, int64_t total_entries, int64_t num_rows,
+                                       const void* count_word, int count_word_is_64, const void* last_id, float lr,
+                                       const float* lr_device, float eps, cuembed_stream_t stream);
+/* cuembed::SparseRowAdamGrouped: cuembed_sparse_row_adam on such a group.  exp_avg_* hold the bases of the fp32 [rows_t,
+ * embed_width] first moments, exp_avg_sq_* those of the second moments: [rows_t, embed_width] (CUEMBED_ADAM; host copy
+ * required) or [rows_t] (CUEMBED_ROWWISE_ADAM; host copy not read).  bias_factor_device serves the whole group.  The
+ * other parameters as above and as in cuembed_sparse_row_adam. */
+void cuembed_sparse_row_adam_grouped(const void* const* tables_host, const void* const* tables_device,
+                                     const void* const* exp_avg_host, const void* const* exp_avg_device,
+                                     const void* const* exp_avg_sq_host, const void* const* exp_avg_sq_device,
+                                     int num_tables, int elem_type, int embed_width, const int64_t* row_base, int rule,
+                                     const void* ids, int index_type, const void* rows, int64_t total_entries,
+                                     int64_t num_rows, const void* count_word, int count_word_is_64, const void* last_id,
+                                     float lr, const float* lr_device, float bias_factor, const float* bias_factor_device,
+                                     float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float eps,
+                                     float weight_decay, cuembed_stream_t stream);
 /* hipPeekAtLastError() as an int (0 = hipSuccess); launches themselves never
  * report errors, exactly like the reference. */
 int cuembed_peek_last_error(void);
