@@ -24,6 +24,16 @@ Shape families (those of the grouped forward and backward):
 
     python benchmarks/grouped_optimizer_step_benchmark.py --out profiles/grouped_optimizer_step_timing.json
 
+Stochastic rounding: `--stochastic-rounding` times the step alone with one seed per table instead (fp16 tables, the same
+two shapes and three rules; `--out profiles/grouped_optimizer_step_stochastic_timing.json`):
+    stochastic   the grouped step with stochastic_rounding=True, seeds=[one per table]
+    nearest      the grouped step with round to nearest, on the same tree: the difference prices the rounding
+    loop         GroupedGrad.per_table() -- the read-back -- and T single-table stochastic steps with seed = seeds[t]: the
+                 same bits as `stochastic`, and the only way to them without it; eager only
+    flat         the existing single-table stochastic step on a one-storage copy: other bits (named by the global row),
+                 the same work
+The step comes from one int64 device word in every stochastic arm.
+
 No regression on the existing step: `--existing-only --tree DIR --out FILE` times the `flat` arms alone with the package of
 another checkout (built there), e.g. the parent commit's; a full run with `--parent-existing FILE [FILE ...]` records them
 next to its own `flat` arms with the verdict of each pair (one such run before and one after the full run show the
@@ -66,7 +76,78 @@ def flat_state(torch, rule, total, width):
     return ()
 
 
+def run_family_stochastic(torch, ce, a, name, row_counts, width, batch, idx, offsets, hot, timers):
+    """--stochastic-rounding: the step alone, grouped with seeds against grouped nearest, the per-table loop and the
+    one-storage step, for the three rules."""
+    alternate, captured = timers
+    T, total, dtype = len(row_counts), sum(row_counts), torch.float16
+    flat_group = ce.TableGroup.allocate(row_counts, width, dtype=dtype)
+    flat_group.flat.uniform_(-1, 1)
+    grad_y = torch.empty((batch, T, width), dtype=dtype, device="cuda").uniform_(-1, 1)
+    grad = ce.embedding_backward_grouped(flat_group, grad_y, idx, offsets, num_hots=hot)
+    bias = torch.full((1,), 0.8, dtype=torch.float32, device="cuda")
+    step = torch.full((1,), 2 ** 32 + 5, dtype=torch.int64, device="cuda")
+    seeds = [0x9E3779B97F4A7C15 * (t + 1) % 2 ** 64 for t in range(T)]
+    r = dict(family=name, tables=T, width=width, batch_per_table=batch, hotness=hot or None, lookups=int(idx.numel()),
+             total_rows=int(total), entries=int(grad.last_id.item()) + 1, step_alone={})
+    group = ce.TableGroup([t.clone() for t in flat_group.tables])          # the same tables as separate tensors
+    from cuembed_amd import optim
+    for rule in RULES:
+        state = flat_state(torch, rule, total, width)
+        if rule == "rowwise_adam":
+            updater = optim.GroupSparseAdamUpdater(group, LR, rowwise=True)
+        else:
+            updater = optim.GroupSparseUpdater(group, rule, LR, initial_accumulator_value=0.1)
+
+        def grouped(rounding, updater=updater, rule=rule):
+            if rule == "rowwise_adam":      # (the functions, not updater.apply: no clock or step-word launch in any arm)
+                return lambda: ce.sparse_row_adam_grouped(group, grad.ids, grad.rows, exp_avg=updater.exp_avg,
+                                                          exp_avg_sq=updater.exp_avg_sq, lr=LR, bias_factor=bias,
+                                                          rowwise=True, last_id=grad.last_id, **rounding)
+            return lambda: ce.sparse_row_update_grouped(group, grad.ids, grad.rows, rule=rule, lr=LR, states=updater.states,
+                                                        last_id=grad.last_id, **rounding)
+
+        def loop(updater=updater, rule=rule):
+            for t, (ids, rows) in enumerate(grad.per_table()):           # (the read-back is inside per_table)
+                kw = dict(stochastic_rounding=True, seed=seeds[t], step=step)
+                if rule == "rowwise_adam":
+                    ce.sparse_row_adam(group.tables[t], ids, rows, exp_avg=updater.exp_avg[t],
+                                       exp_avg_sq=updater.exp_avg_sq[t], lr=LR, bias_factor=bias, rowwise=True, **kw)
+                else:
+                    ce.sparse_row_update(group.tables[t], ids, rows, rule=rule, lr=LR,
+                                         state=updater.states[t] if updater.states else None, **kw)
+
+        def flat(rule=rule, state=state):
+            kw = dict(stochastic_rounding=True, seed=seeds[0], step=step, last_id=grad.last_id)
+            if rule == "rowwise_adam":
+                return ce.sparse_row_adam(flat_group.flat, grad.ids, grad.rows, exp_avg=state[0], exp_avg_sq=state[1],
+                                          lr=LR, bias_factor=bias, rowwise=True, **kw)
+            return ce.sparse_row_update(flat_group.flat, grad.ids, grad.rows, rule=rule, lr=LR,
+                                        state=state[0] if state else None, **kw)
+
+        sides = {"stochastic": grouped(dict(stochastic_rounding=True, seeds=seeds, step=step)), "nearest": grouped({}),
+                 "loop": loop, "flat": flat}
+        eager = alternate(torch, sides, a.calls, a.rounds, a.warmup)
+        graph = alternate(torch, {k: captured(torch, f) for k, f in sides.items() if k != "loop"}, a.calls, a.rounds,
+                          a.warmup)
+        r["step_alone"][rule] = dict(
+            eager=eager, graph=graph,
+            verdicts={"eager stochastic against loop": verdict(eager["stochastic"], eager["loop"]),
+                      "graph stochastic against eager loop": verdict(graph["stochastic"], eager["loop"]),
+                      "eager stochastic against nearest": verdict(eager["stochastic"], eager["nearest"]),
+                      "graph stochastic against nearest": verdict(graph["stochastic"], graph["nearest"]),
+                      "eager stochastic against flat": verdict(eager["stochastic"], eager["flat"]),
+                      "graph stochastic against flat": verdict(graph["stochastic"], graph["flat"])})
+        line(name + " " + rule, "eager", eager)
+        line(name + " " + rule, "graph", graph)
+        print("    ", r["step_alone"][rule]["verdicts"], flush=True)
+        del state, updater, sides, grouped, loop, flat
+    return r
+
+
 def run_family(torch, ce, a, name, row_counts, width, batch, idx, offsets, hot, timers):
+    if a.stochastic_rounding:
+        return run_family_stochastic(torch, ce, a, name, row_counts, width, batch, idx, offsets, hot, timers)
     """idx: the group's ids (CSR: [nnz]; fixed: [T, B, H]); offsets: [T * B + 1] or None."""
     alternate, captured = timers
     T, total, dtype = len(row_counts), sum(row_counts), torch.float16
@@ -178,6 +259,9 @@ def main():
     p.add_argument("--out", default=None, help="write the JSON here as well")
     p.add_argument("--commit", default=None, help="commit the tree was built from (default: git rev-parse)")
     p.add_argument("--existing-only", action="store_true", help="time the one-storage (`flat`) step alone")
+    p.add_argument("--stochastic-rounding", action="store_true",
+                   help="time the step alone with stochastic rounding: grouped with one seed per table against grouped "
+                        "nearest, the per-table loop and the one-storage step")
     p.add_argument("--tree", default=ROOT, help="import cuembed_amd from this checkout (with --existing-only: e.g. the parent's)")
     p.add_argument("--this-existing", default=None,
                    help="the JSON of an --existing-only run of THIS tree: what the parent's runs are compared with "
@@ -185,6 +269,8 @@ def main():
     p.add_argument("--parent-existing", nargs="*", default=None,
                    help="the JSON files of --existing-only runs on the parent commit, to record next to this run")
     a = p.parse_args()
+    if a.stochastic_rounding and (a.existing_only or a.parent_existing or a.this_existing):
+        sys.exit("--stochastic-rounding is a run of its own: not with --existing-only / --parent-existing / --this-existing")
     if a.tree != ROOT and not a.existing_only:
         sys.exit("--tree goes with --existing-only: another checkout has no grouped step to time")
     sys.path.insert(0, os.path.abspath(a.tree))
@@ -201,7 +287,8 @@ def main():
                   package="this tree" if os.path.abspath(a.tree) == ROOT else "another checkout (--tree)",
                   device=torch.cuda.get_device_name(0),
                   arch=getattr(torch.cuda.get_device_properties(0), "gcnArchName", None), torch=torch.__version__,
-                  calls_per_round=a.calls, rounds=a.rounds, existing_only=a.existing_only, families=[])
+                  calls_per_round=a.calls, rounds=a.rounds, existing_only=a.existing_only,
+                  stochastic_rounding=a.stochastic_rounding, families=[])
     timers = (alternate, captured)
     families = a.families.split(",")
 

@@ -205,6 +205,13 @@ def _declare(L):
     L.cuembed_sparse_row_adam_grouped.restype = None
     L.cuembed_sparse_row_adam_grouped.argtypes = [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _I, _VP, _L, _L,
                                                   _VP, _I, _VP, _F, _VP, _F, _VP, _F, _F, _F, _F, _F, _F, _VP]
+    # the same with stochastic rounding: ... + seeds_device, step, step_device in front of the stream
+    L.cuembed_sparse_row_update_grouped_stochastic.restype = None
+    L.cuembed_sparse_row_update_grouped_stochastic.argtypes = (
+        list(L.cuembed_sparse_row_update_grouped.argtypes[:-1]) + [_VP, _U, _VP, _VP])
+    L.cuembed_sparse_row_adam_grouped_stochastic.restype = None
+    L.cuembed_sparse_row_adam_grouped_stochastic.argtypes = (
+        list(L.cuembed_sparse_row_adam_grouped.argtypes[:-1]) + [_VP, _U, _VP, _VP])
     L.cuembed_peek_last_error.restype = _I
     L.cuembed_peek_last_error.argtypes = []
     L.cuembed_version.restype = ctypes.c_char_p

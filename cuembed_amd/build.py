@@ -24,7 +24,8 @@ UNITS = ["c_api_forward.hip", "c_api_backward.hip", "c_api_transforms.hip", "c_a
          "c_api_optimizer.hip", "c_api_optimizer_stochastic.hip", "c_api_optimizer_adam.hip",
          "c_api_optimizer_adam_stochastic.hip", "c_api_optimizer_placed_stochastic.hip",
          "c_api_optimizer_adam_placed_stochastic.hip", "c_api_quantized.hip", "c_api_grouped.hip",
-         "c_api_grouped_backward.hip", "c_api_row_cache.hip", "c_api_optimizer_grouped.hip"]
+         "c_api_grouped_backward.hip", "c_api_row_cache.hip", "c_api_optimizer_grouped.hip",
+         "c_api_optimizer_grouped_stochastic.hip"]
 ARCH = "gfx950"
 
 HIPCC_FLAGS = [
@@ -381,6 +382,31 @@ def build_grouped_sparse_update_test(force=False):
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed for tests/cpp/grouped_sparse_update_kat.hip:\n" + r.stdout)
+    with open(stamp, "w") as f:
+        f.write(digest)
+    return exe
+
+
+def build_grouped_stochastic_rounding_test(force=False):
+    """Compiles tests/cpp/grouped_stochastic_rounding_kat.hip: cuembed::SparseRowUpdateGrouped / SparseRowAdamGrouped with
+    stochastic rounding and one seed per table through the header-only API on a three-table group, against a host
+    recomputation with stochastic_rounding.hpp's host functions on exactly representable data.  Needs a GPU to RUN
+    (tests/test_gpu_cpp_grouped_stochastic_rounding.py)."""
+    src = os.path.join(ROOT, "tests", "cpp", "grouped_stochastic_rounding_kat.hip")
+    exe = os.path.join(ROOT, "tests", "cpp", "grouped_stochastic_rounding_kat")
+    stamp = exe + ".stamp"
+    deps = [src]
+    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
+        deps += [os.path.join(dirpath, f) for f in files]
+    digest = _digest_files(deps)
+    if not force and os.path.exists(exe) and os.path.exists(stamp):
+        with open(stamp) as f:
+            if f.read().strip() == digest:
+                return exe
+    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-I" + CSRC, src, "-o", exe]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("hipcc failed for tests/cpp/grouped_stochastic_rounding_kat.hip:\n" + r.stdout)
     with open(stamp, "w") as f:
         f.write(digest)
     return exe

@@ -1,6 +1,6 @@
 // C ABI: the sparse optimizer step on a group of separate table tensors = explicit instantiations of
-// cuembed::SparseRowUpdateGrouped / SparseRowAdamGrouped (round to nearest; an extension: the reference ends at the
-// gradient and takes one table).
+// cuembed::SparseRowUpdateGrouped / SparseRowAdamGrouped (round to nearest; c_api_optimizer_grouped_stochastic.hip holds
+// the stochastic kernels.  An extension: the reference ends at the gradient and takes one table).
 #include "c_api_optimizer_adam_common.hpp"
 #include "cuembed/include/grouped_sparse_update.hpp"
 
@@ -11,7 +11,7 @@ void UpdateGrouped(const void* const* tables_host, const void* const* tables_dev
                    const void* const* state_device, int num_tables, const int64_t* row_base, int embed_width,
                    const void* ids, const void* rows, int64_t total_entries, const cuembed::SparseUpdateOptions& options,
                    cuembed_stream_t stream) {
-  cuembed::SparseRowUpdateGrouped<ElemT, IndexT>(
+  cuembed::SparseRowUpdateGrouped<ElemT, IndexT, cuembed::UpdateRoundings::kNearestOnly>(
       reinterpret_cast<const ElemT* const*>(tables_host),
       reinterpret_cast<ElemT* const*>(const_cast<void* const*>(reinterpret_cast<const void* const*>(tables_device))),
       reinterpret_cast<const float* const*>(state_host),
@@ -29,7 +29,7 @@ void AdamGrouped(const void* const* tables_host, const void* const* tables_devic
   const auto mut = [](const void* const* p) {
     return reinterpret_cast<float* const*>(const_cast<void* const*>(reinterpret_cast<const void* const*>(p)));
   };
-  cuembed::SparseRowAdamGrouped<ElemT, IndexT>(
+  cuembed::SparseRowAdamGrouped<ElemT, IndexT, cuembed::UpdateRoundings::kNearestOnly>(
       reinterpret_cast<const ElemT* const*>(tables_host),
       reinterpret_cast<ElemT* const*>(const_cast<void* const*>(reinterpret_cast<const void* const*>(tables_device))),
       reinterpret_cast<const float* const*>(exp_avg_host), mut(exp_avg_device),

@@ -2,10 +2,11 @@
 // API (an extension: the reference ends at the gradient and takes one table).
 //
 //   cuembed::SparseRowUpdateGrouped<ElemT, IndexT>(tables_host, tables_device, state_host, state_device, num_tables,
-//                                                  row_base_device, embed_width, ids, rows, total_entries, options, stream)
+//                                                  row_base_device, embed_width, ids, rows, total_entries, options, stream,
+//                                                  seeds_device)
 //   cuembed::SparseRowAdamGrouped<ElemT, IndexT>(tables_host, tables_device, exp_avg_host, exp_avg_device,
 //                                                exp_avg_sq_host, exp_avg_sq_device, num_tables, row_base_device,
-//                                                embed_width, ids, rows, total_entries, options, stream)
+//                                                embed_width, ids, rows, total_entries, options, stream, seeds_device)
 //
 // consume the compressed gradient of a table group (grouped_backward.hpp: `ids` are GLOBAL rows of the tables laid end to
 // end, ascending, `rows` their gradient rows) and update the named rows of T separate tensors and of their T (or 2 T) state
@@ -19,9 +20,16 @@
 // the host never waits; misuse CUEMBED_ASSERTs (prints and aborts) like every other entry point.
 //
 // Arithmetic, lane groups, entries in flight and launch shape are those of SparseRowUpdate / SparseRowAdam at the same
-// lane width: the result has the bits of T single-table calls that run at that lane width.  Round to nearest only: a
-// grouped step with stochastic rounding does not exist (the rounding bits are named by the table row, and a global row
-// is not one), and options.stochastic_rounding aborts.  Tables behind the row cache are not taken either.
+// lane width: the result has the bits of T single-table calls that run at that lane width.
+//
+// Stochastic rounding (16-bit tables): options.stochastic_rounding with seeds_device, ONE 64-bit SEED PER TABLE in device
+// memory.  The bits of entry k are those of (seeds[t], step, r, column), t the table that owns ids[k] and r = ids[k] -
+// row_base[t] its row inside that table; the step is options.rounding_step or the device word options.rounding_step_device,
+// one value for the group, and options.rounding_seed is not read.  So the step has the bits of T single-table stochastic
+// steps with seed = seeds[t] at the same step, and a table's trajectory depends neither on the group it is in nor on its
+// place in it.  (This is NOT the naming of the single-table step on a one-storage group's flat tensor, which names the
+// bits by the global row: the two draw different bits.)  There are no default seeds: stochastic_rounding without
+// seeds_device, and seeds_device without stochastic_rounding, abort.  Tables behind the row cache are not taken.
 #ifndef CUEMBED_INCLUDE_GROUPED_SPARSE_UPDATE_HPP_
 #define CUEMBED_INCLUDE_GROUPED_SPARSE_UPDATE_HPP_
 
@@ -36,16 +44,19 @@ namespace detail {
 //! Entries in flight of the grouped kernels whose lanes hold one slice per entry (WalkNamedRows' kEntries): those of
 //! their single-table counterparts.  No instantiation spills with them (profiles/sparse_update_grouped_kernel_resources.txt).
 constexpr int kGroupedEntriesInFlight = 2;
+//! The same for the stochastic grouped kernels (profiles/sparse_update_grouped_stochastic_kernel_resources.txt).
+constexpr int kGroupedStochasticEntriesInFlight = 2;
 
 //! The checks both grouped steps share, and the options of the one piece they walk: (false: nothing to do).
 inline bool CheckGroupedStep(SparseStepOptions& o, const void* tables_host, const void* tables_device,
                              const int num_tables, const int64_t* row_base_device, const void* ids, const void* rows,
-                             const int64_t total_entries) {
+                             const int64_t total_entries, const uint64_t* seeds_device) {
   CUEMBED_ASSERT(total_entries >= 0);
   CUEMBED_ASSERT(o.pieces == 1 && (o.piece_rows == 0 || o.piece_rows == total_entries));   // one piece: the whole array
   o.piece_rows = total_entries;
   CheckCountSource(o);
-  CUEMBED_ASSERT(!o.stochastic_rounding && "a grouped step rounds to nearest");
+  CUEMBED_ASSERT(o.stochastic_rounding == (seeds_device != nullptr) &&
+                 "stochastic rounding on a grouped step takes one seed per table, and seeds go with stochastic rounding");
   CUEMBED_ASSERT(num_tables >= 1 && num_tables <= kGroupedMaxTables);
   CUEMBED_ASSERT(tables_host != nullptr && tables_device != nullptr && row_base_device != nullptr);
   if (total_entries == 0 || o.num_rows == 0) return false;
@@ -82,9 +93,14 @@ inline const float* GroupStateBits(const float* const* state_host, const int num
  * @param total_entries    the entries `ids` and `rows` have room for
  * @param options          rule, lr, eps and ONE count source (num_rows, counts -- one word --, or last_id);
  *                         piece_rows may stay 0 (it is total_entries), pieces must be 1; a count below zero or above
- *                         total_entries applies nothing; stochastic_rounding aborts
+ *                         total_entries applies nothing; stochastic_rounding (16-bit tables) requires seeds_device
+ *                         and reads rounding_step / rounding_step_device, not rounding_seed
+ * @param seeds_device     [num_tables] 64-bit seeds in DEVICE memory, one per table, with options.stochastic_rounding;
+ *                         nullptr without it
+ *
+ * kRoundings: which roundings the instantiation carries kernels for (the C ABI splits them over two units).
  */
-template <typename ElemT, typename IndexT>
+template <typename ElemT, typename IndexT, UpdateRoundings kRoundings = UpdateRoundings::kBoth>
 void SparseRowUpdateGrouped(const ElemT* const* tables_host,
                             ElemT* const* tables_device,
                             const float* const* state_host,
@@ -96,7 +112,8 @@ void SparseRowUpdateGrouped(const ElemT* const* tables_host,
                             const ElemT* rows,
                             const int64_t total_entries,
                             const SparseUpdateOptions& options,
-                            const hipStream_t stream = 0) {
+                            const hipStream_t stream = 0,
+                            const uint64_t* seeds_device = nullptr) {
   static_assert(std::is_same<ElemT, float>::value || std::is_same<ElemT, __half>::value ||
                     std::is_same<ElemT, __hip_bfloat16>::value,
                 "SparseRowUpdateGrouped: tables must be float, __half or __hip_bfloat16");
@@ -105,8 +122,10 @@ void SparseRowUpdateGrouped(const ElemT* const* tables_host,
   using DevT = detail::DeviceElemT<ElemT>;
   SparseUpdateOptions o = options;
   const bool work = detail::CheckGroupedStep(o, tables_host, tables_device, num_tables, row_base_device, ids, rows,
-                                             total_entries);
+                                             total_entries, seeds_device);
   CUEMBED_ASSERT((o.rule == UpdateRule::kSgd) == (state_device == nullptr));
+  CUEMBED_ASSERT(!o.stochastic_rounding || (detail::kCanRoundStochastically<ElemT, kRoundings>));
+  CUEMBED_ASSERT(o.stochastic_rounding || kRoundings != UpdateRoundings::kStochasticOnly);
   if (!work) return;
   const void* table_bits = detail::GroupAlignmentBits(reinterpret_cast<const void* const*>(tables_host), num_tables);
   const bool per_element = o.rule == UpdateRule::kAdagrad;
@@ -116,17 +135,28 @@ void SparseRowUpdateGrouped(const ElemT* const* tables_host,
   const detail::GroupedTables<true> grouped = {reinterpret_cast<const void* const*>(tables_device),
                                                const_cast<const float* const*>(state_device), nullptr, row_base_device,
                                                num_tables};
-  const size_t lds = sizeof(int64_t) * detail::GroupedLdsWords(num_tables, o.rule == UpdateRule::kSgd ? 0 : 1);
+  const size_t lds = sizeof(int64_t) * detail::GroupedLdsWords(num_tables, o.rule == UpdateRule::kSgd ? 0 : 1,
+                                                              o.stochastic_rounding);
   const DevT* g = reinterpret_cast<const DevT*>(rows);
-  detail::DispatchUpdate<DevT, UpdateRoundings::kNearestOnly>(
-      bytes, embed_width, o, [&](auto, auto n, auto chunks, const detail::UpdateShape& s) {
+  detail::DispatchUpdate<DevT, kRoundings>(
+      bytes, embed_width, o, [&](auto stochastic, auto n, auto chunks, const detail::UpdateShape& s) {
         const auto with_rule = [&](auto rule) {
           constexpr int kChunks = decltype(chunks)::value;
-          detail::SparseRowUpdateGroupedKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, kChunks,
-                                               kChunks == 1 ? detail::kGroupedEntriesInFlight : 1>
-              <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), lds, stream>>>(
-                  ids, g, grouped, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr,
-                  o.lr_device, o.eps);
+          if constexpr (decltype(stochastic)::value) {
+            const detail::GroupedSeededTables seeded = {grouped, seeds_device};
+            detail::SparseRowUpdateGroupedStochasticKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value,
+                                                           kChunks,
+                                                           kChunks == 1 ? detail::kGroupedStochasticEntriesInFlight : 1>
+                <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), lds, stream>>>(
+                    ids, g, seeded, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr,
+                    o.lr_device, o.eps, detail::RoundingOf<true>(o));
+          } else {
+            detail::SparseRowUpdateGroupedKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, kChunks,
+                                                 kChunks == 1 ? detail::kGroupedEntriesInFlight : 1>
+                <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), lds, stream>>>(
+                    ids, g, grouped, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr,
+                    o.lr_device, o.eps);
+          }
         };
         switch (o.rule) {
           case UpdateRule::kSgd: return with_rule(std::integral_constant<UpdateRule, UpdateRule::kSgd>());
@@ -147,9 +177,10 @@ void SparseRowUpdateGrouped(const ElemT* const* tables_host,
  *                                             HOST memory (read here, for the access width) and in DEVICE memory
  * @param exp_avg_sq_host / exp_avg_sq_device  the second moments: fp32 [rows_t, embed_width] (kAdam; both copies
  *                                             required) or fp32 [rows_t] (kRowwiseAdam; the host copy is not read)
- * Everything else as SparseRowUpdateGrouped; the hyper-parameters are checked as in SparseRowAdam.
+ * Everything else, seeds_device and kRoundings included, as SparseRowUpdateGrouped; the hyper-parameters are checked as in
+ * SparseRowAdam.
  */
-template <typename ElemT, typename IndexT>
+template <typename ElemT, typename IndexT, UpdateRoundings kRoundings = UpdateRoundings::kBoth>
 void SparseRowAdamGrouped(const ElemT* const* tables_host,
                           ElemT* const* tables_device,
                           const float* const* exp_avg_host,
@@ -163,7 +194,8 @@ void SparseRowAdamGrouped(const ElemT* const* tables_host,
                           const ElemT* rows,
                           const int64_t total_entries,
                           const SparseAdamOptions& options,
-                          const hipStream_t stream = 0) {
+                          const hipStream_t stream = 0,
+                          const uint64_t* seeds_device = nullptr) {
   static_assert(std::is_same<ElemT, float>::value || std::is_same<ElemT, __half>::value ||
                     std::is_same<ElemT, __hip_bfloat16>::value,
                 "SparseRowAdamGrouped: tables must be float, __half or __hip_bfloat16");
@@ -172,7 +204,9 @@ void SparseRowAdamGrouped(const ElemT* const* tables_host,
   using DevT = detail::DeviceElemT<ElemT>;
   SparseAdamOptions o = options;
   const bool work = detail::CheckGroupedStep(o, tables_host, tables_device, num_tables, row_base_device, ids, rows,
-                                             total_entries);
+                                             total_entries, seeds_device);
+  CUEMBED_ASSERT(!o.stochastic_rounding || (detail::kCanRoundStochastically<ElemT, kRoundings>));
+  CUEMBED_ASSERT(o.stochastic_rounding || kRoundings != UpdateRoundings::kStochasticOnly);
   CUEMBED_ASSERT(o.beta1 >= 0.f && o.beta1 < 1.f && o.beta2 >= 0.f && o.beta2 < 1.f);
   CUEMBED_ASSERT(o.eps >= 0.f && o.weight_decay >= 0.f);
   CUEMBED_ASSERT(exp_avg_device != nullptr && exp_avg_sq_device != nullptr);
@@ -187,17 +221,26 @@ void SparseRowAdamGrouped(const ElemT* const* tables_host,
                                                const_cast<const float* const*>(exp_avg_device),
                                                const_cast<const float* const*>(exp_avg_sq_device), row_base_device,
                                                num_tables};
-  const size_t lds = sizeof(int64_t) * detail::GroupedLdsWords(num_tables, 2);
+  const size_t lds = sizeof(int64_t) * detail::GroupedLdsWords(num_tables, 2, o.stochastic_rounding);
   const DevT* g = reinterpret_cast<const DevT*>(rows);
-  detail::DispatchUpdate<DevT, UpdateRoundings::kNearestOnly>(
-      bytes, embed_width, o, [&](auto, auto n, auto chunks, const detail::UpdateShape& s) {
+  detail::DispatchUpdate<DevT, kRoundings>(
+      bytes, embed_width, o, [&](auto stochastic, auto n, auto chunks, const detail::UpdateShape& s) {
         const auto with_rule = [&](auto rule) {
           constexpr int kChunks = decltype(chunks)::value;
-          detail::SparseRowAdamGroupedKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, kChunks,
-                                             kChunks == 1 ? detail::kGroupedEntriesInFlight : 1>
-              <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), lds, stream>>>(
-                  ids, g, grouped, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr,
-                  o.lr_device, o.bias_factor, o.bias_factor_device, h);
+          if constexpr (decltype(stochastic)::value) {
+            const detail::GroupedSeededTables seeded = {grouped, seeds_device};
+            detail::SparseRowAdamGroupedStochasticKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, kChunks,
+                                                         kChunks == 1 ? detail::kGroupedStochasticEntriesInFlight : 1>
+                <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), lds, stream>>>(
+                    ids, g, seeded, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr,
+                    o.lr_device, o.bias_factor, o.bias_factor_device, h, detail::RoundingOf<true>(o));
+          } else {
+            detail::SparseRowAdamGroupedKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, kChunks,
+                                               kChunks == 1 ? detail::kGroupedEntriesInFlight : 1>
+                <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), lds, stream>>>(
+                    ids, g, grouped, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr,
+                    o.lr_device, o.bias_factor, o.bias_factor_device, h);
+          }
         };
         if (o.rule == AdamRule::kAdam) with_rule(std::integral_constant<AdamRule, AdamRule::kAdam>());
         else with_rule(std::integral_constant<AdamRule, AdamRule::kRowwiseAdam>());

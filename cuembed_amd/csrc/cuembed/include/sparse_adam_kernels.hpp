@@ -220,6 +220,30 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
 }
 
 /**
+ * @brief The grouped Adam step with stochastic rounding (16-bit tables): as SparseRowAdamGroupedKernel, and the one
+ * rounding of entry k draws the bits of (grouped.seeds[t], step, ids[k] - row_base[t], column), t the entry's table:
+ * those of SparseRowAdamKernel<.., kStochastic> on table t alone with seed seeds[t].  rounding.seed is not read.
+ * GroupedLdsWords(num_tables, 2, true) * 8 bytes of dynamic LDS.
+ */
+template <typename ElemT, typename IndexT, int N, AdamRule kRule, int kChunks, int kEntriesInFlight>
+__global__ void __launch_bounds__(kUpdateBlockThreads)
+    SparseRowAdamGroupedStochasticKernel(const IndexT* __restrict__ ids, const ElemT* __restrict__ rows,
+                                         const GroupedSeededTables grouped, const int width,
+                                         const int lanes_per_row, const int group, const int64_t piece_rows,
+                                         const int pieces, const UpdateCounts counts, const float lr_value,
+                                         const float* __restrict__ lr_word, const float bias_value,
+                                         const float* __restrict__ bias_word, const AdamScalars h,
+                                         const UpdateRounding<true> rounding) {
+  static_assert(sizeof(ElemT) == 2, "stochastic rounding is for the 16-bit table types");
+  const float lr = lr_word != nullptr ? *lr_word : lr_value;
+  const float c = bias_word != nullptr ? *bias_word : bias_value;
+  const AdamStepRule<kRule> rule{{Arith<float>::mul(lr, c), Arith<float>::mul(lr, h.weight_decay), h.weight_decay != 0.f}, h};
+  WalkNamedRows<ElemT, IndexT, N, kChunks, kEntriesInFlight, true, false, false, false, true>(
+      ids, rows, nullptr, nullptr, nullptr, width, lanes_per_row, group, piece_rows, pieces, counts, rounding, rule,
+      nullptr, nullptr, nullptr, grouped);
+}
+
+/**
  * @brief The bias-factor clock: one thread advances (t, beta1^t, beta2^t) in fp64 and writes
  * c = sqrt(1 - beta2^t) / (1 - beta1^t), computed in fp64 and rounded once, to the fp32 word the update kernel reads.
  * Launch <<<1, 1>>>.  The running products carry a relative error of about t * 2^-53.  (A template so that the header

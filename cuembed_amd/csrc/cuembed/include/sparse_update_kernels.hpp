@@ -27,7 +27,7 @@
 //     carries (0 / 1 / 2), whether the row has a state word of its own, and the arithmetic of a row and of a slice.
 //   * The tables may be a GROUP of separate tensors (kGrouped; host API: grouped_sparse_update.hpp): the ids are then
 //     global rows of the tables laid end to end and the walk finds each entry's table itself, from row_base and the base
-//     pointers staged in LDS.
+//     pointers staged in LDS.  A grouped stochastic walk rounds table t with a seed of its own, seeds[t], staged there too.
 #ifndef CUEMBED_INCLUDE_SPARSE_UPDATE_KERNELS_HPP_
 #define CUEMBED_INCLUDE_SPARSE_UPDATE_KERNELS_HPP_
 
@@ -265,26 +265,47 @@ struct GroupedTables<true> {
   const int64_t* row_base;       //!< [num_tables + 1] in device memory, ascending, row_base[0] = 0
   int num_tables;
 };
+//! The same for a grouped STOCHASTIC walk, with the tables' rounding seeds: a type of its own, so that the kernel
+//! arguments of the round-to-nearest kernels keep their layout.
+struct GroupedSeededTables : GroupedTables<true> {
+  const uint64_t* seeds;         //!< [num_tables] in device memory: table t rounds with the bits of (seeds[t], step, row, column)
+};
+//! The argument of a walk: nothing, the group, or (kSeeded) the group with its seeds.
+template <bool kGrouped, bool kSeeded>
+using GroupedTablesOf = std::conditional_t<kGrouped && kSeeded, GroupedSeededTables, GroupedTables<kGrouped>>;
 
 //! Dynamic LDS of a grouped walk, in 8-byte words: row_base[T + 1], then the T table bases, then the T bases of each
-//! state tensor the rule has.
-constexpr int GroupedLdsWords(const int num_tables, const int state_tensors) {
-  return num_tables + 1 + num_tables * (1 + state_tensors);
+//! state tensor the rule has, then (a stochastic walk) the T seeds.
+constexpr int GroupedLdsWords(const int num_tables, const int state_tensors, const bool stochastic = false) {
+  return num_tables + 1 + num_tables * (1 + state_tensors + (stochastic ? 1 : 0));
 }
-//! The most tables a grouped step takes: 32 KiB of LDS with two state tensors.
+//! The most tables a grouped step takes: 32 KiB of LDS with two state tensors, 40 KiB with the seeds of a stochastic
+//! step -- inside the 64 KiB a launch gets without asking.
 constexpr int kGroupedMaxTables = 1023;
+
+//! The rounding seed of one entry's table: kept only by a grouped stochastic walk.
+template <bool kSeeded>
+struct EntrySeed {};
+template <>
+struct EntrySeed<true> {
+  uint64_t seed;
+};
 
 //! Where one entry's weights and state live.  Without kGrouped: in the walk's own table / state0 / state1, nothing is
 //! kept and every accessor hands its argument back.  With kGrouped: in the tensors of the table that owns the entry's
-//! global row, found by Resolve; the accessors ignore their argument.
-template <typename ElemT, bool kGrouped, bool kUsesState0, bool kUsesState1>
+//! global row, found by Resolve; the accessors ignore their argument.  kSeeded (with kGrouped only): the group's seeds
+//! are staged behind the pointers and Resolve keeps seeds[t] next to them; without it nothing of the seeds is compiled in.
+template <typename ElemT, bool kGrouped, bool kUsesState0, bool kUsesState1, bool kSeeded = false>
 struct EntryPlace {
+  static_assert(!kSeeded, "only a grouped walk has a seed per table");
   __device__ __forceinline__ ElemT* Table(ElemT* table) const { return table; }
   __device__ __forceinline__ float* State0(float* state0) const { return state0; }
   __device__ __forceinline__ float* State1(float* state1) const { return state1; }
 };
-template <typename ElemT, bool kUsesState0, bool kUsesState1>
-struct EntryPlace<ElemT, true, kUsesState0, kUsesState1> {
+template <typename ElemT, bool kUsesState0, bool kUsesState1, bool kSeeded>
+struct EntryPlace<ElemT, true, kUsesState0, kUsesState1, kSeeded> : EntrySeed<kSeeded> {
+  //! Where the seeds begin in the staged words, in units of T (after the + 1 of row_base).
+  static constexpr int kSeedPlane = 2 + (kUsesState0 ? 1 : 0) + (kUsesState1 ? 1 : 0);
   GlobalRowPtr<ElemT> table;
   GlobalRowPtr<float> state0, state1;
   __device__ __forceinline__ ElemT* Table(ElemT*) const { return (ElemT*)table; }
@@ -293,7 +314,7 @@ struct EntryPlace<ElemT, true, kUsesState0, kUsesState1> {
 
   //! The group's words from device memory into LDS (GroupedLdsWords), by the whole workgroup, with the barrier.  Every
   //! thread of the workgroup must call it.
-  static __device__ __forceinline__ void Stage(int64_t* words, const GroupedTables<true>& g) {
+  static __device__ __forceinline__ void Stage(int64_t* words, const GroupedTablesOf<true, kSeeded>& g) {
     const int T = g.num_tables;
     for (int i = threadIdx.x; i <= T; i += kUpdateBlockThreads) words[i] = g.row_base[i];
     for (int i = threadIdx.x; i < T; i += kUpdateBlockThreads) {
@@ -301,6 +322,7 @@ struct EntryPlace<ElemT, true, kUsesState0, kUsesState1> {
       if constexpr (kUsesState0) words[2 * T + 1 + i] = static_cast<int64_t>(reinterpret_cast<uintptr_t>(g.state0[i]));
       if constexpr (kUsesState1)
         words[(kUsesState0 ? 3 : 2) * T + 1 + i] = static_cast<int64_t>(reinterpret_cast<uintptr_t>(g.state1[i]));
+      if constexpr (kSeeded) words[kSeedPlane * T + 1 + i] = static_cast<int64_t>(g.seeds[i]);
     }
     __syncthreads();
   }
@@ -322,6 +344,7 @@ struct EntryPlace<ElemT, true, kUsesState0, kUsesState1> {
     if constexpr (kUsesState1)
       state1 = (GlobalRowPtr<float>)reinterpret_cast<float*>(
           static_cast<uintptr_t>(words[(kUsesState0 ? 3 : 2) * T + 1 + t]));
+    if constexpr (kSeeded) this->seed = static_cast<uint64_t>(words[kSeedPlane * T + 1 + t]);
   }
 };
 
@@ -345,7 +368,7 @@ struct EntryPlace<ElemT, true, kUsesState0, kUsesState1> {
  * one, so the walk carries the table rows next to the placed ids.  A placed stochastic walk must therefore be named.
  * The names are loaded with the ids, before the row data, and the Philox calls stay where they are (kChunks >= 1: while
  * the row loads are in flight).  Again a separate instantiation: without kNamed nothing of row_names is compiled in.
- * kGrouped (never with kPlaced, round to nearest only): the tables are `grouped.num_tables` SEPARATE tensors and ids[k] is
+ * kGrouped (never with kPlaced or kNamed): the tables are `grouped.num_tables` SEPARATE tensors and ids[k] is
  * a global row of the tables laid end to end (grouped_backward.hpp's keys).  `table`, `state0` and `state1` are not read;
  * entry k's table t is the one with row_base[t] <= ids[k] < row_base[t + 1], its weights are at tables[t] + (ids[k] -
  * row_base[t]) * width and each of its state planes at states[t] + (ids[k] - row_base[t]) * (width, or 1 for the row
@@ -355,6 +378,10 @@ struct EntryPlace<ElemT, true, kUsesState0, kUsesState1> {
  * search through global memory would (loads return in order).  The pointers stay in a global-address-space type, so
  * row traffic is global_load / global_store as in every other walk.  Again a separate instantiation: without kGrouped
  * every accessor of EntryPlace hands its argument back and nothing of `grouped` is compiled in.
+ * kGrouped with kStochastic: the rounding bits of entry k are those of (grouped.seeds[t], step, ids[k] - row_base[t],
+ * column) -- the bits of a single-table stochastic step on table t with seed seeds[t]; rounding.seed is not read.  The
+ * seeds are staged in LDS behind the pointers and Resolve hands an entry's seed back with its pointers, so the order of a
+ * kChunks >= 1 iteration stays: gradient loads, Resolve, table / state loads, then Philox while they are in flight.
  * kEntries entries are in flight per group: 2 when a lane holds one slice per entry (kChunks == 1), else 1.  With the
  * two moment packs of an Adam slice next to its weights and gradient, two entries take 32 (fp32) to 48 (16-bit)
  * registers of row data per lane: every kChunks == 1 instantiation stays free of scratch and at or above 4 waves per
@@ -370,9 +397,10 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
                                               const RuleT& rule, const int64_t* __restrict__ state_ids = nullptr,
                                               const int64_t* __restrict__ state1_ids = nullptr,
                                               const int64_t* __restrict__ row_names = nullptr,
-                                              const GroupedTables<kGrouped>& grouped = GroupedTables<kGrouped>()) {
+                                              const GroupedTablesOf<kGrouped, kStochastic>& grouped =
+                                                  GroupedTablesOf<kGrouped, kStochastic>()) {
   static_assert(!kStochastic || sizeof(ElemT) == 2, "stochastic rounding is for the 16-bit table types");
-  static_assert(!kGrouped || (!kPlaced && !kStochastic), "a grouped walk is neither placed nor stochastic");
+  static_assert(!kGrouped || (!kPlaced && !kNamed), "a grouped walk is neither placed nor named");
   static_assert(!kNamed || kStochastic, "row names name rounding bits: only a stochastic walk carries them");
   static_assert(!(kPlaced && kStochastic) || kNamed, "a placed, stochastic walk must be named");
   static_assert(!kPlacedTwice || (kPlaced && RuleT::kStates >= 1), "a second placed id is for a rule with a state1");
@@ -383,7 +411,8 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
   constexpr int kHeld = kStates > 0 ? kStates : 1;
   constexpr int kSlices = kChunks == 0 ? 1 : kChunks;
   // where an entry's weights and state live: the walk's own tensors, or (kGrouped) those of the entry's table
-  using PlaceT = EntryPlace<ElemT, kGrouped, kStates >= 1 || kRowState, kStates == 2 || (kStates == 1 && kRowState)>;
+  using PlaceT = EntryPlace<ElemT, kGrouped, kStates >= 1 || kRowState, kStates == 2 || (kStates == 1 && kRowState),
+                            kGrouped && kStochastic>;
   // the tensor of the row words (only read if kRowState)
   const auto row_words_at = [&](const PlaceT& at) { return kStates == 0 ? at.State0(state0) : at.State1(state1); };
   // the row of an entry's row word: it lives in state0 and goes by state0's row, or in state1 and goes by state1's
@@ -393,9 +422,14 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
   };
   uint64_t seed = 0, round_step = 0;
   if constexpr (kStochastic) {
-    seed = rounding.seed;
+    if constexpr (!kGrouped) seed = rounding.seed;
     round_step = rounding.step_word != nullptr ? static_cast<uint64_t>(*rounding.step_word) : rounding.step;
   }
+  // the seed of an entry's rounding bits: the walk's, or (kGrouped) that of the entry's table
+  const auto seed_at = [&](const PlaceT& at) {
+    if constexpr (kGrouped && kStochastic) return at.seed;
+    else return seed;
+  };
   const int64_t* group_words = nullptr;   // (kGrouped: row_base and the base pointers, staged in LDS)
   int num_tables = 0;
   if constexpr (kGrouped) {
@@ -462,7 +496,7 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
           LoadStates<kStates>(s, at.State0(state0), at.State1(state1), RowElems(StateRow<kPlaced>(r[0], placed[0]), width) + c * N,
                               RowElems(State1Row<kPlaced, kPlacedTwice>(r[0], placed[0], placed1[0]), width) + c * N);
           RoundT round;
-          if constexpr (kStochastic) round = RoundT(seed, round_step, RoundingRow<kNamed>(r[0], named[0]), c * N);
+          if constexpr (kStochastic) round = RoundT(seed_at(at), round_step, RoundingRow<kNamed>(r[0], named[0]), c * N);
           StorePack<ElemT, N>(w_row + c * N, rule.Slice(w, g, s, row, round));
           StoreStates<kStates>(s, at.State0(state0), at.State1(state1), RowElems(StateRow<kPlaced>(r[0], placed[0]), width) + c * N,
                                RowElems(State1Row<kPlaced, kPlacedTwice>(r[0], placed[0], placed1[0]), width) + c * N);
@@ -513,7 +547,8 @@ __device__ __forceinline__ void WalkNamedRows(const IndexT* __restrict__ ids, co
 #pragma unroll
             for (int c = 0; c < kSlices; ++c)
               if (has[u][c])
-                round[u][c] = RoundT(seed, round_step, RoundingRow<kNamed>(r[u], named[u]), (lane + c * group) * N);
+                round[u][c] = RoundT(seed_at(at[u]), round_step, RoundingRow<kNamed>(r[u], named[u]),
+                                     (lane + c * group) * N);
         }
 #pragma unroll
         for (int u = 0; u < kEntries; ++u) {
@@ -617,6 +652,27 @@ __global__ void __launch_bounds__(kUpdateBlockThreads)
   WalkNamedRows<ElemT, IndexT, N, kChunks, kEntriesInFlight, false, false, false, false, true>(
       ids, rows, nullptr, nullptr, nullptr, width, lanes_per_row, group, piece_rows, pieces, counts,
       UpdateRounding<false>(), rule, nullptr, nullptr, nullptr, grouped);
+}
+
+/**
+ * @brief The grouped step with stochastic rounding (16-bit tables): as SparseRowUpdateGroupedKernel, and the one rounding
+ * of entry k draws the bits of (grouped.seeds[t], step, ids[k] - row_base[t], column), t the entry's table: those of
+ * SparseRowUpdateKernel<.., kStochastic> on table t alone with seed seeds[t].  rounding.step / step_word are read,
+ * rounding.seed is not.  GroupedLdsWords(num_tables, the rule's state tensors, true) * 8 bytes of dynamic LDS.
+ */
+template <typename ElemT, typename IndexT, int N, UpdateRule kRule, int kChunks, int kEntriesInFlight>
+__global__ void __launch_bounds__(kUpdateBlockThreads)
+    SparseRowUpdateGroupedStochasticKernel(const IndexT* __restrict__ ids, const ElemT* __restrict__ rows,
+                                           const GroupedSeededTables grouped, const int width,
+                                           const int lanes_per_row, const int group, const int64_t piece_rows,
+                                           const int pieces, const UpdateCounts counts, const float lr_value,
+                                           const float* __restrict__ lr_word, const float eps,
+                                           const UpdateRounding<true> rounding) {
+  static_assert(sizeof(ElemT) == 2, "stochastic rounding is for the 16-bit table types");
+  const UpdateStep<kRule> rule{lr_word != nullptr ? *lr_word : lr_value, eps};
+  WalkNamedRows<ElemT, IndexT, N, kChunks, kEntriesInFlight, true, false, false, false, true>(
+      ids, rows, nullptr, nullptr, nullptr, width, lanes_per_row, group, piece_rows, pieces, counts, rounding, rule,
+      nullptr, nullptr, nullptr, grouped);
 }
 
 }  // namespace detail

@@ -900,7 +900,10 @@ void cuembed_sparse_row_adam_op(at::Tensor table, at::Tensor exp_avg, at::Tensor
 // gradient of the grouped backward), rows their gradient rows.  Each state list holds one float32 tensor per table and
 // comes with the int64 device tensor of its base pointers, built once by the caller.  Valid entries, at most one of:
 // count >= 0 (host-known), count_word (one int32 / int64 device word), last_id (one word of ids' dtype, count = last_id +
-// 1); none: every entry.  Round to nearest: stochastic_rounding = True is refused.  Nothing is read back.
+// 1); none: every entry.  stochastic_rounding = True (float16 / bfloat16 tables) takes `seeds`, the int64 device tensor
+// [num_tables] that holds the bits of ONE unsigned 64-bit SEED PER TABLE, and the step, `step` or the one-element int64
+// device tensor step_device: the bits of entry k are those of (seeds[t], step, row inside table t, column).  There are
+// no default seeds: stochastic_rounding without seeds is refused, and so are seeds without it.  Nothing is read back.
 
 struct GroupedStep {
   std::vector<const void*> table_host;
@@ -909,6 +912,8 @@ struct GroupedStep {
   const void* count_word = nullptr;
   const void* last_id = nullptr;
   const float* lr_word = nullptr;
+  const uint64_t* seeds = nullptr;          // one per table, on the device: a stochastic step
+  const int64_t* step_word = nullptr;
 };
 
 // One state list of a grouped step: `per_element` [rows_t, width] tensors, else [rows_t]; returns the host pointers.
@@ -935,12 +940,33 @@ std::vector<const void*> CheckGroupedStates(const at::TensorList tables, const a
 GroupedStep CheckGroupedStep(const at::TensorList tables, const at::Tensor& table_ptrs, const at::Tensor& row_base,
                              const at::Tensor& ids, const at::Tensor& rows, const c10::optional<at::Tensor>& lr_device,
                              const int64_t count, const c10::optional<at::Tensor>& count_word,
-                             const c10::optional<at::Tensor>& last_id, const bool stochastic_rounding) {
+                             const c10::optional<at::Tensor>& last_id, const bool stochastic_rounding,
+                             const c10::optional<at::Tensor>& seeds, const int64_t step,
+                             const c10::optional<at::Tensor>& step_device) {
   GroupedStep c;
-  TORCH_CHECK(!stochastic_rounding, "cuembed_pyt: stochastic rounding on a grouped step does not exist: round to nearest");
+  const bool has_seeds = seeds.has_value() && seeds->defined();
+  TORCH_CHECK(!stochastic_rounding || has_seeds,
+              "cuembed_pyt: stochastic rounding on a grouped step takes one seed per table: pass seeds=[...]");
+  TORCH_CHECK(stochastic_rounding || !has_seeds, "cuembed_pyt: seeds go with stochastic_rounding = True");
   const int64_t num_tables = static_cast<int64_t>(tables.size());
   TORCH_CHECK(num_tables >= 1 && num_tables <= 1023, "cuembed_pyt: a grouped step takes 1 to 1023 tables");
   c.elem = ElemCode(tables[0], "tables");
+  if (stochastic_rounding) {
+    TORCH_CHECK(c.elem != CUEMBED_F32,
+                "cuembed_pyt: stochastic_rounding is for float16 / bfloat16 tables: a float32 table is not rounded");
+    CheckGpu(*seeds, "seeds");
+    TORCH_CHECK(seeds->scalar_type() == at::kLong && seeds->is_contiguous() && seeds->dim() == 1 &&
+                    seeds->numel() == num_tables && seeds->device() == tables[0].device(),
+                "cuembed_pyt: seeds must be the contiguous int64 tensor [num_tables] of the tables' seeds on their device");
+    c.seeds = static_cast<const uint64_t*>(seeds->data_ptr());
+    if (step_device.has_value() && step_device->defined()) {
+      CheckGpu(*step_device, "step_device");
+      TORCH_CHECK(step_device->scalar_type() == at::kLong && step_device->numel() == 1 &&
+                      step_device->device() == tables[0].device(),
+                  "cuembed_pyt: step_device must be one int64 word on the tables' device");
+      c.step_word = static_cast<const int64_t*>(step_device->data_ptr());
+    }
+  }
   for (const at::Tensor& t : tables) {
     CheckGpu(t, "tables");
     TORCH_CHECK(t.dim() == 2 && t.is_contiguous() && t.scalar_type() == tables[0].scalar_type() &&
@@ -1009,14 +1035,17 @@ void cuembed_sparse_row_update_grouped_op(const at::TensorList tables, const at:
                                           const std::string& rule, const double lr, const double eps,
                                           const c10::optional<at::Tensor>& lr_device, const int64_t count,
                                           const c10::optional<at::Tensor>& count_word,
-                                          const c10::optional<at::Tensor>& last_id, const bool stochastic_rounding) {
+                                          const c10::optional<at::Tensor>& last_id, const bool stochastic_rounding,
+                                          const c10::optional<at::Tensor>& seeds, const int64_t step,
+                                          const c10::optional<at::Tensor>& step_device) {
   const int code = rule == "sgd" ? CUEMBED_UPDATE_SGD
                    : rule == "adagrad" ? CUEMBED_UPDATE_ADAGRAD
                    : rule == "rowwise_adagrad" ? CUEMBED_UPDATE_ROWWISE_ADAGRAD : -1;
   TORCH_CHECK(code >= 0, "cuembed_pyt: rule must be 'sgd', 'adagrad' or 'rowwise_adagrad'");
   TORCH_CHECK(!tables.empty(), "cuembed_pyt: a group needs at least one table");
   const GroupedStep c =
-      CheckGroupedStep(tables, table_ptrs, row_base, ids, rows, lr_device, count, count_word, last_id, stochastic_rounding);
+      CheckGroupedStep(tables, table_ptrs, row_base, ids, rows, lr_device, count, count_word, last_id, stochastic_rounding,
+                       seeds, step, step_device);
   std::vector<const void*> state_host;
   if (code == CUEMBED_UPDATE_SGD) {
     TORCH_CHECK(states.empty(), "cuembed_pyt: rule 'sgd' takes no states");
@@ -1029,6 +1058,16 @@ void cuembed_sparse_row_update_grouped_op(const at::TensorList tables, const at:
   if (ids.numel() == 0) return;
   const at::DeviceGuard guard(tables[0].device());
   const bool stateful = code != CUEMBED_UPDATE_SGD;
+  if (stochastic_rounding) {
+    ::cuembed_sparse_row_update_grouped_stochastic(
+        c.table_host.data(), static_cast<const void* const*>(table_ptrs.data_ptr()),
+        stateful ? state_host.data() : nullptr,
+        stateful ? static_cast<const void* const*>(state_ptrs->data_ptr()) : nullptr, static_cast<int>(tables.size()),
+        c.elem, static_cast<int>(rows.size(1)), static_cast<const int64_t*>(row_base.data_ptr()), code, Ptr(ids), c.idx,
+        Ptr(rows), ids.numel(), c.num_rows, c.count_word, c.words64, c.last_id, static_cast<float>(lr), c.lr_word,
+        static_cast<float>(eps), c.seeds, static_cast<uint64_t>(step), c.step_word, CurrentStream(rows));
+    return;
+  }
   ::cuembed_sparse_row_update_grouped(
       c.table_host.data(), static_cast<const void* const*>(table_ptrs.data_ptr()), stateful ? state_host.data() : nullptr,
       stateful ? static_cast<const void* const*>(state_ptrs->data_ptr()) : nullptr, static_cast<int>(tables.size()),
@@ -1046,10 +1085,13 @@ void cuembed_sparse_row_adam_grouped_op(const at::TensorList tables, const at::T
                                         const c10::optional<at::Tensor>& lr_device,
                                         const c10::optional<at::Tensor>& bias_factor_device, const int64_t count,
                                         const c10::optional<at::Tensor>& count_word,
-                                        const c10::optional<at::Tensor>& last_id, const bool stochastic_rounding) {
+                                        const c10::optional<at::Tensor>& last_id, const bool stochastic_rounding,
+                                        const c10::optional<at::Tensor>& seeds, const int64_t step,
+                                        const c10::optional<at::Tensor>& step_device) {
   TORCH_CHECK(!tables.empty(), "cuembed_pyt: a group needs at least one table");
   const GroupedStep c =
-      CheckGroupedStep(tables, table_ptrs, row_base, ids, rows, lr_device, count, count_word, last_id, stochastic_rounding);
+      CheckGroupedStep(tables, table_ptrs, row_base, ids, rows, lr_device, count, count_word, last_id, stochastic_rounding,
+                       seeds, step, step_device);
   const std::vector<const void*> m_host = CheckGroupedStates(tables, exp_avg, exp_avg_ptrs, true, "exp_avg");
   const std::vector<const void*> v_host = CheckGroupedStates(tables, exp_avg_sq, exp_avg_sq_ptrs, !rowwise, "exp_avg_sq");
   std::vector<const std::vector<const void*>*> per_element = {&m_host};
@@ -1067,6 +1109,19 @@ void cuembed_sparse_row_adam_grouped_op(const at::TensorList tables, const at::T
   }
   if (ids.numel() == 0) return;
   const at::DeviceGuard guard(tables[0].device());
+  if (stochastic_rounding) {
+    ::cuembed_sparse_row_adam_grouped_stochastic(
+        c.table_host.data(), static_cast<const void* const*>(table_ptrs.data_ptr()), m_host.data(),
+        static_cast<const void* const*>(exp_avg_ptrs.data_ptr()), v_host.data(),
+        static_cast<const void* const*>(exp_avg_sq_ptrs.data_ptr()), static_cast<int>(tables.size()), c.elem,
+        static_cast<int>(rows.size(1)), static_cast<const int64_t*>(row_base.data_ptr()),
+        rowwise ? CUEMBED_ROWWISE_ADAM : CUEMBED_ADAM, Ptr(ids), c.idx, Ptr(rows), ids.numel(), c.num_rows, c.count_word,
+        c.words64, c.last_id, static_cast<float>(lr), c.lr_word, static_cast<float>(bias_factor), bias_word,
+        static_cast<float>(beta1), static_cast<float>(1.0 - beta1), static_cast<float>(beta2),
+        static_cast<float>(1.0 - beta2), static_cast<float>(eps), static_cast<float>(weight_decay), c.seeds,
+        static_cast<uint64_t>(step), c.step_word, CurrentStream(rows));
+    return;
+  }
   ::cuembed_sparse_row_adam_grouped(
       c.table_host.data(), static_cast<const void* const*>(table_ptrs.data_ptr()), m_host.data(),
       static_cast<const void* const*>(exp_avg_ptrs.data_ptr()), v_host.data(),
@@ -1638,12 +1693,14 @@ TORCH_LIBRARY(cuembed_pyt, m) {
   m.def(
       "cuembed_sparse_row_update_grouped(Tensor(a!)[] tables, Tensor table_ptrs, Tensor(b!)[] states, Tensor? state_ptrs, "
       "Tensor row_base, Tensor ids, Tensor rows, str rule, float lr, float eps, Tensor? lr_device, int count, Tensor? "
-      "count_word, Tensor? last_id, bool stochastic_rounding=False) -> ()");
+      "count_word, Tensor? last_id, bool stochastic_rounding=False, Tensor? seeds=None, int step=0, Tensor? "
+      "step_device=None) -> ()");
   m.def(
       "cuembed_sparse_row_adam_grouped(Tensor(a!)[] tables, Tensor table_ptrs, Tensor(b!)[] exp_avg, Tensor exp_avg_ptrs, "
       "Tensor(c!)[] exp_avg_sq, Tensor exp_avg_sq_ptrs, Tensor row_base, Tensor ids, Tensor rows, bool rowwise, float lr, "
       "float bias_factor, float beta1, float beta2, float eps, float weight_decay, Tensor? lr_device, Tensor? "
-      "bias_factor_device, int count, Tensor? count_word, Tensor? last_id, bool stochastic_rounding=False) -> ()");
+      "bias_factor_device, int count, Tensor? count_word, Tensor? last_id, bool stochastic_rounding=False, Tensor? "
+      "seeds=None, int step=0, Tensor? step_device=None) -> ()");
   // 8-bit row-wise quantized tables (torch's fused layout), inference only
   m.def("quantize_rows(Tensor table) -> Tensor");
   m.def("dequantize_rows(Tensor qtable, Tensor? ids, ScalarType dtype) -> Tensor");

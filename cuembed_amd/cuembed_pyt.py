@@ -79,12 +79,14 @@ def _define_python_ops():
                 " Tensor? step_device=None) -> ()")
     _lib.define("cuembed_sparse_row_update_grouped(Tensor(a!)[] tables, Tensor table_ptrs, Tensor(b!)[] states,"
                 " Tensor? state_ptrs, Tensor row_base, Tensor ids, Tensor rows, str rule, float lr, float eps,"
-                " Tensor? lr_device, int count, Tensor? count_word, Tensor? last_id, bool stochastic_rounding=False) -> ()")
+                " Tensor? lr_device, int count, Tensor? count_word, Tensor? last_id, bool stochastic_rounding=False,"
+                " Tensor? seeds=None, int step=0, Tensor? step_device=None) -> ()")
     _lib.define("cuembed_sparse_row_adam_grouped(Tensor(a!)[] tables, Tensor table_ptrs, Tensor(b!)[] exp_avg,"
                 " Tensor exp_avg_ptrs, Tensor(c!)[] exp_avg_sq, Tensor exp_avg_sq_ptrs, Tensor row_base, Tensor ids,"
                 " Tensor rows, bool rowwise, float lr, float bias_factor, float beta1, float beta2, float eps,"
                 " float weight_decay, Tensor? lr_device, Tensor? bias_factor_device, int count, Tensor? count_word,"
-                " Tensor? last_id, bool stochastic_rounding=False) -> ()")
+                " Tensor? last_id, bool stochastic_rounding=False, Tensor? seeds=None, int step=0,"
+                " Tensor? step_device=None) -> ()")
     _lib.define("quantize_rows(Tensor table) -> Tensor")
     _lib.define("dequantize_rows(Tensor qtable, Tensor? ids, ScalarType dtype) -> Tensor")
     _lib.define("cuemb_embedding_quantized(Tensor qtable, Tensor indices, Tensor? offsets, Tensor? weights, str mode,"
@@ -330,6 +332,17 @@ def _sparse_row_adam_impl(table, exp_avg, exp_avg_sq, ids, rows, rowwise, lr, bi
                          betas=(beta1, beta2), eps=eps, weight_decay=weight_decay, rowwise=rowwise, **kw)
 
 
+def _unsigned(word):
+    """The unsigned 64-bit value whose bits the schema's int carries."""
+    return int(word) & (2 ** 64 - 1)
+
+
+def _signed(word):
+    """An unsigned 64-bit value as the int of a schema (its bits, two's complement)."""
+    word = int(word)
+    return word - 2 ** 64 if word >= 2 ** 63 else word
+
+
 def _grouped_count(count, count_word, last_id):
     _require((count >= 0) + (count_word is not None) + (last_id is not None) <= 1,
              "give at most one of count, count_word and last_id")
@@ -341,22 +354,28 @@ def _grouped_count(count, count_word, last_id):
 
 
 def _sparse_row_update_grouped_impl(tables, table_ptrs, states, state_ptrs, row_base, ids, rows, rule, lr, eps, lr_device,
-                                    count, count_word, last_id, stochastic_rounding=False):
+                                    count, count_word, last_id, stochastic_rounding=False, seeds=None, step=0,
+                                    step_device=None):
     from . import grouped as _g, grouped_backward as _gb
     _gb.sparse_row_update_grouped(_g.TableGroup(tables, table_ptrs=table_ptrs), ids, rows, rule=rule,
                                   lr=lr if lr_device is None else lr_device, states=list(states) or None, eps=eps,
-                                  stochastic_rounding=stochastic_rounding, **_grouped_count(count, count_word, last_id))
+                                  stochastic_rounding=stochastic_rounding, seeds=seeds,
+                                  step=_unsigned(step) if step_device is None else step_device,
+                                  **_grouped_count(count, count_word, last_id))
 
 
 def _sparse_row_adam_grouped_impl(tables, table_ptrs, exp_avg, exp_avg_ptrs, exp_avg_sq, exp_avg_sq_ptrs, row_base, ids,
                                   rows, rowwise, lr, bias_factor, beta1, beta2, eps, weight_decay, lr_device,
-                                  bias_factor_device, count, count_word, last_id, stochastic_rounding=False):
+                                  bias_factor_device, count, count_word, last_id, stochastic_rounding=False, seeds=None,
+                                  step=0, step_device=None):
     from . import grouped as _g, grouped_backward as _gb
     _gb.sparse_row_adam_grouped(_g.TableGroup(tables, table_ptrs=table_ptrs), ids, rows, exp_avg=list(exp_avg),
                                 exp_avg_sq=list(exp_avg_sq), lr=lr if lr_device is None else lr_device,
                                 bias_factor=bias_factor if bias_factor_device is None else bias_factor_device,
                                 betas=(beta1, beta2), eps=eps, weight_decay=weight_decay, rowwise=rowwise,
-                                stochastic_rounding=stochastic_rounding, **_grouped_count(count, count_word, last_id))
+                                stochastic_rounding=stochastic_rounding, seeds=seeds,
+                                step=_unsigned(step) if step_device is None else step_device,
+                                **_grouped_count(count, count_word, last_id))
 
 
 def _quantize_rows_impl(table):
@@ -571,27 +590,43 @@ def _grouped_step_args(group, count, last_id):
     return group, -1 if (count is None or word is not None) else int(count), word
 
 
+def _grouped_rounding_args(group, seeds, step):
+    """(seeds tensor or None, step, step_device) of a grouped op.  Whether the rounding and the seeds go together is the
+    op's to say: only the seeds themselves are validated here, since they have to be put on the device."""
+    from . import grouped_backward as _gb
+    if seeds is not None and not isinstance(seeds, torch.Tensor):
+        seeds = _gb._seeds_tensor(group, _gb._check_seeds(group, True, seeds))
+    if isinstance(step, torch.Tensor):
+        return seeds, 0, step
+    if isinstance(step, bool) or not isinstance(step, int) or not 0 <= step < 2 ** 64:
+        raise ValueError("step must be an int in [0, 2**64) or a one-element int64 device tensor, got %r" % (step,))
+    return seeds, _signed(step), None
+
+
 def cuembed_sparse_row_update_grouped(group, ids, rows, *, rule, lr, states=None, eps=1e-8, count=None, last_id=None,
-                                      stochastic_rounding=False):
+                                      stochastic_rounding=False, seeds=None, step=0):
     """cuembed_amd.sparse_row_update_grouped as the torch op cuembed_pyt::cuembed_sparse_row_update_grouped (in place on the
-    group's tables and on `states`; traces under torch.compile).  Same arguments."""
+    group's tables and on `states`; traces under torch.compile).  Same arguments; the op takes the seeds as the int64
+    device tensor [num_tables] of their bits, which is built once per tuple of seeds and kept on the group."""
     from . import grouped_backward as _gb
     group, host_count, word = _grouped_step_args(group, count, last_id)
+    seeds, step, step_device = _grouped_rounding_args(group, seeds, step)
     lr_device = lr if isinstance(lr, torch.Tensor) else None
     state_ptrs = None if not states else _gb._state_ptrs(group, states)[1]
     torch.ops.cuembed_pyt.cuembed_sparse_row_update_grouped(
         list(group.tables), group.table_ptrs, list(states or ()), state_ptrs, group.row_base_device, ids, rows, rule,
         0.0 if lr_device is not None else float(lr), float(eps), lr_device, host_count, word, last_id,
-        bool(stochastic_rounding))
+        bool(stochastic_rounding), seeds, step, step_device)
 
 
 def cuembed_sparse_row_adam_grouped(group, ids, rows, *, exp_avg, exp_avg_sq, lr, bias_factor=1.0, betas=(0.9, 0.999),
                                     eps=1e-8, weight_decay=0.0, rowwise=False, count=None, last_id=None,
-                                    stochastic_rounding=False):
+                                    stochastic_rounding=False, seeds=None, step=0):
     """cuembed_amd.sparse_row_adam_grouped as the torch op cuembed_pyt::cuembed_sparse_row_adam_grouped (in place on the
     group's tables, `exp_avg` and `exp_avg_sq`; traces under torch.compile).  Same arguments."""
     from . import grouped_backward as _gb
     group, host_count, word = _grouped_step_args(group, count, last_id)
+    seeds, step, step_device = _grouped_rounding_args(group, seeds, step)
     lr_device = lr if isinstance(lr, torch.Tensor) else None
     bias_device = bias_factor if isinstance(bias_factor, torch.Tensor) else None
     beta1, beta2 = betas
@@ -600,7 +635,7 @@ def cuembed_sparse_row_adam_grouped(group, ids, rows, *, exp_avg, exp_avg_sq, lr
         _gb._state_ptrs(group, exp_avg_sq)[1], group.row_base_device, ids, rows, bool(rowwise),
         0.0 if lr_device is not None else float(lr), 1.0 if bias_device is not None else float(bias_factor), float(beta1),
         float(beta2), float(eps), float(weight_decay), lr_device, bias_device, host_count, word, last_id,
-        bool(stochastic_rounding))
+        bool(stochastic_rounding), seeds, step, step_device)
 
 
 def quantize_rows(table):
@@ -1176,14 +1211,14 @@ def _(table, exp_avg, exp_avg_sq, ids, rows, rowwise, lr, bias_factor, beta1, be
 
 @torch.library.register_fake("cuembed_pyt::cuembed_sparse_row_update_grouped")
 def _(tables, table_ptrs, states, state_ptrs, row_base, ids, rows, rule, lr, eps, lr_device=None, count=-1,
-      count_word=None, last_id=None, stochastic_rounding=False):
+      count_word=None, last_id=None, stochastic_rounding=False, seeds=None, step=0, step_device=None):
     return None
 
 
 @torch.library.register_fake("cuembed_pyt::cuembed_sparse_row_adam_grouped")
 def _(tables, table_ptrs, exp_avg, exp_avg_ptrs, exp_avg_sq, exp_avg_sq_ptrs, row_base, ids, rows, rowwise, lr,
       bias_factor, beta1, beta2, eps, weight_decay, lr_device=None, bias_factor_device=None, count=-1, count_word=None,
-      last_id=None, stochastic_rounding=False):
+      last_id=None, stochastic_rounding=False, seeds=None, step=0, step_device=None):
     return None
 
 

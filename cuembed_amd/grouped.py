@@ -84,6 +84,7 @@ class TableGroup:
         self.flat = None                 # the one storage of allocate() / from_flat(); None for separate tensors
         self._row_base_device = None
         self._state_ptr_arrays = {}      # the pointer arrays of per-table optimizer state (grouped_backward._state_ptrs)
+        self._seed_arrays = {}           # the per-table rounding seeds on the device (grouped_backward._seeds_tensor)
 
     @property
     def row_base(self):

@@ -23,6 +23,7 @@ launch by the grouped step, which finds each entry's table on the device -- no c
 
     sparse_row_update_grouped(group, g.ids, g.rows, rule="sgd", lr=lr, last_id=g.last_id)   # or sparse_row_adam_grouped, or
                                                                                             # cuembed_amd.optim.GroupSparseUpdater
+(fp16 / bf16 tables: stochastic_rounding=True, seeds=[one per table], step=...)
 The sort is stable, so inside one table row the lookups keep the order of the single-table pipeline: on exactly
 representable data, and with reference_sums=True on any data, the result has the bits of T single-table calls.  With
 the default arithmetic the segment cuts of the scatter-add move with the position in the combined stream: the same
@@ -386,14 +387,76 @@ def embedding_backward_grouped(group, grad_y, indices, offsets=None, weights=Non
 MAX_GROUPED_STEP_TABLES = 1023   # detail::kGroupedMaxTables: row_base and the base pointers are staged in 32 KiB of LDS
 
 
-def _step_group(group, ids, rows, stochastic_rounding):
-    """What both grouped steps check first, without the GPU: the group, ids and rows.  Returns (group, index code, n)."""
+def _check_seeds(group, stochastic_rounding, seeds):
+    """The rounding of a grouped step, validated without the GPU: None (to nearest) or the tables' seeds, as a tuple of
+    ints (or as the int64 device tensor [num_tables] of their bits, if that is what was passed).
+    There are no default seeds: one seed for the group would give row r of every table the same bits."""
+    if stochastic_rounding and seeds is None:
+        raise ValueError("stochastic rounding on a grouped step takes one seed per table: pass seeds=[...]")
+    if seeds is None:
+        return None
+    if not stochastic_rounding:
+        raise ValueError("seeds go with stochastic_rounding=True: a step that rounds to nearest draws no bits")
+    if isinstance(seeds, torch.Tensor):
+        # the seeds as they live on the device (what the torch op is handed): int64 [num_tables] holding their bits
+        if seeds.dtype != torch.int64 or seeds.dim() != 1 or not seeds.is_contiguous():
+            raise TypeError("seeds as a tensor must be a contiguous int64 tensor [num_tables] that holds the seeds' bits")
+        if seeds.numel() != group.num_tables:
+            raise ValueError("seeds must hold one seed per table: the group has %d tables, got %d"
+                             % (group.num_tables, seeds.numel()))
+        if group.dtype == torch.float32:
+            raise TypeError("stochastic_rounding is for float16 / bfloat16 tables: a float32 table is not rounded")
+        return seeds
+    if not isinstance(seeds, (list, tuple)):
+        raise TypeError("seeds must be a sequence of %d ints, one per table" % group.num_tables)
+    if len(seeds) != group.num_tables:
+        raise ValueError("seeds must hold one seed per table: the group has %d tables, got %d"
+                         % (group.num_tables, len(seeds)))
+    for t, seed in enumerate(seeds):
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise TypeError("seeds[%d] must be an int in [0, 2**64), got %r" % (t, seed))
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seeds[%d] must be an int in [0, 2**64), got %r" % (t, seed))
+    if group.dtype == torch.float32:
+        raise TypeError("stochastic_rounding is for float16 / bfloat16 tables: a float32 table is not rounded")
+    return tuple(seeds)
+
+
+def _seeds_tensor(group, seeds):
+    """The seeds on the device, as the int64 [num_tables] tensor that holds their bits.  Built ONCE per tuple of seeds and
+    kept on the group, next to the state pointer arrays: a step copies nothing, so it can run under capture."""
+    if isinstance(seeds, torch.Tensor):
+        return seeds
+    cache = group._seed_arrays
+    hit = cache.get(seeds)
+    if hit is None:
+        if len(cache) >= 16:    # (seeds that came and went)
+            cache.clear()
+        hit = cache[seeds] = torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64,
+                                        device=group.device)
+    return hit
+
+
+def _check_step(seeds, step):
+    """The step of a stochastic grouped step, validated: (step, step word).  Not read without seeds."""
+    if seeds is None:
+        return 0, None
+    if isinstance(step, torch.Tensor):
+        if step.dtype != torch.int64 or step.numel() != 1:
+            raise TypeError("a device-side step must be a one-element int64 tensor")
+        return 0, step
+    if isinstance(step, bool) or not isinstance(step, int) or not 0 <= step < 2 ** 64:
+        raise ValueError("step must be an int in [0, 2**64) or a one-element int64 device tensor, got %r" % (step,))
+    return step, None
+
+
+def _step_group(group, ids, rows, stochastic_rounding, seeds=None):
+    """What both grouped steps check first, without the GPU: the group, the rounding, ids and rows.  Returns (group, index
+    code, n, seeds)."""
     group = _as_group(group)
     if group.quantized:
         raise TypeError("a group of fused 8-bit tables has no optimizer step: quantized tables are inference only")
-    if stochastic_rounding:
-        raise ValueError("stochastic rounding on a grouped step does not exist: its bits are named by the table row, which "
-                         "a global row is not; round to nearest, or step table by table (GroupedGrad.per_table)")
+    seeds = _check_seeds(group, stochastic_rounding, seeds)
     if group.num_tables > MAX_GROUPED_STEP_TABLES:
         raise ValueError("a grouped step takes at most %d tables, the group has %d"
                          % (MAX_GROUPED_STEP_TABLES, group.num_tables))
@@ -409,7 +472,7 @@ def _step_group(group, ids, rows, stochastic_rounding):
         raise ValueError("the row size must be a multiple of 4 bytes")
     if ids.dim() != 1 or rows.shape[0] != ids.numel():
         raise ValueError("ids must hold one entry per row of rows: %d ids, %d rows" % (ids.numel(), rows.shape[0]))
-    return group, it, ids.numel()
+    return group, it, ids.numel(), seeds
 
 
 def _check_group_states(group, name, states, rowwise):
@@ -464,7 +527,7 @@ def _step_devices(group, named):
 
 
 def sparse_row_update_grouped(group, ids, rows, *, rule, lr, states=None, eps=1e-8, count=None, last_id=None,
-                              stochastic_rounding=False):
+                              stochastic_rounding=False, seeds=None, step=0):
     """sparse_row_update on a group of SEPARATE table tensors, in ONE launch (cuembed::SparseRowUpdateGrouped): (ids, rows)
     is the compressed gradient of the group -- GroupedGrad's ids, GLOBAL rows of the tables laid end to end, distinct and
     inside [0, group.total_rows) wherever valid -- and for every valid entry k the kernel finds the table t with
@@ -478,10 +541,21 @@ def sparse_row_update_grouped(group, ids, rows, *, rule, lr, states=None, eps=1e
     The rules, lr (a float or a one-element fp32 device tensor), eps and the count sources count=int | count=tensor |
     last_id=tensor are sparse_row_update's; a count below zero or above ids.numel() applies nothing.  The least aligned
     table (and, for "adagrad", state tensor) decides the lane width for the whole group, and the result has the bits of
-    num_tables sparse_row_update calls at that lane width.  Round to nearest: stochastic_rounding=True is an error.
+    num_tables sparse_row_update calls at that lane width.
+
+    stochastic_rounding=True, seeds=[...] (float16 / bfloat16 tables): ONE SEED PER TABLE, ints in [0, 2**64), and one
+    `step` for the group, an int in [0, 2**64) or a one-element int64 device tensor.  (seeds may also be the int64
+    device tensor [num_tables] that holds the seeds' bits, as the torch op takes it.)  The bits of entry k are those of
+    (seeds[t], step, ids[k] - row_base[t], column): the step equals num_tables sparse_row_update(stochastic_rounding=True,
+    seed=seeds[t], step=step) calls, and a table's bits depend neither on the group it is in nor on its place there.  (The
+    single-table step on a one-storage group's flat tensor names its bits by the global row: other bits.)  There are no
+    default seeds -- one seed for the group would give row r of every table the same bits -- so stochastic_rounding=True
+    without seeds is an error, and so are seeds without it.  The seeds' device tensor is built at the first call with
+    these seeds and kept on the group.
     Everything is validated before the launch; nothing is read back, so the call can be captured into a HIP graph (the
     pointer arrays of `states` are built at the first call with these tensors and kept on the group)."""
-    group, it, n = _step_group(group, ids, rows, stochastic_rounding)
+    group, it, n, seeds = _step_group(group, ids, rows, stochastic_rounding, seeds)
+    step, step_word = _check_step(seeds, step)
     if rule not in UPDATE_RULES:
         raise ValueError("rule must be one of %r, got %r" % (sorted(UPDATE_RULES), rule))
     if rule == "sgd":
@@ -492,7 +566,8 @@ def sparse_row_update_grouped(group, ids, rows, *, rule, lr, states=None, eps=1e
     num_rows, count_word, words64, _, _ = _entry_counts(ids, count, last_id, None, None)
     lr, lr_word = _word("lr", lr, torch.float32)
     # ---- the call is in order: now the devices
-    _step_devices(group, (("ids", ids), ("rows", rows), ("count", count_word), ("last_id", last_id), ("lr", lr_word)) +
+    _step_devices(group, (("ids", ids), ("rows", rows), ("count", count_word), ("last_id", last_id), ("lr", lr_word),
+                          ("step", step_word), ("seeds", seeds if isinstance(seeds, torch.Tensor) else None)) +
                   tuple(("states[%d]" % t, s) for t, s in enumerate(states or ())))
     host = dev = None
     state_bits = ()
@@ -504,6 +579,13 @@ def sparse_row_update_grouped(group, ids, rows, *, rule, lr, states=None, eps=1e
     if n == 0:
         return None
     with torch.cuda.device(group.device):
+        if seeds is not None:
+            _lib.lib().cuembed_sparse_row_update_grouped_stochastic(
+                group._host_array, _ptr(group.table_ptrs), host, _ptr(dev), group.num_tables, _ELEM[group.dtype],
+                group.width, _ptr(group.row_base_device), UPDATE_RULES[rule], _ptr(ids), it, _ptr(rows), n, int(num_rows),
+                _ptr(count_word), int(words64), _ptr(last_id), lr, _ptr(lr_word), float(eps),
+                _ptr(_seeds_tensor(group, seeds)), step, _ptr(step_word), _stream(rows))
+            return None
         _lib.lib().cuembed_sparse_row_update_grouped(
             group._host_array, _ptr(group.table_ptrs), host, _ptr(dev), group.num_tables, _ELEM[group.dtype], group.width,
             _ptr(group.row_base_device), UPDATE_RULES[rule], _ptr(ids), it, _ptr(rows), n, int(num_rows), _ptr(count_word),
@@ -512,14 +594,18 @@ def sparse_row_update_grouped(group, ids, rows, *, rule, lr, states=None, eps=1e
 
 
 def sparse_row_adam_grouped(group, ids, rows, *, exp_avg, exp_avg_sq, lr, bias_factor=1.0, betas=(0.9, 0.999), eps=1e-8,
-                            weight_decay=0.0, rowwise=False, count=None, last_id=None, stochastic_rounding=False):
+                            weight_decay=0.0, rowwise=False, count=None, last_id=None, stochastic_rounding=False,
+                            seeds=None, step=0):
     """sparse_row_adam on a group of SEPARATE table tensors, in ONE launch (cuembed::SparseRowAdamGrouped): as
     sparse_row_update_grouped, with exp_avg a sequence of num_tables float32 tensors [rows_t, width] and exp_avg_sq one of
     [rows_t, width] tensors, or with rowwise=True of [rows_t] tensors.  lr, bias_factor (a float or a one-element fp32
     device tensor: adam_clock_advance's word, one clock for the group), betas, eps, weight_decay (decoupled, named rows
     only) and the formulas are sparse_row_adam's; the result has the bits of num_tables sparse_row_adam calls at the
-    group's lane width.  Round to nearest: stochastic_rounding=True is an error.  Nothing is read back."""
-    group, it, n = _step_group(group, ids, rows, stochastic_rounding)
+    group's lane width.  stochastic_rounding=True, seeds=[...], step: as in sparse_row_update_grouped -- one seed per table,
+    the bits of num_tables sparse_row_adam(stochastic_rounding=True, seed=seeds[t], step=step) calls.  Nothing is read
+    back."""
+    group, it, n, seeds = _step_group(group, ids, rows, stochastic_rounding, seeds)
+    step, step_word = _check_step(seeds, step)
     exp_avg = _check_group_states(group, "exp_avg", exp_avg, False)
     exp_avg_sq = _check_group_states(group, "exp_avg_sq", exp_avg_sq, bool(rowwise))
     beta1, beta2 = _check_betas(betas)
@@ -532,7 +618,8 @@ def sparse_row_adam_grouped(group, ids, rows, *, exp_avg, exp_avg_sq, lr, bias_f
     bias_factor, bias_word = _word("bias_factor", bias_factor, torch.float32)
     # ---- the call is in order: now the devices
     _step_devices(group, (("ids", ids), ("rows", rows), ("count", count_word), ("last_id", last_id), ("lr", lr_word),
-                          ("bias_factor", bias_word)) +
+                          ("bias_factor", bias_word), ("step", step_word),
+                          ("seeds", seeds if isinstance(seeds, torch.Tensor) else None)) +
                   tuple(("exp_avg[%d]" % t, s) for t, s in enumerate(exp_avg)) +
                   tuple(("exp_avg_sq[%d]" % t, s) for t, s in enumerate(exp_avg_sq)))
     m_host, m_dev, m_bits = _state_ptrs(group, exp_avg)
@@ -543,6 +630,15 @@ def sparse_row_adam_grouped(group, ids, rows, *, exp_avg, exp_avg_sq, lr, bias_f
     if n == 0:
         return None
     with torch.cuda.device(group.device):
+        if seeds is not None:
+            _lib.lib().cuembed_sparse_row_adam_grouped_stochastic(
+                group._host_array, _ptr(group.table_ptrs), m_host, _ptr(m_dev), v_host, _ptr(v_dev), group.num_tables,
+                _ELEM[group.dtype], group.width, _ptr(group.row_base_device),
+                ADAM_RULES["rowwise_adam" if rowwise else "adam"], _ptr(ids), it, _ptr(rows), n, int(num_rows),
+                _ptr(count_word), int(words64), _ptr(last_id), lr, _ptr(lr_word), bias_factor, _ptr(bias_word), beta1,
+                1.0 - beta1, beta2, 1.0 - beta2, float(eps), float(weight_decay), _ptr(_seeds_tensor(group, seeds)), step,
+                _ptr(step_word), _stream(rows))
+            return None
         _lib.lib().cuembed_sparse_row_adam_grouped(
             group._host_array, _ptr(group.table_ptrs), m_host, _ptr(m_dev), v_host, _ptr(v_dev), group.num_tables,
             _ELEM[group.dtype], group.width, _ptr(group.row_base_device),

@@ -47,7 +47,12 @@ number of tables, by
         .apply(grad)                            a GroupedGrad (cuembed_amd.grouped_backward.embedding_backward_grouped);
         .backward_and_apply(grad_y, idx, offsets, weights, mode)     the grouped backward in its compressed form + the
                                                 step: no read-back, so forward + backward_and_apply can be captured.
-                                                They own one state tensor (Adam: two) per table; round to nearest only.
+                                                They own one state tensor (Adam: two) per table.  With
+                                                stochastic_rounding=True, seeds=[one per table] (16-bit tables) the step
+                                                rounds table t with the bits of (seeds[t], rounding_step, row in the
+                                                table, column): those of one SparseUpdater(seed=seeds[t]) per table, and
+                                                not those of an updater on a one-storage group's flat tensor, which names
+                                                its bits by the global row.  There are no default seeds.
 
 Stochastic rounding (stochastic_rounding=True, seed=...; float16 / bfloat16 tables): the rounding to the table's dtype
 goes up or down with the probability of the fp32 value's position between its neighbours, so that updates below half a
@@ -230,14 +235,25 @@ class _GroupedGradientStep:
     """The index path shared by GroupSparseUpdater and GroupSparseAdamUpdater: the grouped backward in its compressed form
     -- global ids, rows, the count left on the device -- handed to self.apply(grad).  Needs self.group."""
 
-    def _init_group(self, group, stochastic_rounding):
+    def _init_group(self, group, stochastic_rounding, seeds):
         group = _grouped._as_group(group)
         if group.quantized:
             raise TypeError("a group of fused 8-bit tables has no optimizer step: quantized tables are inference only")
-        if stochastic_rounding:
-            raise ValueError("stochastic rounding on a grouped step does not exist: use one SparseUpdater / "
-                             "SparseAdamUpdater per table (or a one-storage group's flat tensor) for it")
+        self.seeds = _grouped_backward._check_seeds(group, stochastic_rounding, seeds)
+        self.stochastic_rounding = self.seeds is not None
         self.group = group
+        self.rounding_step = None
+        if self.stochastic_rounding:
+            # the step word and the seeds on the device, now: the first apply may be under capture
+            self.rounding_step = torch.zeros((1,), dtype=torch.int64, device=group.device)
+            if group.device.type == "cuda":
+                _grouped_backward._seeds_tensor(group, self.seeds)
+
+    def _rounding(self):
+        """The rounding keywords of one grouped step."""
+        if not self.stochastic_rounding:
+            return {}
+        return dict(stochastic_rounding=True, seeds=self.seeds, step=self.rounding_step)
 
     def backward_and_apply(self, grad_y, idx, offsets=None, weights=None, mode="sum"):
         """The backward of out = embedding_forward_grouped(group, idx, offsets, weights, mode=mode) and the step, in one
@@ -267,13 +283,19 @@ class GroupSparseUpdater(_GroupedGradientStep):
     """SparseUpdater for a TableGroup (or a list of tables) of SEPARATE tensors: applies a GroupedGrad to all tables in ONE
     launch (cuembed_amd.grouped_backward.sparse_row_update_grouped) and owns the state, `.states`: None ("sgd") or one
     fp32 tensor per table, [rows_t, width] ("adagrad") or [rows_t] ("rowwise_adagrad").  lr: a float or a one-element
-    fp32 device tensor; assign `.lr` to change it.  Round to nearest: stochastic_rounding=True is an error.  Works on a
-    one-storage group as well (its tables are views of group.flat)."""
+    fp32 device tensor; assign `.lr` to change it.  Works on a one-storage group as well (its tables are views of
+    group.flat).
 
-    def __init__(self, group, rule, lr, eps=1e-8, initial_accumulator_value=0.0, stochastic_rounding=False):
+    stochastic_rounding=True, seeds=[...] (16-bit tables): one seed per table, ints in [0, 2**64); every apply rounds
+    table t with the bits of (seeds[t], rounding_step), where `.rounding_step` is an int64 device word that starts at 0
+    and is advanced on the device after every apply -- also one whose gradient has no entries -- so nothing is read back
+    and a captured backward_and_apply draws fresh bits at every replay.  stochastic_rounding=True without seeds is an
+    error: there are no default seeds."""
+
+    def __init__(self, group, rule, lr, eps=1e-8, initial_accumulator_value=0.0, stochastic_rounding=False, seeds=None):
         if rule not in _ops.UPDATE_RULES:
             raise ValueError("rule must be one of %r, got %r" % (sorted(_ops.UPDATE_RULES), rule))
-        self._init_group(group, stochastic_rounding)
+        self._init_group(group, stochastic_rounding, seeds)
         self.rule = rule
         self.lr = lr
         self.eps = float(eps)
@@ -288,7 +310,10 @@ class GroupSparseUpdater(_GroupedGradientStep):
         """tables[t][r] (and its state) <- rule, for the valid entries of a GroupedGrad.  Nothing is read back."""
         self._check_grad(grad)
         _grouped_backward.sparse_row_update_grouped(self.group, grad.ids, grad.rows, rule=self.rule, lr=self.lr,
-                                                    states=self.states, eps=self.eps, last_id=grad.last_id)
+                                                    states=self.states, eps=self.eps, last_id=grad.last_id,
+                                                    **self._rounding())
+        if self.stochastic_rounding:
+            self.rounding_step.add_(1)      # on the device, after the kernel in stream order: one apply = one step
 
 
 class GroupSparseAdamUpdater(_GroupedGradientStep):
@@ -296,14 +321,15 @@ class GroupSparseAdamUpdater(_GroupedGradientStep):
     (cuembed_amd.grouped_backward.sparse_row_adam_grouped).  Owns `.exp_avg` and `.exp_avg_sq`, one fp32 tensor per table
     each ([rows_t, width]; exp_avg_sq [rows_t] with rowwise=True), and ONE bias-factor clock for the group (`.powers`,
     `.bias_factor`), which every apply advances on the device: a captured step takes the next step at every replay.
-    bias_correction=False leaves the factor at 1.  Round to nearest: stochastic_rounding=True is an error."""
+    bias_correction=False leaves the factor at 1.  stochastic_rounding / seeds / `.rounding_step` are
+    GroupSparseUpdater's."""
 
     def __init__(self, group, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rowwise=False, bias_correction=True,
-                 stochastic_rounding=False):
+                 stochastic_rounding=False, seeds=None):
         self.betas = _ops._check_betas(betas)
         if not float(eps) >= 0.0 or not float(weight_decay) >= 0.0:
             raise ValueError("eps and weight_decay must not be negative")
-        self._init_group(group, stochastic_rounding)
+        self._init_group(group, stochastic_rounding, seeds)
         self.lr = lr
         self.eps = float(eps)
         self.weight_decay = float(weight_decay)
@@ -328,7 +354,9 @@ class GroupSparseAdamUpdater(_GroupedGradientStep):
         _grouped_backward.sparse_row_adam_grouped(
             self.group, grad.ids, grad.rows, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, lr=self.lr,
             bias_factor=self.bias_factor if self.bias_correction else self._one, betas=self.betas, eps=self.eps,
-            weight_decay=self.weight_decay, rowwise=self.rowwise, last_id=grad.last_id)
+            weight_decay=self.weight_decay, rowwise=self.rowwise, last_id=grad.last_id, **self._rounding())
+        if self.stochastic_rounding:
+            self.rounding_step.add_(1)      # on the device, after the kernel in stream order: one apply = one step
 
 
 def _new_moments(table, rowwise):

@@ -862,6 +862,34 @@ void cuembed_sparse_row_adam_grouped(const void* const* tables_host, const void*
                                      float lr, const float* lr_device, float bias_factor, const float* bias_factor_device,
                                      float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float eps,
                                      float weight_decay, cuembed_stream_t stream);
+/* The two grouped steps with STOCHASTIC ROUNDING (CUEMBED_F16 / CUEMBED_BF16 tables; CUEMBED_F32 is a bad type): the
+ * arguments of the functions above, then seeds_device -- num_tables uint64 seeds in DEVICE memory, ONE PER TABLE, required
+ * -- and the step, one value for the group: `step`, or step_device (one int64 word on the device, read by the kernel;
+ * advance it on the device and a replayed graph draws fresh bits).  The one rounding of entry k draws the bits of
+ * (seeds[t], step, id - row_base[t], column), t the entry's table: those of cuembed_sparse_row_update_stochastic /
+ * cuembed_sparse_row_adam_stochastic on table t alone with seed = seeds[t], so a table's bits depend neither on the group
+ * it is in nor on its place there.  (Not the bits of the single-table step on the tables laid end to end in one
+ * allocation: that one names them by the global row.)  Arithmetic and state as with round to nearest. */
+void cuembed_sparse_row_update_grouped_stochastic(const void* const* tables_host, const void* const* tables_device,
+                                                  const void* const* state_host, const void* const* state_device,
+                                                  int num_tables, int elem_type, int embed_width, const int64_t* row_base,
+                                                  int rule, const void* ids, int index_type, const void* rows,
+                                                  int64_t total_entries, int64_t num_rows, const void* count_word,
+                                                  int count_word_is_64, const void* last_id, float lr,
+                                                  const float* lr_device, float eps, const uint64_t* seeds_device,
+                                                  uint64_t step, const int64_t* step_device, cuembed_stream_t stream);
+void cuembed_sparse_row_adam_grouped_stochastic(const void* const* tables_host, const void* const* tables_device,
+                                                const void* const* exp_avg_host, const void* const* exp_avg_device,
+                                                const void* const* exp_avg_sq_host, const void* const* exp_avg_sq_device,
+                                                int num_tables, int elem_type, int embed_width, const int64_t* row_base,
+                                                int rule, const void* ids, int index_type, const void* rows,
+                                                int64_t total_entries, int64_t num_rows, const void* count_word,
+                                                int count_word_is_64, const void* last_id, float lr,
+                                                const float* lr_device, float bias_factor,
+                                                const float* bias_factor_device, float beta1, float one_minus_beta1,
+                                                float beta2, float one_minus_beta2, float eps, float weight_decay,
+                                                const uint64_t* seeds_device, uint64_t step, const int64_t* step_device,
+                                                cuembed_stream_t stream);
 /* hipPeekAtLastError() as an int (0 = hipSuccess); launches themselves never
  * report errors, exactly like the reference. */
 int cuembed_peek_last_error(void);
