@@ -171,13 +171,15 @@ def build_torch_binding(force=False):
     return TORCH_BINDING_PATH
 
 
-def build_header_api_test(force=False):
-    """Compiles tests/cpp/header_api_kat.hip against the header-only API (the C++ side of the
-    drop-in boundary).  Returns the path of the executable."""
-    src = os.path.join(ROOT, "tests", "cpp", "header_api_kat.hip")
-    exe = os.path.join(ROOT, "tests", "cpp", "header_api_kat")
+def _build_program(what, flags, force, error_name=None, extra_srcs=(), extra_deps=(), link=()):
+    """Compiles one stand-alone program against the header-only API: the .hip file `what` (a path under ROOT) and
+    `extra_srcs` with `flags`, to the executable of the same name without the suffix, unless the stamp next to it holds
+    the digest of the sources, `extra_deps` and every header of the header-only API.  `error_name` names the program in
+    the error message, where its path does not.  Returns the path of the executable."""
+    src = os.path.join(ROOT, what)
+    exe = src[:-len(".hip")]
     stamp = exe + ".stamp"
-    deps = [src]
+    deps = [src] + list(extra_srcs) + list(extra_deps)
     for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
         deps += [os.path.join(dirpath, f) for f in files]
     digest = _digest_files(deps)
@@ -185,133 +187,57 @@ def build_header_api_test(force=False):
         with open(stamp) as f:
             if f.read().strip() == digest:
                 return exe
-    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-munsafe-fp-atomics", "-I" + CSRC,
-           src, "-o", exe]
+    cmd = [_hipcc(), "--offload-arch=" + ARCH] + flags + ["-I" + CSRC, src] + list(extra_srcs) + list(link) + ["-o", exe]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
-        raise RuntimeError("hipcc failed for the header-only API test:\n" + r.stdout)
+        raise RuntimeError("hipcc failed for %s:\n" % (error_name or what) + r.stdout)
     with open(stamp, "w") as f:
         f.write(digest)
     return exe
+
+
+_O2 = ["-O2", "-std=c++17"]
+_O2_ATOMICS = _O2 + ["-munsafe-fp-atomics"]      # float atomics as hardware instructions, as in the library
+
+
+def build_header_api_test(force=False):
+    """Compiles tests/cpp/header_api_kat.hip against the header-only API (the C++ side of the
+    drop-in boundary).  Returns the path of the executable."""
+    return _build_program("tests/cpp/header_api_kat.hip", _O2_ATOMICS, force, error_name="the header-only API test")
 
 
 def build_sparse_update_test(force=False):
     """Compiles tests/cpp/sparse_update_kat.hip: cuembed::SparseRowUpdate through the header-only API against a host
     recomputation on exactly representable data.  Needs a GPU to RUN (tests/test_gpu_cpp_sparse_update.py)."""
-    src = os.path.join(ROOT, "tests", "cpp", "sparse_update_kat.hip")
-    exe = os.path.join(ROOT, "tests", "cpp", "sparse_update_kat")
-    stamp = exe + ".stamp"
-    deps = [src]
-    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
-        deps += [os.path.join(dirpath, f) for f in files]
-    digest = _digest_files(deps)
-    if not force and os.path.exists(exe) and os.path.exists(stamp):
-        with open(stamp) as f:
-            if f.read().strip() == digest:
-                return exe
-    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-I" + CSRC, src, "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("hipcc failed for tests/cpp/sparse_update_kat.hip:\n" + r.stdout)
-    with open(stamp, "w") as f:
-        f.write(digest)
-    return exe
+    return _build_program("tests/cpp/sparse_update_kat.hip", _O2, force)
 
 
 def build_stochastic_rounding_test(force=False):
     """Compiles tests/cpp/stochastic_rounding_kat.hip: cuembed::SparseRowUpdate with stochastic rounding through the
     header-only API against a host recomputation with the same rounding functions.  Needs a GPU to RUN
     (tests/test_gpu_cpp_stochastic_rounding.py)."""
-    src = os.path.join(ROOT, "tests", "cpp", "stochastic_rounding_kat.hip")
-    exe = os.path.join(ROOT, "tests", "cpp", "stochastic_rounding_kat")
-    stamp = exe + ".stamp"
-    deps = [src]
-    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
-        deps += [os.path.join(dirpath, f) for f in files]
-    digest = _digest_files(deps)
-    if not force and os.path.exists(exe) and os.path.exists(stamp):
-        with open(stamp) as f:
-            if f.read().strip() == digest:
-                return exe
-    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-I" + CSRC, src, "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("hipcc failed for tests/cpp/stochastic_rounding_kat.hip:\n" + r.stdout)
-    with open(stamp, "w") as f:
-        f.write(digest)
-    return exe
+    return _build_program("tests/cpp/stochastic_rounding_kat.hip", _O2, force)
 
 
 def build_sparse_adam_test(force=False):
     """Compiles tests/cpp/sparse_adam_kat.hip: cuembed::SparseRowAdam and cuembed::AdamClockAdvance through the
     header-only API against expected values written in the source (exactly representable data).  Needs a GPU to RUN
     (tests/test_gpu_cpp_sparse_adam.py)."""
-    src = os.path.join(ROOT, "tests", "cpp", "sparse_adam_kat.hip")
-    exe = os.path.join(ROOT, "tests", "cpp", "sparse_adam_kat")
-    stamp = exe + ".stamp"
-    deps = [src]
-    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
-        deps += [os.path.join(dirpath, f) for f in files]
-    digest = _digest_files(deps)
-    if not force and os.path.exists(exe) and os.path.exists(stamp):
-        with open(stamp) as f:
-            if f.read().strip() == digest:
-                return exe
-    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-I" + CSRC, src, "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("hipcc failed for tests/cpp/sparse_adam_kat.hip:\n" + r.stdout)
-    with open(stamp, "w") as f:
-        f.write(digest)
-    return exe
+    return _build_program("tests/cpp/sparse_adam_kat.hip", _O2, force)
 
 
 def build_row_cache_state_test(force=False):
     """Compiles tests/cpp/row_cache_state_kat.hip: cuembed::RowCachePrefetch / RowCacheFlush with a state plane and
     cuembed::SparseRowUpdate with state_ids through the header-only API against a host recomputation on exactly
     representable data.  Needs a GPU to RUN (tests/test_gpu_cpp_row_cache_state.py)."""
-    src = os.path.join(ROOT, "tests", "cpp", "row_cache_state_kat.hip")
-    exe = os.path.join(ROOT, "tests", "cpp", "row_cache_state_kat")
-    stamp = exe + ".stamp"
-    deps = [src]
-    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
-        deps += [os.path.join(dirpath, f) for f in files]
-    digest = _digest_files(deps)
-    if not force and os.path.exists(exe) and os.path.exists(stamp):
-        with open(stamp) as f:
-            if f.read().strip() == digest:
-                return exe
-    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-munsafe-fp-atomics", "-I" + CSRC, src, "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("hipcc failed for tests/cpp/row_cache_state_kat.hip:\n" + r.stdout)
-    with open(stamp, "w") as f:
-        f.write(digest)
-    return exe
+    return _build_program("tests/cpp/row_cache_state_kat.hip", _O2_ATOMICS, force)
 
 
 def build_row_cache_adam_test(force=False):
     """Compiles tests/cpp/row_cache_adam_kat.hip: cuembed::RowCachePrefetch / RowCacheFlush with two state planes,
     cuembed::TranslateIndicesForRowCachePlanes and cuembed::SparseRowAdam with placed moments through the header-only API
     against a host recomputation on exactly representable data.  Needs a GPU to RUN (tests/test_gpu_cpp_row_cache_adam.py)."""
-    src = os.path.join(ROOT, "tests", "cpp", "row_cache_adam_kat.hip")
-    exe = os.path.join(ROOT, "tests", "cpp", "row_cache_adam_kat")
-    stamp = exe + ".stamp"
-    deps = [src]
-    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
-        deps += [os.path.join(dirpath, f) for f in files]
-    digest = _digest_files(deps)
-    if not force and os.path.exists(exe) and os.path.exists(stamp):
-        with open(stamp) as f:
-            if f.read().strip() == digest:
-                return exe
-    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-munsafe-fp-atomics", "-I" + CSRC, src, "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("hipcc failed for tests/cpp/row_cache_adam_kat.hip:\n" + r.stdout)
-    with open(stamp, "w") as f:
-        f.write(digest)
-    return exe
+    return _build_program("tests/cpp/row_cache_adam_kat.hip", _O2_ATOMICS, force)
 
 
 def build_row_cache_stochastic_test(force=False):
@@ -319,72 +245,21 @@ def build_row_cache_stochastic_test(force=False):
     planes, cuembed::TranslateIndicesForRowCachePlanes and cuembed::SparseRowUpdate / SparseRowAdam with row_names
     (stochastic rounding behind the cache) through the header-only API against a host recomputation with
     stochastic_rounding.hpp's host functions.  Needs a GPU to RUN (tests/test_gpu_cpp_row_cache_stochastic.py)."""
-    src = os.path.join(ROOT, "tests", "cpp", "row_cache_stochastic_kat.hip")
-    exe = os.path.join(ROOT, "tests", "cpp", "row_cache_stochastic_kat")
-    stamp = exe + ".stamp"
-    deps = [src]
-    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
-        deps += [os.path.join(dirpath, f) for f in files]
-    digest = _digest_files(deps)
-    if not force and os.path.exists(exe) and os.path.exists(stamp):
-        with open(stamp) as f:
-            if f.read().strip() == digest:
-                return exe
-    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-munsafe-fp-atomics", "-I" + CSRC, src, "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("hipcc failed for tests/cpp/row_cache_stochastic_kat.hip:\n" + r.stdout)
-    with open(stamp, "w") as f:
-        f.write(digest)
-    return exe
+    return _build_program("tests/cpp/row_cache_stochastic_kat.hip", _O2_ATOMICS, force)
 
 
 def build_grouped_train_test(force=False):
     """Compiles tests/cpp/grouped_train_kat.hip: cuembed::EmbeddingWeightGradGrouped and cuembed::GroupedMeanScale through
     the header-only API on a three-table group against a host recomputation on exactly representable data.  Needs a GPU
     to RUN (tests/test_gpu_cpp_grouped_train.py)."""
-    src = os.path.join(ROOT, "tests", "cpp", "grouped_train_kat.hip")
-    exe = os.path.join(ROOT, "tests", "cpp", "grouped_train_kat")
-    stamp = exe + ".stamp"
-    deps = [src]
-    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
-        deps += [os.path.join(dirpath, f) for f in files]
-    digest = _digest_files(deps)
-    if not force and os.path.exists(exe) and os.path.exists(stamp):
-        with open(stamp) as f:
-            if f.read().strip() == digest:
-                return exe
-    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-munsafe-fp-atomics", "-I" + CSRC, src, "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("hipcc failed for tests/cpp/grouped_train_kat.hip:\n" + r.stdout)
-    with open(stamp, "w") as f:
-        f.write(digest)
-    return exe
+    return _build_program("tests/cpp/grouped_train_kat.hip", _O2_ATOMICS, force)
 
 
 def build_grouped_sparse_update_test(force=False):
     """Compiles tests/cpp/grouped_sparse_update_kat.hip: cuembed::SparseRowUpdateGrouped / SparseRowAdamGrouped through the
     header-only API on a three-table group against cuembed::SparseRowUpdate / SparseRowAdam per table, bit for bit, on
     hashed data.  Needs a GPU to RUN (tests/test_gpu_cpp_grouped_sparse_update.py)."""
-    src = os.path.join(ROOT, "tests", "cpp", "grouped_sparse_update_kat.hip")
-    exe = os.path.join(ROOT, "tests", "cpp", "grouped_sparse_update_kat")
-    stamp = exe + ".stamp"
-    deps = [src]
-    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
-        deps += [os.path.join(dirpath, f) for f in files]
-    digest = _digest_files(deps)
-    if not force and os.path.exists(exe) and os.path.exists(stamp):
-        with open(stamp) as f:
-            if f.read().strip() == digest:
-                return exe
-    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-I" + CSRC, src, "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("hipcc failed for tests/cpp/grouped_sparse_update_kat.hip:\n" + r.stdout)
-    with open(stamp, "w") as f:
-        f.write(digest)
-    return exe
+    return _build_program("tests/cpp/grouped_sparse_update_kat.hip", _O2, force)
 
 
 def build_grouped_stochastic_rounding_test(force=False):
@@ -392,95 +267,28 @@ def build_grouped_stochastic_rounding_test(force=False):
     stochastic rounding and one seed per table through the header-only API on a three-table group, against a host
     recomputation with stochastic_rounding.hpp's host functions on exactly representable data.  Needs a GPU to RUN
     (tests/test_gpu_cpp_grouped_stochastic_rounding.py)."""
-    src = os.path.join(ROOT, "tests", "cpp", "grouped_stochastic_rounding_kat.hip")
-    exe = os.path.join(ROOT, "tests", "cpp", "grouped_stochastic_rounding_kat")
-    stamp = exe + ".stamp"
-    deps = [src]
-    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
-        deps += [os.path.join(dirpath, f) for f in files]
-    digest = _digest_files(deps)
-    if not force and os.path.exists(exe) and os.path.exists(stamp):
-        with open(stamp) as f:
-            if f.read().strip() == digest:
-                return exe
-    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-I" + CSRC, src, "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("hipcc failed for tests/cpp/grouped_stochastic_rounding_kat.hip:\n" + r.stdout)
-    with open(stamp, "w") as f:
-        f.write(digest)
-    return exe
+    return _build_program("tests/cpp/grouped_stochastic_rounding_kat.hip", _O2, force)
 
 
 def build_sort_unit_test(force=False):
     """Compiles tests/cpp/sort_route_unit.hip: host-side unit tests of the sort's integer building blocks (buffer
     routing, implicit payload division, tile maps, workspace plans).  The program makes no HIP call: it runs on the CPU."""
-    src = os.path.join(ROOT, "tests", "cpp", "sort_route_unit.hip")
-    exe = os.path.join(ROOT, "tests", "cpp", "sort_route_unit")
-    stamp = exe + ".stamp"
-    deps = [src]
-    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
-        deps += [os.path.join(dirpath, f) for f in files]
-    digest = _digest_files(deps)
-    if not force and os.path.exists(exe) and os.path.exists(stamp):
-        with open(stamp) as f:
-            if f.read().strip() == digest:
-                return exe
-    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O1", "-std=c++17", "-I" + CSRC, src, "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("hipcc failed for tests/cpp/sort_route_unit.hip:\n" + r.stdout)
-    with open(stamp, "w") as f:
-        f.write(digest)
-    return exe
+    return _build_program("tests/cpp/sort_route_unit.hip", ["-O1", "-std=c++17"], force)
 
 
 def build_device_blocks_test(force=False):
     """Compiles tests/cpp/device_blocks_unit.hip: unit tests of the gather / scatter building blocks (addressing, column
     slices, Pack / Arith / RowPool, FinishPooledRow, the backward's RunSum, staging and chaining) instantiated in small kernels and compared with host
     recomputation, bit for bit.  Needs a GPU to RUN (tests/test_gpu_device_blocks.py)."""
-    src = os.path.join(ROOT, "tests", "cpp", "device_blocks_unit.hip")
-    exe = os.path.join(ROOT, "tests", "cpp", "device_blocks_unit")
-    stamp = exe + ".stamp"
-    deps = [src]
-    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
-        deps += [os.path.join(dirpath, f) for f in files]
-    digest = _digest_files(deps)
-    if not force and os.path.exists(exe) and os.path.exists(stamp):
-        with open(stamp) as f:
-            if f.read().strip() == digest:
-                return exe
-    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-munsafe-fp-atomics", "-I" + CSRC, src, "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("hipcc failed for tests/cpp/device_blocks_unit.hip:\n" + r.stdout)
-    with open(stamp, "w") as f:
-        f.write(digest)
-    return exe
+    return _build_program("tests/cpp/device_blocks_unit.hip", ["-O3", "-std=c++17", "-munsafe-fp-atomics"], force)
 
 
 def build_manual_benchmark(force=False):
     """Compiles benchmarks/manual_benchmark.hip (C++ harness on the header-only API)."""
-    src = os.path.join(ROOT, "benchmarks", "manual_benchmark.hip")
     gen = os.path.join(CSRC, "utils", "synthetic_inputs.cpp")
-    exe = os.path.join(ROOT, "benchmarks", "manual_benchmark")
-    stamp = exe + ".stamp"
-    deps = [src, gen, os.path.join(CSRC, "utils", "datagen.hpp")]
-    for dirpath, _, files in os.walk(os.path.join(CSRC, "cuembed", "include")):
-        deps += [os.path.join(dirpath, f) for f in files]
-    digest = _digest_files(deps)
-    if not force and os.path.exists(exe) and os.path.exists(stamp):
-        with open(stamp) as f:
-            if f.read().strip() == digest:
-                return exe
-    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-munsafe-fp-atomics", "-I" + CSRC,
-           src, gen, "-ldl", "-o", exe]     # (-ldl: --check_result loads the CPU checker with dlopen)
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("hipcc failed for benchmarks/manual_benchmark.hip:\n" + r.stdout)
-    with open(stamp, "w") as f:
-        f.write(digest)
-    return exe
+    return _build_program("benchmarks/manual_benchmark.hip", ["-O3", "-std=c++17", "-munsafe-fp-atomics"], force,
+                          extra_srcs=[gen], extra_deps=[os.path.join(CSRC, "utils", "datagen.hpp")],
+                          link=["-ldl"])     # (-ldl: --check_result loads the CPU checker with dlopen)
 
 
 if __name__ == "__main__":

@@ -11,18 +11,12 @@ void cuembed_sparse_row_update(void* table, int elem_type, int embed_width, floa
   // (round to nearest only: the stochastic kernels are c_api_optimizer_stochastic.hip's)
   const cuembed::SparseUpdateOptions o = cuembed_c_api::UpdateOptions(rule, piece_rows, pieces, num_rows, counts,
                                                                       counts_are_int64, last_id, lr, lr_device, eps);
-#define UPD(E, I) \
-  cuembed_c_api::Update<E, I, cuembed::UpdateRoundings::kNearestOnly>(table, state, embed_width, ids, rows, o, stream)
-  switch ((elem_type << 1) | index_type) {
-    case 0: UPD(float, int32_t); break;
-    case 1: UPD(float, int64_t); break;
-    case 2: UPD(__half, int32_t); break;
-    case 3: UPD(__half, int64_t); break;
-    case 4: UPD(__hip_bfloat16, int32_t); break;
-    case 5: UPD(__hip_bfloat16, int64_t); break;
-    default: CUEMBED_C_API_BAD_TYPE();
-  }
-#undef UPD
+  const bool known = cuembed_c_api::DispatchTypes<true>(elem_type, index_type, [&](auto elem, auto index) {
+    using E = typename decltype(elem)::type;
+    using I = typename decltype(index)::type;
+    cuembed_c_api::Update<E, I, cuembed::UpdateRoundings::kNearestOnly>(table, state, embed_width, ids, rows, o, stream);
+  });
+  if (!known) CUEMBED_C_API_BAD_TYPE();
 }
 
 void cuembed_sparse_row_update_placed(void* table, int elem_type, int embed_width, float* state, int rule,
@@ -32,20 +26,14 @@ void cuembed_sparse_row_update_placed(void* table, int elem_type, int embed_widt
                                       const int64_t* state_ids) {
   const cuembed::SparseUpdateOptions o = cuembed_c_api::UpdateOptions(rule, piece_rows, pieces, num_rows, counts,
                                                                       counts_are_int64, last_id, lr, lr_device, eps);
-#define UPD(E, I)                                                                                                  \
-  cuembed::SparseRowUpdate<E, I, cuembed::UpdateRoundings::kNearestOnly>(                                          \
-      static_cast<E*>(table), state, embed_width, static_cast<const I*>(ids), static_cast<const E*>(rows), o,      \
-      cuembed_c_api::Stream(stream), state_ids)
-  switch ((elem_type << 1) | index_type) {
-    case 0: UPD(float, int32_t); break;
-    case 1: UPD(float, int64_t); break;
-    case 2: UPD(__half, int32_t); break;
-    case 3: UPD(__half, int64_t); break;
-    case 4: UPD(__hip_bfloat16, int32_t); break;
-    case 5: UPD(__hip_bfloat16, int64_t); break;
-    default: CUEMBED_C_API_BAD_TYPE();
-  }
-#undef UPD
+  const bool known = cuembed_c_api::DispatchTypes<true>(elem_type, index_type, [&](auto elem, auto index) {
+    using E = typename decltype(elem)::type;
+    using I = typename decltype(index)::type;
+    cuembed::SparseRowUpdate<E, I, cuembed::UpdateRoundings::kNearestOnly>(
+        static_cast<E*>(table), state, embed_width, static_cast<const I*>(ids), static_cast<const E*>(rows), o,
+        cuembed_c_api::Stream(stream), state_ids);
+  });
+  if (!known) CUEMBED_C_API_BAD_TYPE();
 }
 
 void cuembed_sparse_row_update_launch_shape(int elem_type, int embed_width, int64_t total_entries, int compute_units,

@@ -13,18 +13,13 @@ void cuembed_sparse_row_adam(void* table, int elem_type, int embed_width, float*
   const cuembed::SparseAdamOptions o = cuembed_c_api::AdamOptions(
       rule, piece_rows, pieces, num_rows, counts, counts_are_int64, last_id, lr, lr_device, bias_factor,
       bias_factor_device, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay);
-#define ADAM(E, I) \
-  cuembed_c_api::Adam<E, I, cuembed::UpdateRoundings::kNearestOnly>(table, exp_avg, exp_avg_sq, embed_width, ids, rows, o, stream)
-  switch ((elem_type << 1) | index_type) {
-    case 0: ADAM(float, int32_t); break;
-    case 1: ADAM(float, int64_t); break;
-    case 2: ADAM(__half, int32_t); break;
-    case 3: ADAM(__half, int64_t); break;
-    case 4: ADAM(__hip_bfloat16, int32_t); break;
-    case 5: ADAM(__hip_bfloat16, int64_t); break;
-    default: CUEMBED_C_API_BAD_TYPE();
-  }
-#undef ADAM
+  const bool known = cuembed_c_api::DispatchTypes<true>(elem_type, index_type, [&](auto elem, auto index) {
+    using E = typename decltype(elem)::type;
+    using I = typename decltype(index)::type;
+    cuembed_c_api::Adam<E, I, cuembed::UpdateRoundings::kNearestOnly>(table, exp_avg, exp_avg_sq, embed_width, ids, rows, o,
+                                                                      stream);
+  });
+  if (!known) CUEMBED_C_API_BAD_TYPE();
 }
 
 void cuembed_sparse_row_adam_placed(void* table, int elem_type, int embed_width, float* exp_avg, float* exp_avg_sq,
@@ -37,20 +32,14 @@ void cuembed_sparse_row_adam_placed(void* table, int elem_type, int embed_width,
   const cuembed::SparseAdamOptions o = cuembed_c_api::AdamOptions(
       rule, piece_rows, pieces, num_rows, counts, counts_are_int64, last_id, lr, lr_device, bias_factor,
       bias_factor_device, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay);
-#define ADAM(E, I)                                                                                                 \
-  cuembed::SparseRowAdam<E, I, cuembed::UpdateRoundings::kNearestOnly>(                                            \
-      static_cast<E*>(table), exp_avg, exp_avg_sq, embed_width, static_cast<const I*>(ids), static_cast<const E*>(rows), \
-      o, cuembed_c_api::Stream(stream), exp_avg_ids, exp_avg_sq_ids)
-  switch ((elem_type << 1) | index_type) {
-    case 0: ADAM(float, int32_t); break;
-    case 1: ADAM(float, int64_t); break;
-    case 2: ADAM(__half, int32_t); break;
-    case 3: ADAM(__half, int64_t); break;
-    case 4: ADAM(__hip_bfloat16, int32_t); break;
-    case 5: ADAM(__hip_bfloat16, int64_t); break;
-    default: CUEMBED_C_API_BAD_TYPE();
-  }
-#undef ADAM
+  const bool known = cuembed_c_api::DispatchTypes<true>(elem_type, index_type, [&](auto elem, auto index) {
+    using E = typename decltype(elem)::type;
+    using I = typename decltype(index)::type;
+    cuembed::SparseRowAdam<E, I, cuembed::UpdateRoundings::kNearestOnly>(
+        static_cast<E*>(table), exp_avg, exp_avg_sq, embed_width, static_cast<const I*>(ids), static_cast<const E*>(rows), o,
+        cuembed_c_api::Stream(stream), exp_avg_ids, exp_avg_sq_ids);
+  });
+  if (!known) CUEMBED_C_API_BAD_TYPE();
 }
 
 void cuembed_adam_clock_advance(double* powers, float* bias_factor, double beta1, double beta2, cuembed_stream_t stream) {

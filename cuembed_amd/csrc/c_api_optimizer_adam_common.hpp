@@ -1,6 +1,5 @@
 // Shared by the two C-ABI units of the sparse Adam step (c_api_optimizer_adam.hip: round to nearest and the bias-factor
-// clock; c_api_optimizer_adam_stochastic.hip: stochastic rounding): the options of a call and the dispatch on the type
-// codes.
+// clock; c_api_optimizer_adam_stochastic.hip: stochastic rounding): the options of a call and the call on its types.
 #ifndef CUEMBED_AMD_C_API_OPTIMIZER_ADAM_COMMON_HPP_
 #define CUEMBED_AMD_C_API_OPTIMIZER_ADAM_COMMON_HPP_
 

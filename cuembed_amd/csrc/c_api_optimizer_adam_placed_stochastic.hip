@@ -20,18 +20,14 @@ void cuembed_sparse_row_adam_placed_stochastic(void* table, int elem_type, int e
       bias_factor_device, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay);
   cuembed_c_api::FillStochasticRounding(o, seed, step, step_device);
   // (the named step alone: without names the call is cuembed_sparse_row_adam_stochastic's, and aborts here)
-#define ADAM(E, I)                                                                                                 \
-  cuembed::detail::SparseRowAdamNamed<E, I, cuembed::UpdateRoundings::kStochasticOnly>(                            \
-      static_cast<E*>(table), exp_avg, exp_avg_sq, embed_width, static_cast<const I*>(ids), static_cast<const E*>(rows), \
-      o, cuembed_c_api::Stream(stream), exp_avg_ids, exp_avg_sq_ids, row_names)
-  switch ((elem_type << 1) | index_type) {
-    case 2: ADAM(__half, int32_t); break;
-    case 3: ADAM(__half, int64_t); break;
-    case 4: ADAM(__hip_bfloat16, int32_t); break;
-    case 5: ADAM(__hip_bfloat16, int64_t); break;
-    default: CUEMBED_C_API_BAD_TYPE();   // (float tables have no rounding to randomise)
-  }
-#undef ADAM
+  const bool known = cuembed_c_api::DispatchTypes<false>(elem_type, index_type, [&](auto elem, auto index) {
+    using E = typename decltype(elem)::type;
+    using I = typename decltype(index)::type;
+    cuembed::detail::SparseRowAdamNamed<E, I, cuembed::UpdateRoundings::kStochasticOnly>(
+        static_cast<E*>(table), exp_avg, exp_avg_sq, embed_width, static_cast<const I*>(ids), static_cast<const E*>(rows), o,
+        cuembed_c_api::Stream(stream), exp_avg_ids, exp_avg_sq_ids, row_names);
+  });
+  if (!known) CUEMBED_C_API_BAD_TYPE();   // (float tables have no rounding to randomise)
 }
 
 }  // extern "C"

@@ -15,16 +15,13 @@ void cuembed_sparse_row_adam_stochastic(void* table, int elem_type, int embed_wi
       rule, piece_rows, pieces, num_rows, counts, counts_are_int64, last_id, lr, lr_device, bias_factor,
       bias_factor_device, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay);
   cuembed_c_api::FillStochasticRounding(o, seed, step, step_device);
-#define ADAM(E, I) \
-  cuembed_c_api::Adam<E, I, cuembed::UpdateRoundings::kStochasticOnly>(table, exp_avg, exp_avg_sq, embed_width, ids, rows, o, stream)
-  switch ((elem_type << 1) | index_type) {
-    case 2: ADAM(__half, int32_t); break;
-    case 3: ADAM(__half, int64_t); break;
-    case 4: ADAM(__hip_bfloat16, int32_t); break;
-    case 5: ADAM(__hip_bfloat16, int64_t); break;
-    default: CUEMBED_C_API_BAD_TYPE();   // (float tables have no rounding to randomise)
-  }
-#undef ADAM
+  const bool known = cuembed_c_api::DispatchTypes<false>(elem_type, index_type, [&](auto elem, auto index) {
+    using E = typename decltype(elem)::type;
+    using I = typename decltype(index)::type;
+    cuembed_c_api::Adam<E, I, cuembed::UpdateRoundings::kStochasticOnly>(table, exp_avg, exp_avg_sq, embed_width, ids, rows,
+                                                                         o, stream);
+  });
+  if (!known) CUEMBED_C_API_BAD_TYPE();   // (float tables have no rounding to randomise)
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // Shared by the two C-ABI units of the sparse optimizer step (c_api_optimizer.hip: round to nearest;
-// c_api_optimizer_stochastic.hip: stochastic rounding): the options of a call and the dispatch on the type codes.
+// c_api_optimizer_stochastic.hip: stochastic rounding): the options of a call and the call on its types.
 #ifndef CUEMBED_AMD_C_API_OPTIMIZER_COMMON_HPP_
 #define CUEMBED_AMD_C_API_OPTIMIZER_COMMON_HPP_
 

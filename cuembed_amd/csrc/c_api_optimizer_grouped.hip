@@ -50,19 +50,13 @@ void cuembed_sparse_row_update_grouped(const void* const* tables_host, const voi
                                        const float* lr_device, float eps, cuembed_stream_t stream) {
   const cuembed::SparseUpdateOptions o = cuembed_c_api::UpdateOptions(rule, total_entries, 1, num_rows, count_word,
                                                                       count_word_is_64, last_id, lr, lr_device, eps);
-#define UPD(E, I)                                                                                                  \
-  UpdateGrouped<E, I>(tables_host, tables_device, state_host, state_device, num_tables, row_base, embed_width, ids, \
-                      rows, total_entries, o, stream)
-  switch ((elem_type << 1) | index_type) {
-    case 0: UPD(float, int32_t); break;
-    case 1: UPD(float, int64_t); break;
-    case 2: UPD(__half, int32_t); break;
-    case 3: UPD(__half, int64_t); break;
-    case 4: UPD(__hip_bfloat16, int32_t); break;
-    case 5: UPD(__hip_bfloat16, int64_t); break;
-    default: CUEMBED_C_API_BAD_TYPE();
-  }
-#undef UPD
+  const bool known = cuembed_c_api::DispatchTypes<true>(elem_type, index_type, [&](auto elem, auto index) {
+    using E = typename decltype(elem)::type;
+    using I = typename decltype(index)::type;
+    UpdateGrouped<E, I>(tables_host, tables_device, state_host, state_device, num_tables, row_base, embed_width, ids, rows,
+                        total_entries, o, stream);
+  });
+  if (!known) CUEMBED_C_API_BAD_TYPE();
 }
 
 void cuembed_sparse_row_adam_grouped(const void* const* tables_host, const void* const* tables_device,
@@ -77,19 +71,13 @@ void cuembed_sparse_row_adam_grouped(const void* const* tables_host, const void*
   const cuembed::SparseAdamOptions o = cuembed_c_api::AdamOptions(
       rule, total_entries, 1, num_rows, count_word, count_word_is_64, last_id, lr, lr_device, bias_factor,
       bias_factor_device, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay);
-#define ADAM(E, I)                                                                                                \
-  AdamGrouped<E, I>(tables_host, tables_device, exp_avg_host, exp_avg_device, exp_avg_sq_host, exp_avg_sq_device, \
-                    num_tables, row_base, embed_width, ids, rows, total_entries, o, stream)
-  switch ((elem_type << 1) | index_type) {
-    case 0: ADAM(float, int32_t); break;
-    case 1: ADAM(float, int64_t); break;
-    case 2: ADAM(__half, int32_t); break;
-    case 3: ADAM(__half, int64_t); break;
-    case 4: ADAM(__hip_bfloat16, int32_t); break;
-    case 5: ADAM(__hip_bfloat16, int64_t); break;
-    default: CUEMBED_C_API_BAD_TYPE();
-  }
-#undef ADAM
+  const bool known = cuembed_c_api::DispatchTypes<true>(elem_type, index_type, [&](auto elem, auto index) {
+    using E = typename decltype(elem)::type;
+    using I = typename decltype(index)::type;
+    AdamGrouped<E, I>(tables_host, tables_device, exp_avg_host, exp_avg_device, exp_avg_sq_host, exp_avg_sq_device,
+                      num_tables, row_base, embed_width, ids, rows, total_entries, o, stream);
+  });
+  if (!known) CUEMBED_C_API_BAD_TYPE();
 }
 
 }  // extern "C"

@@ -55,17 +55,13 @@ void cuembed_sparse_row_update_grouped_stochastic(const void* const* tables_host
   cuembed::SparseUpdateOptions o = cuembed_c_api::UpdateOptions(rule, total_entries, 1, num_rows, count_word,
                                                                 count_word_is_64, last_id, lr, lr_device, eps);
   cuembed_c_api::FillStochasticRounding(o, 0, step, step_device);   // (the seeds are the tables': seeds_device)
-#define UPD(E, I)                                                                                                  \
-  UpdateGrouped<E, I>(tables_host, tables_device, state_host, state_device, num_tables, row_base, embed_width, ids, \
-                      rows, total_entries, o, seeds_device, stream)
-  switch ((elem_type << 1) | index_type) {
-    case 2: UPD(__half, int32_t); break;
-    case 3: UPD(__half, int64_t); break;
-    case 4: UPD(__hip_bfloat16, int32_t); break;
-    case 5: UPD(__hip_bfloat16, int64_t); break;
-    default: CUEMBED_C_API_BAD_TYPE();   // (float tables have no rounding to randomise)
-  }
-#undef UPD
+  const bool known = cuembed_c_api::DispatchTypes<false>(elem_type, index_type, [&](auto elem, auto index) {
+    using E = typename decltype(elem)::type;
+    using I = typename decltype(index)::type;
+    UpdateGrouped<E, I>(tables_host, tables_device, state_host, state_device, num_tables, row_base, embed_width, ids, rows,
+                        total_entries, o, seeds_device, stream);
+  });
+  if (!known) CUEMBED_C_API_BAD_TYPE();   // (float tables have no rounding to randomise)
 }
 
 void cuembed_sparse_row_adam_grouped_stochastic(const void* const* tables_host, const void* const* tables_device,
@@ -84,17 +80,13 @@ void cuembed_sparse_row_adam_grouped_stochastic(const void* const* tables_host, 
       rule, total_entries, 1, num_rows, count_word, count_word_is_64, last_id, lr, lr_device, bias_factor,
       bias_factor_device, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay);
   cuembed_c_api::FillStochasticRounding(o, 0, step, step_device);
-#define ADAM(E, I)                                                                                                \
-  AdamGrouped<E, I>(tables_host, tables_device, exp_avg_host, exp_avg_device, exp_avg_sq_host, exp_avg_sq_device, \
-                    num_tables, row_base, embed_width, ids, rows, total_entries, o, seeds_device, stream)
-  switch ((elem_type << 1) | index_type) {
-    case 2: ADAM(__half, int32_t); break;
-    case 3: ADAM(__half, int64_t); break;
-    case 4: ADAM(__hip_bfloat16, int32_t); break;
-    case 5: ADAM(__hip_bfloat16, int64_t); break;
-    default: CUEMBED_C_API_BAD_TYPE();
-  }
-#undef ADAM
+  const bool known = cuembed_c_api::DispatchTypes<false>(elem_type, index_type, [&](auto elem, auto index) {
+    using E = typename decltype(elem)::type;
+    using I = typename decltype(index)::type;
+    AdamGrouped<E, I>(tables_host, tables_device, exp_avg_host, exp_avg_device, exp_avg_sq_host, exp_avg_sq_device,
+                      num_tables, row_base, embed_width, ids, rows, total_entries, o, seeds_device, stream);
+  });
+  if (!known) CUEMBED_C_API_BAD_TYPE();
 }
 
 }  // extern "C"

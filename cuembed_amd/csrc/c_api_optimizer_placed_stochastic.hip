@@ -16,18 +16,14 @@ void cuembed_sparse_row_update_placed_stochastic(void* table, int elem_type, int
                                                                 counts_are_int64, last_id, lr, lr_device, eps);
   cuembed_c_api::FillStochasticRounding(o, seed, step, step_device);
   // (the named step alone: without names the call is cuembed_sparse_row_update_stochastic's, and aborts here)
-#define UPD(E, I)                                                                                                  \
-  cuembed::detail::SparseRowUpdateNamed<E, I, cuembed::UpdateRoundings::kStochasticOnly>(                          \
-      static_cast<E*>(table), state, embed_width, static_cast<const I*>(ids), static_cast<const E*>(rows), o,      \
-      cuembed_c_api::Stream(stream), state_ids, row_names)
-  switch ((elem_type << 1) | index_type) {
-    case 2: UPD(__half, int32_t); break;
-    case 3: UPD(__half, int64_t); break;
-    case 4: UPD(__hip_bfloat16, int32_t); break;
-    case 5: UPD(__hip_bfloat16, int64_t); break;
-    default: CUEMBED_C_API_BAD_TYPE();   // (float tables have no rounding to randomise)
-  }
-#undef UPD
+  const bool known = cuembed_c_api::DispatchTypes<false>(elem_type, index_type, [&](auto elem, auto index) {
+    using E = typename decltype(elem)::type;
+    using I = typename decltype(index)::type;
+    cuembed::detail::SparseRowUpdateNamed<E, I, cuembed::UpdateRoundings::kStochasticOnly>(
+        static_cast<E*>(table), state, embed_width, static_cast<const I*>(ids), static_cast<const E*>(rows), o,
+        cuembed_c_api::Stream(stream), state_ids, row_names);
+  });
+  if (!known) CUEMBED_C_API_BAD_TYPE();   // (float tables have no rounding to randomise)
 }
 
 }  // extern "C"

@@ -14,16 +14,12 @@ void cuembed_sparse_row_update_stochastic(void* table, int elem_type, int embed_
   cuembed::SparseUpdateOptions o = cuembed_c_api::UpdateOptions(rule, piece_rows, pieces, num_rows, counts,
                                                                 counts_are_int64, last_id, lr, lr_device, eps);
   cuembed_c_api::FillStochasticRounding(o, seed, step, step_device);
-#define UPD(E, I) \
-  cuembed_c_api::Update<E, I, cuembed::UpdateRoundings::kStochasticOnly>(table, state, embed_width, ids, rows, o, stream)
-  switch ((elem_type << 1) | index_type) {
-    case 2: UPD(__half, int32_t); break;
-    case 3: UPD(__half, int64_t); break;
-    case 4: UPD(__hip_bfloat16, int32_t); break;
-    case 5: UPD(__hip_bfloat16, int64_t); break;
-    default: CUEMBED_C_API_BAD_TYPE();   // (float tables have no rounding to randomise)
-  }
-#undef UPD
+  const bool known = cuembed_c_api::DispatchTypes<false>(elem_type, index_type, [&](auto elem, auto index) {
+    using E = typename decltype(elem)::type;
+    using I = typename decltype(index)::type;
+    cuembed_c_api::Update<E, I, cuembed::UpdateRoundings::kStochasticOnly>(table, state, embed_width, ids, rows, o, stream);
+  });
+  if (!known) CUEMBED_C_API_BAD_TYPE();   // (float tables have no rounding to randomise)
 }
 
 void cuembed_stochastic_rounding_words(uint64_t seed, uint64_t step, int64_t row, uint32_t column_group, uint32_t* out) {

@@ -41,12 +41,6 @@ namespace cuembed {
 
 namespace detail {
 
-//! Entries in flight of the grouped kernels whose lanes hold one slice per entry (WalkNamedRows' kEntries): those of
-//! their single-table counterparts.  No instantiation spills with them (profiles/sparse_update_grouped_kernel_resources.txt).
-constexpr int kGroupedEntriesInFlight = 2;
-//! The same for the stochastic grouped kernels (profiles/sparse_update_grouped_stochastic_kernel_resources.txt).
-constexpr int kGroupedStochasticEntriesInFlight = 2;
-
 //! The checks both grouped steps share, and the options of the one piece they walk: (false: nothing to do).
 inline bool CheckGroupedStep(SparseStepOptions& o, const void* tables_host, const void* tables_device,
                              const int num_tables, const int64_t* row_base_device, const void* ids, const void* rows,
@@ -69,6 +63,20 @@ inline const float* GroupStateBits(const float* const* state_host, const int num
   if (!per_element) return nullptr;
   CUEMBED_ASSERT(state_host != nullptr);
   return static_cast<const float*>(GroupAlignmentBits(reinterpret_cast<const void* const*>(state_host), num_tables));
+}
+
+//! The operands of a grouped step: the pointer arrays in device memory, and what the host copies say about alignment
+//! (GroupAlignmentBits of the tables, GroupStateBits of the state tensors).
+template <typename ElemT>
+inline StepOperands GroupedOperands(const void* table_bits, ElemT* const* tables_device, const float* state_bits,
+                                    float* const* state_device, const float* state2_bits, float* const* state2_device,
+                                    const int num_tables, const int64_t* row_base_device, const uint64_t* seeds_device) {
+  StepOperands p;
+  p.table = table_bits, p.state = state_bits, p.state2 = state2_bits;
+  p.grouped = {reinterpret_cast<const void* const*>(tables_device), const_cast<const float* const*>(state_device),
+               const_cast<const float* const*>(state2_device), row_base_device, num_tables};
+  p.seeds = seeds_device;
+  return p;
 }
 
 }  // namespace detail
@@ -119,7 +127,6 @@ void SparseRowUpdateGrouped(const ElemT* const* tables_host,
                 "SparseRowUpdateGrouped: tables must be float, __half or __hip_bfloat16");
   static_assert(std::is_same<IndexT, int32_t>::value || std::is_same<IndexT, int64_t>::value,
                 "SparseRowUpdateGrouped: ids must be int32_t or int64_t");
-  using DevT = detail::DeviceElemT<ElemT>;
   SparseUpdateOptions o = options;
   const bool work = detail::CheckGroupedStep(o, tables_host, tables_device, num_tables, row_base_device, ids, rows,
                                              total_entries, seeds_device);
@@ -128,44 +135,10 @@ void SparseRowUpdateGrouped(const ElemT* const* tables_host,
   CUEMBED_ASSERT(o.stochastic_rounding || kRoundings != UpdateRoundings::kStochasticOnly);
   if (!work) return;
   const void* table_bits = detail::GroupAlignmentBits(reinterpret_cast<const void* const*>(tables_host), num_tables);
-  const bool per_element = o.rule == UpdateRule::kAdagrad;
-  const int bytes = detail::UpdateLaneBytes<DevT>(embed_width, table_bits, rows,
-                                                  detail::GroupStateBits(state_host, num_tables, per_element), per_element);
-  const detail::UpdateCounts counts = detail::CountsOf(o);
-  const detail::GroupedTables<true> grouped = {reinterpret_cast<const void* const*>(tables_device),
-                                               const_cast<const float* const*>(state_device), nullptr, row_base_device,
-                                               num_tables};
-  const size_t lds = sizeof(int64_t) * detail::GroupedLdsWords(num_tables, o.rule == UpdateRule::kSgd ? 0 : 1,
-                                                              o.stochastic_rounding);
-  const DevT* g = reinterpret_cast<const DevT*>(rows);
-  detail::DispatchUpdate<DevT, kRoundings>(
-      bytes, embed_width, o, [&](auto stochastic, auto n, auto chunks, const detail::UpdateShape& s) {
-        const auto with_rule = [&](auto rule) {
-          constexpr int kChunks = decltype(chunks)::value;
-          if constexpr (decltype(stochastic)::value) {
-            const detail::GroupedSeededTables seeded = {grouped, seeds_device};
-            detail::SparseRowUpdateGroupedStochasticKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value,
-                                                           kChunks,
-                                                           kChunks == 1 ? detail::kGroupedStochasticEntriesInFlight : 1>
-                <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), lds, stream>>>(
-                    ids, g, seeded, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr,
-                    o.lr_device, o.eps, detail::RoundingOf<true>(o));
-          } else {
-            detail::SparseRowUpdateGroupedKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, kChunks,
-                                                 kChunks == 1 ? detail::kGroupedEntriesInFlight : 1>
-                <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), lds, stream>>>(
-                    ids, g, grouped, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr,
-                    o.lr_device, o.eps);
-          }
-        };
-        switch (o.rule) {
-          case UpdateRule::kSgd: return with_rule(std::integral_constant<UpdateRule, UpdateRule::kSgd>());
-          case UpdateRule::kAdagrad: return with_rule(std::integral_constant<UpdateRule, UpdateRule::kAdagrad>());
-          case UpdateRule::kRowwiseAdagrad:
-            return with_rule(std::integral_constant<UpdateRule, UpdateRule::kRowwiseAdagrad>());
-        }
-        CUEMBED_ASSERT(false && "unknown update rule");
-      });
+  const float* state_bits = detail::GroupStateBits(state_host, num_tables, o.rule == UpdateRule::kAdagrad);
+  const detail::StepOperands p = detail::GroupedOperands(table_bits, tables_device, state_bits, state_device, nullptr,
+                                                         nullptr, num_tables, row_base_device, seeds_device);
+  detail::LaunchSparseRowUpdate<detail::StepVariant::kGrouped, kRoundings>(p, embed_width, ids, rows, o, stream);
 }
 
 /**
@@ -201,50 +174,21 @@ void SparseRowAdamGrouped(const ElemT* const* tables_host,
                 "SparseRowAdamGrouped: tables must be float, __half or __hip_bfloat16");
   static_assert(std::is_same<IndexT, int32_t>::value || std::is_same<IndexT, int64_t>::value,
                 "SparseRowAdamGrouped: ids must be int32_t or int64_t");
-  using DevT = detail::DeviceElemT<ElemT>;
   SparseAdamOptions o = options;
   const bool work = detail::CheckGroupedStep(o, tables_host, tables_device, num_tables, row_base_device, ids, rows,
                                              total_entries, seeds_device);
   CUEMBED_ASSERT(!o.stochastic_rounding || (detail::kCanRoundStochastically<ElemT, kRoundings>));
   CUEMBED_ASSERT(o.stochastic_rounding || kRoundings != UpdateRoundings::kStochasticOnly);
-  CUEMBED_ASSERT(o.beta1 >= 0.f && o.beta1 < 1.f && o.beta2 >= 0.f && o.beta2 < 1.f);
-  CUEMBED_ASSERT(o.eps >= 0.f && o.weight_decay >= 0.f);
+  detail::CheckAdamOptions(o);
   CUEMBED_ASSERT(exp_avg_device != nullptr && exp_avg_sq_device != nullptr);
   if (!work) return;
   const void* table_bits = detail::GroupAlignmentBits(reinterpret_cast<const void* const*>(tables_host), num_tables);
-  const int bytes = detail::UpdateLaneBytes<DevT>(
-      embed_width, table_bits, rows, detail::GroupStateBits(exp_avg_host, num_tables, true), true,
-      detail::GroupStateBits(exp_avg_sq_host, num_tables, o.rule == AdamRule::kAdam));
-  const detail::UpdateCounts counts = detail::CountsOf(o);
-  const detail::AdamScalars h = {o.beta1, o.one_minus_beta1, o.beta2, o.one_minus_beta2, o.eps, o.weight_decay};
-  const detail::GroupedTables<true> grouped = {reinterpret_cast<const void* const*>(tables_device),
-                                               const_cast<const float* const*>(exp_avg_device),
-                                               const_cast<const float* const*>(exp_avg_sq_device), row_base_device,
-                                               num_tables};
-  const size_t lds = sizeof(int64_t) * detail::GroupedLdsWords(num_tables, 2, o.stochastic_rounding);
-  const DevT* g = reinterpret_cast<const DevT*>(rows);
-  detail::DispatchUpdate<DevT, kRoundings>(
-      bytes, embed_width, o, [&](auto stochastic, auto n, auto chunks, const detail::UpdateShape& s) {
-        const auto with_rule = [&](auto rule) {
-          constexpr int kChunks = decltype(chunks)::value;
-          if constexpr (decltype(stochastic)::value) {
-            const detail::GroupedSeededTables seeded = {grouped, seeds_device};
-            detail::SparseRowAdamGroupedStochasticKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, kChunks,
-                                                         kChunks == 1 ? detail::kGroupedStochasticEntriesInFlight : 1>
-                <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), lds, stream>>>(
-                    ids, g, seeded, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr,
-                    o.lr_device, o.bias_factor, o.bias_factor_device, h, detail::RoundingOf<true>(o));
-          } else {
-            detail::SparseRowAdamGroupedKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, kChunks,
-                                               kChunks == 1 ? detail::kGroupedEntriesInFlight : 1>
-                <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), lds, stream>>>(
-                    ids, g, grouped, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr,
-                    o.lr_device, o.bias_factor, o.bias_factor_device, h);
-          }
-        };
-        if (o.rule == AdamRule::kAdam) with_rule(std::integral_constant<AdamRule, AdamRule::kAdam>());
-        else with_rule(std::integral_constant<AdamRule, AdamRule::kRowwiseAdam>());
-      });
+  const float* exp_avg_bits = detail::GroupStateBits(exp_avg_host, num_tables, true);
+  const float* exp_avg_sq_bits = detail::GroupStateBits(exp_avg_sq_host, num_tables, o.rule == AdamRule::kAdam);
+  const detail::StepOperands p =
+      detail::GroupedOperands(table_bits, tables_device, exp_avg_bits, exp_avg_device, exp_avg_sq_bits, exp_avg_sq_device,
+                              num_tables, row_base_device, seeds_device);
+  detail::LaunchSparseRowAdam<detail::StepVariant::kGrouped, kRoundings>(p, embed_width, ids, rows, o, stream);
 }
 
 }  // namespace cuembed

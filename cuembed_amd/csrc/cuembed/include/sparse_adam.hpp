@@ -33,6 +33,80 @@ struct SparseAdamOptions : SparseStepOptions {
   float weight_decay = 0.f;                   //!< decoupled (AdamW): w <- w - (lr * weight_decay) * w on the named rows; 0: off
 };
 
+namespace detail {
+
+//! The checks of the hyper-parameters, and of the moments of a single-table step that has work.
+inline void CheckAdamOptions(const SparseAdamOptions& options) {
+  CUEMBED_ASSERT(options.beta1 >= 0.f && options.beta1 < 1.f && options.beta2 >= 0.f && options.beta2 < 1.f);
+  CUEMBED_ASSERT(options.eps >= 0.f && options.weight_decay >= 0.f);
+}
+
+inline void CheckMoments(const float* exp_avg, const float* exp_avg_sq) {
+  CUEMBED_ASSERT(exp_avg != nullptr && exp_avg_sq != nullptr);
+  CUEMBED_ASSERT(reinterpret_cast<uintptr_t>(exp_avg_sq) % 4 == 0);
+}
+
+//! From options.rule to the instantiation: calls with_rule(rule) with the rule as an integral constant.
+template <typename WithRuleT>
+inline void DispatchRule(const AdamRule rule, const WithRuleT& with_rule) {
+  switch (rule) {
+    case AdamRule::kAdam: return with_rule(std::integral_constant<AdamRule, AdamRule::kAdam>());
+    case AdamRule::kRowwiseAdam: return with_rule(std::integral_constant<AdamRule, AdamRule::kRowwiseAdam>());
+  }
+  CUEMBED_ASSERT(false && "unknown Adam rule");
+}
+
+//! The one launch path of Adam / row-wise Adam, for every variant (as LaunchSparseRowUpdate; p.state = exp_avg,
+//! p.state2 = exp_avg_sq): lane bytes, counts, scalars, dispatch and the launch.
+template <StepVariant kVariant, UpdateRoundings kRoundings, typename ElemT, typename IndexT>
+void LaunchSparseRowAdam(const StepOperands& p, const int embed_width, const IndexT* ids, const ElemT* rows,
+                         const SparseAdamOptions& o, const hipStream_t stream) {
+  using DevT = DeviceElemT<ElemT>;
+  const int bytes = UpdateLaneBytes<DevT>(embed_width, p.table, rows, p.state, true,
+                                          o.rule == AdamRule::kAdam ? p.state2 : nullptr);
+  const UpdateCounts counts = CountsOf(o);
+  const AdamScalars h = {o.beta1, o.one_minus_beta1, o.beta2, o.one_minus_beta2, o.eps, o.weight_decay};
+  DevT* t = reinterpret_cast<DevT*>(const_cast<void*>(p.table));
+  float* m = const_cast<float*>(p.state);
+  float* v = const_cast<float*>(p.state2);
+  const DevT* g = reinterpret_cast<const DevT*>(rows);
+  DispatchUpdate<DevT, kRoundings>(bytes, embed_width, o, [&](auto stochastic, auto n, auto chunks, const UpdateShape& s) {
+    DispatchRule(o.rule, [&](auto rule) {
+      constexpr bool kStochastic = decltype(stochastic)::value;
+      constexpr int N = decltype(n)::value, kChunks = decltype(chunks)::value;
+      constexpr AdamRule kRule = decltype(rule)::value;
+      constexpr int kInFlight = kStepEntriesInFlight<kVariant, kStochastic, kRule, N, kChunks>;
+      const dim3 grid(s.grid), block(kUpdateBlockThreads);
+      if constexpr (kVariant == StepVariant::kPlain) {
+        SparseRowAdamKernel<DevT, IndexT, N, kRule, kChunks, kInFlight, kStochastic><<<grid, block, 0, stream>>>(
+            ids, g, t, m, v, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr, o.lr_device,
+            o.bias_factor, o.bias_factor_device, h, RoundingOf<kStochastic>(o));
+      } else if constexpr (kVariant == StepVariant::kPlaced) {
+        SparseRowAdamPlacedKernel<DevT, IndexT, N, kRule, kChunks, kInFlight><<<grid, block, 0, stream>>>(
+            ids, p.state_ids, p.state2_ids, g, t, m, v, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces,
+            counts, o.lr, o.lr_device, o.bias_factor, o.bias_factor_device, h);
+      } else if constexpr (kVariant == StepVariant::kNamed) {
+        SparseRowAdamNamedKernel<DevT, IndexT, N, kRule, kChunks, kInFlight><<<grid, block, 0, stream>>>(
+            ids, p.state_ids, p.state2_ids, p.row_names, g, t, m, v, embed_width, s.lanes_per_row, s.group, o.piece_rows,
+            o.pieces, counts, o.lr, o.lr_device, o.bias_factor, o.bias_factor_device, h, RoundingOf<true>(o));
+      } else {
+        const size_t lds = sizeof(int64_t) * GroupedLdsWords(p.grouped.num_tables, 2, kStochastic);
+        if constexpr (kStochastic) {
+          SparseRowAdamGroupedStochasticKernel<DevT, IndexT, N, kRule, kChunks, kInFlight><<<grid, block, lds, stream>>>(
+              ids, g, GroupedSeededTables{p.grouped, p.seeds}, embed_width, s.lanes_per_row, s.group, o.piece_rows,
+              o.pieces, counts, o.lr, o.lr_device, o.bias_factor, o.bias_factor_device, h, RoundingOf<true>(o));
+        } else {
+          SparseRowAdamGroupedKernel<DevT, IndexT, N, kRule, kChunks, kInFlight><<<grid, block, lds, stream>>>(
+              ids, g, p.grouped, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr, o.lr_device,
+              o.bias_factor, o.bias_factor_device, h);
+        }
+      }
+    });
+  });
+}
+
+}  // namespace detail
+
 /**
  * @brief Sparse Adam step: for every valid entry k, table[ids[k], :] and the moments of row ids[k] are updated in place
  * from rows[k, :] by options.rule (AdamRule).  Rows that no valid entry names are neither read nor written: their
@@ -69,44 +143,14 @@ void SparseRowAdam(ElemT* table,
                 "SparseRowAdam: tables must be float, __half or __hip_bfloat16");
   static_assert(std::is_same<IndexT, int32_t>::value || std::is_same<IndexT, int64_t>::value,
                 "SparseRowAdam: ids must be int32_t or int64_t");
-  using DevT = detail::DeviceElemT<ElemT>;
   detail::CheckCountSource(options);
-  CUEMBED_ASSERT(options.beta1 >= 0.f && options.beta1 < 1.f && options.beta2 >= 0.f && options.beta2 < 1.f);
-  CUEMBED_ASSERT(options.eps >= 0.f && options.weight_decay >= 0.f);
+  detail::CheckAdamOptions(options);
   if (!detail::CheckRoundingAndWork<ElemT, kRoundings>(options, table, ids, rows)) return;
-  CUEMBED_ASSERT(exp_avg != nullptr && exp_avg_sq != nullptr);
-  CUEMBED_ASSERT(reinterpret_cast<uintptr_t>(exp_avg_sq) % 4 == 0);
-  const int bytes = detail::UpdateLaneBytes<DevT>(embed_width, table, rows, exp_avg, true,
-                                                  options.rule == AdamRule::kAdam ? exp_avg_sq : nullptr);
-  const detail::UpdateCounts counts = detail::CountsOf(options);
-  const detail::AdamScalars h = {options.beta1, options.one_minus_beta1, options.beta2, options.one_minus_beta2,
-                                 options.eps, options.weight_decay};
-  DevT* t = reinterpret_cast<DevT*>(table);
-  const DevT* g = reinterpret_cast<const DevT*>(rows);
-  detail::DispatchUpdate<DevT, kRoundings>(
-      bytes, embed_width, options, [&](auto stochastic, auto n, auto chunks, const detail::UpdateShape& s) {
-        const auto with_rule = [&](auto rule) {
-          // entries in flight: two when a lane holds one slice per entry (WalkNamedRows)
-          constexpr int kChunks = decltype(chunks)::value;
-          detail::SparseRowAdamKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, kChunks,
-                                      kChunks == 1 ? 2 : 1, decltype(stochastic)::value>
-              <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), 0, stream>>>(
-                  ids, g, t, exp_avg, exp_avg_sq, embed_width, s.lanes_per_row, s.group, options.piece_rows,
-                  options.pieces, counts, options.lr, options.lr_device, options.bias_factor, options.bias_factor_device,
-                  h, detail::RoundingOf<decltype(stochastic)::value>(options));
-        };
-        switch (options.rule) {
-          case AdamRule::kAdam: return with_rule(std::integral_constant<AdamRule, AdamRule::kAdam>());
-          case AdamRule::kRowwiseAdam: return with_rule(std::integral_constant<AdamRule, AdamRule::kRowwiseAdam>());
-        }
-        CUEMBED_ASSERT(false && "unknown Adam rule");
-      });
+  detail::CheckMoments(exp_avg, exp_avg_sq);
+  detail::StepOperands p;
+  p.table = table, p.state = exp_avg, p.state2 = exp_avg_sq;
+  detail::LaunchSparseRowAdam<detail::StepVariant::kPlain, kRoundings>(p, embed_width, ids, rows, options, stream);
 }
-
-namespace detail {
-//! Entries in flight of the placed Adam kernels whose lanes hold one slice per entry (WalkNamedRows' kEntries).
-constexpr int kAdamPlacedEntriesInFlight = 2;
-}  // namespace detail
 
 /**
  * @brief The same step with the moments in places of their own: entry k updates table[ids[k], :] as above, but reads
@@ -138,84 +182,38 @@ void SparseRowAdam(ElemT* table,
   if (exp_avg_ids == nullptr && exp_avg_sq_ids == nullptr)
     return SparseRowAdam<ElemT, IndexT, kRoundings>(table, exp_avg, exp_avg_sq, embed_width, ids, rows, options, stream);
   static_assert(kRoundings != UpdateRoundings::kStochasticOnly, "placed moments are updated with round to nearest");
-  using DevT = detail::DeviceElemT<ElemT>;
   detail::CheckCountSource(options);
-  CUEMBED_ASSERT(options.beta1 >= 0.f && options.beta1 < 1.f && options.beta2 >= 0.f && options.beta2 < 1.f);
-  CUEMBED_ASSERT(options.eps >= 0.f && options.weight_decay >= 0.f);
+  detail::CheckAdamOptions(options);
   CUEMBED_ASSERT(exp_avg_ids != nullptr && exp_avg_sq_ids != nullptr);
   CUEMBED_ASSERT(!options.stochastic_rounding);
   if (!detail::CheckRoundingAndWork<ElemT, UpdateRoundings::kNearestOnly>(options, table, ids, rows)) return;
-  CUEMBED_ASSERT(exp_avg != nullptr && exp_avg_sq != nullptr);
-  CUEMBED_ASSERT(reinterpret_cast<uintptr_t>(exp_avg_sq) % 4 == 0);
-  const int bytes = detail::UpdateLaneBytes<DevT>(embed_width, table, rows, exp_avg, true,
-                                                  options.rule == AdamRule::kAdam ? exp_avg_sq : nullptr);
-  const detail::UpdateCounts counts = detail::CountsOf(options);
-  const detail::AdamScalars h = {options.beta1, options.one_minus_beta1, options.beta2, options.one_minus_beta2,
-                                 options.eps, options.weight_decay};
-  DevT* t = reinterpret_cast<DevT*>(table);
-  const DevT* g = reinterpret_cast<const DevT*>(rows);
-  detail::DispatchUpdate<DevT, UpdateRoundings::kNearestOnly>(
-      bytes, embed_width, options, [&](auto, auto n, auto chunks, const detail::UpdateShape& s) {
-        const auto with_rule = [&](auto rule) {
-          constexpr int kChunks = decltype(chunks)::value;
-          detail::SparseRowAdamPlacedKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, kChunks,
-                                            kChunks == 1 ? detail::kAdamPlacedEntriesInFlight : 1>
-              <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), 0, stream>>>(
-                  ids, exp_avg_ids, exp_avg_sq_ids, g, t, exp_avg, exp_avg_sq, embed_width, s.lanes_per_row, s.group,
-                  options.piece_rows, options.pieces, counts, options.lr, options.lr_device, options.bias_factor,
-                  options.bias_factor_device, h);
-        };
-        if (options.rule == AdamRule::kAdam) with_rule(std::integral_constant<AdamRule, AdamRule::kAdam>());
-        else with_rule(std::integral_constant<AdamRule, AdamRule::kRowwiseAdam>());
-      });
+  detail::CheckMoments(exp_avg, exp_avg_sq);
+  detail::StepOperands p;
+  p.table = table, p.state = exp_avg, p.state2 = exp_avg_sq, p.state_ids = exp_avg_ids, p.state2_ids = exp_avg_sq_ids;
+  detail::LaunchSparseRowAdam<detail::StepVariant::kPlaced, UpdateRoundings::kNearestOnly>(p, embed_width, ids, rows,
+                                                                                            options, stream);
 }
 
 namespace detail {
-//! Entries in flight of the named (placed, stochastic) Adam kernels whose lanes hold one slice per entry: those of
-//! their placed siblings (profiles/sparse_update_placed_stochastic_kernel_resources.txt).
-template <AdamRule kRule, int N>
-constexpr int kAdamNamedEntriesInFlight = kAdamPlacedEntriesInFlight;
-
 //! The named step itself (row_names != nullptr): the body of the overload below, and what a translation unit that wants
 //! the named kernels alone calls.
 template <typename ElemT, typename IndexT, UpdateRoundings kRoundings>
 void SparseRowAdamNamed(ElemT* table, float* exp_avg, float* exp_avg_sq, const int embed_width, const IndexT* ids,
                         const ElemT* rows, const SparseAdamOptions& options, const hipStream_t stream,
                         const int64_t* exp_avg_ids, const int64_t* exp_avg_sq_ids, const int64_t* row_names) {
-  using DevT = DeviceElemT<ElemT>;
   CUEMBED_ASSERT(row_names != nullptr);
   CheckCountSource(options);
-  CUEMBED_ASSERT(options.beta1 >= 0.f && options.beta1 < 1.f && options.beta2 >= 0.f && options.beta2 < 1.f);
-  CUEMBED_ASSERT(options.eps >= 0.f && options.weight_decay >= 0.f);
+  CheckAdamOptions(options);
   CUEMBED_ASSERT(exp_avg_ids != nullptr && exp_avg_sq_ids != nullptr);
   CUEMBED_ASSERT(options.stochastic_rounding);
   CUEMBED_ASSERT(sizeof(ElemT) == 2);
   if (!CheckRoundingAndWork<ElemT, kRoundings>(options, table, ids, rows)) return;
-  CUEMBED_ASSERT(exp_avg != nullptr && exp_avg_sq != nullptr);
-  CUEMBED_ASSERT(reinterpret_cast<uintptr_t>(exp_avg_sq) % 4 == 0);
+  CheckMoments(exp_avg, exp_avg_sq);
   if constexpr (kCanRoundStochastically<ElemT, kRoundings>) {
-    const int bytes = UpdateLaneBytes<DevT>(embed_width, table, rows, exp_avg, true,
-                                            options.rule == AdamRule::kAdam ? exp_avg_sq : nullptr);
-    const UpdateCounts counts = CountsOf(options);
-    const AdamScalars h = {options.beta1, options.one_minus_beta1, options.beta2, options.one_minus_beta2,
-                           options.eps, options.weight_decay};
-    DevT* t = reinterpret_cast<DevT*>(table);
-    const DevT* g = reinterpret_cast<const DevT*>(rows);
-    DispatchUpdate<DevT, UpdateRoundings::kStochasticOnly>(
-        bytes, embed_width, options, [&](auto, auto n, auto chunks, const UpdateShape& s) {
-          const auto with_rule = [&](auto rule) {
-            constexpr int kChunks = decltype(chunks)::value;
-            constexpr int kInFlight =
-                kChunks == 1 ? kAdamNamedEntriesInFlight<decltype(rule)::value, decltype(n)::value> : 1;
-            SparseRowAdamNamedKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, kChunks, kInFlight>
-                <<<dim3(s.grid), dim3(kUpdateBlockThreads), 0, stream>>>(
-                    ids, exp_avg_ids, exp_avg_sq_ids, row_names, g, t, exp_avg, exp_avg_sq, embed_width, s.lanes_per_row,
-                    s.group, options.piece_rows, options.pieces, counts, options.lr, options.lr_device,
-                    options.bias_factor, options.bias_factor_device, h, RoundingOf<true>(options));
-          };
-          if (options.rule == AdamRule::kAdam) with_rule(std::integral_constant<AdamRule, AdamRule::kAdam>());
-          else with_rule(std::integral_constant<AdamRule, AdamRule::kRowwiseAdam>());
-        });
+    StepOperands p;
+    p.table = table, p.state = exp_avg, p.state2 = exp_avg_sq, p.state_ids = exp_avg_ids, p.state2_ids = exp_avg_sq_ids;
+    p.row_names = row_names;
+    LaunchSparseRowAdam<StepVariant::kNamed, UpdateRoundings::kStochasticOnly>(p, embed_width, ids, rows, options, stream);
   }
 }
 }  // namespace detail

@@ -173,6 +173,96 @@ inline void DispatchUpdate(const int bytes, const int width, const SparseStepOpt
   if constexpr (kRoundings != UpdateRoundings::kStochasticOnly) with_rounding(std::false_type());
 }
 
+//! The variants of a step, by what the caller supplied beyond ids and rows: nothing; ids of their own for the state
+//! tensors (round to nearest); those and the table rows that name the bits of stochastic rounding; or a group of
+//! separate tables (grouped_sparse_update.hpp), whose stochastic kernels are a fifth variant with a seed per table.
+enum class StepVariant { kPlain, kPlaced, kNamed, kGrouped };
+
+//! What the kernels of a step read and write besides ids and rows; a variant reads its own fields.
+struct StepOperands {
+  //! The tensors of a single-table step (state2: Adam's second moment).  Of a grouped step, what decides the lane bytes
+  //! alone: the bases of each tensor list OR-ed into one address (GroupAlignmentBits), nullptr where no state moves in
+  //! the lanes of the weights.
+  const void* table = nullptr;
+  const float* state = nullptr;
+  const float* state2 = nullptr;
+  const int64_t* state_ids = nullptr;    //!< kPlaced, kNamed: where entry k keeps its state ...
+  const int64_t* state2_ids = nullptr;   //!< ... and Adam's second moment
+  const int64_t* row_names = nullptr;    //!< kNamed: the table row of entry k
+  GroupedTables<true> grouped = {};      //!< kGrouped: the pointer arrays in device memory ...
+  const uint64_t* seeds = nullptr;       //!< ... and, with stochastic rounding, a seed per table
+};
+
+//! Entries in flight per lane group (WalkNamedRows' kEntries) of the kernel that a variant launches for (rounding, rule,
+//! N, kChunks): two when a lane holds one slice per entry, else one.  Every variant takes what its plain sibling takes:
+//! the placed Adam kernels, the named ones (profiles/sparse_update_placed_stochastic_kernel_resources.txt) and the
+//! grouped ones, of which no instantiation spills with two (profiles/sparse_update_grouped_kernel_resources.txt,
+//! profiles/sparse_update_grouped_stochastic_kernel_resources.txt).  A specialisation on (variant, rounding, rule, N) is
+//! where a fallback to one would go.  (SparseRowUpdateKernel and its placed and named siblings take no such parameter:
+//! they hold the same answer themselves.)
+template <StepVariant kVariant, bool kStochastic, auto kRule, int N, int kChunks>
+constexpr int kStepEntriesInFlight = kChunks == 1 ? 2 : 1;
+
+//! From options.rule to the instantiation: calls with_rule(rule) with the rule as an integral constant.
+template <typename WithRuleT>
+inline void DispatchRule(const UpdateRule rule, const WithRuleT& with_rule) {
+  switch (rule) {
+    case UpdateRule::kSgd: return with_rule(std::integral_constant<UpdateRule, UpdateRule::kSgd>());
+    case UpdateRule::kAdagrad: return with_rule(std::integral_constant<UpdateRule, UpdateRule::kAdagrad>());
+    case UpdateRule::kRowwiseAdagrad: return with_rule(std::integral_constant<UpdateRule, UpdateRule::kRowwiseAdagrad>());
+  }
+  CUEMBED_ASSERT(false && "unknown update rule");
+}
+
+//! The one launch path of SGD / Adagrad / row-wise Adagrad, for every variant: lane bytes, counts, dispatch on rounding,
+//! lane width, slices and rule, and the launch.  The entry points below have made their checks; kRoundings is what the
+//! variant may launch of what its caller carries.
+template <StepVariant kVariant, UpdateRoundings kRoundings, typename ElemT, typename IndexT>
+void LaunchSparseRowUpdate(const StepOperands& p, const int embed_width, const IndexT* ids, const ElemT* rows,
+                           const SparseUpdateOptions& o, const hipStream_t stream) {
+  using DevT = DeviceElemT<ElemT>;
+  const int bytes = UpdateLaneBytes<DevT>(embed_width, p.table, rows, p.state, o.rule == UpdateRule::kAdagrad);
+  const UpdateCounts counts = CountsOf(o);
+  DevT* t = reinterpret_cast<DevT*>(const_cast<void*>(p.table));
+  float* state = const_cast<float*>(p.state);
+  const DevT* g = reinterpret_cast<const DevT*>(rows);
+  DispatchUpdate<DevT, kRoundings>(bytes, embed_width, o, [&](auto stochastic, auto n, auto chunks, const UpdateShape& s) {
+    DispatchRule(o.rule, [&](auto rule) {
+      constexpr bool kStochastic = decltype(stochastic)::value;
+      constexpr int N = decltype(n)::value, kChunks = decltype(chunks)::value;
+      constexpr UpdateRule kRule = decltype(rule)::value;
+      const dim3 grid(s.grid), block(kUpdateBlockThreads);
+      if constexpr (kVariant == StepVariant::kPlain) {
+        SparseRowUpdateKernel<DevT, IndexT, N, kRule, kChunks, kStochastic><<<grid, block, 0, stream>>>(
+            ids, g, t, state, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr, o.lr_device,
+            o.eps, RoundingOf<kStochastic>(o));
+      } else if constexpr (kVariant == StepVariant::kPlaced) {
+        if constexpr (kRule != UpdateRule::kSgd) {   // (SGD has no state to place: its entry point refuses it)
+          SparseRowUpdatePlacedKernel<DevT, IndexT, N, kRule, kChunks><<<grid, block, 0, stream>>>(
+              ids, p.state_ids, g, t, state, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr,
+              o.lr_device, o.eps);
+        }
+      } else if constexpr (kVariant == StepVariant::kNamed) {
+        SparseRowUpdateNamedKernel<DevT, IndexT, N, kRule, kChunks><<<grid, block, 0, stream>>>(
+            ids, p.state_ids, p.row_names, g, t, state, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces,
+            counts, o.lr, o.lr_device, o.eps, RoundingOf<true>(o));
+      } else {
+        constexpr int kInFlight = kStepEntriesInFlight<kVariant, kStochastic, kRule, N, kChunks>;
+        const size_t lds = sizeof(int64_t) * GroupedLdsWords(p.grouped.num_tables, kRule == UpdateRule::kSgd ? 0 : 1, kStochastic);
+        if constexpr (kStochastic) {
+          SparseRowUpdateGroupedStochasticKernel<DevT, IndexT, N, kRule, kChunks, kInFlight><<<grid, block, lds, stream>>>(
+              ids, g, GroupedSeededTables{p.grouped, p.seeds}, embed_width, s.lanes_per_row, s.group, o.piece_rows,
+              o.pieces, counts, o.lr, o.lr_device, o.eps, RoundingOf<true>(o));
+        } else {
+          SparseRowUpdateGroupedKernel<DevT, IndexT, N, kRule, kChunks, kInFlight><<<grid, block, lds, stream>>>(
+              ids, g, p.grouped, embed_width, s.lanes_per_row, s.group, o.piece_rows, o.pieces, counts, o.lr, o.lr_device,
+              o.eps);
+        }
+      }
+    });
+  });
+}
+
 }  // namespace detail
 
 /**
@@ -214,31 +304,12 @@ void SparseRowUpdate(ElemT* table,
                 "SparseRowUpdate: tables must be float, __half or __hip_bfloat16");
   static_assert(std::is_same<IndexT, int32_t>::value || std::is_same<IndexT, int64_t>::value,
                 "SparseRowUpdate: ids must be int32_t or int64_t");
-  using DevT = detail::DeviceElemT<ElemT>;
   detail::CheckCountSource(options);
   CUEMBED_ASSERT((options.rule == UpdateRule::kSgd) == (state == nullptr));
   if (!detail::CheckRoundingAndWork<ElemT, kRoundings>(options, table, ids, rows)) return;
-  const int bytes = detail::UpdateLaneBytes<DevT>(embed_width, table, rows, state, options.rule == UpdateRule::kAdagrad);
-  const detail::UpdateCounts counts = detail::CountsOf(options);
-  DevT* t = reinterpret_cast<DevT*>(table);
-  const DevT* g = reinterpret_cast<const DevT*>(rows);
-  detail::DispatchUpdate<DevT, kRoundings>(
-      bytes, embed_width, options, [&](auto stochastic, auto n, auto chunks, const detail::UpdateShape& s) {
-        const auto with_rule = [&](auto rule) {
-          detail::SparseRowUpdateKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, decltype(chunks)::value,
-                                        decltype(stochastic)::value>
-              <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), 0, stream>>>(
-                  ids, g, t, state, embed_width, s.lanes_per_row, s.group, options.piece_rows, options.pieces, counts,
-                  options.lr, options.lr_device, options.eps, detail::RoundingOf<decltype(stochastic)::value>(options));
-        };
-        switch (options.rule) {
-          case UpdateRule::kSgd: return with_rule(std::integral_constant<UpdateRule, UpdateRule::kSgd>());
-          case UpdateRule::kAdagrad: return with_rule(std::integral_constant<UpdateRule, UpdateRule::kAdagrad>());
-          case UpdateRule::kRowwiseAdagrad:
-            return with_rule(std::integral_constant<UpdateRule, UpdateRule::kRowwiseAdagrad>());
-        }
-        CUEMBED_ASSERT(false && "unknown update rule");
-      });
+  detail::StepOperands p;
+  p.table = table, p.state = state;
+  detail::LaunchSparseRowUpdate<detail::StepVariant::kPlain, kRoundings>(p, embed_width, ids, rows, options, stream);
 }
 
 /**
@@ -266,27 +337,14 @@ void SparseRowUpdate(ElemT* table,
   if (state_ids == nullptr)
     return SparseRowUpdate<ElemT, IndexT, kRoundings>(table, state, embed_width, ids, rows, options, stream);
   static_assert(kRoundings != UpdateRoundings::kStochasticOnly, "a placed state is updated with round to nearest");
-  using DevT = detail::DeviceElemT<ElemT>;
   detail::CheckCountSource(options);
   CUEMBED_ASSERT(options.rule != UpdateRule::kSgd && state != nullptr);
   CUEMBED_ASSERT(!options.stochastic_rounding);
   if (!detail::CheckRoundingAndWork<ElemT, UpdateRoundings::kNearestOnly>(options, table, ids, rows)) return;
-  const int bytes = detail::UpdateLaneBytes<DevT>(embed_width, table, rows, state, options.rule == UpdateRule::kAdagrad);
-  const detail::UpdateCounts counts = detail::CountsOf(options);
-  DevT* t = reinterpret_cast<DevT*>(table);
-  const DevT* g = reinterpret_cast<const DevT*>(rows);
-  detail::DispatchUpdate<DevT, UpdateRoundings::kNearestOnly>(
-      bytes, embed_width, options, [&](auto, auto n, auto chunks, const detail::UpdateShape& s) {
-        const auto with_rule = [&](auto rule) {
-          detail::SparseRowUpdatePlacedKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value,
-                                              decltype(chunks)::value>
-              <<<dim3(s.grid), dim3(detail::kUpdateBlockThreads), 0, stream>>>(
-                  ids, state_ids, g, t, state, embed_width, s.lanes_per_row, s.group, options.piece_rows, options.pieces,
-                  counts, options.lr, options.lr_device, options.eps);
-        };
-        if (options.rule == UpdateRule::kAdagrad) with_rule(std::integral_constant<UpdateRule, UpdateRule::kAdagrad>());
-        else with_rule(std::integral_constant<UpdateRule, UpdateRule::kRowwiseAdagrad>());
-      });
+  detail::StepOperands p;
+  p.table = table, p.state = state, p.state_ids = state_ids;
+  detail::LaunchSparseRowUpdate<detail::StepVariant::kPlaced, UpdateRoundings::kNearestOnly>(p, embed_width, ids, rows,
+                                                                                              options, stream);
 }
 
 namespace detail {
@@ -296,7 +354,6 @@ template <typename ElemT, typename IndexT, UpdateRoundings kRoundings>
 void SparseRowUpdateNamed(ElemT* table, float* state, const int embed_width, const IndexT* ids, const ElemT* rows,
                           const SparseUpdateOptions& options, const hipStream_t stream, const int64_t* state_ids,
                           const int64_t* row_names) {
-  using DevT = DeviceElemT<ElemT>;
   CUEMBED_ASSERT(row_names != nullptr);
   CheckCountSource(options);
   CUEMBED_ASSERT(options.stochastic_rounding);
@@ -305,26 +362,9 @@ void SparseRowUpdateNamed(ElemT* table, float* state, const int embed_width, con
   else CUEMBED_ASSERT(state != nullptr && state_ids != nullptr);
   if (!CheckRoundingAndWork<ElemT, kRoundings>(options, table, ids, rows)) return;
   if constexpr (kCanRoundStochastically<ElemT, kRoundings>) {
-    const int bytes = UpdateLaneBytes<DevT>(embed_width, table, rows, state, options.rule == UpdateRule::kAdagrad);
-    const UpdateCounts counts = CountsOf(options);
-    DevT* t = reinterpret_cast<DevT*>(table);
-    const DevT* g = reinterpret_cast<const DevT*>(rows);
-    DispatchUpdate<DevT, UpdateRoundings::kStochasticOnly>(
-        bytes, embed_width, options, [&](auto, auto n, auto chunks, const UpdateShape& s) {
-          const auto with_rule = [&](auto rule) {
-            SparseRowUpdateNamedKernel<DevT, IndexT, decltype(n)::value, decltype(rule)::value, decltype(chunks)::value>
-                <<<dim3(s.grid), dim3(kUpdateBlockThreads), 0, stream>>>(
-                    ids, state_ids, row_names, g, t, state, embed_width, s.lanes_per_row, s.group, options.piece_rows,
-                    options.pieces, counts, options.lr, options.lr_device, options.eps, RoundingOf<true>(options));
-          };
-          switch (options.rule) {
-            case UpdateRule::kSgd: return with_rule(std::integral_constant<UpdateRule, UpdateRule::kSgd>());
-            case UpdateRule::kAdagrad: return with_rule(std::integral_constant<UpdateRule, UpdateRule::kAdagrad>());
-            case UpdateRule::kRowwiseAdagrad:
-              return with_rule(std::integral_constant<UpdateRule, UpdateRule::kRowwiseAdagrad>());
-          }
-          CUEMBED_ASSERT(false && "unknown update rule");
-        });
+    StepOperands p;
+    p.table = table, p.state = state, p.state_ids = state_ids, p.row_names = row_names;
+    LaunchSparseRowUpdate<StepVariant::kNamed, UpdateRoundings::kStochasticOnly>(p, embed_width, ids, rows, options, stream);
   }
 }
 }  // namespace detail

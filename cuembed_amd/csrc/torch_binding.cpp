@@ -684,6 +684,90 @@ class CuEmbEmbeddingNode : public torch::autograd::Function<CuEmbEmbeddingNode> 
 // collectives was ~60 launches and more host time than the whole forward + backward step; here it is two ops that
 // enqueue 2 and ~13 launches without returning to Python.  Nothing is read back.
 
+// What the two single-table optimizer ops below share (GroupedStep further down is the grouped ops'): the type codes,
+// the entries and the source of their count, and the one-word device tensors.  The checks run in the order of the
+// three functions, with the op's own (the rule, the state tensors, the hyper-parameters) in between.
+struct RowStep {
+  int elem = CUEMBED_F32, idx = CUEMBED_I32, pieces = 1, words64 = 0;
+  int64_t num_rows = -1, piece_rows = 0;
+  const void* counts = nullptr;
+  const void* last_id = nullptr;
+  const float* lr_word = nullptr;
+  const float* bias_word = nullptr;
+  const int64_t* step_word = nullptr;
+};
+
+RowStep RowStepCodes(const at::Tensor& table, const at::Tensor& ids, const at::Tensor& rows) {
+  RowStep c;
+  CheckGpu(table, "table");
+  CheckGpu(ids, "ids");
+  CheckGpu(rows, "rows");
+  c.elem = ElemCode(table, "table");
+  c.idx = IndexCode(ids, "ids");
+  return c;
+}
+
+void CheckRowStepShapes(const at::Tensor& table, const at::Tensor& ids, const at::Tensor& rows) {
+  TORCH_CHECK(rows.scalar_type() == table.scalar_type(), "cuembed_pyt: rows must have the table's dtype");
+  TORCH_CHECK(table.dim() == 2 && rows.dim() == 2 && rows.size(1) == table.size(1) && ids.dim() == 1 &&
+                  rows.size(0) == ids.numel() && table.is_contiguous() && rows.is_contiguous() && ids.is_contiguous(),
+              "cuembed_pyt: table [rows, width], rows [entries, width] and ids [entries] must be contiguous and agree");
+  TORCH_CHECK((table.size(1) * table.element_size()) % 4 == 0, "cuembed_pyt: the row size must be a multiple of 4 bytes");
+  CheckRowAlignment("table / rows", table.size(1), table.element_size(), {table.data_ptr(), Ptr(rows)}, false);
+}
+
+// The count source (count / counts + piece_rows / last_id / none), lr_device and (Adam: bias_factor_device, else
+// nullptr) the other one-word tensor, then stochastic rounding and step_device.
+void ParseRowStepSources(RowStep& c, const at::Tensor& table, const at::Tensor& ids, const int64_t count,
+                         const c10::optional<at::Tensor>& counts, const c10::optional<at::Tensor>& last_id,
+                         const int64_t piece_rows_arg, const c10::optional<at::Tensor>& lr_device,
+                         const c10::optional<at::Tensor>* bias_factor_device, const bool stochastic_rounding,
+                         const c10::optional<at::Tensor>& step_device) {
+  const bool has_counts = counts.has_value() && counts->defined();
+  const bool has_last = last_id.has_value() && last_id->defined();
+  TORCH_CHECK((count >= 0) + has_counts + has_last <= 1, "cuembed_pyt: give at most one of count, counts and last_id");
+  c.piece_rows = ids.numel();
+  if (has_counts) {
+    CheckGpu(*counts, "counts");
+    c.words64 = IndexCode(*counts, "counts") == CUEMBED_I64;
+    TORCH_CHECK(counts->is_contiguous() && counts->numel() >= 1, "cuembed_pyt: counts must be contiguous words");
+    if (piece_rows_arg > 0) {
+      c.pieces = static_cast<int>(counts->numel());
+      c.piece_rows = piece_rows_arg;
+    }
+    TORCH_CHECK(c.pieces == counts->numel() && c.pieces * c.piece_rows == ids.numel(),
+                "cuembed_pyt: ids must hold counts.numel() * piece_rows entries");
+    c.counts = counts->data_ptr();
+  } else if (has_last) {
+    CheckGpu(*last_id, "last_id");
+    TORCH_CHECK(last_id->scalar_type() == ids.scalar_type() && last_id->numel() == 1,
+                "cuembed_pyt: last_id must be one word of ids' dtype");
+    c.last_id = last_id->data_ptr();
+  } else {
+    c.num_rows = count >= 0 ? count : ids.numel();
+    TORCH_CHECK(c.num_rows <= ids.numel(), "cuembed_pyt: count exceeds the entries");
+  }
+  const auto word = [&](const c10::optional<at::Tensor>& t, const char* name) -> const float* {
+    if (!t.has_value() || !t->defined()) return nullptr;
+    CheckGpu(*t, name);
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() == 1, "cuembed_pyt: ", name, " must be one float32 word");
+    return static_cast<const float*>(t->data_ptr());
+  };
+  c.lr_word = word(lr_device, "lr_device");
+  if (bias_factor_device != nullptr) c.bias_word = word(*bias_factor_device, "bias_factor_device");
+  if (stochastic_rounding) {
+    TORCH_CHECK(table.scalar_type() != at::kFloat,
+                "cuembed_pyt: stochastic_rounding is for float16 / bfloat16 tables: a float32 table is not rounded");
+    if (step_device.has_value() && step_device->defined()) {
+      CheckGpu(*step_device, "step_device");
+      TORCH_CHECK(step_device->scalar_type() == at::kLong && step_device->numel() == 1 &&
+                      step_device->device() == table.device(),
+                  "cuembed_pyt: step_device must be one int64 word on the table's device");
+      c.step_word = static_cast<const int64_t*>(step_device->data_ptr());
+    }
+  }
+}
+
 // Extension (cuembed::SparseRowUpdate): the sparse optimizer step on a compressed gradient, in place.  rule "sgd" /
 // "adagrad" (state fp32 [rows, width]) / "rowwise_adagrad" (state fp32 [rows]).  Valid entries, at most one of:
 // count >= 0 (host-known); counts (device words, int32 / int64: with piece_rows > 0 one per piece of piece_rows
@@ -697,21 +781,12 @@ void cuembed_sparse_row_update_op(at::Tensor table, const c10::optional<at::Tens
                                   const c10::optional<at::Tensor>& counts, const c10::optional<at::Tensor>& last_id,
                                   const int64_t piece_rows_arg, const bool stochastic_rounding, const int64_t seed,
                                   const int64_t step, const c10::optional<at::Tensor>& step_device) {
-  CheckGpu(table, "table");
-  CheckGpu(ids, "ids");
-  CheckGpu(rows, "rows");
-  const int elem = ElemCode(table, "table");
-  const int idx = IndexCode(ids, "ids");
+  RowStep c = RowStepCodes(table, ids, rows);
   const int code = rule == "sgd" ? CUEMBED_UPDATE_SGD
                    : rule == "adagrad" ? CUEMBED_UPDATE_ADAGRAD
                    : rule == "rowwise_adagrad" ? CUEMBED_UPDATE_ROWWISE_ADAGRAD : -1;
   TORCH_CHECK(code >= 0, "cuembed_pyt: rule must be 'sgd', 'adagrad' or 'rowwise_adagrad'");
-  TORCH_CHECK(rows.scalar_type() == table.scalar_type(), "cuembed_pyt: rows must have the table's dtype");
-  TORCH_CHECK(table.dim() == 2 && rows.dim() == 2 && rows.size(1) == table.size(1) && ids.dim() == 1 &&
-                  rows.size(0) == ids.numel() && table.is_contiguous() && rows.is_contiguous() && ids.is_contiguous(),
-              "cuembed_pyt: table [rows, width], rows [entries, width] and ids [entries] must be contiguous and agree");
-  TORCH_CHECK((table.size(1) * table.element_size()) % 4 == 0, "cuembed_pyt: the row size must be a multiple of 4 bytes");
-  CheckRowAlignment("table / rows", table.size(1), table.element_size(), {table.data_ptr(), Ptr(rows)}, false);
+  CheckRowStepShapes(table, ids, rows);
   at::Tensor state = state_arg.has_value() ? *state_arg : at::Tensor();
   if (code == CUEMBED_UPDATE_SGD) {
     TORCH_CHECK(!state.defined(), "cuembed_pyt: rule 'sgd' takes no state");
@@ -726,64 +801,22 @@ void cuembed_sparse_row_update_op(at::Tensor table, const c10::optional<at::Tens
     TORCH_CHECK(code != CUEMBED_UPDATE_ADAGRAD || reinterpret_cast<uintptr_t>(state.data_ptr()) % state_align == 0,
                 "cuembed_pyt: the state must be ", state_align, "-byte aligned for a ", table.scalar_type(), " table");
   }
-  const bool has_counts = counts.has_value() && counts->defined();
-  const bool has_last = last_id.has_value() && last_id->defined();
-  TORCH_CHECK((count >= 0) + has_counts + has_last <= 1, "cuembed_pyt: give at most one of count, counts and last_id");
-  int64_t num_rows = -1, piece_rows = ids.numel();
-  int pieces = 1, words64 = 0;
-  if (has_counts) {
-    CheckGpu(*counts, "counts");
-    words64 = IndexCode(*counts, "counts") == CUEMBED_I64;
-    TORCH_CHECK(counts->is_contiguous() && counts->numel() >= 1, "cuembed_pyt: counts must be contiguous words");
-    if (piece_rows_arg > 0) {
-      pieces = static_cast<int>(counts->numel());
-      piece_rows = piece_rows_arg;
-    }
-    TORCH_CHECK(pieces == counts->numel() && pieces * piece_rows == ids.numel(),
-                "cuembed_pyt: ids must hold counts.numel() * piece_rows entries");
-  } else if (has_last) {
-    CheckGpu(*last_id, "last_id");
-    TORCH_CHECK(last_id->scalar_type() == ids.scalar_type() && last_id->numel() == 1,
-                "cuembed_pyt: last_id must be one word of ids' dtype");
-  } else {
-    num_rows = count >= 0 ? count : ids.numel();
-    TORCH_CHECK(num_rows <= ids.numel(), "cuembed_pyt: count exceeds the entries");
-  }
-  const bool has_lr = lr_device.has_value() && lr_device->defined();
-  if (has_lr) {
-    CheckGpu(*lr_device, "lr_device");
-    TORCH_CHECK(lr_device->scalar_type() == at::kFloat && lr_device->numel() == 1, "cuembed_pyt: lr_device must be one float32 word");
-  }
-  const bool has_step = step_device.has_value() && step_device->defined();
-  if (stochastic_rounding) {
-    TORCH_CHECK(table.scalar_type() != at::kFloat,
-                "cuembed_pyt: stochastic_rounding is for float16 / bfloat16 tables: a float32 table is not rounded");
-    if (has_step) {
-      CheckGpu(*step_device, "step_device");
-      TORCH_CHECK(step_device->scalar_type() == at::kLong && step_device->numel() == 1 &&
-                      step_device->device() == table.device(),
-                  "cuembed_pyt: step_device must be one int64 word on the table's device");
-    }
-  }
+  ParseRowStepSources(c, table, ids, count, counts, last_id, piece_rows_arg, lr_device, nullptr, stochastic_rounding,
+                      step_device);
   if (ids.numel() == 0) return;
   const at::DeviceGuard guard(table.device());
+  float* state_ptr = state.defined() ? static_cast<float*>(state.data_ptr()) : nullptr;
   if (stochastic_rounding) {
-    ::cuembed_sparse_row_update_stochastic(
-        table.data_ptr(), elem, static_cast<int>(table.size(1)),
-        state.defined() ? static_cast<float*>(state.data_ptr()) : nullptr, code, Ptr(ids), idx, Ptr(rows), piece_rows,
-        pieces, num_rows, has_counts ? counts->data_ptr() : nullptr, words64,
-        has_last ? last_id->data_ptr() : nullptr, static_cast<float>(lr),
-        has_lr ? static_cast<const float*>(lr_device->data_ptr()) : nullptr, static_cast<float>(eps),
-        static_cast<uint64_t>(seed), static_cast<uint64_t>(step),
-        has_step ? static_cast<const int64_t*>(step_device->data_ptr()) : nullptr, CurrentStream(table));
+    ::cuembed_sparse_row_update_stochastic(table.data_ptr(), c.elem, static_cast<int>(table.size(1)), state_ptr, code,
+                                           Ptr(ids), c.idx, Ptr(rows), c.piece_rows, c.pieces, c.num_rows, c.counts,
+                                           c.words64, c.last_id, static_cast<float>(lr), c.lr_word,
+                                           static_cast<float>(eps), static_cast<uint64_t>(seed),
+                                           static_cast<uint64_t>(step), c.step_word, CurrentStream(table));
     return;
   }
-  ::cuembed_sparse_row_update(table.data_ptr(), elem, static_cast<int>(table.size(1)),
-                              state.defined() ? static_cast<float*>(state.data_ptr()) : nullptr, code, Ptr(ids), idx,
-                              Ptr(rows), piece_rows, pieces, num_rows, has_counts ? counts->data_ptr() : nullptr, words64,
-                              has_last ? last_id->data_ptr() : nullptr, static_cast<float>(lr),
-                              has_lr ? static_cast<const float*>(lr_device->data_ptr()) : nullptr,
-                              static_cast<float>(eps), CurrentStream(table));
+  ::cuembed_sparse_row_update(table.data_ptr(), c.elem, static_cast<int>(table.size(1)), state_ptr, code, Ptr(ids), c.idx,
+                              Ptr(rows), c.piece_rows, c.pieces, c.num_rows, c.counts, c.words64, c.last_id,
+                              static_cast<float>(lr), c.lr_word, static_cast<float>(eps), CurrentStream(table));
 }
 
 // Extension (cuembed::SparseRowAdam): the sparse Adam step on a compressed gradient, in place on the table and both
@@ -799,17 +832,8 @@ void cuembed_sparse_row_adam_op(at::Tensor table, at::Tensor exp_avg, at::Tensor
                                 const c10::optional<at::Tensor>& counts, const c10::optional<at::Tensor>& last_id,
                                 const int64_t piece_rows_arg, const bool stochastic_rounding, const int64_t seed,
                                 const int64_t step, const c10::optional<at::Tensor>& step_device) {
-  CheckGpu(table, "table");
-  CheckGpu(ids, "ids");
-  CheckGpu(rows, "rows");
-  const int elem = ElemCode(table, "table");
-  const int idx = IndexCode(ids, "ids");
-  TORCH_CHECK(rows.scalar_type() == table.scalar_type(), "cuembed_pyt: rows must have the table's dtype");
-  TORCH_CHECK(table.dim() == 2 && rows.dim() == 2 && rows.size(1) == table.size(1) && ids.dim() == 1 &&
-                  rows.size(0) == ids.numel() && table.is_contiguous() && rows.is_contiguous() && ids.is_contiguous(),
-              "cuembed_pyt: table [rows, width], rows [entries, width] and ids [entries] must be contiguous and agree");
-  TORCH_CHECK((table.size(1) * table.element_size()) % 4 == 0, "cuembed_pyt: the row size must be a multiple of 4 bytes");
-  CheckRowAlignment("table / rows", table.size(1), table.element_size(), {table.data_ptr(), Ptr(rows)}, false);
+  RowStep c = RowStepCodes(table, ids, rows);
+  CheckRowStepShapes(table, ids, rows);
   TORCH_CHECK(exp_avg.defined() && exp_avg.is_cuda() && exp_avg.scalar_type() == at::kFloat && exp_avg.is_contiguous() &&
                   exp_avg.sizes() == table.sizes(),
               "cuembed_pyt: exp_avg must be a contiguous float32 GPU tensor of the table's shape");
@@ -828,48 +852,8 @@ void cuembed_sparse_row_adam_op(at::Tensor table, at::Tensor exp_avg, at::Tensor
               "cuembed_pyt: exp_avg_sq must be ", state_align, "-byte aligned for a ", table.scalar_type(), " table");
   TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "cuembed_pyt: betas must lie in [0, 1)");
   TORCH_CHECK(eps >= 0.0 && weight_decay >= 0.0, "cuembed_pyt: eps and weight_decay must not be negative");
-  const bool has_counts = counts.has_value() && counts->defined();
-  const bool has_last = last_id.has_value() && last_id->defined();
-  TORCH_CHECK((count >= 0) + has_counts + has_last <= 1, "cuembed_pyt: give at most one of count, counts and last_id");
-  int64_t num_rows = -1, piece_rows = ids.numel();
-  int pieces = 1, words64 = 0;
-  if (has_counts) {
-    CheckGpu(*counts, "counts");
-    words64 = IndexCode(*counts, "counts") == CUEMBED_I64;
-    TORCH_CHECK(counts->is_contiguous() && counts->numel() >= 1, "cuembed_pyt: counts must be contiguous words");
-    if (piece_rows_arg > 0) {
-      pieces = static_cast<int>(counts->numel());
-      piece_rows = piece_rows_arg;
-    }
-    TORCH_CHECK(pieces == counts->numel() && pieces * piece_rows == ids.numel(),
-                "cuembed_pyt: ids must hold counts.numel() * piece_rows entries");
-  } else if (has_last) {
-    CheckGpu(*last_id, "last_id");
-    TORCH_CHECK(last_id->scalar_type() == ids.scalar_type() && last_id->numel() == 1,
-                "cuembed_pyt: last_id must be one word of ids' dtype");
-  } else {
-    num_rows = count >= 0 ? count : ids.numel();
-    TORCH_CHECK(num_rows <= ids.numel(), "cuembed_pyt: count exceeds the entries");
-  }
-  const auto word = [&](const c10::optional<at::Tensor>& t, const char* name) -> const float* {
-    if (!t.has_value() || !t->defined()) return nullptr;
-    CheckGpu(*t, name);
-    TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() == 1, "cuembed_pyt: ", name, " must be one float32 word");
-    return static_cast<const float*>(t->data_ptr());
-  };
-  const float* lr_word = word(lr_device, "lr_device");
-  const float* bias_word = word(bias_factor_device, "bias_factor_device");
-  const bool has_step = step_device.has_value() && step_device->defined();
-  if (stochastic_rounding) {
-    TORCH_CHECK(table.scalar_type() != at::kFloat,
-                "cuembed_pyt: stochastic_rounding is for float16 / bfloat16 tables: a float32 table is not rounded");
-    if (has_step) {
-      CheckGpu(*step_device, "step_device");
-      TORCH_CHECK(step_device->scalar_type() == at::kLong && step_device->numel() == 1 &&
-                      step_device->device() == table.device(),
-                  "cuembed_pyt: step_device must be one int64 word on the table's device");
-    }
-  }
+  ParseRowStepSources(c, table, ids, count, counts, last_id, piece_rows_arg, lr_device, &bias_factor_device,
+                      stochastic_rounding, step_device);
   if (ids.numel() == 0) return;
   const at::DeviceGuard guard(table.device());
   const int rule = rowwise ? CUEMBED_ROWWISE_ADAM : CUEMBED_ADAM;
@@ -879,19 +863,17 @@ void cuembed_sparse_row_adam_op(at::Tensor table, at::Tensor exp_avg, at::Tensor
   const float b2 = static_cast<float>(beta2), omb2 = static_cast<float>(1.0 - beta2);
   if (stochastic_rounding) {
     ::cuembed_sparse_row_adam_stochastic(
-        table.data_ptr(), elem, static_cast<int>(table.size(1)), m, v, rule, Ptr(ids), idx, Ptr(rows), piece_rows, pieces,
-        num_rows, has_counts ? counts->data_ptr() : nullptr, words64, has_last ? last_id->data_ptr() : nullptr,
-        static_cast<float>(lr), lr_word, static_cast<float>(bias_factor), bias_word, b1, omb1, b2, omb2,
-        static_cast<float>(eps), static_cast<float>(weight_decay), static_cast<uint64_t>(seed),
-        static_cast<uint64_t>(step), has_step ? static_cast<const int64_t*>(step_device->data_ptr()) : nullptr,
+        table.data_ptr(), c.elem, static_cast<int>(table.size(1)), m, v, rule, Ptr(ids), c.idx, Ptr(rows), c.piece_rows,
+        c.pieces, c.num_rows, c.counts, c.words64, c.last_id, static_cast<float>(lr), c.lr_word,
+        static_cast<float>(bias_factor), c.bias_word, b1, omb1, b2, omb2, static_cast<float>(eps),
+        static_cast<float>(weight_decay), static_cast<uint64_t>(seed), static_cast<uint64_t>(step), c.step_word,
         CurrentStream(table));
     return;
   }
-  ::cuembed_sparse_row_adam(table.data_ptr(), elem, static_cast<int>(table.size(1)), m, v, rule, Ptr(ids), idx, Ptr(rows),
-                            piece_rows, pieces, num_rows, has_counts ? counts->data_ptr() : nullptr, words64,
-                            has_last ? last_id->data_ptr() : nullptr, static_cast<float>(lr), lr_word,
-                            static_cast<float>(bias_factor), bias_word, b1, omb1, b2, omb2, static_cast<float>(eps),
-                            static_cast<float>(weight_decay), CurrentStream(table));
+  ::cuembed_sparse_row_adam(table.data_ptr(), c.elem, static_cast<int>(table.size(1)), m, v, rule, Ptr(ids), c.idx, Ptr(rows),
+                            c.piece_rows, c.pieces, c.num_rows, c.counts, c.words64, c.last_id, static_cast<float>(lr),
+                            c.lr_word, static_cast<float>(bias_factor), c.bias_word, b1, omb1, b2, omb2,
+                            static_cast<float>(eps), static_cast<float>(weight_decay), CurrentStream(table));
 }
 
 // ---- the optimizer step on a group of SEPARATE table tensors, in one launch (cuembed::SparseRowUpdateGrouped /

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "cuembed/include/sparse_update.hpp"
@@ -143,9 +144,51 @@ void UpdateKat(hipStream_t stream, const char* what) {
       for (const auto source : sources) Case<ElemT, IndexT>(rule, width, source, stream, what);
 }
 
+// The widest overload with every id array nullptr is the plain overload: on copies of the same tensors the two calls
+// must leave the same bits.  An fp16 table of width 8 (one 16-byte slice per row: two entries in flight), 5 valid
+// entries of 8 (the last group's second entry is dead), the count from last_id, both roundings.  Forwarding is host
+// code: no other shape is needed.
+void NullIdsForward(const cuembed::UpdateRule rule, const bool stochastic, hipStream_t stream) {
+  constexpr int kWidth = 8;
+  const int ids_h[kCapacity] = {3, 7, 0, 12, 5, 9, 7, 3};
+  std::vector<__half> table, grad;
+  for (int i = 0; i < kRows * kWidth; ++i) table.push_back(__float2half(static_cast<float>(i % 17 - 8) / 3.f));
+  for (int i = 0; i < kCapacity * kWidth; ++i) grad.push_back(__float2half(static_cast<float>(i % 11 - 5) / 7.f));
+  const std::vector<float> state(rule == cuembed::UpdateRule::kAdagrad ? kRows * kWidth : kRows, 0.25f);
+  DeviceArray<__half> d_wide(table), d_plain(table), d_grad(grad);
+  DeviceArray<float> d_wide_state(state), d_plain_state(state);
+  DeviceArray<int32_t> d_ids(std::vector<int32_t>(ids_h, ids_h + kCapacity));
+  DeviceArray<int32_t> d_last(std::vector<int32_t>{4});
+  cuembed::SparseUpdateOptions o;
+  o.rule = rule;
+  o.lr = 0.3f;
+  o.piece_rows = kCapacity;
+  o.last_id = d_last.ptr;
+  o.stochastic_rounding = stochastic;
+  o.rounding_seed = 11;
+  o.rounding_step = 3;
+  cuembed::SparseRowUpdate<__half, int32_t>(d_wide.ptr, d_wide_state.ptr, kWidth, d_ids.ptr, d_grad.ptr, o, stream, nullptr,
+                                            nullptr);
+  cuembed::SparseRowUpdate<__half, int32_t>(d_plain.ptr, d_plain_state.ptr, kWidth, d_ids.ptr, d_grad.ptr, o, stream);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipStreamSynchronize(stream));
+  const std::vector<__half> wide = d_wide.host(), plain = d_plain.host();
+  const bool same = std::memcmp(wide.data(), plain.data(), wide.size() * sizeof(__half)) == 0 &&
+                    std::memcmp(wide.data(), table.data(), wide.size() * sizeof(__half)) != 0 &&   // (and something moved)
+                    d_wide_state.host() == d_plain_state.host();
+  ++g_checks;
+  if (!same) {
+    ++g_failures;
+    std::fprintf(stderr, "MISMATCH null ids do not forward to the plain overload: rule %d stochastic %d\n",
+                 static_cast<int>(rule), static_cast<int>(stochastic));
+  }
+}
+
 int main() {
   hipStream_t stream;
   HIP_OK(hipStreamCreate(&stream));
+  for (const auto rule : {cuembed::UpdateRule::kAdagrad, cuembed::UpdateRule::kRowwiseAdagrad})
+    for (const bool stochastic : {false, true}) NullIdsForward(rule, stochastic, stream);
   UpdateKat<float, int32_t>(stream, "float/int32");
   UpdateKat<float, int64_t>(stream, "float/int64");
   UpdateKat<__half, int32_t>(stream, "half/int32");
