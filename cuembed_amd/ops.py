@@ -380,6 +380,8 @@ def embedding_backward(grad_y, num_grad_embedding_rows, transpose_indices, trans
     Compressed: remapped indices given, num_grad_embedding_rows = num_unique; also returns
     inverse_mapping[num_unique].  With skip_grad_init=True the caller's grad_embedding must
     already be zero.  Returns (grad_embedding, inverse_mapping or None).
+    A non-finite element of grad_y reaches exactly the (row, column) pairs that look it up, and a sum of zeros is +0
+    whatever their signs (tests/test_gpu_backward_edges.py).
 
     Extension (compressed only): num_grad_embedding_rows=None = "num_unique is only known on the device"
     (it is transpose_remapped_indices[-1] + 1).  grad_embedding and inverse_mapping must then be given
@@ -1140,7 +1142,9 @@ def exchange_merge(ids, rows, num_categories, pad_lo, pad_len, out_ids, out_rows
     out_rows[capacity + 1, W] + cuembed::FinishOwnerPiece.  ids (int64) >= num_categories are padding and dropped.
     Afterwards: the first *count entries are the ascending distinct ids and their summed rows, every entry past them a
     zero row named pad_lo + i % pad_len; `tail` (int64[capacity + 2] or None) = the ids, min(count, capacity), the flag
-    word; flag |= 1 when count > capacity (nothing was written then).  Nothing read back."""
+    word; flag |= 1 when count > capacity (nothing was written then).  Nothing read back.
+    The rows of padding ids may hold anything (NaNs, infinities, what an earlier step left there): they leave no trace,
+    every row from *count on has +0 bits."""
     _check_dev("rows", rows)
     dev = rows.device
     for name, t in (("ids", ids), ("out_ids", out_ids), ("out_rows", out_rows), ("flag", flag)):

@@ -71,9 +71,11 @@ def _etype(a):
 
 
 def to_bf16_bits(a):
-    """float32 array -> bfloat16 bit patterns (uint16), round-to-nearest-even."""
+    """float32 array -> bfloat16 bit patterns (uint16), round-to-nearest-even; a NaN stays a NaN (f2b of
+    cuembed_oracle.cpp: the upper half with the quiet bit set, so that no payload can carry into the sign)."""
     x = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)
     r = ((x + 0x7fff + ((x >> 16) & 1)) >> 16).astype(np.uint16)
+    r = np.where((x & 0x7fffffff) > 0x7f800000, ((x >> 16) | 0x0040).astype(np.uint16), r)
     return r.reshape(np.shape(a))
 
 

@@ -48,17 +48,24 @@ def raw_bytes(t):
     return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()]).numpy().tobytes()
 
 
-def run_case(ce, oracle, case):
-    """One call; returns the fingerprint.  Exact data is also compared with the oracle."""
+def planned_shape(ce, case):
+    """The case's launch shape on a full chip, which this device must plan too."""
     full = pinned_shape(ce, case, compute_units=256, xcds=8)
     here = pinned_shape(ce, case)
     keep = ("column_slices", "lanes", "segments_per_block", "segment_len")
     assert [here[k] for k in keep] == [full[k] for k in keep], "this device plans another launch shape: %r" % (here,)
     assert full["column_slices"] == case.slices
-    d = C.build(case, full["segment_len"], full["segments_per_block"])
+    return full
+
+
+def launch_case(ce, case, d, gy=None, w=None):
+    """The call sequence of one case on the inputs `d` (backward_bits_cases.build's dict; gy / w: device tensors to use
+    in place of d's grad_y / weights).  Returns (grad_embedding, inverse_mapping, the overflow word, and
+    backward_bits_cases.compressed_ids(keys))."""
     dev = lambda a, dtype: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dtype).cuda()
     elem, index = TORCH[case.kind], INDEX[case.index]
-    gy, w = dev(d["grad_y"], elem), dev(d["weights"], elem)
+    gy = dev(d["grad_y"], elem) if gy is None else gy
+    w = dev(d["weights"], elem) if w is None else w
     keys, sids = dev(d["keys"], index), dev(d["sids"], index)
     dense_ids, order, unique = C.compressed_ids(d["keys"])
     table = None
@@ -90,6 +97,14 @@ def run_case(ce, oracle, case):
     finally:
         ce.set_backward_tuning(0, 0)
     overflowed = ce.capacity_overflowed(reset=True)
+    return grad, inverse, overflowed, (dense_ids, order, unique)
+
+
+def run_case(ce, oracle, case):
+    """One call; returns the fingerprint.  Exact data is also compared with the oracle."""
+    full = planned_shape(ce, case)
+    d = C.build(case, full["segment_len"], full["segments_per_block"])
+    grad, inverse, overflowed, (dense_ids, order, unique) = launch_case(ce, case, d)
     assert overflowed == (case.out == "small")
     if case.out == "small":
         assert float(grad.float().max()) == C.PATTERN == float(grad.float().min()), "nothing may be written"
