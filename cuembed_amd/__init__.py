@@ -30,5 +30,7 @@ from .grouped import (EmbeddingBagGroup, QuantizedEmbeddingBagGroup, TableGroup,
 from .grouped_backward import (GroupedGrad, embedding_backward_grouped, embedding_weight_grad_grouped,  # noqa: F401
                                grouped_backward_keys, grouped_mean_scale, grouped_table_cuts,
                                sparse_row_adam_grouped, sparse_row_update_grouped)
+from .index_check import (IndexCheck, check_indices, check_indices_workspace_bytes,  # noqa: F401
+                          new_index_report)
 
 __version__ = "0.1.0"

@@ -212,6 +212,9 @@ def _declare(L):
     L.cuembed_sparse_row_adam_grouped_stochastic.restype = None
     L.cuembed_sparse_row_adam_grouped_stochastic.argtypes = (
         list(L.cuembed_sparse_row_adam_grouped.argtypes[:-1]) + [_VP, _U, _VP, _VP])
+    L.cuembed_check_indices.restype = None
+    L.cuembed_check_indices.argtypes = [_VP, _I, _VP, _I, _L, _VP, _L, _I, _I, _I, _VP, _VP, _VP, _VP,
+                                        ctypes.POINTER(ctypes.c_size_t), _VP]
     L.cuembed_peek_last_error.restype = _I
     L.cuembed_peek_last_error.argtypes = []
     L.cuembed_version.restype = ctypes.c_char_p

@@ -25,7 +25,7 @@ UNITS = ["c_api_forward.hip", "c_api_backward.hip", "c_api_transforms.hip", "c_a
          "c_api_optimizer_adam_stochastic.hip", "c_api_optimizer_placed_stochastic.hip",
          "c_api_optimizer_adam_placed_stochastic.hip", "c_api_quantized.hip", "c_api_grouped.hip",
          "c_api_grouped_backward.hip", "c_api_row_cache.hip", "c_api_optimizer_grouped.hip",
-         "c_api_optimizer_grouped_stochastic.hip"]
+         "c_api_optimizer_grouped_stochastic.hip", "c_api_index_check.hip"]
 ARCH = "gfx950"
 
 HIPCC_FLAGS = [
@@ -268,6 +268,13 @@ def build_grouped_stochastic_rounding_test(force=False):
     recomputation with stochastic_rounding.hpp's host functions on exactly representable data.  Needs a GPU to RUN
     (tests/test_gpu_cpp_grouped_stochastic_rounding.py)."""
     return _build_program("tests/cpp/grouped_stochastic_rounding_kat.hip", _O2, force)
+
+
+def build_index_check_test(force=False):
+    """Compiles tests/cpp/index_check_kat.hip: cuembed::CheckIndices through the header-only API on a small hand-written
+    batch (a three-table CSR group and a fixed-hotness table) with the answers written in the source.  Needs a GPU to RUN
+    (tests/test_gpu_cpp_index_check.py)."""
+    return _build_program("tests/cpp/index_check_kat.hip", _O2, force)
 
 
 def build_sort_unit_test(force=False):

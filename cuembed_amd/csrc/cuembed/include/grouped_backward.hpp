@@ -47,7 +47,8 @@ namespace cuembed {
  * pipeline and independent of IndexT: int32_t whenever the group has fewer than 2^31 rows in all (the kernel writes
  * fresh arrays, so narrowing int64 ids costs nothing), int64_t otherwise -- keys that do not fit KeyT are the
  * caller's error.  Ids outside [0, rows_t) are a contract violation, as in the forward.  nnz <= INT_MAX (the
- * pipeline's own limit) and num_tables * batch_per_table <= INT_MAX.
+ * pipeline's own limit) and num_tables * batch_per_table <= INT_MAX.  (cuembed::CheckIndices, index_check.hpp, finds
+ * and repairs such ids and offsets on the device, in front of this call.)
  */
 template <typename IndexT, typename OffsetT, typename KeyT>
 void GroupedBackwardKeys(const IndexT* indices,

@@ -1619,6 +1619,60 @@ at::Tensor cuembed_grouped_mean_scale_op(const at::Tensor& y_grad, const c10::op
   return out;
 }
 
+// Extension (cuembed::CheckIndices): is this batch safe to hand to the row-addressing ops?  No table is read and nothing
+// is read back.  row_base: the int64 device tensor of num_tables + 1 entries of a group, or undefined and ONE table of
+// num_rows rows.  CSR: offsets of num_tables * batch + 1 entries, num_hots = 0; fixed hotness: no offsets, num_hots > 0.
+// Returns (report int64[4], repaired indices, repaired offsets); without `repair` -- and for the offsets of a
+// fixed-hotness batch -- the latter are tensors of 0 entries.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> cuembed_check_indices_op(
+    const at::Tensor& indices, const c10::optional<at::Tensor>& offsets, const c10::optional<at::Tensor>& row_base,
+    const int64_t num_rows, const int64_t num_tables, const int64_t batch, const int64_t num_hots, const bool repair) {
+  CheckGpu(indices, "indices");
+  const int idx = IndexCode(indices, "indices");
+  const bool grouped = row_base.has_value() && row_base->defined();
+  TORCH_CHECK(num_tables >= 1 && num_tables <= 1023, "cuembed_pyt: 1 <= num_tables <= 1023");
+  if (grouped) {
+    CheckGpu(*row_base, "row_base");
+    TORCH_CHECK(row_base->scalar_type() == at::kLong && row_base->numel() == num_tables + 1 && row_base->is_contiguous() &&
+                    row_base->device() == indices.device(),
+                "cuembed_pyt: row_base must be the contiguous int64 tensor of num_tables + 1 entries on indices' device");
+  } else {
+    TORCH_CHECK(num_tables == 1 && num_rows >= 1, "cuembed_pyt: without row_base: one table of num_rows >= 1 rows");
+  }
+  TORCH_CHECK(batch >= 0 && num_tables * batch <= INT32_MAX, "cuembed_pyt: num_tables * batch must fit a 32-bit int");
+  const at::DeviceGuard guard(indices.device());
+  const at::Tensor i = indices.contiguous();
+  const int64_t nnz = i.numel();
+  TORCH_CHECK(nnz <= (int64_t{1} << 38), "cuembed_pyt: at most 2^38 lookups per call");
+  at::Tensor o;
+  int off = CUEMBED_I32;
+  if (offsets.has_value() && offsets->defined()) {
+    CheckGpu(*offsets, "offsets");
+    off = IndexCode(*offsets, "offsets");
+    o = offsets->contiguous();
+    TORCH_CHECK(num_hots == 0 && o.numel() == num_tables * batch + 1 && o.device() == i.device(),
+                "cuembed_pyt: CSR: num_hots = 0 and offsets of num_tables * batch + 1 entries on indices' device");
+    TORCH_CHECK(off == CUEMBED_I64 || nnz <= INT32_MAX, "cuembed_pyt: int32 offsets cannot address that many lookups");
+  } else {
+    TORCH_CHECK(num_hots > 0 && nnz == num_tables * batch * num_hots,
+                "cuembed_pyt: fixed hotness: num_hots > 0 and indices of num_tables * batch * num_hots entries");
+  }
+  at::Tensor report = at::empty({4}, i.options().dtype(at::kLong));
+  at::Tensor i_out = repair ? at::empty_like(i) : at::empty({0}, i.options());
+  at::Tensor o_out = repair && o.defined() ? at::empty_like(o) : at::empty({0}, o.defined() ? o.options() : i.options());
+  size_t lwork = 0;
+  const int64_t* base = grouped ? static_cast<const int64_t*>(row_base->data_ptr()) : nullptr;
+  ::cuembed_check_indices(nullptr, idx, nullptr, off, nnz, base, num_rows, static_cast<int>(num_tables),
+                          static_cast<int>(batch), static_cast<int>(num_hots), nullptr, nullptr, nullptr, nullptr, &lwork,
+                          nullptr);
+  at::Tensor work = at::empty({static_cast<int64_t>(lwork > 0 ? lwork : 8)}, i.options().dtype(at::kByte));
+  ::cuembed_check_indices(Ptr(i), idx, Ptr(o), off, nnz, base, num_rows, static_cast<int>(num_tables),
+                          static_cast<int>(batch), static_cast<int>(num_hots), static_cast<int64_t*>(report.data_ptr()),
+                          repair ? i_out.data_ptr() : nullptr, repair && o.defined() ? o_out.data_ptr() : nullptr,
+                          static_cast<char*>(work.data_ptr()), &lwork, CurrentStream(i));
+  return {report, i_out, o_out};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(cuembed_pyt, m) {
@@ -1704,6 +1758,10 @@ TORCH_LIBRARY(cuembed_pyt, m) {
   // a group beyond sum pooling with table gradients: the per-lookup weight gradient, the scale of a mean's y_grad
   m.def("cuembed_grouped_weight_grad(Tensor[] tables, Tensor table_ptrs, Tensor idx, Tensor? offsets, Tensor y_grad) -> Tensor");
   m.def("cuembed_grouped_mean_scale(Tensor y_grad, Tensor? offsets, Tensor? weights, int num_tables, int hotness) -> Tensor");
+  // the device-side index check in front of the row-addressing ops: (report, repaired indices, repaired offsets)
+  m.def(
+      "cuembed_check_indices(Tensor indices, Tensor? offsets, Tensor? row_base, int num_rows, int num_tables, int batch, "
+      "int num_hots, bool repair=False) -> (Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(cuembed_pyt, Autograd, m) {
@@ -1749,4 +1807,5 @@ TORCH_LIBRARY_IMPL(cuembed_pyt, CUDA, m) {  // HIP tensors use the CUDA dispatch
   m.impl("cuembed_grouped_table_cuts", cuembed_grouped_table_cuts_op);
   m.impl("cuembed_grouped_weight_grad", cuembed_grouped_weight_grad_op);
   m.impl("cuembed_grouped_mean_scale", cuembed_grouped_mean_scale_op);
+  m.impl("cuembed_check_indices", cuembed_check_indices_op);
 }

@@ -102,6 +102,9 @@ def _define_python_ops():
                 " Tensor y_grad) -> Tensor")
     _lib.define("cuembed_grouped_mean_scale(Tensor y_grad, Tensor? offsets, Tensor? weights, int num_tables, int hotness)"
                 " -> Tensor")
+    _lib.define("cuembed_check_indices(Tensor indices, Tensor? offsets, Tensor? row_base, int num_rows, int num_tables,"
+                " int batch, int num_hots, bool repair=False) -> (Tensor, Tensor, Tensor)")
+    _lib.impl("cuembed_check_indices", _check_indices_impl, "CUDA")
     _lib.impl("cuembed_grouped_weight_grad", _grouped_weight_grad_impl, "CUDA")
     _lib.impl("cuembed_grouped_mean_scale", _grouped_mean_scale_impl, "CUDA")
     _lib.impl("cuembed_grouped_backward_keys", _grouped_backward_keys_impl, "CUDA")
@@ -497,6 +500,48 @@ def _grouped_mean_scale_impl(y_grad, offsets, weights, num_tables, hotness):
                 0 if offsets is None else _ops._INDEX[offsets.dtype], _ops._ptr(weights), int(num_tables), int(batch),
                 int(hotness), _ops._ptr(out), _ops._stream(y_grad))
     return out
+
+
+def _check_indices_impl(indices, offsets, row_base, num_rows, num_tables, batch, num_hots, repair=False):
+    import ctypes
+    from . import _lib as _clib
+    _require(indices.is_cuda and indices.dtype in _INTS, "indices must be int tensors on the GPU")
+    _require(1 <= num_tables <= 1023, "1 <= num_tables <= 1023")
+    if row_base is not None:
+        _require(row_base.is_cuda and row_base.dtype == torch.int64 and row_base.numel() == num_tables + 1 and
+                 row_base.is_contiguous() and row_base.device == indices.device,
+                 "row_base must be the contiguous int64 tensor of num_tables + 1 entries on indices' device")
+    else:
+        _require(num_tables == 1 and num_rows >= 1, "without row_base: one table of num_rows >= 1 rows")
+    _require(batch >= 0 and num_tables * batch < 2 ** 31, "num_tables * batch must fit a 32-bit int")
+    indices = indices.contiguous()
+    nnz = indices.numel()
+    _require(nnz <= 2 ** 38, "at most 2^38 lookups per call")
+    if offsets is not None:
+        _require(offsets.is_cuda and offsets.dtype in _INTS and num_hots == 0 and offsets.numel() == num_tables * batch + 1
+                 and offsets.device == indices.device,
+                 "CSR: num_hots = 0 and offsets of num_tables * batch + 1 entries on indices' device")
+        _require(offsets.dtype == torch.int64 or nnz < 2 ** 31, "int32 offsets cannot address that many lookups")
+        offsets = offsets.contiguous()
+    else:
+        _require(num_hots > 0 and nnz == num_tables * batch * num_hots,
+                 "fixed hotness: num_hots > 0 and indices of num_tables * batch * num_hots entries")
+    like = offsets if offsets is not None else indices
+    report = torch.empty((4,), dtype=torch.int64, device=indices.device)
+    out_i = torch.empty_like(indices) if repair else torch.empty((0,), dtype=indices.dtype, device=indices.device)
+    out_o = (torch.empty_like(offsets) if repair and offsets is not None
+             else torch.empty((0,), dtype=like.dtype, device=like.device))
+    it, ot = _ops._INDEX[indices.dtype], 0 if offsets is None else _ops._INDEX[offsets.dtype]
+    shape = (_ops._ptr(row_base), int(num_rows), int(num_tables), int(batch), int(num_hots))
+    need = ctypes.c_size_t(0)
+    _clib.lib().cuembed_check_indices(None, it, None, ot, nnz, *shape, None, None, None, None, ctypes.byref(need), None)
+    work = torch.empty((max(need.value, 8),), dtype=torch.uint8, device=indices.device)
+    with torch.cuda.device(indices.device):
+        _clib.lib().cuembed_check_indices(
+            _ops._ptr(indices), it, _ops._ptr(offsets), ot, nnz, *shape, _ops._ptr(report),
+            _ops._ptr(out_i) if repair else None, _ops._ptr(out_o) if repair and offsets is not None else None,
+            _ops._ptr(work), ctypes.byref(need), _ops._stream(indices))
+    return report, out_i, out_o
 
 
 def _compress_impl(transpose_indices):
@@ -1284,6 +1329,14 @@ def _(tables, table_ptrs, idx, offsets, y_grad):
 @torch.library.register_fake("cuembed_pyt::cuembed_grouped_mean_scale")
 def _(y_grad, offsets, weights, num_tables, hotness):
     return torch.empty(y_grad.shape, device=y_grad.device, dtype=y_grad.dtype)
+
+
+@torch.library.register_fake("cuembed_pyt::cuembed_check_indices")
+def _(indices, offsets, row_base, num_rows, num_tables, batch, num_hots, repair=False):
+    like = offsets if offsets is not None else indices
+    return (torch.empty((4,), device=indices.device, dtype=torch.int64),
+            torch.empty(indices.shape if repair else (0,), device=indices.device, dtype=indices.dtype),
+            torch.empty(offsets.shape if repair and offsets is not None else (0,), device=like.device, dtype=like.dtype))
 
 
 @torch.library.register_fake("cuembed_pyt::cuembed_embedding_forward_hinted")

@@ -324,18 +324,41 @@ def grouped_forward_launch_shape(elem_dtype, index_dtype, embed_width, num_table
                 staged=out[5] == 1, index_source=_SOURCES[out[6]])
 
 
+_BOUNDS_CHECKS = (None, "raise", "repair")
+
+
+def _checked_batch(bags, idx, offsets, hot):
+    """The batch a group module hands to its forward.  bounds_check None: the caller's, untouched (ids outside their table
+    are then a contract violation).  "repair": cuembed_amd.check_indices with repair runs on the stream in front of the
+    forward, which gets the repaired arrays; the report stays on the device as bags.last_check -- no synchronisation.
+    "raise": the check, then IndexCheck.raise_if_bad() (one synchronisation) before the forward is launched."""
+    if bags.bounds_check is None:
+        return idx, offsets
+    from .index_check import check_indices
+    check = check_indices(idx, offsets, group=bags.group, num_hots=hot, repair=bags.bounds_check == "repair")
+    bags.last_check = check
+    if bags.bounds_check == "raise":
+        check.raise_if_bad()
+    return check.indices, check.offsets
+
+
 class EmbeddingBagGroup:
     """A TableGroup with a mode and the call shape of nn.EmbeddingBag: bags(idx, offsets, weights) with CSR offsets
     (num_tables * batch + 1 entries), or bags(idx) with idx [num_tables, batch, hotness].  Returns [batch, num_tables,
-    width].  Forward only."""
+    width].  Forward only.  bounds_check: None (the batch is trusted), "raise" or "repair" (_checked_batch); the last
+    check is kept as .last_check."""
 
-    def __init__(self, tables, mode="sum"):
+    def __init__(self, tables, mode="sum", bounds_check=None):
         if mode not in ("sum", "mean"):
             raise ValueError("mode must be 'sum' or 'mean'")
+        if bounds_check not in _BOUNDS_CHECKS:
+            raise ValueError("bounds_check must be None, 'raise' or 'repair'")
         self.group = _as_group(tables)
         if self.group.quantized:
             raise TypeError("fused 8-bit tables go into a QuantizedEmbeddingBagGroup")
         self.mode = mode
+        self.bounds_check = bounds_check
+        self.last_check = None
 
     @property
     def num_tables(self):
@@ -351,6 +374,7 @@ class EmbeddingBagGroup:
             if idx.dim() != 3:
                 raise ValueError("without offsets, idx must be [num_tables, batch, hotness]")
             hot = idx.shape[2]
+        idx, offsets = _checked_batch(self, idx, offsets, hot)
         return embedding_forward_grouped(self.group, idx, offsets, weights, num_hots=hot, mode=self.mode,
                                          sample_order=sample_order, out=out)
 
@@ -358,19 +382,23 @@ class EmbeddingBagGroup:
 class QuantizedEmbeddingBagGroup:
     """EmbeddingBagGroup on fused 8-bit tables; from_float quantizes fp32 / fp16 / bf16 tables on the device."""
 
-    def __init__(self, qtables, mode="sum", out_dtype=torch.float16):
+    def __init__(self, qtables, mode="sum", out_dtype=torch.float16, bounds_check=None):
         if mode not in ("sum", "mean"):
             raise ValueError("mode must be 'sum' or 'mean'")
+        if bounds_check not in _BOUNDS_CHECKS:
+            raise ValueError("bounds_check must be None, 'raise' or 'repair'")
         _out_code("out_dtype", out_dtype)
         self.group = _as_group(qtables)
         if not self.group.quantized:
             raise TypeError("QuantizedEmbeddingBagGroup takes fused uint8 tables; see from_float")
         self.mode = mode
         self.out_dtype = out_dtype
+        self.bounds_check = bounds_check
+        self.last_check = None
 
     @classmethod
-    def from_float(cls, tables, mode="sum", out_dtype=torch.float16):
-        return cls([quantize_rows(t.detach()) for t in tables], mode=mode, out_dtype=out_dtype)
+    def from_float(cls, tables, mode="sum", out_dtype=torch.float16, bounds_check=None):
+        return cls([quantize_rows(t.detach()) for t in tables], mode=mode, out_dtype=out_dtype, bounds_check=bounds_check)
 
     @property
     def num_tables(self):
@@ -386,5 +414,6 @@ class QuantizedEmbeddingBagGroup:
             if idx.dim() != 3:
                 raise ValueError("without offsets, idx must be [num_tables, batch, hotness]")
             hot = idx.shape[2]
+        idx, offsets = _checked_batch(self, idx, offsets, hot)
         return embedding_forward_quantized_grouped(self.group, idx, offsets, weights, num_hots=hot, mode=self.mode,
                                                    out_dtype=self.out_dtype, sample_order=sample_order, out=out)

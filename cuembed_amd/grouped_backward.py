@@ -102,7 +102,8 @@ def grouped_backward_keys(group, indices, offsets=None, batch_size=None, num_hot
     indices and offsets in any combination.  key_dtype: the dtype of both results, the index type of the backward
     pipeline; None = int32 whenever the group has fewer than 2^31 rows (whatever the indices' dtype: the arrays are
     written fresh, so narrowing is free), else int64; int32 with 2^31 rows or more is a ValueError.  out: optional
-    (keys, sample_ids) buffers of nnz entries.  Ids outside [0, rows_t) are a contract violation, as in the forward."""
+    (keys, sample_ids) buffers of nnz entries.  Ids outside [0, rows_t) are a contract violation, as in the forward
+    (cuembed_amd.check_indices finds and repairs them on the device)."""
     group = _float_group(group)
     batch_size, nnz = _layout(group, indices, offsets, batch_size, num_hots)
     kd = _key_dtype(group, key_dtype)

@@ -799,7 +799,8 @@ void cuembed_grouped_forward_launch_shape(int quantized, int elem_type, int inde
 /* cuembed::GroupedBackwardKeys: for lookup p of bag t * batch_per_table + b, keys[p] = row_base[t] + indices[p] and
  * sample_ids[p] = b * num_tables + t, both of key_type (CUEMBED_I32 needs total_rows < 2^31; independent of index_type).
  * CSR: offsets[num_tables * batch_per_table + 1] of offset_type, num_hots = 0; fixed hotness: offsets = NULL, num_hots
- * > 0.  nnz = the number of lookups, <= INT_MAX.  Ids outside their table are a contract violation. */
+ * > 0.  nnz = the number of lookups, <= INT_MAX.  Ids outside their table are a contract violation
+ * (cuembed_check_indices finds and repairs them on the device). */
 void cuembed_grouped_backward_keys(const void* indices, int index_type, const void* offsets, int offset_type,
                                    const int64_t* row_base, int num_tables, int batch_per_table, int num_hots,
                                    int64_t nnz, void* keys, void* sample_ids, int key_type, cuembed_stream_t stream);
@@ -890,6 +891,27 @@ void cuembed_sparse_row_adam_grouped_stochastic(const void* const* tables_host, 
                                                 float beta2, float one_minus_beta2, float eps, float weight_decay,
                                                 const uint64_t* seeds_device, uint64_t step, const int64_t* step_device,
                                                 cuembed_stream_t stream);
+/* ---- extension: the device-side index check (cuembed::CheckIndices, index_check.hpp) ---------------------------------
+ * Is this batch safe to hand to the row-addressing calls above, which all trust their indices and offsets?  Never reads
+ * a table, reads nothing back, allocates nothing, capturable.  n = num_tables * batch_per_table bags, table-major.  Row
+ * counts: row_base[num_tables + 1] (int64, device, as for cuembed_grouped_backward_keys), or row_base == NULL and ONE
+ * table of num_rows rows; every table has at least one row.  num_tables <= 1023.
+ *   CSR (num_hots == 0, offsets[n + 1] of offset_type): position i is bad iff o[i] < 0, o[i] > nnz, or i > 0 and o[i] <
+ *     o[i - 1]; the repaired offsets r are the running maximum clamped into [0, nnz].  Checked indices: [r[0], r[n]);
+ *     position p belongs to the table t with r[t * batch_per_table] <= p < r[(t + 1) * batch_per_table].
+ *   Fixed hotness (num_hots > 0, offsets == NULL, nnz == n * num_hots): every position is checked, t = p /
+ *     (batch_per_table * num_hots).
+ *   p is bad iff indices[p] < 0 or indices[p] >= rows_t (64-bit comparison); the repaired index is 0 where bad.
+ * report: int64[4] on the device, initialised by the call: [bad indices, first (smallest) bad index position or -1, bad
+ * offsets, first bad offset position or -1].  indices_out / offsets_out: NULL (report only), the input (in place), or a
+ * separate array of the same type; bit-identical copies on a clean batch; positions outside the checked range are
+ * copied through.  Any garbage in either array is a defined input: nothing is addressed with an unchecked value.
+ * Two-phase workspace query: work == NULL writes the bytes needed to *lwork (0 for fixed hotness, which still needs a
+ * non-NULL work to run) and runs nothing.  Launches: 3 (CSR), 2 (fixed hotness); one fewer for nnz == 0. */
+void cuembed_check_indices(const void* indices, int index_type, const void* offsets, int offset_type, int64_t nnz,
+                           const int64_t* row_base, int64_t num_rows, int num_tables, int batch_per_table, int num_hots,
+                           int64_t* report, void* indices_out, void* offsets_out, char* work, size_t* lwork,
+                           cuembed_stream_t stream);
 /* hipPeekAtLastError() as an int (0 = hipSuccess); launches themselves never
  * report errors, exactly like the reference. */
 int cuembed_peek_last_error(void);
