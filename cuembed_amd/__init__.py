@@ -27,6 +27,8 @@ from .quantized import (QuantizedEmbeddingBag, dequantize_rows, embedding_forwar
                         quantize_rows, quantized_forward_launch_shape, quantized_row_bytes)
 from .grouped import (EmbeddingBagGroup, QuantizedEmbeddingBagGroup, TableGroup,  # noqa: F401
                       embedding_forward_grouped, embedding_forward_quantized_grouped, grouped_forward_launch_shape)
+from .mixed_group import (MixedEmbeddingBagGroup, MixedTableGroup, embedding_forward_mixed_group,  # noqa: F401
+                          mixed_group_launch_shape)
 from .grouped_backward import (GroupedGrad, embedding_backward_grouped, embedding_weight_grad_grouped,  # noqa: F401
                                grouped_backward_keys, grouped_mean_scale, grouped_table_cuts,
                                sparse_row_adam_grouped, sparse_row_update_grouped)

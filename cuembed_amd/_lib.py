@@ -191,6 +191,15 @@ def _declare(L):
                                                               _I, _I, _VP, _VP]
     L.cuembed_grouped_forward_launch_shape.restype = None
     L.cuembed_grouped_forward_launch_shape.argtypes = [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]
+    L.cuembed_embedding_forward_mixed_group.restype = None
+    L.cuembed_embedding_forward_mixed_group.argtypes = [_VP, _VP, _VP, _VP, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, _I, _VP,
+                                                        _I, _VP]
+    L.cuembed_mixed_group_descriptor_bytes.restype = ctypes.c_size_t
+    L.cuembed_mixed_group_descriptor_bytes.argtypes = [_I]
+    L.cuembed_fill_mixed_group_descriptor.restype = _I
+    L.cuembed_fill_mixed_group_descriptor.argtypes = [_VP, _I, _I, _I, _I, _I, _VP]
+    L.cuembed_mixed_group_launch_shape.restype = None
+    L.cuembed_mixed_group_launch_shape.argtypes = [_VP, _I, _I, _I, _I, _I, _I, ctypes.c_size_t, ctypes.POINTER(_I)]
     L.cuembed_grouped_backward_keys.restype = None
     L.cuembed_grouped_backward_keys.argtypes = [_VP, _I, _VP, _I, _VP, _I, _I, _I, _L, _VP, _VP, _I, _VP]
     L.cuembed_grouped_table_cuts.restype = None

@@ -17,7 +17,8 @@
 // the group) and sample_order (a permutation of the T * B bags: BagOrderByLength on the combined offsets) are honoured
 // as scheduling hints that change no bit; row_loads_device must be null (the decision is per table and nothing carries
 // T decisions); reduction_order is not consulted (there is one order: the wide-load and split kernels are not taken).
-// Groups of mixed widths or types are the caller's job: one group per width.
+// A group of mixed WIDTHS is EmbeddingForwardMixedGroup (mixed_group_lookup.hpp: plain tables, no sample_order); groups of
+// mixed element types are the caller's job: one group per type.
 #ifndef CUEMBED_INCLUDE_GROUPED_LOOKUP_HPP_
 #define CUEMBED_INCLUDE_GROUPED_LOOKUP_HPP_
 

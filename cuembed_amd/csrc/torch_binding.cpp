@@ -1481,6 +1481,91 @@ at::Tensor cuemb_embedding_quantized_grouped_op(const at::TensorList qtables, co
   return out;
 }
 
+// ---- a group of tables of DIFFERENT widths pooled in one launch (extension; forward only: no autograd formula).
+// tables / table_ptrs / idx / offsets / weights as in cuemb_embedding_grouped, except that the widths may differ (plain
+// tables only).  `descriptor` is the caller's int32 device tensor of (num_tables + 1) * 4 words, filled on the host by
+// cuembed_fill_mixed_group_descriptor for this batch and `lane_bytes` and copied to the device once
+// (cuembed_amd.MixedTableGroup.descriptor); lane_bytes is checked here against the pointers, the words cannot be.
+// Returns [batch, sum of the widths]: the per-table results concatenated on dim 1.
+at::Tensor cuemb_embedding_mixed_group_op(const at::TensorList tables, const at::Tensor& table_ptrs,
+                                          const at::Tensor& descriptor, const int64_t lane_bytes, const at::Tensor& indices,
+                                          const c10::optional<at::Tensor>& offsets,
+                                          const c10::optional<at::Tensor>& weights, const std::string& mode,
+                                          const int64_t row_loads) {
+  const int m = GroupedMode(mode);
+  const int64_t num_tables = static_cast<int64_t>(tables.size());
+  TORCH_CHECK(num_tables >= 1, "cuembed_pyt: a group needs at least one table");
+  const int elem = ElemCode(tables[0], "tables");
+  const at::DeviceGuard guard(tables[0].device());
+  std::vector<const void*> host_ptrs;
+  std::vector<int> widths;
+  int64_t dim = 0;
+  uintptr_t bits = 0;
+  for (const at::Tensor& t : tables) {
+    CheckGpu(t, "tables");
+    TORCH_CHECK(t.dim() == 2 && t.is_contiguous() && t.scalar_type() == tables[0].scalar_type() &&
+                    t.device() == tables[0].device() && t.size(1) > 0 && (t.size(1) * t.element_size()) % 4 == 0,
+                "cuembed_pyt: the tables of a mixed-width group must be contiguous [rows, width] of one dtype and device, "
+                "every row a multiple of 4 bytes");
+    TORCH_CHECK(!(at::GradMode::is_enabled() && t.requires_grad()),
+                "cuembed_pyt: a table requires grad: the grouped forward is forward only");
+    host_ptrs.push_back(t.data_ptr());
+    widths.push_back(static_cast<int>(t.size(1)));
+    dim += t.size(1);
+    bits |= reinterpret_cast<uintptr_t>(t.data_ptr());
+  }
+  TORCH_CHECK(dim <= INT32_MAX, "cuembed_pyt: the widths must sum to at most 2^31 - 1");
+  TORCH_CHECK(bits % 4 == 0, "cuembed_pyt: every table must be 4-byte aligned");
+  TORCH_CHECK(table_ptrs.is_cuda() && table_ptrs.device() == tables[0].device() && table_ptrs.scalar_type() == at::kLong &&
+                  table_ptrs.is_contiguous() && table_ptrs.numel() == num_tables,
+              "cuembed_pyt: table_ptrs must be the contiguous int64 tensor of the tables' data pointers on their device");
+  TORCH_CHECK(descriptor.is_cuda() && descriptor.device() == tables[0].device() && descriptor.scalar_type() == at::kInt &&
+                  descriptor.is_contiguous() && descriptor.numel() == (num_tables + 1) * 4,
+              "cuembed_pyt: descriptor must be the contiguous int32 tensor of (num_tables + 1) * 4 words on the tables' "
+              "device");
+  CheckGpu(indices, "indices");
+  const int idx = IndexCode(indices, "indices");
+  TORCH_CHECK(row_loads >= -1 && row_loads <= 1, "cuembed_pyt: row_loads must be -1, 0 or 1");
+  const at::Tensor i = indices.contiguous();
+  at::Tensor o, w;
+  int off = CUEMBED_I32;
+  int64_t batch = 0, hot = 0;
+  if (offsets.has_value() && offsets->defined()) {
+    CheckGpu(*offsets, "offsets");
+    off = IndexCode(*offsets, "offsets");
+    o = offsets->contiguous();
+    TORCH_CHECK(o.numel() >= 1 && (o.numel() - 1) % num_tables == 0,
+                "cuembed_pyt: offsets must hold num_tables * batch_size + 1 entries");
+    batch = (o.numel() - 1) / num_tables;
+  } else {
+    TORCH_CHECK(i.dim() == 3 && i.size(0) == num_tables && i.size(2) > 0,
+                "cuembed_pyt: without offsets, indices must be [num_tables, batch, hotness]");
+    batch = i.size(1);
+    hot = i.size(2);
+  }
+  TORCH_CHECK(num_tables * batch <= INT32_MAX, "cuembed_pyt: num_tables * batch_size must fit a 32-bit int");
+  if (weights.has_value() && weights->defined()) {
+    CheckGpu(*weights, "weights");
+    TORCH_CHECK(weights->scalar_type() == tables[0].scalar_type(), "cuembed_pyt: weights have the wrong dtype");
+    TORCH_CHECK(weights->numel() >= i.numel(), "cuembed_pyt: weights must have one entry per index");
+    w = weights->contiguous();
+  }
+  at::Tensor out = at::empty({batch, dim}, tables[0].options());
+  int shape[7];
+  ::cuembed_mixed_group_launch_shape(widths.data(), static_cast<int>(num_tables), elem, idx, static_cast<int>(batch),
+                                     static_cast<int>(hot), w.defined() ? 1 : 0,
+                                     static_cast<size_t>(bits | reinterpret_cast<uintptr_t>(out.data_ptr())), shape);
+  TORCH_CHECK(lane_bytes == shape[0] * tables[0].element_size(), "cuembed_pyt: the descriptor was filled for lanes of ",
+              lane_bytes, " bytes, these tables and this result take ", shape[0] * tables[0].element_size());
+  if (batch > 0)
+    ::cuembed_embedding_forward_mixed_group(host_ptrs.data(), static_cast<const void* const*>(table_ptrs.data_ptr()),
+                                            widths.data(), descriptor.data_ptr(), static_cast<int>(num_tables), elem,
+                                            Ptr(i), idx, Ptr(o), off, Ptr(w), static_cast<int>(batch),
+                                            static_cast<int>(hot), m, MutPtr(out), static_cast<int>(row_loads),
+                                            CurrentStream(out));
+  return out;
+}
+
 // ---- the backward of a group: keys + sample ids in front of the single-table pipeline, table cuts behind it ----------
 // idx / offsets as in cuemb_embedding_grouped; row_base = the int64 device tensor of num_tables + 1 exclusive prefix sums
 // of the tables' row counts (cuembed_amd.TableGroup.row_base_device).  narrow: int32 results (the caller knows that the
@@ -1750,6 +1835,10 @@ TORCH_LIBRARY(cuembed_pyt, m) {
   m.def(
       "cuemb_embedding_quantized_grouped(Tensor[] qtables, Tensor table_ptrs, Tensor idx, Tensor? offsets, Tensor? weights, "
       "str mode, ScalarType out_dtype, int row_loads=-1, Tensor? sample_order=None) -> Tensor");
+  // a group of plain tables of different widths pooled in one launch -> [batch, sum of widths]; forward only
+  m.def(
+      "cuemb_embedding_mixed_group(Tensor[] tables, Tensor table_ptrs, Tensor descriptor, int lane_bytes, Tensor idx, "
+      "Tensor? offsets, Tensor? weights, str mode, int row_loads=-1) -> Tensor");
   // the backward of a group: the keys in front of the single-table pipeline, the table boundaries behind it
   m.def(
       "cuembed_grouped_backward_keys(Tensor idx, Tensor? offsets, Tensor row_base, int num_tables, int batch, int "
@@ -1803,6 +1892,7 @@ TORCH_LIBRARY_IMPL(cuembed_pyt, CUDA, m) {  // HIP tensors use the CUDA dispatch
   m.impl("cuemb_embedding_quantized", cuemb_embedding_quantized_op);
   m.impl("cuemb_embedding_grouped", cuemb_embedding_grouped_op);
   m.impl("cuemb_embedding_quantized_grouped", cuemb_embedding_quantized_grouped_op);
+  m.impl("cuemb_embedding_mixed_group", cuemb_embedding_mixed_group_op);
   m.impl("cuembed_grouped_backward_keys", cuembed_grouped_backward_keys_op);
   m.impl("cuembed_grouped_table_cuts", cuembed_grouped_table_cuts_op);
   m.impl("cuembed_grouped_weight_grad", cuembed_grouped_weight_grad_op);

@@ -95,6 +95,8 @@ def _define_python_ops():
                 " str mode, int row_loads=-1, Tensor? sample_order=None) -> Tensor")
     _lib.define("cuemb_embedding_quantized_grouped(Tensor[] qtables, Tensor table_ptrs, Tensor idx, Tensor? offsets,"
                 " Tensor? weights, str mode, ScalarType out_dtype, int row_loads=-1, Tensor? sample_order=None) -> Tensor")
+    _lib.define("cuemb_embedding_mixed_group(Tensor[] tables, Tensor table_ptrs, Tensor descriptor, int lane_bytes,"
+                " Tensor idx, Tensor? offsets, Tensor? weights, str mode, int row_loads=-1) -> Tensor")
     _lib.define("cuembed_grouped_backward_keys(Tensor idx, Tensor? offsets, Tensor row_base, int num_tables, int batch,"
                 " int num_hots, bool narrow) -> (Tensor, Tensor)")
     _lib.define("cuembed_grouped_table_cuts(Tensor ids, Tensor count_word, Tensor row_base, bool last_id=False) -> Tensor")
@@ -111,6 +113,7 @@ def _define_python_ops():
     _lib.impl("cuembed_grouped_table_cuts", _grouped_table_cuts_impl, "CUDA")
     _lib.impl("cuemb_embedding_grouped", _embedding_grouped_impl, "CUDA")
     _lib.impl("cuemb_embedding_quantized_grouped", _embedding_quantized_grouped_impl, "CUDA")
+    _lib.impl("cuemb_embedding_mixed_group", _embedding_mixed_group_impl, "CUDA")
     _lib.impl("quantize_rows", _quantize_rows_impl, "CUDA")
     _lib.impl("dequantize_rows", _dequantize_rows_impl, "CUDA")
     _lib.impl("cuemb_embedding_quantized", _embedding_quantized_impl, "CUDA")
@@ -160,6 +163,8 @@ def _define_python_ops():
 #   cuemb_embedding_quantized                 only): the quantizer, its inverse, and the lookup on a fused table
 #   cuemb_embedding_grouped,                  a group of tables of one width and dtype pooled in ONE launch into
 #   cuemb_embedding_quantized_grouped         [batch, tables, width] (forward only: no autograd formula)
+#   cuemb_embedding_mixed_group               a group of plain tables of DIFFERENT widths pooled in ONE launch into
+#                                             [batch, sum of widths] (forward only: no autograd formula)
 #   cuembed_grouped_backward_keys,            the backward of a group through ONE sort and ONE scatter-add: global row
 #   cuembed_grouped_table_cuts                keys + output-row sample ids in front of the single-table pipeline, the
 #                                             table boundaries of the compressed gradient behind it
@@ -415,6 +420,24 @@ def _embedding_grouped_impl(tables, table_ptrs, idx, offsets, weights, mode, row
         _grouped_group(tables, table_ptrs), idx.contiguous(), None if offsets is None else offsets.contiguous(),
         None if weights is None else weights.contiguous(), num_hots=0 if offsets is not None else idx.shape[2], mode=mode,
         row_loads={-1: None, 0: "default", 1: "streaming"}[int(row_loads)], sample_order=sample_order)
+
+
+def _embedding_mixed_group_impl(tables, table_ptrs, descriptor, lane_bytes, idx, offsets, weights, mode, row_loads=-1):
+    from . import mixed_group as _m
+    if offsets is None:
+        _require(idx.dim() == 3, "without offsets, idx must be [num_tables, batch, hotness]")
+    group = _m.MixedTableGroup(tables, table_ptrs=table_ptrs)   # the caller's device pointers: nothing is copied here
+    batch = (offsets.numel() - 1) // len(tables) if offsets is not None else idx.shape[1]
+    _require(descriptor.is_cuda and descriptor.dtype == torch.int32 and descriptor.is_contiguous() and
+             descriptor.numel() == (len(tables) + 1) * 4,
+             "descriptor must be the contiguous int32 tensor of (num_tables + 1) * 4 words on the tables' device")
+    out = torch.empty((batch, group.embedding_dim), dtype=group.dtype, device=group.device)
+    _require(group.lane_bytes(out.data_ptr()) == lane_bytes, "the descriptor was filled for another lane width")
+    group._descriptors[(int(batch), int(lane_bytes))] = descriptor
+    return _m.embedding_forward_mixed_group(
+        group, idx.contiguous(), None if offsets is None else offsets.contiguous(),
+        None if weights is None else weights.contiguous(), num_hots=0 if offsets is not None else idx.shape[2], mode=mode,
+        row_loads={-1: None, 0: "default", 1: "streaming"}[int(row_loads)], out=out)
 
 
 def _embedding_quantized_grouped_impl(qtables, table_ptrs, idx, offsets, weights, mode, out_dtype, row_loads=-1,
@@ -721,6 +744,19 @@ def cuemb_embedding_grouped(group, idx, offsets=None, weights=None, mode="sum", 
     _forward_only(group.tables, weights)
     return torch.ops.cuembed_pyt.cuemb_embedding_grouped(list(group.tables), group.table_ptrs, idx, offsets, weights, mode,
                                                          _ops._ROW_LOADS[row_loads], sample_order)
+
+
+def cuemb_embedding_mixed_group(group, idx, offsets=None, weights=None, mode="sum", row_loads=None):
+    """cuembed_amd.embedding_forward_mixed_group as the torch op cuembed_pyt::cuemb_embedding_mixed_group: `group` is a
+    cuembed_amd.MixedTableGroup (tables of different widths; the device tensors of their pointers and of the
+    per-batch-size descriptor are built once); CSR with `offsets` (num_tables * batch + 1 entries) or fixed hotness with
+    idx [num_tables, batch, hotness].  Returns [batch, group.embedding_dim].  Forward only: no autograd formula."""
+    _forward_only(group.tables, weights)
+    batch, _ = _grouped_batch(group.num_tables, idx, offsets)
+    lane = group.lane_bytes()          # (the op's result is a fresh, 16-byte aligned tensor)
+    return torch.ops.cuembed_pyt.cuemb_embedding_mixed_group(list(group.tables), group.table_ptrs,
+                                                             group.descriptor(batch, lane), lane, idx, offsets, weights,
+                                                             mode, _ops._ROW_LOADS[row_loads])
 
 
 def cuemb_embedding_quantized_grouped(group, idx, offsets=None, weights=None, mode="sum", out_dtype=torch.float16,
@@ -1301,6 +1337,12 @@ def _grouped_fake_shape(tables, idx, offsets, width):
 def _(tables, table_ptrs, idx, offsets=None, weights=None, mode="sum", row_loads=-1, sample_order=None):
     return torch.empty(_grouped_fake_shape(tables, idx, offsets, tables[0].shape[1]), device=tables[0].device,
                        dtype=tables[0].dtype)
+
+
+@torch.library.register_fake("cuembed_pyt::cuemb_embedding_mixed_group")
+def _(tables, table_ptrs, descriptor, lane_bytes, idx, offsets=None, weights=None, mode="sum", row_loads=-1):
+    batch = (offsets.shape[0] - 1) // len(tables) if offsets is not None else idx.shape[1]
+    return torch.empty((batch, sum(t.shape[1] for t in tables)), device=tables[0].device, dtype=tables[0].dtype)
 
 
 @torch.library.register_fake("cuembed_pyt::cuemb_embedding_quantized_grouped")

@@ -28,6 +28,7 @@ import torch
 
 from . import _lib
 from .grouped import INT_MAX, _as_group
+from .mixed_group import MixedTableGroup
 from .ops import _check_dev, _index_code, _ptr, _stream
 
 MAX_CHECK_TABLES = 1023    # detail::kCheckMaxTables: the cuts and row counts of a group are staged in 16 KiB of LDS
@@ -143,9 +144,9 @@ def check_indices(indices, offsets=None, *, num_rows=None, group=None, batch_siz
     hotness, capturable when report, workspace and -- with repair -- the outputs are given).
 
     indices: int32 / int64; CSR: offsets[num_tables * batch_size + 1] (int32 / int64); fixed hotness: offsets=None,
-    num_hots=H, indices [num_tables, batch_size, H].  The rows: num_rows= (one table) or group= (a TableGroup or a list
-    of tables: group.row_base_device is what the kernel reads).  repair=True writes the repaired batch: into new
-    tensors, or into out_indices / out_offsets, each of which may be its input (in place).  report: a 4-word int64
+    num_hots=H, indices [num_tables, batch_size, H].  The rows: num_rows= (one table) or group= (a TableGroup, a
+    MixedTableGroup or a list of same-width tables: group.row_base_device is what the kernel reads).  repair=True writes
+    the repaired batch: into new tensors, or into out_indices / out_offsets, each of which may be its input (in place).  report: a 4-word int64
     device tensor to re-use (new_index_report()); workspace: a uint8 device tensor of at least
     check_indices_workspace_bytes(...) bytes, holding anything.  Returns an IndexCheck."""
     if not isinstance(indices, torch.Tensor):
@@ -154,7 +155,8 @@ def check_indices(indices, offsets=None, *, num_rows=None, group=None, batch_siz
     if (num_rows is None) == (group is None):
         raise ValueError("exactly one of num_rows= (one table) and group= (a TableGroup) must be given")
     if group is not None:
-        group = _as_group(group)
+        if not isinstance(group, MixedTableGroup):   # (a mixed-width group: only its row counts enter)
+            group = _as_group(group)
         row_counts = group.row_counts
     else:
         if isinstance(num_rows, bool) or not isinstance(num_rows, int):

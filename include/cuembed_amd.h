@@ -785,6 +785,38 @@ void cuembed_embedding_forward_quantized_grouped(const void* const* tables_host,
 void cuembed_grouped_forward_launch_shape(int quantized, int elem_type, int index_type, int embed_width, int num_tables,
                                           int batch_per_table, int num_hots, int is_csr, int is_weighted,
                                           int compute_units, int xcds, int* out);
+/* ---- a group of tables of DIFFERENT widths pooled in one launch (extension; forward only, sum / mean only, plain
+ * tables of one element type; cuembed::EmbeddingForwardMixedGroup, mixed_group_lookup.hpp) -----
+ * The input is the group's above: bag g = t * batch_per_table + b; CSR indices[nnz] / offsets[num_tables *
+ * batch_per_table + 1] / optional weights[nnz], or fixed hotness (offsets == NULL) indices[num_tables, batch_per_table,
+ * num_hots].  Table t is [rows_t, widths_host[t]], every row a multiple of 4 bytes.  ret is [batch_per_table, D],
+ * contiguous, D = the sum of the widths: bag (t, b) at ret + b * D + c_t, c_t the exclusive prefix sum of the widths --
+ * the per-table results concatenated on dimension 1, with the bits of num_tables single-table calls.
+ * The caller builds once: tables_host / tables_device as above, widths_host (host memory), and per (group,
+ * batch_per_table, lane bytes) the descriptor: cuembed_mixed_group_descriptor_bytes(num_tables) bytes, filled on the
+ * host by cuembed_fill_mixed_group_descriptor and copied to the device by the caller (4-byte aligned).  lane_bytes is
+ * the widest of 16 / 8 / 4 that every table base, ret, D * sizeof, every c_t * sizeof and every width * sizeof are a
+ * multiple of (cuembed_mixed_group_launch_shape computes it: out[0] * sizeof); block_threads is out[1] of the same
+ * call.  A descriptor filled for another lane width, batch_per_table or block size is a contract violation the library
+ * cannot see.  The library never reads device memory on the host, copies nothing per call and allocates nothing; the
+ * call is one kernel launch.  row_load_policy as above; there is no sample_order.  num_tables * batch_per_table,
+ * D and the grid must fit an int; there is no other limit on num_tables.  Misuse aborts like everywhere else. */
+void cuembed_embedding_forward_mixed_group(const void* const* tables_host, const void* const* tables_device,
+                                           const int* widths_host, const void* descriptor_device, int num_tables,
+                                           int elem_type, const void* indices, int index_type, const void* offsets,
+                                           int offset_type, const void* weights, int batch_per_table, int num_hots,
+                                           int mode, void* ret, int row_load_policy, cuembed_stream_t stream);
+size_t cuembed_mixed_group_descriptor_bytes(int num_tables);
+/* Host arithmetic only.  Entry t < num_tables of host_blob: int32 {width, c_t, L_t, first workgroup}, L_t = min(width *
+ * elem_bytes / lane_bytes, block_threads) lanes per bag, block_threads / L_t bags per workgroup; entry num_tables: {0,
+ * D, 0, grid}.  Returns the grid = sum_t ceil(batch_per_table / (block_threads / L_t)). */
+int cuembed_fill_mixed_group_descriptor(const int* widths_host, int num_tables, int elem_bytes, int lane_bytes,
+                                        int batch_per_table, int block_threads, void* host_blob);
+/* Launch shape of a mixed-width forward (no launch; host arithmetic only).  pointer_bits: the table bases and ret OR-ed
+ * (0 = aligned buffers).  out[0] = elements per lane, out[1] = block threads, out[2] = grid, out[3] = D, out[4] =
+ * dynamic LDS bytes, out[5] = 1 when the indices are staged in LDS, out[6] = the most bags a workgroup holds. */
+void cuembed_mixed_group_launch_shape(const int* widths_host, int num_tables, int elem_type, int index_type,
+                                      int batch_per_table, int num_hots, int is_weighted, size_t pointer_bits, int* out);
 /* ---- the backward of a group (extension): one sort and one scatter-add for all its tables -----
  * The group above is trained through the single-table pipeline, fed the right keys.  row_base[num_tables + 1] is the
  * exclusive prefix sum of the tables' row counts: int64, DEVICE memory, built once by the caller; row_base[num_tables]
