@@ -32,6 +32,8 @@ from .mixed_group import (MixedEmbeddingBagGroup, MixedTableGroup, embedding_for
 from .grouped_backward import (GroupedGrad, embedding_backward_grouped, embedding_weight_grad_grouped,  # noqa: F401
                                grouped_backward_keys, grouped_mean_scale, grouped_table_cuts,
                                sparse_row_adam_grouped, sparse_row_update_grouped)
+from .mixed_group_backward import (MixedGroupedGrad, embedding_backward_mixed_group,  # noqa: F401
+                                   mixed_group_backward_launch_shape, mixed_group_mean_scale)
 from .index_check import (IndexCheck, check_indices, check_indices_workspace_bytes,  # noqa: F401
                           new_index_report)
 

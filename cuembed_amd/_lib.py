@@ -200,6 +200,14 @@ def _declare(L):
     L.cuembed_fill_mixed_group_descriptor.argtypes = [_VP, _I, _I, _I, _I, _I, _VP]
     L.cuembed_mixed_group_launch_shape.restype = None
     L.cuembed_mixed_group_launch_shape.argtypes = [_VP, _I, _I, _I, _I, _I, _I, ctypes.c_size_t, ctypes.POINTER(_I)]
+    L.cuembed_embedding_backward_mixed_group.restype = None
+    L.cuembed_embedding_backward_mixed_group.argtypes = [_VP, _I, _VP, _VP, _I, _I, _L, _VP, _VP, _VP, _I, _VP, _VP, _VP,
+                                                         _L, _VP, _VP]
+    L.cuembed_mixed_group_mean_scale.restype = None
+    L.cuembed_mixed_group_mean_scale.argtypes = [_VP, _I, _VP, _VP, _VP, _I, _VP, _I, _I, _I, _VP, _VP]
+    L.cuembed_mixed_group_backward_launch_shape.restype = None
+    L.cuembed_mixed_group_backward_launch_shape.argtypes = [_VP, _I, _I, _L, _I, ctypes.c_size_t, _I, _I,
+                                                            ctypes.POINTER(_I)]
     L.cuembed_grouped_backward_keys.restype = None
     L.cuembed_grouped_backward_keys.argtypes = [_VP, _I, _VP, _I, _VP, _I, _I, _I, _L, _VP, _VP, _I, _VP]
     L.cuembed_grouped_table_cuts.restype = None

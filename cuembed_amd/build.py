@@ -25,7 +25,8 @@ UNITS = ["c_api_forward.hip", "c_api_backward.hip", "c_api_transforms.hip", "c_a
          "c_api_optimizer_adam_stochastic.hip", "c_api_optimizer_placed_stochastic.hip",
          "c_api_optimizer_adam_placed_stochastic.hip", "c_api_quantized.hip", "c_api_grouped.hip",
          "c_api_grouped_backward.hip", "c_api_row_cache.hip", "c_api_optimizer_grouped.hip",
-         "c_api_optimizer_grouped_stochastic.hip", "c_api_index_check.hip", "c_api_mixed_group.hip"]
+         "c_api_optimizer_grouped_stochastic.hip", "c_api_index_check.hip", "c_api_mixed_group.hip",
+         "c_api_mixed_group_backward.hip"]
 ARCH = "gfx950"
 
 HIPCC_FLAGS = [
@@ -282,6 +283,14 @@ def build_mixed_group_test(force=False):
     hand-written three-table group of widths 4, 8 and 2 (CSR with an empty bag, then fixed hotness) with the answers
     written in the source.  Needs a GPU to RUN (tests/test_gpu_cpp_mixed_group.py)."""
     return _build_program("tests/cpp/mixed_group_kat.hip", _O2, force)
+
+
+def build_mixed_group_backward_test(force=False):
+    """Compiles tests/cpp/mixed_group_backward_kat.hip: cuembed::GroupedBackwardKeys, cuembed::Transpose,
+    cuembed::EmbeddingBackwardMixedGroup and cuembed::MixedGroupMeanScale through the header-only API on a hand-written
+    three-table group of widths 4, 8 and 2 with the answers written in the source, sentinel-filled outputs and the
+    capacity check.  Needs a GPU to RUN (tests/test_gpu_cpp_mixed_group_backward.py)."""
+    return _build_program("tests/cpp/mixed_group_backward_kat.hip", _O2_ATOMICS, force)
 
 
 def build_sort_unit_test(force=False):

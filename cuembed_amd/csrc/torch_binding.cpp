@@ -1704,6 +1704,138 @@ at::Tensor cuembed_grouped_mean_scale_op(const at::Tensor& y_grad, const c10::op
   return out;
 }
 
+// ---- the backward of a group of tables of DIFFERENT widths: the scatter-add for all widths and the mean's scale ---------
+// What both ops check of the group: widths (host ints) and table_columns, the int32 [num_tables, 2] device tensor of
+// (c_t, W_t).  It MUST be cuembed_amd.MixedTableGroup.table_columns_device of the group the widths belong to (c_t the
+// exclusive prefix sum of the widths): its place, dtype and size are checked here, its CONTENTS are on the device and are
+// not -- the kernels address y_grad and pick their lanes from them.  Returns D.
+static int64_t CheckMixedColumns(const at::IntArrayRef widths, const at::Tensor& table_columns, const at::Tensor& y_grad,
+                                 std::vector<int>* widths_out, int64_t* max_width) {
+  const int64_t num_tables = static_cast<int64_t>(widths.size());
+  TORCH_CHECK(num_tables >= 1, "cuembed_pyt: a group needs at least one table");
+  int64_t dim = 0;
+  *max_width = 0;
+  for (const int64_t w : widths) {
+    TORCH_CHECK(w > 0 && (w * y_grad.element_size()) % 4 == 0, "cuembed_pyt: every row must be a multiple of 4 bytes");
+    dim += w;
+    TORCH_CHECK(dim <= INT32_MAX, "cuembed_pyt: the widths must sum to at most 2^31 - 1");
+    if (w > *max_width) *max_width = w;
+    widths_out->push_back(static_cast<int>(w));
+  }
+  TORCH_CHECK(table_columns.is_cuda() && table_columns.device() == y_grad.device() &&
+                  table_columns.scalar_type() == at::kInt && table_columns.is_contiguous() &&
+                  table_columns.numel() == 2 * num_tables,
+              "cuembed_pyt: table_columns must be the contiguous int32 [num_tables, 2] tensor of (column base, width) on "
+              "y_grad's device");
+  TORCH_CHECK(y_grad.dim() == 2 && y_grad.size(1) == dim, "cuembed_pyt: y_grad must be [batch, sum of the widths]");
+  return dim;
+}
+
+// y_grad [batch, D]; the sorted lookups of all tables as cuembed_transpose_* gives them for cuembed_grouped_backward_keys'
+// keys and sample ids, with the remapped ids.  Returns (rows [capacity, W_max], ids [capacity], overflow int32 [1]):
+// the compressed gradient padded to the widest table -- entry k in rows[k, :W_t], the columns past W_t unspecified --,
+// its ascending global row ids, and a word that is 1 when the device-side count (remap[-1] + 1) exceeded `capacity` and
+// nothing was written.  Entries at and past the count hold nothing.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> cuembed_embedding_backward_mixed_group_op(
+    const at::Tensor& y_grad, const at::IntArrayRef widths, const at::Tensor& table_columns,
+    const at::Tensor& transpose_indices, const at::Tensor& transpose_sample_ids,
+    const at::Tensor& transpose_remapped_indices, const c10::optional<at::Tensor>& transpose_weights,
+    const int64_t capacity) {
+  CheckGpu(y_grad, "y_grad");
+  const int elem = ElemCode(y_grad, "y_grad");
+  const at::DeviceGuard guard(y_grad.device());
+  std::vector<int> w_host;
+  int64_t max_width = 0;
+  const int64_t dim = CheckMixedColumns(widths, table_columns, y_grad, &w_host, &max_width);
+  const int64_t num_tables = static_cast<int64_t>(widths.size()), batch = y_grad.size(0);
+  TORCH_CHECK(num_tables * batch <= INT32_MAX, "cuembed_pyt: num_tables * batch must fit a 32-bit int");
+  TORCH_CHECK(capacity >= 0, "cuembed_pyt: capacity must not be negative");
+  CheckGpu(transpose_indices, "transpose_indices");
+  const int idx = IndexCode(transpose_indices, "transpose_indices");
+  const int64_t nnz = transpose_indices.numel();
+  TORCH_CHECK(nnz <= INT32_MAX, "cuembed_pyt: nnz must fit an int");
+  for (const at::Tensor* t : {&transpose_sample_ids, &transpose_remapped_indices})
+    TORCH_CHECK(t->is_cuda() && t->device() == y_grad.device() && t->scalar_type() == transpose_indices.scalar_type() &&
+                    t->numel() == nnz,
+                "cuembed_pyt: the sample ids and the remapped ids must match transpose_indices");
+  const at::Tensor g = y_grad.contiguous(), ti = transpose_indices.contiguous(), ts = transpose_sample_ids.contiguous(),
+                   tr = transpose_remapped_indices.contiguous();
+  at::Tensor tw;
+  if (transpose_weights.has_value() && transpose_weights->defined() && transpose_weights->numel() > 0) {
+    CheckGpu(*transpose_weights, "transpose_weights");
+    TORCH_CHECK(transpose_weights->scalar_type() == g.scalar_type() && transpose_weights->numel() >= nnz,
+                "cuembed_pyt: transpose_weights must have one entry per lookup, of y_grad's dtype");
+    tw = transpose_weights->contiguous();
+  }
+  at::Tensor rows = at::empty({capacity, max_width}, g.options());
+  at::Tensor ids = at::empty({capacity}, ti.options());
+  at::Tensor overflow = at::zeros({1}, g.options().dtype(at::kInt));
+  if (nnz == 0) return std::make_tuple(rows, ids, overflow);
+  if (capacity == 0) {
+    overflow.fill_(1);
+    return std::make_tuple(rows, ids, overflow);
+  }
+  // the launch's lane, by the library's rule: what both bases, D, every column base and every width allow
+  uintptr_t bits = reinterpret_cast<uintptr_t>(g.data_ptr()) | reinterpret_cast<uintptr_t>(rows.data_ptr());
+  TORCH_CHECK(bits % 4 == 0, "cuembed_pyt: y_grad must be 4-byte aligned");
+  int64_t column = 0;
+  for (const int w : w_host) {
+    column += static_cast<int64_t>(w) * g.element_size();
+    bits |= static_cast<uintptr_t>(static_cast<int64_t>(w) * g.element_size()) | static_cast<uintptr_t>(column);
+  }
+  const int64_t lane_elems = (bits % 16 == 0 ? 16 : (bits % 8 == 0 ? 8 : 4)) / g.element_size();
+  TORCH_CHECK(max_width / lane_elems <= 1024, "cuembed_pyt: the widest table is more than 1024 lanes");
+  TORCH_CHECK(batch * (dim / lane_elems) < (int64_t{1} << 31),
+              "cuembed_pyt: batch * sum of the widths / elements per lane must stay below 2^31");
+  ::cuembed_embedding_backward_mixed_group(Ptr(g), elem, w_host.data(), table_columns.data_ptr(),
+                                           static_cast<int>(num_tables), static_cast<int>(batch), nnz, Ptr(ti), Ptr(ts),
+                                           Ptr(tr), idx, Ptr(tw), MutPtr(rows), MutPtr(ids), capacity,
+                                           static_cast<uint32_t*>(overflow.data_ptr()), CurrentStream(g));
+  return std::make_tuple(rows, ids, overflow);
+}
+
+// y_grad [batch, D] of a MEAN-pooled mixed-width group times each bag's mean factor (a new tensor); offsets / weights /
+// hotness as in cuembed_grouped_mean_scale.
+at::Tensor cuembed_mixed_group_mean_scale_op(const at::Tensor& y_grad, const at::IntArrayRef widths,
+                                             const at::Tensor& table_columns, const c10::optional<at::Tensor>& offsets,
+                                             const c10::optional<at::Tensor>& weights, const int64_t hotness) {
+  CheckGpu(y_grad, "y_grad");
+  const int elem = ElemCode(y_grad, "y_grad");
+  const at::DeviceGuard guard(y_grad.device());
+  std::vector<int> w_host;
+  int64_t max_width = 0;
+  CheckMixedColumns(widths, table_columns, y_grad, &w_host, &max_width);
+  const int64_t num_tables = static_cast<int64_t>(widths.size()), batch = y_grad.size(0);
+  TORCH_CHECK(num_tables * batch <= INT32_MAX, "cuembed_pyt: num_tables * batch must fit a 32-bit int");
+  const at::Tensor g = y_grad.contiguous();
+  at::Tensor o, w;
+  int off = CUEMBED_I32;
+  int64_t nnz = num_tables * batch * hotness;
+  if (offsets.has_value() && offsets->defined()) {
+    CheckGpu(*offsets, "offsets");
+    off = IndexCode(*offsets, "offsets");
+    o = offsets->contiguous();
+    TORCH_CHECK(hotness == 0 && o.numel() == num_tables * batch + 1 && o.device() == g.device(),
+                "cuembed_pyt: CSR: hotness = 0 and offsets of num_tables * batch + 1 entries on y_grad's device");
+    nnz = -1;   // (known on the device only)
+  } else {
+    TORCH_CHECK(hotness > 0, "cuembed_pyt: fixed hotness: hotness > 0");
+  }
+  if (weights.has_value() && weights->defined()) {
+    CheckGpu(*weights, "weights");
+    TORCH_CHECK(weights->scalar_type() == g.scalar_type() && weights->device() == g.device() &&
+                    (nnz < 0 || weights->numel() >= nnz),
+                "cuembed_pyt: weights must have one entry per lookup, of y_grad's dtype, on its device");
+    w = weights->contiguous();
+  }
+  at::Tensor out = at::empty_like(g);
+  if (batch > 0)
+    ::cuembed_mixed_group_mean_scale(Ptr(g), elem, w_host.data(), table_columns.data_ptr(), Ptr(o), off, Ptr(w),
+                                     static_cast<int>(num_tables), static_cast<int>(batch), static_cast<int>(hotness),
+                                     MutPtr(out), CurrentStream(g));
+  return out;
+}
+
 // Extension (cuembed::CheckIndices): is this batch safe to hand to the row-addressing ops?  No table is read and nothing
 // is read back.  row_base: the int64 device tensor of num_tables + 1 entries of a group, or undefined and ONE table of
 // num_rows rows.  CSR: offsets of num_tables * batch + 1 entries, num_hots = 0; fixed hotness: no offsets, num_hots > 0.
@@ -1847,6 +1979,14 @@ TORCH_LIBRARY(cuembed_pyt, m) {
   // a group beyond sum pooling with table gradients: the per-lookup weight gradient, the scale of a mean's y_grad
   m.def("cuembed_grouped_weight_grad(Tensor[] tables, Tensor table_ptrs, Tensor idx, Tensor? offsets, Tensor y_grad) -> Tensor");
   m.def("cuembed_grouped_mean_scale(Tensor y_grad, Tensor? offsets, Tensor? weights, int num_tables, int hotness) -> Tensor");
+  // the backward of a mixed-width group: the scatter-add for all widths -> (padded rows, ids, overflow word); the mean's scale
+  m.def(
+      "cuembed_embedding_backward_mixed_group(Tensor y_grad, int[] widths, Tensor table_columns, Tensor transpose_indices, "
+      "Tensor transpose_sample_ids, Tensor transpose_remapped_indices, Tensor? transpose_weights, int capacity) -> "
+      "(Tensor, Tensor, Tensor)");
+  m.def(
+      "cuembed_mixed_group_mean_scale(Tensor y_grad, int[] widths, Tensor table_columns, Tensor? offsets, Tensor? weights, "
+      "int hotness) -> Tensor");
   // the device-side index check in front of the row-addressing ops: (report, repaired indices, repaired offsets)
   m.def(
       "cuembed_check_indices(Tensor indices, Tensor? offsets, Tensor? row_base, int num_rows, int num_tables, int batch, "
@@ -1897,5 +2037,7 @@ TORCH_LIBRARY_IMPL(cuembed_pyt, CUDA, m) {  // HIP tensors use the CUDA dispatch
   m.impl("cuembed_grouped_table_cuts", cuembed_grouped_table_cuts_op);
   m.impl("cuembed_grouped_weight_grad", cuembed_grouped_weight_grad_op);
   m.impl("cuembed_grouped_mean_scale", cuembed_grouped_mean_scale_op);
+  m.impl("cuembed_embedding_backward_mixed_group", cuembed_embedding_backward_mixed_group_op);
+  m.impl("cuembed_mixed_group_mean_scale", cuembed_mixed_group_mean_scale_op);
   m.impl("cuembed_check_indices", cuembed_check_indices_op);
 }

@@ -106,6 +106,13 @@ def _define_python_ops():
                 " -> Tensor")
     _lib.define("cuembed_check_indices(Tensor indices, Tensor? offsets, Tensor? row_base, int num_rows, int num_tables,"
                 " int batch, int num_hots, bool repair=False) -> (Tensor, Tensor, Tensor)")
+    _lib.define("cuembed_embedding_backward_mixed_group(Tensor y_grad, int[] widths, Tensor table_columns,"
+                " Tensor transpose_indices, Tensor transpose_sample_ids, Tensor transpose_remapped_indices,"
+                " Tensor? transpose_weights, int capacity) -> (Tensor, Tensor, Tensor)")
+    _lib.define("cuembed_mixed_group_mean_scale(Tensor y_grad, int[] widths, Tensor table_columns, Tensor? offsets,"
+                " Tensor? weights, int hotness) -> Tensor")
+    _lib.impl("cuembed_embedding_backward_mixed_group", _backward_mixed_group_impl, "CUDA")
+    _lib.impl("cuembed_mixed_group_mean_scale", _mixed_group_mean_scale_impl, "CUDA")
     _lib.impl("cuembed_check_indices", _check_indices_impl, "CUDA")
     _lib.impl("cuembed_grouped_weight_grad", _grouped_weight_grad_impl, "CUDA")
     _lib.impl("cuembed_grouped_mean_scale", _grouped_mean_scale_impl, "CUDA")
@@ -172,6 +179,10 @@ def _define_python_ops():
 #   cuembed_grouped_weight_grad,              a trained group beyond sum pooling with table gradients: the gradient with
 #   cuembed_grouped_mean_scale                respect to the per-lookup weights in ONE launch, and the launch that turns
 #                                             the y_grad of a mean-pooled group into that of the sum-pooled one
+#   cuembed_embedding_backward_mixed_group,   the backward of a MIXED-WIDTH group: the scatter-add for all widths (the
+#   cuembed_mixed_group_mean_scale            compressed gradient padded to the widest table) behind the same keys and
+#                                             sort, and the mean's scale on [batch, sum of widths]
+#                                             (cuemb_embedding_mixed_group_trainable is the autograd surface over them)
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
 _INTS = (torch.int64, torch.int32)
@@ -521,6 +532,100 @@ def _grouped_mean_scale_impl(y_grad, offsets, weights, num_tables, hotness):
             _clib.lib().cuembed_grouped_mean_scale(
                 _ops._ptr(y_grad), _ops._ELEM[y_grad.dtype], int(width), _ops._ptr(offsets),
                 0 if offsets is None else _ops._INDEX[offsets.dtype], _ops._ptr(weights), int(num_tables), int(batch),
+                int(hotness), _ops._ptr(out), _ops._stream(y_grad))
+    return out
+
+
+def _mixed_columns(y_grad, widths, table_columns):
+    """The widths as the C ABI takes them, checked against y_grad and table_columns: (ctypes array, D, W_max).
+    table_columns must be MixedTableGroup.table_columns_device of the group the widths belong to: its dtype and size are
+    checked, its contents (on the device) are not -- the kernels address y_grad and pick their lanes from them."""
+    import ctypes
+    widths = [int(w) for w in widths]
+    _require(y_grad.is_cuda and y_grad.dtype in _FLOATS, "y_grad must be a float tensor on the GPU")
+    _require(len(widths) >= 1 and all(w > 0 and (w * y_grad.element_size()) % 4 == 0 for w in widths) and
+             sum(widths) < 2 ** 31, "every row must be a multiple of 4 bytes and the widths sum to at most 2^31 - 1")
+    _require(table_columns.is_cuda and table_columns.dtype == torch.int32 and table_columns.is_contiguous() and
+             table_columns.numel() == 2 * len(widths),
+             "table_columns must be the contiguous int32 [num_tables, 2] tensor of (column base, width)")
+    _require(y_grad.dim() == 2 and y_grad.shape[1] == sum(widths), "y_grad must be [batch, sum of the widths]")
+    _require(len(widths) * y_grad.shape[0] < 2 ** 31, "num_tables * batch must fit a 32-bit int")
+    return (ctypes.c_int * len(widths))(*widths), sum(widths), max(widths)
+
+
+def _mixed_lane_elems(widths, itemsize, *pointers):
+    bits, column = 0, 0
+    for p in pointers:
+        bits |= int(p)
+    _require(bits % 4 == 0, "y_grad must be 4-byte aligned")
+    for w in widths:
+        column += int(w) * itemsize
+        bits |= (int(w) * itemsize) | column
+    return (16 if bits % 16 == 0 else (8 if bits % 8 == 0 else 4)) // itemsize
+
+
+def _backward_mixed_group_impl(y_grad, widths, table_columns, transpose_indices, transpose_sample_ids,
+                               transpose_remapped_indices, transpose_weights, capacity):
+    from . import _lib as _clib
+    w_host, dim, w_max = _mixed_columns(y_grad, widths, table_columns)
+    _require(capacity >= 0, "capacity must not be negative")
+    nnz = transpose_indices.numel()
+    _require(transpose_indices.is_cuda and transpose_indices.dtype in _INTS and nnz < 2 ** 31,
+             "transpose_indices must be an int tensor on the GPU of fewer than 2^31 entries")
+    for t in (transpose_sample_ids, transpose_remapped_indices):
+        _require(t.is_cuda and t.dtype == transpose_indices.dtype and t.numel() == nnz,
+                 "the sample ids and the remapped ids must match transpose_indices")
+    y_grad = y_grad.contiguous()
+    if transpose_weights is not None and transpose_weights.numel() == 0:
+        transpose_weights = None
+    if transpose_weights is not None:
+        _require(transpose_weights.is_cuda and transpose_weights.dtype == y_grad.dtype and
+                 transpose_weights.numel() >= nnz, "transpose_weights must have one entry per lookup, of y_grad's dtype")
+        transpose_weights = transpose_weights.contiguous()
+    dev = y_grad.device
+    rows = torch.empty((capacity, w_max), dtype=y_grad.dtype, device=dev)
+    ids = torch.empty((capacity,), dtype=transpose_indices.dtype, device=dev)
+    overflow = torch.zeros((1,), dtype=torch.int32, device=dev)
+    if nnz == 0:
+        return rows, ids, overflow
+    if capacity == 0:
+        return rows, ids, overflow.fill_(1)
+    n = _mixed_lane_elems(widths, y_grad.element_size(), y_grad.data_ptr(), rows.data_ptr())
+    _require(w_max // n <= 1024, "the widest table is more than 1024 lanes")
+    _require(y_grad.shape[0] * (dim // n) < 2 ** 31, "batch * sum of the widths / elements per lane must stay below 2^31")
+    with torch.cuda.device(dev):
+        _clib.lib().cuembed_embedding_backward_mixed_group(
+            _ops._ptr(y_grad), _ops._ELEM[y_grad.dtype], w_host, _ops._ptr(table_columns), len(widths),
+            int(y_grad.shape[0]), nnz, _ops._ptr(transpose_indices.contiguous()),
+            _ops._ptr(transpose_sample_ids.contiguous()), _ops._ptr(transpose_remapped_indices.contiguous()),
+            _ops._INDEX[transpose_indices.dtype], _ops._ptr(transpose_weights), _ops._ptr(rows), _ops._ptr(ids),
+            int(capacity), _ops._ptr(overflow), _ops._stream(y_grad))
+    return rows, ids, overflow
+
+
+def _mixed_group_mean_scale_impl(y_grad, widths, table_columns, offsets, weights, hotness):
+    from . import _lib as _clib
+    w_host, _, _ = _mixed_columns(y_grad, widths, table_columns)
+    num_tables, batch = len(widths), y_grad.shape[0]
+    y_grad = y_grad.contiguous()
+    if offsets is not None:
+        _require(offsets.is_cuda and offsets.dtype in _INTS and hotness == 0 and offsets.numel() == num_tables * batch + 1,
+                 "CSR: hotness = 0 and offsets of num_tables * batch + 1 entries")
+        offsets = offsets.contiguous()
+    else:
+        _require(hotness > 0, "fixed hotness: hotness > 0")
+    if weights is not None:
+        _require(weights.is_cuda and weights.dtype == y_grad.dtype and
+                 (offsets is not None or weights.numel() >= num_tables * batch * hotness),
+                 "weights must have one entry per lookup, of y_grad's dtype")
+        weights = weights.contiguous()
+    out = torch.empty_like(y_grad)
+    if batch > 0:
+        _mixed_lane_elems(widths, y_grad.element_size(), y_grad.data_ptr(), out.data_ptr())
+        with torch.cuda.device(y_grad.device):
+            _clib.lib().cuembed_mixed_group_mean_scale(
+                _ops._ptr(y_grad), _ops._ELEM[y_grad.dtype], w_host, _ops._ptr(table_columns), _ops._ptr(offsets),
+                0 if offsets is None else _ops._INDEX[offsets.dtype], _ops._ptr(weights), num_tables, int(batch),
                 int(hotness), _ops._ptr(out), _ops._stream(y_grad))
     return out
 
@@ -971,6 +1076,120 @@ class TrainableEmbeddingBagGroup(torch.nn.Module):
                                                  sample_order=sample_order, mode=self.mode, weight_grad=self.weight_grad)
 
 
+class _CuEmbMixedGroup(torch.autograd.Function):
+    """cuemb_embedding_mixed_group_trainable: the mixed-width forward, and the backward of all tables through one sort and
+    one scatter-add for all widths.  `params` are the group's tables."""
+
+    @staticmethod
+    def forward(ctx, group, idx, offsets, weights, mode, *params):
+        ctx.save_for_backward(idx, offsets, weights)
+        ctx.group = group
+        ctx.mode = mode
+        batch, _ = _grouped_batch(group.num_tables, idx, offsets)
+        lane = group.lane_bytes()          # (the op's result is a fresh, 16-byte aligned tensor)
+        return torch.ops.cuembed_pyt.cuemb_embedding_mixed_group(
+            [t.detach() for t in group.tables], group.table_ptrs, group.descriptor(batch, lane), lane, idx, offsets,
+            None if weights is None else weights.detach(), mode, -1)
+
+    @staticmethod
+    def backward(ctx, out_grad):
+        idx, offsets, weights = ctx.saved_tensors
+        group = ctx.group
+        T, total, base, widths = group.num_tables, group.total_rows, group.row_base, group.widths
+        wanted = ctx.needs_input_grad[5:]
+        head = (None,) * 5
+        if not any(wanted):
+            return head + (None,) * T
+        batch, hot = _grouped_batch(T, idx, offsets)
+        nnz = idx.numel()
+        dev, dtype = out_grad.device, out_grad.dtype
+        out_grad = out_grad.contiguous()
+
+        def per_table(make):
+            return head + tuple(make(t) if wanted[t] else None for t in range(T))
+
+        if nnz == 0:
+            return per_table(lambda t: _empty_sparse(base[t + 1] - base[t], widths[t], dtype, dev))
+        w = None if weights is None else weights.detach()
+        if ctx.mode == "mean":
+            out_grad = torch.ops.cuembed_pyt.cuembed_mixed_group_mean_scale(out_grad, list(widths),
+                                                                            group.table_columns_device, offsets, w, hot)
+        # ---- one key launch, one sort, one remap, one scatter-add for all tables and widths
+        keys, sample_ids = torch.ops.cuembed_pyt.cuembed_grouped_backward_keys(idx, offsets, group.row_base_device, T,
+                                                                               batch, hot, total < 2 ** 31)
+        t_keys, t_sids, t_w = cuembed_transpose_sample_ids(sample_ids, keys, None if w is None else w.reshape(-1), total)
+        remap = torch.ops.cuembed_pyt.cuembed_compute_compressed_grad_indices(t_keys)
+        rows, inv, _ = torch.ops.cuembed_pyt.cuembed_embedding_backward_mixed_group(
+            out_grad, list(widths), group.table_columns_device, t_keys, t_sids, remap, t_w if t_w.numel() else None,
+            min(nnz, total))
+        # ONE read-back, of the num_tables + 1 cuts
+        cuts = torch.ops.cuembed_pyt.cuembed_grouped_table_cuts(inv, remap[-1:], group.row_base_device, True).tolist()
+
+        def table_grad(t):
+            lo, hi = cuts[t], cuts[t + 1]
+            return torch.sparse_coo_tensor((inv[lo:hi].to(torch.int64) - base[t]).unsqueeze(0),
+                                           rows[lo:hi, :widths[t]].contiguous(), size=(base[t + 1] - base[t], widths[t]),
+                                           is_coalesced=True)
+        return per_table(table_grad)
+
+
+def cuemb_embedding_mixed_group_trainable(group_or_tables, idx, offsets=None, weights=None, num_hots=0, mode="sum"):
+    """cuemb_embedding_mixed_group (sum or mean pooling, [batch, sum of the widths]) on a cuembed_amd.MixedTableGroup --
+    or a list of tables, from which one is built -- that is TRAINED: the forward is the mixed-width op, the backward runs
+    ONE key launch, ONE sort and ONE scatter-add for all tables and widths (cuembed_amd.mixed_group_backward) instead of
+    one single-table chain per table on a column slice of out_grad.  A Python autograd.Function over the torch ops
+    cuembed_grouped_backward_keys, cuembed_embedding_backward_mixed_group, cuembed_mixed_group_mean_scale and
+    cuembed_grouped_table_cuts.
+
+    Every table that requires grad gets a COALESCED sparse COO gradient [rows_t, W_t] of exactly its looked-up rows,
+    after ONE read-back (the num_tables + 1 table cuts); its values are made contiguous per table (the compressed
+    gradient is padded to the widest table).  CSR with `offsets` (num_tables * batch + 1 entries), or fixed hotness with
+    idx [num_tables, batch, hotness] (num_hots, if given, must then agree).  mode="mean" as in
+    cuemb_embedding_grouped_trainable.  There is no weight gradient: weights that require grad raise.  With grad mode
+    off, or no table requiring grad, the call is just the forward."""
+    from . import mixed_group as _m
+    if mode not in ("sum", "mean"):
+        raise ValueError("mode must be 'sum' or 'mean', got %r: a trained group has no other pooling" % (mode,))
+    group = _m._as_mixed_group(group_or_tables)
+    if weights is not None and weights.requires_grad:
+        raise ValueError("the mixed-width backward does not take the weight gradient: detach the weights")
+    if offsets is None and num_hots and (idx.dim() != 3 or idx.shape[2] != num_hots):
+        raise ValueError("without offsets, idx must be [num_tables, batch, num_hots = %d]" % num_hots)
+    if offsets is not None and num_hots:
+        raise ValueError("either CSR (offsets given, num_hots == 0) or fixed hotness (offsets None)")
+    if not torch.is_grad_enabled() or not any(t.requires_grad for t in group.tables):
+        with torch.no_grad():
+            return cuemb_embedding_mixed_group(group, idx, offsets, None if weights is None else weights.detach(), mode)
+    return _CuEmbMixedGroup.apply(group, idx, offsets, weights, mode, *group.tables)
+
+
+class TrainableMixedEmbeddingBagGroup(torch.nn.Module):
+    """A MixedTableGroup that is trained, with MixedEmbeddingBagGroup's call shape (mode "sum" or "mean"): bags(idx,
+    offsets, weights) with CSR offsets, or bags(idx) with idx [num_tables, batch, hotness]; returns [batch, sum of the
+    widths] and differentiates through cuemb_embedding_mixed_group_trainable: every table that is an nn.Parameter gets a
+    coalesced sparse gradient.  parameters() yields those tables."""
+
+    def __init__(self, tables, mode="sum"):
+        super().__init__()
+        from . import mixed_group as _m
+        if mode not in ("sum", "mean"):
+            raise ValueError("mode must be 'sum' or 'mean'")
+        self.group = _m._as_mixed_group(tables)
+        self.mode = mode
+        self.tables = torch.nn.ParameterList([t for t in self.group.tables if isinstance(t, torch.nn.Parameter)])
+
+    @property
+    def num_tables(self):
+        return self.group.num_tables
+
+    @property
+    def embedding_dim(self):
+        return self.group.embedding_dim
+
+    def forward(self, idx, offsets=None, weights=None):
+        return cuemb_embedding_mixed_group_trainable(self.group, idx, offsets, weights, mode=self.mode)
+
+
 def cuembed_forward(params, idx, offsets, weights, hints=None):
     if hints is None:
         return cuembed_embedding_forward(params, idx, offsets, weights, mode="sum")
@@ -1370,6 +1589,19 @@ def _(tables, table_ptrs, idx, offsets, y_grad):
 
 @torch.library.register_fake("cuembed_pyt::cuembed_grouped_mean_scale")
 def _(y_grad, offsets, weights, num_tables, hotness):
+    return torch.empty(y_grad.shape, device=y_grad.device, dtype=y_grad.dtype)
+
+
+@torch.library.register_fake("cuembed_pyt::cuembed_embedding_backward_mixed_group")
+def _(y_grad, widths, table_columns, transpose_indices, transpose_sample_ids, transpose_remapped_indices,
+      transpose_weights, capacity):
+    return (torch.empty((capacity, max(widths)), device=y_grad.device, dtype=y_grad.dtype),
+            torch.empty((capacity,), device=y_grad.device, dtype=transpose_indices.dtype),
+            torch.empty((1,), device=y_grad.device, dtype=torch.int32))
+
+
+@torch.library.register_fake("cuembed_pyt::cuembed_mixed_group_mean_scale")
+def _(y_grad, widths, table_columns, offsets, weights, hotness):
     return torch.empty(y_grad.shape, device=y_grad.device, dtype=y_grad.dtype)
 
 

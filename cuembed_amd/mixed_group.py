@@ -1,5 +1,5 @@
-"""The forward on a group of embedding tables of DIFFERENT widths in one launch (an extension: forward only, sum / mean
-only, plain fp32 / fp16 / bf16 tables of one dtype).
+"""The forward on a group of embedding tables of DIFFERENT widths in one launch (an extension: sum / mean only, plain
+fp32 / fp16 / bf16 tables of one dtype).
 
 cuembed_amd.grouped pools T tables of ONE width; a model whose widths follow the tables' cardinality would need one such
 group per width and a torch.cat over the results.  Here the widths may all differ and the kernel writes the
@@ -20,8 +20,10 @@ Every function validates its arguments and raises before any launch; the kernel 
 (cuembed::EmbeddingForwardMixedGroup through the C ABI).  The kernel reads a small per-table descriptor from device
 memory; MixedTableGroup builds it once per (batch size, lane width) -- one host-to-device copy at the FIRST call of a
 shape (or at group.descriptor(B, lane_bytes)), none afterwards -- so with `out=` given every later call copies nothing,
-allocates nothing and can be captured into a HIP graph.  Nothing here is differentiable, and there is no sample_order,
-no per-table row-load decision, no quantized and no mixed-dtype group.
+allocates nothing and can be captured into a HIP graph.  The functions here are forward only and refuse tensors that
+require grad; the backward is cuembed_amd.mixed_group_backward (autograd:
+cuembed_pyt.cuemb_embedding_mixed_group_trainable).  There is no sample_order, no per-table row-load decision, no
+quantized and no mixed-dtype group.
 """
 import ctypes
 
@@ -87,6 +89,7 @@ class MixedTableGroup:
             raise ValueError("table_ptrs must be the contiguous int64 tensor of the tables' data pointers on their device")
         self.table_ptrs = table_ptrs
         self._row_base_device = None
+        self._table_columns_device = None
         self._descriptors = {}
 
     def __len__(self):
@@ -119,6 +122,15 @@ class MixedTableGroup:
         if self._row_base_device is None:
             self._row_base_device = torch.tensor(self.row_base, dtype=torch.int64, device=self.device)
         return self._row_base_device
+
+    @property
+    def table_columns_device(self):
+        """int32 [num_tables, 2] on the device: (column base c_t, width W_t) of every table in elements -- what the
+        backward's kernels read per lookup (cuembed_amd.mixed_group_backward).  Built at the first use, once."""
+        if self._table_columns_device is None:
+            self._table_columns_device = torch.tensor(list(zip(self.column_base[:-1], self.widths)), dtype=torch.int32,
+                                                      device=self.device)
+        return self._table_columns_device
 
     def lane_bytes(self, out_ptr=0):
         """Bytes of a row one lane moves (16, 8 or 4), ONE value for the launch: the widest that every table base,

@@ -785,7 +785,8 @@ void cuembed_embedding_forward_quantized_grouped(const void* const* tables_host,
 void cuembed_grouped_forward_launch_shape(int quantized, int elem_type, int index_type, int embed_width, int num_tables,
                                           int batch_per_table, int num_hots, int is_csr, int is_weighted,
                                           int compute_units, int xcds, int* out);
-/* ---- a group of tables of DIFFERENT widths pooled in one launch (extension; forward only, sum / mean only, plain
+/* ---- a group of tables of DIFFERENT widths pooled in one launch (extension; sum / mean only, its backward:
+ * cuembed_embedding_backward_mixed_group below; plain
  * tables of one element type; cuembed::EmbeddingForwardMixedGroup, mixed_group_lookup.hpp) -----
  * The input is the group's above: bag g = t * batch_per_table + b; CSR indices[nnz] / offsets[num_tables *
  * batch_per_table + 1] / optional weights[nnz], or fixed hotness (offsets == NULL) indices[num_tables, batch_per_table,
@@ -863,6 +864,47 @@ void cuembed_embedding_weight_grad_grouped(const void* const* tables_host, const
 void cuembed_grouped_mean_scale(const void* grad_y, int elem_type, int embed_width, const void* offsets,
                                 int offset_type, const void* weights, int num_tables, int batch_per_table, int num_hots,
                                 void* out, cuembed_stream_t stream);
+/* ---- the backward of a group of tables of DIFFERENT widths (extension): one sort and one scatter-add for all widths -----
+ * The mixed-width group above (cuembed_embedding_forward_mixed_group: grad_y is the gradient of ret, [batch_per_table, D])
+ * is trained through the sequence above with ONE call replaced:
+ *   cuembed_grouped_backward_keys, cuembed_transpose_remapped           unchanged (sample ids b * num_tables + t)
+ *   cuembed_embedding_backward_mixed_group                              for cuembed_embedding_backward
+ *   cuembed_grouped_table_cuts                                          unchanged
+ * The result is a compressed gradient PADDED to the widest table: inverse_mapping[k] = ascending global row ids,
+ * grad_embedding [capacity, W_max], the gradient of entry k in grad_embedding[k * W_max, k * W_max + W_t) for the table t
+ * its id falls in.  Columns >= W_t of an entry are UNSPECIFIED (untouched or zero); nothing in the library reads them.
+ * The count is device-side only: transpose_remapped_indices[nnz - 1] + 1.  capacity_rows > 0: the rows the two outputs
+ * hold; if the count exceeds it nothing is written and *capacity_overflow (device word, may be NULL) is OR-ed with 1;
+ * 0 = unchecked.  widths_host: host memory.  table_columns_device: int32 [num_tables][2] = (c_t, W_t) in elements,
+ * DEVICE memory, 8-byte aligned, built once by the caller -- it MUST agree with widths_host (c_t the exclusive prefix sum):
+ * the kernel addresses grad_y and picks its lanes from it, and the library, which never reads device memory on the host,
+ * cannot check that.  Arithmetic: cuembed_embedding_backward's default.  One lane
+ * width for the launch: the widest of 16 / 8 / 4 bytes that grad_y, grad_embedding, D * sizeof, every c_t * sizeof and
+ * every W_t * sizeof are a multiple of.  Limits: num_tables * batch_per_table and nnz <= INT_MAX, W_max at most 1024
+ * lanes, batch_per_table * D * sizeof / lane bytes < 2^31; no other limit on num_tables.  Allocates nothing, reads
+ * nothing back, capturable.  Not available for a mixed group: the dense gradient, reference sums, the sample-blocked
+ * order, pad_to_capacity, the weight gradient and a one-launch optimizer step. */
+void cuembed_embedding_backward_mixed_group(const void* grad_y, int elem_type, const int* widths_host,
+                                            const void* table_columns_device, int num_tables, int batch_per_table,
+                                            int64_t nnz, const void* transpose_indices, const void* transpose_sample_ids,
+                                            const void* transpose_remapped_indices, int index_type,
+                                            const void* transpose_weights, void* grad_embedding, void* inverse_mapping,
+                                            int64_t capacity_rows, uint32_t* capacity_overflow, cuembed_stream_t stream);
+/* cuembed::MixedGroupMeanScale: cuembed_grouped_mean_scale on the [batch_per_table, D] layout, in one launch:
+ * out[b, c_t + j] = grad_y[b, c_t + j] * f, f the mean factor of bag t * batch_per_table + b.  The bits of num_tables
+ * cuembed_grouped_mean_scale calls on one-table groups (aligned buffers).  out may be grad_y. */
+void cuembed_mixed_group_mean_scale(const void* grad_y, int elem_type, const int* widths_host,
+                                    const void* table_columns_device, const void* offsets, int offset_type,
+                                    const void* weights, int num_tables, int batch_per_table, int num_hots, void* out,
+                                    cuembed_stream_t stream);
+/* Launch shape of cuembed_embedding_backward_mixed_group (no launch; host arithmetic only when compute_units > 0): the
+ * plan of cuembed_backward_launch_shape at W_max.  pointer_bits: grad_y and grad_embedding OR-ed (0 = aligned buffers).
+ * out[0] = elements per lane, out[1] = lanes of a workgroup's column slice, out[2] = segments per workgroup, out[3] =
+ * segment length, out[4] = column slices, out[5] = grid, out[6] = dynamic LDS bytes, out[7] = lookups per workgroup,
+ * out[8] = W_max, out[9] = D. */
+void cuembed_mixed_group_backward_launch_shape(const int* widths_host, int num_tables, int elem_type, int64_t nnz,
+                                               int is_weighted, size_t pointer_bits, int compute_units, int xcds,
+                                               int* out);
 /* ---- extension: the sparse optimizer step on a group of SEPARATE table tensors, in one launch ---------------------------
  * cuembed::SparseRowUpdateGrouped: cuembed_sparse_row_update on num_tables tables of elem_type and embed_width that are
  * separate allocations.  ids (index_type) are GLOBAL rows of the tables laid end to end -- the compressed gradient of
