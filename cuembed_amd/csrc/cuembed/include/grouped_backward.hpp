@@ -32,6 +32,7 @@
 #include <cstdint>
 
 #include "cuembed/include/cuembed_assert.hpp"
+#include "cuembed/include/group_host_plan.hpp"
 #include "cuembed/include/grouped_backward_kernels.hpp"
 #include "cuembed/include/grouped_lookup.hpp"
 #include "cuembed/include/grouped_train_kernels.hpp"
@@ -151,11 +152,8 @@ void EmbeddingWeightGradGrouped(const InputT* const* tables_host,
   CUEMBED_ASSERT(indices != nullptr && grad_y != nullptr && grad_weights != nullptr);
   const void* bits = detail::GroupAlignmentBits(reinterpret_cast<const void* const*>(tables_host), num_tables);
   const detail::RowSplit split = detail::SplitRow<ElemT>(embed_width, bits, grad_y);
-  int group = 1;
-  while (group < split.lanes_per_row && group < 64) group *= 2;
-  const int bags_per_block = detail::kDefaultBlockThreads / group;
-  const dim3 block(group, bags_per_block, 1);
-  const dim3 grid((batch + bags_per_block - 1) / bags_per_block, 1, 1);
+  const detail::LaneGroupShape shape = detail::PlanLaneGroups(split.lanes_per_row, batch);
+  const dim3 block = shape.block, grid = shape.grid;
   const ElemT* const* tables = reinterpret_cast<const ElemT* const*>(tables_device);
   const ElemT* gy = reinterpret_cast<const ElemT*>(grad_y);
   ElemT* gw = reinterpret_cast<ElemT*>(grad_weights);
@@ -192,11 +190,8 @@ void GroupedMeanScale(const InputT* grad_y,
   if (rows <= 0) return;
   CUEMBED_ASSERT(grad_y != nullptr && out != nullptr);
   const detail::RowSplit split = detail::SplitRow<ElemT>(embed_width, grad_y, out);
-  int group = 1;
-  while (group < split.lanes_per_row && group < 64) group *= 2;
-  const int rows_per_block = detail::kDefaultBlockThreads / group;
-  const dim3 block(group, rows_per_block, 1);
-  const dim3 grid((rows + rows_per_block - 1) / rows_per_block, 1, 1);
+  const detail::LaneGroupShape shape = detail::PlanLaneGroups(split.lanes_per_row, rows);
+  const dim3 block = shape.block, grid = shape.grid;
   const ElemT* gy = reinterpret_cast<const ElemT*>(grad_y);
   const ElemT* w = reinterpret_cast<const ElemT*>(weights);
   ElemT* o = reinterpret_cast<ElemT*>(out);

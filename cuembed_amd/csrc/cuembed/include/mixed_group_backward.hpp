@@ -33,38 +33,13 @@
 
 #include "cuembed/include/cuembed_assert.hpp"
 #include "cuembed/include/embedding_backward.hpp"
+#include "cuembed/include/group_host_plan.hpp"
 #include "cuembed/include/index_kernels.hpp"
 #include "cuembed/include/mixed_group_scatter_kernels.hpp"
 
 namespace cuembed {
 
 namespace detail {
-
-//! What one pass over the widths gives.
-struct MixedGroupColumns {
-  int out_width;    //!< D
-  int max_width;    //!< W_max
-  int lane_bytes;   //!< the launch's lane: 16, 8 or 4
-};
-
-//! D, W_max and the widest lane that the address bits `bits` (grad_y and the gradient base OR-ed) and every row pitch
-//! and column offset allow.  Host only.
-inline MixedGroupColumns PlanMixedGroupColumns(const int* widths_host, const int num_tables, const int elem_bytes,
-                                               uintptr_t bits) {
-  CUEMBED_ASSERT(widths_host != nullptr && num_tables >= 1 && (elem_bytes == 2 || elem_bytes == 4));
-  CUEMBED_ASSERT(bits % 4 == 0);
-  int64_t column = 0;
-  int max_width = 0;
-  for (int t = 0; t < num_tables; ++t) {
-    const int64_t row_bytes = static_cast<int64_t>(widths_host[t]) * elem_bytes;
-    CUEMBED_ASSERT(widths_host[t] > 0 && row_bytes % 4 == 0);
-    column += widths_host[t];
-    CUEMBED_ASSERT(column <= INT_MAX);
-    bits |= static_cast<uintptr_t>(row_bytes) | static_cast<uintptr_t>(column * elem_bytes);
-    if (widths_host[t] > max_width) max_width = widths_host[t];
-  }
-  return MixedGroupColumns{static_cast<int>(column), max_width, bits % 16 == 0 ? 16 : (bits % 8 == 0 ? 8 : 4)};
-}
 
 //! Launch shape of MixedGroupScatterAddKernel: PlanScatter's for W_max (so SetBackwardTuning applies), with the LDS
 //! of MixedScatterStage.
@@ -219,11 +194,8 @@ void MixedGroupMeanScale(const InputT* grad_y,
   const detail::MixedGroupColumns columns = detail::PlanMixedGroupColumns(
       widths_host, num_tables, kElemBytes, reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(out));
   const int lane_elems = columns.lane_bytes / kElemBytes;
-  int group = 1;
-  while (group < columns.max_width / lane_elems && group < 64) group *= 2;
-  const int per_block = detail::kDefaultBlockThreads / group;
-  const dim3 block(group, per_block, 1);
-  const dim3 grid((rows + per_block - 1) / per_block, 1, 1);
+  const detail::LaneGroupShape shape = detail::PlanLaneGroups(columns.max_width / lane_elems, rows);
+  const dim3 block = shape.block, grid = shape.grid;
   const ElemT* gy = reinterpret_cast<const ElemT*>(grad_y);
   const ElemT* w = reinterpret_cast<const ElemT*>(weights);
   ElemT* o = reinterpret_cast<ElemT*>(out);

@@ -35,6 +35,7 @@
 
 #include "cuembed/include/cuembed_assert.hpp"
 #include "cuembed/include/embedding_lookup.hpp"
+#include "cuembed/include/group_host_plan.hpp"
 #include "cuembed/include/grouped_lookup.hpp"
 #include "cuembed/include/mixed_group_gather_kernels.hpp"
 
@@ -80,21 +81,6 @@ inline MixedGroupPlan PlanMixedGroup(const int* widths_host, const int num_table
   plan.grid = static_cast<int>(blocks);
   plan.out_width = static_cast<int>(column);
   return plan;
-}
-
-//! The widest lane (16, 8 or 4 bytes) that the address bits `bits` (table bases and ret OR-ed) and every row pitch and
-//! column offset of the group allow.
-inline int MixedGroupLaneBytesOfBits(uintptr_t bits, const int* widths_host, const int num_tables, const int elem_bytes) {
-  CUEMBED_ASSERT(widths_host != nullptr && num_tables >= 1 && (elem_bytes == 2 || elem_bytes == 4));
-  CUEMBED_ASSERT(bits % 4 == 0);
-  int64_t column = 0;
-  for (int t = 0; t < num_tables; ++t) {
-    const int64_t row_bytes = static_cast<int64_t>(widths_host[t]) * elem_bytes;
-    CUEMBED_ASSERT(widths_host[t] > 0 && row_bytes % 4 == 0);
-    column += row_bytes;                      // (c_{t+1} * sizeof; the last one is D * sizeof)
-    bits |= static_cast<uintptr_t>(row_bytes) | static_cast<uintptr_t>(column);
-  }
-  return bits % 16 == 0 ? 16 : (bits % 8 == 0 ? 8 : 4);
 }
 
 //! Dynamic LDS of the staged kernel: fixed hotness whose widest workgroup's indices (+ weights) fit the staging budget of

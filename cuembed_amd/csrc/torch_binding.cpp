@@ -1370,56 +1370,79 @@ struct GroupedCall {
   int64_t batch = 0, hot = 0;
 };
 
-GroupedCall CheckGroupedCall(const at::TensorList tables, const at::Tensor& table_ptrs, const at::Tensor& indices,
-                             const c10::optional<at::Tensor>& offsets, const c10::optional<at::Tensor>& weights,
-                             const at::ScalarType weight_type, const int64_t row_loads,
-                             const c10::optional<at::Tensor>& sample_order) {
-  GroupedCall c;
+// The tables of a group and the device tensor of their pointers.  one_width: a same-width group; else any widths, every
+// row a multiple of 4 bytes.  Returns the host copy of the base pointers.
+std::vector<const void*> CheckGroupTables(const at::TensorList tables, const at::Tensor& table_ptrs, const bool one_width) {
+  std::vector<const void*> host_ptrs;
   const int64_t num_tables = static_cast<int64_t>(tables.size());
   TORCH_CHECK(num_tables >= 1, "cuembed_pyt: a group needs at least one table");
   for (const at::Tensor& t : tables) {
     CheckGpu(t, "tables");
     TORCH_CHECK(t.dim() == 2 && t.is_contiguous() && t.scalar_type() == tables[0].scalar_type() &&
-                    t.size(1) == tables[0].size(1) && t.device() == tables[0].device(),
-                "cuembed_pyt: the tables of a group must be contiguous [rows, width] of one dtype, width and device");
+                    t.device() == tables[0].device() &&
+                    (one_width ? t.size(1) == tables[0].size(1) : t.size(1) > 0 && (t.size(1) * t.element_size()) % 4 == 0),
+                one_width
+                    ? "cuembed_pyt: the tables of a group must be contiguous [rows, width] of one dtype, width and device"
+                    : "cuembed_pyt: the tables of a mixed-width group must be contiguous [rows, width] of one dtype and "
+                      "device, every row a multiple of 4 bytes");
     TORCH_CHECK(!(at::GradMode::is_enabled() && t.requires_grad()),
                 "cuembed_pyt: a table requires grad: the grouped forward is forward only");
-    c.host_ptrs.push_back(t.data_ptr());
+    host_ptrs.push_back(t.data_ptr());
   }
   TORCH_CHECK(table_ptrs.is_cuda() && table_ptrs.device() == tables[0].device() && table_ptrs.scalar_type() == at::kLong &&
                   table_ptrs.is_contiguous() && table_ptrs.numel() == num_tables,
               "cuembed_pyt: table_ptrs must be the contiguous int64 tensor of the tables' data pointers on their device");
+  return host_ptrs;
+}
+
+// The batch of a grouped call -- indices / offsets / weights / sample_order -- into `c`: CSR xor fixed hotness, the batch
+// size, and the contiguous tensors.
+void CheckGroupedBatch(GroupedCall* c, const int64_t num_tables, const at::Tensor& indices,
+                       const c10::optional<at::Tensor>& offsets, const c10::optional<at::Tensor>& weights,
+                       const at::ScalarType weight_type, const int64_t row_loads,
+                       const c10::optional<at::Tensor>& sample_order) {
   CheckGpu(indices, "indices");
-  c.idx = IndexCode(indices, "indices");
+  c->idx = IndexCode(indices, "indices");
   TORCH_CHECK(row_loads >= -1 && row_loads <= 1, "cuembed_pyt: row_loads must be -1, 0 or 1");
-  c.i = indices.contiguous();
+  c->i = indices.contiguous();
   const bool csr = offsets.has_value() && offsets->defined();
   if (csr) {
     CheckGpu(*offsets, "offsets");
-    c.off = IndexCode(*offsets, "offsets");
-    c.o = offsets->contiguous();
-    TORCH_CHECK(c.o.numel() >= 1 && (c.o.numel() - 1) % num_tables == 0,
+    c->off = IndexCode(*offsets, "offsets");
+    c->o = offsets->contiguous();
+    TORCH_CHECK(c->o.numel() >= 1 && (c->o.numel() - 1) % num_tables == 0,
                 "cuembed_pyt: offsets must hold num_tables * batch_size + 1 entries");
-    c.batch = (c.o.numel() - 1) / num_tables;
+    c->batch = (c->o.numel() - 1) / num_tables;
   } else {
-    TORCH_CHECK(c.i.dim() == 3 && c.i.size(0) == num_tables && c.i.size(2) > 0,
+    TORCH_CHECK(c->i.dim() == 3 && c->i.size(0) == num_tables && c->i.size(2) > 0,
                 "cuembed_pyt: without offsets, indices must be [num_tables, batch, hotness]");
-    c.batch = c.i.size(1);
-    c.hot = c.i.size(2);
+    c->batch = c->i.size(1);
+    c->hot = c->i.size(2);
   }
-  TORCH_CHECK(num_tables * c.batch <= INT32_MAX, "cuembed_pyt: num_tables * batch_size must fit a 32-bit int");
+  TORCH_CHECK(num_tables * c->batch <= INT32_MAX, "cuembed_pyt: num_tables * batch_size must fit a 32-bit int");
   if (weights.has_value() && weights->defined()) {
     CheckGpu(*weights, "weights");
     TORCH_CHECK(weights->scalar_type() == weight_type, "cuembed_pyt: weights have the wrong dtype");
-    TORCH_CHECK(weights->numel() >= c.i.numel(), "cuembed_pyt: weights must have one entry per index");
-    c.w = weights->contiguous();
+    TORCH_CHECK(weights->numel() >= c->i.numel(), "cuembed_pyt: weights must have one entry per index");
+    c->w = weights->contiguous();
   }
   if (sample_order.has_value() && sample_order->defined()) {
-    c.order = *sample_order;
-    TORCH_CHECK(csr && c.order.is_cuda() && c.order.scalar_type() == at::kInt &&
-                    c.order.numel() == num_tables * c.batch && c.order.is_contiguous(),
+    c->order = *sample_order;
+    TORCH_CHECK(csr && c->order.is_cuda() && c->order.scalar_type() == at::kInt &&
+                    c->order.numel() == num_tables * c->batch && c->order.is_contiguous(),
                 "cuembed_pyt: sample_order (CSR only) must be a contiguous int32 permutation of the bags on the GPU");
   }
+}
+
+// Both, for a same-width group.
+GroupedCall CheckGroupedCall(const at::TensorList tables, const at::Tensor& table_ptrs, const at::Tensor& indices,
+                             const c10::optional<at::Tensor>& offsets, const c10::optional<at::Tensor>& weights,
+                             const at::ScalarType weight_type, const int64_t row_loads,
+                             const c10::optional<at::Tensor>& sample_order) {
+  GroupedCall c;
+  c.host_ptrs = CheckGroupTables(tables, table_ptrs, true);
+  CheckGroupedBatch(&c, static_cast<int64_t>(tables.size()), indices, offsets, weights, weight_type, row_loads,
+                    sample_order);
   return c;
 }
 
@@ -1497,59 +1520,26 @@ at::Tensor cuemb_embedding_mixed_group_op(const at::TensorList tables, const at:
   TORCH_CHECK(num_tables >= 1, "cuembed_pyt: a group needs at least one table");
   const int elem = ElemCode(tables[0], "tables");
   const at::DeviceGuard guard(tables[0].device());
-  std::vector<const void*> host_ptrs;
+  GroupedCall c;
+  c.host_ptrs = CheckGroupTables(tables, table_ptrs, false);
   std::vector<int> widths;
   int64_t dim = 0;
   uintptr_t bits = 0;
   for (const at::Tensor& t : tables) {
-    CheckGpu(t, "tables");
-    TORCH_CHECK(t.dim() == 2 && t.is_contiguous() && t.scalar_type() == tables[0].scalar_type() &&
-                    t.device() == tables[0].device() && t.size(1) > 0 && (t.size(1) * t.element_size()) % 4 == 0,
-                "cuembed_pyt: the tables of a mixed-width group must be contiguous [rows, width] of one dtype and device, "
-                "every row a multiple of 4 bytes");
-    TORCH_CHECK(!(at::GradMode::is_enabled() && t.requires_grad()),
-                "cuembed_pyt: a table requires grad: the grouped forward is forward only");
-    host_ptrs.push_back(t.data_ptr());
     widths.push_back(static_cast<int>(t.size(1)));
     dim += t.size(1);
     bits |= reinterpret_cast<uintptr_t>(t.data_ptr());
   }
   TORCH_CHECK(dim <= INT32_MAX, "cuembed_pyt: the widths must sum to at most 2^31 - 1");
   TORCH_CHECK(bits % 4 == 0, "cuembed_pyt: every table must be 4-byte aligned");
-  TORCH_CHECK(table_ptrs.is_cuda() && table_ptrs.device() == tables[0].device() && table_ptrs.scalar_type() == at::kLong &&
-                  table_ptrs.is_contiguous() && table_ptrs.numel() == num_tables,
-              "cuembed_pyt: table_ptrs must be the contiguous int64 tensor of the tables' data pointers on their device");
   TORCH_CHECK(descriptor.is_cuda() && descriptor.device() == tables[0].device() && descriptor.scalar_type() == at::kInt &&
                   descriptor.is_contiguous() && descriptor.numel() == (num_tables + 1) * 4,
               "cuembed_pyt: descriptor must be the contiguous int32 tensor of (num_tables + 1) * 4 words on the tables' "
               "device");
-  CheckGpu(indices, "indices");
-  const int idx = IndexCode(indices, "indices");
-  TORCH_CHECK(row_loads >= -1 && row_loads <= 1, "cuembed_pyt: row_loads must be -1, 0 or 1");
-  const at::Tensor i = indices.contiguous();
-  at::Tensor o, w;
-  int off = CUEMBED_I32;
-  int64_t batch = 0, hot = 0;
-  if (offsets.has_value() && offsets->defined()) {
-    CheckGpu(*offsets, "offsets");
-    off = IndexCode(*offsets, "offsets");
-    o = offsets->contiguous();
-    TORCH_CHECK(o.numel() >= 1 && (o.numel() - 1) % num_tables == 0,
-                "cuembed_pyt: offsets must hold num_tables * batch_size + 1 entries");
-    batch = (o.numel() - 1) / num_tables;
-  } else {
-    TORCH_CHECK(i.dim() == 3 && i.size(0) == num_tables && i.size(2) > 0,
-                "cuembed_pyt: without offsets, indices must be [num_tables, batch, hotness]");
-    batch = i.size(1);
-    hot = i.size(2);
-  }
-  TORCH_CHECK(num_tables * batch <= INT32_MAX, "cuembed_pyt: num_tables * batch_size must fit a 32-bit int");
-  if (weights.has_value() && weights->defined()) {
-    CheckGpu(*weights, "weights");
-    TORCH_CHECK(weights->scalar_type() == tables[0].scalar_type(), "cuembed_pyt: weights have the wrong dtype");
-    TORCH_CHECK(weights->numel() >= i.numel(), "cuembed_pyt: weights must have one entry per index");
-    w = weights->contiguous();
-  }
+  CheckGroupedBatch(&c, num_tables, indices, offsets, weights, tables[0].scalar_type(), row_loads, c10::nullopt);
+  const int idx = c.idx, off = c.off;
+  const int64_t batch = c.batch, hot = c.hot;
+  const at::Tensor &i = c.i, &o = c.o, &w = c.w;
   at::Tensor out = at::empty({batch, dim}, tables[0].options());
   int shape[7];
   ::cuembed_mixed_group_launch_shape(widths.data(), static_cast<int>(num_tables), elem, idx, static_cast<int>(batch),
@@ -1558,7 +1548,7 @@ at::Tensor cuemb_embedding_mixed_group_op(const at::TensorList tables, const at:
   TORCH_CHECK(lane_bytes == shape[0] * tables[0].element_size(), "cuembed_pyt: the descriptor was filled for lanes of ",
               lane_bytes, " bytes, these tables and this result take ", shape[0] * tables[0].element_size());
   if (batch > 0)
-    ::cuembed_embedding_forward_mixed_group(host_ptrs.data(), static_cast<const void* const*>(table_ptrs.data_ptr()),
+    ::cuembed_embedding_forward_mixed_group(c.host_ptrs.data(), static_cast<const void* const*>(table_ptrs.data_ptr()),
                                             widths.data(), descriptor.data_ptr(), static_cast<int>(num_tables), elem,
                                             Ptr(i), idx, Ptr(o), off, Ptr(w), static_cast<int>(batch),
                                             static_cast<int>(hot), m, MutPtr(out), static_cast<int>(row_loads),
@@ -1662,6 +1652,38 @@ at::Tensor cuembed_grouped_weight_grad_op(const at::TensorList tables, const at:
   return out;
 }
 
+// The batch of a mean scale: the batch size is y_grad's, so only the offsets (CSR, hotness = 0) or the hotness, and the
+// weights (one per lookup, of the dtype and on the device of `like`, the contiguous y_grad) are left to check.
+struct MeanScaleBatch {
+  at::Tensor o, w;
+  int off = CUEMBED_I32;
+};
+
+MeanScaleBatch CheckMeanScaleBatch(const c10::optional<at::Tensor>& offsets, const c10::optional<at::Tensor>& weights,
+                                   const int64_t num_tables, const int64_t batch, const int64_t hotness,
+                                   const at::Tensor& like) {
+  MeanScaleBatch b;
+  int64_t nnz = num_tables * batch * hotness;
+  if (offsets.has_value() && offsets->defined()) {
+    CheckGpu(*offsets, "offsets");
+    b.off = IndexCode(*offsets, "offsets");
+    b.o = offsets->contiguous();
+    TORCH_CHECK(hotness == 0 && b.o.numel() == num_tables * batch + 1 && b.o.device() == like.device(),
+                "cuembed_pyt: CSR: hotness = 0 and offsets of num_tables * batch + 1 entries on y_grad's device");
+    nnz = -1;   // (known on the device only)
+  } else {
+    TORCH_CHECK(hotness > 0, "cuembed_pyt: fixed hotness: hotness > 0");
+  }
+  if (weights.has_value() && weights->defined()) {
+    CheckGpu(*weights, "weights");
+    TORCH_CHECK(weights->scalar_type() == like.scalar_type() && weights->device() == like.device() &&
+                    (nnz < 0 || weights->numel() >= nnz),
+                "cuembed_pyt: weights must have one entry per lookup, of y_grad's dtype, on its device");
+    b.w = weights->contiguous();
+  }
+  return b;
+}
+
 // y_grad [batch, num_tables, width] of a MEAN-pooled group times each bag's mean factor: the y_grad of the equivalent
 // sum-pooled group (a new tensor).  offsets given: CSR, num_tables * batch + 1 entries, hotness = 0; absent: every bag
 // has `hotness` lookups.  weights: one per lookup, of y_grad's dtype (the mean is then over the weights).
@@ -1676,30 +1698,12 @@ at::Tensor cuembed_grouped_mean_scale_op(const at::Tensor& y_grad, const c10::op
   TORCH_CHECK(num_tables * batch <= INT32_MAX, "cuembed_pyt: num_tables * batch must fit a 32-bit int");
   const at::DeviceGuard guard(y_grad.device());
   const at::Tensor g = y_grad.contiguous();
-  at::Tensor o, w;
-  int off = CUEMBED_I32;
-  int64_t nnz = num_tables * batch * hotness;
-  if (offsets.has_value() && offsets->defined()) {
-    CheckGpu(*offsets, "offsets");
-    off = IndexCode(*offsets, "offsets");
-    o = offsets->contiguous();
-    TORCH_CHECK(hotness == 0 && o.numel() == num_tables * batch + 1 && o.device() == g.device(),
-                "cuembed_pyt: CSR: hotness = 0 and offsets of num_tables * batch + 1 entries on y_grad's device");
-    nnz = -1;   // (known on the device only)
-  } else {
-    TORCH_CHECK(hotness > 0, "cuembed_pyt: fixed hotness: hotness > 0");
-  }
-  if (weights.has_value() && weights->defined()) {
-    CheckGpu(*weights, "weights");
-    TORCH_CHECK(weights->scalar_type() == g.scalar_type() && weights->device() == g.device() &&
-                    (nnz < 0 || weights->numel() >= nnz),
-                "cuembed_pyt: weights must have one entry per lookup, of y_grad's dtype, on its device");
-    w = weights->contiguous();
-  }
+  const MeanScaleBatch b = CheckMeanScaleBatch(offsets, weights, num_tables, batch, hotness, g);
   at::Tensor out = at::empty_like(g);
   CheckRowAlignment("y_grad", width, g.element_size(), {Ptr(g), Ptr(out)}, true);
   if (batch > 0 && width > 0)
-    ::cuembed_grouped_mean_scale(Ptr(g), elem, static_cast<int>(width), Ptr(o), off, Ptr(w), static_cast<int>(num_tables),
+    ::cuembed_grouped_mean_scale(Ptr(g), elem, static_cast<int>(width), Ptr(b.o), b.off, Ptr(b.w),
+                                 static_cast<int>(num_tables),
                                  static_cast<int>(batch), static_cast<int>(hotness), MutPtr(out), CurrentStream(g));
   return out;
 }
@@ -1775,15 +1779,14 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> cuembed_embedding_backward_mixed_
     overflow.fill_(1);
     return std::make_tuple(rows, ids, overflow);
   }
-  // the launch's lane, by the library's rule: what both bases, D, every column base and every width allow
-  uintptr_t bits = reinterpret_cast<uintptr_t>(g.data_ptr()) | reinterpret_cast<uintptr_t>(rows.data_ptr());
+  // the launch's lane is the library's to decide: the C ABI is asked with both bases OR-ed.  (The forward's shape function
+  // at batch 0 is the lane rule and nothing else; the backward's would abort, not raise, on the limit checked next.)
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(g.data_ptr()) | reinterpret_cast<uintptr_t>(rows.data_ptr());
   TORCH_CHECK(bits % 4 == 0, "cuembed_pyt: y_grad must be 4-byte aligned");
-  int64_t column = 0;
-  for (const int w : w_host) {
-    column += static_cast<int64_t>(w) * g.element_size();
-    bits |= static_cast<uintptr_t>(static_cast<int64_t>(w) * g.element_size()) | static_cast<uintptr_t>(column);
-  }
-  const int64_t lane_elems = (bits % 16 == 0 ? 16 : (bits % 8 == 0 ? 8 : 4)) / g.element_size();
+  int shape[7];
+  ::cuembed_mixed_group_launch_shape(w_host.data(), static_cast<int>(num_tables), elem, CUEMBED_I32, 0, 0, 0,
+                                     static_cast<size_t>(bits), shape);
+  const int64_t lane_elems = shape[0];
   TORCH_CHECK(max_width / lane_elems <= 1024, "cuembed_pyt: the widest table is more than 1024 lanes");
   TORCH_CHECK(batch * (dim / lane_elems) < (int64_t{1} << 31),
               "cuembed_pyt: batch * sum of the widths / elements per lane must stay below 2^31");
@@ -1808,29 +1811,10 @@ at::Tensor cuembed_mixed_group_mean_scale_op(const at::Tensor& y_grad, const at:
   const int64_t num_tables = static_cast<int64_t>(widths.size()), batch = y_grad.size(0);
   TORCH_CHECK(num_tables * batch <= INT32_MAX, "cuembed_pyt: num_tables * batch must fit a 32-bit int");
   const at::Tensor g = y_grad.contiguous();
-  at::Tensor o, w;
-  int off = CUEMBED_I32;
-  int64_t nnz = num_tables * batch * hotness;
-  if (offsets.has_value() && offsets->defined()) {
-    CheckGpu(*offsets, "offsets");
-    off = IndexCode(*offsets, "offsets");
-    o = offsets->contiguous();
-    TORCH_CHECK(hotness == 0 && o.numel() == num_tables * batch + 1 && o.device() == g.device(),
-                "cuembed_pyt: CSR: hotness = 0 and offsets of num_tables * batch + 1 entries on y_grad's device");
-    nnz = -1;   // (known on the device only)
-  } else {
-    TORCH_CHECK(hotness > 0, "cuembed_pyt: fixed hotness: hotness > 0");
-  }
-  if (weights.has_value() && weights->defined()) {
-    CheckGpu(*weights, "weights");
-    TORCH_CHECK(weights->scalar_type() == g.scalar_type() && weights->device() == g.device() &&
-                    (nnz < 0 || weights->numel() >= nnz),
-                "cuembed_pyt: weights must have one entry per lookup, of y_grad's dtype, on its device");
-    w = weights->contiguous();
-  }
+  const MeanScaleBatch b = CheckMeanScaleBatch(offsets, weights, num_tables, batch, hotness, g);
   at::Tensor out = at::empty_like(g);
   if (batch > 0)
-    ::cuembed_mixed_group_mean_scale(Ptr(g), elem, w_host.data(), table_columns.data_ptr(), Ptr(o), off, Ptr(w),
+    ::cuembed_mixed_group_mean_scale(Ptr(g), elem, w_host.data(), table_columns.data_ptr(), Ptr(b.o), b.off, Ptr(b.w),
                                      static_cast<int>(num_tables), static_cast<int>(batch), static_cast<int>(hotness),
                                      MutPtr(out), CurrentStream(g));
   return out;

@@ -216,7 +216,7 @@ def _forward_impl(params, indices, offsets, weights, mode, row_loads=-1, sample_
     batch_size = offsets.numel() - 1
     return _ops.embedding_forward(params.contiguous(), indices.contiguous(), offsets.contiguous(), weights,
                                   batch_size=batch_size, num_hots=0, mode=mode,
-                                  row_loads={-1: None, 0: "default", 1: "streaming"}[int(row_loads)],
+                                  row_loads=_ops._ROW_LOADS_BY_CODE[int(row_loads)],
                                   sample_order=sample_order, row_loads_device=row_loads_device)
 
 
@@ -414,7 +414,7 @@ def _embedding_quantized_impl(qtable, indices, offsets, weights, mode, out_dtype
     return _q.embedding_forward_quantized(
         qtable, indices.contiguous(), None if offsets is None else offsets.contiguous(),
         None if weights is None else weights.contiguous(), num_hots=0 if offsets is not None else indices.shape[1],
-        mode=mode, out_dtype=out_dtype, row_loads={-1: None, 0: "default", 1: "streaming"}[int(row_loads)],
+        mode=mode, out_dtype=out_dtype, row_loads=_ops._ROW_LOADS_BY_CODE[int(row_loads)],
         sample_order=sample_order, row_loads_device=row_loads_device)
 
 
@@ -430,7 +430,7 @@ def _embedding_grouped_impl(tables, table_ptrs, idx, offsets, weights, mode, row
     return _g.embedding_forward_grouped(
         _grouped_group(tables, table_ptrs), idx.contiguous(), None if offsets is None else offsets.contiguous(),
         None if weights is None else weights.contiguous(), num_hots=0 if offsets is not None else idx.shape[2], mode=mode,
-        row_loads={-1: None, 0: "default", 1: "streaming"}[int(row_loads)], sample_order=sample_order)
+        row_loads=_ops._ROW_LOADS_BY_CODE[int(row_loads)], sample_order=sample_order)
 
 
 def _embedding_mixed_group_impl(tables, table_ptrs, descriptor, lane_bytes, idx, offsets, weights, mode, row_loads=-1):
@@ -448,7 +448,7 @@ def _embedding_mixed_group_impl(tables, table_ptrs, descriptor, lane_bytes, idx,
     return _m.embedding_forward_mixed_group(
         group, idx.contiguous(), None if offsets is None else offsets.contiguous(),
         None if weights is None else weights.contiguous(), num_hots=0 if offsets is not None else idx.shape[2], mode=mode,
-        row_loads={-1: None, 0: "default", 1: "streaming"}[int(row_loads)], out=out)
+        row_loads=_ops._ROW_LOADS_BY_CODE[int(row_loads)], out=out)
 
 
 def _embedding_quantized_grouped_impl(qtables, table_ptrs, idx, offsets, weights, mode, out_dtype, row_loads=-1,
@@ -459,7 +459,7 @@ def _embedding_quantized_grouped_impl(qtables, table_ptrs, idx, offsets, weights
     return _g.embedding_forward_quantized_grouped(
         _grouped_group(qtables, table_ptrs), idx.contiguous(), None if offsets is None else offsets.contiguous(),
         None if weights is None else weights.contiguous(), num_hots=0 if offsets is not None else idx.shape[2], mode=mode,
-        out_dtype=out_dtype, row_loads={-1: None, 0: "default", 1: "streaming"}[int(row_loads)],
+        out_dtype=out_dtype, row_loads=_ops._ROW_LOADS_BY_CODE[int(row_loads)],
         sample_order=sample_order)
 
 
@@ -507,13 +507,8 @@ def _grouped_weight_grad_impl(tables, table_ptrs, idx, offsets, y_grad):
         None if offsets is None else offsets.contiguous(), num_hots=0 if offsets is not None else idx.shape[2])
 
 
-def _grouped_mean_scale_impl(y_grad, offsets, weights, num_tables, hotness):
-    from . import _lib as _clib
-    _require(y_grad.is_cuda and y_grad.dtype in _FLOATS and y_grad.dim() == 3 and y_grad.shape[1] == num_tables >= 1,
-             "y_grad must be a float [batch, num_tables, width] tensor on the GPU")
-    batch, width = y_grad.shape[0], y_grad.shape[2]
-    _require(num_tables * batch < 2 ** 31, "num_tables * batch must fit a 32-bit int")
-    y_grad = y_grad.contiguous()
+def _mean_scale_batch(y_grad, offsets, weights, num_tables, batch, hotness):
+    """What both mean scales check of their batch (the batch size is y_grad's): the contiguous (offsets, weights)."""
     if offsets is not None:
         _require(offsets.is_cuda and offsets.dtype in _INTS and hotness == 0 and offsets.numel() == num_tables * batch + 1,
                  "CSR: hotness = 0 and offsets of num_tables * batch + 1 entries")
@@ -525,6 +520,17 @@ def _grouped_mean_scale_impl(y_grad, offsets, weights, num_tables, hotness):
                  (offsets is not None or weights.numel() >= num_tables * batch * hotness),
                  "weights must have one entry per lookup, of y_grad's dtype")
         weights = weights.contiguous()
+    return offsets, weights
+
+
+def _grouped_mean_scale_impl(y_grad, offsets, weights, num_tables, hotness):
+    from . import _lib as _clib
+    _require(y_grad.is_cuda and y_grad.dtype in _FLOATS and y_grad.dim() == 3 and y_grad.shape[1] == num_tables >= 1,
+             "y_grad must be a float [batch, num_tables, width] tensor on the GPU")
+    batch, width = y_grad.shape[0], y_grad.shape[2]
+    _require(num_tables * batch < 2 ** 31, "num_tables * batch must fit a 32-bit int")
+    y_grad = y_grad.contiguous()
+    offsets, weights = _mean_scale_batch(y_grad, offsets, weights, num_tables, batch, hotness)
     out = torch.empty_like(y_grad)
     if y_grad.numel() > 0:
         _ops._check_alignment("y_grad", y_grad.data_ptr(), y_grad.element_size(), width, others=(("out", out.data_ptr()),))
@@ -554,14 +560,9 @@ def _mixed_columns(y_grad, widths, table_columns):
 
 
 def _mixed_lane_elems(widths, itemsize, *pointers):
-    bits, column = 0, 0
-    for p in pointers:
-        bits |= int(p)
-    _require(bits % 4 == 0, "y_grad must be 4-byte aligned")
-    for w in widths:
-        column += int(w) * itemsize
-        bits |= (int(w) * itemsize) | column
-    return (16 if bits % 16 == 0 else (8 if bits % 8 == 0 else 4)) // itemsize
+    from .group_layout import mixed_lane_bytes
+    _require(all(int(p) % 4 == 0 for p in pointers), "y_grad must be 4-byte aligned")
+    return mixed_lane_bytes([int(w) for w in widths], itemsize, [("y_grad", p) for p in pointers]) // itemsize
 
 
 def _backward_mixed_group_impl(y_grad, widths, table_columns, transpose_indices, transpose_sample_ids,
@@ -608,17 +609,7 @@ def _mixed_group_mean_scale_impl(y_grad, widths, table_columns, offsets, weights
     w_host, _, _ = _mixed_columns(y_grad, widths, table_columns)
     num_tables, batch = len(widths), y_grad.shape[0]
     y_grad = y_grad.contiguous()
-    if offsets is not None:
-        _require(offsets.is_cuda and offsets.dtype in _INTS and hotness == 0 and offsets.numel() == num_tables * batch + 1,
-                 "CSR: hotness = 0 and offsets of num_tables * batch + 1 entries")
-        offsets = offsets.contiguous()
-    else:
-        _require(hotness > 0, "fixed hotness: hotness > 0")
-    if weights is not None:
-        _require(weights.is_cuda and weights.dtype == y_grad.dtype and
-                 (offsets is not None or weights.numel() >= num_tables * batch * hotness),
-                 "weights must have one entry per lookup, of y_grad's dtype")
-        weights = weights.contiguous()
+    offsets, weights = _mean_scale_batch(y_grad, offsets, weights, num_tables, batch, hotness)
     out = torch.empty_like(y_grad)
     if batch > 0:
         _mixed_lane_elems(widths, y_grad.element_size(), y_grad.data_ptr(), out.data_ptr())
@@ -877,9 +868,11 @@ def cuemb_embedding_quantized_grouped(group, idx, offsets=None, weights=None, mo
 def _grouped_batch(num_tables, idx, offsets):
     """(batch, hotness) of a grouped call: CSR offsets of num_tables * batch + 1 entries, or idx [num_tables, batch, hot]."""
     if offsets is not None:
-        if offsets.numel() < 1 or (offsets.numel() - 1) % num_tables:
+        from .group_layout import csr_batch_size
+        batch = csr_batch_size(num_tables, offsets.numel())
+        if batch is None:
             raise ValueError("offsets must hold num_tables * batch + 1 entries")
-        return (offsets.numel() - 1) // num_tables, 0
+        return batch, 0
     if idx.dim() != 3 or idx.shape[0] != num_tables or idx.shape[2] < 1:
         raise ValueError("without offsets, idx must be [num_tables, batch, hotness]")
     return idx.shape[1], idx.shape[2]
@@ -889,6 +882,27 @@ def _empty_sparse(rows, width, dtype, device):
     return torch.sparse_coo_tensor(torch.empty((1, 0), dtype=torch.int64, device=device),
                                    torch.empty((0, width), dtype=dtype, device=device), size=(rows, width),
                                    is_coalesced=True)
+
+
+def _per_table(head, wanted, make):
+    return head + tuple(make(t) if wanted[t] else None for t in range(len(wanted)))
+
+
+def _sparse_table_grads(head, wanted, group, width_of, dtype, inv=None, last_id=None, rows_of=None):
+    """The tail of a group's sparse backward on separate tensors: `head` and, for every wanted table t, ONE coalesced
+    sparse COO gradient [rows_t, width_of(t)].  inv: the ascending global ids of the compressed gradient, last_id its
+    count word; rows_of(t, lo, hi): the values of table t, whose entries are [lo, hi) -- ONE read-back, of the
+    num_tables + 1 cuts.  inv None: a batch without lookups, empty gradients and no launch."""
+    base = group.row_base
+    if inv is None:
+        return _per_table(head, wanted, lambda t: _empty_sparse(base[t + 1] - base[t], width_of(t), dtype, group.device))
+    cuts = torch.ops.cuembed_pyt.cuembed_grouped_table_cuts(inv, last_id, group.row_base_device, True).tolist()
+
+    def table_grad(t):
+        lo, hi = cuts[t], cuts[t + 1]
+        return torch.sparse_coo_tensor((inv[lo:hi].to(torch.int64) - base[t]).unsqueeze(0), rows_of(t, lo, hi),
+                                       size=(base[t + 1] - base[t], width_of(t)), is_coalesced=True)
+    return _per_table(head, wanted, table_grad)
 
 
 class _CuEmbGrouped(torch.autograd.Function):
@@ -936,16 +950,15 @@ class _CuEmbGrouped(torch.autograd.Function):
                 out_grad, offsets, None if weights is None else weights.detach(), T, hot)
         grad_2d = out_grad.view(batch * T, width)
 
-        def per_table(make):
-            return head + tuple(make(t) if wanted[t] else None for t in range(T))
+        def dense_views(dense):
+            return head + (dense,) if one_storage else _per_table(head, wanted, lambda t: dense[base[t]:base[t + 1]])
 
         if nnz == 0:
             if kind is False:
-                dense = torch.zeros((total, width), dtype=dtype, device=dev)
-                return head + (dense,) if one_storage else per_table(lambda t: dense[base[t]:base[t + 1]])
+                return dense_views(torch.zeros((total, width), dtype=dtype, device=dev))
             if one_storage:
                 return head + (_empty_sparse(total, width, dtype, dev),)
-            return per_table(lambda t: _empty_sparse(base[t + 1] - base[t], width, dtype, dev))
+            return _sparse_table_grads(head, wanted, group, lambda t: width, dtype)
         # ---- one key launch, one sort, (one remap,) one scatter-add for all tables
         keys, sample_ids = torch.ops.cuembed_pyt.cuembed_grouped_backward_keys(idx, offsets, group.row_base_device, T,
                                                                                batch, hot, total < 2 ** 31)
@@ -953,8 +966,7 @@ class _CuEmbGrouped(torch.autograd.Function):
         t_keys, t_sids, t_w = cuembed_transpose_sample_ids(sample_ids, keys, w, total)
         t_w = t_w if t_w.numel() else None
         if kind is False:
-            dense = cuembed_embedding_backward(grad_2d, total, t_keys, t_sids, t_w)
-            return head + (dense,) if one_storage else per_table(lambda t: dense[base[t]:base[t + 1]])
+            return dense_views(cuembed_embedding_backward(grad_2d, total, t_keys, t_sids, t_w))
         remap = torch.ops.cuembed_pyt.cuembed_compute_compressed_grad_indices(t_keys)
         if one_storage and kind is True:      # the count is read back once, after everything is enqueued
             num_unique = int(remap[-1].item()) + 1
@@ -971,13 +983,8 @@ class _CuEmbGrouped(torch.autograd.Function):
             return head + (torch.sparse_coo_tensor(inv.to(torch.int64).unsqueeze(0), rows, size=(total, width),
                                                    is_coalesced=False),)
         # separate tensors, sparse: ONE read-back, of the num_tables + 1 cuts
-        cuts = torch.ops.cuembed_pyt.cuembed_grouped_table_cuts(inv, remap[-1:], group.row_base_device, True).tolist()
-
-        def table_grad(t):
-            lo, hi = cuts[t], cuts[t + 1]
-            return torch.sparse_coo_tensor((inv[lo:hi].to(torch.int64) - base[t]).unsqueeze(0), rows[lo:hi],
-                                           size=(base[t + 1] - base[t], width), is_coalesced=True)
-        return per_table(table_grad)
+        return _sparse_table_grads(head, wanted, group, lambda t: width, dtype, inv, remap[-1:],
+                                   lambda t, lo, hi: rows[lo:hi])
 
 
 def _check_grouped_training(mode, weight_grad):
@@ -1095,21 +1102,17 @@ class _CuEmbMixedGroup(torch.autograd.Function):
     def backward(ctx, out_grad):
         idx, offsets, weights = ctx.saved_tensors
         group = ctx.group
-        T, total, base, widths = group.num_tables, group.total_rows, group.row_base, group.widths
+        T, total, widths = group.num_tables, group.total_rows, group.widths
         wanted = ctx.needs_input_grad[5:]
         head = (None,) * 5
         if not any(wanted):
             return head + (None,) * T
         batch, hot = _grouped_batch(T, idx, offsets)
         nnz = idx.numel()
-        dev, dtype = out_grad.device, out_grad.dtype
+        dtype = out_grad.dtype
         out_grad = out_grad.contiguous()
-
-        def per_table(make):
-            return head + tuple(make(t) if wanted[t] else None for t in range(T))
-
         if nnz == 0:
-            return per_table(lambda t: _empty_sparse(base[t + 1] - base[t], widths[t], dtype, dev))
+            return _sparse_table_grads(head, wanted, group, widths.__getitem__, dtype)
         w = None if weights is None else weights.detach()
         if ctx.mode == "mean":
             out_grad = torch.ops.cuembed_pyt.cuembed_mixed_group_mean_scale(out_grad, list(widths),
@@ -1123,14 +1126,8 @@ class _CuEmbMixedGroup(torch.autograd.Function):
             out_grad, list(widths), group.table_columns_device, t_keys, t_sids, remap, t_w if t_w.numel() else None,
             min(nnz, total))
         # ONE read-back, of the num_tables + 1 cuts
-        cuts = torch.ops.cuembed_pyt.cuembed_grouped_table_cuts(inv, remap[-1:], group.row_base_device, True).tolist()
-
-        def table_grad(t):
-            lo, hi = cuts[t], cuts[t + 1]
-            return torch.sparse_coo_tensor((inv[lo:hi].to(torch.int64) - base[t]).unsqueeze(0),
-                                           rows[lo:hi, :widths[t]].contiguous(), size=(base[t + 1] - base[t], widths[t]),
-                                           is_coalesced=True)
-        return per_table(table_grad)
+        return _sparse_table_grads(head, wanted, group, widths.__getitem__, dtype, inv, remap[-1:],
+                                   lambda t, lo, hi: rows[lo:hi, :widths[t]].contiguous())
 
 
 def cuemb_embedding_mixed_group_trainable(group_or_tables, idx, offsets=None, weights=None, num_hots=0, mode="sum"):

@@ -27,14 +27,14 @@ import ctypes
 import torch
 
 from . import _lib
-from .ops import _ELEM, _INDEX, _MODES, _ROW_LOADS, MEAN, SUM, _check_alignment, _check_dev, _index_code, _ptr, _stream
+from .group_layout import INT_MAX, BagGroupModule, GroupTables, check_weights, group_batch_layout
+from .ops import _ELEM, _INDEX, _MODES, _ROW_LOADS, MEAN, SUM, _check_alignment, _check_dev, _ptr, _stream
 from .quantized import TRAILER_BYTES, _check_qtable, _out_code, quantize_rows
 
-INT_MAX = 2 ** 31 - 1
 _SOURCES = ("lds_staged", "wave_shuffle", "global")
 
 
-class TableGroup:
+class TableGroup(GroupTables):
     """T >= 1 tables of one device, dtype and width (their row counts may differ): all 2-D float32 / float16 / bfloat16
     [rows_t, W], or all fused 8-bit tables, uint8 [rows_t, W + 8].  Holds the tensors (so that the pointers stay
     valid), their base pointers on the host, and `table_ptrs`, ONE int64 device tensor of the same pointers that the
@@ -42,13 +42,12 @@ class TableGroup:
     (`table.data = ...`) needs a new TableGroup; updating rows in place does not."""
 
     def __init__(self, tables, table_ptrs=None):
-        tables = list(tables)
-        if not tables:
-            raise ValueError("a TableGroup needs at least one table")
-        for t in tables:
-            if not isinstance(t, torch.Tensor):
-                raise TypeError("every table must be a torch.Tensor")
-        first = tables[0]
+        super().__init__(tables, table_ptrs)
+        self.flat = None                 # the one storage of allocate() / from_flat(); None for separate tensors
+        self._state_ptr_arrays = {}      # the pointer arrays of per-table optimizer state (grouped_backward._state_ptrs)
+        self._seed_arrays = {}           # the per-table rounding seeds on the device (grouped_backward._seeds_tensor)
+
+    def _first_table(self, first):
         self.quantized = first.dtype == torch.uint8
         if self.quantized:
             self.width = _check_qtable(first)
@@ -58,54 +57,11 @@ class TableGroup:
             if first.dim() != 2:
                 raise ValueError("every table must be [rows, width]")
             self.width = first.shape[1]
-        for k, t in enumerate(tables):
-            if t.dtype != first.dtype:
-                raise TypeError("table %d is %s, table 0 is %s: one dtype per group" % (k, t.dtype, first.dtype))
-            if t.dim() != 2 or t.shape[1] != first.shape[1]:
-                raise ValueError("table %d is %s, table 0 has rows of %d: one width per group"
-                                 % (k, tuple(t.shape), first.shape[1]))
-            if t.device != first.device:
-                raise ValueError("table %d is on %s, table 0 on %s: one device per group" % (k, t.device, first.device))
-            if not t.is_contiguous():
-                raise ValueError("table %d must be contiguous" % k)
-        self.tables = tuple(tables)
-        self.device = first.device
-        self.dtype = first.dtype
-        self.host_ptrs = tuple(int(t.data_ptr()) for t in tables)
-        self._host_array = (ctypes.c_void_p * len(tables))(*self.host_ptrs)
-        if table_ptrs is None:   # (a CPU group can be built and inspected; calls need the GPU)
-            table_ptrs = torch.tensor(self.host_ptrs, dtype=torch.int64, device=self.device)
-        elif (not isinstance(table_ptrs, torch.Tensor) or table_ptrs.dtype != torch.int64 or
-              table_ptrs.numel() != len(tables) or table_ptrs.device != self.device or not table_ptrs.is_contiguous()):
-            # (an earlier group's tensor for the same tables; its values stay on the device, unread)
-            raise ValueError("table_ptrs must be the contiguous int64 tensor of the tables' data pointers on their device")
-        self.table_ptrs = table_ptrs
-        self.row_counts = tuple(int(t.shape[0]) for t in tables)
-        self.flat = None                 # the one storage of allocate() / from_flat(); None for separate tensors
-        self._row_base_device = None
-        self._state_ptr_arrays = {}      # the pointer arrays of per-table optimizer state (grouped_backward._state_ptrs)
-        self._seed_arrays = {}           # the per-table rounding seeds on the device (grouped_backward._seeds_tensor)
 
-    @property
-    def row_base(self):
-        """Host tuple of num_tables + 1 ints: the exclusive prefix sum of row_counts; row_base[-1] = total_rows.  Table
-        t owns the global rows [row_base[t], row_base[t + 1]) of the tables laid end to end."""
-        base = [0]
-        for n in self.row_counts:
-            base.append(base[-1] + n)
-        return tuple(base)
-
-    @property
-    def total_rows(self):
-        return sum(self.row_counts)
-
-    @property
-    def row_base_device(self):
-        """row_base as ONE int64 device tensor of num_tables + 1 entries, which the grouped backward's kernels read --
-        built at the first use, once."""
-        if self._row_base_device is None:
-            self._row_base_device = torch.tensor(self.row_base, dtype=torch.int64, device=self.device)
-        return self._row_base_device
+    def _check_table(self, k, t, first):
+        if t.dim() != 2 or t.shape[1] != first.shape[1]:
+            raise ValueError("table %d is %s, table 0 has rows of %d: one width per group"
+                             % (k, tuple(t.shape), first.shape[1]))
 
     @classmethod
     def from_flat(cls, flat, row_counts):
@@ -144,13 +100,6 @@ class TableGroup:
             raise ValueError("row_counts must be non-negative and width positive")
         return cls.from_flat(torch.zeros((sum(counts), int(width)), dtype=dtype, device=device), counts)
 
-    def __len__(self):
-        return len(self.tables)
-
-    @property
-    def num_tables(self):
-        return len(self.tables)
-
     def lane_bytes(self, out_ptr=0):
         """Bytes of a row one lane moves (16, 8 or 4; codes per lane for fused tables before the 16-code widening): the
         least aligned table -- and `out_ptr` -- decide for the whole group.  ValueError where the library would abort."""
@@ -176,10 +125,10 @@ def _check_no_grad(group, weights):
             raise RuntimeError("weights require grad: the grouped forward is forward only")
 
 
-def _grouped_call(group, indices, offsets, weights, batch_size, num_hots, mode, row_loads, sample_order, out,
-                  row_loads_device, weight_dtype, out_dtype):
-    """Validates one grouped call (everything that does not need the GPU first) and returns
-    (B, mode code, index code, offset code, out)."""
+def _grouped_args(group, indices, offsets, weights, batch_size, num_hots, mode, row_loads, sample_order, row_loads_device,
+                  weight_dtype):
+    """Validates the arguments of one grouped forward that do not need the GPU and returns (B, mode code, index code,
+    offset code)."""
     if mode not in ("sum", "mean", SUM, MEAN):
         raise ValueError("mode must be 'sum' or 'mean': the grouped forward has no concat and no max")
     if row_loads not in _ROW_LOADS:
@@ -187,46 +136,17 @@ def _grouped_call(group, indices, offsets, weights, batch_size, num_hots, mode, 
     if row_loads_device is not None:
         raise ValueError("row_loads_device is not taken by the grouped forward: the decision is per table and nothing "
                          "carries one per table yet; pass row_loads= for the whole group")
-    m = _MODES[mode]
-    T = group.num_tables
-    if not isinstance(indices, torch.Tensor):
-        raise TypeError("indices must be a torch.Tensor")
-    it = _index_code("indices", indices)
     _check_no_grad(group, weights)
-    if not ((offsets is not None and num_hots == 0) or (offsets is None and num_hots > 0)):
-        raise ValueError("either CSR (offsets given, num_hots == 0) or fixed hotness (offsets None, num_hots > 0)")
-    ot = 0
-    if offsets is not None:
-        if not isinstance(offsets, torch.Tensor):
-            raise TypeError("offsets must be a torch.Tensor")
-        ot = _index_code("offsets", offsets)
-        if batch_size is None:
-            if (offsets.numel() - 1) % T or offsets.numel() < 1:
-                raise ValueError("offsets must hold num_tables * batch_size + 1 entries: %d - 1 is not a multiple of %d "
-                                 "tables" % (offsets.numel(), T))
-            batch_size = (offsets.numel() - 1) // T
-        if batch_size < 0 or offsets.numel() != T * batch_size + 1:
-            raise ValueError("offsets must hold num_tables * batch_size + 1 = %d entries, got %d"
-                             % (T * batch_size + 1, offsets.numel()))
-    else:
-        if batch_size is None:
-            if indices.numel() % (T * num_hots):
-                raise ValueError("indices.numel() is not a multiple of num_tables * num_hots")
-            batch_size = indices.numel() // (T * num_hots)
-        if batch_size < 0 or indices.numel() != T * batch_size * num_hots:
-            raise ValueError("indices must hold num_tables * batch_size * num_hots entries")
-    if T * batch_size > INT_MAX:
-        raise ValueError("num_tables * batch_size = %d does not fit a 32-bit int" % (T * batch_size))
+    batch_size, nnz, it, ot = group_batch_layout(group.num_tables, indices, offsets, batch_size, num_hots)
     if weights is not None:
-        if not isinstance(weights, torch.Tensor):
-            raise TypeError("weights must be a torch.Tensor")
-        if weights.dtype != weight_dtype:
-            raise TypeError("weights must be %s, got %s" % (weight_dtype, weights.dtype))
-        if weights.numel() < indices.numel():
-            raise ValueError("weights must have one entry per index")
+        check_weights(weight_dtype, weights, nnz)
     if sample_order is not None and offsets is None:
         raise ValueError("sample_order is a hint for CSR batches (bags of different lengths)")
-    # ---- the call is in order: now the devices
+    return batch_size, _MODES[mode], it, ot
+
+
+def _grouped_devices(group, indices, offsets, weights):
+    """The call is in order: now the devices."""
     dev = group.device
     _check_dev("tables[0]", group.tables[0])
     _check_dev("indices", indices, dev)
@@ -234,6 +154,17 @@ def _grouped_call(group, indices, offsets, weights, batch_size, num_hots, mode, 
         _check_dev("offsets", offsets, dev)
     if weights is not None:
         _check_dev("weights", weights, dev)
+    return dev
+
+
+def _grouped_call(group, indices, offsets, weights, batch_size, num_hots, mode, row_loads, sample_order, out,
+                  row_loads_device, weight_dtype, out_dtype):
+    """Validates one same-width grouped call (everything that does not need the GPU first) and returns
+    (B, mode code, index code, offset code, out)."""
+    batch_size, m, it, ot = _grouped_args(group, indices, offsets, weights, batch_size, num_hots, mode, row_loads,
+                                          sample_order, row_loads_device, weight_dtype)
+    T = group.num_tables
+    dev = _grouped_devices(group, indices, offsets, weights)
     if sample_order is not None:
         _check_dev("sample_order", sample_order, dev)
         if sample_order.dtype != torch.int32 or sample_order.numel() != T * batch_size:
@@ -324,96 +255,48 @@ def grouped_forward_launch_shape(elem_dtype, index_dtype, embed_width, num_table
                 staged=out[5] == 1, index_source=_SOURCES[out[6]])
 
 
-_BOUNDS_CHECKS = (None, "raise", "repair")
-
-
-def _checked_batch(bags, idx, offsets, hot):
-    """The batch a group module hands to its forward.  bounds_check None: the caller's, untouched (ids outside their table
-    are then a contract violation).  "repair": cuembed_amd.check_indices with repair runs on the stream in front of the
-    forward, which gets the repaired arrays; the report stays on the device as bags.last_check -- no synchronisation.
-    "raise": the check, then IndexCheck.raise_if_bad() (one synchronisation) before the forward is launched."""
-    if bags.bounds_check is None:
-        return idx, offsets
-    from .index_check import check_indices
-    check = check_indices(idx, offsets, group=bags.group, num_hots=hot, repair=bags.bounds_check == "repair")
-    bags.last_check = check
-    if bags.bounds_check == "raise":
-        check.raise_if_bad()
-    return check.indices, check.offsets
-
-
-class EmbeddingBagGroup:
+class EmbeddingBagGroup(BagGroupModule):
     """A TableGroup with a mode and the call shape of nn.EmbeddingBag: bags(idx, offsets, weights) with CSR offsets
     (num_tables * batch + 1 entries), or bags(idx) with idx [num_tables, batch, hotness].  Returns [batch, num_tables,
     width].  Forward only.  bounds_check: None (the batch is trusted), "raise" or "repair" (_checked_batch); the last
     check is kept as .last_check."""
 
     def __init__(self, tables, mode="sum", bounds_check=None):
-        if mode not in ("sum", "mean"):
-            raise ValueError("mode must be 'sum' or 'mean'")
-        if bounds_check not in _BOUNDS_CHECKS:
-            raise ValueError("bounds_check must be None, 'raise' or 'repair'")
+        super().__init__(mode, bounds_check)
         self.group = _as_group(tables)
         if self.group.quantized:
             raise TypeError("fused 8-bit tables go into a QuantizedEmbeddingBagGroup")
-        self.mode = mode
-        self.bounds_check = bounds_check
-        self.last_check = None
-
-    @property
-    def num_tables(self):
-        return self.group.num_tables
 
     @property
     def embedding_dim(self):
         return self.group.width
 
     def __call__(self, idx, offsets=None, weights=None, sample_order=None, out=None):
-        hot = 0
-        if offsets is None:
-            if idx.dim() != 3:
-                raise ValueError("without offsets, idx must be [num_tables, batch, hotness]")
-            hot = idx.shape[2]
-        idx, offsets = _checked_batch(self, idx, offsets, hot)
+        idx, offsets, hot = self._batch(idx, offsets)
         return embedding_forward_grouped(self.group, idx, offsets, weights, num_hots=hot, mode=self.mode,
                                          sample_order=sample_order, out=out)
 
 
-class QuantizedEmbeddingBagGroup:
+class QuantizedEmbeddingBagGroup(BagGroupModule):
     """EmbeddingBagGroup on fused 8-bit tables; from_float quantizes fp32 / fp16 / bf16 tables on the device."""
 
     def __init__(self, qtables, mode="sum", out_dtype=torch.float16, bounds_check=None):
-        if mode not in ("sum", "mean"):
-            raise ValueError("mode must be 'sum' or 'mean'")
-        if bounds_check not in _BOUNDS_CHECKS:
-            raise ValueError("bounds_check must be None, 'raise' or 'repair'")
+        super().__init__(mode, bounds_check)
         _out_code("out_dtype", out_dtype)
         self.group = _as_group(qtables)
         if not self.group.quantized:
             raise TypeError("QuantizedEmbeddingBagGroup takes fused uint8 tables; see from_float")
-        self.mode = mode
         self.out_dtype = out_dtype
-        self.bounds_check = bounds_check
-        self.last_check = None
 
     @classmethod
     def from_float(cls, tables, mode="sum", out_dtype=torch.float16, bounds_check=None):
         return cls([quantize_rows(t.detach()) for t in tables], mode=mode, out_dtype=out_dtype, bounds_check=bounds_check)
 
     @property
-    def num_tables(self):
-        return self.group.num_tables
-
-    @property
     def embedding_dim(self):
         return self.group.width
 
     def __call__(self, idx, offsets=None, weights=None, sample_order=None, out=None):
-        hot = 0
-        if offsets is None:
-            if idx.dim() != 3:
-                raise ValueError("without offsets, idx must be [num_tables, batch, hotness]")
-            hot = idx.shape[2]
-        idx, offsets = _checked_batch(self, idx, offsets, hot)
+        idx, offsets, hot = self._batch(idx, offsets)
         return embedding_forward_quantized_grouped(self.group, idx, offsets, weights, num_hots=hot, mode=self.mode,
                                                    out_dtype=self.out_dtype, sample_order=sample_order, out=out)

@@ -37,44 +37,15 @@ import ctypes
 import torch
 
 from . import _lib
-from .grouped import INT_MAX, _as_group
+from .group_layout import INT_MAX, check_weights, group_batch_layout, mean_scale_layout
+from .grouped import _as_group
 from .ops import (ADAM_RULES, UPDATE_RULES, _ELEM, _INDEX, _check_alignment, _check_betas, _check_dev, _entry_counts,
                   _index_code, _ptr, _stream, embedding_backward, transpose)
 
 
 def _layout(group, indices, offsets, batch_size, num_hots):
     """The bag layout of one grouped call, validated without the GPU: (batch_size, nnz)."""
-    T = group.num_tables
-    if not isinstance(indices, torch.Tensor):
-        raise TypeError("indices must be a torch.Tensor")
-    _index_code("indices", indices)
-    if not ((offsets is not None and num_hots == 0) or (offsets is None and num_hots > 0)):
-        raise ValueError("either CSR (offsets given, num_hots == 0) or fixed hotness (offsets None, num_hots > 0)")
-    if offsets is not None:
-        if not isinstance(offsets, torch.Tensor):
-            raise TypeError("offsets must be a torch.Tensor")
-        _index_code("offsets", offsets)
-        if batch_size is None:
-            if (offsets.numel() - 1) % T or offsets.numel() < 1:
-                raise ValueError("offsets must hold num_tables * batch_size + 1 entries: %d - 1 is not a multiple of %d "
-                                 "tables" % (offsets.numel(), T))
-            batch_size = (offsets.numel() - 1) // T
-        if batch_size < 0 or offsets.numel() != T * batch_size + 1:
-            raise ValueError("offsets must hold num_tables * batch_size + 1 = %d entries, got %d"
-                             % (T * batch_size + 1, offsets.numel()))
-    else:
-        if batch_size is None:
-            if indices.numel() % (T * num_hots):
-                raise ValueError("indices.numel() is not a multiple of num_tables * num_hots")
-            batch_size = indices.numel() // (T * num_hots)
-        if batch_size < 0 or indices.numel() != T * batch_size * num_hots:
-            raise ValueError("indices must hold num_tables * batch_size * num_hots entries")
-    if T * batch_size > INT_MAX:
-        raise ValueError("num_tables * batch_size = %d does not fit a 32-bit int" % (T * batch_size))
-    nnz = indices.numel()
-    if nnz > INT_MAX:
-        raise ValueError("%d lookups: the backward pipeline takes at most 2^31 - 1" % nnz)
-    return batch_size, nnz
+    return group_batch_layout(group.num_tables, indices, offsets, batch_size, num_hots, max_nnz=INT_MAX)[:2]
 
 
 def _float_group(group):
@@ -84,7 +55,7 @@ def _float_group(group):
     return group
 
 
-def _key_dtype(group, key_dtype):
+def _key_dtype(group, key_dtype=None):
     total = group.total_rows
     if key_dtype is None:
         return torch.int32 if total < 2 ** 31 else torch.int64
@@ -218,15 +189,6 @@ def _check_grad_y(group, grad_y, batch_size):
         raise ValueError("grad_y must be contiguous")
 
 
-def _check_weights(group, weights, nnz):
-    if not isinstance(weights, torch.Tensor):
-        raise TypeError("weights must be a torch.Tensor")
-    if weights.dtype != group.dtype:
-        raise TypeError("weights must be %s, got %s" % (group.dtype, weights.dtype))
-    if weights.numel() < nnz:
-        raise ValueError("weights must have one entry per index")
-
-
 def _mean_scale(group, grad_y, offsets, weights, batch_size, num_hots, out):
     """The launch of grouped_mean_scale, everything validated and on the device."""
     with torch.cuda.device(grad_y.device):
@@ -250,19 +212,9 @@ def grouped_mean_scale(group, grad_y, offsets=None, weights=None, num_hots=0, ou
     batch_size = grad_y.shape[0]
     _check_grad_y(group, grad_y, batch_size)
     T = group.num_tables
-    if not ((offsets is not None and num_hots == 0) or (offsets is None and num_hots > 0)):
-        raise ValueError("either CSR (offsets given, num_hots == 0) or fixed hotness (offsets None, num_hots > 0)")
-    if offsets is not None:
-        if not isinstance(offsets, torch.Tensor):
-            raise TypeError("offsets must be a torch.Tensor")
-        _index_code("offsets", offsets)
-        if offsets.numel() != T * batch_size + 1:
-            raise ValueError("offsets must hold num_tables * batch_size + 1 = %d entries, got %d"
-                             % (T * batch_size + 1, offsets.numel()))
-    if T * batch_size > INT_MAX:
-        raise ValueError("num_tables * batch_size = %d does not fit a 32-bit int" % (T * batch_size))
+    mean_scale_layout(T, offsets, batch_size, num_hots)
     if weights is not None:
-        _check_weights(group, weights, 0 if offsets is not None else T * batch_size * num_hots)
+        check_weights(group.dtype, weights, 0 if offsets is not None else T * batch_size * num_hots)
     if out is not None:
         if not isinstance(out, torch.Tensor):
             raise TypeError("out must be a torch.Tensor")
@@ -348,7 +300,7 @@ def embedding_backward_grouped(group, grad_y, indices, offsets=None, weights=Non
     if reference_sums and not dense:
         raise ValueError("reference_sums needs a host-known row count: dense=True only")
     if weights is not None:
-        _check_weights(group, weights, nnz)
+        check_weights(group.dtype, weights, nnz)
     # ---- the call is in order: now the devices
     dev = group.device
     _check_dev("tables[0]", group.tables[0])

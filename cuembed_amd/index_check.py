@@ -27,7 +27,8 @@ import ctypes
 import torch
 
 from . import _lib
-from .grouped import INT_MAX, _as_group
+from .group_layout import INT_MAX, group_batch_layout
+from .grouped import _as_group
 from .mixed_group import MixedTableGroup
 from .ops import _check_dev, _index_code, _ptr, _stream
 
@@ -169,33 +170,9 @@ def check_indices(indices, offsets=None, *, num_rows=None, group=None, batch_siz
         if rows < 1:
             raise ValueError("table %d has %d rows: every checked table needs at least one row (the repaired id is 0)"
                              % (t, rows))
-    if not ((offsets is not None and num_hots == 0) or (offsets is None and num_hots > 0)):
-        raise ValueError("either CSR (offsets given, num_hots == 0) or fixed hotness (offsets None, num_hots > 0)")
-    nnz = indices.numel()
-    ot = 0
-    if offsets is not None:
-        if not isinstance(offsets, torch.Tensor):
-            raise TypeError("offsets must be a torch.Tensor")
-        ot = _index_code("offsets", offsets)
-        if batch_size is None:
-            if offsets.numel() < 1 or (offsets.numel() - 1) % T:
-                raise ValueError("offsets must hold num_tables * batch_size + 1 entries: %d - 1 is not a multiple of %d "
-                                 "tables" % (offsets.numel(), T))
-            batch_size = (offsets.numel() - 1) // T
-        if batch_size < 0 or offsets.numel() != T * batch_size + 1:
-            raise ValueError("offsets must hold num_tables * batch_size + 1 = %d entries, got %d"
-                             % (T * batch_size + 1, offsets.numel()))
-        if offsets.dtype == torch.int32 and nnz > INT_MAX:
-            raise ValueError("int32 offsets cannot address %d lookups" % nnz)
-    else:
-        if batch_size is None:
-            if nnz % (T * num_hots):
-                raise ValueError("indices.numel() is not a multiple of num_tables * num_hots")
-            batch_size = nnz // (T * num_hots)
-        if batch_size < 0 or nnz != T * batch_size * num_hots:
-            raise ValueError("indices must hold num_tables * batch_size * num_hots entries")
-    if T * batch_size > INT_MAX:
-        raise ValueError("num_tables * batch_size = %d does not fit a 32-bit int" % (T * batch_size))
+    batch_size, nnz, it, ot = group_batch_layout(T, indices, offsets, batch_size, num_hots)
+    if offsets is not None and offsets.dtype == torch.int32 and nnz > INT_MAX:
+        raise ValueError("int32 offsets cannot address %d lookups" % nnz)
     if nnz > MAX_CHECK_NNZ:
         raise ValueError("at most 2^38 lookups per call, got %d" % nnz)
     if not repair and (out_indices is not None or out_offsets is not None):

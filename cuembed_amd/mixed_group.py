@@ -30,13 +30,14 @@ import ctypes
 import torch
 
 from . import _lib
-from .grouped import INT_MAX, _BOUNDS_CHECKS, _check_no_grad, _checked_batch
-from .ops import _ELEM, _INDEX, _MODES, _ROW_LOADS, MEAN, SUM, _check_dev, _index_code, _ptr, _stream
+from .group_layout import INT_MAX, BagGroupModule, GroupTables, mixed_lane_bytes
+from .grouped import _grouped_args, _grouped_devices
+from .ops import _ELEM, _INDEX, _ROW_LOADS, _check_dev, _ptr, _stream
 
 BLOCK_THREADS = 256        # cuembed::kMixedGroupBlockThreads
 
 
-class MixedTableGroup:
+class MixedTableGroup(GroupTables):
     """T >= 1 contiguous 2-D tables [rows_t, W_t] of one device and one dtype (float32 / float16 / bfloat16); the widths
     and row counts may all differ, every row is a multiple of 4 bytes.  Holds the tensors (so that the pointers stay
     valid), their base pointers and widths on the host, `table_ptrs` (ONE int64 device tensor of the pointers, which the
@@ -46,82 +47,34 @@ class MixedTableGroup:
     quantized = False
 
     def __init__(self, tables, table_ptrs=None):
-        tables = list(tables)
-        if not tables:
-            raise ValueError("a MixedTableGroup needs at least one table")
-        for t in tables:
-            if not isinstance(t, torch.Tensor):
-                raise TypeError("every table must be a torch.Tensor")
-        first = tables[0]
-        if first.dtype not in _ELEM:
-            raise TypeError("tables must be float32, float16 or bfloat16, got %s" % first.dtype)
-        for k, t in enumerate(tables):
-            if t.dtype != first.dtype:
-                raise TypeError("table %d is %s, table 0 is %s: one dtype per group" % (k, t.dtype, first.dtype))
-            if t.dim() != 2:
-                raise ValueError("table %d is %s: every table must be [rows, width]" % (k, tuple(t.shape)))
-            if t.device != first.device:
-                raise ValueError("table %d is on %s, table 0 on %s: one device per group" % (k, t.device, first.device))
-            if not t.is_contiguous():
-                raise ValueError("table %d must be contiguous" % k)
-            if t.shape[1] <= 0 or (t.shape[1] * t.element_size()) % 4:
-                raise ValueError("table %d: the row size must be a multiple of 4 bytes, got %d elements of %d"
-                                 % (k, t.shape[1], t.element_size()))
-        self.tables = tuple(tables)
-        self.device = first.device
-        self.dtype = first.dtype
-        self.widths = tuple(int(t.shape[1]) for t in tables)
+        super().__init__(tables, table_ptrs)
+        self.widths = tuple(int(t.shape[1]) for t in self.tables)
         base = [0]
         for w in self.widths:
             base.append(base[-1] + w)
         if base[-1] > INT_MAX:
             raise ValueError("the widths sum to %d, which does not fit a 32-bit int" % base[-1])
         self.column_base = tuple(base)
-        self.row_counts = tuple(int(t.shape[0]) for t in tables)
-        self.host_ptrs = tuple(int(t.data_ptr()) for t in tables)
-        self._host_array = (ctypes.c_void_p * len(tables))(*self.host_ptrs)
-        self._widths_array = (ctypes.c_int * len(tables))(*self.widths)
-        if table_ptrs is None:
-            table_ptrs = torch.tensor(self.host_ptrs, dtype=torch.int64, device=self.device)
-        elif (not isinstance(table_ptrs, torch.Tensor) or table_ptrs.dtype != torch.int64 or
-              table_ptrs.numel() != len(tables) or table_ptrs.device != self.device or not table_ptrs.is_contiguous()):
-            # (an earlier group's tensor for the same tables; its values stay on the device, unread)
-            raise ValueError("table_ptrs must be the contiguous int64 tensor of the tables' data pointers on their device")
-        self.table_ptrs = table_ptrs
-        self._row_base_device = None
+        self._widths_array = (ctypes.c_int * len(self.tables))(*self.widths)
+        self._named_ptrs = None          # (name, pointer) of every table, for lane_bytes(): built at its first call
         self._table_columns_device = None
         self._descriptors = {}
 
-    def __len__(self):
-        return len(self.tables)
+    def _first_table(self, first):
+        if first.dtype not in _ELEM:
+            raise TypeError("tables must be float32, float16 or bfloat16, got %s" % first.dtype)
 
-    @property
-    def num_tables(self):
-        return len(self.tables)
+    def _check_table(self, k, t, first):
+        if t.dim() != 2:
+            raise ValueError("table %d is %s: every table must be [rows, width]" % (k, tuple(t.shape)))
+        if t.shape[1] <= 0 or (t.shape[1] * t.element_size()) % 4:
+            raise ValueError("table %d: the row size must be a multiple of 4 bytes, got %d elements of %d"
+                             % (k, t.shape[1], t.element_size()))
 
     @property
     def embedding_dim(self):
         """D: the columns of a result row, the sum of the widths."""
         return self.column_base[-1]
-
-    @property
-    def row_base(self):
-        """Host tuple of num_tables + 1 ints: the exclusive prefix sum of row_counts (as TableGroup.row_base)."""
-        base = [0]
-        for n in self.row_counts:
-            base.append(base[-1] + n)
-        return tuple(base)
-
-    @property
-    def total_rows(self):
-        return sum(self.row_counts)
-
-    @property
-    def row_base_device(self):
-        """row_base as ONE int64 device tensor (what check_indices reads) -- built at the first use, once."""
-        if self._row_base_device is None:
-            self._row_base_device = torch.tensor(self.row_base, dtype=torch.int64, device=self.device)
-        return self._row_base_device
 
     @property
     def table_columns_device(self):
@@ -136,20 +89,9 @@ class MixedTableGroup:
         """Bytes of a row one lane moves (16, 8 or 4), ONE value for the launch: the widest that every table base,
         `out_ptr`, D * itemsize, every column base * itemsize and every width * itemsize are a multiple of (the least
         aligned one decides).  ValueError where the library would abort."""
-        size = self.tables[0].element_size()
-        bits = 0
-        for k, p in enumerate(self.host_ptrs):
-            if p % 4:
-                raise ValueError("tables[%d] must be 4-byte aligned: its data pointer is %d bytes past a 4-byte boundary"
-                                 % (k, p % 4))
-            bits |= p
-        if int(out_ptr) % 4:
-            raise ValueError("out must be 4-byte aligned: its data pointer is %d bytes past a 4-byte boundary"
-                             % (int(out_ptr) % 4))
-        bits |= int(out_ptr)
-        for w, c in zip(self.widths, self.column_base[1:]):
-            bits |= (w * size) | (c * size)
-        return 16 if bits % 16 == 0 else (8 if bits % 8 == 0 else 4)
+        if self._named_ptrs is None:
+            self._named_ptrs = tuple(("tables[%d]" % k, p) for k, p in enumerate(self.host_ptrs))
+        return mixed_lane_bytes(self.widths, self.tables[0].element_size(), self._named_ptrs + (("out", out_ptr),))
 
     def descriptor_words(self, batch_size, lane_bytes):
         """The descriptor of (batch_size, lane_bytes) on the host (cuembed_fill_mixed_group_descriptor: host arithmetic):
@@ -192,66 +134,18 @@ def embedding_forward_mixed_group(group, indices, offsets=None, weights=None, ba
     in the tables' dtype; fp32 accumulation in lookup order; empty bags give zeros.  row_loads ("default" | "streaming" |
     None, one value for the group) changes no bit.  sample_order and row_loads_device must stay None."""
     group = _as_mixed_group(group)
-    if mode not in ("sum", "mean", SUM, MEAN):
-        raise ValueError("mode must be 'sum' or 'mean': the grouped forward has no concat and no max")
-    if row_loads not in _ROW_LOADS:
-        raise ValueError("row_loads: None, 'default' or 'streaming'")
-    if row_loads_device is not None:
-        raise ValueError("row_loads_device is not taken by the grouped forward: the decision is per table and nothing "
-                         "carries one per table yet; pass row_loads= for the whole group")
     if sample_order is not None:
         raise ValueError("sample_order is not taken by the mixed-width forward in this version")
-    m = _MODES[mode]
+    batch_size, m, it, ot = _grouped_args(group, indices, offsets, weights, batch_size, num_hots, mode, row_loads, None,
+                                          row_loads_device, group.dtype)
     T, D = group.num_tables, group.embedding_dim
-    if not isinstance(indices, torch.Tensor):
-        raise TypeError("indices must be a torch.Tensor")
-    it = _index_code("indices", indices)
-    _check_no_grad(group, weights)
-    if not ((offsets is not None and num_hots == 0) or (offsets is None and num_hots > 0)):
-        raise ValueError("either CSR (offsets given, num_hots == 0) or fixed hotness (offsets None, num_hots > 0)")
-    ot = 0
-    if offsets is not None:
-        if not isinstance(offsets, torch.Tensor):
-            raise TypeError("offsets must be a torch.Tensor")
-        ot = _index_code("offsets", offsets)
-        if batch_size is None:
-            if (offsets.numel() - 1) % T or offsets.numel() < 1:
-                raise ValueError("offsets must hold num_tables * batch_size + 1 entries: %d - 1 is not a multiple of %d "
-                                 "tables" % (offsets.numel(), T))
-            batch_size = (offsets.numel() - 1) // T
-        if batch_size < 0 or offsets.numel() != T * batch_size + 1:
-            raise ValueError("offsets must hold num_tables * batch_size + 1 = %d entries, got %d"
-                             % (T * batch_size + 1, offsets.numel()))
-    else:
-        if batch_size is None:
-            if indices.numel() % (T * num_hots):
-                raise ValueError("indices.numel() is not a multiple of num_tables * num_hots")
-            batch_size = indices.numel() // (T * num_hots)
-        if batch_size < 0 or indices.numel() != T * batch_size * num_hots:
-            raise ValueError("indices must hold num_tables * batch_size * num_hots entries")
-    if T * batch_size > INT_MAX:
-        raise ValueError("num_tables * batch_size = %d does not fit a 32-bit int" % (T * batch_size))
-    if weights is not None:
-        if not isinstance(weights, torch.Tensor):
-            raise TypeError("weights must be a torch.Tensor")
-        if weights.dtype != group.dtype:
-            raise TypeError("weights must be %s, got %s" % (group.dtype, weights.dtype))
-        if weights.numel() < indices.numel():
-            raise ValueError("weights must have one entry per index")
     if out is not None:
         if not isinstance(out, torch.Tensor):
             raise TypeError("out must be a torch.Tensor")
         if out.dtype != group.dtype or out.numel() != batch_size * D:
             raise ValueError("out must be a contiguous %s tensor [batch_size, embedding_dim] = [%d, %d]"
                              % (group.dtype, batch_size, D))
-    # ---- the call is in order: now the devices
-    dev = group.device
-    _check_dev("tables[0]", group.tables[0])
-    _check_dev("indices", indices, dev)
-    if offsets is not None:
-        _check_dev("offsets", offsets, dev)
-    if weights is not None:
-        _check_dev("weights", weights, dev)
+    dev = _grouped_devices(group, indices, offsets, weights)
     if out is None:
         out = torch.empty((batch_size, D), dtype=group.dtype, device=dev)
     else:
@@ -292,35 +186,20 @@ def mixed_group_launch_shape(elem_dtype, index_dtype, widths, batch_size, num_ho
                 staged=out[5] == 1, max_bags_per_block=out[6])
 
 
-class MixedEmbeddingBagGroup:
+class MixedEmbeddingBagGroup(BagGroupModule):
     """A MixedTableGroup with a mode and the call shape of nn.EmbeddingBag: bags(idx, offsets, weights) with CSR offsets
     (num_tables * batch + 1 entries), or bags(idx) with idx [num_tables, batch, hotness].  Returns [batch, embedding_dim].
     Forward only.  bounds_check: None (the batch is trusted), "raise" or "repair" (cuembed_amd.check_indices in front of
     the forward, as in EmbeddingBagGroup); the last check is kept as .last_check."""
 
     def __init__(self, tables, mode="sum", bounds_check=None):
-        if mode not in ("sum", "mean"):
-            raise ValueError("mode must be 'sum' or 'mean'")
-        if bounds_check not in _BOUNDS_CHECKS:
-            raise ValueError("bounds_check must be None, 'raise' or 'repair'")
+        super().__init__(mode, bounds_check)
         self.group = _as_mixed_group(tables)
-        self.mode = mode
-        self.bounds_check = bounds_check
-        self.last_check = None
-
-    @property
-    def num_tables(self):
-        return self.group.num_tables
 
     @property
     def embedding_dim(self):
         return self.group.embedding_dim
 
     def __call__(self, idx, offsets=None, weights=None, out=None):
-        hot = 0
-        if offsets is None:
-            if idx.dim() != 3:
-                raise ValueError("without offsets, idx must be [num_tables, batch, hotness]")
-            hot = idx.shape[2]
-        idx, offsets = _checked_batch(self, idx, offsets, hot)
+        idx, offsets, hot = self._batch(idx, offsets)
         return embedding_forward_mixed_group(self.group, idx, offsets, weights, num_hots=hot, mode=self.mode, out=out)

@@ -26,30 +26,15 @@ import ctypes
 import torch
 
 from . import _lib
-from .grouped import INT_MAX
-from .grouped_backward import _layout, grouped_table_cuts
+from .group_layout import INT_MAX, check_weights, mean_scale_layout, mixed_lane_bytes
+from .grouped_backward import GroupedGrad, _key_dtype, _layout
 from .mixed_group import MixedTableGroup, _as_mixed_group
-from .ops import MAX_LANES_PER_ROW, _ELEM, _INDEX, _check_dev, _index_code, _overflow_word, _ptr, _stream, transpose
-
-
-def _key_dtype(group):
-    """grouped_backward._key_dtype's rule: int32 while the group has fewer than 2^31 rows in all."""
-    return torch.int32 if group.total_rows < 2 ** 31 else torch.int64
+from .ops import MAX_LANES_PER_ROW, _ELEM, _INDEX, _check_dev, _overflow_word, _ptr, _stream, transpose
 
 
 def _lane_bytes(group, *pointers):
-    """The launch's lane: the widest of 16 / 8 / 4 bytes that every pointer given, D * itemsize, every column base *
-    itemsize and every width * itemsize (W_max among them) are a multiple of.  ValueError where the library would abort."""
-    size = group.tables[0].element_size()
-    bits = 0
-    for name, p in pointers:
-        if int(p) % 4:
-            raise ValueError("%s must be 4-byte aligned: its data pointer is %d bytes past a 4-byte boundary"
-                             % (name, int(p) % 4))
-        bits |= int(p)
-    for w, c in zip(group.widths, group.column_base[1:]):
-        bits |= (w * size) | (c * size)
-    return 16 if bits % 16 == 0 else (8 if bits % 8 == 0 else 4)
+    """The launch's lane (mixed_lane_bytes) for the (name, address) pairs given.  W_max is one of the widths."""
+    return mixed_lane_bytes(group.widths, group.tables[0].element_size(), pointers)
 
 
 def _check_limits(group, batch_size, lane):
@@ -75,15 +60,6 @@ def _check_grad_y(group, grad_y, batch_size, name="grad_y"):
         raise ValueError("%s must be contiguous" % name)
 
 
-def _check_weights(group, weights, nnz):
-    if not isinstance(weights, torch.Tensor):
-        raise TypeError("weights must be a torch.Tensor")
-    if weights.dtype != group.dtype:
-        raise TypeError("weights must be %s, got %s" % (group.dtype, weights.dtype))
-    if weights.numel() < nnz:
-        raise ValueError("weights must have one entry per index")
-
-
 def _group(group):
     group = _as_mixed_group(group)
     if not isinstance(group, MixedTableGroup):
@@ -91,7 +67,7 @@ def _group(group):
     return group
 
 
-class MixedGroupedGrad:
+class MixedGroupedGrad(GroupedGrad):
     """The compressed gradient of a mixed-width group, nothing read back:
 
         ids        ascending GLOBAL row ids (group.row_base[t] + the row of table t), `capacity` entries of room
@@ -105,25 +81,14 @@ class MixedGroupedGrad:
     and capacity_overflowed() says so."""
 
     def __init__(self, ids, rows, last_id, row_base, row_base_device, widths):
-        self.ids = ids
-        self.rows = rows
-        self.last_id = last_id
-        self.row_base = tuple(row_base)
-        self.row_base_device = row_base_device
+        super().__init__(ids, rows, last_id, row_base, row_base_device)
         self.widths = tuple(widths)
-        self.capacity = ids.numel()
-
-    def table_cuts(self):
-        """The int64 device tensor of num_tables + 1 cuts (grouped_table_cuts): table t owns [cuts[t], cuts[t + 1])."""
-        return grouped_table_cuts(self.ids, self.row_base_device, last_id=self.last_id)
 
     def per_table(self):
         """[(local_ids_t, rows_t)] for every table, with ONE read-back (the num_tables + 1 cuts): local_ids_t =
         ids[c0:c1] - row_base[t], the ascending rows of table t that were looked up; rows_t = rows[c0:c1, :W_t], a view
         (not contiguous where W_t < W_max)."""
-        cuts = self.table_cuts().tolist()
-        return [(self.ids[cuts[t]:cuts[t + 1]] - self.row_base[t], self.rows[cuts[t]:cuts[t + 1], :self.widths[t]])
-                for t in range(len(self.widths))]
+        return [(ids, rows[:, :w]) for (ids, rows), w in zip(super().per_table(), self.widths)]
 
     def capacity_overflowed(self, reset=False):
         """True if a compressed backward on this gradient's device found more rows than its buffers hold since the last
@@ -156,19 +121,9 @@ def mixed_group_mean_scale(group, grad_y, offsets=None, weights=None, num_hots=0
     batch_size = grad_y.shape[0]
     _check_grad_y(group, grad_y, batch_size)
     T = group.num_tables
-    if not ((offsets is not None and num_hots == 0) or (offsets is None and num_hots > 0)):
-        raise ValueError("either CSR (offsets given, num_hots == 0) or fixed hotness (offsets None, num_hots > 0)")
-    if offsets is not None:
-        if not isinstance(offsets, torch.Tensor):
-            raise TypeError("offsets must be a torch.Tensor")
-        _index_code("offsets", offsets)
-        if offsets.numel() != T * batch_size + 1:
-            raise ValueError("offsets must hold num_tables * batch_size + 1 = %d entries, got %d"
-                             % (T * batch_size + 1, offsets.numel()))
-    if T * batch_size > INT_MAX:
-        raise ValueError("num_tables * batch_size = %d does not fit a 32-bit int" % (T * batch_size))
+    mean_scale_layout(T, offsets, batch_size, num_hots)
     if weights is not None:
-        _check_weights(group, weights, 0 if offsets is not None else T * batch_size * num_hots)
+        check_weights(group.dtype, weights, 0 if offsets is not None else T * batch_size * num_hots)
     if out is not None:
         _check_grad_y(group, out, batch_size, name="out")
     # ---- the call is in order: now the devices
@@ -208,7 +163,7 @@ def embedding_backward_mixed_group(group, grad_y, indices, offsets=None, weights
     if mode not in ("sum", "mean"):
         raise ValueError("mode must be 'sum' or 'mean', got %r: the grouped backward has no other pooling" % (mode,))
     if weights is not None:
-        _check_weights(group, weights, nnz)
+        check_weights(group.dtype, weights, nnz)
     total = group.total_rows
     if capacity is None:
         capacity = min(nnz, total)
@@ -273,12 +228,7 @@ def mixed_group_backward_launch_shape(elem_dtype, widths, nnz, is_weighted=False
         raise ValueError("nnz must be in [0, 2^31 - 1]")
     if pointer_bits % 4:
         raise ValueError("every pointer must be 4-byte aligned")
-    bits = pointer_bits
-    column = 0
-    for w in widths:
-        column += w * elem_dtype.itemsize
-        bits |= (w * elem_dtype.itemsize) | column
-    lane = 16 if bits % 16 == 0 else (8 if bits % 8 == 0 else 4)
+    lane = mixed_lane_bytes(widths, elem_dtype.itemsize, (("pointer_bits", pointer_bits),))
     if max(widths) * elem_dtype.itemsize // lane > MAX_LANES_PER_ROW:
         raise ValueError("the widest table is more than %d lanes of %d bytes" % (MAX_LANES_PER_ROW, lane))
     out = (ctypes.c_int * 10)()

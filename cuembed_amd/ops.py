@@ -126,7 +126,9 @@ def get_forward_reduction_order():
 
 
 _ORDERS = {None: -1, "sequential": 0, "split": 1}
+_CSR_XOR_FIXED = "either CSR (offsets given, num_hots == 0) or fixed hotness (offsets None, num_hots > 0)"
 _ROW_LOADS = {None: -1, "default": 0, "streaming": 1}
+_ROW_LOADS_BY_CODE = {code: name for name, code in _ROW_LOADS.items()}   # what a torch op hands back
 
 
 def set_forward_row_load_policy(policy):
@@ -211,8 +213,7 @@ def embedding_forward(params, indices, offsets=None, weights=None, batch_size=No
     if weights is not None and m == CONCAT:
         raise ValueError("concat does not take weights")
     if not ((offsets is not None and num_hots == 0) or (offsets is None and num_hots > 0)):
-        raise ValueError("either CSR (offsets given, num_hots == 0) or fixed hotness "
-                         "(offsets None, num_hots > 0)")
+        raise ValueError(_CSR_XOR_FIXED)
     if offsets is not None and m == CONCAT:
         raise ValueError("CSR layout does not support concat")
     width = params.shape[1]

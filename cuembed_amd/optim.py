@@ -66,6 +66,7 @@ import torch
 from . import grouped as _grouped
 from . import grouped_backward as _grouped_backward
 from . import ops as _ops
+from .mixed_group_backward import MixedGroupedGrad
 
 _ACCEPTED = ("the coalesced sparse COO gradient of cuemb_embedding(..., sparse_grad=True | 'reference' | 'blocked'); "
              "for a step without a host read-back (HIP graph capture) use SparseUpdater.backward_and_apply")
@@ -272,7 +273,8 @@ class _GroupedGradientStep:
         return grad
 
     def _check_grad(self, grad):
-        if not isinstance(grad, _grouped_backward.GroupedGrad):
+        # (a MixedGroupedGrad is a GroupedGrad whose rows are padded to the widest table: not what the grouped step reads)
+        if not isinstance(grad, _grouped_backward.GroupedGrad) or isinstance(grad, MixedGroupedGrad):
             raise TypeError("apply takes the GroupedGrad of embedding_backward_grouped(dense=False), got %s"
                             % type(grad).__name__)
         if grad.row_base != self.group.row_base:

@@ -19,7 +19,7 @@ import ctypes
 import torch
 
 from . import _lib
-from .ops import _MODES, _ROW_LOADS, CONCAT, _check_alignment, _check_dev, _elem_code, _index_code, _ptr, _stream
+from .ops import _CSR_XOR_FIXED, _MODES, _ROW_LOADS, CONCAT, _check_alignment, _check_dev, _elem_code, _index_code, _ptr, _stream
 
 TRAILER_BYTES = 8                                   # fp32 scale + fp32 bias
 _OUT = {torch.float32: 0, torch.float16: 1}
@@ -161,7 +161,7 @@ def embedding_forward_quantized(qtable, indices, offsets=None, weights=None, bat
     if weights is not None and m == CONCAT:
         raise ValueError("concat does not take weights")
     if not ((offsets is not None and num_hots == 0) or (offsets is None and num_hots > 0)):
-        raise ValueError("either CSR (offsets given, num_hots == 0) or fixed hotness (offsets None, num_hots > 0)")
+        raise ValueError(_CSR_XOR_FIXED)
     if offsets is not None and m == CONCAT:
         raise ValueError("CSR layout does not support concat")
     if weights is not None and weights.dtype != out_dtype:

@@ -111,6 +111,30 @@ def test_the_ops_reject_what_the_functions_reject(ce, pyt, group):
         scale(grad_y.cpu(), widths, columns, off_d, None, 0)
 
 
+def test_the_scatter_op_raises_on_a_table_of_more_than_1024_lanes(ce, pyt):
+    """fp16 rows of 2,050 elements are 4,100 bytes: 4-byte lanes, 1,025 of them.  The op takes its lane from the library
+    and must RAISE on the limit, before any launch (the sorted lookups below are never read), as the function does."""
+    T, B, H = 2, 3, 2
+    widths = [2050, 8]
+    group = ce.MixedTableGroup([torch.zeros(5, w, dtype=torch.float16, device="cuda") for w in widths])
+    assert group.lane_bytes() == 4
+    grad_y = torch.zeros((B, sum(widths)), dtype=torch.float16, device="cuda")
+    keys = torch.arange(T * B * H, dtype=torch.int32, device="cuda") % 10
+    keys, _ = torch.sort(keys)
+    sids = torch.zeros_like(keys)
+    remap = torch.unique_consecutive(keys, return_inverse=True)[1].to(torch.int32)
+    scatter = torch.ops.cuembed_pyt.cuembed_embedding_backward_mixed_group
+    with pytest.raises(RuntimeError, match="the widest table is more than 1024 lanes"):
+        scatter(grad_y, widths, group.table_columns_device, keys, sids, remap, None, T * B * H)
+    idx = torch.zeros(T, B, H, dtype=torch.int64, device="cuda")
+    with pytest.raises(ValueError, match="1024 lanes"):
+        ce.embedding_backward_mixed_group(group, grad_y, idx, num_hots=H)
+    # without lookups, or without room, the op launches nothing and does not get as far as the limit
+    empty = keys[:0]
+    rows, ids, overflow = scatter(grad_y, widths, group.table_columns_device, empty, empty, empty, None, 4)
+    assert rows.shape == (4, 2050) and ids.shape == (4,) and int(overflow) == 0
+
+
 def test_fake_implementations_give_shapes_and_dtypes(pyt):
     from torch._subclasses.fake_tensor import FakeTensorMode
     T, D = len(WIDTHS), sum(WIDTHS)

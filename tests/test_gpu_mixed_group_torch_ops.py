@@ -84,6 +84,46 @@ def test_the_op_rejects_what_the_function_rejects(ce, pyt, problem):
                            ce.embedding_forward_mixed_group(group, ids, off))
 
 
+def test_the_op_names_its_own_table_rule_and_the_shared_batch_rules(ce):
+    """The op's checks are the same-width op's in two parts: the table part with the mixed-width rule and message, the
+    batch part as it is.  Two tables of widths (4, 8), 3 bags of 2 lookups each."""
+    T, B, H = 2, 3, 2
+
+    def fp16(rows, width):
+        return torch.zeros(rows, width, dtype=torch.float16, device="cuda")
+
+    tables = [fp16(5, 4), fp16(7, 8)]
+    group = ce.MixedTableGroup(tables)
+    lane = group.lane_bytes()
+    descriptor = group.descriptor(B, lane)
+    idx = torch.zeros(T, B, H, dtype=torch.int64, device="cuda")
+    off = torch.arange(0, T * B * H + 1, H, dtype=torch.int64, device="cuda")
+    op = torch.ops.cuembed_pyt.cuemb_embedding_mixed_group
+
+    def call(tables=tables, idx=idx, off=None, weights=None):
+        ptrs = torch.tensor([t.data_ptr() for t in tables], dtype=torch.int64, device="cuda")
+        return op(tables, ptrs, descriptor, lane, idx, off, weights, "sum")
+
+    assert call().shape == (B, 12) and call(idx=idx.view(-1), off=off).shape == (B, 12)      # mixed widths are in order
+    mixed_rule = "mixed-width group must be contiguous .* of one dtype and device, every row a multiple of 4 bytes"
+    for bad in (fp16(7, 7),                       # 14-byte rows
+                fp16(7, 8).float(),               # another dtype
+                fp16(7, 16)[:, :8],               # not contiguous
+                fp16(7 * 8, 1).view(-1)):         # not [rows, width]
+        with pytest.raises(RuntimeError, match=mixed_rule):
+            call(tables=[tables[0], bad])
+    with pytest.raises(RuntimeError, match=r"offsets must hold num_tables \* batch_size \+ 1 entries"):
+        call(idx=idx.view(-1), off=off[:-1])
+    with pytest.raises(RuntimeError, match=r"without offsets, indices must be \[num_tables, batch, hotness\]"):
+        call(idx=idx.view(-1))
+    with pytest.raises(RuntimeError, match="weights have the wrong dtype"):
+        call(weights=torch.ones(T * B * H, device="cuda"))
+    with pytest.raises(RuntimeError, match="weights must have one entry per index"):
+        call(weights=torch.ones(T * B * H - 1, dtype=torch.float16, device="cuda"))
+    with pytest.raises(RuntimeError, match="indices must be int32 or int64"):
+        call(idx=idx.float())
+
+
 def test_the_same_width_op_still_refuses_mixed_widths(ce, problem):
     batch, tables, layouts = problem
     ids, off, _, _ = layouts["csr_ragged"]
