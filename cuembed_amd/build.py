@@ -227,18 +227,21 @@ def build_sparse_adam_test(force=False):
     return _build_program("tests/cpp/sparse_adam_kat.hip", _O2, force)
 
 
+_ROW_CACHE_KAT_COMMON = os.path.join(ROOT, "tests", "cpp", "row_cache_kat_common.hpp")   # what the next three share
+
+
 def build_row_cache_state_test(force=False):
     """Compiles tests/cpp/row_cache_state_kat.hip: cuembed::RowCachePrefetch / RowCacheFlush with a state plane and
     cuembed::SparseRowUpdate with state_ids through the header-only API against a host recomputation on exactly
     representable data.  Needs a GPU to RUN (tests/test_gpu_cpp_row_cache_state.py)."""
-    return _build_program("tests/cpp/row_cache_state_kat.hip", _O2_ATOMICS, force)
+    return _build_program("tests/cpp/row_cache_state_kat.hip", _O2_ATOMICS, force, extra_deps=[_ROW_CACHE_KAT_COMMON])
 
 
 def build_row_cache_adam_test(force=False):
     """Compiles tests/cpp/row_cache_adam_kat.hip: cuembed::RowCachePrefetch / RowCacheFlush with two state planes,
     cuembed::TranslateIndicesForRowCachePlanes and cuembed::SparseRowAdam with placed moments through the header-only API
     against a host recomputation on exactly representable data.  Needs a GPU to RUN (tests/test_gpu_cpp_row_cache_adam.py)."""
-    return _build_program("tests/cpp/row_cache_adam_kat.hip", _O2_ATOMICS, force)
+    return _build_program("tests/cpp/row_cache_adam_kat.hip", _O2_ATOMICS, force, extra_deps=[_ROW_CACHE_KAT_COMMON])
 
 
 def build_row_cache_stochastic_test(force=False):
@@ -246,7 +249,7 @@ def build_row_cache_stochastic_test(force=False):
     planes, cuembed::TranslateIndicesForRowCachePlanes and cuembed::SparseRowUpdate / SparseRowAdam with row_names
     (stochastic rounding behind the cache) through the header-only API against a host recomputation with
     stochastic_rounding.hpp's host functions.  Needs a GPU to RUN (tests/test_gpu_cpp_row_cache_stochastic.py)."""
-    return _build_program("tests/cpp/row_cache_stochastic_kat.hip", _O2_ATOMICS, force)
+    return _build_program("tests/cpp/row_cache_stochastic_kat.hip", _O2_ATOMICS, force, extra_deps=[_ROW_CACHE_KAT_COMMON])
 
 
 def build_grouped_train_test(force=False):

@@ -5,10 +5,11 @@
 //
 // make a device buffer of num_sets x 64 rows a set-associative LRU write-back cache of a table that lives outside this
 // GPU's HBM.  The cache buffer differs from the table by a whole number of rows, so TranslateIndicesForRowCache +
-// EmbeddingForward (or SparseRowUpdate) on the TABLE's base pointer reach the cached rows unchanged.  An optimizer's fp32
-// state can ride on the same slots as a second plane (RowCache::state): it is translated with its own row offset and
-// handed to SparseRowUpdate as `state_ids`.  The Adam family has two such planes (RowCache::state2): one launch of
-// TranslateIndicesForRowCachePlanes translates the ids for all three and SparseRowAdam takes the two state ids.
+// EmbeddingForward (or SparseRowUpdate) on the TABLE's base pointer reach the cached rows unchanged.  The table's rows are
+// one PLANE of the cache; an optimizer's fp32 state can ride on the same slots as a second plane (RowCache::state): it is
+// translated with its own row offset and handed to SparseRowUpdate as `state_ids`.  The Adam family has two state planes
+// (RowCache::state2): one launch of TranslateIndicesForRowCachePlanes translates the ids for all three and SparseRowAdam
+// takes the two state ids.  The host code sees the planes as one list (detail::PlanesOf): checked and moved in a loop.
 // Everything is stream-ordered and nothing is read back; the kernels and the state they keep are in row_cache_kernels.hpp.
 #ifndef CUEMBED_INCLUDE_ROW_CACHE_HPP_
 #define CUEMBED_INCLUDE_ROW_CACHE_HPP_
@@ -129,29 +130,37 @@ struct RowCachePlan {
   }
 };
 
+//! One plane of the cache: an array of rows outside the cache (`home`) and its slots in HBM (`cached`), a whole number
+//! of rows apart.  The table's rows are a plane, and so is each state tensor that rides on the slots.
+struct CachePlane { void* home; void* cached; int64_t row_bytes; };
+
+//! The planes of a cache in the order the mover takes them: the second state plane, the first, the table's rows.
+struct CachePlanes {
+  CachePlane plane[3] = {};
+  int count = 0;
+  const CachePlane* begin() const { return plane; }
+  const CachePlane* end() const { return plane + count; }
+};
+
+inline CachePlanes PlanesOf(const RowCache& c) {
+  CachePlanes p;
+  if (c.state2_row_bytes != 0) p.plane[p.count++] = {c.state2, c.state2_cache, c.state2_row_bytes};
+  if (c.state_row_bytes != 0) p.plane[p.count++] = {c.state, c.state_cache, c.state_row_bytes};
+  p.plane[p.count++] = {c.table, c.cache_rows, c.row_bytes};
+  return p;
+}
+
 inline void CheckRowCache(const RowCache& c) {
   CUEMBED_ASSERT(c.num_sets >= 1 && c.num_sets <= (1 << 24));
   CUEMBED_ASSERT(c.num_rows >= 1);
-  CUEMBED_ASSERT(c.row_bytes > 0 && c.row_bytes % 4 == 0);
-  CUEMBED_ASSERT(c.table != nullptr && c.cache_rows != nullptr);
-  CUEMBED_ASSERT(reinterpret_cast<uintptr_t>(c.table) % 4 == 0);
-  CUEMBED_ASSERT((reinterpret_cast<intptr_t>(c.cache_rows) - reinterpret_cast<intptr_t>(c.table)) % c.row_bytes == 0);
   CUEMBED_ASSERT(c.tags != nullptr && c.stamps != nullptr && c.dirty != nullptr && c.slot_of_row != nullptr &&
                  c.words != nullptr);
-  if (c.state_row_bytes != 0) {
-    CUEMBED_ASSERT(c.state_row_bytes > 0 && c.state_row_bytes % 4 == 0);
-    CUEMBED_ASSERT(c.state != nullptr && c.state_cache != nullptr);
-    CUEMBED_ASSERT(reinterpret_cast<uintptr_t>(c.state) % 4 == 0);
-    CUEMBED_ASSERT((reinterpret_cast<intptr_t>(c.state_cache) - reinterpret_cast<intptr_t>(c.state)) %
-                       c.state_row_bytes == 0);
-  }
-  if (c.state2_row_bytes != 0) {
-    CUEMBED_ASSERT(c.state_row_bytes != 0);   // a second plane only next to a first
-    CUEMBED_ASSERT(c.state2_row_bytes > 0 && c.state2_row_bytes % 4 == 0);
-    CUEMBED_ASSERT(c.state2 != nullptr && c.state2_cache != nullptr);
-    CUEMBED_ASSERT(reinterpret_cast<uintptr_t>(c.state2) % 4 == 0);
-    CUEMBED_ASSERT((reinterpret_cast<intptr_t>(c.state2_cache) - reinterpret_cast<intptr_t>(c.state2)) %
-                       c.state2_row_bytes == 0);
+  CUEMBED_ASSERT(c.state2_row_bytes == 0 || c.state_row_bytes != 0);   // a second plane only next to a first
+  for (const CachePlane& p : PlanesOf(c)) {
+    CUEMBED_ASSERT(p.row_bytes > 0 && p.row_bytes % 4 == 0);
+    CUEMBED_ASSERT(p.home != nullptr && p.cached != nullptr);
+    CUEMBED_ASSERT(reinterpret_cast<uintptr_t>(p.home) % 4 == 0);
+    CUEMBED_ASSERT((reinterpret_cast<intptr_t>(p.cached) - reinterpret_cast<intptr_t>(p.home)) % p.row_bytes == 0);
   }
 }
 
@@ -174,14 +183,13 @@ inline void LaunchPlaneMove(const RowCache& c, void* home, void* cached, const i
 #undef CUEMBED_MOVE
 }
 
-//! The row exchange of every plane: the second state plane, the first, then the table's, in stream order -- the last
-//! launch alone commits: it clears the dirty bytes of a flush and counts its write-backs (CacheMoveKernel).
+//! The row exchange of every plane, in PlanesOf's order and in stream order -- the last launch, the table's, alone
+//! commits: it clears the dirty bytes of a flush and counts its write-backs (CacheMoveKernel).
 inline void LaunchCacheMove(const RowCache& c, const CacheMove* moves, const int64_t capacity, const hipStream_t stream) {
   if (capacity <= 0) return;
-  if (c.state2_row_bytes != 0)
-    LaunchPlaneMove(c, c.state2, c.state2_cache, c.state2_row_bytes, false, moves, capacity, stream);
-  if (c.state_row_bytes != 0) LaunchPlaneMove(c, c.state, c.state_cache, c.state_row_bytes, false, moves, capacity, stream);
-  LaunchPlaneMove(c, c.table, c.cache_rows, c.row_bytes, true, moves, capacity, stream);
+  const CachePlanes planes = PlanesOf(c);
+  for (const CachePlane& p : planes)
+    LaunchPlaneMove(c, p.home, p.cached, p.row_bytes, &p == planes.end() - 1, moves, capacity, stream);
 }
 
 }  // namespace detail

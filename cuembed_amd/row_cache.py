@@ -42,6 +42,19 @@ from . import ops as _ops
 from .optim import _check_rounding
 
 
+def _plane_behind(home, slots, device):
+    """(raw buffer, cached plane, row offset) of `home` ([rows, width] or [rows], the table or a state tensor): a PLANE of
+    `slots` of its rows on the device.  The plane must differ from `home` by a whole number of rows: the buffer is
+    over-allocated by one row and the plane starts where (plane - home) % row_bytes == 0; row_offset = (plane - home) /
+    row_bytes is what a translate adds to a slot."""
+    row_bytes = home.element_size() * (home.shape[1] if home.dim() == 2 else 1)
+    raw = torch.empty(((slots + 1) * row_bytes,), dtype=torch.uint8, device=device)
+    shift = (home.data_ptr() - raw.data_ptr()) % row_bytes
+    plane = raw[shift:shift + slots * row_bytes].view(home.dtype).view((slots,) + tuple(home.shape[1:]))
+    assert (plane.data_ptr() - home.data_ptr()) % row_bytes == 0
+    return raw, plane, (plane.data_ptr() - home.data_ptr()) // row_bytes
+
+
 class CachedHostTable:
     def __init__(self, host_table, device="cuda", capacity_rows=1 << 20):
         if host_table.is_cuda or not host_table.is_pinned() or host_table.dim() != 2 or not host_table.is_contiguous():
@@ -57,13 +70,7 @@ class CachedHostTable:
         row_bytes = self.width * host_table.element_size()
         if row_bytes % 4:
             raise ValueError("row size must be a multiple of 4 bytes")
-        # the cache must differ from the table by a whole number of rows: over-allocate by one row
-        # and start where (cache - table) % row_bytes == 0
-        self._raw = torch.empty(((self.capacity + 1) * row_bytes,), dtype=torch.uint8, device=self.device)
-        shift = (host_table.data_ptr() - self._raw.data_ptr()) % row_bytes
-        self.cache = self._raw[shift:shift + self.capacity * row_bytes].view(host_table.dtype).view(self.capacity, self.width)
-        assert (self.cache.data_ptr() - host_table.data_ptr()) % row_bytes == 0
-        self.cache_row_offset = (self.cache.data_ptr() - host_table.data_ptr()) // row_bytes
+        self._raw, self.cache, self.cache_row_offset = _plane_behind(host_table, self.capacity, self.device)
         self.slot_of_row = torch.full((self.rows,), -1, dtype=torch.int32, device=self.device)
         self.cached_ids = torch.empty((0,), dtype=torch.int64, device=self.device)
 
@@ -195,6 +202,18 @@ def _check_pinned(name, t):
         raise ValueError("%s must live in PINNED host memory (tensor.pin_memory())" % name)
 
 
+def _check_state_tensor(name, t, shape, what):
+    """What a cache asks of a state tensor `name` that the caller gives: float32, contiguous, of `shape`, pinned.  `what`
+    names the setting that `shape` follows from."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if t.dtype != torch.float32:
+        raise TypeError("%s must be float32, got %s" % (name, t.dtype))
+    if tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError("%s needs a contiguous %s of shape %r, got %r" % (what, name, shape, tuple(t.shape)))
+    _check_pinned(name, t)
+
+
 class DynamicRowCache(CachedHostTable):
     """Device-managed cache of a host-resident table: `num_sets` sets of 64 ways (capacity_rows = 64 * num_sets) in HBM,
     LRU per set, write-back.  All state lives on the device -- tags int64 [S, 64] (-1 = empty), stamps uint32 [S, 64]
@@ -244,18 +263,12 @@ class DynamicRowCache(CachedHostTable):
         if state is not None:
             if rule == "sgd":
                 raise ValueError("rule='sgd' takes no state")
-            if not isinstance(state, torch.Tensor):
-                raise TypeError("state must be a torch.Tensor")
-            if state.dtype != torch.float32:
-                raise TypeError("state must be float32, got %s" % state.dtype)
-            if tuple(state.shape) != state_shape or not state.is_contiguous():
-                raise ValueError("rule=%r needs a contiguous state of shape %r, got %r" % (rule, state_shape,
-                                                                                         tuple(state.shape)))
-            _check_pinned("state", state)
+            _check_state_tensor("state", state, state_shape, "rule=%r" % rule)
         if host_table.is_cuda or not host_table.is_pinned():
             raise ValueError("host_table must live in PINNED host memory (tensor.pin_memory())")
         super().__init__(host_table, device=device, capacity_rows=WAYS * num_sets)
         self.rule, self.eps = rule, float(eps)
+        self._state_planes = []          # (home, cached, row_bytes) of the state tensors that ride on the slots: 0 to 2
         self.state = self.state_cache = None
         self.state_row_bytes = self.state_row_offset = 0
         if state_shape is not None:
@@ -263,7 +276,8 @@ class DynamicRowCache(CachedHostTable):
                 state = torch.full(state_shape, float(initial_accumulator_value), dtype=torch.float32).pin_memory()
             self.state = state
             self.state_row_bytes = 4 * (self.width if rule == "adagrad" else 1)
-            self._raw_state, self.state_cache, self.state_row_offset = self._plane_behind(state, WAYS * num_sets)
+            self._raw_state, self.state_cache, self.state_row_offset = self._add_state_plane(state, self.state_row_bytes)
+        self._aligned_state = (("state", self.state),) if rule == "adagrad" else ()   # per-element state: lanes reach it
         self.num_sets = num_sets
         self.capacity_rows = WAYS * num_sets
         self.row_bytes = self.width * host_table.element_size()
@@ -291,30 +305,19 @@ class DynamicRowCache(CachedHostTable):
                 p(self.tags.data_ptr()), p(self.stamps.data_ptr()), p(self.dirty.data_ptr()),
                 p(self.slot_of_row.data_ptr()), p(self.words.data_ptr()))
 
-    def _plane_behind(self, home, slots):
-        """(raw buffer, cached plane, row offset) of a state tensor `home` ([rows, width] or [rows] float32): `slots`
-        of its rows on the device, like the cached table rows -- over-allocated by one row so that the plane can start
-        where (plane - home) % row_bytes == 0, row_offset = (plane - home) / row_bytes."""
-        row_bytes = 4 * (home.shape[1] if home.dim() == 2 else 1)
-        raw = torch.empty(((slots + 1) * row_bytes,), dtype=torch.uint8, device=self.device)
-        shift = (home.data_ptr() - raw.data_ptr()) % row_bytes
-        plane = raw[shift:shift + slots * row_bytes].view(torch.float32)
-        if home.dim() == 2:
-            plane = plane.view(slots, home.shape[1])
-        assert (plane.data_ptr() - home.data_ptr()) % row_bytes == 0
-        return raw, plane, (plane.data_ptr() - home.data_ptr()) // row_bytes
-
-    def _plane(self):
-        p = ctypes.c_void_p
-        return (p(self.state.data_ptr()), p(self.state_cache.data_ptr()), self.state_row_bytes)
+    def _add_state_plane(self, home, row_bytes):
+        """Let the state tensor `home` ride on the cache's slots: its _plane_behind, noted in self._state_planes."""
+        raw, cached, row_offset = _plane_behind(home, self.capacity, self.device)
+        self._state_planes.append((home, cached, row_bytes))
+        return raw, cached, row_offset
 
     def _call_with_planes(self, name, args):
-        """The entry point `name` of the cache's planes: the table's alone, or with the state plane."""
+        """The entry point `name` of the cache's planes: the table's alone, with one state plane or with two."""
+        p = ctypes.c_void_p
+        for home, cached, row_bytes in self._state_planes:
+            args += (p(home.data_ptr()), p(cached.data_ptr()), row_bytes)
         with torch.cuda.device(self.device):
-            if self.state is None:
-                getattr(_lib.lib(), name)(*args)
-            else:
-                getattr(_lib.lib(), name + "_with_state")(*(args + self._plane()))
+            getattr(_lib.lib(), name + ("", "_with_state", "_with_states")[len(self._state_planes)])(*args)
 
     def _counts(self, ids, count, last_id):
         """(num_valid, count word, word is int64, last_id word) of a prefetch, validated."""
@@ -378,7 +381,7 @@ class DynamicRowCache(CachedHostTable):
         one-element float32 device tensor."""
         if self.rule != "sgd":
             raise RuntimeError("this cache trains with rule=%r: use apply_update()" % self.rule)
-        self._apply(ids, rows, lr, count, last_id)
+        self._step(ids, rows, lr, count, last_id)
 
     def apply_update(self, ids, rows, lr, count=None, last_id=None):
         """The cache's rule through the cache: for every valid entry k of the compressed gradient (ids, rows), row
@@ -393,7 +396,7 @@ class DynamicRowCache(CachedHostTable):
         the caller's ids as int64 next to the translated ones to name the bits (int64 ids are passed as they are,
         int32 ids cost one elementwise widening launch), and rounding_step is advanced on the device afterwards -- on
         every call, like SparseUpdater.apply."""
-        self._apply(ids, rows, lr, count, last_id)
+        self._step(ids, rows, lr, count, last_id)
 
     def _check_step(self, ids, rows, lr):
         """The arguments of a step, validated: (lr as a float, lr as a device word or None)."""
@@ -414,37 +417,41 @@ class DynamicRowCache(CachedHostTable):
         _ops._check_dev("rows", rows, self.device)
         return lr, lr_word
 
-    def _apply(self, ids, rows, lr, count, last_id):
+    def _step(self, ids, rows, lr, count, last_id):
+        """One step through the cache, whatever the rule: the checks, _before_step, the prefetch for update, then -- unless
+        the batch has no entries -- _launch_step with the count as the prefetch resolved it; rounding_step moves last."""
         lr, lr_word = self._check_step(ids, rows, lr)
         _ops._check_alignment("table", self.table.data_ptr(), self.table.element_size(), self.width,
                               others=(("rows", rows.data_ptr()),),
-                              state=(("state", self.state.data_ptr()),) if self.rule == "adagrad" else (), max_lanes=None)
+                              state=tuple((name, t.data_ptr()) for name, t in self._aligned_state), max_lanes=None)
+        self._before_step()
         self.prefetch(ids, for_update=True, count=count, last_id=last_id)
-        n = ids.numel()
-        if n == 0:
-            return self._advance_rounding_step()
+        if ids.numel():
+            # the count of valid entries as the prefetch resolved it on the device: one int64 word
+            resolved = self.words[STAT_WORDS.index("batch_count"):STAT_WORDS.index("batch_count") + 1]
+            with torch.cuda.device(self.device):
+                self._launch_step(ids, rows, float(lr), lr_word, resolved)
+        return self._advance_rounding_step()
+
+    def _before_step(self):
+        """What a rule does on EVERY call before the prefetch, also one without entries.  Here: nothing."""
+
+    def _launch_step(self, ids, rows, lr, lr_word, resolved):
+        """Translate the ids once per plane, then ONE launch of the sparse step: the plain one (rule="sgd"), the placed one
+        (a state plane) or, with stochastic rounding, the placed and named one."""
         translated = self.translate(ids)
-        # the count of valid entries as the prefetch resolved it on the device: one int64 word
-        resolved = self.words[STAT_WORDS.index("batch_count"):STAT_WORDS.index("batch_count") + 1]
-        args = (ctypes.c_void_p(self.table.data_ptr()), _ops._ELEM[self.table.dtype], self.width, _ops._ptr(self.state),
-                _ops.UPDATE_RULES[self.rule], _ops._ptr(translated), _ops._INDEX[torch.int64], _ops._ptr(rows), n, 1, -1,
-                _ops._ptr(resolved), 1, None, float(lr), _ops._ptr(lr_word), self.eps if self.state is not None else 0.0,
-                _ops._stream(ids))
         state_ids = None if self.state is None else self._translate(ids, self.state_row_offset)
+        args = [ctypes.c_void_p(self.table.data_ptr()), _ops._ELEM[self.table.dtype], self.width, _ops._ptr(self.state),
+                _ops.UPDATE_RULES[self.rule], _ops._ptr(translated), _ops._INDEX[torch.int64], _ops._ptr(rows), ids.numel(),
+                1, -1, _ops._ptr(resolved), 1, None, lr, _ops._ptr(lr_word), self.eps if self.state is not None else 0.0]
         if self.stochastic_rounding:
             names = self._row_names(ids)
-            with torch.cuda.device(self.device):
-                _lib.lib().cuembed_sparse_row_update_placed_stochastic(
-                    *(args[:-1] + (self.seed, 0, _ops._ptr(self.rounding_step), args[-1], _ops._ptr(state_ids),
-                                   _ops._ptr(names))))
-            return self._advance_rounding_step()
-        if self.state is None:
-            with torch.cuda.device(self.device):
-                _lib.lib().cuembed_sparse_row_update(*args)
-            return None
-        with torch.cuda.device(self.device):
-            _lib.lib().cuembed_sparse_row_update_placed(*(args + (_ops._ptr(state_ids),)))
-        return None
+            _lib.lib().cuembed_sparse_row_update_placed_stochastic(
+                *args, self.seed, 0, _ops._ptr(self.rounding_step), _ops._stream(ids), _ops._ptr(state_ids), _ops._ptr(names))
+        elif self.state is not None:
+            _lib.lib().cuembed_sparse_row_update_placed(*args, _ops._stream(ids), _ops._ptr(state_ids))
+        else:
+            _lib.lib().cuembed_sparse_row_update(*args, _ops._stream(ids))
 
     @staticmethod
     def _row_names(ids):
@@ -513,16 +520,8 @@ class AdamRowCache(DynamicRowCache):
         rows, width = host_table.shape
         shapes = dict(exp_avg=(rows, width), exp_avg_sq=(rows,) if rowwise else (rows, width))
         for name, t in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
-            if t is None:
-                continue
-            if not isinstance(t, torch.Tensor):
-                raise TypeError("%s must be a torch.Tensor" % name)
-            if t.dtype != torch.float32:
-                raise TypeError("%s must be float32, got %s" % (name, t.dtype))
-            if tuple(t.shape) != shapes[name] or not t.is_contiguous():
-                raise ValueError("rowwise=%r needs a contiguous %s of shape %r, got %r" % (rowwise, name, shapes[name],
-                                                                                         tuple(t.shape)))
-            _check_pinned(name, t)
+            if t is not None:
+                _check_state_tensor(name, t, shapes[name], "rowwise=%r" % rowwise)
         super().__init__(host_table, device=device, num_sets=num_sets, eps=eps, stochastic_rounding=stochastic_rounding,
                          seed=seed)
         self.rule = "rowwise_adam" if rowwise else "adam"        # (apply_sgd points to apply_update)
@@ -531,19 +530,13 @@ class AdamRowCache(DynamicRowCache):
         self.exp_avg = torch.zeros(shapes["exp_avg"], dtype=torch.float32).pin_memory() if exp_avg is None else exp_avg
         self.exp_avg_sq = (torch.zeros(shapes["exp_avg_sq"], dtype=torch.float32).pin_memory() if exp_avg_sq is None
                            else exp_avg_sq)
-        slots = WAYS * num_sets
-        self._raw_exp_avg, self.exp_avg_cache, self.exp_avg_row_offset = self._plane_behind(self.exp_avg, slots)
-        self._raw_exp_avg_sq, self.exp_avg_sq_cache, self.exp_avg_sq_row_offset = self._plane_behind(self.exp_avg_sq, slots)
+        self._raw_exp_avg, self.exp_avg_cache, self.exp_avg_row_offset = self._add_state_plane(self.exp_avg, 4 * width)
+        self._raw_exp_avg_sq, self.exp_avg_sq_cache, self.exp_avg_sq_row_offset = self._add_state_plane(
+            self.exp_avg_sq, 4 if rowwise else 4 * width)
+        self._aligned_state = (("exp_avg", self.exp_avg),) + (() if rowwise else (("exp_avg_sq", self.exp_avg_sq),))
         self.powers, self.bias_factor = _ops.new_adam_clock(self.device)
         self._one = None if self.bias_correction else torch.ones((1,), dtype=torch.float32, device=self.device)
         self._placed = None
-
-    def _call_with_planes(self, name, args):
-        p = ctypes.c_void_p
-        planes = (p(self.exp_avg.data_ptr()), p(self.exp_avg_cache.data_ptr()), 4 * self.width,
-                  p(self.exp_avg_sq.data_ptr()), p(self.exp_avg_sq_cache.data_ptr()), 4 if self.rowwise else 4 * self.width)
-        with torch.cuda.device(self.device):
-            getattr(_lib.lib(), name + "_with_states")(*(args + planes))
 
     def apply_update(self, ids, rows, lr, count=None, last_id=None):
         """One Adam step through the cache, call for call SparseAdamUpdater.apply: for every valid entry k of the
@@ -560,40 +553,32 @@ class AdamRowCache(DynamicRowCache):
         as int64 next to the three translated arrays (int64 ids as they are, int32 ids through one elementwise
         widening launch), and rounding_step is advanced on the device afterwards -- on every call, like
         SparseAdamUpdater.apply."""
-        lr, lr_word = self._check_step(ids, rows, lr)
-        state = (("exp_avg", self.exp_avg.data_ptr()),)
-        if not self.rowwise:
-            state += (("exp_avg_sq", self.exp_avg_sq.data_ptr()),)
-        _ops._check_alignment("table", self.table.data_ptr(), self.table.element_size(), self.width,
-                              others=(("rows", rows.data_ptr()),), state=state, max_lanes=None)
+        self._step(ids, rows, lr, count, last_id)
+
+    def _before_step(self):
         _ops.adam_clock_advance(self.powers, self.bias_factor, self.betas)
-        self.prefetch(ids, for_update=True, count=count, last_id=last_id)
+
+    def _launch_step(self, ids, rows, lr, lr_word, resolved):
+        """ONE launch translates the ids for the three planes, ONE launch of the placed Adam step follows: the plain one,
+        or, with stochastic rounding, the named one."""
         n = ids.numel()
-        if n == 0:
-            return self._advance_rounding_step()
         if self._placed is None or self._placed.shape[1] < n:
             self._placed = torch.empty((3, n), dtype=torch.int64, device=self.device)
-        placed = [self._placed[k, :n] for k in range(3)]
-        # the count of valid entries as the prefetch resolved it on the device: one int64 word
-        resolved = self.words[STAT_WORDS.index("batch_count"):STAT_WORDS.index("batch_count") + 1]
+        placed = [_ops._ptr(self._placed[k, :n]) for k in range(3)]
         beta1, beta2 = self.betas
         bias = self.bias_factor if self.bias_correction else self._one
         L = _lib.lib()
-        with torch.cuda.device(self.device):
-            L.cuembed_translate_indices_for_row_cache_planes(
-                _ops._ptr(ids), _ops._INDEX[ids.dtype], n, _ops._ptr(self.slot_of_row), self.rows,
-                self.cache_row_offset, _ops._ptr(placed[0]), self.exp_avg_row_offset, _ops._ptr(placed[1]),
-                self.exp_avg_sq_row_offset, _ops._ptr(placed[2]), _ops._stream(ids))
-            step = (ctypes.c_void_p(self.table.data_ptr()), _ops._ELEM[self.table.dtype], self.width,
-                    ctypes.c_void_p(self.exp_avg.data_ptr()), ctypes.c_void_p(self.exp_avg_sq.data_ptr()),
-                    _ops.ADAM_RULES[self.rule], _ops._ptr(placed[0]), _ops._INDEX[torch.int64], _ops._ptr(rows), n, 1, -1,
-                    _ops._ptr(resolved), 1, None, float(lr), _ops._ptr(lr_word), 1.0, _ops._ptr(bias), beta1,
-                    1.0 - beta1, beta2, 1.0 - beta2, self.eps, self.weight_decay)
-            if self.stochastic_rounding:
-                names = self._row_names(ids)
-                L.cuembed_sparse_row_adam_placed_stochastic(
-                    *(step + (self.seed, 0, _ops._ptr(self.rounding_step), _ops._stream(ids), _ops._ptr(placed[1]),
-                              _ops._ptr(placed[2]), _ops._ptr(names))))
-            else:
-                L.cuembed_sparse_row_adam_placed(*(step + (_ops._stream(ids), _ops._ptr(placed[1]), _ops._ptr(placed[2]))))
-        return self._advance_rounding_step()
+        L.cuembed_translate_indices_for_row_cache_planes(
+            _ops._ptr(ids), _ops._INDEX[ids.dtype], n, _ops._ptr(self.slot_of_row), self.rows, self.cache_row_offset,
+            placed[0], self.exp_avg_row_offset, placed[1], self.exp_avg_sq_row_offset, placed[2], _ops._stream(ids))
+        args = [ctypes.c_void_p(self.table.data_ptr()), _ops._ELEM[self.table.dtype], self.width,
+                ctypes.c_void_p(self.exp_avg.data_ptr()), ctypes.c_void_p(self.exp_avg_sq.data_ptr()),
+                _ops.ADAM_RULES[self.rule], placed[0], _ops._INDEX[torch.int64], _ops._ptr(rows), n, 1, -1,
+                _ops._ptr(resolved), 1, None, lr, _ops._ptr(lr_word), 1.0, _ops._ptr(bias), beta1, 1.0 - beta1, beta2,
+                1.0 - beta2, self.eps, self.weight_decay]
+        if self.stochastic_rounding:
+            names = self._row_names(ids)
+            L.cuembed_sparse_row_adam_placed_stochastic(*args, self.seed, 0, _ops._ptr(self.rounding_step), _ops._stream(ids),
+                                                        placed[1], placed[2], _ops._ptr(names))
+        else:
+            L.cuembed_sparse_row_adam_placed(*args, _ops._stream(ids), placed[1], placed[2])

@@ -10,31 +10,12 @@
 // The fp32 values are exact (small integers, sqrt of perfect squares, power-of-two denominators) but carry more bits
 // than the 16-bit types hold (the update is a multiple of 3 * 2^-12 on weights of magnitude up to 8), so every store
 // really rounds.  Built and run by tests/test_gpu_cpp_row_cache_stochastic.py.
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-#include <hip/hip_runtime.h>
-
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <vector>
 
-#include "cuembed/include/row_cache.hpp"
 #include "cuembed/include/sparse_adam.hpp"
+#include "row_cache_kat_common.hpp"
 
-#define HIP_OK(x)                                                              \
-  do {                                                                         \
-    hipError_t e_ = (x);                                                       \
-    if (e_ != hipSuccess) {                                                    \
-      std::fprintf(stderr, "%s failed: %s\n", #x, hipGetErrorString(e_));      \
-      std::exit(2);                                                            \
-    }                                                                          \
-  } while (0)
-
-template <typename T> T From(float v);
-template <> __half From<__half>(float v) { return __float2half(v); }
-template <> __hip_bfloat16 From<__hip_bfloat16>(float v) { return __float2bfloat16(v); }
 inline uint16_t RoundBits(__half, float x, uint32_t r) { return cuembed::detail::StochasticRoundToHalfBits(x, r); }
 inline uint16_t RoundBits(__hip_bfloat16, float x, uint32_t r) { return cuembed::detail::StochasticRoundToBf16Bits(x, r); }
 template <typename T>
@@ -44,18 +25,7 @@ uint16_t Bits(T v) {
   return b;
 }
 
-static int g_failures = 0;
-static int g_checks = 0;
-
-static void Expect(const bool ok, const char* what, const char* detail, const long at = -1) {
-  ++g_checks;
-  if (ok) return;
-  ++g_failures;
-  std::fprintf(stderr, "FAILED %s: %s (at %ld)\n", what, detail, at);
-}
-
 constexpr int kRows = 200;
-constexpr int kSlots = cuembed::kRowCacheWays;   // one set
 constexpr int kBatch = 70;
 constexpr int kFirstRow = 100;                   // entry k names row 100 + k
 constexpr float kLr = 0.75f / 64.f;
@@ -69,29 +39,6 @@ constexpr float kMagnitude[3] = {4.f, 6.f, 2.f};
 constexpr float kAccumulator[3] = {33.f, 13.f, 221.f};
 //! The first moment of row r before the step: an even integer in [-4, 4] (m / 2 + g / 2 is exact).
 inline float FirstOf(const int r) { return static_cast<float>((r % 5) * 2 - 4); }
-
-template <typename T>
-T* Pinned(const size_t n) {
-  T* p = nullptr;
-  HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&p), n * sizeof(T), hipHostMallocDefault));
-  return p;
-}
-
-template <typename T>
-T* Device(const std::vector<T>& h) {
-  T* p = nullptr;
-  HIP_OK(hipMalloc(reinterpret_cast<void**>(&p), h.size() * sizeof(T)));
-  HIP_OK(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  return p;
-}
-
-//! `slots` rows of row_bytes in HBM, a whole number of rows away from `home` (one row over-allocated).
-static char* PlaneBehind(const void* home, const int64_t row_bytes, char** raw) {
-  HIP_OK(hipMalloc(reinterpret_cast<void**>(raw), static_cast<size_t>((kSlots + 1) * row_bytes)));
-  const intptr_t gap = reinterpret_cast<intptr_t>(home) - reinterpret_cast<intptr_t>(*raw);
-  const int64_t shift = ((gap % row_bytes) + row_bytes) % row_bytes;
-  return *raw + shift;
-}
 
 //! The stochastic rounding of x for (table row, column), as the specification's host functions give it.
 template <typename ElemT>
@@ -155,28 +102,8 @@ void Case(const bool adam, const int width, hipStream_t stream, const char* what
   for (size_t i = 0; i < want_table.size(); ++i) differ += want_table[i] != nearest_table[i];
   Expect(differ * 8 >= static_cast<size_t>(kBatch) * width, what, "the data: stochastic and nearest differ often");
 
-  cuembed::RowCache c;
-  c.table = table;
-  c.row_bytes = static_cast<int64_t>(width) * sizeof(ElemT);
-  c.num_rows = kRows;
-  c.num_sets = 1;
-  c.state = first;
-  c.state_row_bytes = 4 * first_width;
-  char *raw_rows = nullptr, *raw_first = nullptr, *raw_second = nullptr;
-  c.cache_rows = PlaneBehind(table, c.row_bytes, &raw_rows);
-  c.state_cache = reinterpret_cast<float*>(PlaneBehind(first, c.state_row_bytes, &raw_first));
-  if (adam) {
-    c.state2 = second;
-    c.state2_row_bytes = 4 * width;
-    c.state2_cache = reinterpret_cast<float*>(PlaneBehind(second, c.state2_row_bytes, &raw_second));
-  }
-  c.tags = Device(std::vector<int64_t>(kSlots, -1));
-  c.stamps = Device(std::vector<uint32_t>(kSlots, 0));
-  c.dirty = Device(std::vector<uint8_t>(kSlots, 0));
-  c.slot_of_row = Device(std::vector<int32_t>(kRows, -1));
-  std::vector<unsigned long long> words_h(cuembed::kCacheWords, 0);
-  words_h[cuembed::kCacheClock] = 1;
-  c.words = Device(words_h);
+  const cuembed::RowCache c = OneSetCache(table, static_cast<int64_t>(width) * sizeof(ElemT), kRows, first, 4 * first_width,
+                                          second, adam ? 4 * width : 0);
   IndexT* ids = Device(ids_h);
   int64_t* names = Device(names_h);
   ElemT* grad = Device(grad_h);
@@ -186,19 +113,11 @@ void Case(const bool adam, const int width, hipStream_t stream, const char* what
   int64_t* placed_second = Device(std::vector<int64_t>(kBatch, -7));
 
   // 1. the prefetch
-  cuembed::RowCacheCounts counts;
-  counts.num_valid = kBatch;
-  size_t lwork = 0;
-  cuembed::RowCachePrefetch<IndexT>(c, ids, kBatch, counts, true, nullptr, &lwork, stream);
-  char* work = nullptr;
-  HIP_OK(hipMalloc(reinterpret_cast<void**>(&work), lwork ? lwork : 1));
-  cuembed::RowCachePrefetch<IndexT>(c, ids, kBatch, counts, true, work, &lwork, stream);
+  PrefetchForUpdate(c, ids, kBatch, stream);
   // 2. one translate for the planes, one named step (the count as the prefetch resolved it; the step in a device word)
-  const int64_t row_offset = (static_cast<char*>(c.cache_rows) - reinterpret_cast<char*>(table)) / c.row_bytes;
-  const int64_t first_offset =
-      (reinterpret_cast<char*>(c.state_cache) - reinterpret_cast<char*>(first)) / c.state_row_bytes;
-  const int64_t second_offset =
-      adam ? (reinterpret_cast<char*>(c.state2_cache) - reinterpret_cast<char*>(second)) / c.state2_row_bytes : 0;
+  const int64_t row_offset = PlaneOffset(table, c.cache_rows, c.row_bytes);
+  const int64_t first_offset = PlaneOffset(first, c.state_cache, c.state_row_bytes);
+  const int64_t second_offset = adam ? PlaneOffset(second, c.state2_cache, c.state2_row_bytes) : 0;
   cuembed::TranslateIndicesForRowCachePlanes<IndexT>(ids, kBatch, c.slot_of_row, kRows, row_offset, placed_rows,
                                                      first_offset, placed_first, second_offset,
                                                      adam ? placed_second : nullptr, stream);
@@ -237,8 +156,7 @@ void Case(const bool adam, const int width, hipStream_t stream, const char* what
   HIP_OK(hipGetLastError());
 
   // no resident row sits in the slot of its own number, or is named by its translated id
-  std::vector<int64_t> got_rows(kBatch);
-  HIP_OK(hipMemcpy(got_rows.data(), placed_rows, kBatch * sizeof(int64_t), hipMemcpyDeviceToHost));
+  const std::vector<int64_t> got_rows = Host(placed_rows, kBatch);
   for (int k = 0; k < kBatch; ++k) {
     const bool resident = k < kSlots;
     Expect(got_rows[k] == (resident ? row_offset + k : kFirstRow + k), what, "translated id, table plane", k);
@@ -262,19 +180,13 @@ void Case(const bool adam, const int width, hipStream_t stream, const char* what
     Expect(first[i] == want_first[i], what, "first state plane after the flush", static_cast<long>(i / first_width));
   for (size_t i = 0; i < want_second.size(); ++i)
     Expect(second[i] == want_second[i], what, "second state plane after the flush", static_cast<long>(i / width));
-  HIP_OK(hipMemcpy(words_h.data(), c.words, words_h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  const std::vector<unsigned long long> words_h = Host(c.words, cuembed::kCacheWords);
   Expect(words_h[cuembed::kCacheMisses] == kBatch && words_h[cuembed::kCacheUnplaced] == kBatch - kSlots, what,
          "misses / unplaced");
   Expect(words_h[cuembed::kCacheWriteBacks] == kSlots && words_h[cuembed::kCacheOverflow] == 0, what,
          "write-backs / overflow");
 
-  for (void* p : {static_cast<void*>(raw_rows), static_cast<void*>(raw_first), static_cast<void*>(raw_second),
-                  static_cast<void*>(c.tags), static_cast<void*>(c.stamps), static_cast<void*>(c.dirty),
-                  static_cast<void*>(c.slot_of_row), static_cast<void*>(c.words), static_cast<void*>(ids),
-                  static_cast<void*>(names), static_cast<void*>(grad), static_cast<void*>(step_word),
-                  static_cast<void*>(placed_rows), static_cast<void*>(placed_first), static_cast<void*>(placed_second),
-                  static_cast<void*>(work)})
-    if (p != nullptr) HIP_OK(hipFree(p));
+  FreeDevice();
   HIP_OK(hipHostFree(table));
   HIP_OK(hipHostFree(first));
   if (second != nullptr) HIP_OK(hipHostFree(second));
@@ -291,10 +203,5 @@ int main() {
     Case<__hip_bfloat16, int64_t>(true, width, stream, "lazy Adam, bf16, int64");
   }
   HIP_OK(hipStreamDestroy(stream));
-  if (g_failures) {
-    std::fprintf(stderr, "%d of %d checks FAILED\n", g_failures, g_checks);
-    return 1;
-  }
-  std::printf("row cache stochastic rounding: %d known-answer checks passed\n", g_checks);
-  return 0;
+  return Report("row cache stochastic rounding");
 }
