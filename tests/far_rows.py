@@ -20,6 +20,15 @@ Layout.  The GPU file fills every alias with a poison row and checks it after a 
     Layout([(view, rows), ...])                      the asserts; .aliases = [(byte offset, length)] to poison
     pick(views, seed, below=None)                    boundary_rows for every view, random rows re-drawn until Layout holds
     fixed_bags / csr_bags / compact                  ids over the picked rows, and their remap to 0..k-1
+
+A View may know more about how its rows are addressed, and aliases() then lists more: row_base (a table of a group of
+separate tensors: the global id narrowed BEFORE row_base is subtracted, grouped_step_aliases) and lane_bytes (grad_y of the
+mixed-width backward: its 31-bit source offset in lane units, source_offset_aliases).
+
+    mixed_views / MIXED_TABLES                       three tables of different widths in grouped_views' regions
+    grouped_step_views / pick_grouped                three separate tables and their states, two layouts
+    row_cache_views                                  the home planes (and slot_of_row) of the row cache's move
+    mixed_grad_y_views                               grad_y that ends 2 lane units under 2^31
 """
 import numpy as np
 
@@ -30,6 +39,7 @@ ARENA_BYTES = 2 * GUARD + SLACK
 ELEM_THRESHOLDS = (1 << 31, 1 << 32)
 BYTE_THRESHOLDS = (1 << 31, 1 << 32, 1 << 33, 1 << 34)
 ROW_THRESHOLDS = (1 << 31, 1 << 32)
+LANE_THRESHOLDS = (1 << 30,)          # the mixed-width backward's source offset: 31 bits under the run-end bit
 RANDOM_ROWS = 6
 
 
@@ -37,11 +47,22 @@ class View:
     """A contiguous [rows, width] tensor of `elem_size`-byte elements that starts `base` bytes into the arena.  Default
     rows: the first row at or above 16 GiB past the base is the last one."""
 
-    def __init__(self, name, base, elem_size, width, rows=None):
+    def __init__(self, name, base, elem_size, width, rows=None, row_base=0, lane_bytes=None, clip_low=False):
         self.name, self.base, self.elem_size, self.width = name, int(base), int(elem_size), int(width)
         self.row_bytes = self.elem_size * self.width
         self.rows = -(-GUARD // self.row_bytes) + 1 if rows is None else int(rows)
+        #: a table of a group of separate tensors: the kernel is handed row + row_base (grouped_step_aliases)
+        self.row_base = int(row_base)
+        #: the mixed-width backward's grad_y: its rows are addressed in lanes of this many bytes (source_offset_aliases)
+        self.lane_bytes = lane_bytes
+        #: a view that must start at byte 0 of the arena: the aliases in front of the arena are left out (aliases())
+        self.clip_low = clip_low
         assert self.base % self.elem_size == 0 and self.rows > 0 and self.row_bytes > 0
+        assert lane_bytes is None or self.row_bytes % lane_bytes == 0
+
+    def moved(self, base):
+        """The same tensor at another byte of the arena."""
+        return View(self.name, base, self.elem_size, self.width, self.rows, self.row_base, self.lane_bytes, self.clip_low)
 
     @property
     def end(self):
@@ -57,8 +78,12 @@ class View:
 def thresholds(view):
     """Every threshold that both of its rows fit under: (what, threshold, last row below, first row at or above)."""
     found = []
-    for what, values, unit in (("elements", ELEM_THRESHOLDS, view.width), ("bytes", BYTE_THRESHOLDS, view.row_bytes),
-                               ("rows", ROW_THRESHOLDS, 1)):
+    units = [("elements", ELEM_THRESHOLDS, view.width), ("bytes", BYTE_THRESHOLDS, view.row_bytes), ("rows", ROW_THRESHOLDS, 1)]
+    if view.row_base:
+        units.append(("global rows", tuple(t - view.row_base for t in ROW_THRESHOLDS), 1))
+    if view.lane_bytes:
+        units.append(("lanes", LANE_THRESHOLDS, view.row_bytes // view.lane_bytes))
+    for what, values, unit in units:
         for t in values:
             first = -(-t // unit)
             if 1 <= first < view.rows:
@@ -97,8 +122,36 @@ def aliases(view, row):
         found.add(view.base + narrow(row) * view.row_bytes)
         found.add(view.base + narrow(row * view.width) * view.elem_size)
         found.add(view.base + narrow(row * view.row_bytes))
+    if view.row_base:
+        found.update(grouped_step_aliases(view, row))
+    if view.lane_bytes:
+        found.update(source_offset_aliases(view, row))
     found.discard(view.addr(row))
+    if view.clip_low:
+        found = {a for a in found if a >= 0}
     return sorted(found)
+
+
+def grouped_step_aliases(view, row):
+    """A table (or state tensor) of a group of SEPARATE tensors: the kernel is handed the GLOBAL id row + row_base and
+    subtracts row_base.  Narrowing AFTER the subtraction is aliases()' own list; narrowing the global id BEFORE it gives
+    narrowed(global) - row_base as the local row, in 64 bits from there on."""
+    return {view.base + (narrow(int(row) + view.row_base) - view.row_base) * view.row_bytes for narrow in (_u32, _s32)}
+
+
+def source_offset_aliases(view, row):
+    """grad_y of the mixed-width backward: a lookup's source is sample * lanes per row + its column lane, in lanes of
+    lane_bytes, kept in 31 bits of a word whose bit 31 is the run-end bit.  What a wrong mask, a 30-bit field or a
+    sign extension from bit 30 would read instead, and the byte offset narrowed to 32 bits -- each seen from the first
+    and from the last lane of the row (a row may straddle a threshold), as the row-long range it would start."""
+    lanes = view.row_bytes // view.lane_bytes
+    found = set()
+    for j in (0, lanes - 1):
+        off = int(row) * lanes + j
+        forms = [off & ~(1 << 30), off & ((1 << 30) - 1), off - (1 << 31) if off & (1 << 30) else off]
+        found.update(view.base + (f - j) * view.lane_bytes for f in forms)
+        found.update(view.base + narrow(off * view.lane_bytes) - j * view.lane_bytes for narrow in (_u32, _s32))
+    return found
 
 
 def _overlaps(intervals):
@@ -356,3 +409,144 @@ def optimizer_views(kind, width, scheme, rule):
 def optimizer_cases():
     """[(kind, width, scheme, rule)] that fit."""
     return [(k, w, s, rule) for k, w, s in OPTIMIZER_TABLES for rule in RULES if optimizer_views(k, w, s, rule)]
+
+
+# ---- mixed-width group forward: three tables of different widths -----------------------------------------------------
+#: (kind, widths, lane bytes of the launch).  fp16: 16-byte lanes.  bf16: the 4-byte row forces 4-byte lanes on every
+#: table, and table 1 has more than 2^31 rows.  fp32: 2048 elements are 512 lanes of 16 bytes, more than the 256 threads
+#: of a workgroup -- the second pass of the column loop.
+MIXED_TABLES = (("f16", (8, 64, 128), 16), ("bf16", (64, 2, 36), 4), ("f32", (2048, 4, 64), 16))
+
+
+def mixed_views(elem_size, widths):
+    """grouped_views' three regions (9 GiB each, 4 KiB apart, the first 4 GiB + 4 KiB in) holding tables of DIFFERENT
+    widths, in the group's order.  A 4-byte element's sign-wrapped offset reaches 8 GiB back, which the first region
+    does not have: with 4-byte elements table t lies in region (t + 1) % 3 and the table of the first region -- the last
+    of the group -- stops short of 2^31 elements (its byte offsets still pass 2^32)."""
+    assert len(widths) == 3
+    views = []
+    for t, w in enumerate(widths):
+        region = (t + 1) % 3 if elem_size == 4 else t
+        rows = GROUPED_BYTES // (elem_size * w)
+        if elem_size == 4 and region == 0:
+            rows = min(rows, ((1 << 31) - 1) // w)
+        views.append(View("table%d" % t, (1 << 32) + GAP + region * (GROUPED_BYTES + GAP), elem_size, w, rows))
+    return views
+
+
+# ---- grouped optimizer step: three SEPARATE tables and their states -----------------------------------------------------
+#: layout "local": a far table is table 1 between a 17-row and a 42-row table -- row_base[1] = 17 is subtracted from an id
+#: whose LOCAL row passes the element threshold (2^32 elements; 2^31 rows of 4 bytes; Adam, whose two moments of 2^32
+#: elements do not fit, 2^31 elements).  Layout "global": table 0 has FLAT_ROW_COUNTS[0] = 2^31 + 5 four-byte rows, and
+#: the GLOBAL ids of the two small tables behind it pass 2^31 while their local rows are tiny.
+GROUPED_STEP_LAYOUTS = ("local", "global")
+GROUPED_STEP_TABLES = (("f16", 2), ("bf16", 2), ("f16", 256), ("bf16", 256), ("f32", 256), ("f16", 2056))
+
+
+def grouped_step_row_counts(layout, width, rule):
+    if layout == "global":
+        return FLAT_ROW_COUNTS if width == 2 else None
+    scheme = "rows31" if width == 2 else ("elems31" if rule == "adam" else "elems32")
+    return (17, SCHEMES[scheme](width), 42)
+
+
+def _reach_back(view, rows):
+    """How far in front of its base an alias of one of `rows` lies at the most."""
+    at0 = view.moved(0)
+    return max([0] + [-a for r in rows for a in aliases(at0, r)])
+
+
+def grouped_step_views(kind, width, rule, layout):
+    """[[table, state...] of table 0, of table 1, of table 2] (STATE[rule]'s order) of one grouped-step case -- every
+    View knows its row_base, so aliases() adds the addresses of a narrowing BEFORE the subtraction --, or None where the
+    tensors, or the aliases of their pinned rows, do not fit the arena.  Placement: every tensor needs as many bytes in
+    front of it as its furthest alias reaches back (and 1 MiB more: what lands there meets no tensor); they are laid out
+    in ascending order of that reach, 4 KiB apart, the tensors that need nothing in front of them last."""
+    counts = grouped_step_row_counts(layout, width, rule)
+    if counts is None:
+        return None
+    tensors, base = [], 0
+    for t, rows in enumerate(counts):
+        tensors.append((t, 0, View("table%d" % t, 0, ELEM_SIZE[kind], width, rows, row_base=base)))
+        for k, what in enumerate(STATE[rule]):
+            tensors.append((t, 1 + k, View("state%d_%d" % (k, t), 0, 4, width if what == "e" else 1, rows, row_base=base)))
+        base += rows
+    reach = {id(v): _reach_back(v, sorted(pinned_rows(v) | {0})) for _, _, v in tensors}
+    tiny = lambda v: reach[id(v)] == 0                                      # (behind the others: clear of their aliases)
+    placed, at = {}, SLACK
+    for t, k, v in sorted(tensors, key=lambda x: (tiny(x[2]), reach[id(x[2])], x[2].rows * x[2].row_bytes, x[0], x[1])):
+        at = -(-max(at, reach[id(v)] + SLACK) // GAP) * GAP
+        placed[(t, k)] = v.moved(at)
+        at = placed[(t, k)].end + GAP
+    if at - GAP > ARENA_BYTES:
+        return None
+    views = [[placed[(t, k)] for k in range(1 + len(STATE[rule]))] for t in range(len(counts))]
+    flat = [(v, sorted(pinned_rows(v))) for per in views for v in per]
+    return views if Layout.problem(flat) is None else None
+
+
+def grouped_step_cases():
+    """[(layout, kind, width, rule)] that fit."""
+    return [(lay, k, w, rule) for lay in GROUPED_STEP_LAYOUTS for k, w in GROUPED_STEP_TABLES for rule in RULES
+            if grouped_step_views(k, w, rule, lay)]
+
+
+def pick_grouped(views, seed, below=None, random_rows=RANDOM_ROWS):
+    """pick_shared() for every table of a group (views: grouped_step_views'), one Layout for all of them.  below: only
+    rows whose GLOBAL id is below it (a table behind it gets no rows).  Returns (Layout, [local rows of table t])."""
+    for attempt in range(64):
+        low = 2 * (attempt % 6)
+        rows, parts = [], []
+        for t, per in enumerate(views):
+            limit = None if below is None else below - per[0].row_base
+            picked = set()
+            if limit is None or limit > low + 2:
+                picked = set(boundary_rows(per[0], seed + 1000 * (attempt // 6) + 17 * t, limit, random_rows, low))
+                for v in per[1:]:
+                    picked |= set(boundary_rows(v, seed, limit, 0, low))
+            rows.append(sorted(picked))
+            parts += [(v, rows[-1]) for v in per]
+        if Layout.problem(parts) is None:
+            return Layout(parts), rows
+    raise AssertionError("no disjoint pick for %r: %s" % (views, Layout.problem(parts)))
+
+
+# ---- the row cache's move: home planes in the arena ----------------------------------------------------------------------
+ROW_CACHE_CASES = ("wide", "rows31")
+
+
+def row_cache_views(case):
+    """[home table, home state or None, slot_of_row or None].  "wide": fp16 W = 64, byte offsets to 2^34, 16-byte lanes
+    (slot_of_row is then an ordinary device tensor).  "rows31": a 4-byte table row and a 4-byte state row, 2^31 + 8 of
+    each -- row * row_bytes passes 2^33 in both planes -- and slot_of_row, as long, behind them in the arena."""
+    if case == "wide":
+        return [table_view("f16", 64, name="home"), None, None]
+    rows = (1 << 31) + 8
+    state = View("home_state", STATE_BASE, 4, 1, rows)
+    home = View("home", GUARD + GAP, 2, 2, rows)
+    return [home, state, View("slot_of_row", home.end + GAP, 4, 1, rows)]
+
+
+# ---- mixed-width group backward: grad_y up to the limit of the packed source offset ---------------------------------------
+#: 2^31 - 2 = 1986 * 1081311: with 1986 lanes to a row of grad_y, B = 1081311 samples end 2 lane units under 2^31, and
+#: one sample more is refused.  (2^31 - 1 is prime: no batch ends closer.)
+GRAD_Y_ROW_LANES = 1986
+GRAD_Y_BATCH = 1081311
+#: (kind, widths, lane bytes, arena base).  D = 1986 lanes; the widest table is 1024 lanes, the most a row may have.  The
+#: base leaves room for a source offset sign-extended from bit 30 (2^30 lanes back); the 16-byte lanes' view fills the
+#: arena from byte 0, and what a narrowing would form in FRONT of it is left out (View.clip_low) -- no edit of that kind
+#: may be tried on the device.
+MIXED_GRAD_Y = (("f16", (2048, 1022, 2, 900), 4, (1 << 32) + (1 << 16)),
+                ("f16", (4096, 2048, 4, 1796), 8, (1 << 33) + (1 << 16)),
+                ("f32", (4096, 2048, 4, 1796), 16, 0))
+
+
+def mixed_grad_y_views():
+    """[(kind, widths, lane bytes, View)]: grad_y [B, D] of the mixed-width backward as an arena view whose last row's
+    source offsets reach 2^31 - 2 lane units: 8 GiB at 4-byte lanes, 16 GiB at 8-byte lanes, 32 GiB - 32 bytes at 16."""
+    out = []
+    for kind, widths, lane, base in MIXED_GRAD_Y:
+        v = View("grad_y", base, ELEM_SIZE[kind], sum(widths), GRAD_Y_BATCH, lane_bytes=lane, clip_low=base == 0)
+        assert v.row_bytes == GRAD_Y_ROW_LANES * lane
+        out.append((kind, widths, lane, v))
+    return out

@@ -167,6 +167,155 @@ def test_every_rule_meets_every_threshold_its_state_allows():
         assert {k for k, _, _, r in cases if r == rule} == {"f32", "f16", "bf16"}
 
 
+def _aliases_hold(layout):
+    assert layout.aliases and all(0 <= a and a + n <= F.ARENA_BYTES for a, n in layout.aliases)
+    touched = sorted(layout.touched)
+    for a, n in layout.aliases:
+        assert all(a + n <= b or b + m <= a for b, m in touched)
+    assert all(b + m <= c for (b, m), (c, _) in zip(touched, touched[1:]))
+
+
+@pytest.mark.parametrize("kind,widths,lane", F.MIXED_TABLES, ids=[c[0] for c in F.MIXED_TABLES])
+def test_mixed_width_tables_share_the_arena(kind, widths, lane):
+    import torch
+    import cuembed_amd
+    from cuembed_amd.group_layout import mixed_lane_bytes
+    size = F.ELEM_SIZE[kind]
+    views = F.mixed_views(size, widths)
+    assert [v.width for v in views] == list(widths) and len(set(widths)) == 3
+    regions = sorted((v.base, v.end) for v in views)
+    assert all(b[0] - a[0] == F.GROUPED_BYTES + F.GAP and b[0] >= a[1] + F.GAP for a, b in zip(regions, regions[1:]))
+    assert mixed_lane_bytes(widths, size, [(v.name, v.base) for v in views]) == lane       # (the arena is 256-byte aligned)
+    for below in (None, INT32):
+        layout, rows = F.pick(views, seed=141, below=below)
+        for v, picked in zip(views, rows):
+            want = [t for t in F.thresholds(v) if below is None or t[3] < below]
+            assert _straddled(v, picked, below) == len(want) >= 2
+            assert max(picked) * v.row_bytes >= (1 << 32)
+            assert max(picked) * v.width >= INT32 or (size == 4 and v is views[2])      # (the first region's fp32 table)
+        _aliases_hold(layout)
+    if kind == "bf16":
+        assert views[1].row_bytes == 4 and views[1].rows > INT32 and ("rows", INT32) in {t[:2] for t in F.thresholds(views[1])}
+    if kind == "f32":
+        # two of the three tables pass 2^31 elements, the two-pass one among them; its row is 512 lanes of 16 bytes
+        assert views[0].rows * widths[0] > INT32 and views[1].rows * widths[1] > INT32 > views[2].rows * widths[2]
+        shape = cuembed_amd.mixed_group_launch_shape(torch.float32, torch.int64, widths, 5, num_hots=3)
+        assert shape["elems_per_lane"] == 4 and widths[0] // shape["elems_per_lane"] == 512 > shape["block_threads"] == 256
+
+
+GROUPED_STEP_CASES = F.grouped_step_cases()
+
+
+def test_grouped_step_cases_cover_what_fits():
+    cases = set(GROUPED_STEP_CASES)
+    rules = {lay: {r for l, _, _, r in cases if l == lay} for lay in F.GROUPED_STEP_LAYOUTS}
+    assert rules["local"] == set(F.RULES)                                # Adam: past 2^31 elements, the others 2^32
+    assert {"sgd", "rowwise_adagrad"} <= rules["global"]
+    assert {k for _, k, _, _ in cases} == {"f16", "bf16", "f32"} and {w for _, _, w, _ in cases} == {2, 256, 2056}
+    assert {(k, w) for lay, k, w, _ in cases if lay == "global"} == {("f16", 2), ("bf16", 2)}
+    for rule in F.RULES:
+        assert ("local", "f16", 256, rule) in cases and ("local", "f16", 2056, rule) in cases
+
+
+@pytest.mark.parametrize("case", GROUPED_STEP_CASES, ids=lambda c: "%s-%s-W%d-%s" % c)
+def test_grouped_step_tensors_share_the_arena(case):
+    layout_name, kind, width, rule = case
+    views = F.grouped_step_views(kind, width, rule, layout_name)
+    counts = F.grouped_step_row_counts(layout_name, width, rule)
+    assert [per[0].rows for per in views] == list(counts) and all(len(per) == 1 + len(F.STATE[rule]) for per in views)
+    assert [per[0].row_base for per in views] == [0, counts[0], counts[0] + counts[1]]
+    assert all(v.rows == per[0].rows and v.row_base == per[0].row_base for per in views for v in per)
+    layout, rows = F.pick_grouped(views, seed=151)
+    _aliases_hold(layout)
+    assert len(layout.touched) == sum(len(r) * len(per) for r, per in zip(rows, views))
+    for per, picked in zip(views, rows):
+        for v in per:
+            assert set(F.pinned_rows(v)) <= set(picked)
+    if layout_name == "local":
+        far, local = views[1][0], rows[1]
+        assert far.row_base == 17
+        if width == 2:
+            assert INT32 - 17 in local and INT32 - 18 in local and INT32 in local            # global and local 2^31
+        else:
+            assert max(local) * width >= ((1 << 31) if rule == "adam" else (1 << 32))
+        # narrowing after the subtraction: the single table's aliases, in every plane
+        for v in views[1]:
+            r = max(local)
+            plain = F.View(v.name, v.base, v.elem_size, v.width, v.rows)
+            assert set(F.aliases(plain, r)) <= set(F.aliases(v, r)) and (F.aliases(plain, r) or v.width == 1)
+    else:
+        # narrowing before it: the small tables' ids pass 2^31, their local rows do not -- (int32)id - row_base is
+        # 2^32 rows in front, inside the arena, in every plane
+        assert views[0][0].rows == F.FLAT_ROW_COUNTS[0] and views[1][0].row_base > INT32
+        for per, picked in zip(views[1:], rows[1:]):
+            for v in per:
+                for r in picked:
+                    assert F.aliases(v, r) == [v.addr(r) - (1 << 32) * v.row_bytes] and F.aliases(v, r)[0] >= 0
+        assert not F.aliases(F.View("t", views[1][0].base, 2, 2, 17), 5)             # (without row_base: none)
+    layout32, rows32 = F.pick_grouped(views, seed=151, below=INT32)
+    assert all(r + per[0].row_base < INT32 for per, picked in zip(views, rows32) for r in picked)
+
+
+@pytest.mark.parametrize("kind,widths,lane,view", F.mixed_grad_y_views(), ids=["lane%d" % c[2] for c in F.MIXED_GRAD_Y])
+def test_mixed_grad_y_reaches_the_packed_offsets_limit(kind, widths, lane, view):
+    import torch
+    from cuembed_amd.group_layout import INT_MAX, mixed_lane_bytes
+    from cuembed_amd.mixed_group import MixedTableGroup
+    from cuembed_amd.mixed_group_backward import _check_limits
+    size, B, D = F.ELEM_SIZE[kind], view.rows, sum(widths)
+    assert mixed_lane_bytes(widths, size, (("grad_y", view.base),)) == lane and view.end <= F.ARENA_BYTES
+    assert B * (D * size // lane) == (1 << 31) - 2 and 1 << 19 <= B <= 1 << 22 and len(widths) * B <= INT_MAX
+    group = MixedTableGroup([torch.zeros((3, w), dtype={"f16": torch.float16, "f32": torch.float32}[kind]) for w in widths])
+    _check_limits(group, B, lane)
+    with pytest.raises(ValueError, match="31 bits"):
+        _check_limits(group, B + 1, lane)
+    layout, (rows,) = F.pick([view], seed=161)
+    lanes = view.row_bytes // lane
+    cross = -(-(1 << 30) // lanes)
+    assert rows[0] in range(16) and rows[1] == rows[0] + 1 and rows[-1] == B - 1 and cross in rows and cross - 1 in rows
+    assert (cross - 1) * lanes < (1 << 30) <= cross * lanes and (B - 1) * lanes + lanes - 1 == (1 << 31) - 3
+    fits = {(what, t) for what, t, _, _ in F.thresholds(view)}
+    assert {("bytes", t) for t in F.BYTE_THRESHOLDS if t < view.rows * view.row_bytes - view.row_bytes} <= fits
+    assert ("bytes", 1 << 33) in fits or lane == 4
+    assert ("bytes", 1 << 34) in fits or lane < 16
+    assert _straddled_lanes(view, rows) == len(fits)
+    _aliases_hold(layout)
+    # the last sample's offsets have bit 30 set: cleared, reduced mod 2^30 and sign-extended they are other rows
+    last = set(F.source_offset_aliases(view, B - 1)) - {view.addr(B - 1)}
+    assert view.addr(B - 1) - (1 << 30) * lane in last
+    assert (view.base - (lanes + 2) * lane in last)                                  # off - 2^31: just in front of the base
+    if view.clip_low:
+        assert view.base == 0 and all(a >= 0 for r in rows for a in F.aliases(view, r))
+    else:
+        assert all(a in F.aliases(view, B - 1) for a in last)
+
+
+@pytest.mark.parametrize("case", F.ROW_CACHE_CASES)
+def test_row_cache_home_planes_share_the_arena(case):
+    home, state, slots = F.row_cache_views(case)
+    shared = [v for v in (home, state, slots) if v is not None]
+    layout, rows = F.pick_shared(shared, seed=171)
+    _aliases_hold(layout)
+    assert len(layout.touched) == len(rows) * len(shared) and len(rows) <= 64          # (they fit one set's ways)
+    for v in shared:
+        assert _straddled(v, rows) == len(F.thresholds(v))
+        assert any(F.aliases(v, r) for r in rows)
+    if case == "wide":
+        assert home.row_bytes == 128 and max(rows) * home.row_bytes >= (1 << 34) and state is None
+    else:
+        assert home.row_bytes == state.row_bytes == slots.row_bytes == 4 and home.rows > INT32
+        assert INT32 in rows and INT32 - 1 in rows and max(rows) * 4 >= (1 << 33)
+
+
+def _straddled_lanes(view, rows):
+    unit = {"elements": view.width, "bytes": view.row_bytes, "rows": 1, "lanes": view.row_bytes // view.lane_bytes}
+    count = 0
+    for what, t, lo, hi in F.thresholds(view):
+        assert lo * unit[what] < t <= hi * unit[what] and hi == lo + 1 and lo in rows and hi in rows
+        count += 1
+    return count
+
+
 def test_bags_cover_the_rows_and_remap():
     rows = [0, 1, 7, (1 << 31) - 1, 1 << 31, (1 << 32) + 3]
     ids = F.fixed_bags(rows, 5, 4, seed=3)

@@ -14,8 +14,16 @@ own index kernels.
 Data: arbitrary bits, except where the summation order is not fixed -- the split forward and the default backward
 (float atomics) get small integers, on which every order is exact.
 
+The kernel families that form row addresses of their own have a test each: the mixed-width group forward (three tables
+of different widths), the mixed-width group backward (grad_y up to the 31-bit limit of its packed source offset), the
+grouped optimizer step on separate table tensors (narrowing before and after the subtraction of row_base) and the row
+cache's move (home planes in the arena).
+
 Not here: far OUTPUT rows of the forward (test_gpu_large_inputs.py), the exchange kernels (ids are values there), more
-than INT_MAX lookups.  Adam's two per-element moments stop past 2^31 elements: two 16 GiB tensors do not fit the arena.
+than INT_MAX lookups.  Adam's two per-element moments stop past 2^31 elements, in a group too: two 16 GiB tensors do not
+fit the arena (a group's Adam moments pass 2^31 elements, not 2^32).  The mixed-width mean scale runs over far rows at
+4-byte lanes only: at 8- and 16-byte lanes it is not covered.  The grouped step with global ids past 2^31 runs with
+SGD and row-wise Adagrad only; the states of the other rules do not fit next to 2^31 rows.
 """
 import ctypes
 
@@ -794,3 +802,376 @@ def test_row_load_decision_sees_the_high_word(ce):
     assert int(ce.decide_row_loads(ids, 2 << 30)[0]) == 1
     assert int(ce.decide_row_loads(ids & 0xFFFFFFFF, 2 << 30)[0]) == 0
     assert int(ce.decide_row_loads(ids >> 32, 2 << 30)[0]) == 1
+
+
+# ---- mixed-width group forward: three tables of different widths, far apart ------------------------------------------------
+@pytest.mark.parametrize("kind,widths,lane", F.MIXED_TABLES, ids=[c[0] for c in F.MIXED_TABLES])
+def test_mixed_group_forward_reads_far_rows(ce, oracle, arena, kind, widths, lane):
+    """embedding_forward_mixed_group on three arena views of different widths (far_rows.mixed_views): the per-table base
+    pointer from the device array, the width from the descriptor, the second pass of the column loop (fp32: 512 lanes
+    on 256 threads) and the int64 ids handed between lanes (CSR, lanes that divide a wavefront).  Want: torch.cat of
+    embedding_forward on the compact copies -- at the launch's lane width -- bit for bit, those being the oracle's."""
+    dtype, size = TORCH[kind], F.ELEM_SIZE[kind]
+    views = F.mixed_views(size, widths)
+    tables = [tensor_of(arena, v, dtype) for v in views]
+    group = ce.MixedTableGroup(tables)
+    assert group.lane_bytes() == lane
+    B, T = 5, 3
+    shift = 0 if lane == 16 else lane                                 # (the twins take the launch's lane width)
+    shuffled = two_pass = False
+    for idt, it in ((np.int64, torch.int64), (np.int32, torch.int32)):
+        layout, rows = F.pick(views, seed=141 + widths[0], below=INT32 if idt == np.int32 else None)
+        assert all(max(r) * v.row_bytes >= (1 << 32) for r, v in zip(rows, views))
+        assert sum(max(r) * v.width >= INT32 for r, v in zip(rows, views)) >= 2
+        rng = np.random.default_rng(widths[0])
+        made = [make(oracle, kind, rng.uniform(-1, 1, (len(r), w))) for r, w in zip(rows, widths)]
+        twins = [at_residue(m[1], shift) for m in made]
+        poison(arena, layout, *[m[1] for m in made])
+        for t in range(T):
+            put_rows(tables[t], rows[t], made[t][1])
+        fixed, ids, off = _grouped_batch(rows, idt, seed=widths[0])
+        w_fixed_o, w_fixed = make(oracle, kind, rng.uniform(-1, 1, fixed.size))
+        w_csr_o, w_csr = make(oracle, kind, rng.uniform(0.25, 1.25, ids.size))
+        for mode in ("sum", "mean"):
+            for weighted in (False, True):
+                s = ce.mixed_group_launch_shape(dtype, it, widths, B, num_hots=3, is_weighted=weighted)
+                assert s["elems_per_lane"] * size == lane
+                two_pass |= max(widths) // s["elems_per_lane"] > s["block_threads"]
+                per = []
+                for t in range(T):
+                    pos = F.compact(fixed[t].reshape(-1), rows[t])
+                    w_o = w_fixed_o.reshape(T, -1)[t] if weighted else None
+                    per.append(ce.embedding_forward(twins[t], dev(pos), num_hots=3, mode=mode,
+                                                    weights=w_fixed.view(T, -1)[t].contiguous() if weighted else None))
+                    want = oracle.embedding_forward(made[t][0], pos, None, w_o, batch_size=B, num_hots=3, mode=mode, fp16_math=False)
+                    assert torch.equal(ibits(per[t]).view(-1), dev_bits(want).view(-1)), (idt.__name__, "fixed", mode, weighted, t)
+                for extra in (dict(), dict(row_loads="streaming")):
+                    got = ce.embedding_forward_mixed_group(group, dev(fixed), num_hots=3, mode=mode,
+                                                           weights=w_fixed if weighted else None, **extra)
+                    same_bits(got, torch.cat(per, dim=1), (idt.__name__, "fixed", mode, weighted, sorted(extra)))
+                s = ce.mixed_group_launch_shape(dtype, it, widths, B, num_hots=0, is_weighted=weighted)
+                assert not s["staged"]                                 # (CSR: the ids come by cross-lane reads or loads)
+                shuffled |= any(64 % min(w // s["elems_per_lane"], s["block_threads"]) == 0 for w in widths)
+                for odt in (np.int64, np.int32):
+                    per = []
+                    for t in range(T):
+                        lo, hi = int(off[t * B]), int(off[(t + 1) * B])
+                        pos, o = F.compact(ids[lo:hi], rows[t]), (off[t * B:(t + 1) * B + 1] - lo).astype(odt)
+                        per.append(ce.embedding_forward(twins[t], dev(pos), dev(o), mode=mode,
+                                                        weights=w_csr[lo:hi].contiguous() if weighted else None))
+                        want = oracle.embedding_forward(made[t][0], pos, o, w_csr_o[lo:hi] if weighted else None, batch_size=B,
+                                                        num_hots=0, mode=mode, fp16_math=False)
+                        assert torch.equal(ibits(per[t]).view(-1), dev_bits(want).view(-1)), (idt.__name__, "csr", mode, weighted, t)
+                    for extra in (dict(), dict(row_loads="streaming")):
+                        got = ce.embedding_forward_mixed_group(group, dev(ids), dev(off.astype(odt)), mode=mode,
+                                                               weights=w_csr if weighted else None, **extra)
+                        same_bits(got, torch.cat(per, dim=1), (idt.__name__, "csr", odt.__name__, mode, weighted, sorted(extra)))
+    assert shuffled, "no CSR case handed its ids between lanes"
+    assert two_pass == (kind == "f32")
+
+
+# ---- mixed-width group backward: grad_y up to the limit of the packed source offset ----------------------------------------
+MIXED_GRAD_Y = F.mixed_grad_y_views()
+TABLE_ROWS = 50                                                       # rows of every (tiny) table of the backward's group
+
+
+def _mixed_backward_problem(oracle, kind, widths, samples, B, seed):
+    """About 700 lookups (table, sample, row) over the touched samples, CSR order; row 7 of table 0 is hot (HOT_RUN
+    lookups: its run chains across segments) and the last lookup in sorted order -- the last row of the last table,
+    looked up once, by the last sample -- is a run of one whose source offset is the largest there is."""
+    rng = np.random.default_rng(seed)
+    T, n = len(widths), len(samples)
+    nnz = 700
+    t = rng.integers(0, T, nnz)
+    s = rng.integers(0, n, nnz)
+    r = rng.integers(0, TABLE_ROWS - 1, nnz)
+    r[(t == 0) & (r == 7)] = 8
+    hot = rng.choice(nnz, HOT_RUN[kind], replace=False)
+    t[hot], r[hot] = 0, 7
+    assert T * n < nnz - HOT_RUN[kind]
+    keep = np.setdiff1d(np.arange(nnz), hot)[:T * n]                  # every (table, touched sample) at least once
+    t[keep], s[keep] = (np.arange(keep.size) % T), (np.arange(keep.size) // T) % n
+    r[keep] = np.where((t[keep] == 0) & (r[keep] == 7), 8, r[keep])
+    last = np.setdiff1d(np.arange(nnz), np.concatenate([hot, keep]))[0]
+    t[last], s[last], r[last] = T - 1, n - 1, TABLE_ROWS - 1
+    order = np.lexsort((np.arange(nnz), s, t))                        # bag g = t * B + sample: ascending
+    t, s, r = t[order], s[order], r[order]
+    top = GRAD_TOP[kind]
+    counts = np.bincount(t * TABLE_ROWS + r)
+    assert counts.max() >= HOT_RUN[kind] and 2 * top * counts.max() <= EXACT_INTEGERS[kind] and counts[-1] == 1
+    w_o, w_d = make(oracle, kind, rng.integers(1, 3, nnz))
+    gy = rng.integers(-top, top + 1, (n, sum(widths)))
+    return dict(t=t, s=s, r=r, w_d=w_d, gy=gy, nnz=nnz)
+
+
+def _bag_offsets(bags, lengths, count):
+    """CSR offsets over `count` bags, all empty but `bags` (ascending, distinct) of `lengths`: built on the device."""
+    lens = torch.zeros((count,), dtype=torch.int64, device="cuda")
+    lens[dev(np.asarray(bags, dtype=np.int64))] = dev(np.asarray(lengths, dtype=np.int64))
+    return torch.cat([torch.zeros((1,), dtype=torch.int64, device="cuda"), torch.cumsum(lens, 0)])
+
+
+@pytest.mark.parametrize("kind,widths,lane,view", MIXED_GRAD_Y, ids=["lane%d" % c[2] for c in MIXED_GRAD_Y])
+def test_mixed_group_backward_gathers_far_grad_y(ce, oracle, arena, kind, widths, lane, view):
+    """grad_y [B, D] is the arena view whose last sample's source offsets end at 2^31 - 3 lane units: bit 30 of the
+    packed word set under the run-end bit.  The touched samples lie on either side of the 2^30-lane and the byte
+    thresholds.  Integer data: the compact twin's bits and the fp64 sums, exactly; the poison stays.  One sample more is
+    refused before any launch.  4-byte lanes: the in-place mean scale over the whole view, power-of-two factors."""
+    dtype, size = TORCH[kind], F.ELEM_SIZE[kind]
+    B, D, T = view.rows, view.width, len(widths)
+    grad_y = tensor_of(arena, view, dtype)
+    group = ce.MixedTableGroup([torch.zeros((TABLE_ROWS, w), dtype=dtype, device="cuda") for w in widths])
+    layout, (samples,) = F.pick([view], seed=161)
+    n = len(samples)
+    assert samples[-1] == B - 1 and (B - 1) * (view.row_bytes // lane) >= (1 << 30) and B * (view.row_bytes // lane) == INT32 - 2
+    p = _mixed_backward_problem(oracle, kind, widths, samples, B, seed=lane)
+    gy_o, gy_d = make(oracle, kind, p["gy"])
+    poison(arena, layout)
+    put_rows(grad_y, samples, gy_d)
+    twin_y = at_residue(gy_d, view.base)
+    far_bags, lens = np.unique(p["t"] * B + np.asarray(samples)[p["s"]], return_counts=True)
+    cmp_bags, cmp_lens = np.unique(p["t"] * n + p["s"], return_counts=True)
+    assert np.array_equal(lens, cmp_lens)
+    off, cmp_off = _bag_offsets(far_bags, lens, T * B), _bag_offsets(cmp_bags, cmp_lens, T * n)
+    assert int(off[-1]) == p["nnz"] == int(cmp_off[-1])
+    ids = dev(p["r"].astype(np.int64))
+    # the fp64 sums per (table, row), ascending global id
+    base = np.arange(T) * TABLE_ROWS
+    column = np.concatenate([[0], np.cumsum(widths)])
+    keys = base[p["t"]] + p["r"]
+    uniq = np.unique(keys)
+    weights = np.asarray(p["w_d"].float().cpu().numpy(), dtype=np.float64)
+    assert ce.get_backward_tuning() == dict(segment_len=0, column_slices=0)
+    try:
+        for segment_len, slices in ((0, 0), (8, 1), (8, 4)):
+            ce.set_backward_tuning(segment_len, slices)
+            for weighted in (False, True):
+                label = (segment_len, slices, weighted)
+                kw = dict(weights=p["w_d"] if weighted else None)
+                got = ce.embedding_backward_mixed_group(group, grad_y, ids, off, **kw)
+                ref = ce.embedding_backward_mixed_group(group, twin_y, ids, cmp_off, **kw)
+                count = int(got.last_id.item()) + 1
+                assert count == uniq.size == int(ref.last_id.item()) + 1, label
+                assert np.array_equal(got.ids[:count].cpu().numpy(), uniq) and torch.equal(ref.ids[:count], got.ids[:count])
+                assert torch.equal(got.table_cuts(), ref.table_cuts()), label
+                assert np.array_equal(got.table_cuts().cpu().numpy(), np.searchsorted(uniq, np.arange(T + 1) * TABLE_ROWS))
+                for t, ((g_ids, g_rows), (r_ids, r_rows)) in enumerate(zip(got.per_table(), ref.per_table())):
+                    assert torch.equal(g_ids, r_ids), label
+                    same_bits(g_rows, r_rows, label + (t,))
+                    sums = np.zeros((TABLE_ROWS, widths[t]))
+                    mine = p["t"] == t
+                    terms = p["gy"][p["s"][mine], column[t]:column[t + 1]].astype(np.float64)
+                    if weighted:
+                        terms = terms * weights[mine, None]
+                    np.add.at(sums, p["r"][mine], terms)
+                    assert np.array_equal(g_rows.float().cpu().numpy().astype(np.float64), sums[g_ids.cpu().numpy()]), label + (t,)
+                poison_intact(arena, layout)
+    finally:
+        ce.set_backward_tuning(0, 0)
+    # one sample more: B * D / N reaches 2^31 -- refused from Python, nothing launched
+    if view.end + view.row_bytes <= F.ARENA_BYTES:
+        longer = arena[view.base:view.end + view.row_bytes].view(dtype).view(B + 1, D)
+        nothing = torch.zeros((T * (B + 1) + 1,), dtype=torch.int64, device="cuda")
+        with pytest.raises(ValueError, match="31 bits"):
+            ce.embedding_backward_mixed_group(group, longer, ids[:0], nothing)
+    if lane != 4:
+        return
+    # the mean scale, in place over the whole view: bags of 1 or 8 lookups with weights of 0.5 -- factors 2 and 1 / 4
+    # (1 and 1 / 8 without weights); every other bag is empty (factor 0).  This rewrites the poison too: the last check.
+    rng = np.random.default_rng(5)
+    bag_t, bag_s = np.repeat(np.arange(T), n), np.tile(np.arange(n), T)
+    lens = rng.choice([1, 8], T * n)
+    half = make(oracle, kind, np.full(int(lens.sum()), 0.5))[1]
+    for weighted in (False, True):
+        put_rows(grad_y, samples, gy_d)
+        twin = at_residue(gy_d, view.base)
+        off = _bag_offsets(bag_t * B + np.asarray(samples)[bag_s], lens, T * B)
+        cmp_off = _bag_offsets(bag_t * n + bag_s, lens, T * n)
+        w = half if weighted else None
+        assert ce.mixed_group_mean_scale(group, grad_y, off, weights=w, out=grad_y) is grad_y
+        ce.mixed_group_mean_scale(group, twin, cmp_off, weights=w, out=twin)
+        same_bits(get_rows(grad_y, samples), twin, ("mean scale", weighted))
+        factor = np.where(lens == 1, 2.0, 0.25) if weighted else 1.0 / lens
+        want = p["gy"].astype(np.float64) * np.repeat(factor.reshape(T, n).T, widths, axis=1)
+        assert np.array_equal(twin.float().cpu().numpy().astype(np.float64), want), ("mean scale", weighted)
+
+
+# ---- grouped optimizer step: three separate tables and their states ------------------------------------------------------
+GROUPED_STEP_CASES = F.grouped_step_cases()
+SEEDS = (0x1234ABCD5678, 0xFEDCBA9876543210, 77)
+
+
+@pytest.mark.parametrize("layout_name,kind,width,rule", GROUPED_STEP_CASES, ids=["%s-%s-W%d-%s" % c for c in GROUPED_STEP_CASES])
+def test_grouped_optimizer_step_updates_far_rows(ce, oracle, arena, layout_name, kind, width, rule):
+    """sparse_row_update_grouped / sparse_row_adam_grouped on three SEPARATE arena tables and their states
+    (far_rows.grouped_step_views).  "local": row_base[1] = 17 is subtracted from ids whose local row passes 2^32 elements
+    (2^31 rows of 4 bytes; Adam: 2^31 elements); "global": the ids of the two small tables pass 2^31, their local rows
+    are tiny.  The bits are the fp32 model's per table -- with stochastic rounding it rounds with the LOCAL row and
+    seeds[t] -- and, rounding to nearest, those of three single-table steps on the compact copies (a stochastic
+    single-table step would name its bits by the compact ids).  Unnamed rows keep their bits; the poison stays."""
+    dtype, bits = TORCH[kind], M.BITS[kind]
+    views = F.grouped_step_views(kind, width, rule, layout_name)
+    tables = [tensor_of(arena, per[0], dtype) for per in views]
+    states = [[tensor_of(arena, v, torch.float32) if what == "e" else tensor_of(arena, v, torch.float32).view(-1)
+               for v, what in zip(per[1:], F.STATE[rule])] for per in views]
+    group = ce.TableGroup(tables)
+    base, T = group.row_base, len(views)
+    assert base == (0, views[1][0].row_base, views[2][0].row_base, base[-1])
+    adam = rule in ("adam", "rowwise_adam")
+    rng = np.random.default_rng(width + len(rule))
+    for idt in (np.int64, np.int32):
+        layout, rows = F.pick_grouped(views, seed=151 + width, below=INT32 if idt == np.int32 else None)
+        if idt == np.int32 and not (all(rows) and max(rows[1]) * width >= INT32):
+            continue                                                   # (int32 ids that reach no far element)
+        if layout_name == "local":
+            assert max(rows[1]) * width >= (INT32 if rule == "adam" else (1 << 32)) or idt == np.int32
+        else:
+            assert min(rows[1]) + base[1] > INT32 and max(rows[2]) < 42
+        named = [np.asarray([k for k in range(len(r)) if not (t < 2 and k == 2)]) for t, r in enumerate(rows)]
+        entry_table = np.concatenate([np.full(len(k), t) for t, k in enumerate(named)])
+        entry_pos = np.concatenate(named)
+        order = rng.permutation(entry_table.size)
+        entry_table, entry_pos = entry_table[order], entry_pos[order]
+        local = np.asarray([rows[t][k] for t, k in zip(entry_table, entry_pos)], dtype=np.int64)
+        ids = local + np.asarray(base)[entry_table]
+        assert ids.max() >= INT32 or width != 2 or idt == np.int32
+        for stochastic in ((False, True) if kind != "f32" else (False,)):
+            label = (idt.__name__, stochastic)
+            grads_o, grads_d = make(oracle, kind, rng.uniform(-0.5, 0.5, (ids.size, width)))
+            data = []
+            poison(arena, layout)
+            for t in range(T):
+                table_o, table_d = make(oracle, kind, rng.uniform(-1, 1, (len(rows[t]), width)))
+                state_np = _state_data(rule, len(rows[t]), width, rng)
+                put_rows(tables[t], rows[t], table_d)
+                for s, d in zip(states[t], state_np):
+                    put_rows(s, rows[t], dev(d))
+                data.append((table_o, table_d, state_np))
+            rounding = dict(stochastic_rounding=True, seeds=list(SEEDS), step=(1 << 33) + 7) if stochastic else {}
+            if adam:
+                ce.sparse_row_adam_grouped(group, dev(ids.astype(idt)), grads_d, exp_avg=[s[0] for s in states],
+                                           exp_avg_sq=[s[1] for s in states], rowwise=rule == "rowwise_adam", **HYPER, **rounding)
+                hyper = HYPER
+            else:
+                ce.sparse_row_update_grouped(group, dev(ids.astype(idt)), grads_d, rule=rule, lr=HYPER["lr"], eps=HYPER["eps"],
+                                             states=[s[0] for s in states] if F.STATE[rule] else None, **rounding)
+                hyper = dict(lr=HYPER["lr"], eps=HYPER["eps"])
+            for t in range(T):
+                table_o, table_d, state_np = data[t]
+                mine = np.flatnonzero(entry_table == t)
+                pos = entry_pos[mine]
+                g_bits = np.ascontiguousarray(np.ascontiguousarray(grads_o).view(bits)[mine])
+                before = np.ascontiguousarray(table_o).view(bits)
+                want_t, want_s, trace = M.step(rule, kind, before, [s.view(np.uint32) for s in state_np], pos, g_bits,
+                                               np.arange(pos.size), **hyper)
+                if stochastic:
+                    want_t[pos] = M.store(trace["x"], kind, "stochastic", SEEDS[t], rounding["step"], local[mine])
+                got_t = ibits(get_rows(tables[t], rows[t])).cpu().numpy().view(bits)
+                assert np.array_equal(got_t, want_t), label + (t,)
+                assert not np.array_equal(got_t[pos], before[pos])
+                for s, want in zip(states[t], want_s):
+                    assert np.array_equal(ibits(get_rows(s, rows[t])).cpu().numpy().view(np.uint32), want), label + (t,)
+                if not stochastic:                                     # one single-table step on the compact copy
+                    twin = table_d.clone()
+                    twin_s = [dev(s) for s in state_np]
+                    g = grads_d[dev(mine)]
+                    if adam:
+                        ce.sparse_row_adam(twin, dev(pos.astype(idt)), g, exp_avg=twin_s[0], exp_avg_sq=twin_s[1],
+                                           rowwise=rule == "rowwise_adam", **HYPER)
+                    else:
+                        ce.sparse_row_update(twin, dev(pos.astype(idt)), g, rule=rule, lr=HYPER["lr"], eps=HYPER["eps"],
+                                             state=twin_s[0] if twin_s else None)
+                    assert np.array_equal(ibits(twin).cpu().numpy().view(bits), got_t), label + (t, "single-table step")
+                    for s, single in zip(states[t], twin_s):
+                        same_bits(get_rows(s, rows[t]), single, label + (t, "single-table state"))
+            poison_intact(arena, layout)
+
+
+# ---- the row cache's move: home planes in the arena ------------------------------------------------------------------------
+def _arena_cache(table, state, slot_of_row, num_sets, rule):
+    """A DynamicRowCache whose home planes are DEVICE tensors (arena views): built field by field -- the constructor asks
+    for pinned host memory, the entry points behind prefetch / apply_update / flush only dereference the addresses."""
+    from cuembed_amd import row_cache as RC
+    c = object.__new__(RC.DynamicRowCache)
+    c.table, c.device = table, table.device
+    c.rows, c.width = table.shape
+    c.capacity = c.capacity_rows = RC.WAYS * num_sets
+    c._raw, c.cache, c.cache_row_offset = RC._plane_behind(table, c.capacity, c.device)
+    c.slot_of_row = slot_of_row
+    c.rule, c.eps = rule, HYPER["eps"]
+    c._state_planes, c.state, c.state_cache, c.state_row_bytes, c.state_row_offset = [], None, None, 0, 0
+    if state is not None:
+        c.state, c.state_row_bytes = state, 4
+        c._raw_state, c.state_cache, c.state_row_offset = c._add_state_plane(state, 4)
+    c._aligned_state = ()
+    c.num_sets, c.row_bytes = num_sets, c.width * table.element_size()
+    c.tags = torch.full((num_sets, RC.WAYS), -1, dtype=torch.int64, device=c.device)
+    c.stamps = torch.zeros((num_sets, RC.WAYS), dtype=torch.int32, device=c.device).view(torch.uint32)
+    c.dirty = torch.zeros((num_sets, RC.WAYS), dtype=torch.uint8, device=c.device)
+    c.words = torch.tensor([1] + [0] * 15, dtype=torch.int64).to(c.device)
+    c._work, c.stochastic_rounding, c.seed, c.rounding_step = None, False, 0, None
+    return c
+
+
+@pytest.mark.parametrize("case", F.ROW_CACHE_CASES)
+def test_row_cache_move_reaches_far_home_rows(ce, oracle, arena, case):
+    """CacheMoveKernel's table + row * row_bytes and cache + slot * row_bytes, per plane, through the entry points that
+    DynamicRowCache calls (no entry point looks at where a pointer lives): the HOME planes are arena views -- fp16
+    W = 64 to 16 GiB, or a 4-byte table row and a 4-byte state row with ids past 2^31 --, the cache planes small device
+    tensors.  Prefetch the boundary rows: the slots hold the home rows.  One step through the cache (SGD, row-wise
+    Adagrad with the state plane) dirties them; the home rows keep their bits until the flush and are the fp32 model's
+    after it; rows no id named keep theirs, the poison stays."""
+    kind = "f16"
+    dtype, bits = TORCH[kind], M.BITS[kind]
+    home_v, state_v, slots_v = F.row_cache_views(case)
+    home = tensor_of(arena, home_v, dtype)
+    state = None if state_v is None else tensor_of(arena, state_v, torch.float32).view(-1)
+    rule = "sgd" if state is None else "rowwise_adagrad"
+    shared = [v for v in (home_v, state_v, slots_v) if v is not None]
+    layout, rows = F.pick_shared(shared, seed=171)
+    n, width = len(rows), home_v.width
+    assert max(rows) * home_v.row_bytes >= ((1 << 34) if case == "wide" else (1 << 33)) and (case == "wide" or max(rows) > INT32)
+    if slots_v is None:
+        slot_of_row = torch.full((home_v.rows,), -1, dtype=torch.int32, device="cuda")
+    else:
+        slot_of_row = tensor_of(arena, slots_v, torch.int32).view(-1)
+    rng = np.random.default_rng(n)
+    table_o, table_d = make(oracle, kind, rng.uniform(-1, 1, (n, width)))
+    state_np = _state_data(rule, n, width, rng)
+    poison(arena, layout, table_d)
+    put_rows(home, rows, table_d)
+    if state is not None:
+        put_rows(state, rows, dev(state_np[0]))
+    if slots_v is not None:
+        for r in rows:
+            slot_of_row[r].fill_(-1)
+    cache = _arena_cache(home, state, slot_of_row, num_sets=4, rule=rule)
+    every = dev(np.asarray(rows, dtype=np.int64))
+    cache.prefetch(every)
+    slots = [int(slot_of_row[r]) for r in rows]
+    assert min(slots) >= 0 and len(set(slots)) == n
+    stats = cache.stats()
+    assert stats["misses"] == n == stats["moves"] and stats["hits"] == 0
+    assert stats["unplaced"] == 0 and stats["overflow"] == 0 and stats["write_backs"] == 0
+    same_bits(torch.stack([cache.cache[s] for s in slots]), table_d, "cached rows")
+    if state is not None:
+        same_bits(torch.stack([cache.state_cache[s] for s in slots]), dev(state_np[0]), "cached state")
+    # one step through the cache on all rows but two, int32 ids where they fit
+    named = np.asarray([k for k in range(n) if k not in (2, n - 3)])
+    named = named[rng.permutation(named.size)]
+    grads_o, grads_d = make(oracle, kind, rng.uniform(-0.5, 0.5, (named.size, width)))
+    ids = np.asarray(rows, dtype=np.int64)[named]
+    cache.apply_update(dev(ids if ids.max() >= INT32 else ids.astype(np.int32)), grads_d, lr=HYPER["lr"])
+    assert cache.stats()["hits"] == named.size
+    same_bits(get_rows(home, rows), table_d, "write-back: the home rows wait for the flush")
+    before = np.ascontiguousarray(table_o).view(bits)
+    want_t, want_s, _ = M.step(rule, kind, before, [s.view(np.uint32) for s in state_np], named,
+                               np.ascontiguousarray(grads_o).view(bits), np.arange(named.size), lr=HYPER["lr"], eps=HYPER["eps"])
+    cache.flush()
+    torch.cuda.synchronize()
+    got = ibits(get_rows(home, rows)).cpu().numpy().view(bits)
+    assert np.array_equal(got, want_t) and not np.array_equal(got[named], before[named])
+    if state is not None:
+        assert np.array_equal(ibits(get_rows(state, rows)).cpu().numpy().view(np.uint32), want_s[0])
+    assert cache.stats()["write_backs"] == named.size and not bool(cache.dirty.any())
+    poison_intact(arena, layout)
