@@ -34,6 +34,8 @@ from .grouped_backward import (GroupedGrad, embedding_backward_grouped, embeddin
                                sparse_row_adam_grouped, sparse_row_update_grouped)
 from .mixed_group_backward import (MixedGroupedGrad, embedding_backward_mixed_group,  # noqa: F401
                                    mixed_group_backward_launch_shape, mixed_group_mean_scale)
+from .mixed_group_sparse_update import (mixed_group_update_launch_shape, sparse_row_adam_mixed_group,  # noqa: F401
+                                        sparse_row_update_mixed_group)
 from .index_check import (IndexCheck, check_indices, check_indices_workspace_bytes,  # noqa: F401
                           new_index_report)
 

@@ -229,6 +229,17 @@ def _declare(L):
     L.cuembed_sparse_row_adam_grouped_stochastic.restype = None
     L.cuembed_sparse_row_adam_grouped_stochastic.argtypes = (
         list(L.cuembed_sparse_row_adam_grouped.argtypes[:-1]) + [_VP, _U, _VP, _VP])
+    # the steps on a mixed-width group: ... the pointer arrays, then widths_host, widths_device, num_tables, elem, W_max
+    L.cuembed_sparse_row_update_mixed_group.restype = None
+    L.cuembed_sparse_row_update_mixed_group.argtypes = [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _I, _VP, _L,
+                                                        _L, _VP, _I, _VP, _F, _VP, _F, _VP]
+    L.cuembed_sparse_row_adam_mixed_group.restype = None
+    L.cuembed_sparse_row_adam_mixed_group.argtypes = [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _I,
+                                                      _VP, _L, _L, _VP, _I, _VP, _F, _VP, _F, _VP, _F, _F, _F, _F, _F, _F,
+                                                      _VP]
+    L.cuembed_mixed_group_update_launch_shape.restype = None
+    L.cuembed_mixed_group_update_launch_shape.argtypes = [_VP, _I, _I, _L, _I, ctypes.c_size_t, ctypes.c_size_t, _I,
+                                                          ctypes.POINTER(_I), ctypes.POINTER(_I)]
     L.cuembed_check_indices.restype = None
     L.cuembed_check_indices.argtypes = [_VP, _I, _VP, _I, _L, _VP, _L, _I, _I, _I, _VP, _VP, _VP, _VP,
                                         ctypes.POINTER(ctypes.c_size_t), _VP]

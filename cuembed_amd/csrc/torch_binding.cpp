@@ -919,6 +919,36 @@ std::vector<const void*> CheckGroupedStates(const at::TensorList tables, const a
   return host;
 }
 
+// The count source (count / count_word / last_id / none) and lr_device of a step on a group, into `c`.
+void ParseGroupedStepSources(GroupedStep& c, const at::Tensor& table0, const at::Tensor& ids,
+                             const c10::optional<at::Tensor>& lr_device, const int64_t count,
+                             const c10::optional<at::Tensor>& count_word, const c10::optional<at::Tensor>& last_id) {
+  const auto on_device = [&](const at::Tensor& t) { return t.is_cuda() && t.device() == table0.device(); };
+  const bool has_word = count_word.has_value() && count_word->defined();
+  const bool has_last = last_id.has_value() && last_id->defined();
+  TORCH_CHECK((count >= 0) + has_word + has_last <= 1, "cuembed_pyt: give at most one of count, count_word and last_id");
+  if (has_word) {
+    CheckGpu(*count_word, "count_word");
+    c.words64 = IndexCode(*count_word, "count_word") == CUEMBED_I64;
+    TORCH_CHECK(count_word->numel() == 1 && on_device(*count_word), "cuembed_pyt: count_word must be one word on the tables' device");
+    c.count_word = count_word->data_ptr();
+  } else if (has_last) {
+    CheckGpu(*last_id, "last_id");
+    TORCH_CHECK(last_id->scalar_type() == ids.scalar_type() && last_id->numel() == 1 && on_device(*last_id),
+                "cuembed_pyt: last_id must be one word of ids' dtype on the tables' device");
+    c.last_id = last_id->data_ptr();
+  } else {
+    c.num_rows = count >= 0 ? count : ids.numel();
+    TORCH_CHECK(c.num_rows <= ids.numel(), "cuembed_pyt: count exceeds the entries");
+  }
+  if (lr_device.has_value() && lr_device->defined()) {
+    CheckGpu(*lr_device, "lr_device");
+    TORCH_CHECK(lr_device->scalar_type() == at::kFloat && lr_device->numel() == 1 && on_device(*lr_device),
+                "cuembed_pyt: lr_device must be one float32 word on the tables' device");
+    c.lr_word = static_cast<const float*>(lr_device->data_ptr());
+  }
+}
+
 GroupedStep CheckGroupedStep(const at::TensorList tables, const at::Tensor& table_ptrs, const at::Tensor& row_base,
                              const at::Tensor& ids, const at::Tensor& rows, const c10::optional<at::Tensor>& lr_device,
                              const int64_t count, const c10::optional<at::Tensor>& count_word,
@@ -971,29 +1001,7 @@ GroupedStep CheckGroupedStep(const at::TensorList tables, const at::Tensor& tabl
                   rows.is_contiguous() && ids.is_contiguous() && on_device(ids) && on_device(rows),
               "cuembed_pyt: rows [entries, width] and ids [entries] must be contiguous, agree and be on the tables' device");
   TORCH_CHECK((rows.size(1) * rows.element_size()) % 4 == 0, "cuembed_pyt: the row size must be a multiple of 4 bytes");
-  const bool has_word = count_word.has_value() && count_word->defined();
-  const bool has_last = last_id.has_value() && last_id->defined();
-  TORCH_CHECK((count >= 0) + has_word + has_last <= 1, "cuembed_pyt: give at most one of count, count_word and last_id");
-  if (has_word) {
-    CheckGpu(*count_word, "count_word");
-    c.words64 = IndexCode(*count_word, "count_word") == CUEMBED_I64;
-    TORCH_CHECK(count_word->numel() == 1 && on_device(*count_word), "cuembed_pyt: count_word must be one word on the tables' device");
-    c.count_word = count_word->data_ptr();
-  } else if (has_last) {
-    CheckGpu(*last_id, "last_id");
-    TORCH_CHECK(last_id->scalar_type() == ids.scalar_type() && last_id->numel() == 1 && on_device(*last_id),
-                "cuembed_pyt: last_id must be one word of ids' dtype on the tables' device");
-    c.last_id = last_id->data_ptr();
-  } else {
-    c.num_rows = count >= 0 ? count : ids.numel();
-    TORCH_CHECK(c.num_rows <= ids.numel(), "cuembed_pyt: count exceeds the entries");
-  }
-  if (lr_device.has_value() && lr_device->defined()) {
-    CheckGpu(*lr_device, "lr_device");
-    TORCH_CHECK(lr_device->scalar_type() == at::kFloat && lr_device->numel() == 1 && on_device(*lr_device),
-                "cuembed_pyt: lr_device must be one float32 word on the tables' device");
-    c.lr_word = static_cast<const float*>(lr_device->data_ptr());
-  }
+  ParseGroupedStepSources(c, tables[0], ids, lr_device, count, count_word, last_id);
   return c;
 }
 
@@ -1113,6 +1121,134 @@ void cuembed_sparse_row_adam_grouped_op(const at::TensorList tables, const at::T
       c.words64, c.last_id, static_cast<float>(lr), c.lr_word, static_cast<float>(bias_factor), bias_word,
       static_cast<float>(beta1), static_cast<float>(1.0 - beta1), static_cast<float>(beta2),
       static_cast<float>(1.0 - beta2), static_cast<float>(eps), static_cast<float>(weight_decay), CurrentStream(rows));
+}
+
+// ---- the same steps on a group of tables of DIFFERENT widths (cuembed::SparseRowUpdateMixedGroup /
+// SparseRowAdamMixedGroup).  As the grouped ops above, except: the tables' widths may differ; `widths` is the int32
+// device tensor [num_tables] of them, built once by the caller (it MUST agree with the tables: the op reads the host
+// widths from the tables and never reads device memory); rows is [entries, W_max], padded to the widest table -- the
+// gradient of cuembed_embedding_backward_mixed_group; per-element state is [rows_t, W_t].  Round to nearest only.
+
+struct MixedGroupStep {
+  GroupedStep c;
+  std::vector<int> widths_host;
+  int max_width = 0;
+};
+
+MixedGroupStep CheckMixedGroupStep(const at::TensorList tables, const at::Tensor& table_ptrs, const at::Tensor& widths,
+                                   const at::Tensor& row_base, const at::Tensor& ids, const at::Tensor& rows,
+                                   const c10::optional<at::Tensor>& lr_device, const int64_t count,
+                                   const c10::optional<at::Tensor>& count_word,
+                                   const c10::optional<at::Tensor>& last_id) {
+  MixedGroupStep m;
+  const int64_t num_tables = static_cast<int64_t>(tables.size());
+  TORCH_CHECK(num_tables >= 1 && num_tables <= 1023, "cuembed_pyt: a grouped step takes 1 to 1023 tables");
+  m.c.elem = ElemCode(tables[0], "tables");
+  for (const at::Tensor& t : tables) {
+    CheckGpu(t, "tables");
+    TORCH_CHECK(t.dim() == 2 && t.is_contiguous() && t.scalar_type() == tables[0].scalar_type() &&
+                    t.device() == tables[0].device() && t.size(1) >= 1 && (t.size(1) * t.element_size()) % 4 == 0,
+                "cuembed_pyt: the tables of a mixed-width group must be contiguous [rows, width] of one dtype and device, "
+                "every row a multiple of 4 bytes");
+    m.c.table_host.push_back(t.data_ptr());
+    m.widths_host.push_back(static_cast<int>(t.size(1)));
+    m.max_width = std::max(m.max_width, m.widths_host.back());
+  }
+  const auto on_device = [&](const at::Tensor& t) { return t.is_cuda() && t.device() == tables[0].device(); };
+  TORCH_CHECK(on_device(table_ptrs) && table_ptrs.scalar_type() == at::kLong && table_ptrs.is_contiguous() &&
+                  table_ptrs.numel() == num_tables,
+              "cuembed_pyt: table_ptrs must be the contiguous int64 tensor of the tables' data pointers on their device");
+  TORCH_CHECK(on_device(widths) && widths.scalar_type() == at::kInt && widths.is_contiguous() && widths.numel() == num_tables,
+              "cuembed_pyt: widths must be the contiguous int32 tensor of the tables' widths on their device");
+  TORCH_CHECK(on_device(row_base) && row_base.scalar_type() == at::kLong && row_base.is_contiguous() &&
+                  row_base.numel() == num_tables + 1,
+              "cuembed_pyt: row_base must be the contiguous int64 tensor of num_tables + 1 prefix sums on the tables' device");
+  CheckGpu(ids, "ids");
+  CheckGpu(rows, "rows");
+  m.c.idx = IndexCode(ids, "ids");
+  TORCH_CHECK(rows.scalar_type() == tables[0].scalar_type(), "cuembed_pyt: rows must have the tables' dtype");
+  TORCH_CHECK(rows.dim() == 2 && rows.size(1) == m.max_width && ids.dim() == 1 && rows.size(0) == ids.numel() &&
+                  rows.is_contiguous() && ids.is_contiguous() && on_device(ids) && on_device(rows),
+              "cuembed_pyt: rows [entries, W_max] (padded to the widest table) and ids [entries] must be contiguous, agree "
+              "and be on the tables' device");
+  ParseGroupedStepSources(m.c, tables[0], ids, lr_device, count, count_word, last_id);
+  return m;
+}
+
+void cuembed_sparse_row_update_mixed_group_op(const at::TensorList tables, const at::Tensor& table_ptrs,
+                                              const at::TensorList states, const c10::optional<at::Tensor>& state_ptrs,
+                                              const at::Tensor& widths, const at::Tensor& row_base, const at::Tensor& ids,
+                                              const at::Tensor& rows, const std::string& rule, const double lr,
+                                              const double eps, const c10::optional<at::Tensor>& lr_device,
+                                              const int64_t count, const c10::optional<at::Tensor>& count_word,
+                                              const c10::optional<at::Tensor>& last_id) {
+  const int code = rule == "sgd" ? CUEMBED_UPDATE_SGD
+                   : rule == "adagrad" ? CUEMBED_UPDATE_ADAGRAD
+                   : rule == "rowwise_adagrad" ? CUEMBED_UPDATE_ROWWISE_ADAGRAD : -1;
+  TORCH_CHECK(code >= 0, "cuembed_pyt: rule must be 'sgd', 'adagrad' or 'rowwise_adagrad'");
+  TORCH_CHECK(!tables.empty(), "cuembed_pyt: a group needs at least one table");
+  const MixedGroupStep m = CheckMixedGroupStep(tables, table_ptrs, widths, row_base, ids, rows, lr_device, count, count_word, last_id);
+  const bool stateful = code != CUEMBED_UPDATE_SGD;
+  std::vector<const void*> state_host;
+  if (stateful) {
+    state_host = CheckGroupedStates(tables, states, state_ptrs, code == CUEMBED_UPDATE_ADAGRAD, "states");
+  } else {
+    TORCH_CHECK(states.empty(), "cuembed_pyt: rule 'sgd' takes no states");
+  }
+  std::vector<const std::vector<const void*>*> per_element;
+  if (code == CUEMBED_UPDATE_ADAGRAD) per_element.push_back(&state_host);
+  CheckGroupedAlignment(m.c, rows, tables[0].element_size(), per_element);
+  if (ids.numel() == 0) return;
+  const at::DeviceGuard guard(tables[0].device());
+  ::cuembed_sparse_row_update_mixed_group(
+      m.c.table_host.data(), static_cast<const void* const*>(table_ptrs.data_ptr()), stateful ? state_host.data() : nullptr,
+      stateful ? static_cast<const void* const*>(state_ptrs->data_ptr()) : nullptr, m.widths_host.data(),
+      static_cast<const int*>(widths.data_ptr()), static_cast<int>(tables.size()), m.c.elem, m.max_width,
+      static_cast<const int64_t*>(row_base.data_ptr()), code, Ptr(ids), m.c.idx, Ptr(rows), ids.numel(), m.c.num_rows,
+      m.c.count_word, m.c.words64, m.c.last_id, static_cast<float>(lr), m.c.lr_word, static_cast<float>(eps),
+      CurrentStream(rows));
+}
+
+void cuembed_sparse_row_adam_mixed_group_op(const at::TensorList tables, const at::Tensor& table_ptrs,
+                                            const at::TensorList exp_avg, const at::Tensor& exp_avg_ptrs,
+                                            const at::TensorList exp_avg_sq, const at::Tensor& exp_avg_sq_ptrs,
+                                            const at::Tensor& widths, const at::Tensor& row_base, const at::Tensor& ids,
+                                            const at::Tensor& rows, const bool rowwise, const double lr,
+                                            const double bias_factor, const double beta1, const double beta2,
+                                            const double eps, const double weight_decay,
+                                            const c10::optional<at::Tensor>& lr_device,
+                                            const c10::optional<at::Tensor>& bias_factor_device, const int64_t count,
+                                            const c10::optional<at::Tensor>& count_word,
+                                            const c10::optional<at::Tensor>& last_id) {
+  TORCH_CHECK(!tables.empty(), "cuembed_pyt: a group needs at least one table");
+  const MixedGroupStep m = CheckMixedGroupStep(tables, table_ptrs, widths, row_base, ids, rows, lr_device, count, count_word, last_id);
+  const std::vector<const void*> m_host = CheckGroupedStates(tables, exp_avg, exp_avg_ptrs, true, "exp_avg");
+  const std::vector<const void*> v_host = CheckGroupedStates(tables, exp_avg_sq, exp_avg_sq_ptrs, !rowwise, "exp_avg_sq");
+  std::vector<const std::vector<const void*>*> per_element = {&m_host};
+  if (!rowwise) per_element.push_back(&v_host);
+  CheckGroupedAlignment(m.c, rows, tables[0].element_size(), per_element);
+  TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "cuembed_pyt: betas must lie in [0, 1)");
+  TORCH_CHECK(eps >= 0.0 && weight_decay >= 0.0, "cuembed_pyt: eps and weight_decay must not be negative");
+  const float* bias_word = nullptr;
+  if (bias_factor_device.has_value() && bias_factor_device->defined()) {
+    CheckGpu(*bias_factor_device, "bias_factor_device");
+    TORCH_CHECK(bias_factor_device->scalar_type() == at::kFloat && bias_factor_device->numel() == 1 &&
+                    bias_factor_device->device() == tables[0].device(),
+                "cuembed_pyt: bias_factor_device must be one float32 word on the tables' device");
+    bias_word = static_cast<const float*>(bias_factor_device->data_ptr());
+  }
+  if (ids.numel() == 0) return;
+  const at::DeviceGuard guard(tables[0].device());
+  ::cuembed_sparse_row_adam_mixed_group(
+      m.c.table_host.data(), static_cast<const void* const*>(table_ptrs.data_ptr()), m_host.data(),
+      static_cast<const void* const*>(exp_avg_ptrs.data_ptr()), v_host.data(),
+      static_cast<const void* const*>(exp_avg_sq_ptrs.data_ptr()), m.widths_host.data(),
+      static_cast<const int*>(widths.data_ptr()), static_cast<int>(tables.size()), m.c.elem, m.max_width,
+      static_cast<const int64_t*>(row_base.data_ptr()), rowwise ? CUEMBED_ROWWISE_ADAM : CUEMBED_ADAM, Ptr(ids), m.c.idx,
+      Ptr(rows), ids.numel(), m.c.num_rows, m.c.count_word, m.c.words64, m.c.last_id, static_cast<float>(lr), m.c.lr_word,
+      static_cast<float>(bias_factor), bias_word, static_cast<float>(beta1), static_cast<float>(1.0 - beta1),
+      static_cast<float>(beta2), static_cast<float>(1.0 - beta2), static_cast<float>(eps),
+      static_cast<float>(weight_decay), CurrentStream(rows));
 }
 
 // Extension (cuembed::PackRowsByOwner): the rank's compressed gradient into the fixed slots of the all-to-all.
@@ -1938,6 +2074,16 @@ TORCH_LIBRARY(cuembed_pyt, m) {
       "float bias_factor, float beta1, float beta2, float eps, float weight_decay, Tensor? lr_device, Tensor? "
       "bias_factor_device, int count, Tensor? count_word, Tensor? last_id, bool stochastic_rounding=False, Tensor? "
       "seeds=None, int step=0, Tensor? step_device=None) -> ()");
+  // ... and on a group of tables of different widths (round to nearest only)
+  m.def(
+      "cuembed_sparse_row_update_mixed_group(Tensor(a!)[] tables, Tensor table_ptrs, Tensor(b!)[] states, Tensor? "
+      "state_ptrs, Tensor widths, Tensor row_base, Tensor ids, Tensor rows, str rule, float lr, float eps, Tensor? "
+      "lr_device, int count, Tensor? count_word, Tensor? last_id) -> ()");
+  m.def(
+      "cuembed_sparse_row_adam_mixed_group(Tensor(a!)[] tables, Tensor table_ptrs, Tensor(b!)[] exp_avg, Tensor "
+      "exp_avg_ptrs, Tensor(c!)[] exp_avg_sq, Tensor exp_avg_sq_ptrs, Tensor widths, Tensor row_base, Tensor ids, Tensor "
+      "rows, bool rowwise, float lr, float bias_factor, float beta1, float beta2, float eps, float weight_decay, Tensor? "
+      "lr_device, Tensor? bias_factor_device, int count, Tensor? count_word, Tensor? last_id) -> ()");
   // 8-bit row-wise quantized tables (torch's fused layout), inference only
   m.def("quantize_rows(Tensor table) -> Tensor");
   m.def("dequantize_rows(Tensor qtable, Tensor? ids, ScalarType dtype) -> Tensor");
@@ -2011,6 +2157,8 @@ TORCH_LIBRARY_IMPL(cuembed_pyt, CUDA, m) {  // HIP tensors use the CUDA dispatch
   m.impl("cuembed_sparse_row_adam_", cuembed_sparse_row_adam_op);
   m.impl("cuembed_sparse_row_update_grouped", cuembed_sparse_row_update_grouped_op);
   m.impl("cuembed_sparse_row_adam_grouped", cuembed_sparse_row_adam_grouped_op);
+  m.impl("cuembed_sparse_row_update_mixed_group", cuembed_sparse_row_update_mixed_group_op);
+  m.impl("cuembed_sparse_row_adam_mixed_group", cuembed_sparse_row_adam_mixed_group_op);
   m.impl("quantize_rows", quantize_rows_op);
   m.impl("dequantize_rows", dequantize_rows_op);
   m.impl("cuemb_embedding_quantized", cuemb_embedding_quantized_op);

@@ -87,6 +87,14 @@ def _define_python_ops():
                 " float weight_decay, Tensor? lr_device, Tensor? bias_factor_device, int count, Tensor? count_word,"
                 " Tensor? last_id, bool stochastic_rounding=False, Tensor? seeds=None, int step=0,"
                 " Tensor? step_device=None) -> ()")
+    _lib.define("cuembed_sparse_row_update_mixed_group(Tensor(a!)[] tables, Tensor table_ptrs, Tensor(b!)[] states,"
+                " Tensor? state_ptrs, Tensor widths, Tensor row_base, Tensor ids, Tensor rows, str rule, float lr, float eps,"
+                " Tensor? lr_device, int count, Tensor? count_word, Tensor? last_id) -> ()")
+    _lib.define("cuembed_sparse_row_adam_mixed_group(Tensor(a!)[] tables, Tensor table_ptrs, Tensor(b!)[] exp_avg,"
+                " Tensor exp_avg_ptrs, Tensor(c!)[] exp_avg_sq, Tensor exp_avg_sq_ptrs, Tensor widths, Tensor row_base,"
+                " Tensor ids, Tensor rows, bool rowwise, float lr, float bias_factor, float beta1, float beta2, float eps,"
+                " float weight_decay, Tensor? lr_device, Tensor? bias_factor_device, int count, Tensor? count_word,"
+                " Tensor? last_id) -> ()")
     _lib.define("quantize_rows(Tensor table) -> Tensor")
     _lib.define("dequantize_rows(Tensor qtable, Tensor? ids, ScalarType dtype) -> Tensor")
     _lib.define("cuemb_embedding_quantized(Tensor qtable, Tensor indices, Tensor? offsets, Tensor? weights, str mode,"
@@ -128,6 +136,8 @@ def _define_python_ops():
     _lib.impl("cuembed_sparse_row_adam_", _sparse_row_adam_impl, "CUDA")
     _lib.impl("cuembed_sparse_row_update_grouped", _sparse_row_update_grouped_impl, "CUDA")
     _lib.impl("cuembed_sparse_row_adam_grouped", _sparse_row_adam_grouped_impl, "CUDA")
+    _lib.impl("cuembed_sparse_row_update_mixed_group", _sparse_row_update_mixed_group_impl, "CUDA")
+    _lib.impl("cuembed_sparse_row_adam_mixed_group", _sparse_row_adam_mixed_group_impl, "CUDA")
     _lib.impl("cuembed_decide_row_loads", _decide_row_loads_impl, "CUDA")
     _lib.impl("cuembed_embedding_forward_hinted", _forward_hinted_impl, "CUDA")
     _lib.impl("cuembed_bag_order_by_length", _bag_order_impl, "CUDA")
@@ -166,6 +176,8 @@ def _define_python_ops():
 #                                             decay; the bias factor may stay on the device)
 #   cuembed_sparse_row_update_grouped,        both steps on a group of SEPARATE table tensors, in one launch each: the
 #   cuembed_sparse_row_adam_grouped           kernel finds every entry's table itself (global row ids, row_base)
+#   cuembed_sparse_row_update_mixed_group,    the same on a group of tables of DIFFERENT widths: rows padded to the widest
+#   cuembed_sparse_row_adam_mixed_group       table (the mixed backward's gradient), round to nearest only
 #   quantize_rows, dequantize_rows,           8-bit row-wise quantized tables in torch's own fused layout (inference
 #   cuemb_embedding_quantized                 only): the quantizer, its inverse, and the lookup on a fused table
 #   cuemb_embedding_grouped,                  a group of tables of one width and dtype pooled in ONE launch into
@@ -395,6 +407,25 @@ def _sparse_row_adam_grouped_impl(tables, table_ptrs, exp_avg, exp_avg_ptrs, exp
                                 stochastic_rounding=stochastic_rounding, seeds=seeds,
                                 step=_unsigned(step) if step_device is None else step_device,
                                 **_grouped_count(count, count_word, last_id))
+
+
+def _sparse_row_update_mixed_group_impl(tables, table_ptrs, states, state_ptrs, widths, row_base, ids, rows, rule, lr, eps,
+                                        lr_device, count, count_word, last_id):
+    from . import mixed_group as _mg, mixed_group_sparse_update as _mu
+    _mu.sparse_row_update_mixed_group(_mg.MixedTableGroup(tables, table_ptrs=table_ptrs), ids, rows, rule=rule,
+                                      lr=lr if lr_device is None else lr_device, states=list(states) or None, eps=eps,
+                                      **_grouped_count(count, count_word, last_id))
+
+
+def _sparse_row_adam_mixed_group_impl(tables, table_ptrs, exp_avg, exp_avg_ptrs, exp_avg_sq, exp_avg_sq_ptrs, widths,
+                                      row_base, ids, rows, rowwise, lr, bias_factor, beta1, beta2, eps, weight_decay,
+                                      lr_device, bias_factor_device, count, count_word, last_id):
+    from . import mixed_group as _mg, mixed_group_sparse_update as _mu
+    _mu.sparse_row_adam_mixed_group(_mg.MixedTableGroup(tables, table_ptrs=table_ptrs), ids, rows, exp_avg=list(exp_avg),
+                                    exp_avg_sq=list(exp_avg_sq), lr=lr if lr_device is None else lr_device,
+                                    bias_factor=bias_factor if bias_factor_device is None else bias_factor_device,
+                                    betas=(beta1, beta2), eps=eps, weight_decay=weight_decay, rowwise=rowwise,
+                                    **_grouped_count(count, count_word, last_id))
 
 
 def _quantize_rows_impl(table):
@@ -800,6 +831,44 @@ def cuembed_sparse_row_adam_grouped(group, ids, rows, *, exp_avg, exp_avg_sq, lr
         0.0 if lr_device is not None else float(lr), 1.0 if bias_device is not None else float(bias_factor), float(beta1),
         float(beta2), float(eps), float(weight_decay), lr_device, bias_device, host_count, word, last_id,
         bool(stochastic_rounding), seeds, step, step_device)
+
+
+def _mixed_step_args(group, count):
+    from . import mixed_group as _mg
+    if not isinstance(group, _mg.MixedTableGroup):
+        group = _mg.MixedTableGroup(group)
+    word = count if isinstance(count, torch.Tensor) else None
+    return group, -1 if (count is None or word is not None) else int(count), word
+
+
+def cuembed_sparse_row_update_mixed_group(group, ids, rows, *, rule, lr, states=None, eps=1e-8, count=None, last_id=None):
+    """cuembed_amd.sparse_row_update_mixed_group as the torch op cuembed_pyt::cuembed_sparse_row_update_mixed_group (in
+    place on the group's tables and on `states`; traces under torch.compile).  Same arguments; the device arrays of the
+    state pointers and of the widths are built once and kept on the group."""
+    from . import grouped_backward as _gb, mixed_group_sparse_update as _mu
+    group, host_count, word = _mixed_step_args(group, count)
+    lr_device = lr if isinstance(lr, torch.Tensor) else None
+    state_ptrs = None if not states else _gb._state_ptrs(group, states)[1]
+    torch.ops.cuembed_pyt.cuembed_sparse_row_update_mixed_group(
+        list(group.tables), group.table_ptrs, list(states or ()), state_ptrs, _mu._widths_device(group),
+        group.row_base_device, ids, rows, rule, 0.0 if lr_device is not None else float(lr), float(eps), lr_device,
+        host_count, word, last_id)
+
+
+def cuembed_sparse_row_adam_mixed_group(group, ids, rows, *, exp_avg, exp_avg_sq, lr, bias_factor=1.0, betas=(0.9, 0.999),
+                                        eps=1e-8, weight_decay=0.0, rowwise=False, count=None, last_id=None):
+    """cuembed_amd.sparse_row_adam_mixed_group as the torch op cuembed_pyt::cuembed_sparse_row_adam_mixed_group (in place
+    on the group's tables, `exp_avg` and `exp_avg_sq`; traces under torch.compile).  Same arguments."""
+    from . import grouped_backward as _gb, mixed_group_sparse_update as _mu
+    group, host_count, word = _mixed_step_args(group, count)
+    lr_device = lr if isinstance(lr, torch.Tensor) else None
+    bias_device = bias_factor if isinstance(bias_factor, torch.Tensor) else None
+    beta1, beta2 = betas
+    torch.ops.cuembed_pyt.cuembed_sparse_row_adam_mixed_group(
+        list(group.tables), group.table_ptrs, list(exp_avg), _gb._state_ptrs(group, exp_avg)[1], list(exp_avg_sq),
+        _gb._state_ptrs(group, exp_avg_sq)[1], _mu._widths_device(group), group.row_base_device, ids, rows, bool(rowwise),
+        0.0 if lr_device is not None else float(lr), 1.0 if bias_device is not None else float(bias_factor), float(beta1),
+        float(beta2), float(eps), float(weight_decay), lr_device, bias_device, host_count, word, last_id)
 
 
 def quantize_rows(table):
@@ -1516,6 +1585,19 @@ def _(tables, table_ptrs, states, state_ptrs, row_base, ids, rows, rule, lr, eps
 def _(tables, table_ptrs, exp_avg, exp_avg_ptrs, exp_avg_sq, exp_avg_sq_ptrs, row_base, ids, rows, rowwise, lr,
       bias_factor, beta1, beta2, eps, weight_decay, lr_device=None, bias_factor_device=None, count=-1, count_word=None,
       last_id=None, stochastic_rounding=False, seeds=None, step=0, step_device=None):
+    return None
+
+
+@torch.library.register_fake("cuembed_pyt::cuembed_sparse_row_update_mixed_group")
+def _(tables, table_ptrs, states, state_ptrs, widths, row_base, ids, rows, rule, lr, eps, lr_device=None, count=-1,
+      count_word=None, last_id=None):
+    return None
+
+
+@torch.library.register_fake("cuembed_pyt::cuembed_sparse_row_adam_mixed_group")
+def _(tables, table_ptrs, exp_avg, exp_avg_ptrs, exp_avg_sq, exp_avg_sq_ptrs, widths, row_base, ids, rows, rowwise, lr,
+      bias_factor, beta1, beta2, eps, weight_decay, lr_device=None, bias_factor_device=None, count=-1, count_word=None,
+      last_id=None):
     return None
 
 

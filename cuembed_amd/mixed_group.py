@@ -59,6 +59,10 @@ class MixedTableGroup(GroupTables):
         self._named_ptrs = None          # (name, pointer) of every table, for lane_bytes(): built at its first call
         self._table_columns_device = None
         self._descriptors = {}
+        # what the optimizer step keeps here (cuembed_amd.mixed_group_sparse_update): the device arrays of the state
+        # tensors' pointers, per set of tensors, and the widths as one int32 device tensor -- each built at its first use
+        self._state_ptr_arrays = {}
+        self._widths_device = None
 
     def _first_table(self, first):
         if first.dtype not in _ELEM:

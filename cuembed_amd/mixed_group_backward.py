@@ -14,9 +14,9 @@ scatter-add is its own kernel, which finds the source slice and the active lanes
 
 The gradient is padded to the widest table: rows is [capacity, W_max], entry k holds its row's gradient in
 rows[k, :W_t] for the table t that ids[k] falls in.  COLUMNS >= W_t ARE UNSPECIFIED (untouched or zero): read an entry
-through per_table(), which slices them off.  A ragged layout, the one-launch optimizer step, the weight gradient, dense
-gradients, reference_sums, the sample-blocked order and pad_to_capacity do not exist for a mixed group (DESIGN.md
-section 7).
+through per_table(), which slices them off, or apply it with the one-launch optimizer step
+(cuembed_amd.mixed_group_sparse_update), which never reads them.  A ragged layout, the weight gradient, dense gradients,
+reference_sums, the sample-blocked order and pad_to_capacity do not exist for a mixed group.
 
 Everything validates before any launch and runs on torch's current stream; nothing is read back, so after one warm call
 (which builds the group's small device arrays) a call can be captured into a HIP graph.

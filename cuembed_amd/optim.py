@@ -54,6 +54,14 @@ number of tables, by
                                                 not those of an updater on a one-storage group's flat tensor, which names
                                                 its bits by the global row.  There are no default seeds.
 
+A group of tables of DIFFERENT widths (cuembed_amd.mixed_group.MixedTableGroup) is stepped in ONE launch as well, by
+
+    MixedGroupSparseUpdater(group, rule, lr) / MixedGroupSparseAdamUpdater(group, lr, ...)
+        .apply(grad)                            a MixedGroupedGrad (embedding_backward_mixed_group): rows padded to the
+                                                widest table, the padding never read;
+        .backward_and_apply(grad_y, idx, offsets, weights, mode)     the mixed-width backward + the step, no read-back.
+                                                State per table: [rows_t, W_t] or [rows_t].  Round to nearest only.
+
 Stochastic rounding (stochastic_rounding=True, seed=...; float16 / bfloat16 tables): the rounding to the table's dtype
 goes up or down with the probability of the fp32 value's position between its neighbours, so that updates below half a
 unit in the last place are kept on average instead of being rounded away at every step.  The bits are a pure function
@@ -65,6 +73,9 @@ import torch
 
 from . import grouped as _grouped
 from . import grouped_backward as _grouped_backward
+from . import mixed_group as _mixed_group
+from . import mixed_group_backward as _mixed_group_backward
+from . import mixed_group_sparse_update as _mixed_step
 from . import ops as _ops
 from .mixed_group_backward import MixedGroupedGrad
 
@@ -359,6 +370,112 @@ class GroupSparseAdamUpdater(_GroupedGradientStep):
             weight_decay=self.weight_decay, rowwise=self.rowwise, last_id=grad.last_id, **self._rounding())
         if self.stochastic_rounding:
             self.rounding_step.add_(1)      # on the device, after the kernel in stream order: one apply = one step
+
+
+class _MixedGroupGradientStep:
+    """The index path shared by MixedGroupSparseUpdater and MixedGroupSparseAdamUpdater: the mixed-width backward -- global
+    ids, rows padded to the widest table, the count left on the device -- handed to self.apply(grad).  Needs self.group."""
+
+    def _init_group(self, group, stochastic_rounding):
+        if stochastic_rounding:
+            raise ValueError("the optimizer step of a mixed-width group rounds to nearest: stochastic rounding is not "
+                             "available for a MixedTableGroup")
+        self.group = _mixed_group._as_mixed_group(group)
+
+    def _device_arrays(self, *state_lists):
+        """The pointer arrays, the widths and row_base on the device, now: the first apply may be under capture."""
+        if self.group.device.type != "cuda":
+            return
+        for states in state_lists:
+            _grouped_backward._state_ptrs(self.group, states)
+        _mixed_step._widths_device(self.group)
+        self.group.row_base_device
+
+    def backward_and_apply(self, grad_y, idx, offsets=None, weights=None, mode="sum"):
+        """The backward of out = embedding_forward_mixed_group(group, idx, offsets, weights, mode=mode) and the step, in one
+        go: embedding_backward_mixed_group -- keys, ONE sort, ONE scatter-add, the entry count left on the device -- then
+        the mixed step, which reads the count itself.  grad_y [batch, embedding_dim] of the tables' dtype; idx [nnz] with
+        offsets [num_tables * batch + 1] (CSR), or idx [num_tables, batch, hotness] with offsets=None.  No host
+        read-back: forward + backward_and_apply on separate tensors of different widths can be captured into a HIP
+        graph (after one warm call, which builds the group's small device arrays)."""
+        hot = 0
+        if offsets is None:
+            if idx.dim() != 3:
+                raise ValueError("without offsets, idx must be [num_tables, batch, hotness]")
+            hot = idx.shape[2]
+        grad = _mixed_group_backward.embedding_backward_mixed_group(self.group, grad_y, idx, offsets, weights,
+                                                                    num_hots=hot, mode=mode)
+        self.apply(grad)
+        return grad
+
+    def _check_grad(self, grad):
+        if not isinstance(grad, MixedGroupedGrad):
+            raise TypeError("apply takes the MixedGroupedGrad of embedding_backward_mixed_group, got %s"
+                            % type(grad).__name__)
+        if grad.row_base != self.group.row_base or grad.widths != self.group.widths:
+            raise ValueError("the gradient belongs to a group with other row counts or widths")
+
+
+class MixedGroupSparseUpdater(_MixedGroupGradientStep):
+    """GroupSparseUpdater for a MixedTableGroup (or a list of tables of DIFFERENT widths): applies a MixedGroupedGrad to all
+    tables in ONE launch (cuembed_amd.sparse_row_update_mixed_group) and owns the state, `.states`: None ("sgd") or one
+    fp32 tensor per table, [rows_t, W_t] ("adagrad") or [rows_t] ("rowwise_adagrad").  lr: a float or a one-element fp32
+    device tensor; assign `.lr` to change it.  Rounds to nearest: stochastic_rounding=True is refused."""
+
+    def __init__(self, group, rule, lr, eps=1e-8, initial_accumulator_value=0.0, stochastic_rounding=False):
+        if rule not in _ops.UPDATE_RULES:
+            raise ValueError("rule must be one of %r, got %r" % (sorted(_ops.UPDATE_RULES), rule))
+        self._init_group(group, stochastic_rounding)
+        self.rule = rule
+        self.lr = lr
+        self.eps = float(eps)
+        self.states = None
+        if rule != "sgd":
+            self.states = tuple(_new_state(t, rule, initial_accumulator_value) for t in self.group.tables)
+        self._device_arrays(*(() if self.states is None else (self.states,)))
+
+    def apply(self, grad):
+        """tables[t][r, :W_t] (and its state) <- rule, for the valid entries of a MixedGroupedGrad.  Nothing is read back."""
+        self._check_grad(grad)
+        _mixed_step.sparse_row_update_mixed_group(self.group, grad.ids, grad.rows, rule=self.rule, lr=self.lr,
+                                                  states=self.states, eps=self.eps, last_id=grad.last_id)
+
+
+class MixedGroupSparseAdamUpdater(_MixedGroupGradientStep):
+    """GroupSparseAdamUpdater for a MixedTableGroup: one launch for the clock, one for all tables
+    (cuembed_amd.sparse_row_adam_mixed_group).  Owns `.exp_avg` and `.exp_avg_sq`, one fp32 tensor per table each
+    ([rows_t, W_t]; exp_avg_sq [rows_t] with rowwise=True), and ONE bias-factor clock for the group (`.powers`,
+    `.bias_factor`), which every apply advances on the device: a captured step takes the next step at every replay.
+    bias_correction=False leaves the factor at 1.  Rounds to nearest: stochastic_rounding=True is refused."""
+
+    def __init__(self, group, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rowwise=False, bias_correction=True,
+                 stochastic_rounding=False):
+        self.betas = _ops._check_betas(betas)
+        if not float(eps) >= 0.0 or not float(weight_decay) >= 0.0:
+            raise ValueError("eps and weight_decay must not be negative")
+        self._init_group(group, stochastic_rounding)
+        self.lr = lr
+        self.eps = float(eps)
+        self.weight_decay = float(weight_decay)
+        self.rowwise = bool(rowwise)
+        self.bias_correction = bool(bias_correction)
+        moments = [_new_moments(t, self.rowwise) for t in self.group.tables]
+        self.exp_avg = tuple(m for m, _ in moments)
+        self.exp_avg_sq = tuple(v for _, v in moments)
+        dev = self.group.device
+        self.powers = torch.tensor([0.0, 1.0, 1.0], dtype=torch.float64, device=dev)
+        self.bias_factor = torch.ones((1,), dtype=torch.float32, device=dev)
+        self._one = None if self.bias_correction else torch.ones((1,), dtype=torch.float32, device=dev)
+        self._device_arrays(self.exp_avg, self.exp_avg_sq)
+
+    def apply(self, grad):
+        """One Adam step on the valid entries of a MixedGroupedGrad: the clock moves on, then the mixed step."""
+        self._check_grad(grad)
+        _ops.adam_clock_advance(self.powers, self.bias_factor, self.betas)
+        _mixed_step.sparse_row_adam_mixed_group(
+            self.group, grad.ids, grad.rows, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, lr=self.lr,
+            bias_factor=self.bias_factor if self.bias_correction else self._one, betas=self.betas, eps=self.eps,
+            weight_decay=self.weight_decay, rowwise=self.rowwise, last_id=grad.last_id)
 
 
 def _new_moments(table, rowwise):

@@ -883,7 +883,8 @@ void cuembed_grouped_mean_scale(const void* grad_y, int elem_type, int embed_wid
  * every W_t * sizeof are a multiple of.  Limits: num_tables * batch_per_table and nnz <= INT_MAX, W_max at most 1024
  * lanes, batch_per_table * D * sizeof / lane bytes < 2^31; no other limit on num_tables.  Allocates nothing, reads
  * nothing back, capturable.  Not available for a mixed group: the dense gradient, reference sums, the sample-blocked
- * order, pad_to_capacity, the weight gradient and a one-launch optimizer step. */
+ * order, pad_to_capacity and the weight gradient.  The optimizer step on this gradient:
+ * cuembed_sparse_row_update_mixed_group / cuembed_sparse_row_adam_mixed_group below. */
 void cuembed_embedding_backward_mixed_group(const void* grad_y, int elem_type, const int* widths_host,
                                             const void* table_columns_device, int num_tables, int batch_per_table,
                                             int64_t nnz, const void* transpose_indices, const void* transpose_sample_ids,
@@ -965,6 +966,48 @@ void cuembed_sparse_row_adam_grouped_stochastic(const void* const* tables_host, 
                                                 float beta2, float one_minus_beta2, float eps, float weight_decay,
                                                 const uint64_t* seeds_device, uint64_t step, const int64_t* step_device,
                                                 cuembed_stream_t stream);
+/* ---- extension: the sparse optimizer step on a group of tables of DIFFERENT widths, in one launch ----------------------
+ * cuembed::SparseRowUpdateMixedGroup: cuembed_sparse_row_update_grouped for the group of
+ * cuembed_embedding_backward_mixed_group.  ids (index_type) are ascending GLOBAL rows, rows is [total_entries, max_width]
+ * with entry k's gradient in rows[k, :W_t] -- exactly that call's grad_embedding; the columns from W_t on are never read.
+ * widths_host / widths_device: the num_tables widths in elements, in host and in DEVICE memory; max_width: the widest
+ * one, the pitch of rows.  Entry k updates row id - row_base[t] of tables[t] ([rows_t, W_t]) and of that table's state
+ * tensor: fp32 [rows_t, W_t] with pitch W_t (CUEMBED_UPDATE_ADAGRAD; host copy of the bases required), fp32 [rows_t]
+ * (CUEMBED_UPDATE_ROWWISE_ADAGRAD), none (CUEMBED_UPDATE_SGD: both NULL).  One lane width for the launch: the widest of
+ * 16 / 8 / 4 bytes that every W_t * sizeof, every table base, rows and every per-element state base allow.  The count
+ * sources as in cuembed_sparse_row_update_grouped.  Round to nearest only; tables and state have the bits of num_tables
+ * cuembed_sparse_row_update calls at width W_t and that lane width.  num_tables <= 1023.  Nothing is allocated or read
+ * back; capturable.  Not taken: stochastic rounding, several pieces, tables behind the row cache. */
+void cuembed_sparse_row_update_mixed_group(const void* const* tables_host, const void* const* tables_device,
+                                           const void* const* state_host, const void* const* state_device,
+                                           const int* widths_host, const int* widths_device, int num_tables,
+                                           int elem_type, int max_width, const int64_t* row_base, int rule,
+                                           const void* ids, int index_type, const void* rows, int64_t total_entries,
+                                           int64_t num_rows, const void* count_word, int count_word_is_64,
+                                           const void* last_id, float lr, const float* lr_device, float eps,
+                                           cuembed_stream_t stream);
+/* cuembed::SparseRowAdamMixedGroup: cuembed_sparse_row_adam on such a group.  exp_avg_*: the bases of the fp32 [rows_t,
+ * W_t] first moments; exp_avg_sq_*: [rows_t, W_t] (CUEMBED_ADAM; host copy required) or [rows_t] (CUEMBED_ROWWISE_ADAM).
+ * The other parameters as above and as in cuembed_sparse_row_adam_grouped. */
+void cuembed_sparse_row_adam_mixed_group(const void* const* tables_host, const void* const* tables_device,
+                                         const void* const* exp_avg_host, const void* const* exp_avg_device,
+                                         const void* const* exp_avg_sq_host, const void* const* exp_avg_sq_device,
+                                         const int* widths_host, const int* widths_device, int num_tables, int elem_type,
+                                         int max_width, const int64_t* row_base, int rule, const void* ids,
+                                         int index_type, const void* rows, int64_t total_entries, int64_t num_rows,
+                                         const void* count_word, int count_word_is_64, const void* last_id, float lr,
+                                         const float* lr_device, float bias_factor, const float* bias_factor_device,
+                                         float beta1, float one_minus_beta1, float beta2, float one_minus_beta2,
+                                         float eps, float weight_decay, cuembed_stream_t stream);
+/* Launch shape of the two calls above (no launch; host arithmetic only when compute_units > 0).  state_tensors: 0 (SGD),
+ * 1 (the Adagrad rules), 2 (the Adam rules).  pointer_bits: the table bases and rows OR-ed; state_pointer_bits: the
+ * per-element state bases OR-ed (0 = aligned buffers).  out[0] = elements per lane, out[1] = grid (workgroups of 256
+ * threads: four wavefronts, each serving tiles of 64 entries), out[2] = dynamic LDS bytes.  per_table[2 t] = lanes per
+ * entry of table t (64: the whole wavefront, for a row of more than 64 lanes too), per_table[2 t + 1] = entries a pass
+ * serves. */
+void cuembed_mixed_group_update_launch_shape(const int* widths_host, int num_tables, int elem_type,
+                                             int64_t total_entries, int state_tensors, size_t pointer_bits,
+                                             size_t state_pointer_bits, int compute_units, int* out, int* per_table);
 /* ---- extension: the device-side index check (cuembed::CheckIndices, index_check.hpp) ---------------------------------
  * Is this batch safe to hand to the row-addressing calls above, which all trust their indices and offsets?  Never reads
  * a table, reads nothing back, allocates nothing, capturable.  n = num_tables * batch_per_table bags, table-major.  Row
