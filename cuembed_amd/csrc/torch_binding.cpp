@@ -684,9 +684,52 @@ class CuEmbEmbeddingNode : public torch::autograd::Function<CuEmbEmbeddingNode> 
 // collectives was ~60 launches and more host time than the whole forward + backward step; here it is two ops that
 // enqueue 2 and ~13 launches without returning to Python.  Nothing is read back.
 
-// What the two single-table optimizer ops below share (GroupedStep further down is the grouped ops'): the type codes,
+// What the two single-table optimizer ops below share (GroupedStep further down is the group ops'): the type codes,
 // the entries and the source of their count, and the one-word device tensors.  The checks run in the order of the
-// three functions, with the op's own (the rule, the state tensors, the hyper-parameters) in between.
+// three functions, with the op's own (the rule, the state tensors, the hyper-parameters) in between.  In front of them,
+// what every optimizer op shares: the rule code, the device words, Adam's hyper-parameters, the state's alignment.
+
+// "sgd" / "adagrad" / "rowwise_adagrad" as the library's code.
+int UpdateRuleCode(const std::string& rule) {
+  const int code = rule == "sgd" ? CUEMBED_UPDATE_SGD
+                   : rule == "adagrad" ? CUEMBED_UPDATE_ADAGRAD
+                   : rule == "rowwise_adagrad" ? CUEMBED_UPDATE_ROWWISE_ADAGRAD : -1;
+  TORCH_CHECK(code >= 0, "cuembed_pyt: rule must be 'sgd', 'adagrad' or 'rowwise_adagrad'");
+  return code;
+}
+
+// An optional one-element device tensor that the kernel reads (float32, or int64 for a step): its pointer, nullptr
+// where none is given.  `home`: the tensor whose device it has to be on -- `whose` "table's" / "tables'" -- or nullptr:
+// the single-table ops do not ask where lr_device and bias_factor_device live.
+template <typename Word>
+const Word* DeviceWord(const c10::optional<at::Tensor>& t, const char* name, const at::Tensor* home = nullptr,
+                       const char* whose = "") {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  CheckGpu(*t, name);
+  constexpr bool is_step = std::is_same<Word, int64_t>::value;
+  TORCH_CHECK(t->scalar_type() == (is_step ? at::kLong : at::kFloat) && t->numel() == 1 &&
+                  (home == nullptr || t->device() == home->device()),
+              "cuembed_pyt: ", name, " must be one ", is_step ? "int64" : "float32", " word",
+              home == nullptr ? "" : " on the ", whose, home == nullptr ? "" : " device");
+  return static_cast<const Word*>(t->data_ptr());
+}
+
+// Adam's hyper-parameters, checked, as the floats the C calls take: 1 - beta is formed in double and rounded once.
+struct AdamFloats {
+  float beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay;
+};
+
+AdamFloats CheckAdamHyperParameters(const double beta1, const double beta2, const double eps, const double weight_decay) {
+  TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "cuembed_pyt: betas must lie in [0, 1)");
+  TORCH_CHECK(eps >= 0.0 && weight_decay >= 0.0, "cuembed_pyt: eps and weight_decay must not be negative");
+  return {static_cast<float>(beta1), static_cast<float>(1.0 - beta1), static_cast<float>(beta2),
+          static_cast<float>(1.0 - beta2), static_cast<float>(eps), static_cast<float>(weight_decay)};
+}
+
+// The alignment of per-element fp32 state (Adagrad's accumulator, Adam's moments): a lane moves at least 4 bytes of
+// the table, so 4 / sizeof(element) state words at a time.
+uintptr_t StateAlignment(const int64_t element_size) { return 4 * (4 / static_cast<uintptr_t>(element_size)); }
+
 struct RowStep {
   int elem = CUEMBED_F32, idx = CUEMBED_I32, pieces = 1, words64 = 0;
   int64_t num_rows = -1, piece_rows = 0;
@@ -747,24 +790,12 @@ void ParseRowStepSources(RowStep& c, const at::Tensor& table, const at::Tensor& 
     c.num_rows = count >= 0 ? count : ids.numel();
     TORCH_CHECK(c.num_rows <= ids.numel(), "cuembed_pyt: count exceeds the entries");
   }
-  const auto word = [&](const c10::optional<at::Tensor>& t, const char* name) -> const float* {
-    if (!t.has_value() || !t->defined()) return nullptr;
-    CheckGpu(*t, name);
-    TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() == 1, "cuembed_pyt: ", name, " must be one float32 word");
-    return static_cast<const float*>(t->data_ptr());
-  };
-  c.lr_word = word(lr_device, "lr_device");
-  if (bias_factor_device != nullptr) c.bias_word = word(*bias_factor_device, "bias_factor_device");
+  c.lr_word = DeviceWord<float>(lr_device, "lr_device");
+  if (bias_factor_device != nullptr) c.bias_word = DeviceWord<float>(*bias_factor_device, "bias_factor_device");
   if (stochastic_rounding) {
     TORCH_CHECK(table.scalar_type() != at::kFloat,
                 "cuembed_pyt: stochastic_rounding is for float16 / bfloat16 tables: a float32 table is not rounded");
-    if (step_device.has_value() && step_device->defined()) {
-      CheckGpu(*step_device, "step_device");
-      TORCH_CHECK(step_device->scalar_type() == at::kLong && step_device->numel() == 1 &&
-                      step_device->device() == table.device(),
-                  "cuembed_pyt: step_device must be one int64 word on the table's device");
-      c.step_word = static_cast<const int64_t*>(step_device->data_ptr());
-    }
+    c.step_word = DeviceWord<int64_t>(step_device, "step_device", &table, "table's");
   }
 }
 
@@ -782,10 +813,7 @@ void cuembed_sparse_row_update_op(at::Tensor table, const c10::optional<at::Tens
                                   const int64_t piece_rows_arg, const bool stochastic_rounding, const int64_t seed,
                                   const int64_t step, const c10::optional<at::Tensor>& step_device) {
   RowStep c = RowStepCodes(table, ids, rows);
-  const int code = rule == "sgd" ? CUEMBED_UPDATE_SGD
-                   : rule == "adagrad" ? CUEMBED_UPDATE_ADAGRAD
-                   : rule == "rowwise_adagrad" ? CUEMBED_UPDATE_ROWWISE_ADAGRAD : -1;
-  TORCH_CHECK(code >= 0, "cuembed_pyt: rule must be 'sgd', 'adagrad' or 'rowwise_adagrad'");
+  const int code = UpdateRuleCode(rule);
   CheckRowStepShapes(table, ids, rows);
   at::Tensor state = state_arg.has_value() ? *state_arg : at::Tensor();
   if (code == CUEMBED_UPDATE_SGD) {
@@ -796,8 +824,7 @@ void cuembed_sparse_row_update_op(at::Tensor table, const c10::optional<at::Tens
                                                     : (state.dim() == 1 && state.size(0) == table.size(0))),
                 "cuembed_pyt: the state must be a contiguous float32 GPU tensor, [rows, width] for 'adagrad', [rows] for "
                 "'rowwise_adagrad'");
-    // a lane moves at least 4 bytes of the table, so 4 / sizeof(element) accumulator words at a time
-    const uintptr_t state_align = 4 * (4 / static_cast<uintptr_t>(table.element_size()));
+    const uintptr_t state_align = StateAlignment(table.element_size());
     TORCH_CHECK(code != CUEMBED_UPDATE_ADAGRAD || reinterpret_cast<uintptr_t>(state.data_ptr()) % state_align == 0,
                 "cuembed_pyt: the state must be ", state_align, "-byte aligned for a ", table.scalar_type(), " table");
   }
@@ -806,17 +833,17 @@ void cuembed_sparse_row_update_op(at::Tensor table, const c10::optional<at::Tens
   if (ids.numel() == 0) return;
   const at::DeviceGuard guard(table.device());
   float* state_ptr = state.defined() ? static_cast<float*>(state.data_ptr()) : nullptr;
+  // (one argument list for the step and its stochastic twin, which takes `rounding` in front of the stream)
+  const auto launch = [&](const auto step_fn, const auto... rounding) {
+    step_fn(table.data_ptr(), c.elem, static_cast<int>(table.size(1)), state_ptr, code, Ptr(ids), c.idx, Ptr(rows),
+            c.piece_rows, c.pieces, c.num_rows, c.counts, c.words64, c.last_id, static_cast<float>(lr), c.lr_word,
+            static_cast<float>(eps), rounding..., CurrentStream(table));
+  };
   if (stochastic_rounding) {
-    ::cuembed_sparse_row_update_stochastic(table.data_ptr(), c.elem, static_cast<int>(table.size(1)), state_ptr, code,
-                                           Ptr(ids), c.idx, Ptr(rows), c.piece_rows, c.pieces, c.num_rows, c.counts,
-                                           c.words64, c.last_id, static_cast<float>(lr), c.lr_word,
-                                           static_cast<float>(eps), static_cast<uint64_t>(seed),
-                                           static_cast<uint64_t>(step), c.step_word, CurrentStream(table));
-    return;
+    launch(::cuembed_sparse_row_update_stochastic, static_cast<uint64_t>(seed), static_cast<uint64_t>(step), c.step_word);
+  } else {
+    launch(::cuembed_sparse_row_update);
   }
-  ::cuembed_sparse_row_update(table.data_ptr(), c.elem, static_cast<int>(table.size(1)), state_ptr, code, Ptr(ids), c.idx,
-                              Ptr(rows), c.piece_rows, c.pieces, c.num_rows, c.counts, c.words64, c.last_id,
-                              static_cast<float>(lr), c.lr_word, static_cast<float>(eps), CurrentStream(table));
 }
 
 // Extension (cuembed::SparseRowAdam): the sparse Adam step on a compressed gradient, in place on the table and both
@@ -844,36 +871,28 @@ void cuembed_sparse_row_adam_op(at::Tensor table, at::Tensor exp_avg, at::Tensor
               "cuembed_pyt: exp_avg_sq must be a contiguous float32 GPU tensor, [rows, width] or, rowwise, [rows]");
   TORCH_CHECK(exp_avg.device() == table.device() && exp_avg_sq.device() == table.device(),
               "cuembed_pyt: exp_avg and exp_avg_sq must be on the table's device");
-  // a lane moves at least 4 bytes of the table, so 4 / sizeof(element) moment words at a time
-  const uintptr_t state_align = 4 * (4 / static_cast<uintptr_t>(table.element_size()));
+  const uintptr_t state_align = StateAlignment(table.element_size());
   TORCH_CHECK(reinterpret_cast<uintptr_t>(exp_avg.data_ptr()) % state_align == 0, "cuembed_pyt: exp_avg must be ",
               state_align, "-byte aligned for a ", table.scalar_type(), " table");
   TORCH_CHECK(rowwise || reinterpret_cast<uintptr_t>(exp_avg_sq.data_ptr()) % state_align == 0,
               "cuembed_pyt: exp_avg_sq must be ", state_align, "-byte aligned for a ", table.scalar_type(), " table");
-  TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "cuembed_pyt: betas must lie in [0, 1)");
-  TORCH_CHECK(eps >= 0.0 && weight_decay >= 0.0, "cuembed_pyt: eps and weight_decay must not be negative");
+  const AdamFloats h = CheckAdamHyperParameters(beta1, beta2, eps, weight_decay);
   ParseRowStepSources(c, table, ids, count, counts, last_id, piece_rows_arg, lr_device, &bias_factor_device,
                       stochastic_rounding, step_device);
   if (ids.numel() == 0) return;
   const at::DeviceGuard guard(table.device());
-  const int rule = rowwise ? CUEMBED_ROWWISE_ADAM : CUEMBED_ADAM;
-  float* m = static_cast<float*>(exp_avg.data_ptr());
-  float* v = static_cast<float*>(exp_avg_sq.data_ptr());
-  const float b1 = static_cast<float>(beta1), omb1 = static_cast<float>(1.0 - beta1);
-  const float b2 = static_cast<float>(beta2), omb2 = static_cast<float>(1.0 - beta2);
+  const auto launch = [&](const auto step_fn, const auto... rounding) {
+    step_fn(table.data_ptr(), c.elem, static_cast<int>(table.size(1)), static_cast<float*>(exp_avg.data_ptr()),
+            static_cast<float*>(exp_avg_sq.data_ptr()), rowwise ? CUEMBED_ROWWISE_ADAM : CUEMBED_ADAM, Ptr(ids), c.idx,
+            Ptr(rows), c.piece_rows, c.pieces, c.num_rows, c.counts, c.words64, c.last_id, static_cast<float>(lr),
+            c.lr_word, static_cast<float>(bias_factor), c.bias_word, h.beta1, h.one_minus_beta1, h.beta2,
+            h.one_minus_beta2, h.eps, h.weight_decay, rounding..., CurrentStream(table));
+  };
   if (stochastic_rounding) {
-    ::cuembed_sparse_row_adam_stochastic(
-        table.data_ptr(), c.elem, static_cast<int>(table.size(1)), m, v, rule, Ptr(ids), c.idx, Ptr(rows), c.piece_rows,
-        c.pieces, c.num_rows, c.counts, c.words64, c.last_id, static_cast<float>(lr), c.lr_word,
-        static_cast<float>(bias_factor), c.bias_word, b1, omb1, b2, omb2, static_cast<float>(eps),
-        static_cast<float>(weight_decay), static_cast<uint64_t>(seed), static_cast<uint64_t>(step), c.step_word,
-        CurrentStream(table));
-    return;
+    launch(::cuembed_sparse_row_adam_stochastic, static_cast<uint64_t>(seed), static_cast<uint64_t>(step), c.step_word);
+  } else {
+    launch(::cuembed_sparse_row_adam);
   }
-  ::cuembed_sparse_row_adam(table.data_ptr(), c.elem, static_cast<int>(table.size(1)), m, v, rule, Ptr(ids), c.idx, Ptr(rows),
-                            c.piece_rows, c.pieces, c.num_rows, c.counts, c.words64, c.last_id, static_cast<float>(lr),
-                            c.lr_word, static_cast<float>(bias_factor), c.bias_word, b1, omb1, b2, omb2,
-                            static_cast<float>(eps), static_cast<float>(weight_decay), CurrentStream(table));
 }
 
 // ---- the optimizer step on a group of SEPARATE table tensors, in one launch (cuembed::SparseRowUpdateGrouped /
@@ -886,9 +905,18 @@ void cuembed_sparse_row_adam_op(at::Tensor table, at::Tensor exp_avg, at::Tensor
 // [num_tables] that holds the bits of ONE unsigned 64-bit SEED PER TABLE, and the step, `step` or the one-element int64
 // device tensor step_device: the bits of entry k are those of (seeds[t], step, row inside table t, column).  There are
 // no default seeds: stochastic_rounding without seeds is refused, and so are seeds without it.  Nothing is read back.
+//
+// The same steps on a group of tables of DIFFERENT widths (cuembed::SparseRowUpdateMixedGroup /
+// SparseRowAdamMixedGroup) share everything below but the final call.  As the grouped ops, except: the tables' widths
+// may differ; `widths` is the int32 device tensor [num_tables] of them, built once by the caller (it MUST agree with the
+// tables: the op reads the host widths from the tables and never reads device memory); rows is [entries, W_max], padded
+// to the widest table -- the gradient of cuembed_embedding_backward_mixed_group; per-element state is [rows_t, W_t].
+// Round to nearest only.
 
 struct GroupedStep {
   std::vector<const void*> table_host;
+  std::vector<int> widths_host;             // a mixed-width group's, from the tables
+  int width = 0;                            // of rows: the tables', or the widest table's
   int elem = CUEMBED_F32, idx = CUEMBED_I32, words64 = 0;
   int64_t num_rows = -1;
   const void* count_word = nullptr;
@@ -898,7 +926,11 @@ struct GroupedStep {
   const int64_t* step_word = nullptr;
 };
 
-// One state list of a grouped step: `per_element` [rows_t, width] tensors, else [rows_t]; returns the host pointers.
+// The int64 device tensor of one base pointer per table, as the C calls take it.
+const void* const* PointerArray(const at::Tensor& ptrs) { return static_cast<const void* const*>(ptrs.data_ptr()); }
+
+// One state list of a step on a group: `per_element` tensors of their table's shape, else [rows_t]; returns the host
+// pointers.
 std::vector<const void*> CheckGroupedStates(const at::TensorList tables, const at::TensorList states,
                                             const c10::optional<at::Tensor>& ptrs, const bool per_element, const char* name) {
   TORCH_CHECK(states.size() == tables.size(), "cuembed_pyt: ", name, " must hold one tensor per table");
@@ -919,11 +951,72 @@ std::vector<const void*> CheckGroupedStates(const at::TensorList tables, const a
   return host;
 }
 
-// The count source (count / count_word / last_id / none) and lr_device of a step on a group, into `c`.
-void ParseGroupedStepSources(GroupedStep& c, const at::Tensor& table0, const at::Tensor& ids,
+// What every step on a group checks first, in this order: the rounding, the tables, their device arrays, ids and rows,
+// the count source (count / count_word / last_id / none) and lr_device.  `widths`: nullptr for a group of ONE width
+// (equal widths, rows [entries, width], seeds allowed), else the widths tensor of a mixed-width group (every row a
+// multiple of 4 bytes, rows [entries, W_max]; its ops have no rounding arguments to pass).
+GroupedStep CheckGroupedStep(const at::TensorList tables, const at::Tensor& table_ptrs, const at::Tensor* widths,
+                             const at::Tensor& row_base, const at::Tensor& ids, const at::Tensor& rows,
                              const c10::optional<at::Tensor>& lr_device, const int64_t count,
-                             const c10::optional<at::Tensor>& count_word, const c10::optional<at::Tensor>& last_id) {
-  const auto on_device = [&](const at::Tensor& t) { return t.is_cuda() && t.device() == table0.device(); };
+                             const c10::optional<at::Tensor>& count_word, const c10::optional<at::Tensor>& last_id,
+                             const bool stochastic_rounding = false, const c10::optional<at::Tensor>& seeds = c10::nullopt,
+                             const c10::optional<at::Tensor>& step_device = c10::nullopt) {
+  TORCH_CHECK(!tables.empty(), "cuembed_pyt: a group needs at least one table");
+  GroupedStep c;
+  const bool mixed = widths != nullptr;
+  const bool has_seeds = seeds.has_value() && seeds->defined();
+  TORCH_CHECK(!stochastic_rounding || has_seeds,
+              "cuembed_pyt: stochastic rounding on a grouped step takes one seed per table: pass seeds=[...]");
+  TORCH_CHECK(stochastic_rounding || !has_seeds, "cuembed_pyt: seeds go with stochastic_rounding = True");
+  const int64_t num_tables = static_cast<int64_t>(tables.size());
+  TORCH_CHECK(num_tables >= 1 && num_tables <= 1023, "cuembed_pyt: a grouped step takes 1 to 1023 tables");
+  const at::Tensor& first = tables[0];
+  c.elem = ElemCode(first, "tables");
+  if (stochastic_rounding) {
+    TORCH_CHECK(c.elem != CUEMBED_F32,
+                "cuembed_pyt: stochastic_rounding is for float16 / bfloat16 tables: a float32 table is not rounded");
+    CheckGpu(*seeds, "seeds");
+    TORCH_CHECK(seeds->scalar_type() == at::kLong && seeds->is_contiguous() && seeds->dim() == 1 &&
+                    seeds->numel() == num_tables && seeds->device() == first.device(),
+                "cuembed_pyt: seeds must be the contiguous int64 tensor [num_tables] of the tables' seeds on their device");
+    c.seeds = static_cast<const uint64_t*>(seeds->data_ptr());
+    c.step_word = DeviceWord<int64_t>(step_device, "step_device", &first, "tables'");
+  }
+  for (const at::Tensor& t : tables) {
+    CheckGpu(t, "tables");
+    const bool alike = t.dim() == 2 && t.is_contiguous() && t.scalar_type() == first.scalar_type() &&
+                       t.device() == first.device();
+    if (mixed) {
+      TORCH_CHECK(alike && t.size(1) >= 1 && (t.size(1) * t.element_size()) % 4 == 0,
+                  "cuembed_pyt: the tables of a mixed-width group must be contiguous [rows, width] of one dtype and device, "
+                  "every row a multiple of 4 bytes");
+      c.widths_host.push_back(static_cast<int>(t.size(1)));
+    } else {
+      TORCH_CHECK(alike && t.size(1) == first.size(1),
+                  "cuembed_pyt: the tables of a group must be contiguous [rows, width] of one dtype, width and device");
+    }
+    c.table_host.push_back(t.data_ptr());
+    c.width = std::max(c.width, static_cast<int>(t.size(1)));
+  }
+  const auto on_device = [&](const at::Tensor& t) { return t.is_cuda() && t.device() == first.device(); };
+  TORCH_CHECK(on_device(table_ptrs) && table_ptrs.scalar_type() == at::kLong && table_ptrs.is_contiguous() &&
+                  table_ptrs.numel() == num_tables,
+              "cuembed_pyt: table_ptrs must be the contiguous int64 tensor of the tables' data pointers on their device");
+  TORCH_CHECK(!mixed || (on_device(*widths) && widths->scalar_type() == at::kInt && widths->is_contiguous() &&
+                         widths->numel() == num_tables),
+              "cuembed_pyt: widths must be the contiguous int32 tensor of the tables' widths on their device");
+  TORCH_CHECK(on_device(row_base) && row_base.scalar_type() == at::kLong && row_base.is_contiguous() &&
+                  row_base.numel() == num_tables + 1,
+              "cuembed_pyt: row_base must be the contiguous int64 tensor of num_tables + 1 prefix sums on the tables' device");
+  CheckGpu(ids, "ids");
+  CheckGpu(rows, "rows");
+  c.idx = IndexCode(ids, "ids");
+  TORCH_CHECK(rows.scalar_type() == first.scalar_type(), "cuembed_pyt: rows must have the tables' dtype");
+  TORCH_CHECK(rows.dim() == 2 && rows.size(1) == c.width && ids.dim() == 1 && rows.size(0) == ids.numel() &&
+                  rows.is_contiguous() && ids.is_contiguous() && on_device(ids) && on_device(rows),
+              "cuembed_pyt: rows [entries, ", mixed ? "W_max] (padded to the widest table)" : "width]",
+              " and ids [entries] must be contiguous, agree and be on the tables' device");
+  TORCH_CHECK(mixed || (rows.size(1) * rows.element_size()) % 4 == 0, "cuembed_pyt: the row size must be a multiple of 4 bytes");
   const bool has_word = count_word.has_value() && count_word->defined();
   const bool has_last = last_id.has_value() && last_id->defined();
   TORCH_CHECK((count >= 0) + has_word + has_last <= 1, "cuembed_pyt: give at most one of count, count_word and last_id");
@@ -941,82 +1034,61 @@ void ParseGroupedStepSources(GroupedStep& c, const at::Tensor& table0, const at:
     c.num_rows = count >= 0 ? count : ids.numel();
     TORCH_CHECK(c.num_rows <= ids.numel(), "cuembed_pyt: count exceeds the entries");
   }
-  if (lr_device.has_value() && lr_device->defined()) {
-    CheckGpu(*lr_device, "lr_device");
-    TORCH_CHECK(lr_device->scalar_type() == at::kFloat && lr_device->numel() == 1 && on_device(*lr_device),
-                "cuembed_pyt: lr_device must be one float32 word on the tables' device");
-    c.lr_word = static_cast<const float*>(lr_device->data_ptr());
-  }
-}
-
-GroupedStep CheckGroupedStep(const at::TensorList tables, const at::Tensor& table_ptrs, const at::Tensor& row_base,
-                             const at::Tensor& ids, const at::Tensor& rows, const c10::optional<at::Tensor>& lr_device,
-                             const int64_t count, const c10::optional<at::Tensor>& count_word,
-                             const c10::optional<at::Tensor>& last_id, const bool stochastic_rounding,
-                             const c10::optional<at::Tensor>& seeds, const int64_t step,
-                             const c10::optional<at::Tensor>& step_device) {
-  GroupedStep c;
-  const bool has_seeds = seeds.has_value() && seeds->defined();
-  TORCH_CHECK(!stochastic_rounding || has_seeds,
-              "cuembed_pyt: stochastic rounding on a grouped step takes one seed per table: pass seeds=[...]");
-  TORCH_CHECK(stochastic_rounding || !has_seeds, "cuembed_pyt: seeds go with stochastic_rounding = True");
-  const int64_t num_tables = static_cast<int64_t>(tables.size());
-  TORCH_CHECK(num_tables >= 1 && num_tables <= 1023, "cuembed_pyt: a grouped step takes 1 to 1023 tables");
-  c.elem = ElemCode(tables[0], "tables");
-  if (stochastic_rounding) {
-    TORCH_CHECK(c.elem != CUEMBED_F32,
-                "cuembed_pyt: stochastic_rounding is for float16 / bfloat16 tables: a float32 table is not rounded");
-    CheckGpu(*seeds, "seeds");
-    TORCH_CHECK(seeds->scalar_type() == at::kLong && seeds->is_contiguous() && seeds->dim() == 1 &&
-                    seeds->numel() == num_tables && seeds->device() == tables[0].device(),
-                "cuembed_pyt: seeds must be the contiguous int64 tensor [num_tables] of the tables' seeds on their device");
-    c.seeds = static_cast<const uint64_t*>(seeds->data_ptr());
-    if (step_device.has_value() && step_device->defined()) {
-      CheckGpu(*step_device, "step_device");
-      TORCH_CHECK(step_device->scalar_type() == at::kLong && step_device->numel() == 1 &&
-                      step_device->device() == tables[0].device(),
-                  "cuembed_pyt: step_device must be one int64 word on the tables' device");
-      c.step_word = static_cast<const int64_t*>(step_device->data_ptr());
-    }
-  }
-  for (const at::Tensor& t : tables) {
-    CheckGpu(t, "tables");
-    TORCH_CHECK(t.dim() == 2 && t.is_contiguous() && t.scalar_type() == tables[0].scalar_type() &&
-                    t.size(1) == tables[0].size(1) && t.device() == tables[0].device(),
-                "cuembed_pyt: the tables of a group must be contiguous [rows, width] of one dtype, width and device");
-    c.table_host.push_back(t.data_ptr());
-  }
-  const auto on_device = [&](const at::Tensor& t) { return t.is_cuda() && t.device() == tables[0].device(); };
-  TORCH_CHECK(on_device(table_ptrs) && table_ptrs.scalar_type() == at::kLong && table_ptrs.is_contiguous() &&
-                  table_ptrs.numel() == num_tables,
-              "cuembed_pyt: table_ptrs must be the contiguous int64 tensor of the tables' data pointers on their device");
-  TORCH_CHECK(on_device(row_base) && row_base.scalar_type() == at::kLong && row_base.is_contiguous() &&
-                  row_base.numel() == num_tables + 1,
-              "cuembed_pyt: row_base must be the contiguous int64 tensor of num_tables + 1 prefix sums on the tables' device");
-  CheckGpu(ids, "ids");
-  CheckGpu(rows, "rows");
-  c.idx = IndexCode(ids, "ids");
-  TORCH_CHECK(rows.scalar_type() == tables[0].scalar_type(), "cuembed_pyt: rows must have the tables' dtype");
-  TORCH_CHECK(rows.dim() == 2 && rows.size(1) == tables[0].size(1) && ids.dim() == 1 && rows.size(0) == ids.numel() &&
-                  rows.is_contiguous() && ids.is_contiguous() && on_device(ids) && on_device(rows),
-              "cuembed_pyt: rows [entries, width] and ids [entries] must be contiguous, agree and be on the tables' device");
-  TORCH_CHECK((rows.size(1) * rows.element_size()) % 4 == 0, "cuembed_pyt: the row size must be a multiple of 4 bytes");
-  ParseGroupedStepSources(c, tables[0], ids, lr_device, count, count_word, last_id);
+  c.lr_word = DeviceWord<float>(lr_device, "lr_device", &first, "tables'");
   return c;
 }
 
 // The lane width the library will pick must exist: 4-byte aligned data, and per-element state that the narrowest lane
-// (4 bytes of the row: 4 / sizeof(element) fp32 words) can move.
+// (4 bytes of the row) can move.
 void CheckGroupedAlignment(const GroupedStep& c, const at::Tensor& rows, const int64_t element_size,
                            const std::vector<const std::vector<const void*>*>& per_element_states) {
   uintptr_t bits = reinterpret_cast<uintptr_t>(rows.data_ptr());
   for (const void* p : c.table_host) bits |= reinterpret_cast<uintptr_t>(p);
   TORCH_CHECK(bits % 4 == 0, "cuembed_pyt: tables and rows must be 4-byte aligned");
-  const uintptr_t state_align = 4 * (4 / static_cast<uintptr_t>(element_size));
+  const uintptr_t state_align = StateAlignment(element_size);
   for (const auto* host : per_element_states)
     for (const void* p : *host)
       TORCH_CHECK(reinterpret_cast<uintptr_t>(p) % state_align == 0, "cuembed_pyt: per-element state must be ", state_align,
                   "-byte aligned for tables of ", element_size, "-byte elements");
+}
+
+// The states of an update rule on a group (none for 'sgd') and the alignment of the call: the states' host pointers.
+std::vector<const void*> CheckGroupedUpdateStates(const GroupedStep& c, const at::TensorList tables,
+                                                  const at::TensorList states, const c10::optional<at::Tensor>& state_ptrs,
+                                                  const int code, const at::Tensor& rows) {
+  std::vector<const void*> state_host;
+  if (code == CUEMBED_UPDATE_SGD) {
+    TORCH_CHECK(states.empty(), "cuembed_pyt: rule 'sgd' takes no states");
+  } else {
+    state_host = CheckGroupedStates(tables, states, state_ptrs, code == CUEMBED_UPDATE_ADAGRAD, "states");
+  }
+  std::vector<const std::vector<const void*>*> per_element;
+  if (code == CUEMBED_UPDATE_ADAGRAD) per_element.push_back(&state_host);
+  CheckGroupedAlignment(c, rows, tables[0].element_size(), per_element);
+  return state_host;
+}
+
+// The moments of an Adam step on a group, the alignment of the call, the hyper-parameters and bias_factor_device.
+struct GroupedAdam {
+  std::vector<const void*> m_host, v_host;
+  AdamFloats h;
+  const float* bias_word;
+};
+
+GroupedAdam CheckGroupedAdam(const GroupedStep& c, const at::TensorList tables, const at::TensorList exp_avg,
+                             const at::Tensor& exp_avg_ptrs, const at::TensorList exp_avg_sq,
+                             const at::Tensor& exp_avg_sq_ptrs, const at::Tensor& rows, const bool rowwise,
+                             const double beta1, const double beta2, const double eps, const double weight_decay,
+                             const c10::optional<at::Tensor>& bias_factor_device) {
+  GroupedAdam a;
+  a.m_host = CheckGroupedStates(tables, exp_avg, exp_avg_ptrs, true, "exp_avg");
+  a.v_host = CheckGroupedStates(tables, exp_avg_sq, exp_avg_sq_ptrs, !rowwise, "exp_avg_sq");
+  std::vector<const std::vector<const void*>*> per_element = {&a.m_host};
+  if (!rowwise) per_element.push_back(&a.v_host);
+  CheckGroupedAlignment(c, rows, tables[0].element_size(), per_element);
+  a.h = CheckAdamHyperParameters(beta1, beta2, eps, weight_decay);
+  a.bias_word = DeviceWord<float>(bias_factor_device, "bias_factor_device", &tables[0], "tables'");
+  return a;
 }
 
 void cuembed_sparse_row_update_grouped_op(const at::TensorList tables, const at::Tensor& table_ptrs,
@@ -1028,42 +1100,25 @@ void cuembed_sparse_row_update_grouped_op(const at::TensorList tables, const at:
                                           const c10::optional<at::Tensor>& last_id, const bool stochastic_rounding,
                                           const c10::optional<at::Tensor>& seeds, const int64_t step,
                                           const c10::optional<at::Tensor>& step_device) {
-  const int code = rule == "sgd" ? CUEMBED_UPDATE_SGD
-                   : rule == "adagrad" ? CUEMBED_UPDATE_ADAGRAD
-                   : rule == "rowwise_adagrad" ? CUEMBED_UPDATE_ROWWISE_ADAGRAD : -1;
-  TORCH_CHECK(code >= 0, "cuembed_pyt: rule must be 'sgd', 'adagrad' or 'rowwise_adagrad'");
-  TORCH_CHECK(!tables.empty(), "cuembed_pyt: a group needs at least one table");
-  const GroupedStep c =
-      CheckGroupedStep(tables, table_ptrs, row_base, ids, rows, lr_device, count, count_word, last_id, stochastic_rounding,
-                       seeds, step, step_device);
-  std::vector<const void*> state_host;
-  if (code == CUEMBED_UPDATE_SGD) {
-    TORCH_CHECK(states.empty(), "cuembed_pyt: rule 'sgd' takes no states");
-  } else {
-    state_host = CheckGroupedStates(tables, states, state_ptrs, code == CUEMBED_UPDATE_ADAGRAD, "states");
-  }
-  std::vector<const std::vector<const void*>*> per_element;
-  if (code == CUEMBED_UPDATE_ADAGRAD) per_element.push_back(&state_host);
-  CheckGroupedAlignment(c, rows, tables[0].element_size(), per_element);
+  const int code = UpdateRuleCode(rule);
+  const GroupedStep c = CheckGroupedStep(tables, table_ptrs, nullptr, row_base, ids, rows, lr_device, count, count_word,
+                                         last_id, stochastic_rounding, seeds, step_device);
+  const std::vector<const void*> state_host = CheckGroupedUpdateStates(c, tables, states, state_ptrs, code, rows);
   if (ids.numel() == 0) return;
   const at::DeviceGuard guard(tables[0].device());
   const bool stateful = code != CUEMBED_UPDATE_SGD;
+  const auto launch = [&](const auto step_fn, const auto... rounding) {
+    step_fn(c.table_host.data(), PointerArray(table_ptrs), stateful ? state_host.data() : nullptr,
+            stateful ? PointerArray(*state_ptrs) : nullptr, static_cast<int>(tables.size()), c.elem, c.width,
+            static_cast<const int64_t*>(row_base.data_ptr()), code, Ptr(ids), c.idx, Ptr(rows), ids.numel(), c.num_rows,
+            c.count_word, c.words64, c.last_id, static_cast<float>(lr), c.lr_word, static_cast<float>(eps), rounding...,
+            CurrentStream(rows));
+  };
   if (stochastic_rounding) {
-    ::cuembed_sparse_row_update_grouped_stochastic(
-        c.table_host.data(), static_cast<const void* const*>(table_ptrs.data_ptr()),
-        stateful ? state_host.data() : nullptr,
-        stateful ? static_cast<const void* const*>(state_ptrs->data_ptr()) : nullptr, static_cast<int>(tables.size()),
-        c.elem, static_cast<int>(rows.size(1)), static_cast<const int64_t*>(row_base.data_ptr()), code, Ptr(ids), c.idx,
-        Ptr(rows), ids.numel(), c.num_rows, c.count_word, c.words64, c.last_id, static_cast<float>(lr), c.lr_word,
-        static_cast<float>(eps), c.seeds, static_cast<uint64_t>(step), c.step_word, CurrentStream(rows));
-    return;
+    launch(::cuembed_sparse_row_update_grouped_stochastic, c.seeds, static_cast<uint64_t>(step), c.step_word);
+  } else {
+    launch(::cuembed_sparse_row_update_grouped);
   }
-  ::cuembed_sparse_row_update_grouped(
-      c.table_host.data(), static_cast<const void* const*>(table_ptrs.data_ptr()), stateful ? state_host.data() : nullptr,
-      stateful ? static_cast<const void* const*>(state_ptrs->data_ptr()) : nullptr, static_cast<int>(tables.size()),
-      c.elem, static_cast<int>(rows.size(1)), static_cast<const int64_t*>(row_base.data_ptr()), code, Ptr(ids), c.idx,
-      Ptr(rows), ids.numel(), c.num_rows, c.count_word, c.words64, c.last_id, static_cast<float>(lr), c.lr_word,
-      static_cast<float>(eps), CurrentStream(rows));
 }
 
 void cuembed_sparse_row_adam_grouped_op(const at::TensorList tables, const at::Tensor& table_ptrs,
@@ -1078,101 +1133,25 @@ void cuembed_sparse_row_adam_grouped_op(const at::TensorList tables, const at::T
                                         const c10::optional<at::Tensor>& last_id, const bool stochastic_rounding,
                                         const c10::optional<at::Tensor>& seeds, const int64_t step,
                                         const c10::optional<at::Tensor>& step_device) {
-  TORCH_CHECK(!tables.empty(), "cuembed_pyt: a group needs at least one table");
-  const GroupedStep c =
-      CheckGroupedStep(tables, table_ptrs, row_base, ids, rows, lr_device, count, count_word, last_id, stochastic_rounding,
-                       seeds, step, step_device);
-  const std::vector<const void*> m_host = CheckGroupedStates(tables, exp_avg, exp_avg_ptrs, true, "exp_avg");
-  const std::vector<const void*> v_host = CheckGroupedStates(tables, exp_avg_sq, exp_avg_sq_ptrs, !rowwise, "exp_avg_sq");
-  std::vector<const std::vector<const void*>*> per_element = {&m_host};
-  if (!rowwise) per_element.push_back(&v_host);
-  CheckGroupedAlignment(c, rows, tables[0].element_size(), per_element);
-  TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "cuembed_pyt: betas must lie in [0, 1)");
-  TORCH_CHECK(eps >= 0.0 && weight_decay >= 0.0, "cuembed_pyt: eps and weight_decay must not be negative");
-  const float* bias_word = nullptr;
-  if (bias_factor_device.has_value() && bias_factor_device->defined()) {
-    CheckGpu(*bias_factor_device, "bias_factor_device");
-    TORCH_CHECK(bias_factor_device->scalar_type() == at::kFloat && bias_factor_device->numel() == 1 &&
-                    bias_factor_device->device() == tables[0].device(),
-                "cuembed_pyt: bias_factor_device must be one float32 word on the tables' device");
-    bias_word = static_cast<const float*>(bias_factor_device->data_ptr());
-  }
+  const GroupedStep c = CheckGroupedStep(tables, table_ptrs, nullptr, row_base, ids, rows, lr_device, count, count_word,
+                                         last_id, stochastic_rounding, seeds, step_device);
+  const GroupedAdam a = CheckGroupedAdam(c, tables, exp_avg, exp_avg_ptrs, exp_avg_sq, exp_avg_sq_ptrs, rows, rowwise, beta1,
+                                         beta2, eps, weight_decay, bias_factor_device);
   if (ids.numel() == 0) return;
   const at::DeviceGuard guard(tables[0].device());
+  const auto launch = [&](const auto step_fn, const auto... rounding) {
+    step_fn(c.table_host.data(), PointerArray(table_ptrs), a.m_host.data(), PointerArray(exp_avg_ptrs), a.v_host.data(),
+            PointerArray(exp_avg_sq_ptrs), static_cast<int>(tables.size()), c.elem, c.width,
+            static_cast<const int64_t*>(row_base.data_ptr()), rowwise ? CUEMBED_ROWWISE_ADAM : CUEMBED_ADAM, Ptr(ids), c.idx,
+            Ptr(rows), ids.numel(), c.num_rows, c.count_word, c.words64, c.last_id, static_cast<float>(lr), c.lr_word,
+            static_cast<float>(bias_factor), a.bias_word, a.h.beta1, a.h.one_minus_beta1, a.h.beta2, a.h.one_minus_beta2,
+            a.h.eps, a.h.weight_decay, rounding..., CurrentStream(rows));
+  };
   if (stochastic_rounding) {
-    ::cuembed_sparse_row_adam_grouped_stochastic(
-        c.table_host.data(), static_cast<const void* const*>(table_ptrs.data_ptr()), m_host.data(),
-        static_cast<const void* const*>(exp_avg_ptrs.data_ptr()), v_host.data(),
-        static_cast<const void* const*>(exp_avg_sq_ptrs.data_ptr()), static_cast<int>(tables.size()), c.elem,
-        static_cast<int>(rows.size(1)), static_cast<const int64_t*>(row_base.data_ptr()),
-        rowwise ? CUEMBED_ROWWISE_ADAM : CUEMBED_ADAM, Ptr(ids), c.idx, Ptr(rows), ids.numel(), c.num_rows, c.count_word,
-        c.words64, c.last_id, static_cast<float>(lr), c.lr_word, static_cast<float>(bias_factor), bias_word,
-        static_cast<float>(beta1), static_cast<float>(1.0 - beta1), static_cast<float>(beta2),
-        static_cast<float>(1.0 - beta2), static_cast<float>(eps), static_cast<float>(weight_decay), c.seeds,
-        static_cast<uint64_t>(step), c.step_word, CurrentStream(rows));
-    return;
+    launch(::cuembed_sparse_row_adam_grouped_stochastic, c.seeds, static_cast<uint64_t>(step), c.step_word);
+  } else {
+    launch(::cuembed_sparse_row_adam_grouped);
   }
-  ::cuembed_sparse_row_adam_grouped(
-      c.table_host.data(), static_cast<const void* const*>(table_ptrs.data_ptr()), m_host.data(),
-      static_cast<const void* const*>(exp_avg_ptrs.data_ptr()), v_host.data(),
-      static_cast<const void* const*>(exp_avg_sq_ptrs.data_ptr()), static_cast<int>(tables.size()), c.elem,
-      static_cast<int>(rows.size(1)), static_cast<const int64_t*>(row_base.data_ptr()),
-      rowwise ? CUEMBED_ROWWISE_ADAM : CUEMBED_ADAM, Ptr(ids), c.idx, Ptr(rows), ids.numel(), c.num_rows, c.count_word,
-      c.words64, c.last_id, static_cast<float>(lr), c.lr_word, static_cast<float>(bias_factor), bias_word,
-      static_cast<float>(beta1), static_cast<float>(1.0 - beta1), static_cast<float>(beta2),
-      static_cast<float>(1.0 - beta2), static_cast<float>(eps), static_cast<float>(weight_decay), CurrentStream(rows));
-}
-
-// ---- the same steps on a group of tables of DIFFERENT widths (cuembed::SparseRowUpdateMixedGroup /
-// SparseRowAdamMixedGroup).  As the grouped ops above, except: the tables' widths may differ; `widths` is the int32
-// device tensor [num_tables] of them, built once by the caller (it MUST agree with the tables: the op reads the host
-// widths from the tables and never reads device memory); rows is [entries, W_max], padded to the widest table -- the
-// gradient of cuembed_embedding_backward_mixed_group; per-element state is [rows_t, W_t].  Round to nearest only.
-
-struct MixedGroupStep {
-  GroupedStep c;
-  std::vector<int> widths_host;
-  int max_width = 0;
-};
-
-MixedGroupStep CheckMixedGroupStep(const at::TensorList tables, const at::Tensor& table_ptrs, const at::Tensor& widths,
-                                   const at::Tensor& row_base, const at::Tensor& ids, const at::Tensor& rows,
-                                   const c10::optional<at::Tensor>& lr_device, const int64_t count,
-                                   const c10::optional<at::Tensor>& count_word,
-                                   const c10::optional<at::Tensor>& last_id) {
-  MixedGroupStep m;
-  const int64_t num_tables = static_cast<int64_t>(tables.size());
-  TORCH_CHECK(num_tables >= 1 && num_tables <= 1023, "cuembed_pyt: a grouped step takes 1 to 1023 tables");
-  m.c.elem = ElemCode(tables[0], "tables");
-  for (const at::Tensor& t : tables) {
-    CheckGpu(t, "tables");
-    TORCH_CHECK(t.dim() == 2 && t.is_contiguous() && t.scalar_type() == tables[0].scalar_type() &&
-                    t.device() == tables[0].device() && t.size(1) >= 1 && (t.size(1) * t.element_size()) % 4 == 0,
-                "cuembed_pyt: the tables of a mixed-width group must be contiguous [rows, width] of one dtype and device, "
-                "every row a multiple of 4 bytes");
-    m.c.table_host.push_back(t.data_ptr());
-    m.widths_host.push_back(static_cast<int>(t.size(1)));
-    m.max_width = std::max(m.max_width, m.widths_host.back());
-  }
-  const auto on_device = [&](const at::Tensor& t) { return t.is_cuda() && t.device() == tables[0].device(); };
-  TORCH_CHECK(on_device(table_ptrs) && table_ptrs.scalar_type() == at::kLong && table_ptrs.is_contiguous() &&
-                  table_ptrs.numel() == num_tables,
-              "cuembed_pyt: table_ptrs must be the contiguous int64 tensor of the tables' data pointers on their device");
-  TORCH_CHECK(on_device(widths) && widths.scalar_type() == at::kInt && widths.is_contiguous() && widths.numel() == num_tables,
-              "cuembed_pyt: widths must be the contiguous int32 tensor of the tables' widths on their device");
-  TORCH_CHECK(on_device(row_base) && row_base.scalar_type() == at::kLong && row_base.is_contiguous() &&
-                  row_base.numel() == num_tables + 1,
-              "cuembed_pyt: row_base must be the contiguous int64 tensor of num_tables + 1 prefix sums on the tables' device");
-  CheckGpu(ids, "ids");
-  CheckGpu(rows, "rows");
-  m.c.idx = IndexCode(ids, "ids");
-  TORCH_CHECK(rows.scalar_type() == tables[0].scalar_type(), "cuembed_pyt: rows must have the tables' dtype");
-  TORCH_CHECK(rows.dim() == 2 && rows.size(1) == m.max_width && ids.dim() == 1 && rows.size(0) == ids.numel() &&
-                  rows.is_contiguous() && ids.is_contiguous() && on_device(ids) && on_device(rows),
-              "cuembed_pyt: rows [entries, W_max] (padded to the widest table) and ids [entries] must be contiguous, agree "
-              "and be on the tables' device");
-  ParseGroupedStepSources(m.c, tables[0], ids, lr_device, count, count_word, last_id);
-  return m;
 }
 
 void cuembed_sparse_row_update_mixed_group_op(const at::TensorList tables, const at::Tensor& table_ptrs,
@@ -1182,31 +1161,18 @@ void cuembed_sparse_row_update_mixed_group_op(const at::TensorList tables, const
                                               const double eps, const c10::optional<at::Tensor>& lr_device,
                                               const int64_t count, const c10::optional<at::Tensor>& count_word,
                                               const c10::optional<at::Tensor>& last_id) {
-  const int code = rule == "sgd" ? CUEMBED_UPDATE_SGD
-                   : rule == "adagrad" ? CUEMBED_UPDATE_ADAGRAD
-                   : rule == "rowwise_adagrad" ? CUEMBED_UPDATE_ROWWISE_ADAGRAD : -1;
-  TORCH_CHECK(code >= 0, "cuembed_pyt: rule must be 'sgd', 'adagrad' or 'rowwise_adagrad'");
-  TORCH_CHECK(!tables.empty(), "cuembed_pyt: a group needs at least one table");
-  const MixedGroupStep m = CheckMixedGroupStep(tables, table_ptrs, widths, row_base, ids, rows, lr_device, count, count_word, last_id);
-  const bool stateful = code != CUEMBED_UPDATE_SGD;
-  std::vector<const void*> state_host;
-  if (stateful) {
-    state_host = CheckGroupedStates(tables, states, state_ptrs, code == CUEMBED_UPDATE_ADAGRAD, "states");
-  } else {
-    TORCH_CHECK(states.empty(), "cuembed_pyt: rule 'sgd' takes no states");
-  }
-  std::vector<const std::vector<const void*>*> per_element;
-  if (code == CUEMBED_UPDATE_ADAGRAD) per_element.push_back(&state_host);
-  CheckGroupedAlignment(m.c, rows, tables[0].element_size(), per_element);
+  const int code = UpdateRuleCode(rule);
+  const GroupedStep c = CheckGroupedStep(tables, table_ptrs, &widths, row_base, ids, rows, lr_device, count, count_word, last_id);
+  const std::vector<const void*> state_host = CheckGroupedUpdateStates(c, tables, states, state_ptrs, code, rows);
   if (ids.numel() == 0) return;
   const at::DeviceGuard guard(tables[0].device());
+  const bool stateful = code != CUEMBED_UPDATE_SGD;
   ::cuembed_sparse_row_update_mixed_group(
-      m.c.table_host.data(), static_cast<const void* const*>(table_ptrs.data_ptr()), stateful ? state_host.data() : nullptr,
-      stateful ? static_cast<const void* const*>(state_ptrs->data_ptr()) : nullptr, m.widths_host.data(),
-      static_cast<const int*>(widths.data_ptr()), static_cast<int>(tables.size()), m.c.elem, m.max_width,
-      static_cast<const int64_t*>(row_base.data_ptr()), code, Ptr(ids), m.c.idx, Ptr(rows), ids.numel(), m.c.num_rows,
-      m.c.count_word, m.c.words64, m.c.last_id, static_cast<float>(lr), m.c.lr_word, static_cast<float>(eps),
-      CurrentStream(rows));
+      c.table_host.data(), PointerArray(table_ptrs), stateful ? state_host.data() : nullptr,
+      stateful ? PointerArray(*state_ptrs) : nullptr, c.widths_host.data(), static_cast<const int*>(widths.data_ptr()),
+      static_cast<int>(tables.size()), c.elem, c.width, static_cast<const int64_t*>(row_base.data_ptr()), code, Ptr(ids),
+      c.idx, Ptr(rows), ids.numel(), c.num_rows, c.count_word, c.words64, c.last_id, static_cast<float>(lr), c.lr_word,
+      static_cast<float>(eps), CurrentStream(rows));
 }
 
 void cuembed_sparse_row_adam_mixed_group_op(const at::TensorList tables, const at::Tensor& table_ptrs,
@@ -1220,36 +1186,20 @@ void cuembed_sparse_row_adam_mixed_group_op(const at::TensorList tables, const a
                                             const c10::optional<at::Tensor>& bias_factor_device, const int64_t count,
                                             const c10::optional<at::Tensor>& count_word,
                                             const c10::optional<at::Tensor>& last_id) {
-  TORCH_CHECK(!tables.empty(), "cuembed_pyt: a group needs at least one table");
-  const MixedGroupStep m = CheckMixedGroupStep(tables, table_ptrs, widths, row_base, ids, rows, lr_device, count, count_word, last_id);
-  const std::vector<const void*> m_host = CheckGroupedStates(tables, exp_avg, exp_avg_ptrs, true, "exp_avg");
-  const std::vector<const void*> v_host = CheckGroupedStates(tables, exp_avg_sq, exp_avg_sq_ptrs, !rowwise, "exp_avg_sq");
-  std::vector<const std::vector<const void*>*> per_element = {&m_host};
-  if (!rowwise) per_element.push_back(&v_host);
-  CheckGroupedAlignment(m.c, rows, tables[0].element_size(), per_element);
-  TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "cuembed_pyt: betas must lie in [0, 1)");
-  TORCH_CHECK(eps >= 0.0 && weight_decay >= 0.0, "cuembed_pyt: eps and weight_decay must not be negative");
-  const float* bias_word = nullptr;
-  if (bias_factor_device.has_value() && bias_factor_device->defined()) {
-    CheckGpu(*bias_factor_device, "bias_factor_device");
-    TORCH_CHECK(bias_factor_device->scalar_type() == at::kFloat && bias_factor_device->numel() == 1 &&
-                    bias_factor_device->device() == tables[0].device(),
-                "cuembed_pyt: bias_factor_device must be one float32 word on the tables' device");
-    bias_word = static_cast<const float*>(bias_factor_device->data_ptr());
-  }
+  const GroupedStep c = CheckGroupedStep(tables, table_ptrs, &widths, row_base, ids, rows, lr_device, count, count_word, last_id);
+  const GroupedAdam a = CheckGroupedAdam(c, tables, exp_avg, exp_avg_ptrs, exp_avg_sq, exp_avg_sq_ptrs, rows, rowwise, beta1,
+                                         beta2, eps, weight_decay, bias_factor_device);
   if (ids.numel() == 0) return;
   const at::DeviceGuard guard(tables[0].device());
   ::cuembed_sparse_row_adam_mixed_group(
-      m.c.table_host.data(), static_cast<const void* const*>(table_ptrs.data_ptr()), m_host.data(),
-      static_cast<const void* const*>(exp_avg_ptrs.data_ptr()), v_host.data(),
-      static_cast<const void* const*>(exp_avg_sq_ptrs.data_ptr()), m.widths_host.data(),
-      static_cast<const int*>(widths.data_ptr()), static_cast<int>(tables.size()), m.c.elem, m.max_width,
-      static_cast<const int64_t*>(row_base.data_ptr()), rowwise ? CUEMBED_ROWWISE_ADAM : CUEMBED_ADAM, Ptr(ids), m.c.idx,
-      Ptr(rows), ids.numel(), m.c.num_rows, m.c.count_word, m.c.words64, m.c.last_id, static_cast<float>(lr), m.c.lr_word,
-      static_cast<float>(bias_factor), bias_word, static_cast<float>(beta1), static_cast<float>(1.0 - beta1),
-      static_cast<float>(beta2), static_cast<float>(1.0 - beta2), static_cast<float>(eps),
-      static_cast<float>(weight_decay), CurrentStream(rows));
+      c.table_host.data(), PointerArray(table_ptrs), a.m_host.data(), PointerArray(exp_avg_ptrs), a.v_host.data(),
+      PointerArray(exp_avg_sq_ptrs), c.widths_host.data(), static_cast<const int*>(widths.data_ptr()),
+      static_cast<int>(tables.size()), c.elem, c.width, static_cast<const int64_t*>(row_base.data_ptr()),
+      rowwise ? CUEMBED_ROWWISE_ADAM : CUEMBED_ADAM, Ptr(ids), c.idx, Ptr(rows), ids.numel(), c.num_rows, c.count_word,
+      c.words64, c.last_id, static_cast<float>(lr), c.lr_word, static_cast<float>(bias_factor), a.bias_word, a.h.beta1,
+      a.h.one_minus_beta1, a.h.beta2, a.h.one_minus_beta2, a.h.eps, a.h.weight_decay, CurrentStream(rows));
 }
+
 
 // Extension (cuembed::PackRowsByOwner): the rank's compressed gradient into the fixed slots of the all-to-all.
 void cuembed_exchange_pack_op(const at::Tensor& ids, const at::Tensor& rows, const c10::optional<at::Tensor>& count,

@@ -384,15 +384,28 @@ def _grouped_count(count, count_word, last_id):
     return dict(count=count if count >= 0 else None)
 
 
+def _group_update_kw(states, rule, lr, eps, lr_device, count, count_word, last_id):
+    """The keywords of sparse_row_update_grouped / _mixed_group from the op's arguments of these names."""
+    return dict(rule=rule, lr=lr if lr_device is None else lr_device, states=list(states) or None, eps=eps,
+                **_grouped_count(count, count_word, last_id))
+
+
+def _group_adam_kw(exp_avg, exp_avg_sq, rowwise, lr, bias_factor, beta1, beta2, eps, weight_decay, lr_device,
+                   bias_factor_device, count, count_word, last_id):
+    """The keywords of sparse_row_adam_grouped / _mixed_group from the op's arguments of these names."""
+    return dict(exp_avg=list(exp_avg), exp_avg_sq=list(exp_avg_sq), lr=lr if lr_device is None else lr_device,
+                bias_factor=bias_factor if bias_factor_device is None else bias_factor_device, betas=(beta1, beta2),
+                eps=eps, weight_decay=weight_decay, rowwise=rowwise, **_grouped_count(count, count_word, last_id))
+
+
 def _sparse_row_update_grouped_impl(tables, table_ptrs, states, state_ptrs, row_base, ids, rows, rule, lr, eps, lr_device,
                                     count, count_word, last_id, stochastic_rounding=False, seeds=None, step=0,
                                     step_device=None):
     from . import grouped as _g, grouped_backward as _gb
-    _gb.sparse_row_update_grouped(_g.TableGroup(tables, table_ptrs=table_ptrs), ids, rows, rule=rule,
-                                  lr=lr if lr_device is None else lr_device, states=list(states) or None, eps=eps,
+    _gb.sparse_row_update_grouped(_g.TableGroup(tables, table_ptrs=table_ptrs), ids, rows,
                                   stochastic_rounding=stochastic_rounding, seeds=seeds,
                                   step=_unsigned(step) if step_device is None else step_device,
-                                  **_grouped_count(count, count_word, last_id))
+                                  **_group_update_kw(states, rule, lr, eps, lr_device, count, count_word, last_id))
 
 
 def _sparse_row_adam_grouped_impl(tables, table_ptrs, exp_avg, exp_avg_ptrs, exp_avg_sq, exp_avg_sq_ptrs, row_base, ids,
@@ -400,32 +413,28 @@ def _sparse_row_adam_grouped_impl(tables, table_ptrs, exp_avg, exp_avg_ptrs, exp
                                   bias_factor_device, count, count_word, last_id, stochastic_rounding=False, seeds=None,
                                   step=0, step_device=None):
     from . import grouped as _g, grouped_backward as _gb
-    _gb.sparse_row_adam_grouped(_g.TableGroup(tables, table_ptrs=table_ptrs), ids, rows, exp_avg=list(exp_avg),
-                                exp_avg_sq=list(exp_avg_sq), lr=lr if lr_device is None else lr_device,
-                                bias_factor=bias_factor if bias_factor_device is None else bias_factor_device,
-                                betas=(beta1, beta2), eps=eps, weight_decay=weight_decay, rowwise=rowwise,
+    _gb.sparse_row_adam_grouped(_g.TableGroup(tables, table_ptrs=table_ptrs), ids, rows,
                                 stochastic_rounding=stochastic_rounding, seeds=seeds,
                                 step=_unsigned(step) if step_device is None else step_device,
-                                **_grouped_count(count, count_word, last_id))
+                                **_group_adam_kw(exp_avg, exp_avg_sq, rowwise, lr, bias_factor, beta1, beta2, eps,
+                                                 weight_decay, lr_device, bias_factor_device, count, count_word, last_id))
 
 
 def _sparse_row_update_mixed_group_impl(tables, table_ptrs, states, state_ptrs, widths, row_base, ids, rows, rule, lr, eps,
                                         lr_device, count, count_word, last_id):
     from . import mixed_group as _mg, mixed_group_sparse_update as _mu
-    _mu.sparse_row_update_mixed_group(_mg.MixedTableGroup(tables, table_ptrs=table_ptrs), ids, rows, rule=rule,
-                                      lr=lr if lr_device is None else lr_device, states=list(states) or None, eps=eps,
-                                      **_grouped_count(count, count_word, last_id))
+    _mu.sparse_row_update_mixed_group(_mg.MixedTableGroup(tables, table_ptrs=table_ptrs), ids, rows,
+                                      **_group_update_kw(states, rule, lr, eps, lr_device, count, count_word, last_id))
 
 
 def _sparse_row_adam_mixed_group_impl(tables, table_ptrs, exp_avg, exp_avg_ptrs, exp_avg_sq, exp_avg_sq_ptrs, widths,
                                       row_base, ids, rows, rowwise, lr, bias_factor, beta1, beta2, eps, weight_decay,
                                       lr_device, bias_factor_device, count, count_word, last_id):
     from . import mixed_group as _mg, mixed_group_sparse_update as _mu
-    _mu.sparse_row_adam_mixed_group(_mg.MixedTableGroup(tables, table_ptrs=table_ptrs), ids, rows, exp_avg=list(exp_avg),
-                                    exp_avg_sq=list(exp_avg_sq), lr=lr if lr_device is None else lr_device,
-                                    bias_factor=bias_factor if bias_factor_device is None else bias_factor_device,
-                                    betas=(beta1, beta2), eps=eps, weight_decay=weight_decay, rowwise=rowwise,
-                                    **_grouped_count(count, count_word, last_id))
+    _mu.sparse_row_adam_mixed_group(_mg.MixedTableGroup(tables, table_ptrs=table_ptrs), ids, rows,
+                                    **_group_adam_kw(exp_avg, exp_avg_sq, rowwise, lr, bias_factor, beta1, beta2, eps,
+                                                     weight_decay, lr_device, bias_factor_device, count, count_word,
+                                                     last_id))
 
 
 def _quantize_rows_impl(table):
@@ -778,11 +787,32 @@ def cuembed_sparse_row_adam_(table, ids, rows, *, exp_avg, exp_avg_sq, lr, bias_
         *args, True, _signed_word("seed", seed), 0 if step_device is not None else _signed_word("step", step), step_device)
 
 
-def _grouped_step_args(group, count, last_id):
-    from . import grouped as _g
-    group = _g._as_group(group)
+def _group_update_args(group, ids, rows, rule, lr, states, eps, count, last_id):
+    """The arguments that the update ops of a same-width and of a mixed-width group share, as (tables to state_ptrs,
+    row_base to last_id): the mixed op takes the widths in between, the grouped op its rounding at the end."""
+    from . import grouped_backward as _gb
     word = count if isinstance(count, torch.Tensor) else None
-    return group, -1 if (count is None or word is not None) else int(count), word
+    lr_device = lr if isinstance(lr, torch.Tensor) else None
+    state_ptrs = None if not states else _gb._state_ptrs(group, states)[1]
+    return ((list(group.tables), group.table_ptrs, list(states or ()), state_ptrs),
+            (group.row_base_device, ids, rows, rule, 0.0 if lr_device is not None else float(lr), float(eps), lr_device,
+             -1 if (count is None or word is not None) else int(count), word, last_id))
+
+
+def _group_adam_args(group, ids, rows, exp_avg, exp_avg_sq, lr, bias_factor, betas, eps, weight_decay, rowwise, count,
+                     last_id):
+    """_group_update_args for the Adam ops: (tables to exp_avg_sq_ptrs, row_base to last_id)."""
+    from . import grouped_backward as _gb
+    word = count if isinstance(count, torch.Tensor) else None
+    lr_device = lr if isinstance(lr, torch.Tensor) else None
+    bias_device = bias_factor if isinstance(bias_factor, torch.Tensor) else None
+    beta1, beta2 = betas
+    return ((list(group.tables), group.table_ptrs, list(exp_avg), _gb._state_ptrs(group, exp_avg)[1], list(exp_avg_sq),
+             _gb._state_ptrs(group, exp_avg_sq)[1]),
+            (group.row_base_device, ids, rows, bool(rowwise), 0.0 if lr_device is not None else float(lr),
+             1.0 if bias_device is not None else float(bias_factor), float(beta1), float(beta2), float(eps),
+             float(weight_decay), lr_device, bias_device, -1 if (count is None or word is not None) else int(count), word,
+             last_id))
 
 
 def _grouped_rounding_args(group, seeds, step):
@@ -803,15 +833,11 @@ def cuembed_sparse_row_update_grouped(group, ids, rows, *, rule, lr, states=None
     """cuembed_amd.sparse_row_update_grouped as the torch op cuembed_pyt::cuembed_sparse_row_update_grouped (in place on the
     group's tables and on `states`; traces under torch.compile).  Same arguments; the op takes the seeds as the int64
     device tensor [num_tables] of their bits, which is built once per tuple of seeds and kept on the group."""
-    from . import grouped_backward as _gb
-    group, host_count, word = _grouped_step_args(group, count, last_id)
-    seeds, step, step_device = _grouped_rounding_args(group, seeds, step)
-    lr_device = lr if isinstance(lr, torch.Tensor) else None
-    state_ptrs = None if not states else _gb._state_ptrs(group, states)[1]
-    torch.ops.cuembed_pyt.cuembed_sparse_row_update_grouped(
-        list(group.tables), group.table_ptrs, list(states or ()), state_ptrs, group.row_base_device, ids, rows, rule,
-        0.0 if lr_device is not None else float(lr), float(eps), lr_device, host_count, word, last_id,
-        bool(stochastic_rounding), seeds, step, step_device)
+    from . import grouped as _g
+    group = _g._as_group(group)
+    rounding = _grouped_rounding_args(group, seeds, step)
+    head, tail = _group_update_args(group, ids, rows, rule, lr, states, eps, count, last_id)
+    torch.ops.cuembed_pyt.cuembed_sparse_row_update_grouped(*head, *tail, bool(stochastic_rounding), *rounding)
 
 
 def cuembed_sparse_row_adam_grouped(group, ids, rows, *, exp_avg, exp_avg_sq, lr, bias_factor=1.0, betas=(0.9, 0.999),
@@ -819,56 +845,33 @@ def cuembed_sparse_row_adam_grouped(group, ids, rows, *, exp_avg, exp_avg_sq, lr
                                     stochastic_rounding=False, seeds=None, step=0):
     """cuembed_amd.sparse_row_adam_grouped as the torch op cuembed_pyt::cuembed_sparse_row_adam_grouped (in place on the
     group's tables, `exp_avg` and `exp_avg_sq`; traces under torch.compile).  Same arguments."""
-    from . import grouped_backward as _gb
-    group, host_count, word = _grouped_step_args(group, count, last_id)
-    seeds, step, step_device = _grouped_rounding_args(group, seeds, step)
-    lr_device = lr if isinstance(lr, torch.Tensor) else None
-    bias_device = bias_factor if isinstance(bias_factor, torch.Tensor) else None
-    beta1, beta2 = betas
-    torch.ops.cuembed_pyt.cuembed_sparse_row_adam_grouped(
-        list(group.tables), group.table_ptrs, list(exp_avg), _gb._state_ptrs(group, exp_avg)[1], list(exp_avg_sq),
-        _gb._state_ptrs(group, exp_avg_sq)[1], group.row_base_device, ids, rows, bool(rowwise),
-        0.0 if lr_device is not None else float(lr), 1.0 if bias_device is not None else float(bias_factor), float(beta1),
-        float(beta2), float(eps), float(weight_decay), lr_device, bias_device, host_count, word, last_id,
-        bool(stochastic_rounding), seeds, step, step_device)
-
-
-def _mixed_step_args(group, count):
-    from . import mixed_group as _mg
-    if not isinstance(group, _mg.MixedTableGroup):
-        group = _mg.MixedTableGroup(group)
-    word = count if isinstance(count, torch.Tensor) else None
-    return group, -1 if (count is None or word is not None) else int(count), word
+    from . import grouped as _g
+    group = _g._as_group(group)
+    rounding = _grouped_rounding_args(group, seeds, step)
+    head, tail = _group_adam_args(group, ids, rows, exp_avg, exp_avg_sq, lr, bias_factor, betas, eps, weight_decay, rowwise,
+                                  count, last_id)
+    torch.ops.cuembed_pyt.cuembed_sparse_row_adam_grouped(*head, *tail, bool(stochastic_rounding), *rounding)
 
 
 def cuembed_sparse_row_update_mixed_group(group, ids, rows, *, rule, lr, states=None, eps=1e-8, count=None, last_id=None):
     """cuembed_amd.sparse_row_update_mixed_group as the torch op cuembed_pyt::cuembed_sparse_row_update_mixed_group (in
     place on the group's tables and on `states`; traces under torch.compile).  Same arguments; the device arrays of the
     state pointers and of the widths are built once and kept on the group."""
-    from . import grouped_backward as _gb, mixed_group_sparse_update as _mu
-    group, host_count, word = _mixed_step_args(group, count)
-    lr_device = lr if isinstance(lr, torch.Tensor) else None
-    state_ptrs = None if not states else _gb._state_ptrs(group, states)[1]
-    torch.ops.cuembed_pyt.cuembed_sparse_row_update_mixed_group(
-        list(group.tables), group.table_ptrs, list(states or ()), state_ptrs, _mu._widths_device(group),
-        group.row_base_device, ids, rows, rule, 0.0 if lr_device is not None else float(lr), float(eps), lr_device,
-        host_count, word, last_id)
+    from . import mixed_group as _mg, mixed_group_sparse_update as _mu
+    group = _mg._as_mixed_group(group)
+    head, tail = _group_update_args(group, ids, rows, rule, lr, states, eps, count, last_id)
+    torch.ops.cuembed_pyt.cuembed_sparse_row_update_mixed_group(*head, _mu._widths_device(group), *tail)
 
 
 def cuembed_sparse_row_adam_mixed_group(group, ids, rows, *, exp_avg, exp_avg_sq, lr, bias_factor=1.0, betas=(0.9, 0.999),
                                         eps=1e-8, weight_decay=0.0, rowwise=False, count=None, last_id=None):
     """cuembed_amd.sparse_row_adam_mixed_group as the torch op cuembed_pyt::cuembed_sparse_row_adam_mixed_group (in place
     on the group's tables, `exp_avg` and `exp_avg_sq`; traces under torch.compile).  Same arguments."""
-    from . import grouped_backward as _gb, mixed_group_sparse_update as _mu
-    group, host_count, word = _mixed_step_args(group, count)
-    lr_device = lr if isinstance(lr, torch.Tensor) else None
-    bias_device = bias_factor if isinstance(bias_factor, torch.Tensor) else None
-    beta1, beta2 = betas
-    torch.ops.cuembed_pyt.cuembed_sparse_row_adam_mixed_group(
-        list(group.tables), group.table_ptrs, list(exp_avg), _gb._state_ptrs(group, exp_avg)[1], list(exp_avg_sq),
-        _gb._state_ptrs(group, exp_avg_sq)[1], _mu._widths_device(group), group.row_base_device, ids, rows, bool(rowwise),
-        0.0 if lr_device is not None else float(lr), 1.0 if bias_device is not None else float(bias_factor), float(beta1),
-        float(beta2), float(eps), float(weight_decay), lr_device, bias_device, host_count, word, last_id)
+    from . import mixed_group as _mg, mixed_group_sparse_update as _mu
+    group = _mg._as_mixed_group(group)
+    head, tail = _group_adam_args(group, ids, rows, exp_avg, exp_avg_sq, lr, bias_factor, betas, eps, weight_decay, rowwise,
+                                  count, last_id)
+    torch.ops.cuembed_pyt.cuembed_sparse_row_adam_mixed_group(*head, _mu._widths_device(group), *tail)
 
 
 def quantize_rows(table):

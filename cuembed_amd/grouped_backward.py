@@ -37,8 +37,9 @@ import ctypes
 import torch
 
 from . import _lib
-from .group_layout import INT_MAX, check_weights, group_batch_layout, mean_scale_layout
+from .group_layout import INT_MAX, check_weights, group_batch_layout, mean_scale_layout, mixed_lane_bytes
 from .grouped import _as_group
+from .mixed_group import MixedTableGroup
 from .ops import (ADAM_RULES, UPDATE_RULES, _ELEM, _INDEX, _check_alignment, _check_betas, _check_dev, _entry_counts,
                   _index_code, _ptr, _stream, embedding_backward, transpose)
 
@@ -403,13 +404,14 @@ def _check_step(seeds, step):
     return step, None
 
 
-def _step_group(group, ids, rows, stochastic_rounding, seeds=None):
-    """What both grouped steps check first, without the GPU: the group, the rounding, ids and rows.  Returns (group, index
-    code, n, seeds)."""
-    group = _as_group(group)
-    if group.quantized:
-        raise TypeError("a group of fused 8-bit tables has no optimizer step: quantized tables are inference only")
-    seeds = _check_seeds(group, stochastic_rounding, seeds)
+def _step_group(group, ids, rows, stochastic_rounding, seeds, step):
+    """What every step on a group checks first, without the GPU: the group -- a TableGroup or a MixedTableGroup, made by
+    the caller from its argument --, the rounding, ids and rows.  Returns (index code, n, seeds, step, step word)."""
+    mixed = isinstance(group, MixedTableGroup)
+    if not mixed:
+        if group.quantized:
+            raise TypeError("a group of fused 8-bit tables has no optimizer step: quantized tables are inference only")
+        seeds = _check_seeds(group, stochastic_rounding, seeds)
     if group.num_tables > MAX_GROUPED_STEP_TABLES:
         raise ValueError("a grouped step takes at most %d tables, the group has %d"
                          % (MAX_GROUPED_STEP_TABLES, group.num_tables))
@@ -419,24 +421,30 @@ def _step_group(group, ids, rows, stochastic_rounding, seeds=None):
     it = _index_code("ids", ids)
     if rows.dtype != group.dtype:
         raise TypeError("rows must have the tables' dtype (%s), got %s" % (group.dtype, rows.dtype))
-    if rows.dim() != 2 or rows.shape[1] != group.width:
-        raise ValueError("rows must be [entries, width = %d], got %r" % (group.width, tuple(rows.shape)))
-    if (group.width * rows.element_size()) % 4 != 0:
-        raise ValueError("the row size must be a multiple of 4 bytes")
+    if mixed:       # (every row of a MixedTableGroup is a multiple of 4 bytes: the group has checked that)
+        if rows.dim() != 2 or rows.shape[1] != max(group.widths):
+            raise ValueError("rows must be [entries, W_max = %d], padded to the widest table (a ragged gradient layout is "
+                             "not taken), got %r" % (max(group.widths), tuple(rows.shape)))
+    else:
+        if rows.dim() != 2 or rows.shape[1] != group.width:
+            raise ValueError("rows must be [entries, width = %d], got %r" % (group.width, tuple(rows.shape)))
+        if (group.width * rows.element_size()) % 4 != 0:
+            raise ValueError("the row size must be a multiple of 4 bytes")
     if ids.dim() != 1 or rows.shape[0] != ids.numel():
         raise ValueError("ids must hold one entry per row of rows: %d ids, %d rows" % (ids.numel(), rows.shape[0]))
-    return group, it, ids.numel(), seeds
+    return (it, ids.numel(), seeds) + _check_step(seeds, step)
 
 
 def _check_group_states(group, name, states, rowwise):
-    """`states`: a sequence of num_tables float32 tensors, [rows_t, width] or (rowwise) [rows_t]."""
+    """`states`: a sequence of num_tables float32 tensors, [rows_t, width of table t] or (rowwise) [rows_t]."""
     if isinstance(states, torch.Tensor) or not isinstance(states, (list, tuple)):
         raise TypeError("%s must be a sequence of %d float32 tensors, one per table" % (name, group.num_tables))
     if len(states) != group.num_tables:
         raise ValueError("%s must hold one tensor per table: the group has %d tables, got %d"
                          % (name, group.num_tables, len(states)))
-    for t, (s, n) in enumerate(zip(states, group.row_counts)):
-        want = (n,) if rowwise else (n, group.width)
+    widths = group.widths if isinstance(group, MixedTableGroup) else (group.width,) * group.num_tables
+    for t, (s, n, w) in enumerate(zip(states, group.row_counts, widths)):
+        want = (n,) if rowwise else (n, w)
         if not isinstance(s, torch.Tensor):
             raise TypeError("%s[%d] must be a float32 tensor of shape %r" % (name, t, want))
         if s.dtype != torch.float32:
@@ -479,6 +487,94 @@ def _step_devices(group, named):
             _check_dev(name, t, group.device)
 
 
+def _check_mixed_alignment(group, rows_ptr, per_element):
+    """ValueError where the library would abort because NO lane width serves a step on a mixed-width group: a table base
+    or rows that is not 4-byte aligned (mixed_lane_bytes says so), or a per-element state base (`per_element`: (name, OR
+    of the bases) pairs) that the narrowest lane, 4 bytes of a row, cannot move as fp32 words.  Which lane width the
+    launch gets is the library's to decide (detail::MixedGroupUpdateLaneBytes; mixed_group_update_launch_shape reports
+    it): nothing here repeats that rule."""
+    size = group.tables[0].element_size()
+    mixed_lane_bytes(group.widths, size,
+                     tuple(("tables[%d]" % k, p) for k, p in enumerate(group.host_ptrs)) + (("rows", rows_ptr),))
+    align = 4 * (4 // size)
+    for name, p in per_element:
+        if int(p) % align:
+            raise ValueError("%s must be %d-byte aligned for a table of %d-byte elements: the narrowest lane moves that "
+                             "much of it" % (name, align, size))
+
+
+def _step_args(group, ids, rows, checked, rule_code, state_lists, count, last_id, words, floats):
+    """What is left of a step on a group once its rule, state tensors and hyper-parameters are in order: the count source
+    and the device words, then the devices, the pointer arrays of the state, the alignment.  `checked`: what _step_group
+    returned; `state_lists`: (name, tensors or None, per element?) of the rule's state tensors; `words`: (name, value) of
+    the hyper-parameters that may be one-element device tensors; `floats`: the ones that may not, as the C call orders them.
+    Returns None where there is no entry to step, else the arguments of the C call as (head, tail, rounding): the tables
+    and the state | num_tables to the last float | (seeds, step, step word) of a stochastic step, else ().  A mixed-width
+    call puts its widths between head and tail; the stream comes last."""
+    it, n, seeds, step, step_word = checked
+    num_rows, count_word, words64, _, _ = _entry_counts(ids, count, last_id, None, None)
+    words = tuple((name,) + _word(name, value, torch.float32) for name, value in words)
+    # ---- the call is in order: now the devices
+    _step_devices(group, (("ids", ids), ("rows", rows), ("count", count_word), ("last_id", last_id)) +
+                  tuple((name, word) for name, _, word in words) +
+                  (("step", step_word), ("seeds", seeds if isinstance(seeds, torch.Tensor) else None)) +
+                  tuple(("%s[%d]" % (name, t), s) for name, states, _ in state_lists for t, s in enumerate(states or ())))
+    head = (group._host_array, _ptr(group.table_ptrs))
+    per_element = ()
+    for name, states, aligned in state_lists:
+        host, dev, bits = (None, None, 0) if states is None else _state_ptrs(group, states)
+        head += (host, _ptr(dev))
+        if aligned:
+            per_element += ((name, bits),)
+    if isinstance(group, MixedTableGroup):
+        width = max(group.widths)
+        _check_mixed_alignment(group, rows.data_ptr(), per_element)
+    else:
+        width = group.width
+        _check_alignment("tables", _or(group.host_ptrs), rows.element_size(), width, others=(("rows", rows.data_ptr()),),
+                         state=per_element, max_lanes=None)
+    if n == 0:
+        return None
+    tail = (group.num_tables, _ELEM[group.dtype], width, _ptr(group.row_base_device), rule_code, _ptr(ids), it, _ptr(rows),
+            n, int(num_rows), _ptr(count_word), int(words64), _ptr(last_id))
+    for _, value, word in words:
+        tail += (value, _ptr(word))
+    tail += tuple(float(f) for f in floats)
+    return head, tail, () if seeds is None else (_ptr(_seeds_tensor(group, seeds)), step, _ptr(step_word))
+
+
+def _update_step(group, ids, rows, rule, lr, states, eps, count, last_id, stochastic_rounding=False, seeds=None, step=0):
+    """sparse_row_update on a TableGroup or a MixedTableGroup, up to the C call: everything validated, its arguments as
+    _step_args returns them."""
+    checked = _step_group(group, ids, rows, stochastic_rounding, seeds, step)
+    if rule not in UPDATE_RULES:
+        raise ValueError("rule must be one of %r, got %r" % (sorted(UPDATE_RULES), rule))
+    if rule == "sgd":
+        if states is not None:
+            raise ValueError("rule='sgd' takes no states")
+    else:
+        states = _check_group_states(group, "states", states, rule == "rowwise_adagrad")
+    return _step_args(group, ids, rows, checked, UPDATE_RULES[rule], (("states", states, rule == "adagrad"),), count,
+                      last_id, (("lr", lr),), (eps,))
+
+
+def _adam_step(group, ids, rows, exp_avg, exp_avg_sq, lr, bias_factor, betas, eps, weight_decay, rowwise, count, last_id,
+               stochastic_rounding=False, seeds=None, step=0):
+    """sparse_row_adam on a TableGroup or a MixedTableGroup, up to the C call: as _update_step."""
+    checked = _step_group(group, ids, rows, stochastic_rounding, seeds, step)
+    exp_avg = _check_group_states(group, "exp_avg", exp_avg, False)
+    exp_avg_sq = _check_group_states(group, "exp_avg_sq", exp_avg_sq, bool(rowwise))
+    beta1, beta2 = _check_betas(betas)
+    if not float(eps) >= 0.0:
+        raise ValueError("eps must not be negative, got %r" % (eps,))
+    if not float(weight_decay) >= 0.0:
+        raise ValueError("weight_decay must not be negative, got %r" % (weight_decay,))
+    return _step_args(group, ids, rows, checked, ADAM_RULES["rowwise_adam" if rowwise else "adam"],
+                      (("exp_avg", exp_avg, True), ("exp_avg_sq", exp_avg_sq, not rowwise)), count, last_id,
+                      (("lr", lr), ("bias_factor", bias_factor)),
+                      (beta1, 1.0 - beta1, beta2, 1.0 - beta2, eps, weight_decay))
+
+
 def sparse_row_update_grouped(group, ids, rows, *, rule, lr, states=None, eps=1e-8, count=None, last_id=None,
                               stochastic_rounding=False, seeds=None, step=0):
     """sparse_row_update on a group of SEPARATE table tensors, in ONE launch (cuembed::SparseRowUpdateGrouped): (ids, rows)
@@ -507,42 +603,14 @@ def sparse_row_update_grouped(group, ids, rows, *, rule, lr, states=None, eps=1e
     these seeds and kept on the group.
     Everything is validated before the launch; nothing is read back, so the call can be captured into a HIP graph (the
     pointer arrays of `states` are built at the first call with these tensors and kept on the group)."""
-    group, it, n, seeds = _step_group(group, ids, rows, stochastic_rounding, seeds)
-    step, step_word = _check_step(seeds, step)
-    if rule not in UPDATE_RULES:
-        raise ValueError("rule must be one of %r, got %r" % (sorted(UPDATE_RULES), rule))
-    if rule == "sgd":
-        if states is not None:
-            raise ValueError("rule='sgd' takes no states")
-    else:
-        states = _check_group_states(group, "states", states, rule == "rowwise_adagrad")
-    num_rows, count_word, words64, _, _ = _entry_counts(ids, count, last_id, None, None)
-    lr, lr_word = _word("lr", lr, torch.float32)
-    # ---- the call is in order: now the devices
-    _step_devices(group, (("ids", ids), ("rows", rows), ("count", count_word), ("last_id", last_id), ("lr", lr_word),
-                          ("step", step_word), ("seeds", seeds if isinstance(seeds, torch.Tensor) else None)) +
-                  tuple(("states[%d]" % t, s) for t, s in enumerate(states or ())))
-    host = dev = None
-    state_bits = ()
-    if states is not None:
-        host, dev, bits = _state_ptrs(group, states)
-        state_bits = (("states", bits),) if rule == "adagrad" else ()
-    _check_alignment("tables", _or(group.host_ptrs), rows.element_size(), group.width,
-                     others=(("rows", rows.data_ptr()),), state=state_bits, max_lanes=None)
-    if n == 0:
-        return None
-    with torch.cuda.device(group.device):
-        if seeds is not None:
-            _lib.lib().cuembed_sparse_row_update_grouped_stochastic(
-                group._host_array, _ptr(group.table_ptrs), host, _ptr(dev), group.num_tables, _ELEM[group.dtype],
-                group.width, _ptr(group.row_base_device), UPDATE_RULES[rule], _ptr(ids), it, _ptr(rows), n, int(num_rows),
-                _ptr(count_word), int(words64), _ptr(last_id), lr, _ptr(lr_word), float(eps),
-                _ptr(_seeds_tensor(group, seeds)), step, _ptr(step_word), _stream(rows))
-            return None
-        _lib.lib().cuembed_sparse_row_update_grouped(
-            group._host_array, _ptr(group.table_ptrs), host, _ptr(dev), group.num_tables, _ELEM[group.dtype], group.width,
-            _ptr(group.row_base_device), UPDATE_RULES[rule], _ptr(ids), it, _ptr(rows), n, int(num_rows), _ptr(count_word),
-            int(words64), _ptr(last_id), lr, _ptr(lr_word), float(eps), _stream(rows))
+    group = _as_group(group)
+    call = _update_step(group, ids, rows, rule, lr, states, eps, count, last_id, stochastic_rounding, seeds, step)
+    if call is not None:
+        head, tail, rounding = call
+        lib = _lib.lib()
+        step_fn = lib.cuembed_sparse_row_update_grouped_stochastic if rounding else lib.cuembed_sparse_row_update_grouped
+        with torch.cuda.device(group.device):
+            step_fn(*head, *tail, *rounding, _stream(rows))
     return None
 
 
@@ -557,47 +625,15 @@ def sparse_row_adam_grouped(group, ids, rows, *, exp_avg, exp_avg_sq, lr, bias_f
     group's lane width.  stochastic_rounding=True, seeds=[...], step: as in sparse_row_update_grouped -- one seed per table,
     the bits of num_tables sparse_row_adam(stochastic_rounding=True, seed=seeds[t], step=step) calls.  Nothing is read
     back."""
-    group, it, n, seeds = _step_group(group, ids, rows, stochastic_rounding, seeds)
-    step, step_word = _check_step(seeds, step)
-    exp_avg = _check_group_states(group, "exp_avg", exp_avg, False)
-    exp_avg_sq = _check_group_states(group, "exp_avg_sq", exp_avg_sq, bool(rowwise))
-    beta1, beta2 = _check_betas(betas)
-    if not float(eps) >= 0.0:
-        raise ValueError("eps must not be negative, got %r" % (eps,))
-    if not float(weight_decay) >= 0.0:
-        raise ValueError("weight_decay must not be negative, got %r" % (weight_decay,))
-    num_rows, count_word, words64, _, _ = _entry_counts(ids, count, last_id, None, None)
-    lr, lr_word = _word("lr", lr, torch.float32)
-    bias_factor, bias_word = _word("bias_factor", bias_factor, torch.float32)
-    # ---- the call is in order: now the devices
-    _step_devices(group, (("ids", ids), ("rows", rows), ("count", count_word), ("last_id", last_id), ("lr", lr_word),
-                          ("bias_factor", bias_word), ("step", step_word),
-                          ("seeds", seeds if isinstance(seeds, torch.Tensor) else None)) +
-                  tuple(("exp_avg[%d]" % t, s) for t, s in enumerate(exp_avg)) +
-                  tuple(("exp_avg_sq[%d]" % t, s) for t, s in enumerate(exp_avg_sq)))
-    m_host, m_dev, m_bits = _state_ptrs(group, exp_avg)
-    v_host, v_dev, v_bits = _state_ptrs(group, exp_avg_sq)
-    _check_alignment("tables", _or(group.host_ptrs), rows.element_size(), group.width,
-                     others=(("rows", rows.data_ptr()),),
-                     state=(("exp_avg", m_bits),) + ((("exp_avg_sq", v_bits),) if not rowwise else ()), max_lanes=None)
-    if n == 0:
-        return None
-    with torch.cuda.device(group.device):
-        if seeds is not None:
-            _lib.lib().cuembed_sparse_row_adam_grouped_stochastic(
-                group._host_array, _ptr(group.table_ptrs), m_host, _ptr(m_dev), v_host, _ptr(v_dev), group.num_tables,
-                _ELEM[group.dtype], group.width, _ptr(group.row_base_device),
-                ADAM_RULES["rowwise_adam" if rowwise else "adam"], _ptr(ids), it, _ptr(rows), n, int(num_rows),
-                _ptr(count_word), int(words64), _ptr(last_id), lr, _ptr(lr_word), bias_factor, _ptr(bias_word), beta1,
-                1.0 - beta1, beta2, 1.0 - beta2, float(eps), float(weight_decay), _ptr(_seeds_tensor(group, seeds)), step,
-                _ptr(step_word), _stream(rows))
-            return None
-        _lib.lib().cuembed_sparse_row_adam_grouped(
-            group._host_array, _ptr(group.table_ptrs), m_host, _ptr(m_dev), v_host, _ptr(v_dev), group.num_tables,
-            _ELEM[group.dtype], group.width, _ptr(group.row_base_device),
-            ADAM_RULES["rowwise_adam" if rowwise else "adam"], _ptr(ids), it, _ptr(rows), n, int(num_rows),
-            _ptr(count_word), int(words64), _ptr(last_id), lr, _ptr(lr_word), bias_factor, _ptr(bias_word), beta1,
-            1.0 - beta1, beta2, 1.0 - beta2, float(eps), float(weight_decay), _stream(rows))
+    group = _as_group(group)
+    call = _adam_step(group, ids, rows, exp_avg, exp_avg_sq, lr, bias_factor, betas, eps, weight_decay, rowwise, count,
+                      last_id, stochastic_rounding, seeds, step)
+    if call is not None:
+        head, tail, rounding = call
+        lib = _lib.lib()
+        step_fn = lib.cuembed_sparse_row_adam_grouped_stochastic if rounding else lib.cuembed_sparse_row_adam_grouped
+        with torch.cuda.device(group.device):
+            step_fn(*head, *tail, *rounding, _stream(rows))
     return None
 
 

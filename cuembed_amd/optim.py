@@ -243,9 +243,15 @@ class SparseAdamUpdater(_CompressedGradientStep):
             self.rounding_step.add_(1)      # on the device, after the kernel in stream order: one apply = one step
 
 
-class _GroupedGradientStep:
-    """The index path shared by GroupSparseUpdater and GroupSparseAdamUpdater: the grouped backward in its compressed form
-    -- global ids, rows, the count left on the device -- handed to self.apply(grad).  Needs self.group."""
+class _GroupGradientStep:
+    """The index path shared by the four group updaters: the group's backward in its compressed form -- global ids, rows,
+    the count left on the device -- handed to self.apply(grad).  As it stands it serves a TableGroup; _MixedGroupStep
+    names what a MixedTableGroup has instead: the backward, the gradient's type, the two steps."""
+
+    _backward = staticmethod(_grouped_backward.embedding_backward_grouped)
+    _grad_type, _grad_from = _grouped_backward.GroupedGrad, "GroupedGrad of embedding_backward_grouped(dense=False)"
+    _update_step = staticmethod(_grouped_backward.sparse_row_update_grouped)
+    _adam_step = staticmethod(_grouped_backward.sparse_row_adam_grouped)
 
     def _init_group(self, group, stochastic_rounding, seeds):
         group = _grouped._as_group(group)
@@ -261,38 +267,70 @@ class _GroupedGradientStep:
             if group.device.type == "cuda":
                 _grouped_backward._seeds_tensor(group, self.seeds)
 
+    def _device_arrays(self, *state_lists):
+        """The pointer arrays and row_base on the device, now: the first apply may be under capture."""
+        if self.group.device.type == "cuda":
+            for states in state_lists:
+                _grouped_backward._state_ptrs(self.group, states)
+            self.group.row_base_device
+
     def _rounding(self):
-        """The rounding keywords of one grouped step."""
+        """The rounding keywords of one step."""
         if not self.stochastic_rounding:
             return {}
         return dict(stochastic_rounding=True, seeds=self.seeds, step=self.rounding_step)
 
     def backward_and_apply(self, grad_y, idx, offsets=None, weights=None, mode="sum"):
-        """The backward of out = embedding_forward_grouped(group, idx, offsets, weights, mode=mode) and the step, in one
-        go: embedding_backward_grouped(dense=False) -- keys, ONE sort, ONE scatter-add, the entry count left on the device
-        -- then the grouped step, which reads the count itself.  grad_y [batch, num_tables, width] of the tables' dtype;
-        idx [nnz] with offsets [num_tables * batch + 1] (CSR), or idx [num_tables, batch, hotness] with offsets=None.  No
-        host read-back: forward + backward_and_apply on separate tensors can be captured into a HIP graph."""
+        """The backward of out = embedding_forward_grouped(group, idx, offsets, weights, mode=mode) -- of a mixed-width
+        group: embedding_forward_mixed_group -- and the step, in one go: embedding_backward_grouped(dense=False) /
+        embedding_backward_mixed_group -- keys, ONE sort, ONE scatter-add, the entry count left on the device -- then the
+        group's step, which reads the count itself.  grad_y [batch, num_tables, width] (mixed widths: [batch,
+        embedding_dim]) of the tables' dtype; idx [nnz] with offsets [num_tables * batch + 1] (CSR), or idx [num_tables,
+        batch, hotness] with offsets=None.  No host read-back: forward + backward_and_apply on separate tensors can be
+        captured into a HIP graph (a mixed-width group after one warm call, which builds its small device arrays)."""
         hot = 0
         if offsets is None:
             if idx.dim() != 3:
                 raise ValueError("without offsets, idx must be [num_tables, batch, hotness]")
             hot = idx.shape[2]
-        grad = _grouped_backward.embedding_backward_grouped(self.group, grad_y, idx, offsets, weights, num_hots=hot,
-                                                            mode=mode)
+        grad = self._backward(self.group, grad_y, idx, offsets, weights, num_hots=hot, mode=mode)
         self.apply(grad)
         return grad
 
     def _check_grad(self, grad):
+        widths = getattr(self.group, "widths", None)        # (of a mixed-width group)
         # (a MixedGroupedGrad is a GroupedGrad whose rows are padded to the widest table: not what the grouped step reads)
-        if not isinstance(grad, _grouped_backward.GroupedGrad) or isinstance(grad, MixedGroupedGrad):
-            raise TypeError("apply takes the GroupedGrad of embedding_backward_grouped(dense=False), got %s"
-                            % type(grad).__name__)
-        if grad.row_base != self.group.row_base:
-            raise ValueError("the gradient belongs to a group with other row counts")
+        if not isinstance(grad, self._grad_type) or (widths is None and isinstance(grad, MixedGroupedGrad)):
+            raise TypeError("apply takes the %s, got %s" % (self._grad_from, type(grad).__name__))
+        if grad.row_base != self.group.row_base or (widths is not None and grad.widths != widths):
+            raise ValueError("the gradient belongs to a group with other row counts" + (" or widths" if widths else ""))
 
 
-class GroupSparseUpdater(_GroupedGradientStep):
+class _MixedGroupStep:
+    """What the updaters of a MixedTableGroup have in place of _GroupGradientStep's: the mixed-width backward -- rows padded
+    to the widest table --, its gradient, the mixed steps; no stochastic rounding."""
+
+    _backward = staticmethod(_mixed_group_backward.embedding_backward_mixed_group)
+    _grad_type, _grad_from = MixedGroupedGrad, "MixedGroupedGrad of embedding_backward_mixed_group"
+    _update_step = staticmethod(_mixed_step.sparse_row_update_mixed_group)
+    _adam_step = staticmethod(_mixed_step.sparse_row_adam_mixed_group)
+
+    def _init_group(self, group, stochastic_rounding, seeds):
+        if stochastic_rounding:
+            raise ValueError("the optimizer step of a mixed-width group rounds to nearest: stochastic rounding is not "
+                             "available for a MixedTableGroup")
+        self.group = _mixed_group._as_mixed_group(group)
+        self.seeds = self.rounding_step = None
+        self.stochastic_rounding = False
+
+    def _device_arrays(self, *state_lists):
+        """The pointer arrays, the widths and row_base on the device, now: the first apply may be under capture."""
+        super()._device_arrays(*state_lists)
+        if self.group.device.type == "cuda":
+            _mixed_step._widths_device(self.group)
+
+
+class GroupSparseUpdater(_GroupGradientStep):
     """SparseUpdater for a TableGroup (or a list of tables) of SEPARATE tensors: applies a GroupedGrad to all tables in ONE
     launch (cuembed_amd.grouped_backward.sparse_row_update_grouped) and owns the state, `.states`: None ("sgd") or one
     fp32 tensor per table, [rows_t, width] ("adagrad") or [rows_t] ("rowwise_adagrad").  lr: a float or a one-element
@@ -315,21 +353,19 @@ class GroupSparseUpdater(_GroupedGradientStep):
         self.states = None
         if rule != "sgd":
             self.states = tuple(_new_state(t, rule, initial_accumulator_value) for t in self.group.tables)
-            if self.group.device.type == "cuda":     # the pointer arrays, now: the first apply may be under capture
-                _grouped_backward._state_ptrs(self.group, self.states)
-                self.group.row_base_device
+        self._device_arrays(*(() if self.states is None else (self.states,)))
 
     def apply(self, grad):
-        """tables[t][r] (and its state) <- rule, for the valid entries of a GroupedGrad.  Nothing is read back."""
+        """tables[t][r] (and its state) <- rule, for the valid entries of the group's gradient -- a GroupedGrad, or the
+        MixedGroupedGrad of a mixed-width group, of which rows[k, :W_t] is read.  Nothing is read back."""
         self._check_grad(grad)
-        _grouped_backward.sparse_row_update_grouped(self.group, grad.ids, grad.rows, rule=self.rule, lr=self.lr,
-                                                    states=self.states, eps=self.eps, last_id=grad.last_id,
-                                                    **self._rounding())
+        self._update_step(self.group, grad.ids, grad.rows, rule=self.rule, lr=self.lr, states=self.states, eps=self.eps,
+                          last_id=grad.last_id, **self._rounding())
         if self.stochastic_rounding:
             self.rounding_step.add_(1)      # on the device, after the kernel in stream order: one apply = one step
 
 
-class GroupSparseAdamUpdater(_GroupedGradientStep):
+class GroupSparseAdamUpdater(_GroupGradientStep):
     """SparseAdamUpdater for a TableGroup of SEPARATE tensors: one launch for the clock, one for all tables
     (cuembed_amd.grouped_backward.sparse_row_adam_grouped).  Owns `.exp_avg` and `.exp_avg_sq`, one fp32 tensor per table
     each ([rows_t, width]; exp_avg_sq [rows_t] with rowwise=True), and ONE bias-factor clock for the group (`.powers`,
@@ -355,93 +391,32 @@ class GroupSparseAdamUpdater(_GroupedGradientStep):
         self.powers = torch.tensor([0.0, 1.0, 1.0], dtype=torch.float64, device=dev)
         self.bias_factor = torch.ones((1,), dtype=torch.float32, device=dev)
         self._one = None if self.bias_correction else torch.ones((1,), dtype=torch.float32, device=dev)
-        if dev.type == "cuda":     # the pointer arrays, now: the first apply may be under capture
-            _grouped_backward._state_ptrs(self.group, self.exp_avg)
-            _grouped_backward._state_ptrs(self.group, self.exp_avg_sq)
-            self.group.row_base_device
+        self._device_arrays(self.exp_avg, self.exp_avg_sq)
 
     def apply(self, grad):
-        """One Adam step on the valid entries of a GroupedGrad: the clock moves on, then the grouped step."""
+        """One Adam step on the valid entries of the group's gradient (a GroupedGrad, or the MixedGroupedGrad of a
+        mixed-width group): the clock moves on, then the group's step."""
         self._check_grad(grad)
         _ops.adam_clock_advance(self.powers, self.bias_factor, self.betas)
-        _grouped_backward.sparse_row_adam_grouped(
-            self.group, grad.ids, grad.rows, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, lr=self.lr,
-            bias_factor=self.bias_factor if self.bias_correction else self._one, betas=self.betas, eps=self.eps,
-            weight_decay=self.weight_decay, rowwise=self.rowwise, last_id=grad.last_id, **self._rounding())
+        self._adam_step(self.group, grad.ids, grad.rows, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, lr=self.lr,
+                        bias_factor=self.bias_factor if self.bias_correction else self._one, betas=self.betas,
+                        eps=self.eps, weight_decay=self.weight_decay, rowwise=self.rowwise, last_id=grad.last_id,
+                        **self._rounding())
         if self.stochastic_rounding:
             self.rounding_step.add_(1)      # on the device, after the kernel in stream order: one apply = one step
 
 
-class _MixedGroupGradientStep:
-    """The index path shared by MixedGroupSparseUpdater and MixedGroupSparseAdamUpdater: the mixed-width backward -- global
-    ids, rows padded to the widest table, the count left on the device -- handed to self.apply(grad).  Needs self.group."""
-
-    def _init_group(self, group, stochastic_rounding):
-        if stochastic_rounding:
-            raise ValueError("the optimizer step of a mixed-width group rounds to nearest: stochastic rounding is not "
-                             "available for a MixedTableGroup")
-        self.group = _mixed_group._as_mixed_group(group)
-
-    def _device_arrays(self, *state_lists):
-        """The pointer arrays, the widths and row_base on the device, now: the first apply may be under capture."""
-        if self.group.device.type != "cuda":
-            return
-        for states in state_lists:
-            _grouped_backward._state_ptrs(self.group, states)
-        _mixed_step._widths_device(self.group)
-        self.group.row_base_device
-
-    def backward_and_apply(self, grad_y, idx, offsets=None, weights=None, mode="sum"):
-        """The backward of out = embedding_forward_mixed_group(group, idx, offsets, weights, mode=mode) and the step, in one
-        go: embedding_backward_mixed_group -- keys, ONE sort, ONE scatter-add, the entry count left on the device -- then
-        the mixed step, which reads the count itself.  grad_y [batch, embedding_dim] of the tables' dtype; idx [nnz] with
-        offsets [num_tables * batch + 1] (CSR), or idx [num_tables, batch, hotness] with offsets=None.  No host
-        read-back: forward + backward_and_apply on separate tensors of different widths can be captured into a HIP
-        graph (after one warm call, which builds the group's small device arrays)."""
-        hot = 0
-        if offsets is None:
-            if idx.dim() != 3:
-                raise ValueError("without offsets, idx must be [num_tables, batch, hotness]")
-            hot = idx.shape[2]
-        grad = _mixed_group_backward.embedding_backward_mixed_group(self.group, grad_y, idx, offsets, weights,
-                                                                    num_hots=hot, mode=mode)
-        self.apply(grad)
-        return grad
-
-    def _check_grad(self, grad):
-        if not isinstance(grad, MixedGroupedGrad):
-            raise TypeError("apply takes the MixedGroupedGrad of embedding_backward_mixed_group, got %s"
-                            % type(grad).__name__)
-        if grad.row_base != self.group.row_base or grad.widths != self.group.widths:
-            raise ValueError("the gradient belongs to a group with other row counts or widths")
-
-
-class MixedGroupSparseUpdater(_MixedGroupGradientStep):
+class MixedGroupSparseUpdater(_MixedGroupStep, GroupSparseUpdater):
     """GroupSparseUpdater for a MixedTableGroup (or a list of tables of DIFFERENT widths): applies a MixedGroupedGrad to all
     tables in ONE launch (cuembed_amd.sparse_row_update_mixed_group) and owns the state, `.states`: None ("sgd") or one
     fp32 tensor per table, [rows_t, W_t] ("adagrad") or [rows_t] ("rowwise_adagrad").  lr: a float or a one-element fp32
     device tensor; assign `.lr` to change it.  Rounds to nearest: stochastic_rounding=True is refused."""
 
     def __init__(self, group, rule, lr, eps=1e-8, initial_accumulator_value=0.0, stochastic_rounding=False):
-        if rule not in _ops.UPDATE_RULES:
-            raise ValueError("rule must be one of %r, got %r" % (sorted(_ops.UPDATE_RULES), rule))
-        self._init_group(group, stochastic_rounding)
-        self.rule = rule
-        self.lr = lr
-        self.eps = float(eps)
-        self.states = None
-        if rule != "sgd":
-            self.states = tuple(_new_state(t, rule, initial_accumulator_value) for t in self.group.tables)
-        self._device_arrays(*(() if self.states is None else (self.states,)))
-
-    def apply(self, grad):
-        """tables[t][r, :W_t] (and its state) <- rule, for the valid entries of a MixedGroupedGrad.  Nothing is read back."""
-        self._check_grad(grad)
-        _mixed_step.sparse_row_update_mixed_group(self.group, grad.ids, grad.rows, rule=self.rule, lr=self.lr,
-                                                  states=self.states, eps=self.eps, last_id=grad.last_id)
+        super().__init__(group, rule, lr, eps, initial_accumulator_value, stochastic_rounding)
 
 
-class MixedGroupSparseAdamUpdater(_MixedGroupGradientStep):
+class MixedGroupSparseAdamUpdater(_MixedGroupStep, GroupSparseAdamUpdater):
     """GroupSparseAdamUpdater for a MixedTableGroup: one launch for the clock, one for all tables
     (cuembed_amd.sparse_row_adam_mixed_group).  Owns `.exp_avg` and `.exp_avg_sq`, one fp32 tensor per table each
     ([rows_t, W_t]; exp_avg_sq [rows_t] with rowwise=True), and ONE bias-factor clock for the group (`.powers`,
@@ -450,32 +425,7 @@ class MixedGroupSparseAdamUpdater(_MixedGroupGradientStep):
 
     def __init__(self, group, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rowwise=False, bias_correction=True,
                  stochastic_rounding=False):
-        self.betas = _ops._check_betas(betas)
-        if not float(eps) >= 0.0 or not float(weight_decay) >= 0.0:
-            raise ValueError("eps and weight_decay must not be negative")
-        self._init_group(group, stochastic_rounding)
-        self.lr = lr
-        self.eps = float(eps)
-        self.weight_decay = float(weight_decay)
-        self.rowwise = bool(rowwise)
-        self.bias_correction = bool(bias_correction)
-        moments = [_new_moments(t, self.rowwise) for t in self.group.tables]
-        self.exp_avg = tuple(m for m, _ in moments)
-        self.exp_avg_sq = tuple(v for _, v in moments)
-        dev = self.group.device
-        self.powers = torch.tensor([0.0, 1.0, 1.0], dtype=torch.float64, device=dev)
-        self.bias_factor = torch.ones((1,), dtype=torch.float32, device=dev)
-        self._one = None if self.bias_correction else torch.ones((1,), dtype=torch.float32, device=dev)
-        self._device_arrays(self.exp_avg, self.exp_avg_sq)
-
-    def apply(self, grad):
-        """One Adam step on the valid entries of a MixedGroupedGrad: the clock moves on, then the mixed step."""
-        self._check_grad(grad)
-        _ops.adam_clock_advance(self.powers, self.bias_factor, self.betas)
-        _mixed_step.sparse_row_adam_mixed_group(
-            self.group, grad.ids, grad.rows, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, lr=self.lr,
-            bias_factor=self.bias_factor if self.bias_correction else self._one, betas=self.betas, eps=self.eps,
-            weight_decay=self.weight_decay, rowwise=self.rowwise, last_id=grad.last_id)
+        super().__init__(group, lr, betas, eps, weight_decay, rowwise, bias_correction, stochastic_rounding)
 
 
 def _new_moments(table, rowwise):
