@@ -29,6 +29,8 @@ from .grouped import (EmbeddingBagGroup, QuantizedEmbeddingBagGroup, TableGroup,
                       embedding_forward_grouped, embedding_forward_quantized_grouped, grouped_forward_launch_shape)
 from .mixed_group import (MixedEmbeddingBagGroup, MixedTableGroup, embedding_forward_mixed_group,  # noqa: F401
                           mixed_group_launch_shape)
+from .quantized_mixed_group import (QuantizedMixedEmbeddingBagGroup, QuantizedMixedTableGroup,  # noqa: F401
+                                    embedding_forward_quantized_mixed_group, quantized_mixed_group_launch_shape)
 from .grouped_backward import (GroupedGrad, embedding_backward_grouped, embedding_weight_grad_grouped,  # noqa: F401
                                grouped_backward_keys, grouped_mean_scale, grouped_table_cuts,
                                sparse_row_adam_grouped, sparse_row_update_grouped)

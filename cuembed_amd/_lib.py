@@ -200,6 +200,16 @@ def _declare(L):
     L.cuembed_fill_mixed_group_descriptor.argtypes = [_VP, _I, _I, _I, _I, _I, _VP]
     L.cuembed_mixed_group_launch_shape.restype = None
     L.cuembed_mixed_group_launch_shape.argtypes = [_VP, _I, _I, _I, _I, _I, _I, ctypes.c_size_t, ctypes.POINTER(_I)]
+    L.cuembed_embedding_forward_quantized_mixed_group.restype = None
+    L.cuembed_embedding_forward_quantized_mixed_group.argtypes = [_VP, _VP, _VP, _VP, _I, _VP, _I, _VP, _I, _VP, _I, _I, _I,
+                                                                  _VP, _I, _I, _VP]
+    L.cuembed_quantized_mixed_group_codes_per_lane.restype = _I
+    L.cuembed_quantized_mixed_group_codes_per_lane.argtypes = [_VP, _VP, _I]
+    L.cuembed_fill_quantized_mixed_group_descriptor.restype = _I
+    L.cuembed_fill_quantized_mixed_group_descriptor.argtypes = [_VP, _I, _I, _I, _I, _VP]
+    L.cuembed_quantized_mixed_group_launch_shape.restype = None
+    L.cuembed_quantized_mixed_group_launch_shape.argtypes = [_VP, _I, _I, _I, _I, _I, _I, ctypes.c_size_t,
+                                                             ctypes.POINTER(_I)]
     L.cuembed_embedding_backward_mixed_group.restype = None
     L.cuembed_embedding_backward_mixed_group.argtypes = [_VP, _I, _VP, _VP, _I, _I, _L, _VP, _VP, _VP, _I, _VP, _VP, _VP,
                                                          _L, _VP, _VP]

@@ -50,23 +50,20 @@ struct MixedGroupPlan {
   int out_width;   //!< D
 };
 
-//! The launch arithmetic of a mixed group, and -- with `entries` non-null -- its descriptor.  Host only.
-inline MixedGroupPlan PlanMixedGroup(const int* widths_host, const int num_tables, const int elem_bytes,
-                                     const int lane_bytes, const int batch_per_table, const int block_threads,
-                                     MixedGroupEntry* entries) {
-  CUEMBED_ASSERT(widths_host != nullptr && num_tables >= 1 && batch_per_table >= 0);
-  CUEMBED_ASSERT(elem_bytes == 2 || elem_bytes == 4);
-  CUEMBED_ASSERT(lane_bytes == 16 || lane_bytes == 8 || lane_bytes == 4);
+//! The launch arithmetic of a group whose lanes hold `n` elements (codes, for fused 8-bit tables) of a row, and -- with
+//! `entries` non-null -- its descriptor: what the plain and the quantized mixed group share.  Host only.
+inline MixedGroupPlan PlanMixedGroupLanes(const int* widths_host, const int num_tables, const int n,
+                                          const int batch_per_table, const int block_threads, MixedGroupEntry* entries) {
+  CUEMBED_ASSERT(widths_host != nullptr && num_tables >= 1 && batch_per_table >= 0 && n >= 1);
   CUEMBED_ASSERT(block_threads >= 64 && block_threads <= kMaxBlockThreads && block_threads % 64 == 0);
   CUEMBED_ASSERT(static_cast<int64_t>(num_tables) * batch_per_table <= INT_MAX);
-  const int n = lane_bytes / elem_bytes;
   int64_t column = 0, blocks = 0;
   MixedGroupPlan plan{0, 0, 0};
   for (int t = 0; t < num_tables; ++t) {
     const int width = widths_host[t];
     CUEMBED_ASSERT(width > 0);
-    CUEMBED_ASSERT((static_cast<int64_t>(width) * elem_bytes) % lane_bytes == 0);
-    CUEMBED_ASSERT((column * elem_bytes) % lane_bytes == 0);
+    CUEMBED_ASSERT(width % n == 0);
+    CUEMBED_ASSERT(column % n == 0);
     const int row_lanes = width / n;
     const int lanes = row_lanes < block_threads ? row_lanes : block_threads;
     const int slots = block_threads / lanes;
@@ -76,11 +73,20 @@ inline MixedGroupPlan PlanMixedGroup(const int* widths_host, const int num_table
     blocks += (static_cast<int64_t>(batch_per_table) + slots - 1) / slots;
     CUEMBED_ASSERT(column <= INT_MAX && blocks <= INT_MAX);
   }
-  CUEMBED_ASSERT((column * elem_bytes) % lane_bytes == 0);
+  CUEMBED_ASSERT(column % n == 0);
   if (entries != nullptr) entries[num_tables] = MixedGroupEntry{0, static_cast<int32_t>(column), 0, static_cast<int32_t>(blocks)};
   plan.grid = static_cast<int>(blocks);
   plan.out_width = static_cast<int>(column);
   return plan;
+}
+
+//! ... of a group of plain tables: lanes of lane_bytes / elem_bytes elements.
+inline MixedGroupPlan PlanMixedGroup(const int* widths_host, const int num_tables, const int elem_bytes,
+                                     const int lane_bytes, const int batch_per_table, const int block_threads,
+                                     MixedGroupEntry* entries) {
+  CUEMBED_ASSERT(elem_bytes == 2 || elem_bytes == 4);
+  CUEMBED_ASSERT(lane_bytes == 16 || lane_bytes == 8 || lane_bytes == 4);
+  return PlanMixedGroupLanes(widths_host, num_tables, lane_bytes / elem_bytes, batch_per_table, block_threads, entries);
 }
 
 //! Dynamic LDS of the staged kernel: fixed hotness whose widest workgroup's indices (+ weights) fit the staging budget of

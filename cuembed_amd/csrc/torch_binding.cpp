@@ -1642,6 +1642,49 @@ at::Tensor cuemb_embedding_mixed_group_op(const at::TensorList tables, const at:
   return out;
 }
 
+// ---- a group of fused 8-bit tables of DIFFERENT widths pooled in one launch (extension; inference only).  qtables are
+// uint8 [rows_t, W_t + 8]; `descriptor` is the caller's int32 device tensor of (num_tables + 1) * 4 words, filled on the
+// host by cuembed_fill_quantized_mixed_group_descriptor for this batch and `codes_per_lane` and copied to the device once
+// (cuembed_amd.QuantizedMixedTableGroup.descriptor); codes_per_lane is checked here against the pointers, the words
+// cannot be.  Returns [batch, sum of the widths] of out_dtype; weights have that dtype.
+at::Tensor cuemb_embedding_quantized_mixed_group_op(const at::TensorList qtables, const at::Tensor& table_ptrs,
+                                                    const at::Tensor& descriptor, const int64_t codes_per_lane,
+                                                    const at::Tensor& indices, const c10::optional<at::Tensor>& offsets,
+                                                    const c10::optional<at::Tensor>& weights, const std::string& mode,
+                                                    const at::ScalarType out_dtype, const int64_t row_loads) {
+  const int m = GroupedMode(mode);
+  const int64_t num_tables = static_cast<int64_t>(qtables.size());
+  TORCH_CHECK(num_tables >= 1, "cuembed_pyt: a group needs at least one table");
+  const int out_code = OutCode(out_dtype, "out_dtype");
+  std::vector<int> widths;
+  int64_t dim = 0;
+  for (const at::Tensor& t : qtables) {
+    const int64_t width = QuantizedWidth(t);   // (uint8, 2-D, contiguous, W % 4 == 0, 4-byte aligned, on the GPU)
+    widths.push_back(static_cast<int>(width));
+    dim += width;
+  }
+  TORCH_CHECK(dim <= INT32_MAX, "cuembed_pyt: the widths must sum to at most 2^31 - 1");
+  const at::DeviceGuard guard(qtables[0].device());
+  GroupedCall c;
+  c.host_ptrs = CheckGroupTables(qtables, table_ptrs, false);
+  TORCH_CHECK(descriptor.is_cuda() && descriptor.device() == qtables[0].device() && descriptor.scalar_type() == at::kInt &&
+                  descriptor.is_contiguous() && descriptor.numel() == (num_tables + 1) * 4,
+              "cuembed_pyt: descriptor must be the contiguous int32 tensor of (num_tables + 1) * 4 words on the tables' "
+              "device");
+  CheckGroupedBatch(&c, num_tables, indices, offsets, weights, out_dtype, row_loads, c10::nullopt);
+  const int codes = ::cuembed_quantized_mixed_group_codes_per_lane(c.host_ptrs.data(), widths.data(),
+                                                                   static_cast<int>(num_tables));
+  TORCH_CHECK(codes_per_lane == codes, "cuembed_pyt: the descriptor was filled for lanes of ", codes_per_lane,
+              " codes, these tables take ", codes);
+  at::Tensor out = at::empty({c.batch, dim}, qtables[0].options().dtype(out_dtype));
+  if (c.batch > 0)
+    ::cuembed_embedding_forward_quantized_mixed_group(
+        c.host_ptrs.data(), static_cast<const void* const*>(table_ptrs.data_ptr()), widths.data(), descriptor.data_ptr(),
+        static_cast<int>(num_tables), Ptr(c.i), c.idx, Ptr(c.o), c.off, Ptr(c.w), static_cast<int>(c.batch),
+        static_cast<int>(c.hot), m, MutPtr(out), out_code, static_cast<int>(row_loads), CurrentStream(out));
+  return out;
+}
+
 // ---- the backward of a group: keys + sample ids in front of the single-table pipeline, table cuts behind it ----------
 // idx / offsets as in cuemb_embedding_grouped; row_base = the int64 device tensor of num_tables + 1 exclusive prefix sums
 // of the tables' row counts (cuembed_amd.TableGroup.row_base_device).  narrow: int32 results (the caller knows that the
@@ -2051,6 +2094,10 @@ TORCH_LIBRARY(cuembed_pyt, m) {
   m.def(
       "cuemb_embedding_mixed_group(Tensor[] tables, Tensor table_ptrs, Tensor descriptor, int lane_bytes, Tensor idx, "
       "Tensor? offsets, Tensor? weights, str mode, int row_loads=-1) -> Tensor");
+  // a group of fused 8-bit tables of different widths pooled in one launch -> [batch, sum of widths]; inference only
+  m.def(
+      "cuemb_embedding_quantized_mixed_group(Tensor[] qtables, Tensor table_ptrs, Tensor descriptor, int codes_per_lane, "
+      "Tensor idx, Tensor? offsets, Tensor? weights, str mode, ScalarType out_dtype, int row_loads=-1) -> Tensor");
   // the backward of a group: the keys in front of the single-table pipeline, the table boundaries behind it
   m.def(
       "cuembed_grouped_backward_keys(Tensor idx, Tensor? offsets, Tensor row_base, int num_tables, int batch, int "
@@ -2115,6 +2162,7 @@ TORCH_LIBRARY_IMPL(cuembed_pyt, CUDA, m) {  // HIP tensors use the CUDA dispatch
   m.impl("cuemb_embedding_grouped", cuemb_embedding_grouped_op);
   m.impl("cuemb_embedding_quantized_grouped", cuemb_embedding_quantized_grouped_op);
   m.impl("cuemb_embedding_mixed_group", cuemb_embedding_mixed_group_op);
+  m.impl("cuemb_embedding_quantized_mixed_group", cuemb_embedding_quantized_mixed_group_op);
   m.impl("cuembed_grouped_backward_keys", cuembed_grouped_backward_keys_op);
   m.impl("cuembed_grouped_table_cuts", cuembed_grouped_table_cuts_op);
   m.impl("cuembed_grouped_weight_grad", cuembed_grouped_weight_grad_op);

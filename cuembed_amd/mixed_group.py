@@ -22,8 +22,9 @@ memory; MixedTableGroup builds it once per (batch size, lane width) -- one host-
 shape (or at group.descriptor(B, lane_bytes)), none afterwards -- so with `out=` given every later call copies nothing,
 allocates nothing and can be captured into a HIP graph.  The functions here are forward only and refuse tensors that
 require grad; the backward is cuembed_amd.mixed_group_backward (autograd:
-cuembed_pyt.cuemb_embedding_mixed_group_trainable).  There is no sample_order, no per-table row-load decision, no
-quantized and no mixed-dtype group.
+cuembed_pyt.cuemb_embedding_mixed_group_trainable).  There is no sample_order, no per-table row-load decision and no
+mixed-dtype group; fused 8-bit tables of different widths go into
+cuembed_amd.quantized_mixed_group.QuantizedMixedTableGroup.
 """
 import ctypes
 

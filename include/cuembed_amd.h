@@ -818,6 +818,35 @@ int cuembed_fill_mixed_group_descriptor(const int* widths_host, int num_tables, 
  * dynamic LDS bytes, out[5] = 1 when the indices are staged in LDS, out[6] = the most bags a workgroup holds. */
 void cuembed_mixed_group_launch_shape(const int* widths_host, int num_tables, int elem_type, int index_type,
                                       int batch_per_table, int num_hots, int is_weighted, size_t pointer_bits, int* out);
+/* ---- a group of fused 8-bit tables of DIFFERENT widths pooled in one launch (extension; sum / mean only, inference
+ * only; cuembed::EmbeddingForwardQuantizedMixedGroup, quantized_mixed_group_lookup.hpp) -----
+ * The mixed-width group above on the rows of cuembed_embedding_forward_quantized: table t is [rows_t, widths_host[t] + 8]
+ * bytes (widths_host[t] codes, a multiple of 4, then fp32 scale and fp32 bias), at least 4-byte aligned; weights and ret
+ * are of out_type (CUEMBED_F32 or CUEMBED_F16); ret is [batch_per_table, D], contiguous, 16-byte aligned, D = the sum of
+ * the widths -- the results of num_tables calls of cuembed_embedding_forward_quantized concatenated on dimension 1, with
+ * their bits.  The descriptor has cuembed_mixed_group_descriptor_bytes(num_tables) bytes, is filled on the host by
+ * cuembed_fill_quantized_mixed_group_descriptor for this batch_per_table and codes_per_lane and copied to the device by
+ * the caller, once.  codes_per_lane (cuembed_quantized_mixed_group_codes_per_lane; tables_host may be NULL for aligned
+ * buffers) is 16 when every width is a multiple of 16 and every base 8-byte aligned, 8 when every width is a multiple of
+ * 8 and every base 8-byte aligned, else 4; ret never narrows it.  Everything else as cuembed_embedding_forward_mixed_group:
+ * nothing copied or allocated per call, one kernel launch, no sample_order, misuse aborts. */
+void cuembed_embedding_forward_quantized_mixed_group(const void* const* tables_host, const void* const* tables_device,
+                                                     const int* widths_host, const void* descriptor_device,
+                                                     int num_tables, const void* indices, int index_type,
+                                                     const void* offsets, int offset_type, const void* weights,
+                                                     int batch_per_table, int num_hots, int mode, void* ret, int out_type,
+                                                     int row_load_policy, cuembed_stream_t stream);
+int cuembed_quantized_mixed_group_codes_per_lane(const void* const* tables_host, const int* widths_host, int num_tables);
+/* Host arithmetic only.  Entry t < num_tables of host_blob: int32 {width, c_t, L_t, first workgroup}, L_t = min(width /
+ * codes_per_lane, block_threads); entry num_tables: {0, D, 0, grid}.  Returns the grid. */
+int cuembed_fill_quantized_mixed_group_descriptor(const int* widths_host, int num_tables, int codes_per_lane,
+                                                  int batch_per_table, int block_threads, void* host_blob);
+/* Launch shape (no launch; host arithmetic only).  pointer_bits: the table bases OR-ed (0 = aligned buffers).  out[0] =
+ * codes per lane, out[1] = block threads (what the descriptor is filled for), out[2] = grid, out[3] = D, out[4] =
+ * dynamic LDS bytes, out[5] = 1 when the indices are staged in LDS, out[6] = the most bags a workgroup holds. */
+void cuembed_quantized_mixed_group_launch_shape(const int* widths_host, int num_tables, int out_type, int index_type,
+                                                int batch_per_table, int num_hots, int is_weighted, size_t pointer_bits,
+                                                int* out);
 /* ---- the backward of a group (extension): one sort and one scatter-add for all its tables -----
  * The group above is trained through the single-table pipeline, fed the right keys.  row_base[num_tables + 1] is the
  * exclusive prefix sum of the tables' row counts: int64, DEVICE memory, built once by the caller; row_base[num_tables]
