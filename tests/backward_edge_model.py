@@ -595,3 +595,90 @@ def merge_problem(kind, width, n, distinct, padding, capacity):
     pad = np.flatnonzero(ids >= MERGE_CATEGORIES)
     bits[pad] = hashed_patterns(kind, (pad.size, width), n)
     return ids, bits
+
+
+# ---- the mixed-width group: grad_y [B, D], table t at columns [c_t, c_t + W_t) ------------------------------------------------
+MIXED_ROWS = (5000, 17, 300, 64)
+MIXED_WIDTHS = ((128, 16, 64, 32), (36, 4, 128), (6, 2, 10))
+
+
+def mixed_group_problem(kind, batch, widths, layout):
+    """group_problem for tables of different widths: the same lengths, weight patterns and density, grad_y [B, D] with
+    table t's slice at columns [c_t, c_t + W_t).  Plants sit at columns 0, W_t - 1 and W_t // 2 OF THE SLICE: column
+    c_{t + 1} + 0 of a sample lies directly beside table t's last column, so a lane active past W_t, or a source offset
+    that is off by one table, carries a plant into rows that never look it up.  Every table of every problem holds a
+    +Inf at its column 0 and one at its column W_t - 1 in bags with lookups.
+    dict(ids, offsets or None, hot, weights / weights_bits, grad_y_bits [B, D], grad_y, lengths [T * B], rows, widths,
+    planted = [(b, t, column inside the slice or -1, plant)])."""
+    import mixed_group_backward_reference as MR
+    widths = tuple(widths)
+    T = len(widths)
+    rows = MIXED_ROWS[:T]
+    cols = MR.column_base(widths)
+    D = int(cols[-1])
+    rng = np.random.default_rng(11 * batch + D + 1000 * GROUP_LAYOUTS.index(layout))
+    if layout == "h4":
+        lengths, offsets, hot = np.full((T, batch), 4), None, 4
+    else:
+        lengths = rng.choice(POWER_LENGTHS, size=(T, batch))
+        if layout == "csr_empty_table":
+            lengths[1, :] = 0
+        elif batch >= 3:                      # empty bags on both sides of every table boundary, next to full ones
+            lengths[:, 0] = 0
+            lengths[:, -1] = 0
+            lengths[:, 1] = 8
+        offsets, hot = np.concatenate([[0], np.cumsum(lengths.reshape(-1))]).astype(np.int64), 0
+    flat = lengths.reshape(-1)
+    ids = np.concatenate([rng.integers(0, rows[t], int(lengths[t].sum())) for t in range(T)]).astype(np.int64)
+    weights = np.zeros(ids.shape[0], dtype=np.float32)
+    at = 0
+    for g, n in enumerate(flat):
+        if n:
+            patterns = WEIGHT_PATTERNS[int(n)]
+            pick = int(rng.integers(0, 2)) if layout != "csr_zero_sums" or g % 3 else 2
+            weights[at:at + n] = rng.permutation(np.array(patterns[pick], dtype=np.float32))
+            at += n
+    values = rng.integers(-1, 2, (batch, D)).astype(np.float32) * rng.integers(1, 3, (batch, D))
+    values *= rng.integers(0, GROUP_DENSITY, values.shape) == 0
+    bits = to_bits(kind, values)
+    planted = []
+
+    def plant(b, t, c, what):
+        if what == "-0":
+            zero = np.flatnonzero(values[b, cols[t]:cols[t + 1]] == 0)
+            bits[b, cols[t] + zero] = special(kind, "-0")
+            planted.append((b, t, -1, what))
+        else:
+            bits[b, cols[t] + c] = special(kind, what)
+            planted.append((b, t, c, what))
+
+    bags = [(b, t) for t in range(T) for b in range(batch)]
+    step = max(1, len(bags) // (3 if batch <= 5 else 24))
+    specs = (["+inf", "-inf"], ["nan"], ["-0"]) if batch <= 5 else (["+inf"], ["-inf"], ["nan"], ["-0"])
+    for n, (b, t) in enumerate(bags[(2 if 2 < batch <= 5 else 1)::step]):    # (a small ragged batch: bag 1 is the long one)
+        if n % len(specs) == 0 and lengths[t, b] == 0 and lengths[t].any():      # the infinities: a bag with lookups
+            b = int(np.flatnonzero(np.roll(lengths[t], -b))[0] + b) % batch
+        for k, what in enumerate(specs[n % len(specs)]):
+            plant(b, t, (0, widths[t] - 1, widths[t] // 2)[(n + k) % 3], what)
+    # the edges of every slice: +Inf at column 0 of one sample and at column W_t - 1 of another, in bags with lookups
+    # (where a table has two of them that no plant above took)
+    taken = {(b, t) for b, t, _, _ in planted}
+    for t in range(T):
+        free = [int(b) for b in np.flatnonzero(lengths[t]) if (int(b), t) not in taken]
+        chosen = free[len(free) // 4::max(1, len(free) // 4)][:3]
+        if chosen:
+            plant(chosen[0], t, -1, "-0")       # (a looked-up -0.0 in every table: the +Inf below shares its sample)
+        for b, c in zip(chosen[:2], (0, widths[t] - 1)):
+            plant(b, t, c, "+inf")
+        if chosen:                              # a looked-up NaN in every table, in a sample of its own where there is one
+            plant(chosen[-1] if len(chosen) == 3 else chosen[0], t, widths[t] // 2, "nan")
+    return dict(ids=ids, offsets=offsets, hot=hot, weights=weights, weights_bits=to_bits(kind, weights), grad_y_bits=bits,
+                grad_y=from_bits(kind, bits), lengths=flat, planted=planted, rows=rows, widths=widths)
+
+
+def mixed_group_keys(batch, p):
+    """(global row, sample, table) of every lookup of a mixed-width problem."""
+    import mixed_group_backward_reference as MR
+    bag = np.repeat(np.arange(len(p["widths"]) * batch, dtype=np.int64), p["lengths"])
+    t, b = bag // batch, bag % batch
+    return MR.row_base(p["rows"])[t] + p["ids"], b, t

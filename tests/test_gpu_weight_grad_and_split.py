@@ -140,19 +140,7 @@ def test_split_forward_per_element_bound(ce, oracle, kind, fp16_math, W):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-def _edge_table(rng, kind, rows, W):
-    """A table of edge values of `kind` (as fp32 values exactly representable in it) plus ordinary rows."""
-    if kind == "f16":
-        sub, big, step = 2.0 ** -24, 60000.0, 2.0 ** -10       # smallest subnormal, near max, ulp at 1
-    elif kind == "bf16":
-        sub, big, step = 2.0 ** -133, 3.0e38, 2.0 ** -7
-    else:
-        sub, big, step = 2.0 ** -149, 3.0e38, 2.0 ** -23
-    specials = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, sub, -sub, 3 * sub, 1000 * sub, big, -big,
-                         1.0, step / 2, 1.0 + step, -1.0, 0.5], dtype=np.float64)
-    t = rng.uniform(-1, 1, (rows, W))
-    t[: rows // 2] = specials[rng.integers(0, specials.shape[0], (rows // 2, W))]
-    return t.astype(np.float32)
+from forward_edge_cases import edge_table as _edge_table          # (shared with test_gpu_forward_edges.py)
 
 
 def _to(kind, oracle, t32):
