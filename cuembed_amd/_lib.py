@@ -183,6 +183,12 @@ def _declare(L):
                                                       _VP]
     L.cuembed_quantized_forward_launch_shape.restype = None
     L.cuembed_quantized_forward_launch_shape.argtypes = [_I, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]
+    for name in ("cuembed_quantize_rows", "cuembed_dequantize_rows", "cuembed_embedding_forward_quantized"):
+        fn4 = getattr(L, name + "_4bit")                                   # (parameter for parameter the 8-bit ones)
+        fn4.restype = None
+        fn4.argtypes = list(getattr(L, name).argtypes)
+    L.cuembed_quantized_4bit_forward_launch_shape.restype = None
+    L.cuembed_quantized_4bit_forward_launch_shape.argtypes = [_I, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]
     L.cuembed_embedding_forward_grouped.restype = None
     L.cuembed_embedding_forward_grouped.argtypes = [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, _I, _VP, _I, _VP,
                                                     _VP]

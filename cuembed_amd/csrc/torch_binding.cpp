@@ -1349,23 +1349,60 @@ void CheckQuantizedLanes(const at::Tensor& qtable, const int64_t width) {
               codes, " bytes, more than 1024; align the table to 8 bytes");
 }
 
+// The fused 4-bit layout (quantized::embedding_bag_4bit_prepack): uint8 [rows, W / 2 + 4], two codes a byte, fp16 scale,
+// fp16 bias; W % 8 == 0 here.
+int64_t Quantized4BitWidth(const at::Tensor& qtable) {
+  CheckGpu(qtable, "qtable");
+  TORCH_CHECK(qtable.scalar_type() == at::kByte && qtable.dim() == 2 && qtable.is_contiguous(),
+              "cuembed_pyt: qtable must be a contiguous 2-D uint8 tensor [rows, width/2 + 4]");
+  const int64_t width = (qtable.size(1) - 4) * 2;
+  TORCH_CHECK(width > 0 && width % 8 == 0, "cuembed_pyt: a fused 4-bit row is whole dwords of codes (W % 8 == 0)");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qtable.data_ptr()) % 4 == 0, "cuembed_pyt: qtable must be 4-byte aligned");
+  return width;
+}
+
+// ... and what DequantizeRows4Bit (8 codes a lane) / PlanQuantized4BitForward (32, 16 or 8) would abort on
+void CheckQuantized4BitLanes(const int64_t width, const bool forward) {
+  int64_t codes = 8;
+  if (forward) codes = (width % 32 == 0 && width / 32 <= 256) ? 32 : (width % 16 == 0 ? 16 : 8);
+  TORCH_CHECK(width / codes <= 1024, "cuembed_pyt: qtable: a row of ", width, " 4-bit codes needs ", width / codes,
+              " lanes of ", codes, " codes, more than 1024");
+}
+
+// What the three ops need to know of a fused layout; kBits = 8 or 4.
+template <int kBits>
+struct Fused {
+  static int64_t RowBytes(const int64_t width) { return kBits == 8 ? width + 8 : width / 2 + 4; }
+  static int64_t Width(const at::Tensor& qtable) { return kBits == 8 ? QuantizedWidth(qtable) : Quantized4BitWidth(qtable); }
+  static void CheckLanes(const at::Tensor& qtable, const int64_t width, const bool forward) {
+    if (kBits == 8) CheckQuantizedLanes(qtable, width);
+    else CheckQuantized4BitLanes(width, forward);
+  }
+  static constexpr auto kQuantize = kBits == 8 ? &::cuembed_quantize_rows : &::cuembed_quantize_rows_4bit;
+  static constexpr auto kDequantize = kBits == 8 ? &::cuembed_dequantize_rows : &::cuembed_dequantize_rows_4bit;
+  static constexpr auto kForward =
+      kBits == 8 ? &::cuembed_embedding_forward_quantized : &::cuembed_embedding_forward_quantized_4bit;
+};
+
+template <int kBits>
 at::Tensor quantize_rows_op(const at::Tensor& table) {
   CheckGpu(table, "table");
   const int elem = ElemCode(table, "table");
-  TORCH_CHECK(table.dim() == 2 && table.size(1) > 0 && table.size(1) % 4 == 0,
-              "cuembed_pyt: table must be [rows, width] with a width that is a multiple of 4");
+  TORCH_CHECK(table.dim() == 2 && table.size(1) > 0 && table.size(1) % (kBits == 8 ? 4 : 8) == 0,
+              "cuembed_pyt: table must be [rows, width] with a width that is a multiple of ", kBits == 8 ? 4 : 8);
   const at::DeviceGuard guard(table.device());
   const at::Tensor t = table.contiguous();
   TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "cuembed_pyt: table must be 16-byte aligned");
-  at::Tensor out = at::empty({t.size(0), t.size(1) + 8}, t.options().dtype(at::kByte));
+  at::Tensor out = at::empty({t.size(0), Fused<kBits>::RowBytes(t.size(1))}, t.options().dtype(at::kByte));
   if (t.size(0) > 0)
-    ::cuembed_quantize_rows(Ptr(t), elem, static_cast<int>(t.size(1)), t.size(0), MutPtr(out), CurrentStream(t));
+    Fused<kBits>::kQuantize(Ptr(t), elem, static_cast<int>(t.size(1)), t.size(0), MutPtr(out), CurrentStream(t));
   return out;
 }
 
+template <int kBits>
 at::Tensor dequantize_rows_op(const at::Tensor& qtable, const c10::optional<at::Tensor>& ids, const at::ScalarType dtype) {
-  const int64_t width = QuantizedWidth(qtable);
-  CheckQuantizedLanes(qtable, width);
+  const int64_t width = Fused<kBits>::Width(qtable);
+  Fused<kBits>::CheckLanes(qtable, width, false);
   const int out_code = OutCode(dtype, "dtype");
   const at::DeviceGuard guard(qtable.device());
   at::Tensor i;
@@ -1381,24 +1418,25 @@ at::Tensor dequantize_rows_op(const at::Tensor& qtable, const c10::optional<at::
   at::Tensor out = at::empty(shape, qtable.options().dtype(dtype));
   const int64_t n = i.defined() ? i.numel() : qtable.size(0);
   if (n > 0)
-    ::cuembed_dequantize_rows(Ptr(qtable), static_cast<int>(width), Ptr(i), idx, n, MutPtr(out), out_code,
+    Fused<kBits>::kDequantize(Ptr(qtable), static_cast<int>(width), Ptr(i), idx, n, MutPtr(out), out_code,
                               CurrentStream(qtable));
   return out;
 }
 
 // offsets given: CSR (batch + 1 entries); absent: fixed hotness, indices is [batch, hotness].
+template <int kBits>
 at::Tensor cuemb_embedding_quantized_op(const at::Tensor& qtable, const at::Tensor& indices,
                                         const c10::optional<at::Tensor>& offsets, const c10::optional<at::Tensor>& weights,
                                         const std::string& mode, const at::ScalarType out_dtype, const int64_t row_loads,
                                         const c10::optional<at::Tensor>& sample_order,
                                         const c10::optional<at::Tensor>& row_loads_device) {
-  const int64_t width = QuantizedWidth(qtable);
-  CheckQuantizedLanes(qtable, width);
+  const int64_t width = Fused<kBits>::Width(qtable);
   const int out_code = OutCode(out_dtype, "out_dtype");
   CheckGpu(indices, "indices");
   const int idx = IndexCode(indices, "indices");
   const bool csr = offsets.has_value() && offsets->defined();
   const int m = Mode(mode, !csr);
+  Fused<kBits>::CheckLanes(qtable, width, m != CUEMBED_CONCAT);
   TORCH_CHECK(row_loads >= -1 && row_loads <= 1, "cuembed_pyt: row_loads must be -1, 0 or 1");
   const at::DeviceGuard guard(qtable.device());
   const at::Tensor i = indices.contiguous();
@@ -1436,7 +1474,7 @@ at::Tensor cuemb_embedding_quantized_op(const at::Tensor& qtable, const at::Tens
   at::Tensor out = m == CUEMBED_CONCAT ? at::empty({batch, hot, width}, qtable.options().dtype(out_dtype))
                                        : at::empty({batch, width}, qtable.options().dtype(out_dtype));
   if (batch > 0)
-    ::cuembed_embedding_forward_quantized(Ptr(qtable), static_cast<int>(width), Ptr(i), idx, Ptr(o), off, Ptr(w),
+    Fused<kBits>::kForward(Ptr(qtable), static_cast<int>(width), Ptr(i), idx, Ptr(o), off, Ptr(w),
                                           static_cast<int>(batch), static_cast<int>(hot), m, MutPtr(out), out_code,
                                           static_cast<int>(row_loads), static_cast<const int32_t*>(Ptr(order)),
                                           static_cast<const uint32_t*>(Ptr(decision)), CurrentStream(qtable));
@@ -2083,6 +2121,12 @@ TORCH_LIBRARY(cuembed_pyt, m) {
   m.def(
       "cuemb_embedding_quantized(Tensor qtable, Tensor indices, Tensor? offsets, Tensor? weights, str mode, ScalarType "
       "out_dtype, int row_loads, Tensor? sample_order, Tensor? row_loads_device) -> Tensor");
+  // fused 4-bit row-wise tables (torch's quantized::embedding_bag_4bit_prepack layout): the same three
+  m.def("quantize_rows_4bit(Tensor table) -> Tensor");
+  m.def("dequantize_rows_4bit(Tensor qtable, Tensor? ids, ScalarType dtype) -> Tensor");
+  m.def(
+      "cuemb_embedding_quantized_4bit(Tensor qtable, Tensor indices, Tensor? offsets, Tensor? weights, str mode, ScalarType "
+      "out_dtype, int row_loads, Tensor? sample_order, Tensor? row_loads_device) -> Tensor");
   // a group of tables of one width and dtype pooled in one launch -> [batch, num_tables, width]; forward only
   m.def(
       "cuemb_embedding_grouped(Tensor[] tables, Tensor table_ptrs, Tensor idx, Tensor? offsets, Tensor? weights, str mode, "
@@ -2156,9 +2200,12 @@ TORCH_LIBRARY_IMPL(cuembed_pyt, CUDA, m) {  // HIP tensors use the CUDA dispatch
   m.impl("cuembed_sparse_row_adam_grouped", cuembed_sparse_row_adam_grouped_op);
   m.impl("cuembed_sparse_row_update_mixed_group", cuembed_sparse_row_update_mixed_group_op);
   m.impl("cuembed_sparse_row_adam_mixed_group", cuembed_sparse_row_adam_mixed_group_op);
-  m.impl("quantize_rows", quantize_rows_op);
-  m.impl("dequantize_rows", dequantize_rows_op);
-  m.impl("cuemb_embedding_quantized", cuemb_embedding_quantized_op);
+  m.impl("quantize_rows", quantize_rows_op<8>);
+  m.impl("dequantize_rows", dequantize_rows_op<8>);
+  m.impl("cuemb_embedding_quantized", cuemb_embedding_quantized_op<8>);
+  m.impl("quantize_rows_4bit", quantize_rows_op<4>);
+  m.impl("dequantize_rows_4bit", dequantize_rows_op<4>);
+  m.impl("cuemb_embedding_quantized_4bit", cuemb_embedding_quantized_op<4>);
   m.impl("cuemb_embedding_grouped", cuemb_embedding_grouped_op);
   m.impl("cuemb_embedding_quantized_grouped", cuemb_embedding_quantized_grouped_op);
   m.impl("cuemb_embedding_mixed_group", cuemb_embedding_mixed_group_op);

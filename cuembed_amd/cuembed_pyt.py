@@ -99,6 +99,10 @@ def _define_python_ops():
     _lib.define("dequantize_rows(Tensor qtable, Tensor? ids, ScalarType dtype) -> Tensor")
     _lib.define("cuemb_embedding_quantized(Tensor qtable, Tensor indices, Tensor? offsets, Tensor? weights, str mode,"
                 " ScalarType out_dtype, int row_loads, Tensor? sample_order, Tensor? row_loads_device) -> Tensor")
+    _lib.define("quantize_rows_4bit(Tensor table) -> Tensor")
+    _lib.define("dequantize_rows_4bit(Tensor qtable, Tensor? ids, ScalarType dtype) -> Tensor")
+    _lib.define("cuemb_embedding_quantized_4bit(Tensor qtable, Tensor indices, Tensor? offsets, Tensor? weights, str mode,"
+                " ScalarType out_dtype, int row_loads, Tensor? sample_order, Tensor? row_loads_device) -> Tensor")
     _lib.define("cuemb_embedding_grouped(Tensor[] tables, Tensor table_ptrs, Tensor idx, Tensor? offsets, Tensor? weights,"
                 " str mode, int row_loads=-1, Tensor? sample_order=None) -> Tensor")
     _lib.define("cuemb_embedding_quantized_grouped(Tensor[] qtables, Tensor table_ptrs, Tensor idx, Tensor? offsets,"
@@ -136,6 +140,9 @@ def _define_python_ops():
     _lib.impl("quantize_rows", _quantize_rows_impl, "CUDA")
     _lib.impl("dequantize_rows", _dequantize_rows_impl, "CUDA")
     _lib.impl("cuemb_embedding_quantized", _embedding_quantized_impl, "CUDA")
+    _lib.impl("quantize_rows_4bit", lambda table: _quantize_rows_impl(table, bits=4), "CUDA")
+    _lib.impl("dequantize_rows_4bit", lambda qtable, ids, dtype: _dequantize_rows_impl(qtable, ids, dtype, bits=4), "CUDA")
+    _lib.impl("cuemb_embedding_quantized_4bit", lambda *args: _embedding_quantized_impl(*args, bits=4), "CUDA")
     _lib.impl("cuembed_sparse_row_update_", _sparse_row_update_impl, "CUDA")
     _lib.impl("cuembed_sparse_row_adam_", _sparse_row_adam_impl, "CUDA")
     _lib.impl("cuembed_sparse_row_update_grouped", _sparse_row_update_grouped_impl, "CUDA")
@@ -184,6 +191,8 @@ def _define_python_ops():
 #   cuembed_sparse_row_adam_mixed_group       table (the mixed backward's gradient), round to nearest only
 #   quantize_rows, dequantize_rows,           8-bit row-wise quantized tables in torch's own fused layout (inference
 #   cuemb_embedding_quantized                 only): the quantizer, its inverse, and the lookup on a fused table
+#   quantize_rows_4bit, dequantize_rows_4bit, the same three on torch's fused 4-bit row-wise layout (two codes a byte,
+#   cuemb_embedding_quantized_4bit            fp16 scale and bias)
 #   cuemb_embedding_grouped,                  a group of tables of one width and dtype pooled in ONE launch into
 #   cuemb_embedding_quantized_grouped         [batch, tables, width] (forward only: no autograd formula)
 #   cuemb_embedding_mixed_group               a group of plain tables of DIFFERENT widths pooled in ONE launch into
@@ -442,17 +451,18 @@ def _sparse_row_adam_mixed_group_impl(tables, table_ptrs, exp_avg, exp_avg_ptrs,
                                                      last_id))
 
 
-def _quantize_rows_impl(table):
+def _quantize_rows_impl(table, bits=8):
     from . import quantized as _q
-    return _q.quantize_rows(table.contiguous())
+    return _q.quantize_rows(table.contiguous(), bits=bits)
 
 
-def _dequantize_rows_impl(qtable, ids, dtype):
+def _dequantize_rows_impl(qtable, ids, dtype, bits=8):
     from . import quantized as _q
-    return _q.dequantize_rows(qtable, None if ids is None else ids.contiguous(), dtype)
+    return _q.dequantize_rows(qtable, None if ids is None else ids.contiguous(), dtype, bits=bits)
 
 
-def _embedding_quantized_impl(qtable, indices, offsets, weights, mode, out_dtype, row_loads, sample_order, row_loads_device):
+def _embedding_quantized_impl(qtable, indices, offsets, weights, mode, out_dtype, row_loads, sample_order, row_loads_device,
+                              bits=8):
     from . import quantized as _q
     if offsets is None:
         _require(indices.dim() == 2 and indices.shape[1] > 0, "without offsets, indices must be [batch, hotness]")
@@ -460,7 +470,7 @@ def _embedding_quantized_impl(qtable, indices, offsets, weights, mode, out_dtype
         qtable, indices.contiguous(), None if offsets is None else offsets.contiguous(),
         None if weights is None else weights.contiguous(), num_hots=0 if offsets is not None else indices.shape[1],
         mode=mode, out_dtype=out_dtype, row_loads=_ops._ROW_LOADS_BY_CODE[int(row_loads)],
-        sample_order=sample_order, row_loads_device=row_loads_device)
+        sample_order=sample_order, row_loads_device=row_loads_device, bits=bits)
 
 
 def _grouped_group(tables, table_ptrs):
@@ -897,27 +907,37 @@ def cuembed_sparse_row_adam_mixed_group(group, ids, rows, *, exp_avg, exp_avg_sq
     torch.ops.cuembed_pyt.cuembed_sparse_row_adam_mixed_group(*head, _mu._widths_device(group), *tail)
 
 
-def quantize_rows(table):
-    """cuembed_amd.quantize_rows as the torch op cuembed_pyt::quantize_rows (traces under torch.compile)."""
-    return torch.ops.cuembed_pyt.quantize_rows(table)
+def _bits_op(name, bits):
+    """The torch op `name` of the fused 8-bit layout or its `_4bit` sibling."""
+    if bits not in (8, 4):
+        raise ValueError("bits must be 8 or 4, got %r" % (bits,))
+    return getattr(torch.ops.cuembed_pyt, name if bits == 8 else name + "_4bit")
 
 
-def dequantize_rows(qtable, ids=None, dtype=torch.float32):
-    """cuembed_amd.dequantize_rows as the torch op cuembed_pyt::dequantize_rows."""
-    return torch.ops.cuembed_pyt.dequantize_rows(qtable, ids, dtype)
+def quantize_rows(table, bits=8):
+    """cuembed_amd.quantize_rows as the torch op cuembed_pyt::quantize_rows (traces under torch.compile); bits=4:
+    cuembed_pyt::quantize_rows_4bit."""
+    return _bits_op("quantize_rows", bits)(table)
 
 
-def cuemb_embedding_quantized(qtable, idx, offsets=None, weights=None, mode="sum", out_dtype=torch.float16, hints="auto"):
+def dequantize_rows(qtable, ids=None, dtype=torch.float32, bits=8):
+    """cuembed_amd.dequantize_rows as the torch op cuembed_pyt::dequantize_rows (bits=4: dequantize_rows_4bit)."""
+    return _bits_op("dequantize_rows", bits)(qtable, ids, dtype)
+
+
+def cuemb_embedding_quantized(qtable, idx, offsets=None, weights=None, mode="sum", out_dtype=torch.float16, hints="auto",
+                              bits=8):
     """The lookup on a fused 8-bit row-wise table (torch's quantized::embedding_bag_byte_prepack layout) as the torch op
     cuembed_pyt::cuemb_embedding_quantized: CSR with `offsets` (batch + 1 entries), fixed hotness with idx [batch,
     hotness] and no offsets (then mode may be "concat").  Inference only: nothing here is differentiable.
-    hints="auto" applies cuembed_amd.policy's scheduling hints like cuemb_embedding; results never depend on them."""
+    hints="auto" applies cuembed_amd.policy's scheduling hints like cuemb_embedding; results never depend on them.
+    bits=4: a fused 4-bit row-wise table (quantized::embedding_bag_4bit_prepack), cuemb_embedding_quantized_4bit."""
+    op = _bits_op("cuemb_embedding_quantized", bits)
     order = decision = None
     if hints == "auto" and not torch.compiler.is_compiling():
         order = _policy.sample_order(offsets, idx.numel())
         decision = _policy.row_loads_device(qtable, idx)
-    return torch.ops.cuembed_pyt.cuemb_embedding_quantized(qtable, idx, offsets, weights, mode, out_dtype, -1, order,
-                                                           decision)
+    return op(qtable, idx, offsets, weights, mode, out_dtype, -1, order, decision)
 
 
 def _forward_only(tables, weights):
@@ -1642,28 +1662,39 @@ def _(tables, table_ptrs, exp_avg, exp_avg_ptrs, exp_avg_sq, exp_avg_sq_ptrs, wi
     return None
 
 
-@torch.library.register_fake("cuembed_pyt::quantize_rows")
-def _(table):
-    return torch.empty((table.shape[0], table.shape[1] + 8), device=table.device, dtype=torch.uint8)
+def _fake_quantize_rows(row_bytes):
+    def fake(table):
+        return torch.empty((table.shape[0], row_bytes(table.shape[1])), device=table.device, dtype=torch.uint8)
+    return fake
 
 
-@torch.library.register_fake("cuembed_pyt::dequantize_rows")
-def _(qtable, ids=None, dtype=torch.float32):
-    lead = (qtable.shape[0],) if ids is None else tuple(ids.shape)
-    return torch.empty(lead + (qtable.shape[1] - 8,), device=qtable.device, dtype=dtype)
+def _fake_dequantize_rows(width_of):
+    def fake(qtable, ids=None, dtype=torch.float32):
+        lead = (qtable.shape[0],) if ids is None else tuple(ids.shape)
+        return torch.empty(lead + (width_of(qtable.shape[1]),), device=qtable.device, dtype=dtype)
+    return fake
 
 
-@torch.library.register_fake("cuembed_pyt::cuemb_embedding_quantized")
-def _(qtable, indices, offsets=None, weights=None, mode="sum", out_dtype=torch.float16, row_loads=-1, sample_order=None,
-      row_loads_device=None):
-    width = qtable.shape[1] - 8
-    if offsets is not None:
-        shape = (offsets.shape[0] - 1, width)
-    elif mode == "concat":
-        shape = (indices.shape[0], indices.shape[1], width)
-    else:
-        shape = (indices.shape[0], width)
-    return torch.empty(shape, device=qtable.device, dtype=out_dtype)
+def _fake_embedding_quantized(width_of):
+    def fake(qtable, indices, offsets=None, weights=None, mode="sum", out_dtype=torch.float16, row_loads=-1,
+             sample_order=None, row_loads_device=None):
+        width = width_of(qtable.shape[1])
+        if offsets is not None:
+            shape = (offsets.shape[0] - 1, width)
+        elif mode == "concat":
+            shape = (indices.shape[0], indices.shape[1], width)
+        else:
+            shape = (indices.shape[0], width)
+        return torch.empty(shape, device=qtable.device, dtype=out_dtype)
+    return fake
+
+
+# (row bytes of W values, W of a row's bytes) of the fused 8-bit and 4-bit layouts
+for _suffix, _row_bytes, _width_of in (("", lambda w: w + 8, lambda b: b - 8),
+                                       ("_4bit", lambda w: w // 2 + 4, lambda b: (b - 4) * 2)):
+    torch.library.register_fake("cuembed_pyt::quantize_rows" + _suffix)(_fake_quantize_rows(_row_bytes))
+    torch.library.register_fake("cuembed_pyt::dequantize_rows" + _suffix)(_fake_dequantize_rows(_width_of))
+    torch.library.register_fake("cuembed_pyt::cuemb_embedding_quantized" + _suffix)(_fake_embedding_quantized(_width_of))
 
 
 def _grouped_fake_shape(tables, idx, offsets, width):

@@ -1,4 +1,4 @@
-"""8-bit row-wise quantized tables on the device (an extension: inference only).
+"""8-bit and 4-bit row-wise quantized tables on the device (an extension: inference only).
 
 The format is PyTorch's fused 8-bit row-wise layout -- what `torch.ops.quantized.embedding_bag_byte_prepack` makes on
 the CPU: a uint8 tensor [rows, W + 8]; bytes [0, W) of a row are its codes, [W, W + 4) its fp32 scale, [W + 4, W + 8)
@@ -10,6 +10,12 @@ here, and `quantize_rows` writes the very bytes torch's prepack would.
     embedding_forward_quantized(qtable, ...) embedding_forward on a fused table (sum / mean / concat)
     QuantizedEmbeddingBag                    a table + the scheduling hints cuemb_embedding(hints="auto") applies
 
+Every one of them takes `bits` (8, the default, or 4).  bits=4 is PyTorch's / FBGEMM's fused 4-bit row-wise layout -- what
+`torch.ops.quantized.embedding_bag_4bit_prepack` makes on the CPU: a uint8 tensor [rows, W / 2 + 4]; byte i of a row holds
+element 2i in its low nibble and element 2i + 1 in its high nibble, bytes [W / 2, W / 2 + 2) are its fp16 scale, the last
+two its fp16 bias; W is a multiple of 8 here.  A 4-bit table cannot be told from an 8-bit one by its shape: `bits` is
+always explicit.
+
 Every function validates its arguments and raises before any launch; the kernels run on torch's current stream
 (cuembed::QuantizeRows / DequantizeRows / EmbeddingForwardQuantized through the C ABI).  torch is used for device memory
 and streams only.
@@ -19,15 +25,60 @@ import ctypes
 import torch
 
 from . import _lib
-from .ops import _CSR_XOR_FIXED, _MODES, _ROW_LOADS, CONCAT, _check_alignment, _check_dev, _elem_code, _index_code, _ptr, _stream
+from .ops import _CSR_XOR_FIXED, _MODES, _ROW_LOADS, CONCAT, MAX_LANES_PER_ROW, _check_alignment, _check_dev, _elem_code, _index_code, _ptr, _stream
 
 TRAILER_BYTES = 8                                   # fp32 scale + fp32 bias
+TRAILER_BYTES_4BIT = 4                              # fp16 scale + fp16 bias
 _OUT = {torch.float32: 0, torch.float16: 1}
 
 
-def quantized_row_bytes(width):
+class _Format:
+    """What the functions below need to know of a fused layout: its row size, the widths it takes and the words of its
+    error messages."""
+
+    def __init__(self, bits, trailer, multiple, shape):
+        self.bits, self.trailer, self.multiple, self.shape = bits, trailer, multiple, shape
+
+    def row_bytes(self, width):
+        return int(width) * self.bits // 8 + self.trailer
+
+    def width_of(self, row_bytes):
+        return (int(row_bytes) - self.trailer) * 8 // self.bits
+
+    def check_width(self, width, what):
+        if width <= 0 or width % self.multiple != 0:
+            if self.bits == 8:
+                raise ValueError("row size must be a multiple of 4 bytes: " + what % width)
+            raise ValueError("a fused 4-bit row is whole dwords of codes (W % 8 == 0): " + what % width)
+
+
+def _check_lanes_4bit(name, data_ptr, width, forward):
+    """_check_alignment's part for a fused 4-bit table: the codes per lane the native dispatcher picks (the
+    dequantizer's 8; the forward's 32 / 16 / 8, Quantized4BitForwardCodesPerLane), or ValueError where it would abort."""
+    if data_ptr % 4 != 0:
+        raise ValueError("%s must be 4-byte aligned" % name)
+    codes = 8
+    if forward:
+        codes = 32 if (width % 32 == 0 and width // 32 <= 256) else 16 if width % 16 == 0 else 8
+    if width // codes > MAX_LANES_PER_ROW:
+        raise ValueError("%s: a row of %d 4-bit codes needs %d lanes of %d codes, more than %d"
+                         % (name, width, width // codes, codes, MAX_LANES_PER_ROW))
+    return codes
+
+
+_FORMATS = {8: _Format(8, TRAILER_BYTES, 4, "[rows, width + 8] (the fused 8-bit row-wise layout)"),
+            4: _Format(4, TRAILER_BYTES_4BIT, 8, "[rows, width/2 + 4] (the fused 4-bit row-wise layout)")}
+
+
+def _format(bits):
+    if bits not in _FORMATS:
+        raise ValueError("bits must be 8 or 4, got %r" % (bits,))
+    return _FORMATS[bits]
+
+
+def quantized_row_bytes(width, bits=8):
     """Bytes of one fused row of `width` values."""
-    return int(width) + TRAILER_BYTES
+    return _format(bits).row_bytes(width)
 
 
 def _no_grad(name, t):
@@ -35,17 +86,17 @@ def _no_grad(name, t):
         raise ValueError("%s requires grad: quantized tables are inference only (detach it)" % name)
 
 
-def _check_qtable(qtable):
+def _check_qtable(qtable, bits=8):
     """Validates a fused table (before the device check: the contract of the FORMAT first) and returns W."""
+    fmt = _format(bits)
     if not isinstance(qtable, torch.Tensor):
         raise TypeError("qtable must be a torch.Tensor")
     if qtable.dtype != torch.uint8 or qtable.dim() != 2:
-        raise TypeError("qtable must be a 2-D uint8 tensor [rows, width + 8] (the fused 8-bit row-wise layout)")
+        raise TypeError("qtable must be a 2-D uint8 tensor " + fmt.shape)
     if not qtable.is_contiguous():
         raise ValueError("qtable must be contiguous")
-    width = qtable.shape[1] - TRAILER_BYTES
-    if width <= 0 or width % 4 != 0:
-        raise ValueError("row size must be a multiple of 4 bytes: the fused rows hold %d codes" % width)
+    width = fmt.width_of(qtable.shape[1])
+    fmt.check_width(width, "the fused rows hold %d codes")
     return width
 
 
@@ -55,10 +106,15 @@ def _out_code(name, dtype):
     return _OUT[dtype]
 
 
-def quantize_rows(table, out=None):
+def quantize_rows(table, out=None, bits=8):
     """fp32 / fp16 / bf16 [rows, W] on the device -> uint8 [rows, W + 8], the fused 8-bit row-wise table.  Per row:
     scale = (max - min) / 255, bias = min, code = rint((x - min) * (255 / (max - min + 1e-8))), every step one fp32
-    operation -- bit-identical to torch.ops.quantized.embedding_bag_byte_prepack on the CPU.  One launch."""
+    operation -- bit-identical to torch.ops.quantized.embedding_bag_byte_prepack on the CPU.  One launch.
+
+    bits=4: -> uint8 [rows, W / 2 + 4], the fused 4-bit row-wise table (W % 8 == 0).  Per row: bias = half(min), scale =
+    half((max - bias) / 15) (1 for a constant row), code = clamp(rint((x - bias) * (1 / scale)), 0, 15), every step one
+    fp32 operation -- the bytes torch.ops.quantized.embedding_bag_4bit_prepack writes on the CPU."""
+    fmt = _format(bits)
     if not isinstance(table, torch.Tensor):
         raise TypeError("table must be a torch.Tensor")
     et = _elem_code("table", table)
@@ -66,30 +122,31 @@ def quantize_rows(table, out=None):
         raise ValueError("table must be [rows, width]")
     _no_grad("table", table)
     rows, width = table.shape
-    if width <= 0 or width % 4 != 0:
-        raise ValueError("row size must be a multiple of 4 bytes: width %d is not a multiple of 4" % width)
+    fmt.check_width(width, "width %%d is not a multiple of %d" % fmt.multiple)
     _check_dev("table", table)
     if table.data_ptr() % 16 != 0:
         raise ValueError("table must be 16-byte aligned")
     if out is None:
-        out = torch.empty((rows, width + TRAILER_BYTES), dtype=torch.uint8, device=table.device)
+        out = torch.empty((rows, fmt.row_bytes(width)), dtype=torch.uint8, device=table.device)
     else:
         _check_dev("out", out, table.device)
-        if out.dtype != torch.uint8 or tuple(out.shape) != (rows, width + TRAILER_BYTES) or out.data_ptr() % 4 != 0:
-            raise ValueError("out must be a 4-byte aligned uint8 tensor [rows, width + 8]")
+        if out.dtype != torch.uint8 or tuple(out.shape) != (rows, fmt.row_bytes(width)) or out.data_ptr() % 4 != 0:
+            raise ValueError("out must be a 4-byte aligned uint8 tensor " + fmt.shape.split(" (")[0])
     # (the quantizer's lane groups loop over a row: no limit on its lanes)
-    _check_alignment("out", out.data_ptr(), 1, width, codes=True, max_lanes=None)
+    if bits == 8:
+        _check_alignment("out", out.data_ptr(), 1, width, codes=True, max_lanes=None)
     if rows > 0:
         with torch.cuda.device(table.device):
-            _lib.lib().cuembed_quantize_rows(_ptr(table), et, width, rows, _ptr(out), _stream(table))
+            quantize = _lib.lib().cuembed_quantize_rows if bits == 8 else _lib.lib().cuembed_quantize_rows_4bit
+            quantize(_ptr(table), et, width, rows, _ptr(out), _stream(table))
     return out
 
 
-def dequantize_rows(qtable, ids=None, dtype=torch.float32, out=None):
+def dequantize_rows(qtable, ids=None, dtype=torch.float32, out=None, bits=8):
     """The values of a fused table as `dtype` (float32 or float16): all rows ([rows, W]) or, with `ids` (int32 / int64,
     any shape), the rows they name ([*ids.shape, W]).  float(code) * scale + bias in two rounded fp32 operations, then
-    one rounding to `dtype`."""
-    width = _check_qtable(qtable)
+    one rounding to `dtype` (bits=4: scale and bias widened exactly from fp16)."""
+    width = _check_qtable(qtable, bits)
     oc = _out_code("dtype", dtype)
     _no_grad("qtable", qtable)
     it = 0
@@ -110,21 +167,30 @@ def dequantize_rows(qtable, ids=None, dtype=torch.float32, out=None):
         _check_dev("out", out, qtable.device)
         if out.dtype != dtype or out.numel() != n * width or out.data_ptr() % 16 != 0:
             raise ValueError("out has the wrong dtype, size or alignment (16 bytes)")
-    _check_alignment("qtable", qtable.data_ptr(), 1, width, codes=True)
+    if bits == 8:
+        _check_alignment("qtable", qtable.data_ptr(), 1, width, codes=True)
+    else:
+        _check_lanes_4bit("qtable", qtable.data_ptr(), width, forward=False)
     if n > 0:
         with torch.cuda.device(qtable.device):
-            _lib.lib().cuembed_dequantize_rows(_ptr(qtable), width, _ptr(ids), it, n, _ptr(out), oc, _stream(qtable))
+            dequantize = _lib.lib().cuembed_dequantize_rows if bits == 8 else _lib.lib().cuembed_dequantize_rows_4bit
+            dequantize(_ptr(qtable), width, _ptr(ids), it, n, _ptr(out), oc, _stream(qtable))
     return out
 
 
 def quantized_forward_launch_shape(index_dtype, out_dtype, embed_width, batch_size, num_hots, is_csr=False,
-                                   is_weighted=False, compute_units=256, xcds=8):
+                                   is_weighted=False, compute_units=256, xcds=8, bits=8):
     """Launch shape of the quantized sum / mean forward (pure host arithmetic when compute_units > 0 describes the
     device: e.g. compute_units=32, xcds=1 for a CPX partition; 0 = ask the current device)."""
+    fmt = _format(bits)
+    shape_fn = _lib.lib().cuembed_quantized_forward_launch_shape
+    if bits == 4:                   # (what the native plan would abort on)
+        fmt.check_width(int(embed_width), "width %d is not a multiple of 8")
+        _check_lanes_4bit("qtable", 0, int(embed_width), forward=True)
+        shape_fn = _lib.lib().cuembed_quantized_4bit_forward_launch_shape
     out = (ctypes.c_int * 6)()
-    _lib.lib().cuembed_quantized_forward_launch_shape(_index_code_of(index_dtype), _out_code("out_dtype", out_dtype),
-                                                      int(embed_width), int(batch_size), int(num_hots), int(is_csr),
-                                                      int(is_weighted), int(compute_units), int(xcds), out)
+    shape_fn(_index_code_of(index_dtype), _out_code("out_dtype", out_dtype), int(embed_width), int(batch_size),
+             int(num_hots), int(is_csr), int(is_weighted), int(compute_units), int(xcds), out)
     return dict(codes_per_lane=out[0], lanes_per_row=out[1], samples_per_block=out[2], grid=out[3], lds_bytes=out[4],
                 staged=out[5] == 1)
 
@@ -137,8 +203,8 @@ def _index_code_of(dtype):
 
 def embedding_forward_quantized(qtable, indices, offsets=None, weights=None, batch_size=None, num_hots=0, mode="sum",
                                 out_dtype=torch.float16, out=None, row_loads=None, sample_order=None,
-                                row_loads_device=None):
-    """out[s] = combine_j weights[s,j] * value(qtable[indices[s,j]]) on a fused 8-bit table.
+                                row_loads_device=None, bits=8):
+    """out[s] = combine_j weights[s,j] * value(qtable[indices[s,j]]) on a fused 8-bit (bits=4: 4-bit) table.
 
     Same layouts and modes as embedding_forward: fixed hotness (offsets=None, num_hots>0) or CSR (offsets[batch+1],
     num_hots=0); mode "sum" | "mean" | "concat" (concat: fixed hotness, unweighted -- dequantize_rows on the batch's
@@ -151,7 +217,7 @@ def embedding_forward_quantized(qtable, indices, offsets=None, weights=None, bat
     if row_loads not in _ROW_LOADS:
         raise ValueError("row_loads: None, 'default' or 'streaming'")
     m = _MODES[mode]
-    width = _check_qtable(qtable)
+    width = _check_qtable(qtable, bits)
     oc = _out_code("out_dtype", out_dtype)
     if not isinstance(indices, torch.Tensor):
         raise TypeError("indices must be a torch.Tensor")
@@ -211,23 +277,28 @@ def embedding_forward_quantized(qtable, indices, offsets=None, weights=None, bat
             raise ValueError("out has the wrong dtype or size")
         if out.data_ptr() % 16 != 0:
             raise ValueError("out must be 16-byte aligned")
-    _check_alignment("qtable", qtable.data_ptr(), 1, width, codes=True)
+    if bits == 8:
+        _check_alignment("qtable", qtable.data_ptr(), 1, width, codes=True)
+    else:
+        _check_lanes_4bit("qtable", qtable.data_ptr(), width, forward=m != CONCAT)
     if batch_size > 0:
         with torch.cuda.device(dev):   # the launch must happen on the tensors' device
-            _lib.lib().cuembed_embedding_forward_quantized(
+            forward = (_lib.lib().cuembed_embedding_forward_quantized if bits == 8
+                       else _lib.lib().cuembed_embedding_forward_quantized_4bit)
+            forward(
                 _ptr(qtable), width, _ptr(indices), it, _ptr(offsets), ot, _ptr(weights), batch_size, num_hots, m,
                 _ptr(out), oc, _ROW_LOADS[row_loads], _ptr(sample_order), _ptr(row_loads_device), _stream(qtable))
     return out
 
 
 class QuantizedEmbeddingBag:
-    """A fused 8-bit table with the call shape of nn.EmbeddingBag / cuemb_embedding: bag(idx, offsets, weights).
+    """A fused 8-bit (bits=4: 4-bit) table with the call shape of nn.EmbeddingBag / cuemb_embedding: bag(idx, offsets, weights).
     `offsets` holds batch + 1 entries.  hints="auto" applies the scheduling hints cuemb_embedding(hints="auto")
     applies -- the row-load decision and the bag order, both taken on the device by cuembed_amd.policy; results never
     depend on them."""
 
-    def __init__(self, qtable, mode="sum", out_dtype=torch.float16, hints="auto"):
-        _check_qtable(qtable)
+    def __init__(self, qtable, mode="sum", out_dtype=torch.float16, hints="auto", bits=8):
+        _check_qtable(qtable, bits)
         if mode not in ("sum", "mean"):
             raise ValueError("mode must be 'sum' or 'mean'")
         _out_code("out_dtype", out_dtype)
@@ -237,11 +308,12 @@ class QuantizedEmbeddingBag:
         self.mode = mode
         self.out_dtype = out_dtype
         self.hints = hints
+        self.bits = bits
 
     @classmethod
-    def from_float(cls, table, mode="sum", out_dtype=torch.float16, hints="auto"):
+    def from_float(cls, table, mode="sum", out_dtype=torch.float16, hints="auto", bits=8):
         """Quantizes an fp32 / fp16 / bf16 table on the device."""
-        return cls(quantize_rows(table.detach()), mode=mode, out_dtype=out_dtype, hints=hints)
+        return cls(quantize_rows(table.detach(), bits=bits), mode=mode, out_dtype=out_dtype, hints=hints, bits=bits)
 
     @property
     def num_embeddings(self):
@@ -249,10 +321,10 @@ class QuantizedEmbeddingBag:
 
     @property
     def embedding_dim(self):
-        return self.qtable.shape[1] - TRAILER_BYTES
+        return _format(self.bits).width_of(self.qtable.shape[1])
 
     def dequantize(self, ids=None, dtype=torch.float32):
-        return dequantize_rows(self.qtable, ids, dtype)
+        return dequantize_rows(self.qtable, ids, dtype, bits=self.bits)
 
     def __call__(self, idx, offsets, weights=None):
         order = decision = None
@@ -261,4 +333,4 @@ class QuantizedEmbeddingBag:
             order = policy.sample_order(offsets, idx.numel())
             decision = policy.row_loads_device(self.qtable, idx)
         return embedding_forward_quantized(self.qtable, idx, offsets, weights, mode=self.mode, out_dtype=self.out_dtype,
-                                           sample_order=order, row_loads_device=decision)
+                                           sample_order=order, row_loads_device=decision, bits=self.bits)

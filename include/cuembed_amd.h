@@ -750,6 +750,32 @@ void cuembed_embedding_forward_quantized(const void* qtable, int embed_width, co
  * indices are staged in LDS.  compute_units > 0 describes the device (with xcds); <= 0: the current device. */
 void cuembed_quantized_forward_launch_shape(int index_type, int out_type, int embed_width, int batch_size, int num_hots,
                                             int is_csr, int is_weighted, int compute_units, int xcds, int* out);
+/* ---- fused 4-bit row-wise quantized tables (extension; inference only) ---------------------
+ * The format is PyTorch's / FBGEMM's fused 4-bit row-wise layout (quantized::embedding_bag_4bit_prepack): a row of
+ * embed_width values is embed_width / 2 + 4 bytes -- byte i holds element 2i in its low nibble and element 2i + 1 in
+ * its high nibble, then the row's fp16 scale and its fp16 bias, little endian -- and a value is code * scale + bias.
+ * embed_width must be a multiple of 8 (a row pitch of whole dwords); tables are contiguous
+ * [num_categories, embed_width / 2 + 4] bytes, 4-byte aligned; outputs are 16-byte aligned.  The four functions mirror
+ * the 8-bit four above, parameter for parameter. */
+/* cuembed::QuantizeRows4Bit: bias = half(min), scale = half((max - bias) / 15) (1 for a constant row), code =
+ * clamp(rint((x - bias) * (1 / scale)), 0, 15), every step one fp32 operation: the bytes torch's CPU prepack writes. */
+void cuembed_quantize_rows_4bit(const void* in, int elem_type, int embed_width, int64_t rows, void* out,
+                                cuembed_stream_t stream);
+/* cuembed::DequantizeRows4Bit: float(code) * scale + bias in two rounded fp32 operations, then one rounding to out_type.
+ * embed_width <= 8192 (1,024 lanes of 8 codes). */
+void cuembed_dequantize_rows_4bit(const void* qtable, int embed_width, const void* ids, int index_type, int64_t n,
+                                  void* out, int out_type, cuembed_stream_t stream);
+/* cuembed::EmbeddingForwardQuantized4Bit: cuembed_embedding_forward_quantized on a fused 4-bit table. */
+void cuembed_embedding_forward_quantized_4bit(const void* qtable, int embed_width, const void* indices, int index_type,
+                                              const void* offsets, int offset_type, const void* weights, int batch_size,
+                                              int num_hots, int mode, void* ret, int out_type, int row_load_policy,
+                                              const int32_t* sample_order, const uint32_t* row_loads_device,
+                                              cuembed_stream_t stream);
+/* Launch shape of the 4-bit sum / mean forward (no launch); out[0..5] as cuembed_quantized_forward_launch_shape: codes
+ * per lane are 32 (embed_width % 32 == 0), 16 (% 16) or 8. */
+void cuembed_quantized_4bit_forward_launch_shape(int index_type, int out_type, int embed_width, int batch_size,
+                                                 int num_hots, int is_csr, int is_weighted, int compute_units, int xcds,
+                                                 int* out);
 /* ---- a GROUP of tables pooled in one launch (extension; forward only, sum / mean only) -----
  * num_tables >= 1 tables on one device, of one element type (or all fused 8-bit) and one embed_width; their row counts
  * may differ.  Bag g = t * batch_per_table + b belongs to table t and sample b (table-major).  CSR: one indices[nnz],
