@@ -216,6 +216,11 @@ def _declare(L):
     L.cuembed_quantized_mixed_group_launch_shape.restype = None
     L.cuembed_quantized_mixed_group_launch_shape.argtypes = [_VP, _I, _I, _I, _I, _I, _I, ctypes.c_size_t,
                                                              ctypes.POINTER(_I)]
+    for name in ("cuembed_embedding_forward_quantized_mixed_group", "cuembed_quantized_mixed_group_codes_per_lane",
+                 "cuembed_fill_quantized_mixed_group_descriptor", "cuembed_quantized_mixed_group_launch_shape"):
+        fn4 = getattr(L, name + "_4bit")                                   # (parameter for parameter the 8-bit ones)
+        fn4.restype = getattr(L, name).restype
+        fn4.argtypes = list(getattr(L, name).argtypes)
     L.cuembed_embedding_backward_mixed_group.restype = None
     L.cuembed_embedding_backward_mixed_group.argtypes = [_VP, _I, _VP, _VP, _I, _I, _L, _VP, _VP, _VP, _I, _VP, _VP, _VP,
                                                          _L, _VP, _VP]

@@ -27,7 +27,8 @@ UNITS = ["c_api_forward.hip", "c_api_backward.hip", "c_api_transforms.hip", "c_a
          "c_api_grouped_backward.hip", "c_api_row_cache.hip", "c_api_optimizer_grouped.hip",
          "c_api_optimizer_grouped_stochastic.hip", "c_api_index_check.hip", "c_api_mixed_group.hip",
          "c_api_mixed_group_backward.hip", "c_api_optimizer_mixed_group.hip", "c_api_quantized_mixed_group.hip",
-         "c_api_quantized_fourbit.hip"]     # (letters only: the unit lists are compared by a pattern without digits)
+         "c_api_quantized_fourbit.hip",     # (letters only: the unit lists are compared by a pattern without digits)
+         "c_api_quantized_mixed_group_fourbit.hip"]
 ARCH = "gfx950"
 
 HIPCC_FLAGS = [

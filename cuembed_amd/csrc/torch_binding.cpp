@@ -1382,6 +1382,11 @@ struct Fused {
   static constexpr auto kDequantize = kBits == 8 ? &::cuembed_dequantize_rows : &::cuembed_dequantize_rows_4bit;
   static constexpr auto kForward =
       kBits == 8 ? &::cuembed_embedding_forward_quantized : &::cuembed_embedding_forward_quantized_4bit;
+  // ... and the mixed-width group of such tables
+  static constexpr auto kMixedGroupForward = kBits == 8 ? &::cuembed_embedding_forward_quantized_mixed_group
+                                                        : &::cuembed_embedding_forward_quantized_mixed_group_4bit;
+  static constexpr auto kMixedGroupCodesPerLane = kBits == 8 ? &::cuembed_quantized_mixed_group_codes_per_lane
+                                                             : &::cuembed_quantized_mixed_group_codes_per_lane_4bit;
 };
 
 template <int kBits>
@@ -1684,7 +1689,9 @@ at::Tensor cuemb_embedding_mixed_group_op(const at::TensorList tables, const at:
 // uint8 [rows_t, W_t + 8]; `descriptor` is the caller's int32 device tensor of (num_tables + 1) * 4 words, filled on the
 // host by cuembed_fill_quantized_mixed_group_descriptor for this batch and `codes_per_lane` and copied to the device once
 // (cuembed_amd.QuantizedMixedTableGroup.descriptor); codes_per_lane is checked here against the pointers, the words
-// cannot be.  Returns [batch, sum of the widths] of out_dtype; weights have that dtype.
+// cannot be.  Returns [batch, sum of the widths] of out_dtype; weights have that dtype.  kBits = 4: fused 4-bit tables,
+// uint8 [rows_t, W_t / 2 + 4], the descriptor filled by cuembed_fill_quantized_mixed_group_descriptor_4bit.
+template <int kBits>
 at::Tensor cuemb_embedding_quantized_mixed_group_op(const at::TensorList qtables, const at::Tensor& table_ptrs,
                                                     const at::Tensor& descriptor, const int64_t codes_per_lane,
                                                     const at::Tensor& indices, const c10::optional<at::Tensor>& offsets,
@@ -1697,7 +1704,7 @@ at::Tensor cuemb_embedding_quantized_mixed_group_op(const at::TensorList qtables
   std::vector<int> widths;
   int64_t dim = 0;
   for (const at::Tensor& t : qtables) {
-    const int64_t width = QuantizedWidth(t);   // (uint8, 2-D, contiguous, W % 4 == 0, 4-byte aligned, on the GPU)
+    const int64_t width = Fused<kBits>::Width(t);   // (uint8, 2-D, contiguous, W % 4 or 8 == 0, 4-byte aligned, on the GPU)
     widths.push_back(static_cast<int>(width));
     dim += width;
   }
@@ -1710,13 +1717,13 @@ at::Tensor cuemb_embedding_quantized_mixed_group_op(const at::TensorList qtables
               "cuembed_pyt: descriptor must be the contiguous int32 tensor of (num_tables + 1) * 4 words on the tables' "
               "device");
   CheckGroupedBatch(&c, num_tables, indices, offsets, weights, out_dtype, row_loads, c10::nullopt);
-  const int codes = ::cuembed_quantized_mixed_group_codes_per_lane(c.host_ptrs.data(), widths.data(),
-                                                                   static_cast<int>(num_tables));
+  const int codes = Fused<kBits>::kMixedGroupCodesPerLane(c.host_ptrs.data(), widths.data(),
+                                                          static_cast<int>(num_tables));
   TORCH_CHECK(codes_per_lane == codes, "cuembed_pyt: the descriptor was filled for lanes of ", codes_per_lane,
               " codes, these tables take ", codes);
   at::Tensor out = at::empty({c.batch, dim}, qtables[0].options().dtype(out_dtype));
   if (c.batch > 0)
-    ::cuembed_embedding_forward_quantized_mixed_group(
+    Fused<kBits>::kMixedGroupForward(
         c.host_ptrs.data(), static_cast<const void* const*>(table_ptrs.data_ptr()), widths.data(), descriptor.data_ptr(),
         static_cast<int>(num_tables), Ptr(c.i), c.idx, Ptr(c.o), c.off, Ptr(c.w), static_cast<int>(c.batch),
         static_cast<int>(c.hot), m, MutPtr(out), out_code, static_cast<int>(row_loads), CurrentStream(out));
@@ -2142,6 +2149,11 @@ TORCH_LIBRARY(cuembed_pyt, m) {
   m.def(
       "cuemb_embedding_quantized_mixed_group(Tensor[] qtables, Tensor table_ptrs, Tensor descriptor, int codes_per_lane, "
       "Tensor idx, Tensor? offsets, Tensor? weights, str mode, ScalarType out_dtype, int row_loads=-1) -> Tensor");
+  // ... of fused 4-bit tables
+  m.def(
+      "cuemb_embedding_quantized_mixed_group_4bit(Tensor[] qtables, Tensor table_ptrs, Tensor descriptor, int "
+      "codes_per_lane, Tensor idx, Tensor? offsets, Tensor? weights, str mode, ScalarType out_dtype, int row_loads=-1) -> "
+      "Tensor");
   // the backward of a group: the keys in front of the single-table pipeline, the table boundaries behind it
   m.def(
       "cuembed_grouped_backward_keys(Tensor idx, Tensor? offsets, Tensor row_base, int num_tables, int batch, int "
@@ -2209,7 +2221,8 @@ TORCH_LIBRARY_IMPL(cuembed_pyt, CUDA, m) {  // HIP tensors use the CUDA dispatch
   m.impl("cuemb_embedding_grouped", cuemb_embedding_grouped_op);
   m.impl("cuemb_embedding_quantized_grouped", cuemb_embedding_quantized_grouped_op);
   m.impl("cuemb_embedding_mixed_group", cuemb_embedding_mixed_group_op);
-  m.impl("cuemb_embedding_quantized_mixed_group", cuemb_embedding_quantized_mixed_group_op);
+  m.impl("cuemb_embedding_quantized_mixed_group", cuemb_embedding_quantized_mixed_group_op<8>);
+  m.impl("cuemb_embedding_quantized_mixed_group_4bit", cuemb_embedding_quantized_mixed_group_op<4>);
   m.impl("cuembed_grouped_backward_keys", cuembed_grouped_backward_keys_op);
   m.impl("cuembed_grouped_table_cuts", cuembed_grouped_table_cuts_op);
   m.impl("cuembed_grouped_weight_grad", cuembed_grouped_weight_grad_op);

@@ -112,6 +112,9 @@ def _define_python_ops():
     _lib.define("cuemb_embedding_quantized_mixed_group(Tensor[] qtables, Tensor table_ptrs, Tensor descriptor,"
                 " int codes_per_lane, Tensor idx, Tensor? offsets, Tensor? weights, str mode, ScalarType out_dtype,"
                 " int row_loads=-1) -> Tensor")
+    _lib.define("cuemb_embedding_quantized_mixed_group_4bit(Tensor[] qtables, Tensor table_ptrs, Tensor descriptor,"
+                " int codes_per_lane, Tensor idx, Tensor? offsets, Tensor? weights, str mode, ScalarType out_dtype,"
+                " int row_loads=-1) -> Tensor")
     _lib.define("cuembed_grouped_backward_keys(Tensor idx, Tensor? offsets, Tensor row_base, int num_tables, int batch,"
                 " int num_hots, bool narrow) -> (Tensor, Tensor)")
     _lib.define("cuembed_grouped_table_cuts(Tensor ids, Tensor count_word, Tensor row_base, bool last_id=False) -> Tensor")
@@ -137,6 +140,8 @@ def _define_python_ops():
     _lib.impl("cuemb_embedding_quantized_grouped", _embedding_quantized_grouped_impl, "CUDA")
     _lib.impl("cuemb_embedding_mixed_group", _embedding_mixed_group_impl, "CUDA")
     _lib.impl("cuemb_embedding_quantized_mixed_group", _embedding_quantized_mixed_group_impl, "CUDA")
+    _lib.impl("cuemb_embedding_quantized_mixed_group_4bit",
+              lambda *args: _embedding_quantized_mixed_group_impl(*args, bits=4), "CUDA")
     _lib.impl("quantize_rows", _quantize_rows_impl, "CUDA")
     _lib.impl("dequantize_rows", _dequantize_rows_impl, "CUDA")
     _lib.impl("cuemb_embedding_quantized", _embedding_quantized_impl, "CUDA")
@@ -197,7 +202,8 @@ def _define_python_ops():
 #   cuemb_embedding_quantized_grouped         [batch, tables, width] (forward only: no autograd formula)
 #   cuemb_embedding_mixed_group               a group of plain tables of DIFFERENT widths pooled in ONE launch into
 #                                             [batch, sum of widths] (forward only: no autograd formula)
-#   cuemb_embedding_quantized_mixed_group     the same on fused 8-bit tables of different widths (inference only)
+#   cuemb_embedding_quantized_mixed_group,    the same on fused 8-bit tables of different widths, and (_4bit) on fused
+#   cuemb_embedding_quantized_mixed_group_4bit  4-bit tables (inference only)
 #   cuembed_grouped_backward_keys,            the backward of a group through ONE sort and ONE scatter-add: global row
 #   cuembed_grouped_table_cuts                keys + output-row sample ids in front of the single-table pipeline, the
 #                                             table boundaries of the compressed gradient behind it
@@ -507,11 +513,12 @@ def _embedding_mixed_group_impl(tables, table_ptrs, descriptor, lane_bytes, idx,
 
 
 def _embedding_quantized_mixed_group_impl(qtables, table_ptrs, descriptor, codes_per_lane, idx, offsets, weights, mode,
-                                          out_dtype, row_loads=-1):
+                                          out_dtype, row_loads=-1, bits=8):
     from . import quantized_mixed_group as _q
     if offsets is None:
         _require(idx.dim() == 3, "without offsets, idx must be [num_tables, batch, hotness]")
-    group = _q.QuantizedMixedTableGroup(qtables, table_ptrs=table_ptrs)   # the caller's device pointers: nothing is copied
+    # (the caller's device pointers: nothing is copied)
+    group = _q.QuantizedMixedTableGroup(qtables, table_ptrs=table_ptrs, bits=bits)
     batch = (offsets.numel() - 1) // len(qtables) if offsets is not None else idx.shape[1]
     _require(descriptor.is_cuda and descriptor.dtype == torch.int32 and descriptor.is_contiguous() and
              descriptor.numel() == (len(qtables) + 1) * 4,
@@ -976,11 +983,12 @@ def cuemb_embedding_quantized_mixed_group(group, idx, offsets=None, weights=None
     cuembed_pyt::cuemb_embedding_quantized_mixed_group: `group` is a cuembed_amd.QuantizedMixedTableGroup (fused 8-bit
     tables of different widths; the device tensors of their pointers and of the per-batch-size descriptor are built
     once); CSR with `offsets` (num_tables * batch + 1 entries) or fixed hotness with idx [num_tables, batch, hotness].
-    Returns [batch, group.embedding_dim] of out_dtype.  Inference only."""
+    Returns [batch, group.embedding_dim] of out_dtype.  Inference only.  A group of fused 4-bit tables (group.bits == 4)
+    goes to cuembed_pyt::cuemb_embedding_quantized_mixed_group_4bit."""
     _forward_only(group.tables, weights)
     batch, _ = _grouped_batch(group.num_tables, idx, offsets)
     codes = group.codes_per_lane()
-    return torch.ops.cuembed_pyt.cuemb_embedding_quantized_mixed_group(
+    return _bits_op("cuemb_embedding_quantized_mixed_group", group.bits)(
         list(group.tables), group.table_ptrs, group.descriptor(batch, codes), codes, idx, offsets, weights, mode, out_dtype,
         _ops._ROW_LOADS[row_loads])
 
@@ -1715,11 +1723,17 @@ def _(tables, table_ptrs, descriptor, lane_bytes, idx, offsets=None, weights=Non
     return torch.empty((batch, sum(t.shape[1] for t in tables)), device=tables[0].device, dtype=tables[0].dtype)
 
 
-@torch.library.register_fake("cuembed_pyt::cuemb_embedding_quantized_mixed_group")
-def _(qtables, table_ptrs, descriptor, codes_per_lane, idx, offsets=None, weights=None, mode="sum",
-      out_dtype=torch.float16, row_loads=-1):
-    batch = (offsets.shape[0] - 1) // len(qtables) if offsets is not None else idx.shape[1]
-    return torch.empty((batch, sum(t.shape[1] - 8 for t in qtables)), device=qtables[0].device, dtype=out_dtype)
+def _fake_embedding_quantized_mixed_group(width_of):
+    def fake(qtables, table_ptrs, descriptor, codes_per_lane, idx, offsets=None, weights=None, mode="sum",
+             out_dtype=torch.float16, row_loads=-1):
+        batch = (offsets.shape[0] - 1) // len(qtables) if offsets is not None else idx.shape[1]
+        return torch.empty((batch, sum(width_of(t.shape[1]) for t in qtables)), device=qtables[0].device, dtype=out_dtype)
+    return fake
+
+
+for _suffix, _width_of in (("", lambda b: b - 8), ("_4bit", lambda b: (b - 4) * 2)):
+    torch.library.register_fake("cuembed_pyt::cuemb_embedding_quantized_mixed_group" + _suffix)(
+        _fake_embedding_quantized_mixed_group(_width_of))
 
 
 @torch.library.register_fake("cuembed_pyt::cuemb_embedding_quantized_grouped")

@@ -873,6 +873,29 @@ int cuembed_fill_quantized_mixed_group_descriptor(const int* widths_host, int nu
 void cuembed_quantized_mixed_group_launch_shape(const int* widths_host, int num_tables, int out_type, int index_type,
                                                 int batch_per_table, int num_hots, int is_weighted, size_t pointer_bits,
                                                 int* out);
+/* ---- a group of fused 4-bit tables of DIFFERENT widths pooled in one launch (extension; sum / mean only, inference
+ * only; cuembed::EmbeddingForwardQuantized4BitMixedGroup, quantized_4bit_mixed_group_lookup.hpp) -----
+ * The four above on the rows of cuembed_embedding_forward_quantized_4bit, parameter for parameter: table t is [rows_t,
+ * widths_host[t] / 2 + 4] bytes (two codes a byte, then fp16 scale and fp16 bias), widths_host[t] a multiple of 8, every
+ * base 4-byte aligned -- the results of num_tables calls of cuembed_embedding_forward_quantized_4bit concatenated on
+ * dimension 1, with their bits.  codes_per_lane is 32, 16 or 8: the largest that divides every width; a lane's codes are
+ * one load that needs 4-byte alignment only, so neither the bases nor ret narrow it, and a row of more than 256 lanes
+ * (8,224 values at 32 codes per lane) is pooled in several passes.  The descriptor has
+ * cuembed_mixed_group_descriptor_bytes(num_tables) bytes and the words of the 8-bit one. */
+void cuembed_embedding_forward_quantized_mixed_group_4bit(const void* const* tables_host,
+                                                          const void* const* tables_device, const int* widths_host,
+                                                          const void* descriptor_device, int num_tables,
+                                                          const void* indices, int index_type, const void* offsets,
+                                                          int offset_type, const void* weights, int batch_per_table,
+                                                          int num_hots, int mode, void* ret, int out_type,
+                                                          int row_load_policy, cuembed_stream_t stream);
+int cuembed_quantized_mixed_group_codes_per_lane_4bit(const void* const* tables_host, const int* widths_host,
+                                                      int num_tables);
+int cuembed_fill_quantized_mixed_group_descriptor_4bit(const int* widths_host, int num_tables, int codes_per_lane,
+                                                       int batch_per_table, int block_threads, void* host_blob);
+void cuembed_quantized_mixed_group_launch_shape_4bit(const int* widths_host, int num_tables, int out_type, int index_type,
+                                                     int batch_per_table, int num_hots, int is_weighted,
+                                                     size_t pointer_bits, int* out);
 /* ---- the backward of a group (extension): one sort and one scatter-add for all its tables -----
  * The group above is trained through the single-table pipeline, fed the right keys.  row_base[num_tables + 1] is the
  * exclusive prefix sum of the tables' row counts: int64, DEVICE memory, built once by the caller; row_base[num_tables]
